@@ -8,13 +8,19 @@ embedding -> 32 x (fused RMSNorm+qkv W4A16 GEMV, RoPE + KV scatter, GQA decode a
 o_proj GEMV + residual, fused RMSNorm + gate|up GEMV + silu*mul, down GEMV + residual) ->
 fused final norm + fp16 lm_head GEMV -> argmax -> position / KV bookkeeping, captured in one hipGraph.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (contract fields + the step's configuration).
+--dump-outputs DIR: after the timed steps, the last step's outputs (logits, next tokens) as DIR/<name>.npy.
+--full: everything else the bench measures and checks, around the same timed region: the oracle checks of the bench weights and
+the timed step's logits (exit 3 when those miss the 1e-3 bar), the TTFT leg, the roofline leg, batch 8 / 32 and the INT8 route,
+config 5's micro-benchmarks, the boundary path and the CPU baseline (--no-ttft / --no-extras / --no-cpu-baseline leave legs out).
 
 N > 1 (launched with torch.distributed.run, one rank per GPU): the decode path shards as independent
 TP=1 replicas (one model + its own requests per GPU, no data-path collective), i.e. weak scaling;
 `value` is the whole-job aggregate tokens/s.  Rank 0 prints ONE JSON line with, besides the contract
-fields, `roofline` (the W4A16 GEMV kernel: algorithmic bytes / HIP-event time, vs 8 TB/s HBM) and
-`cpu_baseline` (the CPU oracle timed on a bounded sample on this box's host cores).
+fields and under --full, `roofline` (the W4A16 GEMV kernel: algorithmic bytes / HIP-event time, vs 8 TB/s HBM) and
+`cpu_baseline` (the CPU oracle timed on a bounded sample on the host cores).
 """
 import argparse
 import json
@@ -303,7 +309,7 @@ def config5_leg(timeout_s=180):
 
 def boundary_leg(timeout_s=240):
     """VERDICT r04 item 5: the decode step as the drop-in BOUNDARY offers it -- the reference's own model::LLaMA (compiled unmodified,
-    zhilight_amd/_ref) running LLaMA::encode + get_logits on hostcpp/nn_amd.cpp over the C ABI, one launch per reference op, same
+    oracle/_ref) running LLaMA::encode + get_logits on hostcpp/nn_amd.cpp over the C ABI, one launch per reference op, same
     synthetic checkpoint, 32 layers, batch 1 -- timed by tools/bench_boundary.py in a CHILD process under the switches a deployment
     sets (CPM_FUSE_QKV=1, CPM_FUSE_FF_IN=1, ROPE_CACHE=1: the reference reads them itself), eager and under hipGraph replay, next to
     the Python driver's fused step on the same weights in the same process.  Whatever happens there costs this field only."""
@@ -434,6 +440,24 @@ def check_logits_against_oracle(model, ctx, dev):
         return {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
 
 
+DUMP_BYTES = 60 * 10 ** 6                 # the outputs of one run stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy of each array (float32, or float64 for integers), at most DUMP_BYTES in all: a larger array is replaced by a
+    fixed, seeded sample of its flattened elements (the same indices on every run of the same shape)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    per = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype.kind in "iub" else np.float32)
+        if a.nbytes > per:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, per // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -455,8 +479,14 @@ def main():
                     help="seed of the synthetic KV history and step tokens (torch's default generator is seeded from the OS per process "
                          "on this build: unseeded, every run timed -- and logit-checked -- another draw; profiles/r06_logit_check_draws.txt)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra legs of the default run (batch 8 / 32 of the headline model, INT8 route at batch 32)")
+                    help="skip the extra legs of the --full run (batch 8 / 32 of the headline model, INT8 route at batch 32)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (logits, next tokens) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and the other legs (oracle and logit checks, TTFT, roofline, other batches / INT8 "
+                         "route, config 5, boundary path, CPU baseline); a plain run times the headline step only")
     args = ap.parse_args()
+    full = args.full
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -502,16 +532,16 @@ def main():
     torch.manual_seed(args.seed)           # the history and the tokens: one reproducible draw (every rank the same one)
     ctx = model.new_context(batch, len_buf, seq, fill_random=True, kv_cache_dtype=None if args.kv_cache_dtype == "fp16" else "int8")
     ctx.tokens.copy_(torch.randint(0, cfg.vocab_size, (batch,), device=dev, dtype=torch.int32))
-    oracle_check = check_against_oracle(model, batch, dev) if (rank == 0 and not int8 and tp is None) else None
+    oracle_check = check_against_oracle(model, batch, dev) if (full and rank == 0 and not int8 and tp is None) else None
     logit_check = None
-    if (rank == 0 and world == 1 and not int8 and tp is None and batch == 1 and not args.no_cpu_baseline and not args.layers
+    if (full and rank == 0 and world == 1 and not int8 and tp is None and batch == 1 and not args.no_cpu_baseline and not args.layers
             and args.kv_cache_dtype == "fp16" and os.environ.get("ZL_BENCH_LOGIT_CHECK", "1") != "0"):
         logit_check = check_logits_against_oracle(model, ctx, dev)
 
     # ---- TTFT leg (rank 0, reported next to the decode metric): encode a `seq`-token prompt of one task
     # (M-tiled W4A16 GEMMs, causal attention) and pick the first token.  HIP events around eager launches.
     ttft_ms = None
-    if rank == 0 and not args.no_ttft and tp is None:
+    if full and rank == 0 and not args.no_ttft and tp is None:
         pctx = model.new_context(1, len_buf, 0)
         prompt = torch.randint(0, cfg.vocab_size, (seq,), device=dev, dtype=torch.int32)
         model.prefill(pctx, 0, prompt)
@@ -531,7 +561,7 @@ def main():
     # TP: every rank encodes the same prompt (the collectives need all of them); once single-stream, once as the
     # reference's DUAL_STREAM=1 route (all-reduce of one half on the second stream behind the other half's compute)
     ttft_dual_ms = None
-    if tp is not None and not args.no_ttft:
+    if full and tp is not None and not args.no_ttft:
         gen = torch.Generator(device=dev).manual_seed(7)
         prompt = torch.randint(0, cfg.vocab_size, (seq,), device=dev, dtype=torch.int32, generator=gen)
 
@@ -561,8 +591,12 @@ def main():
         ttft_dual_ms = ttft_leg(True)
         torch.cuda.empty_cache()
 
+    outs = {}
+
     def step():
-        model.step_greedy(ctx)   # encode + greedy pick + advance of the batch state, all on the device
+        # encode + greedy pick + advance of the batch state, all on the device; under the graph the returned tensors are the
+        # replay's static outputs, refilled by every replay
+        outs["logits"], outs["next_tokens"] = model.step_greedy(ctx)
 
     step()  # eager once: allocates the step's buffers, caches device attributes
     torch.cuda.synchronize()
@@ -604,18 +638,20 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v.float().cpu().numpy() if v.is_floating_point() else v.cpu().numpy() for k, v in outs.items()})
 
     # ---- roofline leg (rank 0): the dominant kernel (W4A16 GEMV: k_w4a16_phase / k_w4a16_mfma by default, k_w4a16_gemm
     # under ZL_W4_ALGO=exact; int8 route: k_w8a8_phase)
     roof = None
-    if rank == 0 and int8:
+    if full and rank == 0 and int8:
         roof = roofline_int8(model, cfg, batch, dev)
-    if rank == 0 and not int8 and tp is None:
+    if full and rank == 0 and not int8 and tp is None:
         roof = roofline_w4(model, cfg, batch, dev, ctx, bool(args.layers))
 
     # ---- extra legs of the default single-GPU run: batch 8 / 32 on the headline model, BASELINE configs[2] (INT8, batch 32)
     extras = None
-    if (rank == 0 and world == 1 and not args.no_extras and not int8 and tp is None and batch == 1 and not args.layers
+    if (full and rank == 0 and world == 1 and not args.no_extras and not int8 and tp is None and batch == 1 and not args.layers
             and args.kv_cache_dtype == "fp16"):
         esteps, ewarm = max(8, args.steps // 2), max(2, args.warmup // 2)
         extras = [extra_decode_run(model, cfg, b, seq, esteps, ewarm, dev, False) for b in (8, 32)]
@@ -632,7 +668,7 @@ def main():
             "metric": "decode tokens/s (Llama-3-8B %s, TP=1 per GPU, batch %d, seq %d)" % ("INT8" if int8 else "GPTQ-Int4", batch, seq),
             "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong" if tp else "weak",
-            "vs_baseline": None, "dtype": "f16", "data": "synthetic", "seed": args.seed,
+            "vs_baseline": None, "dtype": "f16", "data": "synthetic", "seed": args.seed, "full": full,
             "config": {"workload": ("Llama-3-8B INT8 (AutoInt8 linears) TP=1 batch=%d decode seq=%d (BASELINE configs[2])" if int8 else
                                     "Llama-3-8B GPTQ-Int4 g128 TP=1 batch=%d decode seq=%d (BASELINE configs[1])") % (batch, seq),
                        "layers": cfg.num_layers,
@@ -653,14 +689,14 @@ def main():
             "step_hbm_roofline_frac": round(step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
             "roofline": roof,
             "other_batches": extras,
-            "config5": config5_leg() if (world == 1 and not args.no_extras and not int8 and tp is None and batch == 1 and not args.layers) else None,
-            "boundary_path": boundary_leg() if (world == 1 and not args.no_extras and not int8 and tp is None and batch == 1 and not args.layers) else None,
+            "config5": config5_leg() if (full and world == 1 and not args.no_extras and not int8 and tp is None and batch == 1 and not args.layers) else None,
+            "boundary_path": boundary_leg() if (full and world == 1 and not args.no_extras and not int8 and tp is None and batch == 1 and not args.layers) else None,
             "oracle_check": None if oracle_check is None else {
                 "what": "layer 0 and last layer, four W4A16 linears each, HIP output vs the CPU oracle's exact product of the "
                         "unpacked (zl_w4m_unpack) bench weights, before the timed region", "max_err_over_max_ref": round(oracle_check, 6)},
             "logit_check": logit_check,
         }
-        if world == 1 and not args.no_cpu_baseline and not int8:
+        if full and world == 1 and not args.no_cpu_baseline and not int8:
             out["cpu_baseline"] = cpu_baseline(cfg, batch, seq)
         else:
             out["cpu_baseline"] = None

@@ -1,4 +1,4 @@
-"""Child process of tests/test_gpu_binding.py: the reference's own `zhilight.C` extension module (zhilight_amd/_ref/C*.so = src/py_export/*.cpp +
+"""Child process of tests/test_gpu_binding.py: the reference's own `zhilight.C` extension module (oracle/_ref/C*.so = src/py_export/*.cpp +
 src/generator/batch_generator.cpp compiled unmodified, linked on libzhilight_amd_host.so) driven the way zhilight/dynamic_batch.py drives it:
 Engine -> LLaMA -> load_state_dict -> BatchGenerator on its own thread -> SearchTask submit / batch_search.  Prints ONE JSON line.
 (The module travels prebuilt; nothing here reads /root/reference.)"""

@@ -1,4 +1,4 @@
-"""The reference's OWN host code on the MI355X boundary.  zhilight_amd/_ref/libzhilight_amd_host.so holds this repository's host layer
+"""The reference's OWN host code on the MI355X boundary.  oracle/_ref/libzhilight_amd_host.so holds this repository's host layer
 (hostcpp/: bmengine on HIP, core::Engine, the operator wrappers, the classes around them) TOGETHER WITH the reference's host translation
 units compiled UNMODIFIED, read in place from /root/reference by zhilight_amd.build.build_host and never copied: src/nn/linear/linear.cpp,
 attention/attention.cpp, attention/multi_head_latent_attention.cpp, feedforward/feedforward.cpp, block/block.cpp, src/model/llama.cpp,
@@ -37,6 +37,13 @@ def ref(dev):
     finally:
         sys.path.pop(0)
     return zl_reflinear
+
+
+def _need_refcompile():
+    """the child-process tests below run the `ref` fixture's module in a fresh process: without it they skip as that fixture does"""
+    from zhilight_amd import build
+    if not os.path.exists(build.refcompile_target()):
+        pytest.skip("zl_reflinear was not built (no reference tree at build time)")
 
 
 def _gptq_state(qw, qz, sc, g_idx=None):
@@ -262,6 +269,7 @@ def test_reference_attention_decode_step_fused_qkv(dev):
     """The same layer under CPM_FUSE_QKV=1 (the reference reads the switch once per process, hence a child process): Linear::fuse
     at load, ONE projection, then rope_qk_cache on DynBatchContext::rope_cache (RopePreparer's tables) in the first step and
     rotary_embedding_qk without them in the second."""
+    _need_refcompile()
     import subprocess
     env = dict(os.environ, CPM_FUSE_QKV="1", ZL_REFATTN_CHILD="1")
     code = ("import sys, os; sys.path.insert(0, os.path.join(%r, 'tests')); import pytest; "
@@ -345,6 +353,7 @@ def test_reference_attention_prompt_chunks_then_decode(ref, oracle):
 def test_reference_attention_int8_kv_cache(dev):
     """The reference's INT8 KV cache path (KV_CACHE_DTYPE=int8, read by ModelContext::get_kv_cache_config) through its own attention
     code, in a child process like the other process-wide switches."""
+    _need_refcompile()
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, KV_CACHE_DTYPE="int8", ZL_REFKV8_CHILD="1")
@@ -491,6 +500,7 @@ def test_reference_encoder_layer_decode_step(ref, oracle):
 def test_reference_mla_layer_latent_cache_decode(dev):
     """The reference's MLA attention layer (MLAImpl, src/nn/attention/multi_head_latent_attention.cpp, compiled unmodified) with the
     compressed cache: LATENT_CACHE=1 FUSE_ATTN_SEARCH=1, both read once per process, hence a child process."""
+    _need_refcompile()
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LATENT_CACHE="1", FUSE_ATTN_SEARCH="1", ZL_REFMLA_CHILD="1")
@@ -710,6 +720,7 @@ def test_reference_llama_model_production_switches(dev):
     """The same whole-model run under the switches a deployment sets (read once per process by the reference, hence a child process):
     CPM_FUSE_QKV=1 (one qkv projection per layer, Linear::fuse at load), ROPE_CACHE=1 (RopePreparer's tables in the context ->
     rope_qk_cache), CPM_FUSE_FF_IN=1 (w_in | w_gated as one projection -> gate_fuse)."""
+    _need_refcompile()
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CPM_FUSE_QKV="1", ROPE_CACHE="1", CPM_FUSE_FF_IN="1", ZL_REFLLAMA_CHILD="1")
@@ -1125,6 +1136,7 @@ def test_reference_deepseek_v3_shaped_layer(dev):
     """Config 5 as a composed LAYER in the reference's own code (VERDICT r04 item 7): nn::EncoderLayer::forward with MLAImpl over
     Fp8Block linears (linear.cpp:1697-1950) followed by FP8BlockMOE.  LATENT_CACHE=1 FUSE_ATTN_SEARCH=1 GROUPED_FP8_GEMM=1
     MOE_EXP_PARALLEL=1 are read once per process by the reference, hence a child process."""
+    _need_refcompile()
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LATENT_CACHE="1", FUSE_ATTN_SEARCH="1", GROUPED_FP8_GEMM="1", MOE_EXP_PARALLEL="1", ZL_REFDS_CHILD="1")
@@ -1196,6 +1208,7 @@ def test_reference_deepseek_v3_shaped_logits_four_layers(dev):
     """one DeepSeek-shaped LOGIT record -- four distinct config-5 layers of the reference's own code (MLA over
     Fp8Block linears + FP8BlockMOE) chained, final RMSNorm, bf16 lm_head -- so that north_star's metric is on file for this
     configuration too (profiles/r06_deepseek_logits.json).  Child process for the same reason as the layer test."""
+    _need_refcompile()
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LATENT_CACHE="1", FUSE_ATTN_SEARCH="1", GROUPED_FP8_GEMM="1", MOE_EXP_PARALLEL="1", ZL_REFDSL_CHILD="1")
@@ -1293,6 +1306,7 @@ def test_reference_deepseek_v3_shaped_layer_sharded_two_ranks(dev):
     compressed cache, decode tasks dealt to the ranks, full-width projections split / kept by on_load's split_out / split_in, FlashMLA
     binding per task) and MOE_EXP_PARALLEL=1: experts e % 2 == rank, tensor-parallel shared expert, route's broadcasts -- every
     exchange on the engine's one-shot transport.  The switches are read once per process: a child process."""
+    _need_refcompile()
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LATENT_CACHE="1", FUSE_ATTN_SEARCH="1", GROUPED_FP8_GEMM="1", MOE_EXP_PARALLEL="1", ATTN_DATA_PARALLEL="1", USE_FLASH_MLA="1",

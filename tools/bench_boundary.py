@@ -1,5 +1,5 @@
 """The decode step as the BOUNDARY offers it (VERDICT r04 missing 3 / item 5): the reference's own model::LLaMA -- src/model/llama.cpp,
-block.cpp, attention.cpp, feedforward.cpp, linear.cpp compiled unmodified (zhilight_amd/_ref/zl_reflinear*.so, built where the
+block.cpp, attention.cpp, feedforward.cpp, linear.cpp compiled unmodified (oracle/_ref/zl_reflinear*.so, built where the
 reference tree exists; this script never reads it) -- running LLaMA::encode (:75-151) + get_logits (:159-165) on hostcpp/nn_amd.cpp
 and the C ABI: one launch and one pooled ctx.tensor per reference op, no fused front ends, 32 full Llama-3-8B layers, batch 1,
 1024 keys of history, the SAME synthetic GPTQ checkpoint bench.py times (LLaMA.init_synthetic, seed 1234).  Prints ONE JSON line:

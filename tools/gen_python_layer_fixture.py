@@ -3,7 +3,7 @@
 The reference's Python sources cannot travel to the GPU box (only /root/reference in this container has them), and this container
 has no GPU -- so "zhilight.llama drops in unchanged" is checked in two halves that meet in this fixture:
   * HERE (CPU): the reference's own `zhilight` package -- every .py symlinked into a temporary package directory next to the built
-    `C*.so` (zhilight_amd/_ref: the reference's src/py_export + batch_generator.cpp compiled unmodified on the MI355X host library),
+    `C*.so` (oracle/_ref: the reference's src/py_export + batch_generator.cpp compiled unmodified on the MI355X host library),
     nothing copied, nothing edited -- is imported and run as far as it goes without a device: config adaptation
     (zhilight/config/adapter.py, zhilight/llama.py:59-113 _get_config), quantisation config + the environment switches it sets
     (zhilight/quant.py:27-91), the safetensors loader and its HF -> internal renaming (zhilight/loader.py:250-358), the dtype views of
