@@ -659,6 +659,22 @@ int zl_prefill_attn(const uint16_t* q, const uint16_t* k_buf, const uint16_t* v_
 int zl_prefill_attn_ex(const uint16_t* q, const uint16_t* k_buf, const uint16_t* v_buf, uint16_t* out, int64_t s_q,
                        int64_t pos0, int64_t h, int64_t hkv, int64_t d, float scale, int64_t len_buf, int bshd,
                        int dtype, int groups, zl_stream_t s);
+/* The same kernel over B tasks' prompt chunks in ONE launch (varlen prompt encode; the reference loops over the tasks and calls flash
+ * attention once per task, attention.cpp:442-562, "TODO: do varlen batch prefill" at :540 against the cu_seqlens_q / cu_seqlens_k
+ * interface of flash_decoding.h:26-33, 71-90).  All pointers are device pointers:
+ *   q / out       (total_q, H, D): task i's query rows are cu_seqlens_q[i] .. cu_seqlens_q[i + 1] - 1 (cu_seqlens_q: b + 1 entries)
+ *   pos0[i]       position of task i's first row: its row r sees keys 0 .. pos0[i] + r of k_bufs[i] / v_bufs[i], buf_lens[i] rows
+ *                 each, BSHD or BHSD, already holding the chunk's own rows (as for zl_prefill_attn)
+ *   work          n_work (task, 64-row query tile) int32 pairs in dispatch order, longest first (LPT over all tasks); the same for
+ *                 every layer of a forward, built once by the caller (zhilight_amd.ops.prefill_varlen_plan)
+ * Per tile the arithmetic of zl_prefill_attn_ex with the same `groups`: a task's rows are bit-identical to that call on the task
+ * alone.  A wrong table never makes the kernel read or write outside the operands (items outside the tasks are dropped, rows are
+ * clamped to total_q, keys to buf_lens[i]).  D = 128; no allocation, no sync.  ZL_EINVAL: null operand, b / total_q / n_work <= 0;
+ * ZL_ESHAPE: d != 128, h % hkv; ZL_EDTYPE: not fp16 / bf16; ZL_ELIMIT: grid overflow. */
+int zl_prefill_attn_varlen(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                           const uint16_t* const* k_bufs, const uint16_t* const* v_bufs, uint16_t* out,
+                           const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
+                           int64_t d, float scale, int bshd, int dtype, int groups, zl_stream_t s);
 
 
 /* ------------------------------------------------------------------------------------------------

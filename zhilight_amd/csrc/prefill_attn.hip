@@ -22,6 +22,11 @@
 // CUs holding the short ones idled.  Group g of a workgroup now walks the key tiles g, g + G, ... of the SAME 64 queries with its
 // own K / V staging buffers and its own (O, m, l); the groups meet once at the end (LDS, flash-decoding's rescale).  The chain is
 // cut G-fold; heavy query tiles are dispatched first.
+//
+// Varlen: one launch covers the (task, query tile, head) work items of B tasks' chunks (zl_prefill_attn_varlen).  Only the work map and
+// the operand addressing differ: a workgroup looks up its (task, tile) in the caller's longest-first table and its task's rows, pos0,
+// buffer length and K / V pointers in device tables; the per-tile arithmetic is the one above, so a task's rows are bit-identical to
+// the one-task launch, which is this kernel with the map computed from the query tile count.
 #include <stdlib.h>
 #include "zl_common.h"
 
@@ -36,13 +41,22 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct PrefillParams {
-    const uint16_t* q;      // (s_q, h, D)
-    const uint16_t* k;      // task buffer, BSHD (len_buf, hkv, D) or BHSD (hkv, len_buf, D)
+    const uint16_t* q;      // (s_q, h, D); varlen: (total_q, h, D), task i's rows cu_q[i] .. cu_q[i + 1] - 1
+    const uint16_t* k;      // task buffer, BSHD (len_buf, hkv, D) or BHSD (hkv, len_buf, D); varlen: k_bufs[task]
     const uint16_t* v;
-    uint16_t* out;          // (s_q, h, D)
+    uint16_t* out;          // (s_q, h, D); varlen: (total_q, h, D)
     int s_q, pos0, h, hkv, n_rep, len_buf, bshd;
     float scale;
     int nx, pair;           // query tiles; workgroup -> work item map (see the kernel)
+    // varlen (work != nullptr): B tasks in one launch.  Work item w = (task, query tile) at work[2 w], work[2 w + 1]; the per-task
+    // s_q / pos0 / len_buf / k / v above are read from these device tables instead
+    const int32_t* work;
+    const int32_t* cu_q;    // (b + 1)
+    const int32_t* pos0s;   // (b)
+    const int32_t* buf_lens;
+    const uint16_t* const* k_bufs;
+    const uint16_t* const* v_bufs;
+    int n_work, b, total_q;
 };
 
 template <int DT>
@@ -72,26 +86,51 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
     // per CU), the first half takes the long items in order and the second half the short ones in REVERSE, so that the two
     // workgroups a CU receives (i and i + half in dispatch order) add up to the same number of key tiles: a 1 024-token prompt
     // gave CU c the query tile c % 16 twice -- 2 to 32 key tiles per CU, 43 us for the unlucky ones, 23 us of work on average
-    const int total = p.nx * p.h;
+    const int total = (p.work ? p.n_work : p.nx) * p.h;
     int item = (int)blockIdx.x;
     if (p.pair == 1 && item >= total / 2) item = total - 1 - (item - total / 2);
-    int head = item % p.h, qt = p.nx - 1 - item / p.h;
-    if (p.pair == 2) {                                    // the round-4 map (A/B): query tile fastest, in ascending order
-        head = item / p.nx;
-        qt = item % p.nx;
+    int head = item % p.h, qt;
+    const uint16_t* qb = p.q;
+    const uint16_t* kb = p.k;
+    const uint16_t* vb = p.v;
+    uint16_t* ob = p.out;
+    int s_q = p.s_q, pos0 = p.pos0, len_buf = p.len_buf;
+    if (p.work) {
+        // varlen: the caller's table lists the (task, query tile) items longest first, so item order is LPT order across the tasks as
+        // it is within one task above.  A wrong table cannot make the workgroup read or write outside the operands: an item outside
+        // the tasks or past its task's rows is dropped, the rows are clamped to total_q and the keys to the buffer's length
+        const int w = item / p.h;
+        const int task = __builtin_amdgcn_readfirstlane(p.work[2 * w]);
+        qt = __builtin_amdgcn_readfirstlane(p.work[2 * w + 1]);
+        if (task < 0 || task >= p.b || qt < 0) return;
+        const int qa = max(p.cu_q[task], 0), qe = min(p.cu_q[task + 1], p.total_q);
+        s_q = qe - qa;
+        pos0 = max(p.pos0s[task], 0);
+        len_buf = p.buf_lens[task];
+        kb = p.k_bufs[task];
+        vb = p.v_bufs[task];
+        if (qt * kBQ >= s_q || len_buf <= 0 || !kb || !vb) return;       // workgroup-uniform: before any barrier
+        qb += (size_t)qa * p.h * kD;
+        ob += (size_t)qa * p.h * kD;
+    } else {
+        qt = p.nx - 1 - item / p.h;
+        if (p.pair == 2) {                                // the round-4 map (A/B): query tile fastest, in ascending order
+            head = item / p.nx;
+            qt = item % p.nx;
+        }
     }
     const int hk = head / p.n_rep;
     const int q0 = qt * kBQ;
     const int qrow = q0 + wave * 16 + nq;                 // the query this lane's scores belong to
-    const int qpos = p.pos0 + qrow;                       // its position: keys 0 .. qpos are visible
+    const int qpos = pos0 + qrow;                         // its position: keys 0 .. qpos are visible
     const size_t kv_stride = p.bshd ? (size_t)p.hkv * kD : (size_t)kD;
-    const size_t kv_off = p.bshd ? (size_t)hk * kD : (size_t)hk * p.len_buf * kD;
+    const size_t kv_off = p.bshd ? (size_t)hk * kD : (size_t)hk * len_buf * kD;
 
     // Q fragments (B operand of S^T = K.Q^T): column q = lane & 15, k-chunk = d 32 t + 8 kq .. +7
     uint4 qf[4];
     {
-        const int qr = qrow < p.s_q ? qrow : p.s_q - 1;
-        const uint16_t* qp = p.q + ((size_t)qr * p.h + head) * kD + 8 * kq;
+        const int qr = qrow < s_q ? qrow : s_q - 1;
+        const uint16_t* qp = qb + ((size_t)qr * p.h + head) * kD + 8 * kq;
 #pragma unroll
         for (int t = 0; t < 4; ++t) qf[t] = *reinterpret_cast<const uint4*>(qp + 32 * t);
     }
@@ -101,8 +140,8 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
     for (int db = 0; db < 8; ++db) o[db] = (f4){0.f, 0.f, 0.f, 0.f};
     float m_run = -1e20f, l_run = 0.f;                    // per query (lane & 15), replicated over kq
 
-    const int last_q = min(q0 + kBQ, p.s_q) - 1;
-    const int n_keys = p.pos0 + last_q + 1;               // keys any row of this block may see
+    const int last_q = min(q0 + kBQ, s_q) - 1;
+    const int n_keys = min(pos0 + last_q + 1, len_buf);  // keys any row of this block may see (never past the buffer)
     const int n_tiles = (n_keys + kBK - 1) / kBK;
 
     // K / V tile loads ride in registers one tile ahead (thread -> key = tid % 64, d chunks tid / 64 + 4 c): a workgroup
@@ -117,8 +156,8 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
     {                                                                                                      \
         const int kg_ = (tile_) * kBK + skey;                                                              \
         const int kc_ = kg_ < n_keys ? kg_ : n_keys - 1;                                                   \
-        const uint16_t* kp_ = p.k + kv_off + (size_t)kc_ * kv_stride;                                     \
-        const uint16_t* vp_ = p.v + kv_off + (size_t)kc_ * kv_stride;                                     \
+        const uint16_t* kp_ = kb + kv_off + (size_t)kc_ * kv_stride;                                       \
+        const uint16_t* vp_ = vb + kv_off + (size_t)kc_ * kv_stride;                                       \
         const bool dead_ = kg_ >= n_keys;                                                                  \
         ZL_PF_LOAD1(0, kp_, vp_, dead_) ZL_PF_LOAD1(1, kp_, vp_, dead_) ZL_PF_LOAD1(2, kp_, vp_, dead_) ZL_PF_LOAD1(3, kp_, vp_, dead_) \
     }
@@ -154,7 +193,7 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
         //      the log2 domain (scale * log2 e folded into one multiply, v_exp_f32 is exp2); the causal select runs only on tiles
         //      that reach this wave's diagonal (wave-uniform: every other tile is fully visible)
         const float sl2 = p.scale * 1.44269504088896340736f;
-        const bool diag = key0 + kBK - 1 > p.pos0 + q0 + wave * 16;      // some key of the tile lies beyond the wave's first query
+        const bool diag = key0 + kBK - 1 > pos0 + q0 + wave * 16;        // some key of the tile lies beyond the wave's first query
         float mloc = -INFINITY;
         if (diag) {
 #pragma unroll
@@ -284,8 +323,8 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = q0 + wave * 16 + 4 * kq + i;
-        if (row >= p.s_q) continue;
-        uint16_t* op = p.out + ((size_t)row * p.h + head) * kD + nq;
+        if (row >= s_q) continue;
+        uint16_t* op = ob + ((size_t)row * p.h + head) * kD + nq;
 #pragma unroll
         for (int db = 0; db < 8; ++db) op[db * 16] = ZT<DT>::from_f32(o[db][i] * inv[i]);
     }
@@ -314,8 +353,29 @@ static int launch_prefill(const PrefillParams& p, dim3 grid, hipStream_t hs) {
     return zl_launch_status();
 }
 
-// groups: wave groups per workgroup (1 / 2 / 4: the key tiles of a query tile are dealt to them round-robin); 0 = the launcher's
-// choice: as many as the longest query tile has key tiles to hand out, up to 4
+// the launch of either form: `groups` wave groups per workgroup (1 / 2 / 4: the key tiles of a query tile are dealt to them
+// round-robin; 0 = the launcher's choice), one workgroup per (work item, head)
+static int dispatch_prefill(PrefillParams& p, int64_t items, int dtype, int groups, bool plain_map, hipStream_t hs) {
+    ZL_CHECK_ARG(items * p.h < ((int64_t)1 << 31), ZL_ELIMIT);
+    const dim3 grid((unsigned)(items * p.h));
+    // measured (profiles/r05_prefill_attn.txt): more wave groups make the launch SLOWER (43 -> 72 us per layer at 1 024 tokens with
+    // four): a CU is throughput-bound from two 4-wave workgroups on, what a long query tile lacked was a short neighbour, not waves
+    if (groups == 0) groups = 1;
+    int cus = zl_device_cu_count();
+    if (cus <= 0) cus = 256;
+    const int total = (int)(items * p.h);
+    p.pair = (groups == 1 && total % 2 == 0 && total <= 2 * cus) ? 1 : 0;
+    if (plain_map) p.pair = 2;
+#define ZL_PF_G(GG) return dtype == ZL_F16 ? launch_prefill<ZL_F16, GG>(p, grid, hs) : launch_prefill<ZL_BF16, GG>(p, grid, hs);
+    switch (groups) {
+        case 1: ZL_PF_G(1)
+        case 2: ZL_PF_G(2)
+        default: ZL_PF_G(4)
+    }
+#undef ZL_PF_G
+}
+
+// groups: wave groups per workgroup (1 / 2 / 4); 0 = the launcher's choice (1); -1 = the round-4 launch (one group, plain map)
 extern "C" int zl_prefill_attn_ex(const uint16_t* q, const uint16_t* k_buf, const uint16_t* v_buf, uint16_t* out, int64_t s_q,
                                   int64_t pos0, int64_t h, int64_t hkv, int64_t d, float scale, int64_t len_buf, int bshd,
                                   int dtype, int groups, zl_stream_t s) {
@@ -327,27 +387,30 @@ extern "C" int zl_prefill_attn_ex(const uint16_t* q, const uint16_t* k_buf, cons
     const bool plain_map = groups == -1;               // A/B switch: one group, work items in plain dispatch order (the round-4 launch)
     if (plain_map) groups = 1;
     ZL_CHECK_ARG(groups == 0 || groups == 1 || groups == 2 || groups == 4, ZL_EINVAL);
-    PrefillParams p;
+    PrefillParams p = {};
     p.q = q; p.k = k_buf; p.v = v_buf; p.out = out;
     p.s_q = (int)s_q; p.pos0 = (int)pos0; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
     p.len_buf = (int)len_buf; p.bshd = bshd; p.scale = scale;
     p.nx = (int)((s_q + kBQ - 1) / kBQ);
-    ZL_CHECK_ARG((int64_t)p.nx * h < ((int64_t)1 << 31), ZL_ELIMIT);
-    const dim3 grid((unsigned)(p.nx * (int)h));
-    // measured (profiles/r05_prefill_attn.txt): more wave groups make the launch SLOWER (43 -> 72 us per layer at 1 024 tokens with
-    // four): a CU is throughput-bound from two 4-wave workgroups on, what a long query tile lacked was a short neighbour, not waves
-    if (groups == 0) groups = 1;
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
-    const int total = p.nx * (int)h;
-    p.pair = (groups == 1 && total % 2 == 0 && total <= 2 * cus) ? 1 : 0;
-    if (plain_map) p.pair = 2;
-    hipStream_t hs = (hipStream_t)s;
-#define ZL_PF_G(GG) return dtype == ZL_F16 ? launch_prefill<ZL_F16, GG>(p, grid, hs) : launch_prefill<ZL_BF16, GG>(p, grid, hs);
-    switch (groups) {
-        case 1: ZL_PF_G(1)
-        case 2: ZL_PF_G(2)
-        default: ZL_PF_G(4)
-    }
-#undef ZL_PF_G
+    return dispatch_prefill(p, p.nx, dtype, groups, plain_map, (hipStream_t)s);
+}
+
+// B tasks in one launch: the work table (n_work (task, query tile) pairs, longest first) comes from the caller, built once per
+// forward (zhilight_amd.ops.prefill_varlen_plan); the kernel reads the per-task operands from the device tables
+extern "C" int zl_prefill_attn_varlen(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                                      const uint16_t* const* k_bufs, const uint16_t* const* v_bufs, uint16_t* out,
+                                      const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
+                                      int64_t d, float scale, int bshd, int dtype, int groups, zl_stream_t s) {
+    ZL_CHECK_ARG(q && cu_seqlens_q && pos0 && buf_lens && k_bufs && v_bufs && out && work, ZL_EINVAL);
+    ZL_CHECK_ARG(b > 0 && total_q > 0 && n_work > 0 && h > 0 && hkv > 0, ZL_EINVAL);
+    ZL_CHECK_ARG(d == kD && h % hkv == 0, ZL_ESHAPE);
+    ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
+    ZL_CHECK_ARG(groups == 0 || groups == 1 || groups == 2 || groups == 4, ZL_EINVAL);
+    ZL_CHECK_ARG(h <= 65535 && b < ((int64_t)1 << 30) && total_q < ((int64_t)1 << 31) && n_work < ((int64_t)1 << 31), ZL_ELIMIT);
+    PrefillParams p = {};
+    p.q = q; p.out = out;
+    p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv); p.bshd = bshd; p.scale = scale;
+    p.work = work; p.cu_q = cu_seqlens_q; p.pos0s = pos0; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs;
+    p.n_work = (int)n_work; p.b = (int)b; p.total_q = (int)total_q;
+    return dispatch_prefill(p, n_work, dtype, groups, false, (hipStream_t)s);
 }

@@ -1375,6 +1375,33 @@ class LLaMA:
         ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - (pos0 + s))
         return logits
 
+    def prefill_batch(self, ctx: DynBatchContext, tasks, prompts, pos0=None):
+        """Prompt encode of several tasks in ONE pass through the layers (LLaMA::encode with the prompt rows of every task of the
+        step in each linear, src/model/llama.cpp:75-165; attention as one varlen launch where attn_encode_group loops over the
+        tasks, src/nn/attention/attention.cpp:442-562).  prompts[j] (1-D int tensor, lengths may differ) goes to the distinct
+        task tasks[j]; pos0[j] (default 0) > 0 continues a prompt whose rows 0 .. pos0[j] - 1 are already in the task's buffers.
+        Returns the logits of each task's last prompt row (len(tasks), vocab) and leaves every task as prefill() does: the greedy
+        first token in ctx.tokens, positions = placement = pos0 + s, valid_lens = pos0 + s + 1, steps_left bounded.
+        INT8 KV cache: fresh prompts only (a continued prompt raises ZLError: chunked prompts go through prefill(chunk=...)).
+        Head sizes other than 128: batched linears, attention per task through the mask form.  Tensor parallelism: single
+        stream, the all-reduces run over the summed rows; DUAL_STREAM does not apply to a batched call.  dynamic (NTK) rope
+        takes the call's last row as its sequence length, as the reference does for any forward.  Duplicate or out-of-range
+        tasks, empty prompts and prompts that do not fit the buffers raise ZLError before any launch."""
+        tasks = [int(t) for t in tasks]
+        n = len(tasks)
+        pos0 = [0] * n if pos0 is None else [int(p) for p in pos0]
+        if n < 1 or len(prompts) != n or len(pos0) != n:
+            raise ops.ZLError("prefill_batch: one prompt and one pos0 per task")
+        if len(set(tasks)) != n or any(t < 0 or t >= ctx.tokens.numel() for t in tasks):
+            raise ops.ZLError("prefill_batch: tasks must be distinct indices of the batch")
+        for t, pr, p0 in zip(tasks, prompts, pos0):
+            s = int(pr.numel())
+            if s < 1 or p0 < 0 or p0 + s + 1 > ctx.max_len_buf:
+                raise ops.ZLError(f"prefill_batch: prompt of task {t} ({s} tokens at {p0}) does not fit the task's KV buffer")
+            if ctx.kv_quant and p0 != 0:
+                raise ops.ZLError("prefill_batch: a continued prompt into the INT8 KV cache goes through LLaMA.prefill(chunk=...)")
+        return self._prefill_rows(ctx, tasks, prompts, pos0)
+
     def _prefill_chunk(self, ctx: DynBatchContext, task: int, prompt: torch.Tensor, pos0: int):
         """The "encode part" of a task (LLaMA::encode with len_q = prompt length for one task:
         src/model/llama.cpp:75-165, Attention::impl::NormalImpl::dynamic_batch_forward encode branch,
@@ -1384,73 +1411,162 @@ class LLaMA:
         the last prompt position (1, vocab).  Sequence: separate RMSNorm, W4A16 GEMM (M = S: the M-tiled MFMA
         kernel, the arithmetic of the reference's M > 40 dequant + GEMM branch), rope_qk_cache,
         copy_to_rag_buffer2, causal MFMA attention (prefill_attention; other head sizes: the mask form of
-        multi_query_attention_rag_buffer)."""
-        c, dev = self.cfg, self.device
+        multi_query_attention_rag_buffer).  The one-task case of _prefill_rows."""
         s = int(prompt.numel())
         if s < 1 or pos0 + s + 1 > ctx.max_len_buf:
             raise ops.ZLError("prompt does not fit the task's KV buffer")
-        unq = ctx.unquant_kv.get(task) if ctx.kv_quant else None
-        if ctx.kv_quant and pos0 != 0 and unq is None:
+        if ctx.kv_quant and pos0 != 0 and ctx.unquant_kv.get(task) is None:
             # a later piece without the prompt's temporary unquantised buffers (prefill(chunk=...) keeps them): the reference
             # falls back to de-quantising the cache there ("WARNING: de-quantize prompt kv cache!", attention.cpp:511-516)
             raise ops.ZLError("chunked prefill into the INT8 KV cache goes through LLaMA.prefill(chunk=...)")
-        tokens = prompt.to(device=dev, dtype=torch.int32).contiguous()
-        pos = torch.arange(pos0, pos0 + s, dtype=torch.int32, device=dev)
+        return self._prefill_rows(ctx, [task], [prompt], [pos0])
+
+    def _prefill_rows(self, ctx: DynBatchContext, tasks, prompts, pos0s):
+        """The layer loop of prompt encode over the rows of n tasks (checked by the callers): one task is _prefill_chunk's
+        launch sequence exactly; n > 1 gathers the per-row scatter tables and the attention tables once per call (one upload of
+        positions and plans), runs every linear over the summed rows, the K/V scatter with one "task" per row, one varlen
+        attention launch per layer, then one gather of the last rows, one lm_head and one pick for the n rows."""
+        c, dev = self.cfg, self.device
+        n = len(tasks)
+        one = n == 1
+        lens = [int(pr.numel()) for pr in prompts]
+        total = sum(lens)
+        hkv, d = c.num_kv_heads, c.dim_head
+        scale = 1.0 / math.sqrt(d)
+        if one:
+            task, s, pos0 = tasks[0], lens[0], pos0s[0]
+            tokens = prompts[0].to(device=dev, dtype=torch.int32).contiguous()
+            pos = torch.arange(pos0, pos0 + s, dtype=torch.int32, device=dev)
+            placement = pos.view(1, s)
+            buf_lens = ctx.buf_lens[task:task + 1]
+            unq = ctx.unquant_kv.get(task) if ctx.kv_quant else None
+        else:
+            tokens = torch.cat([pr.to(device=dev, dtype=torch.int32).reshape(-1) for pr in prompts])
+            ends = [p0 + s for p0, s in zip(pos0s, lens)]
+            cu = [0]
+            for s in lens:
+                cu.append(cu[-1] + s)
+            # one upload of the call's int32 and one of its int64 tables
+            pos_all = torch.tensor([p0 + r for p0, s in zip(pos0s, lens) for r in range(s)] + ends + lens, dtype=torch.int32).to(dev)
+            pos, ends_dev, lens_dev = pos_all[:total], pos_all[total:total + n], pos_all[total + n:]
+            row_bytes = hkv * d * c.torch_dtype.itemsize
+            idx = torch.tensor(tasks + [t for t, s in zip(tasks, lens) for _ in range(s)] + [r - 1 for r in cu[1:]] +
+                               [r * row_bytes for r in cu[:-1]], dtype=torch.int64).to(dev)
+            tasks_dev, rows_dev, last_rows = idx[:n], idx[n:n + total], idx[n + total:2 * n + total]
+            kv_off = idx[2 * n + total:]                      # byte offset of each task's first row in the concatenated k / v
+            placement = pos.view(total, 1)                    # the K/V scatter: one "task" per row
+            buf_lens = ctx.buf_lens.index_select(0, rows_dev)
+            ka_rows, va_rows = ctx.k_addrs.index_select(1, rows_dev), ctx.v_addrs.index_select(1, rows_dev)
+            if ctx.kv_quant:                                  # attention over the call's own rows (fresh prompts only)
+                ks_rows, vs_rows = ctx.ks_addrs.index_select(1, rows_dev), ctx.vs_addrs.index_select(1, rows_dev)
+                att_pos0, len_bufs, len_bufs_dev = [0] * n, lens, lens_dev
+            else:
+                ka_t, va_t = ctx.k_addrs.index_select(1, tasks_dev), ctx.v_addrs.index_select(1, tasks_dev)
+                att_pos0, len_bufs, len_bufs_dev = pos0s, [ctx.max_len_buf] * n, ctx.buf_lens.index_select(0, tasks_dev)
+            plan = ops.prefill_varlen_plan(lens, att_pos0, len_bufs, dev) if d == 128 else None
         hidden = ops.embedding(tokens, self.token_embedding, c.scale_emb)
         cos, sin = self._rope_tables(pos)
-        placement = pos.view(1, s)
-        buf_lens = ctx.buf_lens[task:task + 1]
-        scale = 1.0 / math.sqrt(c.dim_head)
         for li, layer in enumerate(self.layers):
-            ka, va = ctx.k_addrs[li][task:task + 1], ctx.v_addrs[li][task:task + 1]
             qkv = layer.project_qkv(hidden, c.eps)
             self.apply_qk_norm(layer, qkv)
-            q, k, v = ops.rope_qk_cache(cos, sin, qkv, c.num_heads, c.num_kv_heads, c.dim_head, True)
-            if ctx.kv_quant:
-                # attn_encode_group with a quantised buffer (attention.cpp:494-510): the prompt attends to its own
-                # UNquantised K/V rows while their codes go to the cache
-                k3, v3 = k.view(s, c.num_kv_heads, c.dim_head), v.view(s, c.num_kv_heads, c.dim_head)
-                ops.quant_copy_to_rag_buffer(pos, buf_lens, k3, v3, ka, va, ctx.ks_addrs[li][task:task + 1],
-                                             ctx.vs_addrs[li][task:task + 1], len_q=s)
-                if unq is not None:
-                    # chunked: this piece's rows join the prompt's unquantised buffers, the piece attends to all of them
-                    tk, tv = unq[li, 0], unq[li, 1]
-                    tl = torch.tensor([tk.shape[0]], dtype=torch.int32, device=dev)
-                    ops.copy_to_rag_buffer2(placement, tl, k3.view(1, s, c.num_kv_heads, c.dim_head), v3.view(1, s, c.num_kv_heads, c.dim_head),
-                                            ops.make_ptr_table([tk]), ops.make_ptr_table([tv]))
-                    if c.dim_head == 128:
-                        att = ops.prefill_attention(q.view(s, c.num_heads, c.dim_head), tk, tv, pos0, c.num_kv_heads, scale)
-                    else:
-                        mask, ws = self._prefill_mask(s, tk.shape[0], pos0)
-                        att = ops.multi_query_attention_rag_buffer(q.view(1, s, c.num_heads, c.dim_head), tl, ops.make_ptr_table([tk]),
-                                                                   ops.make_ptr_table([tv]), mask, scale, tk.shape[0], c.num_kv_heads,
-                                                                   workspace=ws)
-                elif c.dim_head == 128:
-                    att = ops.prefill_attention(q.view(s, c.num_heads, c.dim_head), k3, v3, 0, c.num_kv_heads, scale)
-                else:
-                    mask, ws = self._prefill_mask(s, s, 0)
-                    att = ops.multi_query_attention_rag_buffer(
-                        q.view(1, s, c.num_heads, c.dim_head), torch.tensor([s], dtype=torch.int32, device=dev),
-                        ops.make_ptr_table([k3]), ops.make_ptr_table([v3]), mask, scale, s, c.num_kv_heads, workspace=ws)
-                layer.attn_out_add(att.view(s, -1), hidden)
-                layer.ff_add(hidden, c.eps)
-                continue
-            ops.copy_to_rag_buffer2(placement, buf_lens, k.view(1, s, c.num_kv_heads, c.dim_head),
-                                    v.view(1, s, c.num_kv_heads, c.dim_head), ka, va)
-            if c.dim_head == 128:
-                att = ops.prefill_attention(q.view(s, c.num_heads, c.dim_head), ctx.kv[task][li, 0], ctx.kv[task][li, 1], pos0,
-                                            c.num_kv_heads, scale)
+            q, k, v = ops.rope_qk_cache(cos, sin, qkv, c.num_heads, hkv, d, True)
+            q3, k3, v3 = q.view(total, c.num_heads, d), k.view(total, hkv, d), v.view(total, hkv, d)
+            if one:
+                att = self._prompt_attention_one(ctx, li, task, q3, k3, v3, pos, placement, buf_lens, pos0, unq, scale)
+            elif ctx.kv_quant:
+                # attn_encode_group with a quantised buffer (attention.cpp:494-510): the prompts attend to their own UNquantised
+                # rows -- the tables point into the concatenated k / v -- while the codes go to the cache
+                ops.quant_copy_to_rag_buffer(pos, buf_lens, k3, v3, ka_rows[li], va_rows[li], ks_rows[li], vs_rows[li], len_q=1)
+                att = self._prompt_attention_tasks(q3, lens, att_pos0, kv_off + k3.data_ptr(), kv_off + v3.data_ptr(), len_bufs,
+                                                   len_bufs_dev, plan, cu, scale)
             else:
-                mask, ws = self._prefill_mask(s, ctx.max_len_buf, pos0)
-                att = ops.multi_query_attention_rag_buffer(q.view(1, s, c.num_heads, c.dim_head), buf_lens, ka, va, mask,
-                                                           scale, ctx.max_len_buf, c.num_kv_heads, workspace=ws)
-            layer.attn_out_add(att.view(s, -1), hidden)
+                ops.copy_to_rag_buffer2(placement, buf_lens, k3.view(total, 1, hkv, d), v3.view(total, 1, hkv, d),
+                                        ka_rows[li], va_rows[li])
+                att = self._prompt_attention_tasks(q3, lens, att_pos0, ka_t[li], va_t[li], len_bufs, len_bufs_dev, plan, cu, scale)
+            layer.attn_out_add(att.view(total, -1), hidden)
             layer.ff_add(hidden, c.eps)
-        logits = self._prompt_logits_and_pick(ctx, task, hidden[s - 1:s])
-        ctx.positions[task] = pos0 + s
-        ctx.placement[task] = pos0 + s
-        ctx.valid_lens[task] = pos0 + s + 1
-        ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - (pos0 + s))
+        if one:
+            logits = self._prompt_logits_and_pick(ctx, task, hidden[s - 1:s])
+            ctx.positions[task] = pos0 + s
+            ctx.placement[task] = pos0 + s
+            ctx.valid_lens[task] = pos0 + s + 1
+            ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - (pos0 + s))
+            return logits
+        logits = self._prompt_logits_and_pick_rows(ctx, tasks_dev, hidden.index_select(0, last_rows))
+        ctx.positions.index_copy_(0, tasks_dev, ends_dev)
+        ctx.placement.index_copy_(0, tasks_dev, ends_dev)
+        ctx.valid_lens.index_copy_(0, tasks_dev, ends_dev + 1)
+        ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - max(ends))
+        return logits
+
+    def _prompt_attention_tasks(self, q3, lens, pos0s, k_tab, v_tab, len_bufs, len_bufs_dev, plan, cu, scale):
+        """attention of n > 1 tasks' prompt rows q3 (total, H, D) against the buffers of the tables k_tab / v_tab (n pointers,
+        len_bufs rows each): one varlen launch (head size 128), or per task the mask form of multi_query_attention_rag_buffer"""
+        c = self.cfg
+        if plan is not None:
+            return ops.prefill_attention_varlen(q3, lens, pos0s, k_tab, v_tab, plan.buf_lens, c.num_kv_heads, scale, plan=plan)
+        att = torch.empty_like(q3)
+        for i, (s, p0) in enumerate(zip(lens, pos0s)):
+            a = cu[i]
+            mask, ws = self._prefill_mask(s, len_bufs[i], p0)
+            ops.multi_query_attention_rag_buffer(q3[a:a + s].view(1, s, c.num_heads, c.dim_head), len_bufs_dev[i:i + 1],
+                                                 k_tab[i:i + 1], v_tab[i:i + 1], mask, scale, len_bufs[i], c.num_kv_heads,
+                                                 out=att[a:a + s].view(1, s, c.num_heads, c.dim_head), workspace=ws)
+        return att
+
+    def _prompt_attention_one(self, ctx, li, task, q3, k3, v3, pos, placement, buf_lens, pos0, unq, scale):
+        """K/V scatter + attention of one task's prompt rows (the launch sequence of the one-task encode)"""
+        c, dev = self.cfg, self.device
+        s = q3.shape[0]
+        ka, va = ctx.k_addrs[li][task:task + 1], ctx.v_addrs[li][task:task + 1]
+        if ctx.kv_quant:
+            # attn_encode_group with a quantised buffer (attention.cpp:494-510): the prompt attends to its own
+            # UNquantised K/V rows while their codes go to the cache
+            ops.quant_copy_to_rag_buffer(pos, buf_lens, k3, v3, ka, va, ctx.ks_addrs[li][task:task + 1],
+                                         ctx.vs_addrs[li][task:task + 1], len_q=s)
+            if unq is not None:
+                # chunked: this piece's rows join the prompt's unquantised buffers, the piece attends to all of them
+                tk, tv = unq[li, 0], unq[li, 1]
+                tl = torch.tensor([tk.shape[0]], dtype=torch.int32, device=dev)
+                ops.copy_to_rag_buffer2(placement, tl, k3.view(1, s, c.num_kv_heads, c.dim_head), v3.view(1, s, c.num_kv_heads, c.dim_head),
+                                        ops.make_ptr_table([tk]), ops.make_ptr_table([tv]))
+                if c.dim_head == 128:
+                    return ops.prefill_attention(q3, tk, tv, pos0, c.num_kv_heads, scale)
+                mask, ws = self._prefill_mask(s, tk.shape[0], pos0)
+                return ops.multi_query_attention_rag_buffer(q3.view(1, s, c.num_heads, c.dim_head), tl, ops.make_ptr_table([tk]),
+                                                            ops.make_ptr_table([tv]), mask, scale, tk.shape[0], c.num_kv_heads,
+                                                            workspace=ws)
+            if c.dim_head == 128:
+                return ops.prefill_attention(q3, k3, v3, 0, c.num_kv_heads, scale)
+            mask, ws = self._prefill_mask(s, s, 0)
+            return ops.multi_query_attention_rag_buffer(
+                q3.view(1, s, c.num_heads, c.dim_head), torch.tensor([s], dtype=torch.int32, device=dev),
+                ops.make_ptr_table([k3]), ops.make_ptr_table([v3]), mask, scale, s, c.num_kv_heads, workspace=ws)
+        ops.copy_to_rag_buffer2(placement, buf_lens, k3.view(1, s, c.num_kv_heads, c.dim_head),
+                                v3.view(1, s, c.num_kv_heads, c.dim_head), ka, va)
+        if c.dim_head == 128:
+            return ops.prefill_attention(q3, ctx.kv[task][li, 0], ctx.kv[task][li, 1], pos0, c.num_kv_heads, scale)
+        mask, ws = self._prefill_mask(s, ctx.max_len_buf, pos0)
+        return ops.multi_query_attention_rag_buffer(q3.view(1, s, c.num_heads, c.dim_head), buf_lens, ka, va, mask,
+                                                    scale, ctx.max_len_buf, c.num_kv_heads, workspace=ws)
+
+    def _prompt_logits_and_pick_rows(self, ctx, tasks_dev, last_hidden):
+        """_prompt_logits_and_pick for the last rows of n tasks (tasks_dev: their int64 indices): the picks go to a temporary and
+        are scattered to ctx.tokens, since greedy_advance / argmax_advance write consecutive rows"""
+        n = last_hidden.shape[0]
+        picks = torch.empty(n, dtype=torch.int32, device=self.device)
+        if self.tp:
+            logits = self._logits(last_hidden)
+            ops.argmax_advance(logits, tokens=picks)
+        else:
+            key = ("argmax", n)
+            if key not in self._bufs:
+                self._bufs[key] = (ops.argmax_workspace(n, self.cfg.vocab_size, self.device),
+                                   torch.empty(n, dtype=torch.int64, device=self.device))
+            ws = self._bufs[key][0]
+            logits = self._logits(last_hidden, argmax_ws=ws)
+            ops.greedy_advance(ws, n, self.cfg.vocab_size, tokens=picks)
+        ctx.tokens.index_copy_(0, tasks_dev, picks)
         return logits
 
     def _prompt_logits_and_pick(self, ctx, task, last_hidden):

@@ -1239,6 +1239,86 @@ def prefill_attention(q, k_buf, v_buf, pos0, num_kv_heads, scale, bshd=True, out
     return out
 
 
+def prefill_work_items(lens, pos0):
+    """The work map of zl_prefill_attn_varlen (host only): every (task, 64-row query tile) of the tasks' chunks once, longest first
+    -- by the key tiles the tile's last row sees -- ties in task order, the later tile first.  For one task this is the order of
+    zl_prefill_attn's own map."""
+    keyed = []
+    for t, (s, p0) in enumerate(zip(lens, pos0)):
+        for qt in range((int(s) + 63) // 64):
+            last = min((qt + 1) * 64, int(s))
+            keyed.append((-((int(p0) + last + 63) // 64), t, -qt))
+    keyed.sort()
+    return [(t, -nqt) for _, t, nqt in keyed]
+
+
+class PrefillVarlenPlan:
+    """The device tables of one varlen prompt-attention call, uploaded once per forward and used by every layer: cu_seqlens_q
+    (b + 1), pos0 (b), buf_lens (b) and the work table (n_work, 2), in one int32 tensor.  The host lists stay for the checks."""
+
+    def __init__(self, lens, pos0, buf_lens, device):
+        self.lens, self.pos0, self.buf_lens = [int(x) for x in lens], [int(x) for x in pos0], [int(x) for x in buf_lens]
+        b = self.b = len(self.lens)
+        if b < 1 or len(self.pos0) != b or len(self.buf_lens) != b:
+            raise ZLError("prefill_varlen_plan: one length, pos0 and buffer length per task")
+        for s, p0, lb in zip(self.lens, self.pos0, self.buf_lens):
+            if s < 1 or p0 < 0 or p0 + s > lb:
+                raise ZLError(f"prefill_varlen_plan: chunk of {s} rows at pos0 {p0} does not fit a buffer of {lb} rows")
+        self.work_items = prefill_work_items(self.lens, self.pos0)
+        self.n_work = len(self.work_items)
+        cu = [0]
+        for s in self.lens:
+            cu.append(cu[-1] + s)
+        self.total_q = cu[-1]
+        self.cu = cu
+        flat = [x for item in self.work_items for x in item]
+        self.tables = torch.tensor(cu + self.pos0 + self.buf_lens + flat, dtype=torch.int32).to(device)
+        self.cu_seqlens_q = self.tables[:b + 1]
+        self.pos0_dev = self.tables[b + 1:2 * b + 1]
+        self.buf_lens_dev = self.tables[2 * b + 1:3 * b + 1]
+        self.work = self.tables[3 * b + 1:]
+
+
+def prefill_varlen_plan(lens, pos0, buf_lens, device):
+    """Plan of a varlen prompt-attention call: lens / pos0 / buf_lens are host ints per task (rows of the chunk, position of its
+    first row, rows of its K/V buffers); raises ZLError for a chunk that does not fit its buffer.  Returns PrefillVarlenPlan."""
+    return PrefillVarlenPlan(lens, pos0, buf_lens, device)
+
+
+def prefill_attention_varlen(q, lens, pos0, k_addrs, v_addrs, buf_lens, num_kv_heads, scale, bshd=True, out=None, groups=None,
+                             plan=None):
+    """Causal attention of B tasks' prompt chunks in one launch (attn_encode_group's per-task flash-attention loop,
+    src/nn/attention/attention.cpp:442-562, as one varlen call).  q (total_q, H, D): task i's rows back to back, lens[i] of them, at
+    positions pos0[i] ..; k_addrs / v_addrs device int64 tables of the tasks' K/V buffers (buf_lens[i] rows each, BSHD or BHSD),
+    which already hold the chunks' own rows.  lens / pos0 / buf_lens are host ints (checked here); `plan` (prefill_varlen_plan of
+    the same lists) spares the upload when several layers share it.  Per task bit-identical to prefill_attention(.., groups)."""
+    _chk_cuda(q, k_addrs, v_addrs)
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError("prefill_attention_varlen: fp16 / bf16 only")
+    if plan is None:
+        plan = prefill_varlen_plan(lens, pos0, buf_lens, q.device)
+    elif plan.lens != [int(x) for x in lens] or plan.pos0 != [int(x) for x in pos0] or plan.buf_lens != [int(x) for x in buf_lens]:
+        raise ZLError("prefill_attention_varlen: the plan was made for other lengths")
+    total_q, h, d = q.shape
+    if total_q != plan.total_q:
+        raise ZLError(f"prefill_attention_varlen: q has {total_q} rows, the lengths add up to {plan.total_q}")
+    for t in (k_addrs, v_addrs):
+        if t.dtype != torch.int64 or t.numel() != plan.b:
+            raise ZLError("prefill_attention_varlen: one int64 K / V pointer per task")
+    if plan.tables.device != q.device:
+        raise ZLError("prefill_attention_varlen: the plan lives on another device")
+    if out is None:
+        out = torch.empty_like(q)
+    else:
+        _chk_out(out.view(total_q, -1), total_q, h * d, q.dtype, q.device, "prefill_attention_varlen")
+    groups = int(os.environ.get("ZL_PREFILL_GROUPS", "0") or 0) if groups is None else groups     # 0: the launcher's choice
+    check(lib().zl_prefill_attn_varlen(_p(q), _p(plan.cu_seqlens_q), _p(plan.pos0_dev), _p(plan.buf_lens_dev), _p(k_addrs),
+                                       _p(v_addrs), _p(out), _p(plan.work), _i(plan.n_work), _i(plan.b), _i(total_q), _i(h),
+                                       _i(num_kv_heads), _i(d), _f(scale), C.c_int(int(bshd)), C.c_int(_dt(q)), C.c_int(groups),
+                                       _stream()), "prefill_attn_varlen")
+    return out
+
+
 def element_add_scale(a, b, scale=1.0, scale_residual=True, out=None):
     """nn::element_add_scale_out (src/nn/block/block_kernel.cu:19-50)."""
     _chk_cuda(a, b)
