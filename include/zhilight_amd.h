@@ -135,6 +135,32 @@ int zl_w4a16_moe_down(const uint16_t* a, int64_t lda, const uint32_t* qw, const 
                       int world_size, int rank, int add_c, zl_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * f3b  Expert-grouped W4A16 GEMM (MOEImpl::forward above GPTQ_MOE_M_THRES rows, src/nn/feedforward/feedforward.cpp:698-790:
+ * one Int4GPTQ linear per active expert over its sorted rows, the M > 40 arithmetic of q_gemm_k_major.cu:1083-1100).
+ * ONE launch for every expert: the `pairs` sorted positions are grouped by expert, expert e owning the run of expert_loads[e]
+ * positions after those of experts 0..e-1 (expert_loads: device, num_experts int32, e.g. the router's expert_load); positions
+ * past the last run are not computed (pairs whose id lies outside the stack, sorted behind it, are dropped and never read).
+ * Position j reads x row index[j] / in_div (in_div = 0: row j) and writes y row j (out_scatter = 0) or index[j] (out_scatter = 1);
+ * x rows are clamped to [0, x_rows), y rows outside [0, y_rows) are not written.  Weights: ZLW4M (zl_w4m_pack) per expert,
+ * expert e at qw + e * expert_stride_qw / meta + e * expert_stride_meta BYTES.  y = half(x_row . W16_e^T), W16 = rn16(rn16(q - z) s),
+ * exact products, fp32 accumulation in zl_w4a16_gemm_tiled's k order (bit-identical to it on each expert's gathered rows);
+ * epilogue 0 or ZL_EPI_SILU_MUL / ZL_EPI_SILU_MUL_F32 (row-interleaved gate|up, n / 2 output columns).  K % 128 == 0; no host
+ * synchronisation: the grid is sized from zl_moe_grouped_tiles(pairs, num_experts, zl_moe_grouped_bm(pairs, num_experts)) and the
+ * per-expert tile table is derived on the device from expert_loads. */
+int zl_moe_grouped_bm(int64_t pairs, int64_t num_experts);
+int64_t zl_moe_grouped_tiles(int64_t pairs, int64_t num_experts, int64_t bm);
+int zl_w4a16_gemm_grouped(const uint16_t* x, int64_t ldx, int64_t x_rows, const uint32_t* qw, const uint32_t* meta,
+                          int64_t num_experts, int64_t expert_stride_qw, int64_t expert_stride_meta,
+                          const int32_t* expert_loads, const int32_t* index, int64_t pairs, int in_div, int out_scatter,
+                          uint16_t* y, int64_t y_rows, int64_t n, int64_t k, int64_t group_size, int epilogue, zl_stream_t s);
+/* The same GEMM in the small-M form (the driver's rows <= GPTQ_MOE_M_THRES): no sort and no work table -- pair j (< pairs <= 65535)
+ * multiplies x row j / in_div (in_div = 0: row j) with expert expert_ids[j]'s matrix (an id outside the stack: row j is not written)
+ * and writes y row j (y: pairs rows).  Each output is the sum of zl_w4a16_gemm_grouped's arithmetic and order: the same bits. */
+int zl_w4a16_gemm_pairs(const uint16_t* x, int64_t ldx, int64_t x_rows, const uint32_t* qw, const uint32_t* meta, int64_t num_experts,
+                        int64_t expert_stride_qw, int64_t expert_stride_meta, const int32_t* expert_ids, int64_t pairs, int in_div,
+                        uint16_t* y, int64_t n, int64_t k, int64_t group_size, int epilogue, zl_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * a2/a5  W4A16 GEMM for decode batches, y = x . dequant(W)^T (+ epilogue).
  * Replaces nn::gptq::gptq_gemm_k_major for M <= 40 / KERNEL_gemm_warp_reduce
  * (src/nn/quant/gptq/q_gemm_k_major.cu:957-1116, 127-237) and nn::gptq::gemm_fuse_gate_in (:765-829).

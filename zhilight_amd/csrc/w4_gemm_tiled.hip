@@ -16,6 +16,7 @@
 // ring of non-temporal buffer loads (4 chunks ahead).  Per chunk and wave: 2 x 52 VALU ops of dequant feed
 // 2 x 4 x (BM/16) MFMAs (v_mfma_f32_16x16x32_f16) on 2 x BM/16 independent accumulators.
 #include "zl_common.h"
+#include "zl_w4m_dequant.h"
 
 namespace {
 
@@ -25,9 +26,7 @@ constexpr int kBN = kWavesT * 32;
 constexpr int kRingT = 8;          // items (2 per chunk)
 constexpr int kRowHalfs = 128 + 8; // padded LDS row (an XOR-swizzled 256-B row image measured the same: 312 us)
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-typedef _Float16 hv2 __attribute__((ext_vector_type(2)));
 
 struct TiledParams {
     const uint16_t* x;
@@ -48,26 +47,6 @@ struct TiledParams {
     float* ws;
     int ld_ws;
 };
-
-__device__ __forceinline__ uint32_t and_or_t(uint32_t w, uint32_t mask_s, uint32_t magic_v) {
-    uint32_t r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(w), "s"(mask_s), "v"(magic_v));
-    return r;
-}
-
-// word -> 8 x fp16 rn16((q - z) * s): exact (q - z), one rounding in the multiply == dequant_k_major
-__device__ __forceinline__ h8 dequant_scaled(uint32_t w, hv2 z1, hv2 z16, hv2 s2, uint32_t mask_lo, uint32_t mask_hi,
-                                             uint32_t magic) {
-    const hv2 one16 = {(_Float16)0.0625f, (_Float16)0.0625f};
-    const hv2 d0 = (__builtin_bit_cast(hv2, and_or_t(w, mask_lo, magic)) + z1) * s2;
-    const hv2 d1 = __builtin_elementwise_fma(__builtin_bit_cast(hv2, and_or_t(w, mask_hi, magic)), one16, z16) * s2;
-    const uint32_t wb = w >> 8;
-    const hv2 d2 = (__builtin_bit_cast(hv2, and_or_t(wb, mask_lo, magic)) + z1) * s2;
-    const hv2 d3 = __builtin_elementwise_fma(__builtin_bit_cast(hv2, and_or_t(wb, mask_hi, magic)), one16, z16) * s2;
-    h8 a;
-    a[0] = d0.x; a[1] = d0.y; a[2] = d1.x; a[3] = d1.y; a[4] = d2.x; a[5] = d2.y; a[6] = d3.x; a[7] = d3.y;
-    return a;
-}
 
 __device__ __forceinline__ float silu_t(float x) { return x / (1.0f + expf(-x)); }
 
@@ -161,7 +140,7 @@ __global__ __launch_bounds__(kThreadsT, 2) void k_w4a16_gemm_tiled(const TiledPa
 #ifdef ZL_TEXP_NODEQ
             for (int t = 0; t < 4; ++t) bfr[j][t] = __builtin_bit_cast(h8, make_uint4(wds[t], mw, wds[(t + 1) & 3], magic));
 #else
-            for (int t = 0; t < 4; ++t) bfr[j][t] = dequant_scaled(wds[t], z1, z16, s2, mask_lo, mask_hi, magic);
+            for (int t = 0; t < 4; ++t) bfr[j][t] = zl_w4m_dequant8(wds[t], z1, z16, s2, mask_lo, mask_hi, magic);
 #endif
         }
         issue_pair(slot0);
@@ -431,8 +410,8 @@ __global__ __launch_bounds__(256, ZL_WIDE_OCC) void k_w4a16_gemm_wide(const Tile
     uint32_t bw[2][NT][4];
     auto dequant_half = [&](int set, int j, uint32_t w, int h) {
         const uint32_t ws = h ? (w >> 8) : w;
-        const hv2 lo = (__builtin_bit_cast(hv2, and_or_t(ws, mask_lo, magic)) + z1[j]) * s2[j];
-        const hv2 hi = __builtin_elementwise_fma(__builtin_bit_cast(hv2, and_or_t(ws, mask_hi, magic)), one16, z16[j]) * s2[j];
+        const hv2 lo = (__builtin_bit_cast(hv2, zl_w4m_and_or(ws, mask_lo, magic)) + z1[j]) * s2[j];
+        const hv2 hi = __builtin_elementwise_fma(__builtin_bit_cast(hv2, zl_w4m_and_or(ws, mask_hi, magic)), one16, z16[j]) * s2[j];
         bw[set][j][2 * h] = __builtin_bit_cast(uint32_t, lo);
         bw[set][j][2 * h + 1] = __builtin_bit_cast(uint32_t, hi);
     };

@@ -56,6 +56,18 @@ class ModelConfig:
     max_position_embeddings: int = 0        # dynamic-NTK rope threshold
     model_type: str = "llama"
     dtype: str = "half"                     # "half" | "bfloat16" (unquantised models; the W4 / int8 routes are fp16)
+    # mixture of experts (Qwen3-MoE: zhilight/config/qwen3_adapter.py; HF keys num_experts, num_experts_per_tok, ...); 0 experts = dense
+    moe_num_experts: int = 0
+    moe_top_k: int = 0
+    moe_intermediate_size: int = 0
+    norm_topk_prob: bool = False
+    decoder_sparse_step: int = 1            # layer i is sparse when (i + 1) % step == 0 and i is not in mlp_only_layers
+    mlp_only_layers: List[int] = field(default_factory=list)
+
+    def is_moe_layer(self, i: int) -> bool:
+        """Qwen3MoeDecoderLayer's rule: an MoE feed-forward unless the layer is listed as dense or off the sparse step"""
+        return (self.moe_num_experts > 0 and i not in self.mlp_only_layers and self.decoder_sparse_step > 0
+                and (i + 1) % self.decoder_sparse_step == 0)
 
     @property
     def torch_dtype(self):
@@ -82,7 +94,10 @@ class ModelConfig:
             qk_norm=("head" if cfg.get("model_type") in ("qwen3", "qwen3_moe") else
                      "multi_head" if cfg.get("use_qk_norm") else None),     # attention.cpp:110-117
             max_position_embeddings=cfg.get("max_position_embeddings", 0), model_type=cfg.get("model_type", "llama"),
-            dtype={"bfloat16": "bfloat16", "float16": "half"}.get(cfg.get("torch_dtype", "float16"), "half"))
+            dtype={"bfloat16": "bfloat16", "float16": "half"}.get(cfg.get("torch_dtype", "float16"), "half"),
+            moe_num_experts=int(cfg.get("num_experts", 0) or 0), moe_top_k=int(cfg.get("num_experts_per_tok", 0) or 0),
+            moe_intermediate_size=int(cfg.get("moe_intermediate_size", 0) or 0), norm_topk_prob=bool(cfg.get("norm_topk_prob", False)),
+            decoder_sparse_step=int(cfg.get("decoder_sparse_step", 1) or 1), mlp_only_layers=list(cfg.get("mlp_only_layers", []) or []))
 
     @classmethod
     def llama3_8b(cls):
@@ -137,6 +152,12 @@ def hf_name_to_internal(name: str) -> str:
     s = re.sub(r"model\.layers\.([0-9]+)\.self_attn\.([qkv])_proj\.", r"layers.\1.attn.project_\2.", s)
     s = re.sub(r"model\.layers\.([0-9]+)\.self_attn\.o_proj\.", r"layers.\1.attn.attn_out.", s)
     s = re.sub(r"model\.layers\.([0-9]+)\.self_attn\.([qk])_norm\.", r"layers.\1.attn.\2_norm.", s)
+    # MoE experts and router (loader.py:318-326); Qwen2-MoE's shared expert keeps a name of its own (refused at load)
+    s = re.sub(r"model\.layers\.([0-9]+)\.mlp\.experts\.([0-9]+)\.gate_proj\.", r"layers.\1.ff.experts.\2.w_in.", s)
+    s = re.sub(r"model\.layers\.([0-9]+)\.mlp\.experts\.([0-9]+)\.up_proj\.", r"layers.\1.ff.experts.\2.w_gated.", s)
+    s = re.sub(r"model\.layers\.([0-9]+)\.mlp\.experts\.([0-9]+)\.down_proj\.", r"layers.\1.ff.experts.\2.w_out.", s)
+    s = re.sub(r"model\.layers\.([0-9]+)\.mlp\.gate\.weight", r"layers.\1.ff.router.weight", s)
+    s = re.sub(r"model\.layers\.([0-9]+)\.mlp\.shared_expert(_gate)?\.", r"layers.\1.ff.shared_expert\2.", s)
     s = re.sub(r"model\.layers\.([0-9]+)\.mlp\.gate_proj\.", r"layers.\1.ff.w_in.", s)
     s = re.sub(r"model\.layers\.([0-9]+)\.mlp\.up_proj\.", r"layers.\1.ff.w_gated.", s)
     s = re.sub(r"model\.layers\.([0-9]+)\.mlp\.down_proj\.", r"layers.\1.ff.w_out.", s)
@@ -599,7 +620,8 @@ class EncoderLayer:
         # attn_out / w_out row-parallel: their partial outputs are summed over the ranks before the residual add
         self.tp = tp if tp is not None and tp.size > 1 else None
 
-    def load_state_dict(self, sd, prefix, device):
+    def load_state_dict(self, sd, prefix, device, ff=True):
+        """ff=False: the attention half and both norms only (MoEEncoderLayer loads its own feed-forward)"""
         c, q = self.cfg, self.quant
         hd = c.num_heads * c.dim_head
         kvd = c.num_kv_heads * c.dim_head
@@ -655,17 +677,20 @@ class EncoderLayer:
         kv_part = getattr(self, "kv_part", None)
         pq, pk, pv = (lin("attn.project_q", c.dim_model, hd, "column"), lin("attn.project_k", c.dim_model, kvd, "column", kv_part),
                       lin("attn.project_v", c.dim_model, kvd, "column", kv_part))
-        w_in = lin("ff.w_in", c.dim_model, c.dim_ff, "column", out_perm=ff_out_perm)
-        w_gated = lin("ff.w_gated", c.dim_model, c.dim_ff, "column", out_perm=ff_out_perm)
+        if ff:
+            w_in = lin("ff.w_in", c.dim_model, c.dim_ff, "column", out_perm=ff_out_perm)
+            w_gated = lin("ff.w_gated", c.dim_model, c.dim_ff, "column", out_perm=ff_out_perm)
         self.attn_out = lin("attn.attn_out", hd, c.dim_model, "row").pack()
-        self.w_out = lin("ff.w_out", c.dim_ff, c.dim_model, "row", prepermuted=ff_out_perm is not None).pack()
-        if not (Int4GPTQ.same_perm([pq, pk, pv]) and Int4GPTQ.same_perm([w_in, w_gated])):
+        if ff:
+            self.w_out = lin("ff.w_out", c.dim_ff, c.dim_model, "row", prepermuted=ff_out_perm is not None).pack()
+        if not (Int4GPTQ.same_perm([pq, pk, pv]) and (not ff or Int4GPTQ.same_perm([w_in, w_gated]))):
             # act-order with DIFFERENT input orders inside a group (not what GPTQ produces for linears sharing their input,
             # but a legal checkpoint): every linear gathers x itself, q/k/v and gate/up stay separate
-            self.unfused = [l.pack() for l in (pq, pk, pv, w_in, w_gated)]
+            self.unfused = [l.pack() for l in ((pq, pk, pv, w_in, w_gated) if ff else (pq, pk, pv))]
         else:
             self.qkv = Int4GPTQ.fuse(prefix + ".attn.project_qkv", [pq, pk, pv])
-            self.w_in_gated = Int4GPTQ.fuse(prefix + ".ff.w_in_gated", [w_in, w_gated], row_interleave=True)
+            if ff:
+                self.w_in_gated = Int4GPTQ.fuse(prefix + ".ff.w_in_gated", [w_in, w_gated], row_interleave=True)
 
     def init_random(self, device, gen):
         """Synthetic weights of the right shapes, generated directly in the packed layout."""
@@ -773,6 +798,115 @@ class EncoderLayer:
         return ops.gate_mul(gate, self.unfused[4].forward(xn), "silu")
 
 
+def moe_route():
+    """Which expert layout a layer holds (ZL_MOE_ROUTE, read at load).  A layer holds ONE copy of its expert weights:
+      "grouped" (default)  ZLW4M stacks.  Rows up to GPTQ_MOE_M_THRES (the reference's switch, feedforward.cpp:1248-1290) take the
+                           small-M form zl_w4a16_gemm_pairs (one tile per (token, expert) pair, no sort); above it the sorted
+                           zl_w4a16_gemm_grouped (one tile per BM rows of an expert).  Both: MOEImpl::forward's arithmetic (the
+                           M > 40 linears), the same bits for the same rows, sum_experts as the combine
+      "fused"              ZLW4 stacks; every row count through the fused GEMVs zl_w4a16_moe_up / _down -- the reference's
+                           FUSE_GPTQ_MOE kernels bit for bit, which stream an expert's weights once per (token, expert) pair"""
+    r = os.environ.get("ZL_MOE_ROUTE", "grouped").lower()
+    if r not in ("grouped", "fused"):
+        raise ops.ZLError(f"ZL_MOE_ROUTE={r!r}: expected 'grouped' or 'fused'")
+    return r
+
+
+_MOE_M_THRES_DEFAULT = "8"             # rows; the pair form measured faster up to 8 rows, the sorted form from 32 (DESIGN 5)
+
+
+class MoEEncoderLayer(EncoderLayer):
+    """EncoderLayer with a routed mixture-of-experts feed-forward (GPTQ experts, Qwen3-MoE; reference FeedForward with
+    FUSE_GPTQ_MOE, feedforward.cpp:1248-1290): the attention half is EncoderLayer's, ln_ff + router + experts replace w_in_gated /
+    w_out.  Not with tensor or expert parallelism, act-order or AWQ checkpoints, or shared experts (ZLError)."""
+
+    def __init__(self, cfg: ModelConfig, quant: QuantConfig, idx: int, tp=None):
+        if tp is not None and tp.size > 1:
+            raise ops.ZLError("MoE layers: tensor parallelism is not supported")
+        if os.environ.get("MOE_EXP_PARALLEL", "0") not in ("", "0"):
+            raise ops.ZLError("MoE layers: expert parallelism is not supported")
+        if quant.quant_type != 5 or quant.act_order or quant.awq:
+            raise ops.ZLError("MoE layers: GPTQ W4A16 experts without act-order only")
+        if quant.group_size % 128 or cfg.dim_model % 128 or cfg.moe_intermediate_size % 128:
+            raise ops.ZLError("MoE layers: group size, dim_model and moe_intermediate_size are multiples of 128")
+        if not (0 < cfg.moe_top_k <= min(32, cfg.moe_num_experts)):
+            raise ops.ZLError("MoE layers: 1 <= num_experts_per_tok <= min(32, num_experts)")
+        super().__init__(cfg, quant, idx, None)
+        self.route = moe_route()
+        # rows up to this take the pair form (GPTQ_MOE_M_THRES, read at load; default: the measured crossover, DESIGN 5)
+        self.m_thres = int(os.environ.get("GPTQ_MOE_M_THRES", _MOE_M_THRES_DEFAULT) or 0)
+        self.router = self.w_up = self.w_down = None
+
+    def load_state_dict(self, sd, prefix, device):
+        c, q = self.cfg, self.quant
+        if any(k.startswith(prefix + ".ff.shared_expert") for k in sd):
+            raise ops.ZLError(f"{prefix}: shared experts are not supported")
+        super().load_state_dict(sd, prefix, device, ff=False)      # ln_attn, ln_ff, fused q|k|v, attn_out
+
+        def lin(sub, din, dout):
+            l = Int4GPTQ(prefix + "." + sub, din, dout, q)
+            l.load_state_dict(sd, prefix + "." + sub, device)
+            return l
+        router = sd[prefix + ".ff.router.weight"]
+        if tuple(router.shape) != (c.moe_num_experts, c.dim_model):
+            raise ops.ZLError(f"{prefix}: router weight shape {tuple(router.shape)} != {(c.moe_num_experts, c.dim_model)}")
+        self.router = _dev_t(router, device).to(torch.float16).contiguous()
+        # every expert through Int4GPTQ's load transforms (shuffle, zero + 1, transposes), packed straight into ONE stack per
+        # projection: gate and up row-interleaved as (gate_n, up_n) pairs for the silu*mul epilogue
+        e, ff = c.moe_num_experts, c.moe_intermediate_size
+        stack = ops.W4MMoEWeight if self.route == "grouped" else ops.W4MoEWeight
+        up_parts, down_parts = ([], [], []), ([], [], [])
+        for i in range(e):
+            g, u = lin(f"ff.experts.{i}.w_in", c.dim_model, ff), lin(f"ff.experts.{i}.w_gated", c.dim_model, ff)
+            for j in range(3):
+                up_parts[j].append(torch.cat([g.km[j], u.km[j]]).contiguous())
+            d = lin(f"ff.experts.{i}.w_out", ff, c.dim_model)
+            for j in range(3):
+                down_parts[j].append(d.km[j])
+        self.w_up = stack.from_k_major(*up_parts, q.group_size, row_interleave=True)
+        self.w_down = stack.from_k_major(*down_parts, q.group_size)
+
+    def init_random(self, device, gen):
+        raise ops.ZLError("MoE layers: use LLaMA.init_synthetic (the real load path)")
+
+    def linears(self):
+        return [self.qkv, self.attn_out]
+
+    def weight_bytes(self):
+        return sum(l.weight.nbytes() for l in self.linears()) + self.w_up.nbytes() + self.w_down.nbytes() + self.router.numel() * 2
+
+    def moe(self, xn):
+        """the routed feed-forward of normalised rows xn (T, dim_model) fp16 -> (T, dim_model) fp16"""
+        c = self.cfg
+        t, e, k = xn.shape[0], c.moe_num_experts, c.moe_top_k
+        # MOEImpl::route (feedforward.cpp:419-482): fp32 router logits, softmax top-k (renormalised with norm_topk_prob)
+        logits = ops.gemm_nt_f32(xn, self.router)
+        loads = torch.zeros(e + 1, dtype=torch.int32, device=xn.device)       # tokens per expert | per worker (one)
+        weights, ids = ops.moe_top_k_softmax(logits, k, norm_topk_prob=c.norm_topk_prob, worker_load=loads[e:], expert_load=loads[:e])
+        self.last_route = (ids, weights)                                        # (tests: the routing the step took)
+        if self.route == "fused":
+            return ops.moe_down(ops.moe_up(xn, self.w_up, ids), self.w_down, ids, weights)
+        # grouped: the (token, slot) pairs sorted by expert on the device (stable), gate|up over the gathered tokens in sorted order,
+        # down scattered back to pair order, then the weighted combine -- deterministic: every output row sums its k slots in order
+        p = t * k
+        pair = ops.arange_i32(p, xn.device)
+        if t <= self.m_thres:
+            # a few rows: one tile per (token, slot) pair straight from the routing ids, pair order throughout
+            act = ops.moe_gemm_pairs(xn, self.w_up, ids, in_div=k, epilogue=ops.EPI_SILU_MUL)
+            return ops.moe_sum_experts(ops.moe_gemm_pairs(act, self.w_down, ids), pair, weights)
+        _, order = ops.sort_pairs_i32(ids.reshape(-1), pair, max_key=e)
+        act = ops.moe_gemm_grouped(xn, self.w_up, loads[:e], order, p, in_div=k, epilogue=ops.EPI_SILU_MUL)
+        down = ops.moe_gemm_grouped(act, self.w_down, loads[:e], order, p, out_scatter=True)
+        return ops.moe_sum_experts(down, pair, weights)
+
+    def ff_add(self, hidden, eps, act_buf=None):
+        """hidden += moe(ln_ff(hidden)) in place (the residual add in T arithmetic, block.cpp:123-140)"""
+        ops.element_add_scale(hidden, self.moe(ops.rmsnorm(hidden, self.ln_ff, eps)), 1.0, True, out=hidden)
+
+    def ff_in(self, hidden, eps, out=None, normed=None):
+        raise ops.ZLError("MoE layers have no gate|up projection of their own (ff_add runs the experts)")
+
+
 @dataclass
 class DynBatchContext:
     """Per-step device state of a decode batch (model::DynBatchContext s_token / s_position /
@@ -801,6 +935,7 @@ class DynBatchContext:
 
 class LLaMA:
     """model::LLaMA (src/model/llama.cpp:11-165) restricted to the dynamic-batch decode step."""
+    moe = False                 # any MoEEncoderLayer (set by __init__)
 
     def __init__(self, cfg: ModelConfig, quant: QuantConfig, device="cuda:0", tp=None):
         """tp: parallel.TPGroup (rank, size, process group) for tensor parallelism over the GPUs of a node -- W4 route
@@ -814,7 +949,17 @@ class LLaMA:
         layer_cls = {0: DenseEncoderLayer, 2: Int8EncoderLayer}.get(quant.quant_type, EncoderLayer)
         self.tp = tp if tp is not None and tp.size > 1 else None
         self.full_cfg = cfg
-        if self.tp:
+        self.moe = any(cfg.is_moe_layer(i) for i in range(cfg.num_layers))
+        if self.moe:
+            # MoE models: the W4 route without tensor / expert parallelism (MoEEncoderLayer refuses the rest); the dense layers a
+            # model lists in mlp_only_layers stay EncoderLayer
+            if self.tp:
+                raise ops.ZLError("MoE models: tensor parallelism is not supported")
+            if layer_cls is not EncoderLayer:
+                raise ops.ZLError("MoE models: GPTQ W4A16 checkpoints only")
+            self.layers = [MoEEncoderLayer(cfg, quant, i) if cfg.is_moe_layer(i) else EncoderLayer(cfg, quant, i)
+                           for i in range(cfg.num_layers)]
+        elif self.tp:
             if layer_cls is not EncoderLayer:
                 raise ops.ZLError("tensor parallelism is wired into the W4A16 layer stack only")
             t = self.tp.size
@@ -943,13 +1088,28 @@ class LLaMA:
             lin(sd, pfx + ".attn.project_k", c.dim_model, kvd)
             lin(sd, pfx + ".attn.project_v", c.dim_model, kvd)
             lin(sd, pfx + ".attn.attn_out", hd, c.dim_model)
-            lin(sd, pfx + ".ff.w_in", c.dim_model, c.dim_ff)
-            lin(sd, pfx + ".ff.w_gated", c.dim_model, c.dim_ff)
-            lin(sd, pfx + ".ff.w_out", c.dim_ff, c.dim_model)
+            if isinstance(layer, MoEEncoderLayer):
+                # the experts with the same recipe at their own shapes; router rows N(0,1) / sqrt(dim_model): logits O(1), so
+                # the top-k picks spread over the experts
+                for e in range(c.moe_num_experts):
+                    lin(sd, f"{pfx}.ff.experts.{e}.w_in", c.dim_model, c.moe_intermediate_size)
+                    lin(sd, f"{pfx}.ff.experts.{e}.w_gated", c.dim_model, c.moe_intermediate_size)
+                    lin(sd, f"{pfx}.ff.experts.{e}.w_out", c.moe_intermediate_size, c.dim_model)
+                sd[pfx + ".ff.router.weight"] = (torch.randn(c.moe_num_experts, c.dim_model, device=dev, generator=gen)
+                                                 / math.sqrt(c.dim_model)).to(torch.float16)
+            else:
+                lin(sd, pfx + ".ff.w_in", c.dim_model, c.dim_ff)
+                lin(sd, pfx + ".ff.w_gated", c.dim_model, c.dim_ff)
+                lin(sd, pfx + ".ff.w_out", c.dim_ff, c.dim_model)
+            if c.qk_norm == "head":
+                for n in ("q", "k"):
+                    sd[f"{pfx}.attn.{n}_norm.weight"] = (1 + 0.1 * torch.randn(c.dim_head, device=dev, generator=gen)).to(torch.float16)
             if sink is not None:
                 sink(sd)
             layer.load_state_dict(sd, pfx, dev)
             layer.q_norm = layer.k_norm = None
+            if c.qk_norm == "head":
+                layer.q_norm, layer.k_norm = (self._qk_norm_weight(sd[f"{pfx}.attn.{n}_norm.weight"], n) for n in ("q", "k"))
             del sd
         u8 = lambda: torch.randint(-127, 128, (c.vocab_size, c.dim_model), dtype=torch.int8, device=dev, generator=gen)
         self.token_embedding = (u8().to(dt) * (1.0 / 128)).contiguous()
@@ -1020,6 +1180,10 @@ class LLaMA:
         greedy bookkeeping), so that step time - this = the projections' time inside the step."""
         c = self.cfg
         b = ctx.tokens.numel()
+        if self.moe and (gemv_only or skip_gemv):
+            # the two legs split a step into "the four W4 projections" and the rest; an MoE layer's feed-forward is a router, a sort
+            # and two grouped launches, which belong to neither side
+            raise ops.ZLError("gemv_only / skip_gemv: dense models only")
         if ctx.steps_left <= 0 and not torch.cuda.is_current_stream_capturing():
             raise ops.ZLError("decode step past the end of the KV buffers (placement >= len_buf): grow the buffers first "
                               "(the reference asserts pos_buf < len_buf, ragged_buffer_kernel.cu:194-222)")
@@ -1085,8 +1249,9 @@ class LLaMA:
         # per row and 16-column tile the sum of squares of what they store, the normalising projections (qkv, gate|up) read those
         # 256 numbers per row instead of running -- or waiting for -- an RMSNorm pass over the rows: no stand-alone norm launch from
         # 9 rows on, no register-resident norm prologue below.  ZL_ROW_SS=0 off; ZL_ROW_SS_MIN_M: rows it starts at
+        # (not with MoE layers: their feed-forward has no w_out to produce the statistics nor a gate|up projection to consume them)
         stats = None
-        if (fuse_qkv_rope and la is not None and not self.tp and os.environ.get("ZL_ROW_SS", "1") != "0"
+        if (fuse_qkv_rope and la is not None and not self.tp and not self.moe and os.environ.get("ZL_ROW_SS", "1") != "0"
                 and int(os.environ.get("ZL_ROW_SS_MIN_M", "8")) <= b <= 32 and c.dim_model % 1024 == 0
                 and all(l.attn_out.perm is None and l.w_out.perm is None and l.w_in_gated.perm is None for l in self.layers)
                 and ops.w4_row_ss_routes(b, [self.layers[0].attn_out.weight, self.layers[0].w_out.weight],
@@ -1106,7 +1271,9 @@ class LLaMA:
                                                         c.num_kv_heads, valid_lens=ctx.valid_lens, out=out.view(b, 1, c.num_heads, c.dim_head),
                                                         workspace=workspace)
         # attention split merge + attn_out + residual and ln_ff + gate|up + silu.mul in ONE launch (w4_engine.hip)
-        fuse_o_ff = (merge_plan is not None and merge_plan[2] and os.environ.get("ZL_FUSE_O_GATEUP", "0") == "1" and ops.experimental_build()
+        # (off for MoE models: the fused launch ends in the dense gate|up projection)
+        fuse_o_ff = (merge_plan is not None and merge_plan[2] and not self.moe and os.environ.get("ZL_FUSE_O_GATEUP", "0") == "1"
+                     and ops.experimental_build()
                      and all(l.w_in_gated.perm is None and isinstance(l.w_in_gated.weight, ops.W4MWeight) for l in self.layers))
         if fuse_o_ff:
             ops.engine_epoch_advance(self.device)

@@ -242,6 +242,120 @@ def moe_down(a, w: W4MoEWeight, expert_ids, expert_weights, n_shared=0, exp_para
     return out
 
 
+class W4MMoEWeight:
+    """The experts of one MoE projection in the ZLW4M layout (what zl_w4a16_gemm_grouped reads), stacked: expert e's words at
+    qw[e], its meta at meta[e].  gate / up: the (2 n_ff, K) [gate; up] k-major tensors of every expert with row_interleave=True."""
+
+    def __init__(self, experts, n, k, group_size, qw, meta, row_interleave):
+        self.experts, self.n, self.k, self.group_size = experts, n, k, group_size
+        self.qw, self.meta, self.row_interleave = qw, meta, row_interleave
+        L = W4MWeight.layout(n, k, group_size)
+        self.stride_bytes = (L.qw_bytes, L.scales_bytes)
+
+    @classmethod
+    def from_k_major(cls, qweights, qzeros, scales, group_size, row_interleave=False):
+        """lists (one entry per expert) of qweight (N, K/8) int32, qzeros (N, K/G) uint8, scales (N, K/G) fp16; packed into
+        the stack one expert at a time (no second copy of the stack)"""
+        e = len(qweights)
+        n, k = qweights[0].shape[0], qweights[0].shape[1] * 8
+        L = W4MWeight.layout(n, k, group_size)
+        dev = qweights[0].device
+        qw = torch.empty((e, L.qw_bytes // 4), dtype=torch.int32, device=dev)
+        meta = torch.empty((e, L.scales_bytes // 4), dtype=torch.int32, device=dev)
+        for i, (q, z, s) in enumerate(zip(qweights, qzeros, scales)):
+            _chk_cuda(q, z, s)
+            if q.shape != (n, k // 8):
+                raise ZLError("W4MMoEWeight: every expert has the same shape")
+            check(lib().zl_w4m_pack(_p(q), _p(z), _p(s), _i(n), _i(k), _i(group_size), C.c_int(int(row_interleave)), _p(qw[i]),
+                                    _p(meta[i]), _stream()), "w4m_pack")
+        return cls(e, n, k, group_size, qw, meta, row_interleave)
+
+    def expert(self, e):
+        """expert e as a W4MWeight (a view: tests, per-expert references)"""
+        return W4MWeight(self.n, self.k, self.group_size, self.qw[e], self.meta[e], self.row_interleave)
+
+    def nbytes(self):
+        return self.qw.numel() * 4 + self.meta.numel() * 4
+
+
+def moe_grouped_slots(pairs, num_experts):
+    """(M-tile rows, grid slots) of a zl_w4a16_gemm_grouped launch over `pairs` sorted rows: the host half of the work table,
+    sizes only -- sum over experts of ceil(load / BM) <= pairs // BM + min(E, pairs)"""
+    if pairs <= 0:
+        return 16, 0
+    a = min(pairs, num_experts)
+    avg = (pairs + a - 1) // a
+    bm = 16 if avg <= 16 else 32 if avg <= 32 else 64 if avg < 128 else 128
+    return bm, pairs // bm + a
+
+
+def moe_gemm_grouped(x, w: W4MMoEWeight, expert_loads, index, pairs, in_div=0, out_scatter=False, out=None, out_rows=None,
+                     epilogue=0):
+    """zl_w4a16_gemm_grouped: the W4A16 GEMM of every expert over its sorted rows in one launch.  Sorted position j (< pairs)
+    reads x row index[j] // in_div (in_div = 0: row j) and writes out row j (out_scatter: row index[j]); expert e owns the
+    expert_loads[e] positions after those of experts < e.  out: (out_rows or pairs, n) -- n / 2 columns with EPI_SILU_MUL."""
+    if x.dtype != torch.float16 or x.dim() != 2:
+        raise ZLError("moe_gemm_grouped: (rows, K) half activations")
+    _chk_cuda(x, expert_loads, index)
+    if x.shape[1] != w.k or x.stride(1) != 1:
+        raise ZLError("moe_gemm_grouped: size K mismatch")
+    if expert_loads.dtype != torch.int32 or expert_loads.numel() != w.experts:
+        raise ZLError("moe_gemm_grouped: expert_loads is one int32 per expert of the stack")
+    if index is not None and (index.dtype != torch.int32 or index.numel() < pairs):
+        raise ZLError("moe_gemm_grouped: index holds pairs int32")
+    if index is None and (in_div or out_scatter):
+        raise ZLError("moe_gemm_grouped: gathering or scattering rows needs the index")
+    if epilogue not in (0, EPI_SILU_MUL, EPI_SILU_MUL_F32) or (epilogue and not w.row_interleave):
+        raise ZLError("moe_gemm_grouped: epilogue 0, or the silu*mul of a row-interleaved gate|up stack")
+    if w.group_size % 128 or w.k % 128:
+        raise ZLError("moe_gemm_grouped: K and the group size are multiples of 128")
+    n_out = w.n // 2 if epilogue else w.n
+    rows = out_rows if out_rows is not None else pairs
+    if out is None:
+        out = torch.empty((rows, n_out), dtype=torch.float16, device=x.device)
+    else:
+        _chk_out(out, rows, n_out, torch.float16, x.device, "moe_gemm_grouped")
+    if pairs == 0:
+        return out
+    sq, sm = w.stride_bytes
+    check(lib().zl_w4a16_gemm_grouped(_p(x), _i(x.stride(0)), _i(x.shape[0]), _p(w.qw), _p(w.meta), _i(w.experts), _i(sq), _i(sm),
+                                      _p(expert_loads), _p(index), _i(pairs), C.c_int(int(in_div)), C.c_int(int(bool(out_scatter))),
+                                      _p(out), _i(rows), _i(w.n), _i(w.k), _i(w.group_size), C.c_int(epilogue), _stream()),
+          "w4a16_gemm_grouped")
+    return out
+
+
+def moe_gemm_pairs(x, w: W4MMoEWeight, expert_ids, in_div=0, out=None, epilogue=0):
+    """zl_w4a16_gemm_pairs, the small-M form of moe_gemm_grouped: pair j of expert_ids (any shape, flattened) multiplies x row
+    j // in_div (in_div = 0: row j) with its expert's matrix -> out row j; the same bits as the sorted form for the same row"""
+    if x.dtype != torch.float16 or x.dim() != 2:
+        raise ZLError("moe_gemm_pairs: (rows, K) half activations")
+    _chk_cuda(x, expert_ids)
+    if x.shape[1] != w.k or x.stride(1) != 1:
+        raise ZLError("moe_gemm_pairs: size K mismatch")
+    if expert_ids.dtype != torch.int32:
+        raise ZLError("moe_gemm_pairs: int32 expert ids")
+    if epilogue not in (0, EPI_SILU_MUL, EPI_SILU_MUL_F32) or (epilogue and not w.row_interleave):
+        raise ZLError("moe_gemm_pairs: epilogue 0, or the silu*mul of a row-interleaved gate|up stack")
+    if w.group_size % 128 or w.k % 128:
+        raise ZLError("moe_gemm_pairs: K and the group size are multiples of 128")
+    p = expert_ids.numel()
+    if p > 65535:
+        raise ZLError("moe_gemm_pairs: at most 65535 pairs")
+    n_out = w.n // 2 if epilogue else w.n
+    if out is None:
+        out = torch.empty((p, n_out), dtype=torch.float16, device=x.device)
+    else:
+        _chk_out(out, p, n_out, torch.float16, x.device, "moe_gemm_pairs")
+    if p == 0:
+        return out
+    sq, sm = w.stride_bytes
+    check(lib().zl_w4a16_gemm_pairs(_p(x), _i(x.stride(0)), _i(x.shape[0]), _p(w.qw), _p(w.meta), _i(w.experts), _i(sq), _i(sm),
+                                    _p(expert_ids), _i(p), C.c_int(int(in_div)), _p(out), _i(w.n), _i(w.k), _i(w.group_size),
+                                    C.c_int(epilogue), _stream()), "w4a16_gemm_pairs")
+    return out
+
+
 def w4a16_gemm(x, w, bias=None, residual=None, out=None, norm_weight=None, norm_eps=1e-5, epilogue=0):
     """y = x . dequant(W)^T with optional fused RMSNorm prologue and bias / ADD_C / residual / silu*mul
     epilogue -- nn::gptq::gptq_gemm_k_major (M <= 40 branch) and nn::gptq::gemm_fuse_gate_in
