@@ -701,6 +701,27 @@ int zl_prefill_attn_varlen(const uint16_t* q, const int32_t* cu_seqlens_q, const
                            const uint16_t* const* k_bufs, const uint16_t* const* v_bufs, uint16_t* out,
                            const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
                            int64_t d, float scale, int bshd, int dtype, int groups, zl_stream_t s);
+/* zl_prefill_attn_varlen on an INT8 K/V cache, for chunks that CONTINUE cached rows: the history is dequantised inside the kernel,
+ * where a K / V tile passes through registers on its way to LDS.  Replaces the reference's fall-back branch for a quantised buffer
+ * whose prompt temporaries are gone (attention.cpp:510-516 "de-quantize prompt kv cache": TransformerBuffer::copy(need_dequant)
+ * -> int8_op::dequant_group into a fresh fp16 buffer, the chunk's rows appended, then flash attention): the same values, without
+ * the buffer.  Key / value row j of task i is
+ *   j <  pos0[i]   rn_T((float(code) - 128) * scale[j, kv head]) from k_codes[i] / v_codes[i] (buf_lens[i], Hkv, D) u8 and
+ *                  k_scales[i] / v_scales[i] (buf_lens[i], Hkv) fp32 -- bit for bit what zl_dequant_group(q_zero = 128) writes
+ *   j >= pos0[i]   row j - pos0[i] of the task's slice of k_new / v_new (total_q, Hkv, D), unquantised, rows laid out as q's; the
+ *                  cache is never read at or beyond pos0[i]
+ * and everything after that is zl_prefill_attn_varlen: same tiles, `groups`, softmax, P rounding and merge, so the output equals
+ * that launch on the dequantised buffers bit for bit.  BSHD only (the reference asserts it for a quantised buffer,
+ * attention.cpp:495); D = 128; fp16 / bf16.  A task with pos0[i] = 0 has no history: its four cache pointers may be null.  A wrong
+ * table, pos0, cu_seqlens_q or buf_lens never makes the kernel read or write outside the operands (items outside the tasks are
+ * dropped, keys are clamped to buf_lens[i], own rows to the task's slice).  No allocation, no sync.  ZL_EINVAL: null operand,
+ * b / total_q / n_work <= 0; ZL_ESHAPE: d != 128, h % hkv; ZL_EDTYPE: not fp16 / bf16; ZL_ELIMIT: grid overflow. */
+int zl_prefill_attn_varlen_q8(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                              const uint8_t* const* k_codes, const uint8_t* const* v_codes,
+                              const float* const* k_scales, const float* const* v_scales,
+                              const uint16_t* k_new, const uint16_t* v_new, uint16_t* out,
+                              const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
+                              int64_t d, float scale, int dtype, int groups, zl_stream_t s);
 
 
 /* ------------------------------------------------------------------------------------------------

@@ -27,6 +27,14 @@
 // the operand addressing differ: a workgroup looks up its (task, tile) in the caller's longest-first table and its task's rows, pos0,
 // buffer length and K / V pointers in device tables; the per-tile arithmetic is the one above, so a task's rows are bit-identical to
 // the one-task launch, which is this kernel with the map computed from the query tile count.
+//
+// Quantised history (Q8, zl_prefill_attn_varlen_q8): chunks that continue rows of the INT8 K/V cache.  The reference dequantises the
+// task's cached rows into a fresh fp16 buffer, appends the chunk's rows and runs flash attention on that (attention.cpp:510-516,
+// TransformerBuffer::copy(need_dequant), int8_op::dequant_group).  Here only the staging differs: a key row below the task's pos0 is
+// loaded as codes + its one scale (8 bytes per 8-element chunk; the registers that ride one tile ahead carry the CODES) and turned
+// into rn_T((code - 128) * scale) where the tile is written to LDS; a row from pos0 on comes unquantised from the call's own k / v
+// rows.  The choice is per row, so a tile may straddle pos0; what reaches LDS is bit for bit what the two-step form would have
+// loaded, and everything behind the staging is the code above.  The flag is compile-time: the other instantiations do not change.
 #include <stdlib.h>
 #include "zl_common.h"
 
@@ -57,6 +65,13 @@ struct PrefillParams {
     const uint16_t* const* k_bufs;
     const uint16_t* const* v_bufs;
     int n_work, b, total_q;
+    // Q8 (varlen only): rows below a task's pos0 come from its INT8 cache, rows from pos0 on from k_new / v_new (k / v above unused)
+    const uint8_t* const* k_codes;  // per task (len_buf, hkv, D) u8
+    const uint8_t* const* v_codes;
+    const float* const* k_scales;   // per task (len_buf, hkv) fp32
+    const float* const* v_scales;
+    const uint16_t* k_new;          // (total_q, hkv, D), rows as q's
+    const uint16_t* v_new;
 };
 
 template <int DT>
@@ -68,10 +83,31 @@ __device__ __forceinline__ f4 pf_mfma(uint4 a, uint4 b, f4 c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
 }
 
+// 8 cache codes -> 8 values of T, rn_T((code - 128) * sc) with the fp32 product rounded first (zl_dequant_group's two roundings):
+// fma(code, sc, -128 sc) rounds the same exact value once (128 sc is exact), and float(byte n of a word) is one instruction.  bf16
+// pairs are rounded by v_cvt_pk_bf16_f32 (nearest even, ZT<ZL_BF16>::from_f32's bits for every finite value at a tenth of its
+// instructions); the fp16 rounding stays behind ZT's barrier against a fused single rounding
+template <int DT>
+__device__ __forceinline__ uint4 pf_deq8(uint32_t lo, uint32_t hi, float sc) {
+    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const float off = -128.f * sc;
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t c = i < 2 ? lo : hi;
+        const float a = __builtin_fmaf((float)((c >> (16 * (i & 1))) & 0xffu), sc, off);
+        const float b = __builtin_fmaf((float)((c >> (16 * (i & 1) + 8)) & 0xffu), sc, off);
+        if constexpr (DT == ZL_F16) w[i] = (uint32_t)ZT<DT>::from_f32(a) | ((uint32_t)ZT<DT>::from_f32(b) << 16);
+        else w[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){a, b}, bf2));
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // DT = ZL_F16 / ZL_BF16: probabilities are rounded to T for the P.V product (flash-attention arithmetic)
 constexpr int kGroupLds = (kBK * kKRow + kBK * kVRow) * 2;     // one group's K + V tile: 35 840 bytes (>= its 32.5 KB merge record)
 
-template <int DT, int G>
+template <int DT, int G, bool Q8 = false>
 __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const PrefillParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_pf[];
     const int group = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));     // 4 waves each
@@ -95,7 +131,11 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
     const uint16_t* vb = p.v;
     uint16_t* ob = p.out;
     int s_q = p.s_q, pos0 = p.pos0, len_buf = p.len_buf;
-    if (p.work) {
+    const uint8_t* kcod = nullptr;                        // Q8: the task's cache (history rows only)
+    const uint8_t* vcod = nullptr;
+    const float* ksc = nullptr;
+    const float* vsc = nullptr;
+    if (Q8 || p.work) {
         // varlen: the caller's table lists the (task, query tile) items longest first, so item order is LPT order across the tasks as
         // it is within one task above.  A wrong table cannot make the workgroup read or write outside the operands: an item outside
         // the tasks or past its task's rows is dropped, the rows are clamped to total_q and the keys to the buffer's length
@@ -107,8 +147,17 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
         s_q = qe - qa;
         pos0 = max(p.pos0s[task], 0);
         len_buf = p.buf_lens[task];
-        kb = p.k_bufs[task];
-        vb = p.v_bufs[task];
+        if constexpr (Q8) {
+            // own rows: the task's slice of k_new / v_new (key j -> row j - pos0 <= the block's last query row < s_q)
+            kb = p.k_new + (size_t)qa * p.hkv * kD;
+            vb = p.v_new + (size_t)qa * p.hkv * kD;
+            kcod = p.k_codes[task]; vcod = p.v_codes[task];
+            ksc = p.k_scales[task]; vsc = p.v_scales[task];
+            if (pos0 > 0 && (!kcod || !vcod || !ksc || !vsc)) return;    // a task without history may leave them null
+        } else {
+            kb = p.k_bufs[task];
+            vb = p.v_bufs[task];
+        }
         if (qt * kBQ >= s_q || len_buf <= 0 || !kb || !vb) return;       // workgroup-uniform: before any barrier
         qb += (size_t)qa * p.h * kD;
         ob += (size_t)qa * p.h * kD;
@@ -152,15 +201,36 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
     kr##c_ = *reinterpret_cast<const uint4*>((kp_) + (sdch + 4 * c_) * 8);                               \
     vr##c_ = *reinterpret_cast<const uint4*>((vp_) + (sdch + 4 * c_) * 8);                               \
     if (dead_) vr##c_ = make_uint4(0, 0, 0, 0);           /* finite: its probability is exactly 0 */
+// Q8: a row below pos0 is loaded as 8 code bytes per chunk (.x, .y) and the row's scale (.z of chunk 0); hq bit 0 / 1 says that
+// kr / vr hold codes.  A dead key's V is zero in T, not codes.  Own row j sits at row j - pos0 of the task's k_new / v_new slice
+#define ZL_PF_LOADQ1(c_, kp_, vp_)                                                                         \
+    { const uint2 kc2_ = *reinterpret_cast<const uint2*>((kp_) + (sdch + 4 * c_) * 8);                     \
+      const uint2 vc2_ = *reinterpret_cast<const uint2*>((vp_) + (sdch + 4 * c_) * 8);                     \
+      kr##c_.x = kc2_.x; kr##c_.y = kc2_.y; vr##c_.x = vc2_.x; vr##c_.y = vc2_.y; }
 #define ZL_PF_LOAD(tile_)                                                                                  \
     {                                                                                                      \
         const int kg_ = (tile_) * kBK + skey;                                                              \
         const int kc_ = kg_ < n_keys ? kg_ : n_keys - 1;                                                   \
-        const uint16_t* kp_ = kb + kv_off + (size_t)kc_ * kv_stride;                                       \
-        const uint16_t* vp_ = vb + kv_off + (size_t)kc_ * kv_stride;                                       \
         const bool dead_ = kg_ >= n_keys;                                                                  \
-        ZL_PF_LOAD1(0, kp_, vp_, dead_) ZL_PF_LOAD1(1, kp_, vp_, dead_) ZL_PF_LOAD1(2, kp_, vp_, dead_) ZL_PF_LOAD1(3, kp_, vp_, dead_) \
+        if (Q8 && kc_ < pos0) {                                                                            \
+            const size_t row_ = (size_t)kc_ * p.hkv + hk;                                                  \
+            const uint8_t* kp_ = kcod + row_ * kD;                                                         \
+            const uint8_t* vp_ = vcod + row_ * kD;                                                         \
+            ZL_PF_LOADQ1(0, kp_, vp_) ZL_PF_LOADQ1(1, kp_, vp_) ZL_PF_LOADQ1(2, kp_, vp_) ZL_PF_LOADQ1(3, kp_, vp_) \
+            kr0.z = __builtin_bit_cast(uint32_t, ksc[row_]);                                               \
+            vr0.z = __builtin_bit_cast(uint32_t, vsc[row_]);                                               \
+            hq = dead_ ? 1 : 3;                                                                            \
+            if (dead_) { vr0 = vr1 = vr2 = vr3 = make_uint4(0, 0, 0, 0); }                                 \
+        } else {                                                                                           \
+            const size_t ro_ = Q8 ? (size_t)(kc_ - pos0) * kv_stride : (size_t)kc_ * kv_stride;            \
+            const uint16_t* kp_ = kb + kv_off + ro_;                                                       \
+            const uint16_t* vp_ = vb + kv_off + ro_;                                                       \
+            ZL_PF_LOAD1(0, kp_, vp_, dead_) ZL_PF_LOAD1(1, kp_, vp_, dead_) ZL_PF_LOAD1(2, kp_, vp_, dead_) ZL_PF_LOAD1(3, kp_, vp_, dead_) \
+            hq = 0;                                                                                        \
+        }                                                                                                  \
     }
+    int hq = 0;
+    if constexpr (Q8) { kr0 = kr1 = kr2 = kr3 = vr0 = vr1 = vr2 = vr3 = make_uint4(0, 0, 0, 0); }
     ZL_PF_LOAD(group)
 
     // group g walks the tiles g, g + G, ...; the barriers are the workgroup's, so every group runs the same number of rounds
@@ -168,6 +238,23 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
     for (int tile = group; tile - group < n_tiles; tile += G) {
         const int key0 = tile * kBK;
         const bool live = tile < n_tiles;                 // group-uniform
+        if constexpr (Q8) {
+            // codes -> T in place, before the barrier: the other waves' last MFMAs of the previous tile cover it (chunk 0 last: it holds
+            // the scales).  Converting inside the P.V loop instead, one chunk after every second matrix product so that the vector
+            // unit works in the matrix core's shadow, gave WRONG values on the GPU, differently from run to run (one output in 3 M
+            // with one group; every tenth where the 128-register variants spill): withdrawn, cause not found ("Prompts
+            // that continue the INT8 cache")
+            if (live && (hq & 1)) {
+                const float sc = __builtin_bit_cast(float, kr0.z);
+                kr3 = pf_deq8<DT>(kr3.x, kr3.y, sc); kr2 = pf_deq8<DT>(kr2.x, kr2.y, sc);
+                kr1 = pf_deq8<DT>(kr1.x, kr1.y, sc); kr0 = pf_deq8<DT>(kr0.x, kr0.y, sc);
+            }
+            if (live && (hq & 2)) {
+                const float sc = __builtin_bit_cast(float, vr0.z);
+                vr3 = pf_deq8<DT>(vr3.x, vr3.y, sc); vr2 = pf_deq8<DT>(vr2.x, vr2.y, sc);
+                vr1 = pf_deq8<DT>(vr1.x, vr1.y, sc); vr0 = pf_deq8<DT>(vr0.x, vr0.y, sc);
+            }
+        }
         __syncthreads();                                  // previous tile fully consumed
 #define ZL_PF_ST(c_)                                                                                       \
         *reinterpret_cast<uint4*>(&ks[skey * kKRow + (sdch + 4 * c_) * 8]) = kr##c_;                       \
@@ -275,6 +362,7 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
     }
 
 #undef ZL_PF_LOAD
+#undef ZL_PF_LOADQ1
 #undef ZL_PF_LOAD1
     // ---- the groups meet: groups 1 .. G - 1 park (O, m, l) in their own tile area, group 0 folds them in with the usual
     //      rescale (scores live in the log2 domain: exp2).  l is still the lane's partial sum; the lanes of a query share m.
@@ -342,19 +430,20 @@ extern "C" int zl_prefill_attn(const uint16_t* q, const uint16_t* k_buf, const u
     return zl_prefill_attn_ex(q, k_buf, v_buf, out, s_q, pos0, h, hkv, d, scale, len_buf, bshd, dtype, 0, s);
 }
 
-template <int DT, int G>
+template <int DT, int G, bool Q8 = false>
 static int launch_prefill(const PrefillParams& p, dim3 grid, hipStream_t hs) {
     const size_t lds = (size_t)G * kGroupLds + (size_t)4 * G * 16 * sizeof(float);       // tiles + one 64-byte strip per wave
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prefill_attn<DT, G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prefill_attn<DT, G, Q8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return ZL_ELIMIT;
     }
-    hipLaunchKernelGGL((k_prefill_attn<DT, G>), grid, dim3(256 * G), lds, hs, p);
+    hipLaunchKernelGGL((k_prefill_attn<DT, G, Q8>), grid, dim3(256 * G), lds, hs, p);
     return zl_launch_status();
 }
 
 // the launch of either form: `groups` wave groups per workgroup (1 / 2 / 4: the key tiles of a query tile are dealt to them
 // round-robin; 0 = the launcher's choice), one workgroup per (work item, head)
+template <bool Q8 = false>
 static int dispatch_prefill(PrefillParams& p, int64_t items, int dtype, int groups, bool plain_map, hipStream_t hs) {
     ZL_CHECK_ARG(items * p.h < ((int64_t)1 << 31), ZL_ELIMIT);
     const dim3 grid((unsigned)(items * p.h));
@@ -366,7 +455,7 @@ static int dispatch_prefill(PrefillParams& p, int64_t items, int dtype, int grou
     const int total = (int)(items * p.h);
     p.pair = (groups == 1 && total % 2 == 0 && total <= 2 * cus) ? 1 : 0;
     if (plain_map) p.pair = 2;
-#define ZL_PF_G(GG) return dtype == ZL_F16 ? launch_prefill<ZL_F16, GG>(p, grid, hs) : launch_prefill<ZL_BF16, GG>(p, grid, hs);
+#define ZL_PF_G(GG) return dtype == ZL_F16 ? launch_prefill<ZL_F16, GG, Q8>(p, grid, hs) : launch_prefill<ZL_BF16, GG, Q8>(p, grid, hs);
     switch (groups) {
         case 1: ZL_PF_G(1)
         case 2: ZL_PF_G(2)
@@ -413,4 +502,28 @@ extern "C" int zl_prefill_attn_varlen(const uint16_t* q, const int32_t* cu_seqle
     p.work = work; p.cu_q = cu_seqlens_q; p.pos0s = pos0; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs;
     p.n_work = (int)n_work; p.b = (int)b; p.total_q = (int)total_q;
     return dispatch_prefill(p, n_work, dtype, groups, false, (hipStream_t)s);
+}
+
+// the varlen launch on an INT8 cache: rows below pos0[i] are dequantised where they are staged, rows from pos0[i] on are read from
+// k_new / v_new (the header has the layouts).  Same work table, same `groups`, same per-tile arithmetic as zl_prefill_attn_varlen
+extern "C" int zl_prefill_attn_varlen_q8(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                                         const uint8_t* const* k_codes, const uint8_t* const* v_codes,
+                                         const float* const* k_scales, const float* const* v_scales,
+                                         const uint16_t* k_new, const uint16_t* v_new, uint16_t* out,
+                                         const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
+                                         int64_t d, float scale, int dtype, int groups, zl_stream_t s) {
+    ZL_CHECK_ARG(q && cu_seqlens_q && pos0 && buf_lens && k_codes && v_codes && k_scales && v_scales && k_new && v_new && out && work,
+                 ZL_EINVAL);
+    ZL_CHECK_ARG(b > 0 && total_q > 0 && n_work > 0 && h > 0 && hkv > 0, ZL_EINVAL);
+    ZL_CHECK_ARG(d == kD && h % hkv == 0, ZL_ESHAPE);
+    ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
+    ZL_CHECK_ARG(groups == 0 || groups == 1 || groups == 2 || groups == 4, ZL_EINVAL);
+    ZL_CHECK_ARG(h <= 65535 && b < ((int64_t)1 << 30) && total_q < ((int64_t)1 << 31) && n_work < ((int64_t)1 << 31), ZL_ELIMIT);
+    PrefillParams p = {};
+    p.q = q; p.out = out;
+    p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv); p.bshd = 1; p.scale = scale;
+    p.work = work; p.cu_q = cu_seqlens_q; p.pos0s = pos0; p.buf_lens = buf_lens;
+    p.k_codes = k_codes; p.v_codes = v_codes; p.k_scales = k_scales; p.v_scales = v_scales; p.k_new = k_new; p.v_new = v_new;
+    p.n_work = (int)n_work; p.b = (int)b; p.total_q = (int)total_q;
+    return dispatch_prefill<true>(p, n_work, dtype, groups, false, (hipStream_t)s);
 }

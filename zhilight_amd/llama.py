@@ -1433,14 +1433,29 @@ class LLaMA:
             self._bufs[key] = (mask, ws)
         return self._bufs[key]
 
-    def prefill(self, ctx: DynBatchContext, task: int, prompt: torch.Tensor, chunk: int = 0):
+    def prefill(self, ctx: DynBatchContext, task: int, prompt: torch.Tensor, chunk: int = 0, kv_history=None):
         """Prompt encode, optionally in chunks of `chunk` tokens (the reference's chunked prefill,
         src/generator/batch_generator.cpp:1048-1084: a long prompt enters the batch piece by piece, each piece
-        attending to the KV of the pieces before it)."""
+        attending to the KV of the pieces before it).
+        kv_history (INT8 KV cache only; an fp16 cache has one route and ignores it) chooses what a later piece reads for the
+        pieces before it:
+          None      the reference's preferred branch (attention.cpp:497-509): the prompt's UNquantised K/V rows, kept for every
+                    layer in a temporary (layers, 2, S, Hkv, D) buffer for the duration of the call;
+          "cache"   the reference's fall-back (attention.cpp:510-516, "de-quantize prompt kv cache"): the cache itself, dequantised
+                    inside the attention kernel (ops.prefill_attention_varlen_q8) -- no temporary of any kind.  Earlier pieces
+                    are seen through their codes, so the logits differ from the default route's by the cache's quantisation
+                    noise; the cache contents differ accordingly from the second piece on."""
+        self._check_kv_history(ctx, kv_history)
         s = int(prompt.numel())
         if chunk <= 0 or chunk >= s:
             return self._encode_prompt(ctx, task, prompt, 0)
         logits = None
+        if ctx.kv_quant and kv_history == "cache":
+            if s + 1 > ctx.max_len_buf:
+                raise ops.ZLError("prompt does not fit the task's KV buffer")
+            for p0 in range(0, s, chunk):
+                logits = self._prefill_rows(ctx, [task], [prompt[p0:p0 + chunk]], [p0], q8_history=True)
+            return logits
         if ctx.kv_quant:
             # INT8 KV cache: the prompt keeps attending to its UNquantised K/V rows across the chunks, held in temporary
             # buffers for the duration of the prompt (dyn_batch->unquant_key_buf, attention.cpp:497-510) while the codes go
@@ -1454,6 +1469,14 @@ class LLaMA:
         finally:
             ctx.unquant_kv.pop(task, None)
         return logits
+
+    def _check_kv_history(self, ctx: DynBatchContext, kv_history):
+        """the kv_history keyword of prefill / prefill_batch: None or "cache"; "cache" on an INT8 context needs head size 128 (the
+        mask-form attention of other head sizes reads a chunk's own rows as codes: another result).  Raises before any launch."""
+        if kv_history not in (None, "cache"):
+            raise ops.ZLError(f"kv_history: None or 'cache', not {kv_history!r}")
+        if kv_history == "cache" and ctx.kv_quant and self.cfg.dim_head != 128:
+            raise ops.ZLError("kv_history='cache' on an INT8 KV cache needs head size 128")
 
     def _encode_prompt(self, ctx: DynBatchContext, task: int, prompt: torch.Tensor, pos0: int):
         """LLaMA::encode's switch (src/model/llama.cpp:102-110): with DUAL_STREAM=1, more than one TP rank and more
@@ -1542,18 +1565,25 @@ class LLaMA:
         ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - (pos0 + s))
         return logits
 
-    def prefill_batch(self, ctx: DynBatchContext, tasks, prompts, pos0=None):
+    def prefill_batch(self, ctx: DynBatchContext, tasks, prompts, pos0=None, kv_history=None):
         """Prompt encode of several tasks in ONE pass through the layers (LLaMA::encode with the prompt rows of every task of the
         step in each linear, src/model/llama.cpp:75-165; attention as one varlen launch where attn_encode_group loops over the
         tasks, src/nn/attention/attention.cpp:442-562).  prompts[j] (1-D int tensor, lengths may differ) goes to the distinct
         task tasks[j]; pos0[j] (default 0) > 0 continues a prompt whose rows 0 .. pos0[j] - 1 are already in the task's buffers.
         Returns the logits of each task's last prompt row (len(tasks), vocab) and leaves every task as prefill() does: the greedy
         first token in ctx.tokens, positions = placement = pos0 + s, valid_lens = pos0 + s + 1, steps_left bounded.
-        INT8 KV cache: fresh prompts only (a continued prompt raises ZLError: chunked prompts go through prefill(chunk=...)).
+        INT8 KV cache: fresh prompts only by default (a continued prompt raises ZLError: chunked prompts go through
+        prefill(chunk=...)).  kv_history="cache" accepts pos0[j] > 0 there -- a second turn, a cached prefix, batched chunks; fresh
+        and continued tasks may be mixed: the call's rows are quantised into the cache as always, and the attention is one
+        ops.prefill_attention_varlen_q8 launch per layer, which reads rows below pos0[j] from the cache (dequantised in the kernel:
+        the reference's fall-back arithmetic, attention.cpp:510-516) and the call's own rows unquantised, with no temporary.  Head
+        size 128 only; on an fp16 cache the keyword changes nothing; any other value raises ZLError.
         Head sizes other than 128: batched linears, attention per task through the mask form.  Tensor parallelism: single
         stream, the all-reduces run over the summed rows; DUAL_STREAM does not apply to a batched call.  dynamic (NTK) rope
         takes the call's last row as its sequence length, as the reference does for any forward.  Duplicate or out-of-range
         tasks, empty prompts and prompts that do not fit the buffers raise ZLError before any launch."""
+        self._check_kv_history(ctx, kv_history)
+        q8_history = bool(ctx.kv_quant and kv_history == "cache")
         tasks = [int(t) for t in tasks]
         n = len(tasks)
         pos0 = [0] * n if pos0 is None else [int(p) for p in pos0]
@@ -1565,9 +1595,9 @@ class LLaMA:
             s = int(pr.numel())
             if s < 1 or p0 < 0 or p0 + s + 1 > ctx.max_len_buf:
                 raise ops.ZLError(f"prefill_batch: prompt of task {t} ({s} tokens at {p0}) does not fit the task's KV buffer")
-            if ctx.kv_quant and p0 != 0:
+            if ctx.kv_quant and p0 != 0 and not q8_history:
                 raise ops.ZLError("prefill_batch: a continued prompt into the INT8 KV cache goes through LLaMA.prefill(chunk=...)")
-        return self._prefill_rows(ctx, tasks, prompts, pos0)
+        return self._prefill_rows(ctx, tasks, prompts, pos0, q8_history=q8_history)
 
     def _prefill_chunk(self, ctx: DynBatchContext, task: int, prompt: torch.Tensor, pos0: int):
         """The "encode part" of a task (LLaMA::encode with len_q = prompt length for one task:
@@ -1588,11 +1618,13 @@ class LLaMA:
             raise ops.ZLError("chunked prefill into the INT8 KV cache goes through LLaMA.prefill(chunk=...)")
         return self._prefill_rows(ctx, [task], [prompt], [pos0])
 
-    def _prefill_rows(self, ctx: DynBatchContext, tasks, prompts, pos0s):
+    def _prefill_rows(self, ctx: DynBatchContext, tasks, prompts, pos0s, q8_history=False):
         """The layer loop of prompt encode over the rows of n tasks (checked by the callers): one task is _prefill_chunk's
         launch sequence exactly; n > 1 gathers the per-row scatter tables and the attention tables once per call (one upload of
         positions and plans), runs every linear over the summed rows, the K/V scatter with one "task" per row, one varlen
-        attention launch per layer, then one gather of the last rows, one lm_head and one pick for the n rows."""
+        attention launch per layer, then one gather of the last rows, one lm_head and one pick for the n rows.
+        q8_history (INT8 cache, head size 128): rows below a task's pos0 are read from the cache by the attention kernel
+        (ops.prefill_attention_varlen_q8), for one task or several; no unquantised copy of earlier rows is used."""
         c, dev = self.cfg, self.device
         n = len(tasks)
         one = n == 1
@@ -1606,7 +1638,8 @@ class LLaMA:
             pos = torch.arange(pos0, pos0 + s, dtype=torch.int32, device=dev)
             placement = pos.view(1, s)
             buf_lens = ctx.buf_lens[task:task + 1]
-            unq = ctx.unquant_kv.get(task) if ctx.kv_quant else None
+            unq = ctx.unquant_kv.get(task) if ctx.kv_quant and not q8_history else None
+            plan = ops.prefill_varlen_plan([s], [pos0], [ctx.max_len_buf], dev) if q8_history else None
         else:
             tokens = torch.cat([pr.to(device=dev, dtype=torch.int32).reshape(-1) for pr in prompts])
             ends = [p0 + s for p0, s in zip(pos0s, lens)]
@@ -1624,8 +1657,13 @@ class LLaMA:
             placement = pos.view(total, 1)                    # the K/V scatter: one "task" per row
             buf_lens = ctx.buf_lens.index_select(0, rows_dev)
             ka_rows, va_rows = ctx.k_addrs.index_select(1, rows_dev), ctx.v_addrs.index_select(1, rows_dev)
-            if ctx.kv_quant:                                  # attention over the call's own rows (fresh prompts only)
+            if ctx.kv_quant:
                 ks_rows, vs_rows = ctx.ks_addrs.index_select(1, rows_dev), ctx.vs_addrs.index_select(1, rows_dev)
+            if q8_history:                                    # history from the cache, own rows from the concatenated k / v
+                ka_t, va_t = ctx.k_addrs.index_select(1, tasks_dev), ctx.v_addrs.index_select(1, tasks_dev)
+                ks_t, vs_t = ctx.ks_addrs.index_select(1, tasks_dev), ctx.vs_addrs.index_select(1, tasks_dev)
+                att_pos0, len_bufs, len_bufs_dev = pos0s, [ctx.max_len_buf] * n, None
+            elif ctx.kv_quant:                                # attention over the call's own rows (fresh prompts only)
                 att_pos0, len_bufs, len_bufs_dev = [0] * n, lens, lens_dev
             else:
                 ka_t, va_t = ctx.k_addrs.index_select(1, tasks_dev), ctx.v_addrs.index_select(1, tasks_dev)
@@ -1639,7 +1677,13 @@ class LLaMA:
             q, k, v = ops.rope_qk_cache(cos, sin, qkv, c.num_heads, hkv, d, True)
             q3, k3, v3 = q.view(total, c.num_heads, d), k.view(total, hkv, d), v.view(total, hkv, d)
             if one:
-                att = self._prompt_attention_one(ctx, li, task, q3, k3, v3, pos, placement, buf_lens, pos0, unq, scale)
+                att = self._prompt_attention_one(ctx, li, task, q3, k3, v3, pos, placement, buf_lens, pos0, unq, scale, plan)
+            elif q8_history:
+                # attn_encode_group with a quantised buffer and no prompt temporaries (attention.cpp:510-516): codes to the cache,
+                # then the history is dequantised where the kernel stages it; the call's own rows are read unquantised
+                ops.quant_copy_to_rag_buffer(pos, buf_lens, k3, v3, ka_rows[li], va_rows[li], ks_rows[li], vs_rows[li], len_q=1)
+                att = ops.prefill_attention_varlen_q8(q3, lens, att_pos0, k3, v3, ka_t[li], va_t[li], ks_t[li], vs_t[li], len_bufs,
+                                                      hkv, scale, plan=plan)
             elif ctx.kv_quant:
                 # attn_encode_group with a quantised buffer (attention.cpp:494-510): the prompts attend to their own UNquantised
                 # rows -- the tables point into the concatenated k / v -- while the codes go to the cache
@@ -1681,7 +1725,7 @@ class LLaMA:
                                                  out=att[a:a + s].view(1, s, c.num_heads, c.dim_head), workspace=ws)
         return att
 
-    def _prompt_attention_one(self, ctx, li, task, q3, k3, v3, pos, placement, buf_lens, pos0, unq, scale):
+    def _prompt_attention_one(self, ctx, li, task, q3, k3, v3, pos, placement, buf_lens, pos0, unq, scale, q8_plan=None):
         """K/V scatter + attention of one task's prompt rows (the launch sequence of the one-task encode)"""
         c, dev = self.cfg, self.device
         s = q3.shape[0]
@@ -1691,6 +1735,11 @@ class LLaMA:
             # UNquantised K/V rows while their codes go to the cache
             ops.quant_copy_to_rag_buffer(pos, buf_lens, k3, v3, ka, va, ctx.ks_addrs[li][task:task + 1],
                                          ctx.vs_addrs[li][task:task + 1], len_q=s)
+            if q8_plan is not None:
+                # no prompt temporaries (attention.cpp:510-516): rows below pos0 come from the cache, dequantised in the kernel
+                return ops.prefill_attention_varlen_q8(q3, [s], [pos0], k3, v3, ka, va, ctx.ks_addrs[li][task:task + 1],
+                                                       ctx.vs_addrs[li][task:task + 1], [ctx.max_len_buf], c.num_kv_heads, scale,
+                                                       plan=q8_plan)
             if unq is not None:
                 # chunked: this piece's rows join the prompt's unquantised buffers, the piece attends to all of them
                 tk, tv = unq[li, 0], unq[li, 1]

@@ -1291,6 +1291,31 @@ def quant_calc_scale_zp(x, q_zero=128):
     return q, s
 
 
+def dequant_group(codes, scale, q_zero=128, dtype=torch.float16, out=None):
+    """int8_op::dequant_group (src/nn/quant/int8/quant_reduce_kernel.cu:144-190): rows of codes back to `dtype`,
+    out = rn_T((code - q_zero) * scale[row]), the fp32 product rounded once.  codes (..., G) uint8 (q_zero = 128: the INT8 KV
+    cache) or int8 (q_zero = 0), scale fp32 with one entry per row; TransformerBuffer::copy(need_dequant) uses it to hand a prompt
+    chunk the cached rows of a quantised buffer (src/kvcache/transformer_buffer.cu:135-151)."""
+    _chk_cuda(codes, scale)
+    if codes.dtype not in (torch.uint8, torch.int8) or scale.dtype != torch.float32:
+        raise ZLError("dequant_group: uint8 / int8 codes and fp32 scales")
+    if (codes.dtype == torch.uint8) != (q_zero != 0):
+        raise ZLError("dequant_group: unsigned codes go with q_zero != 0, signed codes with q_zero = 0")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError("dequant_group: fp16 / bf16 only")
+    if codes.dim() < 1 or codes.numel() == 0 or scale.numel() * codes.shape[-1] != codes.numel() or scale.device != codes.device:
+        raise ZLError("dequant_group: one scale per row of codes")
+    g = codes.shape[-1]
+    m = codes.numel() // g
+    if out is None:
+        out = torch.empty(codes.shape, dtype=dtype, device=codes.device)
+    else:
+        _chk_out(out.view(m, -1), m, g, dtype, codes.device, "dequant_group")
+    check(lib().zl_dequant_group(_p(codes), _p(scale), _p(out), _i(m), _i(g), C.c_int(int(q_zero)),
+                                 C.c_int(F16 if dtype == torch.float16 else BF16), _stream()), "dequant_group")
+    return out
+
+
 def quant_copy_to_rag_buffer(placement, buf_lens, k_src, v_src, k_addrs, v_addrs, k_scale_addrs, v_scale_addrs, len_q=1,
                              bshd=True):
     """quant_calc_scale(127, 128) + copy_to_rag_buffer2 for the codes and the scales (attention.cpp:656-676).
@@ -1430,6 +1455,75 @@ def prefill_attention_varlen(q, lens, pos0, k_addrs, v_addrs, buf_lens, num_kv_h
                                        _p(v_addrs), _p(out), _p(plan.work), _i(plan.n_work), _i(plan.b), _i(total_q), _i(h),
                                        _i(num_kv_heads), _i(d), _f(scale), C.c_int(int(bshd)), C.c_int(_dt(q)), C.c_int(groups),
                                        _stream()), "prefill_attn_varlen")
+    return out
+
+
+def _q8_cache_table(x, plan, hkv, d, dtype, what, device):
+    """one operand of prefill_attention_varlen_q8: the device int64 pointer table a context keeps (one pointer per task; what the
+    pointers lead to cannot be checked here), or the per-task tensors themselves -- (buf_lens[i], Hkv, D) uint8 codes or
+    (buf_lens[i], Hkv) fp32 scales, checked, None for a task without history -- from which the table is made"""
+    if torch.is_tensor(x):
+        if not (x.is_cuda and x.is_contiguous()) or x.device != device or x.dtype != torch.int64 or x.numel() != plan.b:
+            raise ZLError(f"prefill_attention_varlen_q8: {what}: one int64 pointer per task, on q's device")
+        return x
+    if len(x) != plan.b:
+        raise ZLError(f"prefill_attention_varlen_q8: {what}: one tensor per task")
+    ptrs = []
+    for i, t in enumerate(x):
+        if t is None and plan.pos0[i] == 0:
+            ptrs.append(0)
+            continue
+        shape = (plan.buf_lens[i], hkv, d) if d else (plan.buf_lens[i], hkv)
+        if t is None or t.dtype != dtype or tuple(t.shape) != shape or t.device != device or not t.is_contiguous():
+            raise ZLError(f"prefill_attention_varlen_q8: {what} of task {i}: a contiguous {dtype} tensor of shape {shape} on q's device")
+        ptrs.append(t.data_ptr())
+    return torch.tensor(ptrs, dtype=torch.int64).to(device)
+
+
+def prefill_attention_varlen_q8(q, lens, pos0, k_new, v_new, k_addrs, v_addrs, ks_addrs, vs_addrs, buf_lens, num_kv_heads, scale,
+                                out=None, groups=None, plan=None):
+    """prefill_attention_varlen for chunks that continue rows of an INT8 K/V cache, the history dequantised inside the kernel (the
+    reference's fall-back for a quantised buffer without prompt temporaries, attention.cpp:510-516: dequant_group into a fresh
+    buffer + the chunk's rows + flash attention; bit-identical to dequant_group + prefill_attention_varlen on such buffers, with no
+    buffer).  q (total_q, H, D) and k_new / v_new (total_q, Hkv, D): the tasks' rotated rows back to back, unquantised; key row j of
+    task i is cache row j for j < pos0[i] -- rn_T((code - 128) * scale) -- and row j - pos0[i] of its k_new / v_new slice from
+    there on: the cache is not read at or beyond pos0[i].  k_addrs / v_addrs / ks_addrs / vs_addrs: device int64 tables of the
+    tasks' code (buf_lens[i], Hkv, D) u8 and scale (buf_lens[i], Hkv) fp32 buffers, BSHD, or the per-task tensors themselves (then
+    checked; None for a task with pos0 = 0).  D = 128.  lens / pos0 / buf_lens / plan as for prefill_attention_varlen."""
+    _chk_cuda(q, k_new, v_new)
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError("prefill_attention_varlen_q8: fp16 / bf16 only")
+    if q.dim() != 3 or k_new.dim() != 3:
+        raise ZLError("prefill_attention_varlen_q8: q (total_q, H, D), k_new / v_new (total_q, Hkv, D)")
+    total_q, h, d = q.shape
+    if d != 128:
+        raise ZLError(f"prefill_attention_varlen_q8: head size {d}: only 128 (the mask-form attention reads a chunk's own rows as codes)")
+    if plan is None:
+        plan = prefill_varlen_plan(lens, pos0, buf_lens, q.device)
+    elif plan.lens != [int(x) for x in lens] or plan.pos0 != [int(x) for x in pos0] or plan.buf_lens != [int(x) for x in buf_lens]:
+        raise ZLError("prefill_attention_varlen_q8: the plan was made for other lengths")
+    if total_q != plan.total_q:
+        raise ZLError(f"prefill_attention_varlen_q8: q has {total_q} rows, the lengths add up to {plan.total_q}")
+    if num_kv_heads < 1 or h % num_kv_heads:
+        raise ZLError("prefill_attention_varlen_q8: H must be a multiple of Hkv")
+    for t in (k_new, v_new):
+        if tuple(t.shape) != (total_q, num_kv_heads, d) or t.dtype != q.dtype or t.device != q.device:
+            raise ZLError("prefill_attention_varlen_q8: k_new / v_new: (total_q, Hkv, D) rows of q's dtype on q's device")
+    if plan.tables.device != q.device:
+        raise ZLError("prefill_attention_varlen_q8: the plan lives on another device")
+    k_tab = _q8_cache_table(k_addrs, plan, num_kv_heads, d, torch.uint8, "k codes", q.device)
+    v_tab = _q8_cache_table(v_addrs, plan, num_kv_heads, d, torch.uint8, "v codes", q.device)
+    ks_tab = _q8_cache_table(ks_addrs, plan, num_kv_heads, 0, torch.float32, "k scales", q.device)
+    vs_tab = _q8_cache_table(vs_addrs, plan, num_kv_heads, 0, torch.float32, "v scales", q.device)
+    if out is None:
+        out = torch.empty_like(q)
+    else:
+        _chk_out(out.view(total_q, -1), total_q, h * d, q.dtype, q.device, "prefill_attention_varlen_q8")
+    groups = int(os.environ.get("ZL_PREFILL_GROUPS", "0") or 0) if groups is None else groups     # 0: the launcher's choice
+    check(lib().zl_prefill_attn_varlen_q8(_p(q), _p(plan.cu_seqlens_q), _p(plan.pos0_dev), _p(plan.buf_lens_dev), _p(k_tab),
+                                          _p(v_tab), _p(ks_tab), _p(vs_tab), _p(k_new), _p(v_new), _p(out), _p(plan.work),
+                                          _i(plan.n_work), _i(plan.b), _i(total_q), _i(h), _i(num_kv_heads), _i(d), _f(scale),
+                                          C.c_int(_dt(q)), C.c_int(groups), _stream()), "prefill_attn_varlen_q8")
     return out
 
 
