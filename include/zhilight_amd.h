@@ -342,6 +342,34 @@ int zl_gemm_nt_small_m_argmax(const uint16_t* x, int64_t ldx, const uint16_t* w 
 int zl_greedy_advance(const void* argmax_ws, int64_t m, int64_t n, int32_t* tokens, int32_t* positions,
                       int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, zl_stream_t s);
 
+/* Score every row against the lm_head WITHOUT storing the logits: functions::Gemm + nn::log_prob_raw / greedy_match_raw
+ * (src/nn/functions/cross_entropy.cu:7-69, 358-403) as LLaMA::calc_log_prob / calc_greedy_match use them (src/model/llama.cpp:220-244),
+ * with the soft-max statistics formed in the epilogue of the GEMM tile (csrc/lm_head_score.hip).  For x (M, K) T, row stride ldx, and
+ * w (N, K) row-major, y[m, n] = the value zl_gemm_nt would have stored (fp32 MFMA accumulation in its k order, one rounding to T);
+ * on those rounded values, in fp32:
+ *   lse[m]          log sum_n exp(y[m, n])
+ *   label_logit[m]  y[m, labels[m] - col0]; 0 when labels[m] == ignore_index, labels == NULL, or the label lies outside
+ *                   [col0, col0 + n) (a vocabulary slice sees such labels: not an error here)
+ *   logprob[m]      label_logit[m] - lse[m] (one fp32 subtraction); 0 in the cases above
+ *   greedy[m], greedy_logit[m]   col0 + arg-max column (lowest on ties, zl_greedy_advance's rule) and its value
+ * Logits are assumed finite (a rounded logit of +inf makes the row's lse NaN).
+ * label_logit, greedy and greedy_logit are exact functions of zl_gemm_nt's output; lse is deterministic (fixed reduction order,
+ * no atomics) and within (128 + ceil(N / 128)) 2^-24 + 88 2^-23 of the exact log-sum-exp of the rounded logits.  Any of the
+ * five outputs and labels may be NULL.  workspace: zl_lm_head_score_ws_bytes(m, n) bytes, 16-byte aligned ((m, ceil(n / 128))
+ * records of 16 bytes + m floats).  Two launches, no allocation, no sync.  ZL_EINVAL: null x / w / workspace, non-positive size;
+ * ZL_ESHAPE: K % 128, ldx, alignment, col0 < 0; ZL_EDTYPE: not fp16 / bf16; ZL_ELIMIT: m x column blocks beyond the grid. */
+int64_t zl_lm_head_score_ws_bytes(int64_t m, int64_t n);      /* < 0: ZL_ESHAPE / ZL_EINVAL */
+int zl_lm_head_score(const uint16_t* x, int64_t ldx, const uint16_t* w /* (N,K) */, const int32_t* labels, int32_t ignore_index,
+                     int32_t col0, float* lse, float* label_logit, float* logprob, int32_t* greedy, float* greedy_logit,
+                     void* workspace, int64_t m, int64_t n, int64_t k, int dtype, zl_stream_t s);
+/* The same with the tile launch order as an explicit argument (a tuning override; the results do not depend on it).  All row
+ * tiles of a 128-column block are adjacent in either: 0 = plain, 1 = each XCD takes a contiguous range of tiles,
+ * ZL_SCORE_ORDER_AUTO = what zl_lm_head_score does (1 up to 16 row tiles of 64 rows, 0 beyond).  ZL_EINVAL otherwise. */
+enum { ZL_SCORE_ORDER_AUTO = -1 };
+int zl_lm_head_score_ex(const uint16_t* x, int64_t ldx, const uint16_t* w /* (N,K) */, const int32_t* labels, int32_t ignore_index,
+                        int32_t col0, float* lse, float* label_logit, float* logprob, int32_t* greedy, float* greedy_logit,
+                        void* workspace, int64_t m, int64_t n, int64_t k, int dtype, int order, zl_stream_t s);
+
 
 /* ------------------------------------------------------------------------------------------------
  * a2 (W4A8, FP8 activations)  gptq_gemm_k_major's W4_FP8_ALGO branch (src/nn/quant/gptq/q_gemm_k_major.cu:1003-1035) for

@@ -20,6 +20,7 @@ The roundings are the reference's single-stream path: every linear output, the n
 rotated q/k, the attention output and each residual sum is rounded to fp16 exactly where the
 reference materialises an fp16 tensor.
 """
+import collections
 import math
 import os
 import re
@@ -907,6 +908,9 @@ class MoEEncoderLayer(EncoderLayer):
         raise ops.ZLError("MoE layers have no gate|up projection of their own (ff_add runs the experts)")
 
 
+ScoreResult = collections.namedtuple("ScoreResult", "logprobs lse greedy greedy_logit cu sums matches logits")
+
+
 @dataclass
 class DynBatchContext:
     """Per-step device state of a decode batch (model::DynBatchContext s_token / s_position /
@@ -1582,22 +1586,75 @@ class LLaMA:
         stream, the all-reduces run over the summed rows; DUAL_STREAM does not apply to a batched call.  dynamic (NTK) rope
         takes the call's last row as its sequence length, as the reference does for any forward.  Duplicate or out-of-range
         tasks, empty prompts and prompts that do not fit the buffers raise ZLError before any launch."""
+        tasks, pos0, q8_history = self._check_prompt_batch("prefill_batch", ctx, tasks, prompts, pos0, kv_history)
+        return self._prefill_rows(ctx, tasks, prompts, pos0, q8_history=q8_history)
+
+    def _check_prompt_batch(self, what, ctx: DynBatchContext, tasks, prompts, pos0, kv_history):
+        """the argument checks of prefill_batch / score, before any launch -> (tasks, pos0 as int lists, q8_history)"""
         self._check_kv_history(ctx, kv_history)
         q8_history = bool(ctx.kv_quant and kv_history == "cache")
         tasks = [int(t) for t in tasks]
         n = len(tasks)
         pos0 = [0] * n if pos0 is None else [int(p) for p in pos0]
         if n < 1 or len(prompts) != n or len(pos0) != n:
-            raise ops.ZLError("prefill_batch: one prompt and one pos0 per task")
+            raise ops.ZLError(f"{what}: one prompt and one pos0 per task")
         if len(set(tasks)) != n or any(t < 0 or t >= ctx.tokens.numel() for t in tasks):
-            raise ops.ZLError("prefill_batch: tasks must be distinct indices of the batch")
+            raise ops.ZLError(f"{what}: tasks must be distinct indices of the batch")
         for t, pr, p0 in zip(tasks, prompts, pos0):
             s = int(pr.numel())
             if s < 1 or p0 < 0 or p0 + s + 1 > ctx.max_len_buf:
-                raise ops.ZLError(f"prefill_batch: prompt of task {t} ({s} tokens at {p0}) does not fit the task's KV buffer")
+                raise ops.ZLError(f"{what}: prompt of task {t} ({s} tokens at {p0}) does not fit the task's KV buffer")
             if ctx.kv_quant and p0 != 0 and not q8_history:
-                raise ops.ZLError("prefill_batch: a continued prompt into the INT8 KV cache goes through LLaMA.prefill(chunk=...)")
-        return self._prefill_rows(ctx, tasks, prompts, pos0, q8_history=q8_history)
+                raise ops.ZLError(f"{what}: a continued prompt into the INT8 KV cache goes through LLaMA.prefill(chunk=...)")
+        return tasks, pos0, q8_history
+
+    def score(self, ctx: DynBatchContext, tasks, prompts, pos0=None, labels=None, kv_history=None):
+        """prefill_batch that also scores EVERY prompt row against the lm_head (LLaMA::calc_log_prob / calc_greedy_match,
+        src/model/llama.cpp:194-244, over nn::log_prob_raw / greedy_match_raw, src/nn/functions/cross_entropy.cu:7-69, 358-403):
+        same arguments, checks, refusals and effects as prefill_batch -- the same layer loop, then output_layernorm over all rows,
+        ONE ops.lm_head_score launch pair that never stores the (rows, vocab) logits, then prefill_batch's own lm_head and pick
+        on the last rows, so the context ends exactly as after prefill_batch.
+        labels None: next-token labels (row r of task j is labelled prompts[j][r + 1], the last row is not scored); else one
+        int sequence per task of its prompt's length, -100 = not scored (calc_log_prob's `label`).  Labels outside the vocabulary
+        raise ZLError before any launch.  Prompts and labels are read on the host to build the labels: give host tensors (device
+        prompts work as in prefill_batch but cost a synchronising copy here).
+        Returns ScoreResult: logprobs / lse / greedy / greedy_logit (device tensors over the summed rows, task after task; the
+        logits are the values the prompt GEMM would store, rounded once to the model dtype), cu (host row offsets per task),
+        sums (n,) fp32 = per-task sum of logprobs over the scored rows (the negative of log_prob_raw's first value), matches (n,)
+        bool = every scored row's greedy equals its label, logits (n, vocab) of the last rows as prefill_batch returns them.
+        sums and matches are formed on the device, without a host synchronisation.  Unlike the reference's calc_greedy_match,
+        no label value is exempt (it skips rows whose target is token 7) and ties go to the LOWEST index (it takes the highest).
+        Tensor parallelism is not supported."""
+        if self.tp:
+            raise ops.ZLError("score: tensor parallelism is not supported")
+        tasks, pos0, q8_history = self._check_prompt_batch("score", ctx, tasks, prompts, pos0, kv_history)
+        rows = ops.score_labels(prompts, labels)
+        if any(l != ops.SCORE_IGNORE and not 0 <= l < self.cfg.vocab_size for l in rows):
+            raise ops.ZLError("score: a label lies outside the vocabulary")
+        return self._prefill_rows(ctx, tasks, prompts, pos0, q8_history=q8_history, score_labels=rows)
+
+    def _score_rows(self, hidden, labels_dev, lens, last_rows=None):
+        """output_layernorm over all rows + the fused lm_head scoring; per-task sums / matches on the device"""
+        c = self.cfg
+        ln_scale = (c.dim_model / c.dim_model_base) if c.dim_model_base > 0 else 1.0
+        xn = ops.rmsnorm(hidden, self.output_layernorm, c.eps, ln_scale)
+        if c.dim_model % 128 == 0:
+            r = ops.lm_head_score(xn, self.lm_head, labels_dev)
+        else:
+            r = ops.lm_head_score_unfused(xn, self.lm_head, labels_dev)
+        miss = ((r.greedy != labels_dev) & (labels_dev != ops.SCORE_IGNORE)).float()
+        cu = [0]
+        for s in lens:
+            cu.append(cu[-1] + s)
+        if last_rows is None:
+            sums, matches = r.logprob.sum().view(1), (miss.sum() == 0).view(1)
+        else:
+            # per-task sums as differences of ONE float64 running sum at the tasks' last rows (ignored rows hold 0; the running sum
+            # of at most 2^31 fp32 terms is exact to 2^-53 relative, far inside the fp32 result): no host read, no atomics
+            run = torch.stack([r.logprob.double(), miss.double()]).cumsum(1).index_select(1, last_rows)
+            d = torch.diff(run, dim=1, prepend=run.new_zeros(2, 1))
+            sums, matches = d[0].float(), d[1] == 0
+        return ScoreResult(r.logprob, r.lse, r.greedy, r.greedy_logit, cu, sums, matches, None)
 
     def _prefill_chunk(self, ctx: DynBatchContext, task: int, prompt: torch.Tensor, pos0: int):
         """The "encode part" of a task (LLaMA::encode with len_q = prompt length for one task:
@@ -1618,13 +1675,16 @@ class LLaMA:
             raise ops.ZLError("chunked prefill into the INT8 KV cache goes through LLaMA.prefill(chunk=...)")
         return self._prefill_rows(ctx, [task], [prompt], [pos0])
 
-    def _prefill_rows(self, ctx: DynBatchContext, tasks, prompts, pos0s, q8_history=False):
+    def _prefill_rows(self, ctx: DynBatchContext, tasks, prompts, pos0s, q8_history=False, score_labels=None):
         """The layer loop of prompt encode over the rows of n tasks (checked by the callers): one task is _prefill_chunk's
         launch sequence exactly; n > 1 gathers the per-row scatter tables and the attention tables once per call (one upload of
         positions and plans), runs every linear over the summed rows, the K/V scatter with one "task" per row, one varlen
         attention launch per layer, then one gather of the last rows, one lm_head and one pick for the n rows.
         q8_history (INT8 cache, head size 128): rows below a task's pos0 are read from the cache by the attention kernel
-        (ops.prefill_attention_varlen_q8), for one task or several; no unquantised copy of earlier rows is used."""
+        (ops.prefill_attention_varlen_q8), for one task or several; no unquantised copy of earlier rows is used.
+        score_labels (LLaMA.score: one host label per row): the launches are the same, then every row is scored before the last
+        rows' logits and pick; the labels ride the call's int32 upload (n > 1; the one-task path has no such table and uploads the
+        labels on their own: one extra host-to-device copy).  Returns a ScoreResult then, else the logits."""
         c, dev = self.cfg, self.device
         n = len(tasks)
         one = n == 1
@@ -1640,6 +1700,7 @@ class LLaMA:
             buf_lens = ctx.buf_lens[task:task + 1]
             unq = ctx.unquant_kv.get(task) if ctx.kv_quant and not q8_history else None
             plan = ops.prefill_varlen_plan([s], [pos0], [ctx.max_len_buf], dev) if q8_history else None
+            labels_dev = torch.tensor(score_labels, dtype=torch.int32).to(dev) if score_labels is not None else None
         else:
             tokens = torch.cat([pr.to(device=dev, dtype=torch.int32).reshape(-1) for pr in prompts])
             ends = [p0 + s for p0, s in zip(pos0s, lens)]
@@ -1647,8 +1708,10 @@ class LLaMA:
             for s in lens:
                 cu.append(cu[-1] + s)
             # one upload of the call's int32 and one of its int64 tables
-            pos_all = torch.tensor([p0 + r for p0, s in zip(pos0s, lens) for r in range(s)] + ends + lens, dtype=torch.int32).to(dev)
-            pos, ends_dev, lens_dev = pos_all[:total], pos_all[total:total + n], pos_all[total + n:]
+            pos_all = torch.tensor([p0 + r for p0, s in zip(pos0s, lens) for r in range(s)] + ends + lens + (score_labels or []),
+                                   dtype=torch.int32).to(dev)
+            pos, ends_dev, lens_dev = pos_all[:total], pos_all[total:total + n], pos_all[total + n:total + 2 * n]
+            labels_dev = pos_all[total + 2 * n:] if score_labels is not None else None
             row_bytes = hkv * d * c.torch_dtype.itemsize
             idx = torch.tensor(tasks + [t for t, s in zip(tasks, lens) for _ in range(s)] + [r - 1 for r in cu[1:]] +
                                [r * row_bytes for r in cu[:-1]], dtype=torch.int64).to(dev)
@@ -1696,19 +1759,20 @@ class LLaMA:
                 att = self._prompt_attention_tasks(q3, lens, att_pos0, ka_t[li], va_t[li], len_bufs, len_bufs_dev, plan, cu, scale)
             layer.attn_out_add(att.view(total, -1), hidden)
             layer.ff_add(hidden, c.eps)
+        scored = self._score_rows(hidden, labels_dev, lens, None if one else last_rows) if score_labels is not None else None
         if one:
             logits = self._prompt_logits_and_pick(ctx, task, hidden[s - 1:s])
             ctx.positions[task] = pos0 + s
             ctx.placement[task] = pos0 + s
             ctx.valid_lens[task] = pos0 + s + 1
             ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - (pos0 + s))
-            return logits
+            return logits if scored is None else scored._replace(logits=logits)
         logits = self._prompt_logits_and_pick_rows(ctx, tasks_dev, hidden.index_select(0, last_rows))
         ctx.positions.index_copy_(0, tasks_dev, ends_dev)
         ctx.placement.index_copy_(0, tasks_dev, ends_dev)
         ctx.valid_lens.index_copy_(0, tasks_dev, ends_dev + 1)
         ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - max(ends))
-        return logits
+        return logits if scored is None else scored._replace(logits=logits)
 
     def _prompt_attention_tasks(self, q3, lens, pos0s, k_tab, v_tab, len_bufs, len_bufs_dev, plan, cu, scale):
         """attention of n > 1 tasks' prompt rows q3 (total, H, D) against the buffers of the tables k_tab / v_tab (n pointers,

@@ -8,6 +8,7 @@ current torch stream.  There is no CPU / eager fallback: without the HIP library
 Names, argument meaning and error behaviour follow the reference (citations on each function;
 paths relative to the ZhiLight tree).
 """
+import collections
 import ctypes as C
 import os
 import math
@@ -820,6 +821,119 @@ def argmax_advance(logits, tokens=None, positions=None, placement=None, valid_le
     check(lib().zl_argmax_advance(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(tokens), _p(positions), _p(placement),
                                   _p(valid_lens), _p(next_tokens), _stream()), "argmax_advance")
     return next_tokens if next_tokens is not None else tokens
+
+
+# --------------------------------------------------------------------------------------------------
+# scoring: functions::Gemm + nn::log_prob_raw / greedy_match_raw (src/nn/functions/cross_entropy.cu:7-69, 358-403) without the
+# (M, N) logits: csrc/lm_head_score.hip
+# --------------------------------------------------------------------------------------------------
+ScoreRows = collections.namedtuple("ScoreRows", "lse label_logit logprob greedy greedy_logit")
+SCORE_IGNORE = -100
+
+
+def lm_head_score_workspace(m, n, device):
+    nbytes = int(lib().zl_lm_head_score_ws_bytes(_i(m), _i(n)))
+    if nbytes < 0:
+        check(nbytes, "lm_head_score_ws_bytes")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def score_labels(prompts, labels=None, ignore_index=SCORE_IGNORE):
+    """Host label list of a scoring call over the concatenated rows of `prompts` (1-D int sequences): labels None = next-token
+    labels (row r of prompt j is labelled prompts[j][r + 1], its last row ignore_index); else labels[j] gives prompt j's labels,
+    one per row (ignore_index = not scored), as calc_log_prob's `label` (src/model/llama.cpp:220-232).  Pure host code: the
+    sequences are read with .tolist(), so give host tensors / lists (a device tensor costs a synchronising copy here)."""
+    rows = []
+    if labels is None:
+        for pr in prompts:
+            ids = [int(t) for t in (pr.tolist() if hasattr(pr, "tolist") else pr)]
+            rows += ids[1:] + [ignore_index]
+        return rows
+    if len(labels) != len(prompts):
+        raise ZLError("score: one label sequence per prompt")
+    for pr, lb in zip(prompts, labels):
+        ids = [int(t) for t in (lb.tolist() if hasattr(lb, "tolist") else lb)]
+        if len(ids) != (int(pr.numel()) if hasattr(pr, "numel") else len(pr)):
+            raise ZLError("score: a label sequence must have its prompt's length")
+        rows += ids
+    return rows
+
+
+def _score_args(x, weight, labels, ignore_index, what):
+    """host checks shared by lm_head_score / lm_head_score_unfused -> (x2, m, n, k, labels on the device or None)"""
+    _chk_cuda(weight)
+    if not (x.is_cuda and x.dim() >= 1 and x.stride(-1) == 1) or x.device != weight.device:
+        raise ZLError(what + ": CUDA activations with unit column stride on the weight's device")
+    x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])
+    m, k = x2.shape
+    if weight.dim() != 2 or weight.shape[1] != k or weight.dtype != x.dtype or m < 1:
+        raise ZLError(what + ": size K / dtype mismatch")
+    _dt(x)
+    n = weight.shape[0]
+    if labels is not None:
+        if not (torch.is_tensor(labels) and labels.is_cuda):        # host labels: checked here, one upload
+            host = torch.as_tensor(labels)
+            if host.dim() != 1 or host.numel() != m or host.dtype.is_floating_point:
+                raise ZLError(what + ": labels: one integer per row")
+            if bool(((host != ignore_index) & ((host < 0) | (host >= n))).any()):
+                raise ZLError(what + ": a label lies outside the vocabulary")
+            labels = host.to(torch.int32).to(x.device)
+        elif labels.dtype != torch.int32 or labels.dim() != 1 or labels.numel() != m or not labels.is_contiguous() or labels.device != x.device:
+            raise ZLError(what + ": device labels: contiguous int32 of length M on the activations' device")    # (their values are trusted)
+    return x2, m, n, k, labels
+
+
+def lm_head_score(x, weight, labels=None, ignore_index=SCORE_IGNORE, workspace=None, order=None):
+    """Per row of y = x . weight^T (the values gemm_nt would store), without storing y: ScoreRows(lse, label_logit, logprob, greedy,
+    greedy_logit) -- fp32 log-sum-exp, the label's logit, label_logit - lse, the arg-max column (int32, lowest on ties) and its
+    value; rows whose label is ignore_index (or all rows with labels=None) get label_logit = logprob = 0.  labels: int32 device
+    tensor of length M (values trusted), or a host tensor / list (checked against [0, N) here, uploaded once).  workspace:
+    lm_head_score_workspace(M, N, device) to reuse one (graph capture); K % 128 == 0 (ZLError otherwise: lm_head_score_unfused
+    covers other shapes).  order: the tile launch order of zl_lm_head_score_ex (0 / 1; results do not depend on it), default
+    ZL_SCORE_ORDER from the environment, else the library's choice by row count (-1).  Logits are assumed finite."""
+    x2, m, n, k, labels = _score_args(x, weight, labels, ignore_index, "lm_head_score")
+    if workspace is None:
+        workspace = lm_head_score_workspace(m, n, x.device)
+    else:
+        need = int(lib().zl_lm_head_score_ws_bytes(_i(m), _i(n)))
+        if not (workspace.is_cuda and workspace.is_contiguous() and workspace.device == x.device) or workspace.numel() * workspace.element_size() < need:
+            raise ZLError("lm_head_score: workspace too small / wrong device")
+    f = torch.empty((4, m), dtype=torch.float32, device=x.device)
+    greedy = torch.empty(m, dtype=torch.int32, device=x.device)
+    if order is None:
+        order = int(os.environ.get("ZL_SCORE_ORDER", "-1"))
+    check(lib().zl_lm_head_score_ex(_p(x2), _i(x2.stride(0)), _p(weight), _p(labels), C.c_int(ignore_index), C.c_int(0), _p(f[0]),
+                                    _p(f[1]), _p(f[2]), _p(greedy), _p(f[3]), _p(workspace), _i(m), _i(n), _i(k), C.c_int(_dt(x)),
+                                    C.c_int(order), _stream()), "lm_head_score")
+    return ScoreRows(f[0], f[1], f[2], greedy, f[3])
+
+
+def lm_head_score_unfused(x, weight, labels=None, ignore_index=SCORE_IGNORE, rows_per_block=256):
+    """lm_head_score's five results from the existing ops over blocks of rows_per_block rows, so that at most that slab of logits
+    (and its fp32 copy) exists at once: gemm_nt (gemm_nt_small_m for K % 128 != 0), then fp32 torch logsumexp / gather / max on
+    the rounded logits.  The form for shapes the fused kernel refuses and the baseline tools/bench_score.py times."""
+    x2, m, n, k, labels = _score_args(x, weight, labels, ignore_index, "lm_head_score_unfused")
+    f = torch.zeros((4, m), dtype=torch.float32, device=x.device)
+    greedy = torch.empty(m, dtype=torch.int32, device=x.device)
+    step = max(1, int(rows_per_block))
+    for a in range(0, m, step):
+        xb = x2[a:a + step]
+        if k % 128 == 0:
+            y = gemm_nt(xb if xb.is_contiguous() else xb.contiguous(), weight).float()
+        else:
+            y = gemm_nt_small_m(xb.contiguous(), weight).float()
+        b = a + y.shape[0]
+        f[0, a:b] = torch.logsumexp(y, dim=1)
+        gi = torch.argmax(y, dim=1)
+        f[3, a:b] = y.gather(1, gi.view(-1, 1)).view(-1)
+        greedy[a:b] = gi
+        if labels is not None:
+            lb = labels[a:b].long()
+            keep = lb != ignore_index
+            ll = y.gather(1, lb.clamp(0, n - 1).view(-1, 1)).view(-1)
+            f[1, a:b] = torch.where(keep, ll, torch.zeros_like(ll))
+            f[2, a:b] = torch.where(keep, ll - f[0, a:b], torch.zeros_like(ll))
+    return ScoreRows(f[0], f[1], f[2], greedy, f[3])
 
 
 # --------------------------------------------------------------------------------------------------
