@@ -878,7 +878,11 @@ int zl_quant_back_copy_to_buffer(const int32_t* src, const float* scale_x, const
  * Load-time / glue tensor operations behind the bmengine::functions names the reference's layer code calls around its
  * GEMMs (the headers under 3rd/bmengine/bmengine/include/bmengine/functions; hostcpp/bm_functions.h binds them).  Off the decode step's
  * critical path.  Element type codes `zl_elem_t` are bmengine's DataType enumerators (core/dtype.h:12-22).
- *   zl_cast               functions::typecast (typecast.h:7): out[i] = OutT(in[i]) (through fp32; fp32 -> half/bf16 RNE)
+ *   zl_cast               functions::typecast (typecast.h:7): out[i] = OutT(in[i]), converted directly: the same type copies bits;
+ *                         int -> int is C's conversion (widening exact, narrowing modular); to a wider float type exact; f64 / f32 ->
+ *                         half / bf16, f64 -> f32 and half <-> bf16 ONE round-to-nearest-even of the source value (f64 never passes
+ *                         through a rounded fp32); int -> float exact where representable, else one RNE; float -> int truncates
+ *                         towards zero (a value outside the target's range is undefined, as in C)
  *   zl_copy_2d            rows of width_bytes between pitched buffers: functions::concat_tensor / slice_last_dim /
  *                         copy_last_dim (tensor_ops.h:8-12, index_select.h:33-47)
  *   zl_index_select       functions::index_select (index_select.h:8-14): out[o, j, :] = in[o, index[j], :]
@@ -886,7 +890,10 @@ int zl_quant_back_copy_to_buffer(const int32_t* src, const float* scale_x, const
  *   zl_binary_op          functions::BinaryElementwiseOp (element.cu:44-150): op 0 add 1 sub 2 mul 3 div 4 max;
  *                         bmode 0 same shape, 1 b has one value per row (broadcast over the last dim), 2 b is one row
  *   zl_scale              nn::multiply (src/nn/functions/element.cu:11-31): c = a * T(b)
- *   zl_act_inplace        nn::silu_inplace / gelu_inplace (src/nn/linear/activation_kernel.cu:14-57): act 0 silu, 1 gelu(tanh)
+ *   zl_act_inplace        nn::silu_inplace / gelu_inplace (src/nn/linear/activation_kernel.cu:14-57): act 0 silu, 1 gelu(tanh); within
+ *                         1 ulp of T of the exact function over ALL inputs -- differs from the reference's fp32 expressions far below
+ *                         zero, where those return -0 early (gelu from x = -5.2: 1 + tanhf cancels; silu from x = -88.7: expf
+ *                         overflows); gelu is evaluated as x / (1 + e^-2u), silu(-inf) = -0
  *   zl_count_nonfinite    functions::check_numeric: adds the number of NaN / Inf elements to *counter (device int32)
  *   zl_perm_narrow_u16    nn::gptq::int32_to_int16 (src/nn/quant/gptq/utils.cu:253-283)
  *   zl_perm_reverse_u16   nn::gptq::reverse_perm (utils.cu:287-319): out[perm[i]] = i

@@ -26,10 +26,49 @@ template <> struct EL<T_I8> { typedef int8_t type; static __device__ float ld(co
 template <> struct EL<T_I16> { typedef int16_t type; static __device__ float ld(const int16_t* p, int64_t i) { return (float)p[i]; } static __device__ void st(int16_t* p, int64_t i, float v) { p[i] = (int16_t)v; } };
 template <> struct EL<T_I32> { typedef int32_t type; static __device__ float ld(const int32_t* p, int64_t i) { return (float)p[i]; } static __device__ void st(int32_t* p, int64_t i, float v) { p[i] = (int32_t)v; } };
 
+// f64 -> f32 rounded to ODD (the inexact result keeps a set last bit): a following round-to-nearest-even to half / bf16 then equals ONE
+// rounding of the f64 value (fp32 carries more than two bits beyond either format, subnormals and the overflow to inf included)
+__device__ __forceinline__ float f64_to_f32_odd(double d) {
+    const float f = (float)d;
+    if ((double)f == d || d != d) return f;
+    const uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if (u & 1u) return f;
+    return __builtin_bit_cast(float, __builtin_fabs((double)f) < __builtin_fabs(d) ? u + 1u : u - 1u);    // one step towards d
+}
+
+constexpr bool t_is_int(int t) { return t == T_I8 || t == T_I16 || t == T_I32; }
+constexpr bool t_is_f16b(int t) { return t == T_F16 || t == T_BF16; }
+
+// OutT(in[i]) as C converts it (functions::typecast, typecast.cu: T2(in[i]); half <-> bf16 through fp32): the same type copies bits,
+// int -> int is the integer conversion (narrowing modular), anything from or to f64 and int32 -> half / bf16 goes through double with
+// ONE rounding to the target, the rest through fp32 where it is exact or rounded once; float -> int truncates (in range only)
+template <int TI, int TO>
+__device__ __forceinline__ typename EL<TO>::type cast_one(typename EL<TI>::type v) {
+    typedef typename EL<TO>::type O;
+    if constexpr (TI == TO) {
+        return v;
+    } else if constexpr (t_is_int(TI) && t_is_int(TO)) {
+        return (O)v;
+    } else if constexpr (TI == T_F64 || (TI == T_I32 && t_is_f16b(TO))) {
+        if constexpr (t_is_f16b(TO)) return ZT<TO == T_F16 ? ZL_F16 : ZL_BF16>::from_f32(f64_to_f32_odd((double)v));
+        else return (O)v;
+    } else if constexpr (TO == T_F64 && t_is_int(TI)) {
+        return (double)v;
+    } else {
+        float f;
+        if constexpr (TI == T_F16) f = ZT<ZL_F16>::to_f32(v);
+        else if constexpr (TI == T_BF16) f = ZT<ZL_BF16>::to_f32(v);
+        else f = (float)v;
+        if constexpr (TO == T_F16) return ZT<ZL_F16>::from_f32(f);
+        else if constexpr (TO == T_BF16) return ZT<ZL_BF16>::from_f32(f);
+        else return (O)f;
+    }
+}
+
 template <int TI, int TO>
 __global__ void k_cast(const typename EL<TI>::type* __restrict__ in, typename EL<TO>::type* __restrict__ out, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        EL<TO>::st(out, i, EL<TI>::ld(in, i));
+        out[i] = cast_one<TI, TO>(in[i]);
 }
 template <int TI> int cast_from(const void* in, void* out, int to, int64_t n, hipStream_t s) {
     typedef typename EL<TI>::type I;
@@ -119,7 +158,13 @@ template <int T>
 __global__ void k_act_inplace(typename EL<T>::type* __restrict__ x, int64_t n, int act) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float v = EL<T>::ld(x, i);
-        const float a = act == 0 ? v / (1.0f + expf(-v)) : 0.5f * v * (1.0f + tanhf(0.7978845608028654f * v * (1.0f + 0.044715f * v * v)));
+        // silu x / (1 + e^-x); gelu(tanh) 0.5 x (1 + tanh(u)) = x / (1 + e^-2u), u = sqrt(2 / pi) x (1 + 0.044715 x^2): the second form
+        // has no cancellation (1 + tanhf(u) is 0 from u = -9 on, x = -5.2, where the value is still 1e-8 -- an ordinary bf16 number).
+        // Far below zero e^-z overflows (z = -88.7) while x e^z is a bf16 / fp32 value down to z = -103, and 1 + e^-z is e^-z to
+        // fp32: x e^z there.  silu(-inf) takes the limit -0 (the quotient is inf / inf)
+        const float z = act == 0 ? v : 1.5957691216057308f * v * (1.0f + 0.044715f * v * v);
+        float a = z < -80.0f ? v * expf(z) : v / (1.0f + expf(-z));
+        if (act == 0 && v == -INFINITY) a = -0.0f;
         EL<T>::st(x, i, a);
     }
 }
@@ -189,6 +234,7 @@ __global__ __launch_bounds__(1024) void k_argmax_advance(const typename EL<TI>::
     unsigned long long best = 0;
     auto take = [&](float v, int i) {
         uint32_t u = __builtin_bit_cast(uint32_t, v);
+        u = (u << 1) == 0 ? 0u : u;                                    // -0.0 takes +0.0's key: the two zeros are one value, the first index wins
         u = (v != v) ? 0xffffffffu : (u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u));
         const unsigned long long key = ((unsigned long long)u << 32) | (uint32_t)~(uint32_t)i;
         best = key > best ? key : best;
