@@ -185,6 +185,42 @@ def test_prefill_batch_head_size_64(dev):
     assert ctx_b.positions.tolist() == lens
 
 
+# measured on these inputs before the prompt path was restructured (profiles/prompt_path_refactor.txt): 0 on all three calls -- at
+# these lengths the mask-form kernel splits both buffer lengths alike.  The bar is four times the measurement (another split
+# partition under later kernel changes), never below one bf16 step of the largest logit, never above the 2e-2 of
+# test_prefill_batch_head_size_64
+HS64_INT8_BAR = min(2e-2, max(2.0 ** -7, 4 * 0.0))
+
+
+def test_head_size_64_int8_cache_routes_against_fp16_cache(dev):
+    """the mask-form (head size 64) prompt routes of an INT8 KV cache -- a fresh prompt on its own rows, a chunked prompt on its
+    temporaries, several fresh prompts in one pass -- against the same calls on an fp16 cache: on every INT8 route the attention
+    reads UNquantised rows, so the logits differ only by how the mask-form kernel partitions another buffer length"""
+    from zhilight_amd.llama import LLaMA, ModelConfig, QuantConfig
+    cfg = ModelConfig.minicpm_2b()
+    cfg.num_layers = 2
+    model = LLaMA(cfg, QuantConfig(0, 0), dev).init_random(seed=3)
+    model.token_embedding.mul_(0.1)
+    g = torch.Generator().manual_seed(64)
+    p9, p20, p5 = (torch.randint(0, cfg.vocab_size, (s,), generator=g, dtype=torch.int32) for s in (9, 20, 5))
+    calls = {"one task": lambda ctx: model.prefill(ctx, 0, p20),
+             "chunked": lambda ctx: model.prefill(ctx, 0, p20, chunk=8),          # pieces of 8, 8 and 4 rows; temporaries exist
+             "three tasks": lambda ctx: model.prefill_batch(ctx, [0, 1, 2], [p9, p20, p5])}
+    for name, call in calls.items():
+        ctx_q, ctx_f = model.new_context(3, 64, 0, kv_cache_dtype="int8"), model.new_context(3, 64, 0)
+        lq, lf = call(ctx_q).float(), call(ctx_f).float()
+        n = lq.shape[0]
+        for ctx, logits in ((ctx_q, lq), (ctx_f, lf)):
+            assert torch.isfinite(logits).all(), name
+            assert ctx.tokens[:n].tolist() == logits.argmax(dim=1).tolist(), name
+        assert ctx_q.positions.tolist() == ctx_f.positions.tolist(), name
+        assert ctx_q.valid_lens.tolist() == ctx_f.valid_lens.tolist(), name
+        assert not ctx_q.unquant_kv, name
+        err = (lq - lf).abs().max().item() / lf.abs().max().item()
+        print(f"head size 64, INT8 against fp16 cache, {name}: max |dlogit| / max |logit| = {err:.3e}")
+        assert err < HS64_INT8_BAR, (name, err)
+
+
 def test_prefill_batch_tensor_parallel(dev):
     from zhilight_amd.llama import LLaMA, QuantConfig
     rng, cfg, sd, ref_model = _gptq_model(dev, seed=41, rope=False)

@@ -275,7 +275,7 @@ def test_kv_history_defaults_unchanged(dev):
     with pytest.raises(ops.ZLError):                          # without the keyword the refusals stand
         model.prefill_batch(ctx, [0, 1], [p[10:14], p[:4]], pos0=[10, 0])
     with pytest.raises(ops.ZLError):
-        model._prefill_chunk(ctx, 0, p[10:14], 10)
+        model._encode_prompt(ctx, 0, p[10:14], 10)
     with pytest.raises(ops.ZLError):                          # any other value of the keyword
         model.prefill_batch(ctx, [0, 1], [p[10:14], p[:4]], pos0=[10, 0], kv_history="dequant")
     with pytest.raises(ops.ZLError):

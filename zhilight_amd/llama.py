@@ -937,6 +937,116 @@ class DynBatchContext:
     unquant_kv: Dict[int, torch.Tensor] = field(default_factory=dict)   # INT8 cache: a chunked prompt's temporary fp16 K/V
 
 
+class _PromptRows:
+    """The rows of one prompt-encode call -- one task's piece, or the pieces of several tasks back to back -- as the layer loop, the
+    K/V scatter, the attention and the tail see them.  Built once per call, and the only place that knows whether the call has one
+    task or several: one task uploads no table (positions from torch.arange, scatter tables that are slices of the context's, the
+    pick straight into ctx.tokens); several tasks gather theirs in one int32 and one int64 upload.
+      tasks, lens, cu, ends      host lists: task indices, rows per task, row offsets (n + 1), pos0 + rows per task
+      tokens, pos, labels_dev    int32 per row on the device (labels_dev: LLaMA.score only)
+      placement, buf_lens, len_q, k_rows / v_rows / ks_rows / vs_rows    the scatter: one "task" of len_q = s rows, or one per row with
+                                 len_q = 1; (layers, scatter tasks) pointer tables, ks_rows / vs_rows None on an fp16 cache
+      route, att_pos0s, len_bufs, len_bufs_dev, plan    what the attention reads (LLaMA._prompt_scatter_attend lists the routes): per
+                                 task the first key row's position and the buffer rows (host; device for the mask form), and the
+                                 varlen plan (head size 128: several tasks, or the "q8" route)
+      k_tab / v_tab / ks_tab / vs_tab, kv, kv_off    its buffers: (layers, n) pointer tables ("cache", "temp", "q8"); the one task's
+                                 (layers, 2, rows, Hkv, D) tensor for the one-task launch ("cache", "temp"); "own": the byte offset
+                                 of each task's first row in the call's k / v
+      last_rows, tasks_dev, ends_dev    the tail: int64 row of each task's last token, its index, int32 end -- None for one task"""
+    labels_dev = ks_rows = vs_rows = len_bufs_dev = plan = k_tab = v_tab = ks_tab = vs_tab = kv = kv_off = None
+    last_rows = tasks_dev = ends_dev = None
+
+    @classmethod
+    def of(cls, model, ctx, tasks, prompts, pos0s, q8_history=False, labels=None):
+        if len(tasks) == 1:
+            return cls.one(model, ctx, tasks[0], prompts[0], pos0s[0], q8_history, labels)
+        return cls.many(model, ctx, tasks, prompts, pos0s, q8_history, labels)
+
+    @classmethod
+    def one(cls, model, ctx, task, prompt, pos0, q8_history=False, labels=None, pos=None):
+        """one task's piece at pos0; pos: its positions where the caller holds them already (a part of a dual-stream piece).  The
+        labels are the one upload of this form"""
+        r, c, dev = cls(), model.cfg, model.device
+        s = int(prompt.numel())
+        r.tasks, r.lens, r.cu, r.ends = [task], [s], [0, s], [pos0 + s]
+        r.tokens = prompt.to(device=dev, dtype=torch.int32).contiguous()
+        r.pos = torch.arange(pos0, pos0 + s, dtype=torch.int32, device=dev) if pos is None else pos
+        if labels is not None:
+            r.labels_dev = torch.tensor(labels, dtype=torch.int32).to(dev)
+        col = slice(task, task + 1)
+        r.placement, r.buf_lens, r.len_q = r.pos.view(1, s), ctx.buf_lens[col], s
+        r.k_rows, r.v_rows = ctx.k_addrs[:, col], ctx.v_addrs[:, col]
+        if ctx.kv_quant:
+            r.ks_rows, r.vs_rows = ctx.ks_addrs[:, col], ctx.vs_addrs[:, col]
+        unq = ctx.unquant_kv.get(task) if ctx.kv_quant and not q8_history else None
+        if q8_history:
+            r.route, r.att_pos0s, r.len_bufs = "q8", [pos0], [ctx.max_len_buf]
+            r.k_tab, r.v_tab, r.ks_tab, r.vs_tab = r.k_rows, r.v_rows, r.ks_rows, r.vs_rows
+            r.plan = ops.prefill_varlen_plan(r.lens, r.att_pos0s, r.len_bufs, dev)
+        elif unq is not None:
+            r.route, r.att_pos0s, r.len_bufs, r.kv = "temp", [pos0], [unq.shape[2]], unq
+            r.len_bufs_dev = torch.tensor(r.len_bufs, dtype=torch.int32, device=dev)
+            tab = ops.make_ptr_table([unq[li, j] for li in range(unq.shape[0]) for j in (0, 1)]).view(-1, 2)
+            r.k_tab, r.v_tab = tab[:, 0:1], tab[:, 1:2]
+        elif ctx.kv_quant:
+            r.route, r.att_pos0s, r.len_bufs = "own", [0], [s]
+            if c.dim_head != 128:                         # the mask form's tables; the one-task launch takes k3 / v3 themselves
+                r.len_bufs_dev = torch.tensor(r.len_bufs, dtype=torch.int32, device=dev)
+                r.kv_off = torch.zeros(1, dtype=torch.int64, device=dev)
+        else:
+            r.route, r.att_pos0s, r.len_bufs, r.kv = "cache", [pos0], [ctx.max_len_buf], ctx.kv[task]
+            r.len_bufs_dev, r.k_tab, r.v_tab = r.buf_lens, r.k_rows, r.v_rows
+        return r
+
+    @classmethod
+    def many(cls, model, ctx, tasks, prompts, pos0s, q8_history=False, labels=None):
+        """the pieces of n tasks back to back: the K/V scatter takes one "task" per row, the attention one table entry per task"""
+        r, c, dev = cls(), model.cfg, model.device
+        n = len(tasks)
+        lens = [int(pr.numel()) for pr in prompts]
+        total = sum(lens)
+        cu = [0]
+        for s in lens:
+            cu.append(cu[-1] + s)
+        r.tasks, r.lens, r.cu, r.ends = tasks, lens, cu, [p0 + s for p0, s in zip(pos0s, lens)]
+        r.tokens = torch.cat([pr.to(device=dev, dtype=torch.int32).reshape(-1) for pr in prompts])
+        # one upload of the call's int32 and one of its int64 tables
+        ints = torch.tensor([p0 + i for p0, s in zip(pos0s, lens) for i in range(s)] + r.ends + lens + (labels or []),
+                            dtype=torch.int32).to(dev)
+        r.pos, r.ends_dev, lens_dev = ints[:total], ints[total:total + n], ints[total + n:total + 2 * n]
+        if labels is not None:
+            r.labels_dev = ints[total + 2 * n:]
+        row_bytes = c.num_kv_heads * c.dim_head * c.torch_dtype.itemsize
+        idx = torch.tensor(tasks + [t for t, s in zip(tasks, lens) for _ in range(s)] + [e - 1 for e in cu[1:]] +
+                           [a * row_bytes for a in cu[:-1]], dtype=torch.int64).to(dev)
+        r.tasks_dev, rows_dev, r.last_rows = idx[:n], idx[n:n + total], idx[n + total:2 * n + total]
+        r.placement, r.len_q = r.pos.view(total, 1), 1
+        r.buf_lens = ctx.buf_lens.index_select(0, rows_dev)
+        r.k_rows, r.v_rows = ctx.k_addrs.index_select(1, rows_dev), ctx.v_addrs.index_select(1, rows_dev)
+        if ctx.kv_quant:
+            r.ks_rows, r.vs_rows = ctx.ks_addrs.index_select(1, rows_dev), ctx.vs_addrs.index_select(1, rows_dev)
+        if q8_history:                                    # history from the cache, own rows from the concatenated k / v
+            r.route, r.att_pos0s, r.len_bufs = "q8", pos0s, [ctx.max_len_buf] * n
+            r.k_tab, r.v_tab = ctx.k_addrs.index_select(1, r.tasks_dev), ctx.v_addrs.index_select(1, r.tasks_dev)
+            r.ks_tab, r.vs_tab = ctx.ks_addrs.index_select(1, r.tasks_dev), ctx.vs_addrs.index_select(1, r.tasks_dev)
+        elif ctx.kv_quant:                                # attention over the call's own rows (fresh prompts only)
+            r.route, r.att_pos0s, r.len_bufs, r.len_bufs_dev = "own", [0] * n, lens, lens_dev
+            r.kv_off = idx[2 * n + total:]
+        else:
+            r.route, r.att_pos0s, r.len_bufs = "cache", pos0s, [ctx.max_len_buf] * n
+            r.k_tab, r.v_tab = ctx.k_addrs.index_select(1, r.tasks_dev), ctx.v_addrs.index_select(1, r.tasks_dev)
+            r.len_bufs_dev = ctx.buf_lens.index_select(0, r.tasks_dev)
+        if c.dim_head == 128:
+            r.plan = ops.prefill_varlen_plan(lens, r.att_pos0s, r.len_bufs, dev)
+        return r
+
+    def att_tables(self, li, k3, v3):
+        """layer li's K / V pointer tables, one entry per task; "own": they point into the concatenated k3 / v3"""
+        if self.route == "own":
+            return self.kv_off + k3.data_ptr(), self.kv_off + v3.data_ptr()
+        return self.k_tab[li], self.v_tab[li]
+
+
 class LLaMA:
     """model::LLaMA (src/model/llama.cpp:11-165) restricted to the dynamic-batch decode step."""
     moe = False                 # any MoEEncoderLayer (set by __init__)
@@ -1449,18 +1559,12 @@ class LLaMA:
                     inside the attention kernel (ops.prefill_attention_varlen_q8) -- no temporary of any kind.  Earlier pieces
                     are seen through their codes, so the logits differ from the default route's by the cache's quantisation
                     noise; the cache contents differ accordingly from the second piece on."""
-        self._check_kv_history(ctx, kv_history)
+        q8_history = self._check_kv_history(ctx, kv_history)
         s = int(prompt.numel())
         if chunk <= 0 or chunk >= s:
             return self._encode_prompt(ctx, task, prompt, 0)
-        logits = None
-        if ctx.kv_quant and kv_history == "cache":
-            if s + 1 > ctx.max_len_buf:
-                raise ops.ZLError("prompt does not fit the task's KV buffer")
-            for p0 in range(0, s, chunk):
-                logits = self._prefill_rows(ctx, [task], [prompt[p0:p0 + chunk]], [p0], q8_history=True)
-            return logits
-        if ctx.kv_quant:
+        self._check_prompt_piece("prefill", ctx, task, s, 0, True)
+        if ctx.kv_quant and not q8_history:
             # INT8 KV cache: the prompt keeps attending to its UNquantised K/V rows across the chunks, held in temporary
             # buffers for the duration of the prompt (dyn_batch->unquant_key_buf, attention.cpp:497-510) while the codes go
             # to the cache; the decode steps that follow read the cache
@@ -1469,26 +1573,46 @@ class LLaMA:
                                                dtype=c.torch_dtype, device=self.device)
         try:
             for p0 in range(0, s, chunk):
-                logits = self._encode_prompt(ctx, task, prompt[p0:p0 + chunk], p0)
+                logits = self._encode_prompt(ctx, task, prompt[p0:p0 + chunk], p0, q8_history)
         finally:
             ctx.unquant_kv.pop(task, None)
         return logits
 
     def _check_kv_history(self, ctx: DynBatchContext, kv_history):
         """the kv_history keyword of prefill / prefill_batch: None or "cache"; "cache" on an INT8 context needs head size 128 (the
-        mask-form attention of other head sizes reads a chunk's own rows as codes: another result).  Raises before any launch."""
+        mask-form attention of other head sizes reads a chunk's own rows as codes: another result).  Raises before any launch;
+        returns whether the call reads its history from the INT8 cache."""
         if kv_history not in (None, "cache"):
             raise ops.ZLError(f"kv_history: None or 'cache', not {kv_history!r}")
         if kv_history == "cache" and ctx.kv_quant and self.cfg.dim_head != 128:
             raise ops.ZLError("kv_history='cache' on an INT8 KV cache needs head size 128")
+        return bool(ctx.kv_quant and kv_history == "cache")
 
-    def _encode_prompt(self, ctx: DynBatchContext, task: int, prompt: torch.Tensor, pos0: int):
-        """LLaMA::encode's switch (src/model/llama.cpp:102-110): with DUAL_STREAM=1, more than one TP rank and more
+    def _check_prompt_piece(self, what, ctx: DynBatchContext, task, s, pos0, history_readable):
+        """the checks of one task's piece (s rows at pos0), before any launch: it fits the task's buffers, and a continued piece
+        into an INT8 cache has something to read its history from -- the prompt's temporaries or kv_history="cache"."""
+        if s < 1 or pos0 < 0 or pos0 + s + 1 > ctx.max_len_buf:
+            raise ops.ZLError(f"{what}: prompt of task {task} ({s} tokens at {pos0}) does not fit the task's KV buffer")
+        if ctx.kv_quant and pos0 != 0 and not history_readable:
+            # a later piece without the prompt's temporary unquantised buffers (prefill(chunk=...) keeps them): the reference
+            # falls back to de-quantising the cache there ("WARNING: de-quantize prompt kv cache!", attention.cpp:511-516)
+            raise ops.ZLError(f"{what}: a continued prompt into the INT8 KV cache goes through LLaMA.prefill(chunk=...) "
+                              "or kv_history='cache'")
+
+    def _encode_prompt(self, ctx: DynBatchContext, task: int, prompt: torch.Tensor, pos0: int, q8_history=False):
+        """The "encode part" of a task (LLaMA::encode with len_q = prompt length for one task:
+        src/model/llama.cpp:75-165, Attention::impl::NormalImpl::dynamic_batch_forward encode branch,
+        src/nn/attention/attention.cpp:846-964 / attn_encode_group :442-622): runs the piece through the layers, fills the
+        task's KV buffers at slots pos0 .. pos0 + S - 1, leaves the task ready for decode steps (tokens <- greedy first token,
+        positions = placement = pos0 + S, valid_lens = pos0 + S + 1) and returns the logits of the last row (1, vocab).
+        LLaMA::encode's switch (src/model/llama.cpp:102-110): with DUAL_STREAM=1, more than one TP rank and more
         than DUAL_STREAM_THRESHOLD (1024) tokens in the piece, the layers run as dual_stream_encode."""
+        self._check_prompt_piece("prefill", ctx, task, int(prompt.numel()), pos0,
+                                 q8_history or ctx.unquant_kv.get(task) is not None)
         if (self.tp and int(os.environ.get("DUAL_STREAM", "0")) > 0 and not ctx.kv_quant
                 and int(prompt.numel()) > int(os.environ.get("DUAL_STREAM_THRESHOLD", "1024"))):
             return self._prefill_dual_stream(ctx, task, prompt, pos0)
-        return self._prefill_chunk(ctx, task, prompt, pos0)
+        return self._prompt_tail(ctx, *self._prefill_rows(ctx, [task], [prompt], [pos0], q8_history))
 
     def _prefill_dual_stream(self, ctx: DynBatchContext, task: int, prompt: torch.Tensor, pos0: int):
         """EncoderLayer::impl::dual_stream_encode (src/nn/block/block.cpp:205-441) on two HIP streams: the piece is
@@ -1496,23 +1620,21 @@ class LLaMA:
         (attn_out, w_out) is all-reduced on a second, higher-priority stream while the main stream computes the other
         part, so the xGMI transfer of one half hides behind the GEMMs / attention of the other.  Part k of a layer
         starts with add_fuse_ln (layernorm.cu:227-302: c = T(hidden + reduced), norm of the fp32 sum) once its own
-        reduce has landed; the later part attends to the earlier part's K/V through the cache, like a prefill chunk.
+        reduce has landed; the later part attends to the earlier part's K/V through the cache, like a prefill chunk:
+        each part is a one-task fp16-cache piece (_PromptRows.one) at pos0 + a.
         Ordering is stream events only (main -> reduce before the collective, reduce -> main before the add); the
         partial stays referenced until the main stream has consumed it, so no allocator hand-over is needed."""
         c, dev = self.cfg, self.device
         s = int(prompt.numel())
-        if s < 1 or pos0 + s + 1 > ctx.max_len_buf:
-            raise ops.ZLError("prompt does not fit the task's KV buffer")
         num_split = max(1, int(os.environ.get("DUAL_STREAM_NUM_SPLIT", "2")))
         round_up = max(1, int(os.environ.get("DUAL_STREAM_SPLIT_ROUND_UP", "16")))
         part = -(-(-(-s // num_split)) // round_up) * round_up
         bounds = [(a, min(a + part, s)) for a in range(0, s, part)]
         tokens = prompt.to(device=dev, dtype=torch.int32).contiguous()
         pos = torch.arange(pos0, pos0 + s, dtype=torch.int32, device=dev)
+        parts = [_PromptRows.one(self, ctx, task, tokens[a:b], pos0 + a, pos=pos[a:b]) for a, b in bounds]
         hidden_all = ops.embedding(tokens, self.token_embedding, c.scale_emb)
         cos, sin = self._rope_tables(pos)
-        buf_lens = ctx.buf_lens[task:task + 1]
-        scale = 1.0 / math.sqrt(c.dim_head)
         main = torch.cuda.current_stream(dev)
         if "reduce_stream" not in self._bufs:
             self._bufs["reduce_stream"] = torch.cuda.Stream(device=dev, priority=int(os.environ.get("DUAL_STREAM_PRIORITY", "-1")))
@@ -1536,7 +1658,6 @@ class LLaMA:
             return partial
 
         for li, layer in enumerate(self.layers):
-            ka, va = ctx.k_addrs[li][task:task + 1], ctx.v_addrs[li][task:task + 1]
             for k, (a, b) in enumerate(bounds):
                 n = b - a
                 if li == 0:
@@ -1546,15 +1667,8 @@ class LLaMA:
                 qkv = layer.project_qkv(None, c.eps, normed=xn)
                 self.apply_qk_norm(layer, qkv)
                 q, kr, v = ops.rope_qk_cache(cos[a:b], sin[a:b], qkv, c.num_heads, c.num_kv_heads, c.dim_head, True)
-                ops.copy_to_rag_buffer2(pos[a:b].view(1, n), buf_lens, kr.view(1, n, c.num_kv_heads, c.dim_head),
-                                        v.view(1, n, c.num_kv_heads, c.dim_head), ka, va)
-                if c.dim_head == 128:
-                    att = ops.prefill_attention(q.view(n, c.num_heads, c.dim_head), ctx.kv[task][li, 0], ctx.kv[task][li, 1],
-                                                pos0 + a, c.num_kv_heads, scale)
-                else:
-                    mask, ws = self._prefill_mask(n, ctx.max_len_buf, pos0 + a)
-                    att = ops.multi_query_attention_rag_buffer(q.view(1, n, c.num_heads, c.dim_head), buf_lens, ka, va, mask,
-                                                               scale, ctx.max_len_buf, c.num_kv_heads, workspace=ws)
+                att = self._prompt_scatter_attend(parts[k], li, q.view(n, c.num_heads, c.dim_head),
+                                                  kr.view(n, c.num_kv_heads, c.dim_head), v.view(n, c.num_kv_heads, c.dim_head))
                 reduce_async(k, layer.row_partial(layer.attn_out, att.view(n, -1)))
             for k in range(len(bounds)):
                 xn, hidden[k] = ops.rmsnorm(hidden[k], layer.ln_ff, c.eps, x2=reduced(k))
@@ -1562,12 +1676,7 @@ class LLaMA:
         for k in range(len(bounds)):
             hidden[k] = ops.element_add_scale(hidden[k], reduced(k), 1.0, True)
         self.dual_stream_runs = getattr(self, "dual_stream_runs", 0) + 1
-        logits = self._prompt_logits_and_pick(ctx, task, hidden[-1][-1:])
-        ctx.positions[task] = pos0 + s
-        ctx.placement[task] = pos0 + s
-        ctx.valid_lens[task] = pos0 + s + 1
-        ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - (pos0 + s))
-        return logits
+        return self._prompt_tail(ctx, parts[-1], hidden[-1])        # the last part ends where the piece ends
 
     def prefill_batch(self, ctx: DynBatchContext, tasks, prompts, pos0=None, kv_history=None):
         """Prompt encode of several tasks in ONE pass through the layers (LLaMA::encode with the prompt rows of every task of the
@@ -1587,12 +1696,11 @@ class LLaMA:
         takes the call's last row as its sequence length, as the reference does for any forward.  Duplicate or out-of-range
         tasks, empty prompts and prompts that do not fit the buffers raise ZLError before any launch."""
         tasks, pos0, q8_history = self._check_prompt_batch("prefill_batch", ctx, tasks, prompts, pos0, kv_history)
-        return self._prefill_rows(ctx, tasks, prompts, pos0, q8_history=q8_history)
+        return self._prompt_tail(ctx, *self._prefill_rows(ctx, tasks, prompts, pos0, q8_history))
 
     def _check_prompt_batch(self, what, ctx: DynBatchContext, tasks, prompts, pos0, kv_history):
         """the argument checks of prefill_batch / score, before any launch -> (tasks, pos0 as int lists, q8_history)"""
-        self._check_kv_history(ctx, kv_history)
-        q8_history = bool(ctx.kv_quant and kv_history == "cache")
+        q8_history = self._check_kv_history(ctx, kv_history)
         tasks = [int(t) for t in tasks]
         n = len(tasks)
         pos0 = [0] * n if pos0 is None else [int(p) for p in pos0]
@@ -1601,11 +1709,7 @@ class LLaMA:
         if len(set(tasks)) != n or any(t < 0 or t >= ctx.tokens.numel() for t in tasks):
             raise ops.ZLError(f"{what}: tasks must be distinct indices of the batch")
         for t, pr, p0 in zip(tasks, prompts, pos0):
-            s = int(pr.numel())
-            if s < 1 or p0 < 0 or p0 + s + 1 > ctx.max_len_buf:
-                raise ops.ZLError(f"{what}: prompt of task {t} ({s} tokens at {p0}) does not fit the task's KV buffer")
-            if ctx.kv_quant and p0 != 0 and not q8_history:
-                raise ops.ZLError(f"{what}: a continued prompt into the INT8 KV cache goes through LLaMA.prefill(chunk=...)")
+            self._check_prompt_piece(what, ctx, t, int(pr.numel()), p0, q8_history)
         return tasks, pos0, q8_history
 
     def score(self, ctx: DynBatchContext, tasks, prompts, pos0=None, labels=None, kv_history=None):
@@ -1628,10 +1732,12 @@ class LLaMA:
         if self.tp:
             raise ops.ZLError("score: tensor parallelism is not supported")
         tasks, pos0, q8_history = self._check_prompt_batch("score", ctx, tasks, prompts, pos0, kv_history)
-        rows = ops.score_labels(prompts, labels)
-        if any(l != ops.SCORE_IGNORE and not 0 <= l < self.cfg.vocab_size for l in rows):
+        labels = ops.score_labels(prompts, labels)
+        if any(l != ops.SCORE_IGNORE and not 0 <= l < self.cfg.vocab_size for l in labels):
             raise ops.ZLError("score: a label lies outside the vocabulary")
-        return self._prefill_rows(ctx, tasks, prompts, pos0, q8_history=q8_history, score_labels=rows)
+        r, hidden = self._prefill_rows(ctx, tasks, prompts, pos0, q8_history, labels)
+        scored = self._score_rows(hidden, r.labels_dev, r.lens, r.last_rows)
+        return scored._replace(logits=self._prompt_tail(ctx, r, hidden))
 
     def _score_rows(self, hidden, labels_dev, lens, last_rows=None):
         """output_layernorm over all rows + the fused lm_head scoring; per-task sums / matches on the device"""
@@ -1656,214 +1762,108 @@ class LLaMA:
             sums, matches = d[0].float(), d[1] == 0
         return ScoreResult(r.logprob, r.lse, r.greedy, r.greedy_logit, cu, sums, matches, None)
 
-    def _prefill_chunk(self, ctx: DynBatchContext, task: int, prompt: torch.Tensor, pos0: int):
-        """The "encode part" of a task (LLaMA::encode with len_q = prompt length for one task:
-        src/model/llama.cpp:75-165, Attention::impl::NormalImpl::dynamic_batch_forward encode branch,
-        src/nn/attention/attention.cpp:846-964 / attn_encode_group :442-622): runs the whole prompt through
-        the layers, fills the task's KV buffers at slots 0..S-1, leaves the task ready for decode steps
-        (tokens <- greedy first token, positions = placement = S, valid_lens = S + 1) and returns the logits of
-        the last prompt position (1, vocab).  Sequence: separate RMSNorm, W4A16 GEMM (M = S: the M-tiled MFMA
-        kernel, the arithmetic of the reference's M > 40 dequant + GEMM branch), rope_qk_cache,
-        copy_to_rag_buffer2, causal MFMA attention (prefill_attention; other head sizes: the mask form of
-        multi_query_attention_rag_buffer).  The one-task case of _prefill_rows."""
-        s = int(prompt.numel())
-        if s < 1 or pos0 + s + 1 > ctx.max_len_buf:
-            raise ops.ZLError("prompt does not fit the task's KV buffer")
-        if ctx.kv_quant and pos0 != 0 and ctx.unquant_kv.get(task) is None:
-            # a later piece without the prompt's temporary unquantised buffers (prefill(chunk=...) keeps them): the reference
-            # falls back to de-quantising the cache there ("WARNING: de-quantize prompt kv cache!", attention.cpp:511-516)
-            raise ops.ZLError("chunked prefill into the INT8 KV cache goes through LLaMA.prefill(chunk=...)")
-        return self._prefill_rows(ctx, [task], [prompt], [pos0])
-
-    def _prefill_rows(self, ctx: DynBatchContext, tasks, prompts, pos0s, q8_history=False, score_labels=None):
-        """The layer loop of prompt encode over the rows of n tasks (checked by the callers): one task is _prefill_chunk's
-        launch sequence exactly; n > 1 gathers the per-row scatter tables and the attention tables once per call (one upload of
-        positions and plans), runs every linear over the summed rows, the K/V scatter with one "task" per row, one varlen
-        attention launch per layer, then one gather of the last rows, one lm_head and one pick for the n rows.
+    def _prefill_rows(self, ctx: DynBatchContext, tasks, prompts, pos0s, q8_history=False, labels=None):
+        """The layer loop of prompt encode over the rows of the call's tasks (checked by the callers) -> (_PromptRows, hidden rows
+        before the output norm).  Sequence: separate RMSNorm, W4A16 GEMM (M = rows: the M-tiled MFMA kernel, the arithmetic of
+        the reference's M > 40 dequant + GEMM branch) -- every linear over the summed rows --, rope_qk_cache, then the K/V scatter
+        and the attention of the call's route (_prompt_scatter_attend).  _prompt_tail finishes the call.
         q8_history (INT8 cache, head size 128): rows below a task's pos0 are read from the cache by the attention kernel
         (ops.prefill_attention_varlen_q8), for one task or several; no unquantised copy of earlier rows is used.
-        score_labels (LLaMA.score: one host label per row): the launches are the same, then every row is scored before the last
-        rows' logits and pick; the labels ride the call's int32 upload (n > 1; the one-task path has no such table and uploads the
-        labels on their own: one extra host-to-device copy).  Returns a ScoreResult then, else the logits."""
-        c, dev = self.cfg, self.device
-        n = len(tasks)
-        one = n == 1
-        lens = [int(pr.numel()) for pr in prompts]
-        total = sum(lens)
-        hkv, d = c.num_kv_heads, c.dim_head
-        scale = 1.0 / math.sqrt(d)
-        if one:
-            task, s, pos0 = tasks[0], lens[0], pos0s[0]
-            tokens = prompts[0].to(device=dev, dtype=torch.int32).contiguous()
-            pos = torch.arange(pos0, pos0 + s, dtype=torch.int32, device=dev)
-            placement = pos.view(1, s)
-            buf_lens = ctx.buf_lens[task:task + 1]
-            unq = ctx.unquant_kv.get(task) if ctx.kv_quant and not q8_history else None
-            plan = ops.prefill_varlen_plan([s], [pos0], [ctx.max_len_buf], dev) if q8_history else None
-            labels_dev = torch.tensor(score_labels, dtype=torch.int32).to(dev) if score_labels is not None else None
-        else:
-            tokens = torch.cat([pr.to(device=dev, dtype=torch.int32).reshape(-1) for pr in prompts])
-            ends = [p0 + s for p0, s in zip(pos0s, lens)]
-            cu = [0]
-            for s in lens:
-                cu.append(cu[-1] + s)
-            # one upload of the call's int32 and one of its int64 tables
-            pos_all = torch.tensor([p0 + r for p0, s in zip(pos0s, lens) for r in range(s)] + ends + lens + (score_labels or []),
-                                   dtype=torch.int32).to(dev)
-            pos, ends_dev, lens_dev = pos_all[:total], pos_all[total:total + n], pos_all[total + n:total + 2 * n]
-            labels_dev = pos_all[total + 2 * n:] if score_labels is not None else None
-            row_bytes = hkv * d * c.torch_dtype.itemsize
-            idx = torch.tensor(tasks + [t for t, s in zip(tasks, lens) for _ in range(s)] + [r - 1 for r in cu[1:]] +
-                               [r * row_bytes for r in cu[:-1]], dtype=torch.int64).to(dev)
-            tasks_dev, rows_dev, last_rows = idx[:n], idx[n:n + total], idx[n + total:2 * n + total]
-            kv_off = idx[2 * n + total:]                      # byte offset of each task's first row in the concatenated k / v
-            placement = pos.view(total, 1)                    # the K/V scatter: one "task" per row
-            buf_lens = ctx.buf_lens.index_select(0, rows_dev)
-            ka_rows, va_rows = ctx.k_addrs.index_select(1, rows_dev), ctx.v_addrs.index_select(1, rows_dev)
-            if ctx.kv_quant:
-                ks_rows, vs_rows = ctx.ks_addrs.index_select(1, rows_dev), ctx.vs_addrs.index_select(1, rows_dev)
-            if q8_history:                                    # history from the cache, own rows from the concatenated k / v
-                ka_t, va_t = ctx.k_addrs.index_select(1, tasks_dev), ctx.v_addrs.index_select(1, tasks_dev)
-                ks_t, vs_t = ctx.ks_addrs.index_select(1, tasks_dev), ctx.vs_addrs.index_select(1, tasks_dev)
-                att_pos0, len_bufs, len_bufs_dev = pos0s, [ctx.max_len_buf] * n, None
-            elif ctx.kv_quant:                                # attention over the call's own rows (fresh prompts only)
-                att_pos0, len_bufs, len_bufs_dev = [0] * n, lens, lens_dev
-            else:
-                ka_t, va_t = ctx.k_addrs.index_select(1, tasks_dev), ctx.v_addrs.index_select(1, tasks_dev)
-                att_pos0, len_bufs, len_bufs_dev = pos0s, [ctx.max_len_buf] * n, ctx.buf_lens.index_select(0, tasks_dev)
-            plan = ops.prefill_varlen_plan(lens, att_pos0, len_bufs, dev) if d == 128 else None
-        hidden = ops.embedding(tokens, self.token_embedding, c.scale_emb)
-        cos, sin = self._rope_tables(pos)
+        labels (LLaMA.score: one host label per row) are uploaded with the call's tables for _score_rows."""
+        c = self.cfg
+        r = _PromptRows.of(self, ctx, tasks, prompts, pos0s, q8_history, labels)
+        total = r.cu[-1]
+        hidden = ops.embedding(r.tokens, self.token_embedding, c.scale_emb)
+        cos, sin = self._rope_tables(r.pos)
         for li, layer in enumerate(self.layers):
             qkv = layer.project_qkv(hidden, c.eps)
             self.apply_qk_norm(layer, qkv)
-            q, k, v = ops.rope_qk_cache(cos, sin, qkv, c.num_heads, hkv, d, True)
-            q3, k3, v3 = q.view(total, c.num_heads, d), k.view(total, hkv, d), v.view(total, hkv, d)
-            if one:
-                att = self._prompt_attention_one(ctx, li, task, q3, k3, v3, pos, placement, buf_lens, pos0, unq, scale, plan)
-            elif q8_history:
-                # attn_encode_group with a quantised buffer and no prompt temporaries (attention.cpp:510-516): codes to the cache,
-                # then the history is dequantised where the kernel stages it; the call's own rows are read unquantised
-                ops.quant_copy_to_rag_buffer(pos, buf_lens, k3, v3, ka_rows[li], va_rows[li], ks_rows[li], vs_rows[li], len_q=1)
-                att = ops.prefill_attention_varlen_q8(q3, lens, att_pos0, k3, v3, ka_t[li], va_t[li], ks_t[li], vs_t[li], len_bufs,
-                                                      hkv, scale, plan=plan)
-            elif ctx.kv_quant:
-                # attn_encode_group with a quantised buffer (attention.cpp:494-510): the prompts attend to their own UNquantised
-                # rows -- the tables point into the concatenated k / v -- while the codes go to the cache
-                ops.quant_copy_to_rag_buffer(pos, buf_lens, k3, v3, ka_rows[li], va_rows[li], ks_rows[li], vs_rows[li], len_q=1)
-                att = self._prompt_attention_tasks(q3, lens, att_pos0, kv_off + k3.data_ptr(), kv_off + v3.data_ptr(), len_bufs,
-                                                   len_bufs_dev, plan, cu, scale)
-            else:
-                ops.copy_to_rag_buffer2(placement, buf_lens, k3.view(total, 1, hkv, d), v3.view(total, 1, hkv, d),
-                                        ka_rows[li], va_rows[li])
-                att = self._prompt_attention_tasks(q3, lens, att_pos0, ka_t[li], va_t[li], len_bufs, len_bufs_dev, plan, cu, scale)
+            q, k, v = ops.rope_qk_cache(cos, sin, qkv, c.num_heads, c.num_kv_heads, c.dim_head, True)
+            att = self._prompt_scatter_attend(r, li, q.view(total, c.num_heads, c.dim_head),
+                                              k.view(total, c.num_kv_heads, c.dim_head), v.view(total, c.num_kv_heads, c.dim_head))
             layer.attn_out_add(att.view(total, -1), hidden)
             layer.ff_add(hidden, c.eps)
-        scored = self._score_rows(hidden, labels_dev, lens, None if one else last_rows) if score_labels is not None else None
-        if one:
-            logits = self._prompt_logits_and_pick(ctx, task, hidden[s - 1:s])
-            ctx.positions[task] = pos0 + s
-            ctx.placement[task] = pos0 + s
-            ctx.valid_lens[task] = pos0 + s + 1
-            ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - (pos0 + s))
-            return logits if scored is None else scored._replace(logits=logits)
-        logits = self._prompt_logits_and_pick_rows(ctx, tasks_dev, hidden.index_select(0, last_rows))
-        ctx.positions.index_copy_(0, tasks_dev, ends_dev)
-        ctx.placement.index_copy_(0, tasks_dev, ends_dev)
-        ctx.valid_lens.index_copy_(0, tasks_dev, ends_dev + 1)
-        ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - max(ends))
-        return logits if scored is None else scored._replace(logits=logits)
+        return r, hidden
 
-    def _prompt_attention_tasks(self, q3, lens, pos0s, k_tab, v_tab, len_bufs, len_bufs_dev, plan, cu, scale):
-        """attention of n > 1 tasks' prompt rows q3 (total, H, D) against the buffers of the tables k_tab / v_tab (n pointers,
-        len_bufs rows each): one varlen launch (head size 128), or per task the mask form of multi_query_attention_rag_buffer"""
+    def _prompt_scatter_attend(self, r, li, q3, k3, v3):
+        """One layer's K/V scatter and causal attention for the rows r (_PromptRows): q3 (rows, H, D), k3 / v3 (rows, Hkv, D), rotated.
+        Scatter: copy_to_rag_buffer2 into an fp16 cache; into an INT8 cache the codes and scales, and with the prompt's temporaries
+        the unquantised rows into those as well.  Attention, by r.route, over
+          "cache"  the fp16 cache (rows below pos0 and the call's own);
+          "own"    the call's own unquantised k3 / v3: attn_encode_group with a quantised buffer (attention.cpp:494-510), the
+                   prompts attend to their UNquantised rows while the codes go to the cache;
+          "temp"   the chunked prompt's temporaries, which this piece's rows have just joined (attention.cpp:497-510);
+          "q8"     the INT8 cache below pos0, dequantised where the kernel stages it, and k3 / v3 from there on: a quantised buffer
+                   and no prompt temporaries (attention.cpp:510-516).
+        Head size 128: the MFMA kernels -- the one-task launch on the task's tensors, or one varlen launch over the tables of
+        several tasks; other head sizes: per task the mask form of multi_query_attention_rag_buffer."""
         c = self.cfg
-        if plan is not None:
-            return ops.prefill_attention_varlen(q3, lens, pos0s, k_tab, v_tab, plan.buf_lens, c.num_kv_heads, scale, plan=plan)
+        h, hkv, d = c.num_heads, c.num_kv_heads, c.dim_head
+        scale = 1.0 / math.sqrt(d)
+        k4, v4 = k3.view(*r.placement.shape, hkv, d), v3.view(*r.placement.shape, hkv, d)
+        if r.ks_rows is None:
+            ops.copy_to_rag_buffer2(r.placement, r.buf_lens, k4, v4, r.k_rows[li], r.v_rows[li])
+        else:
+            ops.quant_copy_to_rag_buffer(r.pos, r.buf_lens, k3, v3, r.k_rows[li], r.v_rows[li], r.ks_rows[li], r.vs_rows[li],
+                                         len_q=r.len_q)
+            if r.route == "temp":
+                ops.copy_to_rag_buffer2(r.placement, r.len_bufs_dev, k4, v4, r.k_tab[li], r.v_tab[li])
+        if d == 128:
+            if r.route == "q8":
+                return ops.prefill_attention_varlen_q8(q3, r.lens, r.att_pos0s, k3, v3, r.k_tab[li], r.v_tab[li], r.ks_tab[li],
+                                                       r.vs_tab[li], r.len_bufs, hkv, scale, plan=r.plan)
+            if r.plan is None:                            # one task: the launch takes the tensors themselves
+                k_buf, v_buf = (k3, v3) if r.route == "own" else (r.kv[li, 0], r.kv[li, 1])
+                return ops.prefill_attention(q3, k_buf, v_buf, r.att_pos0s[0], hkv, scale)
+            return ops.prefill_attention_varlen(q3, r.lens, r.att_pos0s, *r.att_tables(li, k3, v3), r.plan.buf_lens, hkv, scale,
+                                                plan=r.plan)
+        k_tab, v_tab = r.att_tables(li, k3, v3)
         att = torch.empty_like(q3)
-        for i, (s, p0) in enumerate(zip(lens, pos0s)):
-            a = cu[i]
-            mask, ws = self._prefill_mask(s, len_bufs[i], p0)
-            ops.multi_query_attention_rag_buffer(q3[a:a + s].view(1, s, c.num_heads, c.dim_head), len_bufs_dev[i:i + 1],
-                                                 k_tab[i:i + 1], v_tab[i:i + 1], mask, scale, len_bufs[i], c.num_kv_heads,
-                                                 out=att[a:a + s].view(1, s, c.num_heads, c.dim_head), workspace=ws)
+        for i, (s, p0) in enumerate(zip(r.lens, r.att_pos0s)):
+            a = r.cu[i]
+            mask, ws = self._prefill_mask(s, r.len_bufs[i], p0)
+            ops.multi_query_attention_rag_buffer(q3[a:a + s].view(1, s, h, d), r.len_bufs_dev[i:i + 1], k_tab[i:i + 1],
+                                                 v_tab[i:i + 1], mask, scale, r.len_bufs[i], hkv,
+                                                 out=att[a:a + s].view(1, s, h, d), workspace=ws)
         return att
 
-    def _prompt_attention_one(self, ctx, li, task, q3, k3, v3, pos, placement, buf_lens, pos0, unq, scale, q8_plan=None):
-        """K/V scatter + attention of one task's prompt rows (the launch sequence of the one-task encode)"""
-        c, dev = self.cfg, self.device
-        s = q3.shape[0]
-        ka, va = ctx.k_addrs[li][task:task + 1], ctx.v_addrs[li][task:task + 1]
-        if ctx.kv_quant:
-            # attn_encode_group with a quantised buffer (attention.cpp:494-510): the prompt attends to its own
-            # UNquantised K/V rows while their codes go to the cache
-            ops.quant_copy_to_rag_buffer(pos, buf_lens, k3, v3, ka, va, ctx.ks_addrs[li][task:task + 1],
-                                         ctx.vs_addrs[li][task:task + 1], len_q=s)
-            if q8_plan is not None:
-                # no prompt temporaries (attention.cpp:510-516): rows below pos0 come from the cache, dequantised in the kernel
-                return ops.prefill_attention_varlen_q8(q3, [s], [pos0], k3, v3, ka, va, ctx.ks_addrs[li][task:task + 1],
-                                                       ctx.vs_addrs[li][task:task + 1], [ctx.max_len_buf], c.num_kv_heads, scale,
-                                                       plan=q8_plan)
-            if unq is not None:
-                # chunked: this piece's rows join the prompt's unquantised buffers, the piece attends to all of them
-                tk, tv = unq[li, 0], unq[li, 1]
-                tl = torch.tensor([tk.shape[0]], dtype=torch.int32, device=dev)
-                ops.copy_to_rag_buffer2(placement, tl, k3.view(1, s, c.num_kv_heads, c.dim_head), v3.view(1, s, c.num_kv_heads, c.dim_head),
-                                        ops.make_ptr_table([tk]), ops.make_ptr_table([tv]))
-                if c.dim_head == 128:
-                    return ops.prefill_attention(q3, tk, tv, pos0, c.num_kv_heads, scale)
-                mask, ws = self._prefill_mask(s, tk.shape[0], pos0)
-                return ops.multi_query_attention_rag_buffer(q3.view(1, s, c.num_heads, c.dim_head), tl, ops.make_ptr_table([tk]),
-                                                            ops.make_ptr_table([tv]), mask, scale, tk.shape[0], c.num_kv_heads,
-                                                            workspace=ws)
-            if c.dim_head == 128:
-                return ops.prefill_attention(q3, k3, v3, 0, c.num_kv_heads, scale)
-            mask, ws = self._prefill_mask(s, s, 0)
-            return ops.multi_query_attention_rag_buffer(
-                q3.view(1, s, c.num_heads, c.dim_head), torch.tensor([s], dtype=torch.int32, device=dev),
-                ops.make_ptr_table([k3]), ops.make_ptr_table([v3]), mask, scale, s, c.num_kv_heads, workspace=ws)
-        ops.copy_to_rag_buffer2(placement, buf_lens, k3.view(1, s, c.num_kv_heads, c.dim_head),
-                                v3.view(1, s, c.num_kv_heads, c.dim_head), ka, va)
-        if c.dim_head == 128:
-            return ops.prefill_attention(q3, ctx.kv[task][li, 0], ctx.kv[task][li, 1], pos0, c.num_kv_heads, scale)
-        mask, ws = self._prefill_mask(s, ctx.max_len_buf, pos0)
-        return ops.multi_query_attention_rag_buffer(q3.view(1, s, c.num_heads, c.dim_head), buf_lens, ka, va, mask,
-                                                    scale, ctx.max_len_buf, c.num_kv_heads, workspace=ws)
+    def _prompt_tail(self, ctx, r, hidden):
+        """The end of a prompt-encode call over the rows r (_PromptRows): lm_head on the tasks' last rows, the greedy first tokens
+        into ctx.tokens, positions = placement = end, valid_lens = end + 1, steps_left bounded -> logits (tasks, vocab).  One task
+        writes in place (r.tasks_dev is None); several go through index_copy_, since greedy_advance / argmax_advance write
+        consecutive rows."""
+        if r.tasks_dev is None:
+            task, end = r.tasks[0], r.ends[0]
+            logits = self._prompt_logits_and_pick(hidden[-1:], ctx.tokens[task:task + 1])
+            ctx.positions[task] = end
+            ctx.placement[task] = end
+            ctx.valid_lens[task] = end + 1
+        else:
+            picks = torch.empty(len(r.tasks), dtype=torch.int32, device=self.device)
+            logits = self._prompt_logits_and_pick(hidden.index_select(0, r.last_rows), picks)
+            ctx.tokens.index_copy_(0, r.tasks_dev, picks)
+            ctx.positions.index_copy_(0, r.tasks_dev, r.ends_dev)
+            ctx.placement.index_copy_(0, r.tasks_dev, r.ends_dev)
+            ctx.valid_lens.index_copy_(0, r.tasks_dev, r.ends_dev + 1)
+        ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - max(r.ends))
+        return logits
 
-    def _prompt_logits_and_pick_rows(self, ctx, tasks_dev, last_hidden):
-        """_prompt_logits_and_pick for the last rows of n tasks (tasks_dev: their int64 indices): the picks go to a temporary and
-        are scattered to ctx.tokens, since greedy_advance / argmax_advance write consecutive rows"""
+    def _prompt_logits_and_pick(self, last_hidden, picks):
+        """logits of the prompts' last rows and the first generated tokens into picks (n int32): the pick rides the lm_head launch
+        (zl_gemm_nt_small_m_argmax leaves one candidate per wavefront, zl_greedy_advance reduces them -- first index on ties,
+        as torch.argmax) instead of three torch launches over the 128 k logits; TP picks on the gathered rows (zl_argmax_advance)"""
         n = last_hidden.shape[0]
-        picks = torch.empty(n, dtype=torch.int32, device=self.device)
         if self.tp:
             logits = self._logits(last_hidden)
             ops.argmax_advance(logits, tokens=picks)
-        else:
-            key = ("argmax", n)
-            if key not in self._bufs:
-                self._bufs[key] = (ops.argmax_workspace(n, self.cfg.vocab_size, self.device),
-                                   torch.empty(n, dtype=torch.int64, device=self.device))
-            ws = self._bufs[key][0]
-            logits = self._logits(last_hidden, argmax_ws=ws)
-            ops.greedy_advance(ws, n, self.cfg.vocab_size, tokens=picks)
-        ctx.tokens.index_copy_(0, tasks_dev, picks)
-        return logits
-
-    def _prompt_logits_and_pick(self, ctx, task, last_hidden):
-        """logits of a prompt's last row and the first generated token into ctx.tokens[task]: the pick rides the lm_head launch
-        (zl_gemm_nt_small_m_argmax leaves one candidate per wavefront, zl_greedy_advance reduces them -- first index on ties,
-        as torch.argmax) instead of three torch launches over the 128 k logits; TP picks on the gathered row (zl_argmax_advance)"""
-        if self.tp:
-            logits = self._logits(last_hidden)
-            ops.argmax_advance(logits[:1], tokens=ctx.tokens[task:task + 1])
             return logits
-        key = ("argmax", 1)
+        key = ("argmax", n)
         if key not in self._bufs:
-            self._bufs[key] = (ops.argmax_workspace(1, self.cfg.vocab_size, self.device),
-                               torch.empty(1, dtype=torch.int64, device=self.device))
+            self._bufs[key] = (ops.argmax_workspace(n, self.cfg.vocab_size, self.device),
+                               torch.empty(n, dtype=torch.int64, device=self.device))
         ws = self._bufs[key][0]
         logits = self._logits(last_hidden, argmax_ws=ws)
-        ops.greedy_advance(ws, 1, self.cfg.vocab_size, tokens=ctx.tokens[task:task + 1])
+        ops.greedy_advance(ws, n, self.cfg.vocab_size, tokens=picks)
         return logits
 
     def step_greedy(self, ctx: DynBatchContext, skip_gemv=False):

@@ -1538,6 +1538,29 @@ def prefill_varlen_plan(lens, pos0, buf_lens, device):
     return PrefillVarlenPlan(lens, pos0, buf_lens, device)
 
 
+def _varlen_args(what, q, lens, pos0, buf_lens, plan, out, groups):
+    """the checks prefill_attention_varlen and prefill_attention_varlen_q8 share, in `what`'s name: q's dtype, the plan against the
+    host lists (made here when the caller has none), q's rows against the plan, the plan's device, `out`; the ZL_PREFILL_GROUPS
+    default of `groups` -> (plan, out, groups)"""
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError(f"{what}: fp16 / bf16 only")
+    if plan is None:
+        plan = prefill_varlen_plan(lens, pos0, buf_lens, q.device)
+    elif plan.lens != [int(x) for x in lens] or plan.pos0 != [int(x) for x in pos0] or plan.buf_lens != [int(x) for x in buf_lens]:
+        raise ZLError(f"{what}: the plan was made for other lengths")
+    total_q, h, d = q.shape
+    if total_q != plan.total_q:
+        raise ZLError(f"{what}: q has {total_q} rows, the lengths add up to {plan.total_q}")
+    if plan.tables.device != q.device:
+        raise ZLError(f"{what}: the plan lives on another device")
+    if out is None:
+        out = torch.empty_like(q)
+    else:
+        _chk_out(out.view(total_q, -1), total_q, h * d, q.dtype, q.device, what)
+    groups = int(os.environ.get("ZL_PREFILL_GROUPS", "0") or 0) if groups is None else groups     # 0: the launcher's choice
+    return plan, out, groups
+
+
 def prefill_attention_varlen(q, lens, pos0, k_addrs, v_addrs, buf_lens, num_kv_heads, scale, bshd=True, out=None, groups=None,
                              plan=None):
     """Causal attention of B tasks' prompt chunks in one launch (attn_encode_group's per-task flash-attention loop,
@@ -1546,25 +1569,11 @@ def prefill_attention_varlen(q, lens, pos0, k_addrs, v_addrs, buf_lens, num_kv_h
     which already hold the chunks' own rows.  lens / pos0 / buf_lens are host ints (checked here); `plan` (prefill_varlen_plan of
     the same lists) spares the upload when several layers share it.  Per task bit-identical to prefill_attention(.., groups)."""
     _chk_cuda(q, k_addrs, v_addrs)
-    if q.dtype not in (torch.float16, torch.bfloat16):
-        raise ZLError("prefill_attention_varlen: fp16 / bf16 only")
-    if plan is None:
-        plan = prefill_varlen_plan(lens, pos0, buf_lens, q.device)
-    elif plan.lens != [int(x) for x in lens] or plan.pos0 != [int(x) for x in pos0] or plan.buf_lens != [int(x) for x in buf_lens]:
-        raise ZLError("prefill_attention_varlen: the plan was made for other lengths")
+    plan, out, groups = _varlen_args("prefill_attention_varlen", q, lens, pos0, buf_lens, plan, out, groups)
     total_q, h, d = q.shape
-    if total_q != plan.total_q:
-        raise ZLError(f"prefill_attention_varlen: q has {total_q} rows, the lengths add up to {plan.total_q}")
     for t in (k_addrs, v_addrs):
         if t.dtype != torch.int64 or t.numel() != plan.b:
             raise ZLError("prefill_attention_varlen: one int64 K / V pointer per task")
-    if plan.tables.device != q.device:
-        raise ZLError("prefill_attention_varlen: the plan lives on another device")
-    if out is None:
-        out = torch.empty_like(q)
-    else:
-        _chk_out(out.view(total_q, -1), total_q, h * d, q.dtype, q.device, "prefill_attention_varlen")
-    groups = int(os.environ.get("ZL_PREFILL_GROUPS", "0") or 0) if groups is None else groups     # 0: the launcher's choice
     check(lib().zl_prefill_attn_varlen(_p(q), _p(plan.cu_seqlens_q), _p(plan.pos0_dev), _p(plan.buf_lens_dev), _p(k_addrs),
                                        _p(v_addrs), _p(out), _p(plan.work), _i(plan.n_work), _i(plan.b), _i(total_q), _i(h),
                                        _i(num_kv_heads), _i(d), _f(scale), C.c_int(int(bshd)), C.c_int(_dt(q)), C.c_int(groups),
@@ -1605,35 +1614,21 @@ def prefill_attention_varlen_q8(q, lens, pos0, k_new, v_new, k_addrs, v_addrs, k
     tasks' code (buf_lens[i], Hkv, D) u8 and scale (buf_lens[i], Hkv) fp32 buffers, BSHD, or the per-task tensors themselves (then
     checked; None for a task with pos0 = 0).  D = 128.  lens / pos0 / buf_lens / plan as for prefill_attention_varlen."""
     _chk_cuda(q, k_new, v_new)
-    if q.dtype not in (torch.float16, torch.bfloat16):
-        raise ZLError("prefill_attention_varlen_q8: fp16 / bf16 only")
     if q.dim() != 3 or k_new.dim() != 3:
         raise ZLError("prefill_attention_varlen_q8: q (total_q, H, D), k_new / v_new (total_q, Hkv, D)")
     total_q, h, d = q.shape
     if d != 128:
         raise ZLError(f"prefill_attention_varlen_q8: head size {d}: only 128 (the mask-form attention reads a chunk's own rows as codes)")
-    if plan is None:
-        plan = prefill_varlen_plan(lens, pos0, buf_lens, q.device)
-    elif plan.lens != [int(x) for x in lens] or plan.pos0 != [int(x) for x in pos0] or plan.buf_lens != [int(x) for x in buf_lens]:
-        raise ZLError("prefill_attention_varlen_q8: the plan was made for other lengths")
-    if total_q != plan.total_q:
-        raise ZLError(f"prefill_attention_varlen_q8: q has {total_q} rows, the lengths add up to {plan.total_q}")
+    plan, out, groups = _varlen_args("prefill_attention_varlen_q8", q, lens, pos0, buf_lens, plan, out, groups)
     if num_kv_heads < 1 or h % num_kv_heads:
         raise ZLError("prefill_attention_varlen_q8: H must be a multiple of Hkv")
     for t in (k_new, v_new):
         if tuple(t.shape) != (total_q, num_kv_heads, d) or t.dtype != q.dtype or t.device != q.device:
             raise ZLError("prefill_attention_varlen_q8: k_new / v_new: (total_q, Hkv, D) rows of q's dtype on q's device")
-    if plan.tables.device != q.device:
-        raise ZLError("prefill_attention_varlen_q8: the plan lives on another device")
     k_tab = _q8_cache_table(k_addrs, plan, num_kv_heads, d, torch.uint8, "k codes", q.device)
     v_tab = _q8_cache_table(v_addrs, plan, num_kv_heads, d, torch.uint8, "v codes", q.device)
     ks_tab = _q8_cache_table(ks_addrs, plan, num_kv_heads, 0, torch.float32, "k scales", q.device)
     vs_tab = _q8_cache_table(vs_addrs, plan, num_kv_heads, 0, torch.float32, "v scales", q.device)
-    if out is None:
-        out = torch.empty_like(q)
-    else:
-        _chk_out(out.view(total_q, -1), total_q, h * d, q.dtype, q.device, "prefill_attention_varlen_q8")
-    groups = int(os.environ.get("ZL_PREFILL_GROUPS", "0") or 0) if groups is None else groups     # 0: the launcher's choice
     check(lib().zl_prefill_attn_varlen_q8(_p(q), _p(plan.cu_seqlens_q), _p(plan.pos0_dev), _p(plan.buf_lens_dev), _p(k_tab),
                                           _p(v_tab), _p(ks_tab), _p(vs_tab), _p(k_new), _p(v_new), _p(out), _p(plan.work),
                                           _i(plan.n_work), _i(plan.b), _i(total_q), _i(h), _i(num_kv_heads), _i(d), _f(scale),
