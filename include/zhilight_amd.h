@@ -500,6 +500,21 @@ int zl_decode_attn_ex(const uint16_t* q, const int32_t* buf_lens, const uint16_t
                       uint16_t* out, void* workspace, int64_t b, int64_t len_q, int64_t h, int64_t hkv,
                       int64_t d, float scale, int64_t max_len_buf, int bshd, int dtype, int algo, zl_stream_t s);
 
+/* Causal ("staircase") decode attention: the len_q rows of task b are the last token and len_q - 1 draft tokens of a speculative
+ * step, row qi sees the keys j < min(buf_lens[b], valid_lens[b] + qi) -- what zl_decode_attn computes with the int8 mask
+ * mask[b][qi, j] = j < valid_lens[b] + qi, on the matrix-core kernel and with ONE pass over the task's K / V for all of its rows
+ * (posing every row as a task of its own streams them len_q times; the mask route runs on the VALU kernel).  The reference verifies
+ * draft tokens through its prompt path (SessionGenerator.feed + rollback_speculative, zhilight/session_generator.py:25-66).
+ * q / out (B, len_q, H, D) T, fp16 or bf16, BSHD or BHSD buffers; D == 128 (ZL_ESHAPE otherwise), len_q <= 32 (ZL_ELIMIT);
+ * len_q * H / Hkv rows beyond 16 run as 16-row tiles of the same launch, each walking only the keys its last row sees.
+ * The slots [valid_lens[b], valid_lens[b] + len_q - 1) must hold this step's K / V rows; slots beyond are never read.
+ * Two launches (split kernel + merge) as zl_decode_attn, same split length and workspace (zl_decode_attn_workspace_bytes(b, len_q,
+ * h, d, max_len_buf)); at len_q == 1 the result is zl_decode_attn(mask = NULL, valid_lens)'s bit for bit.  No allocation, no sync. */
+int zl_decode_attn_causal(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs,
+                          const uint16_t* const* v_bufs, const int32_t* valid_lens, uint16_t* out, void* workspace,
+                          int64_t b, int64_t len_q, int64_t h, int64_t hkv, int64_t d, float scale, int64_t max_len_buf,
+                          int bshd, int dtype, zl_stream_t s);
+
 /* Fused decode attention front end (len_q == 1 per task, prefix visibility): rope_qk_cache +
  * copy_to_rag_buffer2 + multi_query_attention_rag_buffer in one pass over the fused qkv rows
  * (B, (H + 2 Hkv) D).  q and the new k are rotated with the cached cos/sin (one rounding to T, as the
@@ -926,6 +941,17 @@ int zl_sort_pairs_i32(const int32_t* keys, const int32_t* values, int32_t* keys_
  * form that never writes the pick's logits pass for <= 4 rows. */
 int zl_argmax_advance(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, int32_t* tokens, int32_t* positions, int32_t* placement,
                       int32_t* valid_lens, int64_t* next_tokens, zl_stream_t s);
+/* Greedy acceptance of a speculative step + the roll-back of the batch state.  logits: (b * len_q, n) rows, task-major, row stride ld
+ * elements, type = ZL_T_F16 / ZL_T_BF16 / ZL_T_F32; drafts (b, len_q - 1) int32, len_q >= 2.  picks[t, i] = arg-max of row (t, i)
+ * under zl_argmax_advance's rule (first index of the largest value, NaN largest); accepted[t] = the largest n <= len_q - 1 with
+ * drafts[t, j] == picks[t, j] for all j < n; out_tokens (b, len_q) int32 = picks[t, 0 .. n], -1 behind them; tokens[t] = picks[t, n],
+ * positions / placement / valid_lens += n + 1 (any of the four may be null).  The K / V rows of rejected drafts stay where they are,
+ * beyond the new valid_lens -- the reference's drop_token (sess_drop_speculative, src/generator/batch_generator.cpp:843-852).
+ * TWO launches: zl_argmax_advance's kernel for the picks (one 1024-thread workgroup per row streams the 128 k logits of all rows
+ * at once; an acceptance inside it would need the rows of a task to meet through a counter in memory) and one thread per task for
+ * the prefix match over its len_q int32 picks.  Ordinary vector stores only; no allocation, no sync. */
+int zl_spec_accept(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts, int32_t* tokens,
+                   int32_t* positions, int32_t* placement, int32_t* valid_lens, int32_t* accepted, int32_t* out_tokens, zl_stream_t s);
 /* The logit post-processing of the reference's batch generator (src/generator/beam_util.cu, 3rd/bmengine/bmengine/functions/{softmax,topk}.cu):
  * what src/generator/batch_generator.cpp calls between a decode step and its host-side search, so that the py_export surface (zhilight.C)
  * links against this boundary.  Rows of n logits of type ZL_T_F16 / ZL_T_BF16 / ZL_T_F32; fp32 arithmetic, one rounding to T.

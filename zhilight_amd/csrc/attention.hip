@@ -59,6 +59,9 @@ struct AttnParams {
     // (no merge launch, no merging prologue); la_cnt is all zero between launches (the last arriver resets its word)
     int la;
     int* la_cnt;
+    // causal ("staircase") form of k_decode_attn_mfma (zl_decode_attn_causal): query row qi of a task sees valid_lens[b] + qi keys;
+    // the 16-row tiles of its len_q * n_rep rows are folded into grid.y (blockIdx.y = tile * hkv + kv head)
+    int causal;
 };
 
 typedef _Float16 hv2 __attribute__((ext_vector_type(2)));
@@ -845,14 +848,24 @@ __device__ __forceinline__ void attn_tail_la(const AttnParams& p, float* xw, int
 // multi_query_attention_rag_buffer is handed, attention_kernel.cu:1252-1457): every key of the buffer is walked, a chunk's 32
 // visibility bytes travel with its K / V loads (one byte per lane) and become a wave-uniform 32-bit word by ballot; an invisible
 // key scores -inf AND its V row is zeroed before the product (a buffer's tail is not initialised: 0 x NaN must not reach the MFMA).
-template <int DT, int NW = 4, bool LA = false, int PF = 1, bool MASKED = false>
+// CAUSAL (several draft rows per task, zl_decode_attn_causal): query row qi sees valid_lens[b] + qi keys, so one pass over a task's K / V
+// serves all of its rows.  The row of a score is lane-constant (r = lane & 15), hence the row's limit is one register compared where
+// the prefix form compares t1; a 16-row tile walks the keys its LAST row sees, rows that see none of a split leave (0, -1e20, 0)
+// records the merge never reads (k_decode_attn_combine counts a row's splits from its own limit).  The keys a later row sees and an
+// earlier one does not were written this step, so they are finite and need no V zeroing (the mask form's 0 x NaN problem).
+template <int DT, int NW = 4, bool LA = false, int PF = 1, bool MASKED = false, bool CAUSAL = false>
 __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL_ATTN8_OCC(NW)) void k_decode_attn_mfma(const AttnParams p) {
     // (MASKED: two workgroups per SIMD set -- under the prefix form's 128-register budget the visibility word sent the V set to scratch)
     static_assert(!MASKED || (!LA && PF == 1), "the mask form exists for the two-launch route only");
+    static_assert(!CAUSAL || (!LA && PF == 1 && !MASKED && NW == 4), "the causal form exists for the two-launch route only");
     __shared__ __attribute__((aligned(16))) uint16_t vs[NW][32 * kMVS];     // 9 KB per wave (36 / 72 KB); reused for the wave merge
-    const int b = blockIdx.z, hk = blockIdx.y, split = blockIdx.x;
+    const int b = blockIdx.z, hk = CAUSAL ? (int)(blockIdx.y % (unsigned)p.hkv) : (int)blockIdx.y, split = blockIdx.x;
+    // this workgroup's query rows: [row0, row0 + nrows) of the task's len_q * n_rep (one tile of 16 in the causal form)
+    const int row0 = CAUSAL ? 16 * (int)(blockIdx.y / (unsigned)p.hkv) : 0;
+    const int nrows = CAUSAL ? min(16, p.rows - row0) : p.rows;
     const int len = p.buf_lens[b];
-    const int vlen_in = MASKED ? 0x7fffffff : p.valid_lens[b];
+    // CAUSAL: the tile's last row sees the most keys
+    const int vlen_in = MASKED ? 0x7fffffff : CAUSAL ? p.valid_lens[b] + (row0 + nrows - 1) / p.n_rep : p.valid_lens[b];
     const int8_t* mrow = nullptr;
     if constexpr (MASKED) {
         size_t mask_off = 0;
@@ -926,11 +939,13 @@ __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL
 
     // Q^T fragments: query row m = r -> (qi, head)
     uint4 qf[4];
+    int rlim = t1;                                     // CAUSAL: first key this lane's query row does not see
     {
         uint4 z = make_uint4(0, 0, 0, 0);
-        const bool live = r < p.rows;
-        const int rr = live ? r : 0;
+        const bool live = r < nrows;
+        const int rr = row0 + (live ? r : 0);
         const int qi = rr / p.n_rep, head = hk * p.n_rep + rr % p.n_rep;
+        if constexpr (CAUSAL) rlim = min(t1, p.valid_lens[b] + qi);
         const uint16_t* qp = p.q + (((size_t)b * p.len_q + qi) * p.h + head) * kMD + 8 * kq;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -984,7 +999,7 @@ __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int key = cur + 16 * blk + 4 * kq + i;
-                bool vis = key < t1;
+                bool vis = key < (CAUSAL ? rlim : t1);
                 if constexpr (MASKED) vis = (vbits >> (16 * blk + 4 * kq + i)) & 1u;      // the ballot already holds key < t1
                 sv[blk][i] = vis ? st[blk][i] * p.scale : -INFINITY;
                 mloc = fmaxf(mloc, sv[blk][i]);
@@ -1069,7 +1084,7 @@ __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL
     l_run += __shfl_xor(l_run, 32, 64);
     __syncthreads();
     float* xw = reinterpret_cast<float*>(&vs[0][0]);       // [wave][16 rows][D + 2]
-    if (r < p.rows) {
+    if (r < nrows) {
         float* dst = xw + ((size_t)wave * 16 + r) * (kMD + 2);
 #pragma unroll
         for (int db = 0; db < 8; ++db) *reinterpret_cast<f4v*>(dst + 16 * db + 4 * kq) = o[db];
@@ -1088,7 +1103,7 @@ __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL
 #endif
         return;
     }
-    for (int idx = threadIdx.x; idx < p.rows * kMD; idx += NW * 64) {
+    for (int idx = threadIdx.x; idx < nrows * kMD; idx += NW * 64) {
         const int i = idx / kMD, d = idx % kMD;
         const float* src = xw + (size_t)i * (kMD + 2);
         constexpr int WS = 16 * (kMD + 2);
@@ -1102,7 +1117,7 @@ __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL
             a = __builtin_fmaf(src[w * WS + d], f, a);
             lt = __builtin_fmaf(src[w * WS + kMD + 1], f, lt);
         }
-        const int qi = i / p.n_rep, head = hk * p.n_rep + i % p.n_rep;
+        const int qi = (row0 + i) / p.n_rep, head = hk * p.n_rep + (row0 + i) % p.n_rep;
         const size_t rec = (((size_t)b * p.len_q + qi) * p.h + head) * p.max_splits + split;
         if (p.half_partials) {
             uint16_t* hp = reinterpret_cast<uint16_t*>(p.ws);
@@ -1343,7 +1358,8 @@ __global__ void k_decode_attn_combine(const AttnParams p) {
     const int vh = blockIdx.x;
     const int b = vh / (p.len_q * p.h);
     const int len = p.buf_lens[b];
-    const int vlen_in = p.valid_lens ? p.valid_lens[b] : 0x7fffffff;
+    // causal form: row qi's splits end at its own limit valid + qi (the splits beyond hold no record of it, or an empty one)
+    const int vlen_in = p.valid_lens ? p.valid_lens[b] + (p.causal ? (vh / p.h) % p.len_q : 0) : 0x7fffffff;
     const int elen = p.mask ? len : min(len, vlen_in);
     const int ns = min((elen + p.split_len - 1) / p.split_len, kMaxS);
     const int d = threadIdx.x;
@@ -1505,7 +1521,7 @@ int zl_decode_attn_ex(const uint16_t* q, const int32_t* buf_lens, const uint16_t
     ZL_CHECK_ARG((int64_t)p.b * p.passes <= 65535 && hkv <= 65535, ZL_ELIMIT);
     hipStream_t hs = (hipStream_t)s;
     p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr;
+    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
     {   // decode fast path on the matrix cores: all query rows of a kv head in one 16-row MFMA block
         // with the reference's visibility mask instead of prefix lengths: the same kernel's mask form, for one query row per task
         if (algo != 1 && (!mask || (len_q == 1 && !valid_lens)) && d == kMD && p.rows <= 16) {
@@ -1534,6 +1550,39 @@ int zl_decode_attn_ex(const uint16_t* q, const int32_t* buf_lens, const uint16_t
     ZL_ATTN_D(ZL_BF16, false)
 }
 
+int zl_decode_attn_causal(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs, const uint16_t* const* v_bufs,
+                          const int32_t* valid_lens, uint16_t* out, void* workspace, int64_t b, int64_t len_q, int64_t h, int64_t hkv,
+                          int64_t d, float scale, int64_t max_len_buf, int bshd, int dtype, zl_stream_t s) {
+    ZL_CHECK_ARG(q && buf_lens && k_bufs && v_bufs && valid_lens && out && workspace, ZL_EINVAL);
+    ZL_CHECK_ARG(b > 0 && len_q > 0 && h > 0 && hkv > 0 && d > 0 && max_len_buf > 0, ZL_EINVAL);
+    ZL_CHECK_ARG(h % hkv == 0 && d == kMD, ZL_ESHAPE);                                     // the matrix-core kernel
+    ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
+    ZL_CHECK_ARG(len_q <= 32, ZL_ELIMIT);
+    AttnParams p;
+    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.mask = nullptr; p.valid_lens = valid_lens;
+    p.out = out; p.ws = (float*)workspace;
+    p.b = (int)b; p.len_q = (int)len_q; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
+    p.rows = p.len_q * p.n_rep; p.passes = 1;
+    // the split length of zl_decode_attn over the same b tasks: at len_q == 1 the records and the merge are that launch's
+    p.split_len = attn_split_len(b, hkv, max_len_buf);
+    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
+    ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
+    const int64_t tiles = (p.rows + 15) / 16;
+    ZL_CHECK_ARG(b <= 65535 && hkv * tiles <= 65535 && b * len_q * h < ((int64_t)1 << 31), ZL_ELIMIT);
+    p.scale = scale; p.bshd = bshd;
+    p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
+    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr; p.causal = 1;
+    hipStream_t hs = (hipStream_t)s;
+    const dim3 grid((unsigned)p.max_splits, (unsigned)(hkv * tiles), (unsigned)b);
+    if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_mfma<ZL_F16, 4, false, 1, false, true>), grid, dim3(256), 0, hs, p);
+    else hipLaunchKernelGGL((k_decode_attn_mfma<ZL_BF16, 4, false, 1, false, true>), grid, dim3(256), 0, hs, p);
+    int e = zl_launch_status();
+    if (e) return e;
+    if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_combine<ZL_F16, kMD>), dim3((unsigned)(b * len_q * h)), dim3(kMD), 0, hs, p);
+    else hipLaunchKernelGGL((k_decode_attn_combine<ZL_BF16, kMD>), dim3((unsigned)(b * len_q * h)), dim3(kMD), 0, hs, p);
+    return zl_launch_status();
+}
+
 int64_t zl_decode_attn_split_len(int64_t b, int64_t hkv, int64_t max_len_buf) {
     if (b <= 0 || hkv <= 0 || max_len_buf <= 0) return ZL_EINVAL;
     return attn_split_len(b, hkv, max_len_buf);
@@ -1556,7 +1605,7 @@ int zl_decode_attn_splits(const uint16_t* q, const int32_t* buf_lens, const uint
     ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
     p.scale = scale; p.bshd = bshd;
     p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr;
+    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
     const dim3 grid((unsigned)p.max_splits, (unsigned)hkv, (unsigned)b);
     if (dtype == ZL_F16) hipLaunchKernelGGL(k_decode_attn_mfma<ZL_F16>, grid, dim3(256), 0, (hipStream_t)s, p);
     else hipLaunchKernelGGL(k_decode_attn_mfma<ZL_BF16>, grid, dim3(256), 0, (hipStream_t)s, p);
@@ -1579,7 +1628,7 @@ int zl_decode_attn_splits_h(const uint16_t* q, const int32_t* buf_lens, const ui
     ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
     p.scale = scale; p.bshd = bshd;
     p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 1; p.la = 0; p.la_cnt = nullptr;
+    p.k_scales = p.v_scales = nullptr; p.half_partials = 1; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
     const dim3 grid((unsigned)p.max_splits, (unsigned)hkv, (unsigned)b);
     hipLaunchKernelGGL(k_decode_attn_mfma<ZL_F16>, grid, dim3(256), 0, (hipStream_t)s, p);
     return zl_launch_status();
@@ -1601,7 +1650,7 @@ int zl_decode_attn_splits_h_mask(const uint16_t* q, const int32_t* buf_lens, con
     ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
     p.scale = scale; p.bshd = bshd;
     p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 1; p.la = 0; p.la_cnt = nullptr;
+    p.k_scales = p.v_scales = nullptr; p.half_partials = 1; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
     const dim3 grid((unsigned)p.max_splits, (unsigned)hkv, (unsigned)b);
     hipLaunchKernelGGL((k_decode_attn_mfma<ZL_F16, 4, false, 1, true>), grid, dim3(256), 0, (hipStream_t)s, p);
     return zl_launch_status();
@@ -1620,7 +1669,7 @@ int zl_decode_attn_combine_h(const void* workspace, const int32_t* buf_lens, con
     ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
     p.scale = 0.f; p.bshd = 1;
     p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 1; p.la = 0; p.la_cnt = nullptr;
+    p.k_scales = p.v_scales = nullptr; p.half_partials = 1; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
     hipLaunchKernelGGL(k_decode_attn_combine_h, dim3((unsigned)(b * h)), dim3(kMD), 0, (hipStream_t)s, p);
     return zl_launch_status();
 }
@@ -1679,7 +1728,7 @@ int zl_decode_attn_la(const uint16_t* q, const int32_t* buf_lens, const uint16_t
     AttnParams p;
     p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.mask = nullptr; p.valid_lens = valid_lens;
     p.out = out;
-    p.la = 1; p.la_cnt = reinterpret_cast<int*>(workspace);
+    p.la = 1; p.la_cnt = reinterpret_cast<int*>(workspace); p.causal = 0;
     p.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + la_counter_bytes(b, hkv));
     p.b = (int)b; p.len_q = 1; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
     p.rows = p.n_rep; p.passes = 1;
@@ -1730,7 +1779,7 @@ int zl_decode_attn_fused(const float* cosv, const float* sinv, const uint16_t* q
     ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
     p.scale = scale; p.bshd = bshd;
     p.qkv = qkv; p.cosv = cosv; p.sinv = sinv; p.placement = placement; p.k_bufs_w = k_bufs; p.v_bufs_w = v_bufs; p.neox = neox;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr;
+    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
     ZL_CHECK_ARG((int64_t)p.b * p.passes <= 65535 && hkv <= 65535, ZL_ELIMIT);
     hipStream_t hs = (hipStream_t)s;
     if (dtype == ZL_F16) { ZL_ATTN_D(ZL_F16, true) }
@@ -1761,7 +1810,7 @@ int zl_decode_attn_quant_ex(const uint16_t* q, const int32_t* buf_lens, const ui
     p.q = q; p.buf_lens = buf_lens;
     p.k_bufs = reinterpret_cast<const uint16_t* const*>(k_bufs);
     p.v_bufs = reinterpret_cast<const uint16_t* const*>(v_bufs);
-    p.k_scales = k_scales; p.v_scales = v_scales; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr;
+    p.k_scales = k_scales; p.v_scales = v_scales; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
     p.mask = mask; p.valid_lens = valid_lens; p.out = out; p.ws = (float*)workspace;
     p.b = (int)b; p.len_q = (int)len_q; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
     p.rows = p.len_q * p.n_rep;

@@ -9,6 +9,8 @@
 //   zl_scatter_logits     beam_utility::scatter_update (:224-241, 285-315): logits[batch_ids[i], token_ids[i]] = / += T(values[i])
 //   zl_repetition_penalty beam_utility::beam_repetition_penalty (:199-222, 243-283): l = presence != 0 ? l - T(presence) :
 //                         (l < 0 ? l * T(factor) : l / T(factor)), arithmetic in T as written there
+//   zl_spec_accept        the greedy acceptance of a speculative step over (b, len_q) logit rows and the roll-back of the batch state
+//                         (SessionGenerator.rollback_speculative -> sess_drop_speculative, src/generator/batch_generator.cpp:843-852)
 // One workgroup of 256 threads per row (the reference: up to 1024); every row is read a handful of times: a few hundred KB per
 // decode step next to the 4.8 GB of weights -- nothing to tune, everything to get right.  T = fp16 / bf16 / fp32 (enum zl_elem_t).
 #include <hip/hip_runtime.h>
@@ -212,6 +214,27 @@ __global__ void k_repetition_penalty(const float* __restrict__ factor, const flo
     }
     logits[at] = ET<TY>::cvt(r);
 }
+
+// zl_spec_accept's second launch: out_tokens holds the picks of the (b, len_q) rows (zl_argmax_advance left them); one thread per
+// task finds the longest prefix of its drafts that the picks confirm, pads the row behind the bonus token with -1 and advances the
+// task's state by accepted + 1
+__global__ void k_spec_accept(const int32_t* __restrict__ drafts, int32_t* __restrict__ out_tokens, int32_t* __restrict__ accepted,
+                              int32_t* __restrict__ tokens, int32_t* __restrict__ positions, int32_t* __restrict__ placement,
+                              int32_t* __restrict__ valid_lens, int b, int len_q) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= b) return;
+    int32_t* pk = out_tokens + (int64_t)t * len_q;
+    const int32_t* dr = drafts + (int64_t)t * (len_q - 1);
+    int n = 0;
+    while (n < len_q - 1 && dr[n] == pk[n]) ++n;
+    const int32_t last = pk[n];
+    for (int j = n + 1; j < len_q; ++j) pk[j] = -1;
+    accepted[t] = n;
+    if (tokens) tokens[t] = last;
+    if (positions) positions[t] += n + 1;
+    if (placement) placement[t] += n + 1;
+    if (valid_lens) valid_lens[t] += n + 1;
+}
 }  // namespace
 
 #define ZL_TYPE_SWITCH(type, CALL)                      \
@@ -275,6 +298,18 @@ int zl_repetition_penalty(const float* factor, const float* presence, const int3
 #define CALL(TY) hipLaunchKernelGGL(k_repetition_penalty<TY>, grid, dim3(256), 0, (hipStream_t)s, factor, presence, tokens, batch_ids, (ET<TY>::type*)logits, n, vocab);
     ZL_TYPE_SWITCH(type, CALL)
 #undef CALL
+    return zl_launch_status();
+}
+
+int zl_spec_accept(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts, int32_t* tokens,
+                   int32_t* positions, int32_t* placement, int32_t* valid_lens, int32_t* accepted, int32_t* out_tokens, zl_stream_t s) {
+    ZL_CHECK_ARG(logits && drafts && accepted && out_tokens && b > 0 && len_q > 1 && n > 0 && ld >= n, ZL_EINVAL);
+    ZL_CHECK_ARG(n < ((int64_t)1 << 31) && b * len_q < ((int64_t)1 << 31), ZL_ESHAPE);
+    // the picks: one 1024-thread workgroup per logit row, zl_argmax_advance's kernel and tie rule, into out_tokens
+    const int e = zl_argmax_advance(logits, type, b * len_q, n, ld, out_tokens, nullptr, nullptr, nullptr, nullptr, s);
+    if (e) return e;
+    hipLaunchKernelGGL(k_spec_accept, dim3((unsigned)((b + 63) / 64)), dim3(64), 0, (hipStream_t)s, drafts, out_tokens, accepted, tokens, positions,
+                       placement, valid_lens, (int)b, (int)len_q);
     return zl_launch_status();
 }
 

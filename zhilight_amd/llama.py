@@ -935,6 +935,18 @@ class DynBatchContext:
     # step bounds its replays itself (the scatter kernels drop a row whose slot lies outside its buffer -- never a stray write)
     steps_left: int = 1 << 60
     unquant_kv: Dict[int, torch.Tensor] = field(default_factory=dict)   # INT8 cache: a chunked prompt's temporary fp16 K/V
+    # LLaMA.verify: per len_q the row-expanded view of this context and the call's result buffers (built on first use, the view's
+    # tables refilled from this context by every call)
+    spec: Dict[int, tuple] = field(default_factory=dict)
+    # a row-expanded view (LLaMA.verify): several "tasks" are rows of ONE task and share its buffers, so a row's attention reads K/V
+    # that other rows of the same call write -- encode() must scatter every row before any row attends (never the launch that
+    # scatters and attends at once)
+    row_expanded: bool = False
+
+
+# LLaMA.verify's result: the (B * len_q, vocab) logits of the step's rows, accepted (B) int32 drafts per task, tokens (B, len_q) int32 =
+# the accepted drafts and the model's own next token, -1 behind them (fed back as drafts, a -1 is simply a draft that is never accepted)
+SpecResult = collections.namedtuple("SpecResult", "logits accepted tokens")
 
 
 class _PromptRows:
@@ -1285,15 +1297,20 @@ class LLaMA:
         return self._bufs[b]
 
     # ---- one decode step -----------------------------------------------------------------------
-    def encode(self, ctx: DynBatchContext, workspace=None, argmax_ws=None, gemv_only=False, skip_gemv=False):
+    def encode(self, ctx: DynBatchContext, workspace=None, argmax_ws=None, gemv_only=False, skip_gemv=False, attend_rows=None):
         """LLaMA::encode for a pure decode ("search") batch: returns logits (B, vocab) fp16.
         gemv_only (bench.py's roofline leg): issue ONLY the four quantised projections of every layer, exactly as the step
         launches them (fused norm / rotary + scatter / split merge / gated activation / residual), on whatever the buffers
         hold -- no embedding, attention or lm_head; returns None.
         skip_gemv (bench.py again): the complement -- everything BUT those projections (embedding, rope table, attention, lm_head,
-        greedy bookkeeping), so that step time - this = the projections' time inside the step."""
+        greedy bookkeeping), so that step time - this = the projections' time inside the step.
+        attend_rows (LLaMA.verify): ctx is a row-expanded view -- several rows of one task posed as tasks of the scatter -- and
+        attend_rows(li, q, out, workspace) is layer li's attention over them, q / out (rows, H * D).  The routes that hard-wire one row
+        per task into the attention (the merging attn_out prologue, the in-launch merge) and the two bench legs are off with it."""
         c = self.cfg
         b = ctx.tokens.numel()
+        if attend_rows is not None and (gemv_only or skip_gemv):
+            raise ops.ZLError("gemv_only / skip_gemv: not with an attention hook")
         if self.moe and (gemv_only or skip_gemv):
             # the two legs split a step into "the four W4 projections" and the rest; an MoE layer's feed-forward is a router, a sort
             # and two grouped launches, which belong to neither side
@@ -1332,7 +1349,7 @@ class LLaMA:
                             and all(isinstance(l, Int8EncoderLayer) and l._stream(b) for l in self.layers))
         # a few rows: the split merge of the decode attention rides in the attn_out projection's prologue (one launch less)
         merge_plan = None
-        if (fuse_qkv_rope and not self.tp and os.environ.get("ZL_ATTN_MERGE", "1") != "0"
+        if (fuse_qkv_rope and not self.tp and attend_rows is None and os.environ.get("ZL_ATTN_MERGE", "1") != "0"
                 and all(l.attn_out.perm is None for l in self.layers)):
             merge_plan = ops.attn_merge_plan(b, c.num_heads, c.num_kv_heads, c.dim_head, ctx.max_len_buf,
                                              self.layers[0].attn_out.weight, c.torch_dtype)
@@ -1344,7 +1361,8 @@ class LLaMA:
         # path's), ZL_ATTN_LA_HALF = 1 half-precision split records
         la = None
         la_mode = os.environ.get("ZL_ATTN_LA", _ATTN_LA_DEFAULT)
-        if (mfma_attn and not ctx.kv_quant and c.dim_head == 128 and (la_mode == "1" or (la_mode == "auto" and merge_plan is None))):
+        if (mfma_attn and not ctx.kv_quant and c.dim_head == 128 and attend_rows is None
+                and (la_mode == "1" or (la_mode == "auto" and merge_plan is None))):
             la_split = int(os.environ.get("ZL_ATTN_LA_SPLIT", "0") or 0)
             la_half = os.environ.get("ZL_ATTN_LA_HALF", "0") == "1" and c.torch_dtype == torch.float16
             eff = la_split or ops.decode_attn_la_split_len(b, c.num_kv_heads, ctx.max_len_buf)
@@ -1365,7 +1383,8 @@ class LLaMA:
         # 9 rows on, no register-resident norm prologue below.  ZL_ROW_SS=0 off; ZL_ROW_SS_MIN_M: rows it starts at
         # (not with MoE layers: their feed-forward has no w_out to produce the statistics nor a gate|up projection to consume them)
         stats = None
-        if (fuse_qkv_rope and la is not None and not self.tp and not self.moe and os.environ.get("ZL_ROW_SS", "1") != "0"
+        if (fuse_qkv_rope and (la is not None or attend_rows is not None) and not self.tp and not self.moe
+                and os.environ.get("ZL_ROW_SS", "1") != "0"
                 and int(os.environ.get("ZL_ROW_SS_MIN_M", "8")) <= b <= 32 and c.dim_model % 1024 == 0
                 and all(l.attn_out.perm is None and l.w_out.perm is None and l.w_in_gated.perm is None for l in self.layers)
                 and ops.w4_row_ss_routes(b, [self.layers[0].attn_out.weight, self.layers[0].w_out.weight],
@@ -1377,6 +1396,8 @@ class LLaMA:
 
         def attend(li, out):
             """decode attention of layer li over the tasks' buffers: bufs["q"] -> out (B, H * D)"""
+            if attend_rows is not None:
+                return attend_rows(li, bufs["q"], out, workspace)
             q4 = bufs["q"].view(b, 1, c.num_heads, c.dim_head)
             if la is not None:
                 return ops.decode_attention_la(q4, ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li], ctx.valid_lens, scale, ctx.max_len_buf,
@@ -1463,7 +1484,8 @@ class LLaMA:
                     bufs["q"].view(b, 1, c.num_heads, c.dim_head), ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li], ctx.ks_addrs[li],
                     ctx.vs_addrs[li], None, scale, ctx.max_len_buf, c.num_kv_heads, valid_lens=ctx.valid_lens,
                     out=bufs["attn"].view(b, 1, c.num_heads, c.dim_head), workspace=workspace)
-            elif mfma_attn:
+            elif mfma_attn or attend_rows is not None or ctx.row_expanded:
+                # (a row-expanded view always comes here: the fused launch below orders a row's own K/V only)
                 # rope + KV scatter in one small launch, then the matrix-core decode attention (attention.hip:
                 # k_decode_attn_mfma; 11.0 / 18.7 / 39.8 us vs 11.9 / 24.0 / 49.7 us for the fused VALU kernel at batch 1 / 8 / 32)
                 ops.rope_scatter_decode(cos, sin, bufs["qkv"], ctx.placement, ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li],
@@ -1890,6 +1912,95 @@ class LLaMA:
         ops.greedy_advance(ws, b, self.cfg.vocab_size, ctx.tokens, ctx.positions, ctx.placement, ctx.valid_lens, nxt)
         ctx.steps_left -= 1
         return logits, nxt
+
+    @staticmethod
+    def verify_route(b, len_q):
+        """the attention route verify(attn="auto") takes for b tasks of len_q rows, from the measured table ("Speculative
+        verify step"; profiles/spec_verify.txt).  The rule: causal stays where the p10 .. p90 intervals of the two routes' step
+        times overlap.  They do at every measured shape of up to 4 rows (ratios 0.987 - 1.010); from 8 rows on they are disjoint
+        everywhere: the rows route is ahead by 0.7 - 1.2 % of the step at B <= 2 and by 4 - 9 % at B >= 4"""
+        return "causal" if b * len_q <= 4 else "rows"
+
+    def verify(self, ctx: DynBatchContext, drafts: torch.Tensor, attn="auto"):
+        """One speculative step on the device (graph-capturable, no host round trip): check the K = drafts.shape[1] draft tokens of
+        every task in ONE pass of the decode layer loop over len_q = K + 1 rows per task, keep the longest prefix the model's own
+        greedy picks confirm plus one token of its own, and roll the batch state back to there -- SessionGenerator.feed +
+        rollback_speculative (zhilight/session_generator.py:25-66), which the reference runs through its prompt path.
+        State as step_greedy leaves it (ctx.tokens not yet in the cache).  Row (b, i) carries ctx.tokens[b] (i = 0) or
+        drafts[b, i - 1] at position positions[b] + i, writes its K / V to slot placement[b] + i and sees the keys
+        j < min(buf_lens[b], valid_lens[b] + i).  Afterwards tokens[b] = the pick behind the accepted drafts, positions / placement /
+        valid_lens += accepted + 1; the K / V rows of rejected drafts stay beyond valid_lens until later steps overwrite them (the
+        reference's drop_token).  ctx.steps_left -= len_q: the host-side bound counts the worst case.
+        attn: "causal" = zl_decode_attn_causal, a task's K / V read once for all of its rows; "rows" = every row a task of its own
+        for the len_q = 1 kernels of step_greedy (valid = valid_lens[b] + i), the A/B baseline; "auto" (default) = whichever of
+        the two measured faster for this many rows (verify_route).
+        drafts: (B, K) int32 on the device.  A draft id outside [0, vocab) -- the -1 padding of a previous call's tokens, say -- is
+        never accepted: its row runs on the id clamped into the vocabulary (no out-of-range embedding read) and the comparison
+        with the pick uses the id as given.  The row-expanded view and the result buffers are allocated on the first eager call
+        per K (run one before capturing); its pointer tables and buffer lengths are re-read from ctx by every call, replays
+        included, so a caller may swap a task's buffers in place between calls.
+        Returns SpecResult(logits (B * len_q, vocab), accepted (B) int32, tokens (B, len_q) int32); the three are reused by the next
+        call with the same K."""
+        c, dev = self.cfg, self.device
+        if ctx.kv_quant:
+            raise ops.ZLError("verify: not on the INT8 KV cache")
+        if self.tp:
+            raise ops.ZLError("verify: not under tensor parallelism")
+        if c.dim_head != 128:
+            raise ops.ZLError("verify: head size 128 only (the matrix-core decode attention)")
+        if attn not in ("auto", "causal", "rows"):
+            raise ops.ZLError("verify: attn is 'auto', 'causal' or 'rows'")
+        b = ctx.tokens.numel()
+        if not (torch.is_tensor(drafts) and drafts.dim() == 2 and drafts.shape[0] == b and drafts.shape[1] >= 1
+                and drafts.dtype == torch.int32 and drafts.device == ctx.tokens.device and drafts.is_contiguous()):
+            raise ops.ZLError("verify: drafts are (B, K) contiguous int32 on the context's device, K >= 1")
+        len_q = drafts.shape[1] + 1
+        m = b * len_q
+        if attn == "auto":
+            attn = self.verify_route(b, len_q)
+        if len_q > 32 or m > 32:
+            raise ops.ZLError("verify: at most 32 rows per step (B * (K + 1) <= 32)")
+        capturing = torch.cuda.is_current_stream_capturing()
+        if ctx.steps_left < len_q and not capturing:
+            raise ops.ZLError("verify: the draft rows do not fit the KV buffers (steps_left < K + 1)")
+        if len_q not in ctx.spec:
+            if capturing:
+                raise ops.ZLError("verify: run one eager call before capturing (it allocates the row-expanded view)")
+            i32 = dict(dtype=torch.int32, device=dev)
+            rows = DynBatchContext(
+                tokens=torch.empty(m, **i32), positions=torch.empty(m, **i32), placement=torch.empty(m, **i32),
+                valid_lens=torch.empty(m, **i32), buf_lens=torch.empty(m, **i32),
+                k_addrs=torch.empty((c.num_layers, m), dtype=torch.int64, device=dev),
+                v_addrs=torch.empty((c.num_layers, m), dtype=torch.int64, device=dev),
+                max_len_buf=ctx.max_len_buf, kv=ctx.kv, row_expanded=True)
+            ctx.spec[len_q] = (rows, torch.arange(len_q, **i32).view(1, len_q), torch.empty(b, **i32), torch.empty((b, len_q), **i32),
+                               torch.arange(b, device=dev).view(b, 1).expand(b, len_q).reshape(m))
+        rows, ar, accepted, out_tokens, task_of_row = ctx.spec[len_q]
+        # the view's tables from the context as it is NOW (a swapped buffer, a regrown table), then the rows of this call: tokens
+        # (draft ids clamped into the vocabulary), and the three counters of task b + 0 .. K
+        torch.index_select(ctx.buf_lens, 0, task_of_row, out=rows.buf_lens)
+        torch.index_select(ctx.k_addrs, 1, task_of_row, out=rows.k_addrs)
+        torch.index_select(ctx.v_addrs, 1, task_of_row, out=rows.v_addrs)
+        rows.max_len_buf, rows.kv = ctx.max_len_buf, ctx.kv
+        tok = rows.tokens.view(b, len_q)
+        tok[:, 0].copy_(ctx.tokens)
+        tok[:, 1:].copy_(drafts.clamp(0, c.vocab_size - 1))
+        torch.add(ctx.positions.view(b, 1), ar, out=rows.positions.view(b, len_q))
+        torch.add(ctx.placement.view(b, 1), ar, out=rows.placement.view(b, len_q))
+        torch.add(ctx.valid_lens.view(b, 1), ar, out=rows.valid_lens.view(b, len_q))
+        rows.steps_left = ctx.steps_left
+        hook = None
+        if attn == "causal":
+            scale = 1.0 / math.sqrt(c.dim_head)
+
+            def hook(li, q, out, workspace):
+                shape = (b, len_q, c.num_heads, c.dim_head)
+                return ops.decode_attention_causal(q.view(shape), ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li], ctx.valid_lens, scale,
+                                                   ctx.max_len_buf, c.num_kv_heads, out=out.view(shape), workspace=workspace)
+        logits = self.encode(rows, attend_rows=hook)
+        ops.spec_accept(logits, drafts, ctx.tokens, ctx.positions, ctx.placement, ctx.valid_lens, accepted=accepted, out_tokens=out_tokens)
+        ctx.steps_left -= len_q
+        return SpecResult(logits, accepted, out_tokens)
 
     def advance(self, ctx: DynBatchContext, next_tokens: torch.Tensor):
         """Device-side bookkeeping between steps (what fill_search_tokens does on the host in the

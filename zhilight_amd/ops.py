@@ -823,6 +823,40 @@ def argmax_advance(logits, tokens=None, positions=None, placement=None, valid_le
     return next_tokens if next_tokens is not None else tokens
 
 
+def spec_accept(logits, drafts, tokens=None, positions=None, placement=None, valid_lens=None, accepted=None, out_tokens=None):
+    """Greedy acceptance of a speculative step (zl_spec_accept): logits (B * len_q, n) rows, task-major, unit column stride; drafts
+    (B, K) int32, len_q = K + 1.  picks = per-row arg-max (argmax_advance's rule); accepted[b] = length of the longest prefix of
+    drafts[b] that the picks confirm; out_tokens[b] = picks[b, :accepted + 1], -1 behind them; tokens <- picks[b, accepted],
+    positions / placement / valid_lens += accepted + 1 (each optional).  Returns (accepted (B) int32, out_tokens (B, len_q) int32);
+    accepted / out_tokens: buffers to write into (a captured call)."""
+    if not (torch.is_tensor(logits) and torch.is_tensor(drafts)):
+        raise ZLError("spec_accept: logits and drafts are tensors")
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1] or logits.shape[1] < 1:
+        raise ZLError("spec_accept: (B * len_q, n) logits with unit column stride")
+    if logits.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ZLError(f"spec_accept: unsupported logits dtype {logits.dtype}")
+    if drafts.dim() != 2 or drafts.shape[1] < 1 or drafts.dtype != torch.int32 or not drafts.is_contiguous():
+        raise ZLError("spec_accept: drafts are (B, K) contiguous int32, K >= 1")
+    b, len_q = drafts.shape[0], drafts.shape[1] + 1
+    if b < 1 or logits.shape[0] != b * len_q:
+        raise ZLError("spec_accept: one logit row per task and draft position: B * (K + 1) rows")
+    if not logits.is_cuda or drafts.device != logits.device:
+        raise ZLError("spec_accept: CUDA logits, drafts on the logits' device")
+    for t, what in ((tokens, "tokens"), (positions, "positions"), (placement, "placement"), (valid_lens, "valid_lens"), (accepted, "accepted")):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != b or not t.is_contiguous() or t.device != logits.device):
+            raise ZLError(f"spec_accept: {what}: contiguous int32 of length B on the logits' device")
+    if accepted is None:
+        accepted = torch.empty(b, dtype=torch.int32, device=logits.device)
+    if out_tokens is None:
+        out_tokens = torch.empty((b, len_q), dtype=torch.int32, device=logits.device)
+    elif out_tokens.dtype != torch.int32 or out_tokens.numel() != b * len_q or not out_tokens.is_contiguous() or out_tokens.device != logits.device:
+        raise ZLError("spec_accept: out_tokens: contiguous int32 (B, K + 1) on the logits' device")
+    code = {torch.float16: 2, torch.bfloat16: 6, torch.float32: 1}[logits.dtype]
+    check(lib().zl_spec_accept(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(logits.shape[1]), _i(logits.stride(0)), _p(drafts), _p(tokens),
+                               _p(positions), _p(placement), _p(valid_lens), _p(accepted), _p(out_tokens), _stream()), "spec_accept")
+    return accepted, out_tokens.view(b, len_q)
+
+
 # --------------------------------------------------------------------------------------------------
 # scoring: functions::Gemm + nn::log_prob_raw / greedy_match_raw (src/nn/functions/cross_entropy.cu:7-69, 358-403) without the
 # (M, N) logits: csrc/lm_head_score.hip
@@ -1203,6 +1237,54 @@ def multi_query_attention_rag_buffer(batch_q, buf_lens, key_buf_addrs, val_buf_a
                                _p(valid_lens), _p(out), _p(workspace), _i(b), _i(len_q), _i(h), _i(num_kv_heads),
                                _i(d), _f(scale), _i(max_len_buf), C.c_int(int(bshd)), C.c_int(_dt(batch_q)),
                                C.c_int(_attn_algo()), _stream()), "decode_attn")
+    return out
+
+
+def causal_step_mask(buf_lens, valid_lens, len_q):
+    """The int8 mask of a speculative step in multi_query_attention_rag_buffer's layout, built on the host: task b contributes a
+    (len_q, buf_lens[b]) block with mask[qi, j] = j < min(buf_lens[b], valid_lens[b] + qi), the blocks concatenated.  What
+    decode_attention_causal computes without a mask; returns a 1-D int8 host tensor."""
+    lens = [int(v) for v in (buf_lens.tolist() if hasattr(buf_lens, "tolist") else buf_lens)]
+    valid = [int(v) for v in (valid_lens.tolist() if hasattr(valid_lens, "tolist") else valid_lens)]
+    if len(lens) != len(valid) or int(len_q) < 1 or any(n < 0 for n in lens):
+        raise ZLError("causal_step_mask: one buffer length and one valid length per task, len_q >= 1")
+    parts = [(torch.arange(n)[None, :] < (torch.arange(int(len_q)) + v)[:, None]).to(torch.int8).reshape(-1) for n, v in zip(lens, valid)]
+    return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int8)
+
+
+def decode_attention_causal(batch_q, buf_lens, k_addrs, v_addrs, valid_lens, scale, max_len_buf, num_kv_heads, bshd=True, out=None,
+                            workspace=None):
+    """Decode attention of a speculative step (zl_decode_attn_causal): batch_q (B, len_q, H, 128), row qi of task b sees the keys
+    j < min(buf_lens[b], valid_lens[b] + qi) -- multi_query_attention_rag_buffer with causal_step_mask(...), on the matrix cores and
+    with one pass over a task's K / V for all of its rows.  workspace: decode_attn_workspace(B, len_q, H, 128, max_len_buf, device).
+    Returns out, shaped like batch_q."""
+    _chk_cuda(batch_q, buf_lens, k_addrs, v_addrs, valid_lens, out, workspace)
+    if batch_q.dim() != 4:
+        raise ZLError("decode_attention_causal: batch_q is (B, len_q, H, D)")
+    b, len_q, h, d = batch_q.shape
+    dt = _dt(batch_q)
+    if d != 128 or num_kv_heads < 1 or h % num_kv_heads:
+        raise ZLError("decode_attention_causal: head size 128, H a multiple of the kv heads")
+    if not 1 <= len_q <= 32:
+        raise ZLError("decode_attention_causal: 1 <= len_q <= 32")
+    for t, dty, what in ((buf_lens, torch.int32, "buf_lens"), (valid_lens, torch.int32, "valid_lens"), (k_addrs, torch.int64, "k_addrs"),
+                         (v_addrs, torch.int64, "v_addrs")):
+        if t.dtype != dty or t.numel() != b or t.device != batch_q.device:
+            raise ZLError(f"decode_attention_causal: {what}: {b} entries of {dty} on the queries' device")
+    if out is None:
+        out = torch.empty_like(batch_q)
+    else:
+        _chk_out(out, b * len_q, h * d, batch_q.dtype, batch_q.device, "decode_attention_causal")
+    need = int(lib().zl_decode_attn_workspace_bytes(_i(b), _i(len_q), _i(h), _i(d), _i(max_len_buf)))
+    if need < 0:
+        check(need, "decode_attn_workspace_bytes")
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=batch_q.device)
+    elif workspace.device != batch_q.device or workspace.numel() * workspace.element_size() < need:
+        raise ZLError("decode_attention_causal: workspace too small / wrong device")
+    check(lib().zl_decode_attn_causal(_p(batch_q), _p(buf_lens), _p(k_addrs), _p(v_addrs), _p(valid_lens), _p(out), _p(workspace),
+                                      _i(b), _i(len_q), _i(h), _i(num_kv_heads), _i(d), _f(scale), _i(max_len_buf), C.c_int(int(bshd)),
+                                      C.c_int(dt), _stream()), "decode_attn_causal")
     return out
 
 
