@@ -108,9 +108,10 @@ __global__ __launch_bounds__(256) void k_dense_gemv(const DenseParams p) {
                     float b = p.bias ? ZT<DT>::to_f32(p.bias[crow]) : 0.f;
                     const uint16_t y16 = ZT<DT>::from_f32(p.alpha * v + b);
                     p.y[(size_t)(m0 + m) * p.n + crow] = y16;
-                    // greedy pick on the ROUNDED logit, first index on ties (rows ascend inside a wave)
+                    // greedy pick on the ROUNDED logit, first index on ties (rows ascend inside a wave); a NaN is the largest
+                    // value and the first NaN stays (zl_argmax_advance's rule: nothing compares greater than a NaN best_v)
                     const float yv = ZT<DT>::to_f32(y16);
-                    if (yv > best_v[m] || best_i[m] == 0x7fffffff) {
+                    if (yv > best_v[m] || best_i[m] == 0x7fffffff || (yv != yv && best_v[m] == best_v[m])) {
                         best_v[m] = yv;
                         best_i[m] = crow;
                     }
@@ -141,7 +142,15 @@ __global__ __launch_bounds__(256) void k_dense_gemv(const DenseParams p) {
 // launch (what fill_search_tokens does on the host in the reference between steps,
 // src/generator/batch_generator.cpp:1226-1335): tokens <- argmax, positions / placement / valid_lens += 1.
 // One workgroup per task; candidates are scanned in wave order (= ascending row index), ties keep the
-// lowest index like torch.argmax / the reference's top-1.
+// lowest index like torch.argmax / the reference's top-1; a NaN is the largest value and the first NaN wins (zl_argmax_advance's rule).
+// candidate (v, i) beats the best so far (bv, bi); index 0x7fffffff = no candidate (an empty wave)
+__device__ __forceinline__ bool greedy_beats(float v, int i, float bv, int bi) {
+    if (i == 0x7fffffff) return false;
+    if (bi == 0x7fffffff) return true;
+    if (v != v) return bv == bv || i < bi;
+    return v > bv || (v == bv && i < bi);        // both false against a NaN bv
+}
+
 __global__ __launch_bounds__(256) void k_greedy_advance(const float2* ws, int total_waves, int32_t* tokens,
                                                         int32_t* positions, int32_t* placement, int32_t* valid_lens,
                                                         int64_t* next_out) {
@@ -162,7 +171,7 @@ __global__ __launch_bounds__(256) void k_greedy_advance(const float2* ws, int to
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int ci = __float_as_int(c[u].y);
-            if (ci != 0x7fffffff && (c[u].x > bv || (c[u].x == bv && ci < bi) || bi == 0x7fffffff)) {
+            if (greedy_beats(c[u].x, ci, bv, bi)) {
                 bv = c[u].x;
                 bi = ci;
             }
@@ -175,8 +184,7 @@ __global__ __launch_bounds__(256) void k_greedy_advance(const float2* ws, int to
         if ((int)threadIdx.x < off) {
             const float ov = sv[threadIdx.x + off];
             const int oi = si[threadIdx.x + off];
-            if (oi != 0x7fffffff && (ov > sv[threadIdx.x] || (ov == sv[threadIdx.x] && oi < si[threadIdx.x]) ||
-                                     si[threadIdx.x] == 0x7fffffff)) {
+            if (greedy_beats(ov, oi, sv[threadIdx.x], si[threadIdx.x])) {
                 sv[threadIdx.x] = ov;
                 si[threadIdx.x] = oi;
             }
