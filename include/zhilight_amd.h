@@ -952,6 +952,22 @@ int zl_argmax_advance(const void* logits, int type, int64_t rows, int64_t n, int
  * the prefix match over its len_q int32 picks.  Ordinary vector stores only; no allocation, no sync. */
 int zl_spec_accept(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts, int32_t* tokens,
                    int32_t* positions, int32_t* placement, int32_t* valid_lens, int32_t* accepted, int32_t* out_tokens, zl_stream_t s);
+/* The drafter of a speculative step: prompt lookup over device-resident token histories (csrc/spec_draft.hip).  The reference has no
+ * counterpart: it leaves drafting to the caller of SessionGenerator.feed / rollback_speculative (zhilight/session_generator.py:25-66).
+ * history (b, cap) int32 rows, hist_lens (b) int32; both are this call's only state and are updated in place.  Per task, in order:
+ * APPEND  a = the number of ids of new_tokens[t, :n_new] before the first negative one (a row of zl_spec_accept's out_tokens is such a
+ *         row; new_tokens == NULL: a = 0).  Token j < a goes to history[t, hist_lens[t] + j] if that index is < cap and is dropped
+ *         otherwise -- nothing is written outside the row -- and hist_lens[t] += a: the length counts every token fed and may exceed cap.
+ * DRAFT   L = hist_lens[t], h = history[t, :L].  L > cap (the task has overflowed) or L < 2: drafts[t, :] = -1, match[t] = (0, -1).
+ *         Otherwise for n from min(max_ngram, L - 1) down to min_ngram a match is a start s >= 0 with s + n <= L - 1 and
+ *         h[s : s + n] == h[L - n : L] (never the suffix itself; at least one token follows).  The first n with a match decides; among
+ *         its matches the LARGEST s with a full continuation (s + n + k <= L), else the SMALLEST s (the longest continuation).
+ *         drafts[t] = h[s + n : s + n + k], -1 behind the history's end; match[t] = (n, s) (match may be NULL).  No match: as above.
+ * ZL_EINVAL: a null history / hist_lens / drafts, b < 1, k < 1, cap < 2, n_new < 0, new_tokens given with n_new == 0, or not
+ * 1 <= min_ngram <= max_ngram <= 16; ZL_ESHAPE: k > 31 (zl_spec_accept's row limit), n_new > 32, cap or b >= 2^31.
+ * ONE launch, one 1024-thread workgroup per task; ordinary vector stores only; no allocation, no sync, no workspace. */
+int zl_lookup_draft(int32_t* history, int64_t cap, int32_t* hist_lens, const int32_t* new_tokens, int64_t n_new, int64_t b, int64_t k,
+                    int max_ngram, int min_ngram, int32_t* drafts, int32_t* match, zl_stream_t s);
 /* The logit post-processing of the reference's batch generator (src/generator/beam_util.cu, 3rd/bmengine/bmengine/functions/{softmax,topk}.cu):
  * what src/generator/batch_generator.cpp calls between a decode step and its host-side search, so that the py_export surface (zhilight.C)
  * links against this boundary.  Rows of n logits of type ZL_T_F16 / ZL_T_BF16 / ZL_T_F32; fp32 arithmetic, one rounding to T.

@@ -949,6 +949,19 @@ class DynBatchContext:
 SpecResult = collections.namedtuple("SpecResult", "logits accepted tokens")
 
 
+@dataclass
+class LookupState:
+    """The device-resident state of the prompt-lookup drafter (LLaMA.new_lookup / step_lookup; ops.lookup_draft states the rule):
+    every task's token history -- what it has consumed plus its pending ctx.tokens entry -- and the drafts of the next step."""
+    history: torch.Tensor       # (B, cap) int32; row b holds its first min(hist_lens[b], cap) ids
+    hist_lens: torch.Tensor     # (B) int32   tokens fed so far; beyond cap the task has overflowed and drafts nothing (-1) from then on
+    drafts: torch.Tensor        # (B, K) int32   the next verify step's drafts, -1 = none
+    match: torch.Tensor         # (B, 2) int32   (n, start) of the n-gram the drafts follow, (0, -1) = no match
+    k: int
+    max_ngram: int
+    min_ngram: int
+
+
 class _PromptRows:
     """The rows of one prompt-encode call -- one task's piece, or the pieces of several tasks back to back -- as the layer loop, the
     K/V scatter, the attention and the tail see them.  Built once per call, and the only place that knows whether the call has one
@@ -2001,6 +2014,85 @@ class LLaMA:
         ops.spec_accept(logits, drafts, ctx.tokens, ctx.positions, ctx.placement, ctx.valid_lens, accepted=accepted, out_tokens=out_tokens)
         ctx.steps_left -= len_q
         return SpecResult(logits, accepted, out_tokens)
+
+    # ---- speculative steps with the prompt-lookup drafter ----------------------------------------
+    def new_lookup(self, ctx: DynBatchContext, histories, k, max_ngram=3, min_ngram=1, cap=None) -> LookupState:
+        """The drafter state for step_lookup: histories[j] = the ids task j has consumed so far (normally its prompt), WITHOUT the
+        pending ctx.tokens[j]; that one enters through the kernel's append path right here, so state.drafts is ready on return.
+        Drafts are found by prompt lookup (ops.lookup_draft): the longest n-gram, max_ngram down to min_ngram ids, at the history's
+        end that occurs earlier in it, and the k ids that followed it.  cap: ids a history row holds, default ctx.max_len_buf + 1 -- a
+        task never holds more tokens than that, so the default never overflows; a task fed past a smaller cap drafts nothing
+        (-1) from then on and runs as plain greedy steps."""
+        k, b = int(k), ctx.tokens.numel()
+        if ctx.kv_quant:                                  # what verify refuses at call time, before any drafter state exists
+            raise ops.ZLError("new_lookup: not on the INT8 KV cache")
+        if self.tp:
+            raise ops.ZLError("new_lookup: not under tensor parallelism")
+        if self.cfg.dim_head != 128:
+            raise ops.ZLError("new_lookup: head size 128 only (the matrix-core decode attention)")
+        if k < 1 or b * (k + 1) > 32:
+            raise ops.ZLError("new_lookup: k >= 1 and at most 32 rows per step (B * (k + 1) <= 32)")
+        if not 1 <= int(min_ngram) <= int(max_ngram) <= 16:
+            raise ops.ZLError("new_lookup: 1 <= min_ngram <= max_ngram <= 16")
+        cap = ctx.max_len_buf + 1 if cap is None else int(cap)
+        if cap < 2:
+            raise ops.ZLError("new_lookup: cap >= 2")
+        if len(histories) != b:
+            raise ops.ZLError(f"new_lookup: {b} tasks, {len(histories)} histories")
+        rows = np.zeros((b, cap), np.int32)
+        lens = np.zeros(b, np.int32)
+        for j, h in enumerate(histories):
+            h = np.asarray(h.cpu() if torch.is_tensor(h) else h, dtype=np.int64).reshape(-1)
+            if h.size > cap - 1:
+                raise ops.ZLError(f"new_lookup: task {j}: {h.size} ids and the pending token do not fit cap = {cap}")
+            if h.size and (h.min() < 0 or h.max() >= self.cfg.vocab_size):
+                raise ops.ZLError(f"new_lookup: task {j}: ids outside [0, {self.cfg.vocab_size})")
+            rows[j, :h.size], lens[j] = h, h.size
+        dev = ctx.tokens.device
+        state = LookupState(history=torch.from_numpy(rows).to(dev), hist_lens=torch.from_numpy(lens).to(dev),
+                            drafts=torch.empty((b, k), dtype=torch.int32, device=dev), match=torch.empty((b, 2), dtype=torch.int32, device=dev),
+                            k=k, max_ngram=int(max_ngram), min_ngram=int(min_ngram))
+        ops.lookup_draft(state.history, state.hist_lens, k, state.max_ngram, state.min_ngram, new_tokens=ctx.tokens.view(b, 1),
+                         drafts=state.drafts, match=state.match)
+        return state
+
+    def step_lookup(self, ctx: DynBatchContext, state: LookupState, attn="auto"):
+        """One speculative step with the drafter inside, all on the device: verify(ctx, state.drafts, attn), then ONE launch
+        (ops.lookup_draft) appends the tokens the step emitted to the tasks' histories and drafts the next step's tokens into
+        state.drafts.  No host round trip; capturable after one eager call (verify's rule), and a replay carries ctx and state
+        forward together.  Returns verify's SpecResult.
+        A caller that interleaves step_greedy keeps the state in step by feeding the token that step left pending:
+        ops.lookup_draft(state.history, state.hist_lens, state.k, state.max_ngram, state.min_ngram,
+        new_tokens=ctx.tokens.view(B, 1), drafts=state.drafts, match=state.match)."""
+        b = ctx.tokens.numel()
+        if state.drafts.shape != (b, state.k) or state.history.shape[0] != b:
+            raise ops.ZLError("step_lookup: the state belongs to another batch size")
+        res = self.verify(ctx, state.drafts, attn)
+        ops.lookup_draft(state.history, state.hist_lens, state.k, state.max_ngram, state.min_ngram, new_tokens=res.tokens,
+                         drafts=state.drafts, match=state.match)
+        return res
+
+    def generate_lookup(self, ctx: DynBatchContext, state: LookupState, max_new_tokens):
+        """The eager convenience loop around step_lookup -- the NON-captured path: it reads accepted / tokens back to the host once per
+        round.  Runs rounds until every task has emitted max_new_tokens tokens or the KV buffers have no room for another step
+        (ctx.steps_left < k + 1); the batch moves in lock step, so tasks that are done keep running until the last one is.
+        Returns (tokens, stats): tokens[j] = the ids task j emitted behind its pending ctx.tokens[j] of the time of the call, cut to
+        max_new_tokens; stats = {"steps", "emitted": ids per task before the cut (= steps + accepted), "accepted": accepted drafts per
+        task, "mean_accepted": accepted drafts per task and step}."""
+        b = ctx.tokens.numel()
+        out = [[] for _ in range(b)]
+        accepted = [0] * b
+        steps = 0
+        while min(len(o) for o in out) < max_new_tokens and ctx.steps_left >= state.k + 1:
+            res = self.step_lookup(ctx, state)
+            acc, tok = res.accepted.tolist(), res.tokens.tolist()
+            for j in range(b):
+                out[j] += tok[j][:acc[j] + 1]
+                accepted[j] += acc[j]
+            steps += 1
+        stats = {"steps": steps, "emitted": [len(o) for o in out], "accepted": accepted,
+                 "mean_accepted": sum(accepted) / (steps * b) if steps else 0.0}
+        return [o[:max_new_tokens] for o in out], stats
 
     def advance(self, ctx: DynBatchContext, next_tokens: torch.Tensor):
         """Device-side bookkeeping between steps (what fill_search_tokens does on the host in the

@@ -857,6 +857,50 @@ def spec_accept(logits, drafts, tokens=None, positions=None, placement=None, val
     return accepted, out_tokens.view(b, len_q)
 
 
+def lookup_draft(history, hist_lens, k, max_ngram=3, min_ngram=1, new_tokens=None, drafts=None, match=None):
+    """The drafter of a speculative step by prompt lookup (zl_lookup_draft, one launch): history (B, cap) int32 rows and hist_lens (B)
+    int32 are the tasks' token histories, updated in place.  Per task: append the ids of new_tokens[b] (B, n_new <= 32, int32) before its
+    first negative one -- a row of spec_accept's out_tokens -- to the row (ids beyond cap are dropped, the length still counts them:
+    such a task has overflowed and drafts nothing from then on), then find the longest n-gram (max_ngram down to min_ngram) at the
+    history's end that also occurs earlier in it, at the latest start that has k tokens behind it (else the earliest), and propose
+    those tokens.  Returns (drafts (B, k) int32, -1 where the history ends or nothing matched; match (B, 2) int32 = (n, start), (0, -1)
+    without a match); drafts / match: buffers to write into (a captured call)."""
+    if not (torch.is_tensor(history) and torch.is_tensor(hist_lens)):
+        raise ZLError("lookup_draft: history and hist_lens are tensors")
+    if history.dim() != 2 or history.dtype != torch.int32 or not history.is_contiguous() or history.shape[0] < 1 or history.shape[1] < 2:
+        raise ZLError("lookup_draft: history is (B, cap) contiguous int32, cap >= 2")
+    b, cap = history.shape
+    if cap >= 1 << 31:
+        raise ZLError("lookup_draft: a history row holds fewer than 2^31 ids")
+    if hist_lens.dtype != torch.int32 or hist_lens.dim() != 1 or hist_lens.numel() != b or not hist_lens.is_contiguous():
+        raise ZLError("lookup_draft: hist_lens is (B) contiguous int32")
+    k, max_ngram, min_ngram = int(k), int(max_ngram), int(min_ngram)
+    if not 1 <= k <= 31:
+        raise ZLError("lookup_draft: 1 <= k <= 31 (a verify step has at most 32 rows per task)")
+    if not 1 <= min_ngram <= max_ngram <= 16:
+        raise ZLError("lookup_draft: 1 <= min_ngram <= max_ngram <= 16")
+    n_new = 0
+    if new_tokens is not None:
+        if not (torch.is_tensor(new_tokens) and new_tokens.dim() == 2 and new_tokens.shape[0] == b and 1 <= new_tokens.shape[1] <= 32
+                and new_tokens.dtype == torch.int32 and new_tokens.is_contiguous()):
+            raise ZLError("lookup_draft: new_tokens is (B, n_new) contiguous int32, 1 <= n_new <= 32")
+        n_new = new_tokens.shape[1]
+    if drafts is not None and not (torch.is_tensor(drafts) and drafts.dtype == torch.int32 and drafts.numel() == b * k
+                                   and drafts.is_contiguous()):
+        raise ZLError("lookup_draft: drafts: contiguous int32 (B, k)")
+    if match is not None and not (torch.is_tensor(match) and match.dtype == torch.int32 and match.numel() == b * 2 and match.is_contiguous()):
+        raise ZLError("lookup_draft: match: contiguous int32 (B, 2)")
+    if not history.is_cuda or any(t is not None and t.device != history.device for t in (hist_lens, new_tokens, drafts, match)):
+        raise ZLError("lookup_draft: CUDA history, every other tensor on the history's device")
+    if drafts is None:
+        drafts = torch.empty((b, k), dtype=torch.int32, device=history.device)
+    if match is None:
+        match = torch.empty((b, 2), dtype=torch.int32, device=history.device)
+    check(lib().zl_lookup_draft(_p(history), _i(cap), _p(hist_lens), _p(new_tokens), _i(n_new), _i(b), _i(k), C.c_int(max_ngram),
+                                C.c_int(min_ngram), _p(drafts), _p(match), _stream()), "lookup_draft")
+    return drafts.view(b, k), match.view(b, 2)
+
+
 # --------------------------------------------------------------------------------------------------
 # scoring: functions::Gemm + nn::log_prob_raw / greedy_match_raw (src/nn/functions/cross_entropy.cu:7-69, 358-403) without the
 # (M, N) logits: csrc/lm_head_score.hip
