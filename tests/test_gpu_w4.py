@@ -750,6 +750,33 @@ def test_attention_mask_form_split_records_merge(oracle, dev, b, h, hkv, n, lens
     assert torch.equal(got, want) and torch.equal(got_res, want_res)
 
 
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_fp32_split_records_are_the_two_launch_path_s(dev, dtype, monkeypatch):
+    """zl_decode_attn_splits (fp32 records, no merge) and zl_decode_attn_ex launch the same kernel with the same parameters: the
+    workspaces they leave are equal bit for bit, the words neither writes included.  Three 128-key splits; one task ends inside a
+    split, one has a single key."""
+    from zhilight_amd import ops
+    monkeypatch.setenv("ZL_W4_SMALL_ALGO", "1")                # the fp32-record entry point, for fp16 rows too
+    b, h, hkv, d, lens, valid = 3, 8, 2, 128, [160, 128, 300], [129, 1, 300]
+    max_len = max(lens)
+    gen = torch.Generator(device="cpu").manual_seed(811)
+    dk = [torch.randn(L, hkv, d, generator=gen).to(dtype).to(dev) for L in lens]
+    dv = [torch.randn(L, hkv, d, generator=gen).to(dtype).to(dev) for L in lens]
+    q = torch.randn(b, 1, h, d, generator=gen).to(dtype).to(dev)
+    bl, vl = _t(np.array(lens, np.int32), dev), _t(np.array(valid, np.int32), dev)
+    ka, va = ops.make_ptr_table(dk), ops.make_ptr_table(dv)
+    scale = 1.0 / np.sqrt(d)
+    assert ops.decode_attn_split_len(b, hkv, max_len) == 128
+    ws = ops.decode_attn_workspace(b, 1, h, d, max_len, dev)
+    ws.fill_(-12345.0)
+    ops.multi_query_attention_rag_buffer(q, bl, ka, va, None, scale, max_len, hkv, valid_lens=vl, workspace=ws)
+    two_launch = ws.clone()
+    ws.fill_(-12345.0)
+    ops.decode_attention_splits(q, bl, ka, va, vl, scale, max_len, hkv, ws)
+    assert (ws != -12345.0).any()
+    assert torch.equal(ws, two_launch)
+
+
 def test_attention_split_merge_plan_limits(dev):
     from zhilight_amd import ops
     from zhilight_amd._lib import ZLError

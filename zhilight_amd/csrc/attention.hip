@@ -20,6 +20,7 @@
 //  * partial (acc[D], m, l) per split goes to a small fp32 workspace; a second tiny kernel merges
 //    the splits:  out = sum_s acc_s e^{m_s-M} / (sum_s l_s e^{m_s-M} + 1e-20).
 #include <algorithm>
+#include <type_traits>
 #include "zl_common.h"
 
 namespace {
@@ -28,40 +29,40 @@ constexpr int kSteps = 8;  // key-steps per chunk
 constexpr int kMaxSplits = 512;   // splits a merge can hold (k_decode_attn_combine's kMaxS)
 
 struct AttnParams {
-    const uint16_t* q;
-    const int32_t* buf_lens;
-    const uint16_t* const* k_bufs;
-    const uint16_t* const* v_bufs;
-    const int8_t* mask;
-    const int32_t* valid_lens;
-    uint16_t* out;
-    float* ws;
-    int b, len_q, h, hkv, n_rep, rows;  // rows = len_q * n_rep
-    int passes, split_len, max_splits;
-    float scale;
-    int bshd;
+    const uint16_t* q = nullptr;
+    const int32_t* buf_lens = nullptr;
+    const uint16_t* const* k_bufs = nullptr;
+    const uint16_t* const* v_bufs = nullptr;
+    const int8_t* mask = nullptr;
+    const int32_t* valid_lens = nullptr;
+    uint16_t* out = nullptr;
+    float* ws = nullptr;
+    int b = 0, len_q = 0, h = 0, hkv = 0, n_rep = 0, rows = 0;  // rows = len_q * n_rep
+    int passes = 0, split_len = 0, max_splits = 0;
+    float scale = 0.f;
+    int bshd = 0;
     // fused decode front end (FUSE): q/k/v come from the fused qkv rows and are rotated in-kernel
-    const uint16_t* qkv;        // (B, (H + 2 Hkv) * D)
-    const float* cosv;          // (B, D)
-    const float* sinv;
-    const int32_t* placement;   // (B) slot of the new token in its task's buffers
-    uint16_t* const* k_bufs_w;  // writable views of k_bufs / v_bufs
-    uint16_t* const* v_bufs_w;
-    int neox;
+    const uint16_t* qkv = nullptr;        // (B, (H + 2 Hkv) * D)
+    const float* cosv = nullptr;          // (B, D)
+    const float* sinv = nullptr;
+    const int32_t* placement = nullptr;   // (B) slot of the new token in its task's buffers
+    uint16_t* const* k_bufs_w = nullptr;  // writable views of k_bufs / v_bufs
+    uint16_t* const* v_bufs_w = nullptr;
+    int neox = 1;
     // INT8 cache (k_decode_attn_partial_q8): k_bufs / v_bufs hold u8 codes, one fp32 scale per (key, kv head)
-    const float* const* k_scales;
-    const float* const* v_scales;
+    const float* const* k_scales = nullptr;
+    const float* const* v_scales = nullptr;
     // k_decode_attn_mfma: 1 = partials leave as NORMALISED fp16 rows [vh][split][128] + fp32 (max, sum) pairs behind them
     // (zl_decode_attn_splits_h: 264 instead of 520 bytes per (head, split) for the merging projection to re-read)
-    int half_partials;
+    int half_partials = 0;
     // k_decode_attn_mfma, last-arriver merge (zl_decode_attn_la): la = 1 -> every workgroup publishes its split record write-through,
     // counts its arrival on la_cnt[task * hkv + kv head] and the LAST one of the pair merges the pair's records into `out`
     // (no merge launch, no merging prologue); la_cnt is all zero between launches (the last arriver resets its word)
-    int la;
-    int* la_cnt;
+    int la = 0;
+    int* la_cnt = nullptr;
     // causal ("staircase") form of k_decode_attn_mfma (zl_decode_attn_causal): query row qi of a task sees valid_lens[b] + qi keys;
     // the 16-row tiles of its len_q * n_rep rows are folded into grid.y (blockIdx.y = tile * hkv + kv head)
-    int causal;
+    int causal = 0;
 };
 
 typedef _Float16 hv2 __attribute__((ext_vector_type(2)));
@@ -1440,43 +1441,153 @@ __global__ __launch_bounds__(kMD) void k_decode_attn_combine_h(const AttnParams 
     p.out[(size_t)vh * kMD + d] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(a * zi));
 }
 
+// ---- host side: one place for the launch parameters' geometry, one for each launch --------------------------------------------
+// An entry point below checks its arguments, names the AttnParams fields it sets differently from the struct's defaults, takes the
+// geometry from attn_geometry and hands the struct to a launch helper.  A new variant's field is a default in the struct and one
+// assignment in the entry point that uses it.
+//
+// Statuses.  The checks run in the order EINVAL (null pointer, non-positive size), ESHAPE, EDTYPE, ELIMIT.  Known inconsistencies,
+// kept as callers see them today: zl_decode_attn_splits / _splits_h / _splits_h_mask / _la report b > 65535 and more than 16 query
+// heads per kv head as ESHAPE where _ex / _causal / _fused / _quant_ex report their grid limits as ELIMIT; _combine_h checks neither
+// h % hkv nor a dtype; _la checks its split_len (EINVAL) after its dtype.  tests/test_decode_attn_host.py pins them.
+#define ZL_ATTN_TRY(...)                /* variadic: template argument lists carry commas */ \
+    do {                                \
+        const int e_ = (__VA_ARGS__);   \
+        if (e_) return e_;              \
+    } while (0)
+
+// f(std::integral_constant<int, DT>) for the runtime dtype, which the caller has checked to be ZL_F16 or ZL_BF16
+template <class F>
+static inline int by_dtype(int dtype, F&& f) {
+    return dtype == ZL_F16 ? f(std::integral_constant<int, ZL_F16>{}) : f(std::integral_constant<int, ZL_BF16>{});
+}
+
+// the checks every launcher but _combine_h starts with (`pointers`: all of its required ones are there)
+static inline int attn_check_args(bool pointers, int64_t b, int64_t len_q, int64_t h, int64_t hkv, int64_t d, int64_t max_len_buf) {
+    ZL_CHECK_ARG(pointers, ZL_EINVAL);
+    ZL_CHECK_ARG(b > 0 && len_q > 0 && h > 0 && hkv > 0 && d > 0 && max_len_buf > 0, ZL_EINVAL);
+    ZL_CHECK_ARG(h % hkv == 0, ZL_ESHAPE);
+    return ZL_OK;
+}
+
+static inline bool attn_dtype_ok(int dtype) { return dtype == ZL_F16 || dtype == ZL_BF16; }
+
+// what the matrix-core kernel takes at one query row per task (after attn_check_args: hkv > 0)
+static inline bool attn_mfma_shape_ok(int64_t b, int64_t h, int64_t hkv, int64_t d) {
+    return d == kMD && h / hkv <= 16 && b <= 65535 && hkv <= 65535;
+}
+
+// b, len_q, h, hkv, n_rep, rows, split_len, max_splits of a launch over buffers of max_len_buf slots; ZL_ELIMIT when the splits
+// exceed what the merge holds (`cap`).  split_len == 0: attn_split_len's
+static int attn_geometry(AttnParams& p, int64_t b, int64_t len_q, int64_t h, int64_t hkv, int64_t max_len_buf,
+                         int cap = kMaxSplits, int split_len = 0) {
+    p.b = (int)b; p.len_q = (int)len_q; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
+    p.rows = p.len_q * p.n_rep;
+    p.split_len = split_len ? split_len : attn_split_len(b, hkv, max_len_buf);
+    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
+    return p.max_splits <= cap ? ZL_OK : ZL_ELIMIT;
+}
+
+// the VALU kernels take `rt` query rows of a kv head per workgroup, in grid (splits, hkv, b * passes)
+static int attn_set_passes(AttnParams& p, int rt) {
+    p.passes = (p.rows + rt - 1) / rt;
+    return (int64_t)p.b * p.passes <= 65535 && p.hkv <= 65535 ? ZL_OK : ZL_ELIMIT;
+}
+
+// k_decode_attn_mfma<DT, ...> on `waves` wavefronts per workgroup; grid (splits, kv heads [x 16-row tiles, causal form], tasks)
+template <int NW = 4, bool LA = false, int PF = 1, bool MASKED = false, bool CAUSAL = false>
+int launch_mfma(const AttnParams& p, int dtype, hipStream_t st, int waves = NW) {
+    const int tiles = CAUSAL ? (p.rows + 15) / 16 : 1;
+    const dim3 grid((unsigned)p.max_splits, (unsigned)(p.hkv * tiles), (unsigned)p.b);
+    return by_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_decode_attn_mfma<decltype(dt)::value, NW, LA, PF, MASKED, CAUSAL>), grid, dim3(64 * waves), 0, st, p);
+        return zl_launch_status();
+    });
+}
+
+// the merge of fp32 split records as a launch of its own
+template <int D>
+int launch_combine(const AttnParams& p, int dtype, hipStream_t st) {
+    return by_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_decode_attn_combine<decltype(dt)::value, D>), dim3((unsigned)((int64_t)p.b * p.len_q * p.h)), dim3(D), 0, st, p);
+        return zl_launch_status();
+    });
+}
+
+static inline int valu_rt(int rows) { return rows >= 8 ? 8 : (rows >= 4 ? 4 : (rows >= 2 ? 2 : 1)); }
+static inline int q8_rt(int rows) { return rows >= 4 ? 4 : (rows >= 2 ? 2 : 1); }
+
 template <int DT, int D, bool FUSE>
 int launch_d(const AttnParams& p, hipStream_t st) {
     dim3 grid((unsigned)p.max_splits, (unsigned)p.hkv, (unsigned)(p.b * p.passes));
-    const int rt = p.rows >= 8 ? 8 : (p.rows >= 4 ? 4 : (p.rows >= 2 ? 2 : 1));
 #define ZL_ATTN_RT(RT)                                                                                          \
     if (p.mask) hipLaunchKernelGGL((k_decode_attn_partial<DT, D, RT, FUSE, true>), grid, dim3(256), 0, st, p);      \
     else hipLaunchKernelGGL((k_decode_attn_partial<DT, D, RT, FUSE, false>), grid, dim3(256), 0, st, p);
-    switch (rt) {
+    switch (valu_rt(p.rows)) {
         case 1: ZL_ATTN_RT(1) break;
         case 2: ZL_ATTN_RT(2) break;
         case 4: ZL_ATTN_RT(4) break;
         default: ZL_ATTN_RT(8) break;
     }
 #undef ZL_ATTN_RT
-    int e = zl_launch_status();
-    if (e) return e;
-    hipLaunchKernelGGL((k_decode_attn_combine<DT, D>), dim3((unsigned)(p.b * p.len_q * p.h)), dim3(D), 0, st, p);
-    return zl_launch_status();
+    ZL_ATTN_TRY(zl_launch_status());
+    return launch_combine<D>(p, DT, st);
 }
 
 template <int DT, int D>
 int launch_q8(const AttnParams& p, hipStream_t st) {
     dim3 grid((unsigned)p.max_splits, (unsigned)p.hkv, (unsigned)(p.b * p.passes));
-    const int rt = p.rows >= 4 ? 4 : (p.rows >= 2 ? 2 : 1);
 #define ZL_ATTN_RT(RT)                                                                                       \
     if (p.mask) hipLaunchKernelGGL((k_decode_attn_partial_q8<DT, D, RT, true>), grid, dim3(256), 0, st, p);  \
     else hipLaunchKernelGGL((k_decode_attn_partial_q8<DT, D, RT, false>), grid, dim3(256), 0, st, p);
-    switch (rt) {
+    switch (q8_rt(p.rows)) {
         case 1: ZL_ATTN_RT(1) break;
         case 2: ZL_ATTN_RT(2) break;
         default: ZL_ATTN_RT(4) break;
     }
 #undef ZL_ATTN_RT
-    int e = zl_launch_status();
-    if (e) return e;
-    hipLaunchKernelGGL((k_decode_attn_combine<DT, D>), dim3((unsigned)(p.b * p.len_q * p.h)), dim3(D), 0, st, p);
-    return zl_launch_status();
+    ZL_ATTN_TRY(zl_launch_status());
+    return launch_combine<D>(p, DT, st);
+}
+
+// launch_d / launch_q8 by runtime head size and dtype (after attn_set_passes with the same row tile)
+template <bool FUSE>
+int launch_valu(const AttnParams& p, int64_t d, int dtype, hipStream_t st) {
+    return by_dtype(dtype, [&](auto dt) -> int {
+        constexpr int DT = decltype(dt)::value;
+        switch (d) {
+            case 64: return launch_d<DT, 64, FUSE>(p, st);
+            case 128: return launch_d<DT, 128, FUSE>(p, st);
+            case 256: return launch_d<DT, 256, FUSE>(p, st);
+            default: return ZL_ESHAPE;
+        }
+    });
+}
+
+int launch_valu_q8(const AttnParams& p, int64_t d, int dtype, hipStream_t st) {
+    return by_dtype(dtype, [&](auto dt) -> int {
+        constexpr int DT = decltype(dt)::value;
+        switch (d) {
+            case 64: return launch_q8<DT, 64>(p, st);
+            case 128: return launch_q8<DT, 128>(p, st);
+            case 256: return launch_q8<DT, 256>(p, st);
+            default: return ZL_ESHAPE;
+        }
+    });
+}
+
+// zl_decode_attn_splits / _splits_h / _splits_h_mask: one query row per task on the matrix-core kernel, records only, no merge
+int attn_splits(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs, const uint16_t* const* v_bufs,
+                const int8_t* mask, const int32_t* valid_lens, void* workspace, int64_t b, int64_t h, int64_t hkv, int64_t d,
+                float scale, int64_t max_len_buf, int bshd, int dtype, int half_partials, zl_stream_t s) {
+    ZL_ATTN_TRY(attn_check_args(q && buf_lens && k_bufs && v_bufs && (mask || valid_lens) && workspace, b, 1, h, hkv, d, max_len_buf));
+    ZL_CHECK_ARG(attn_mfma_shape_ok(b, h, hkv, d), ZL_ESHAPE);
+    ZL_CHECK_ARG(attn_dtype_ok(dtype), ZL_EDTYPE);
+    AttnParams p;
+    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.mask = mask; p.valid_lens = valid_lens;
+    p.ws = (float*)workspace; p.scale = scale; p.bshd = bshd; p.passes = 1; p.half_partials = half_partials;
+    ZL_ATTN_TRY(attn_geometry(p, b, 1, h, hkv, max_len_buf));
+    return mask ? launch_mfma<4, false, 1, true>(p, dtype, (hipStream_t)s) : launch_mfma<>(p, dtype, (hipStream_t)s);
 }
 
 }  // namespace
@@ -1502,85 +1613,41 @@ int zl_decode_attn_ex(const uint16_t* q, const int32_t* buf_lens, const uint16_t
                       const uint16_t* const* v_bufs, const int8_t* mask, const int32_t* valid_lens, uint16_t* out,
                       void* workspace, int64_t b, int64_t len_q, int64_t h, int64_t hkv, int64_t d, float scale,
                       int64_t max_len_buf, int bshd, int dtype, int algo, zl_stream_t s) {
-    ZL_CHECK_ARG(q && buf_lens && k_bufs && v_bufs && out && workspace, ZL_EINVAL);
-    ZL_CHECK_ARG(mask || valid_lens, ZL_EINVAL);
-    ZL_CHECK_ARG(b > 0 && len_q > 0 && h > 0 && hkv > 0 && d > 0 && max_len_buf > 0, ZL_EINVAL);
-    ZL_CHECK_ARG(h % hkv == 0, ZL_ESHAPE);
-    ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
+    ZL_ATTN_TRY(attn_check_args(q && buf_lens && k_bufs && v_bufs && out && workspace && (mask || valid_lens), b, len_q, h, hkv, d,
+                                max_len_buf));
+    ZL_CHECK_ARG(attn_dtype_ok(dtype), ZL_EDTYPE);
     AttnParams p;
     p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.mask = mask; p.valid_lens = valid_lens;
-    p.out = out; p.ws = (float*)workspace;
-    p.b = (int)b; p.len_q = (int)len_q; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
-    p.rows = p.len_q * p.n_rep;
-    const int rt = p.rows >= 8 ? 8 : (p.rows >= 4 ? 4 : (p.rows >= 2 ? 2 : 1));
-    p.passes = (p.rows + rt - 1) / rt;
-    p.split_len = attn_split_len(b, hkv, max_len_buf);
-    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
-    ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
-    p.scale = scale; p.bshd = bshd;
-    ZL_CHECK_ARG((int64_t)p.b * p.passes <= 65535 && hkv <= 65535, ZL_ELIMIT);
+    p.out = out; p.ws = (float*)workspace; p.scale = scale; p.bshd = bshd;
+    ZL_ATTN_TRY(attn_geometry(p, b, len_q, h, hkv, max_len_buf));
+    ZL_ATTN_TRY(attn_set_passes(p, valu_rt(p.rows)));
     hipStream_t hs = (hipStream_t)s;
-    p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
-    {   // decode fast path on the matrix cores: all query rows of a kv head in one 16-row MFMA block
-        // with the reference's visibility mask instead of prefix lengths: the same kernel's mask form, for one query row per task
-        if (algo != 1 && (!mask || (len_q == 1 && !valid_lens)) && d == kMD && p.rows <= 16) {
-            p.passes = 1;
-            const dim3 grid((unsigned)p.max_splits, (unsigned)hkv, (unsigned)b);
-            if (mask) {
-                if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_mfma<ZL_F16, 4, false, 1, true>), grid, dim3(256), 0, hs, p);
-                else hipLaunchKernelGGL((k_decode_attn_mfma<ZL_BF16, 4, false, 1, true>), grid, dim3(256), 0, hs, p);
-            } else if (dtype == ZL_F16) hipLaunchKernelGGL(k_decode_attn_mfma<ZL_F16>, grid, dim3(256), 0, hs, p);
-            else hipLaunchKernelGGL(k_decode_attn_mfma<ZL_BF16>, grid, dim3(256), 0, hs, p);
-            int e = zl_launch_status();
-            if (e) return e;
-            if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_combine<ZL_F16, kMD>), dim3((unsigned)(b * len_q * h)), dim3(kMD), 0, hs, p);
-            else hipLaunchKernelGGL((k_decode_attn_combine<ZL_BF16, kMD>), dim3((unsigned)(b * len_q * h)), dim3(kMD), 0, hs, p);
-            return zl_launch_status();
-        }
+    // decode fast path on the matrix cores: all query rows of a kv head in one 16-row MFMA block
+    // with the reference's visibility mask instead of prefix lengths: the same kernel's mask form, for one query row per task
+    if (algo != 1 && (!mask || (len_q == 1 && !valid_lens)) && d == kMD && p.rows <= 16) {
+        p.passes = 1;
+        ZL_ATTN_TRY(mask ? launch_mfma<4, false, 1, true>(p, dtype, hs) : launch_mfma<>(p, dtype, hs));
+        return launch_combine<kMD>(p, dtype, hs);
     }
-#define ZL_ATTN_D(DT, FUSE)                                    \
-    switch (d) {                                               \
-        case 64: return launch_d<DT, 64, FUSE>(p, hs);         \
-        case 128: return launch_d<DT, 128, FUSE>(p, hs);       \
-        case 256: return launch_d<DT, 256, FUSE>(p, hs);       \
-        default: return ZL_ESHAPE;                             \
-    }
-    if (dtype == ZL_F16) { ZL_ATTN_D(ZL_F16, false) }
-    ZL_ATTN_D(ZL_BF16, false)
+    return launch_valu<false>(p, d, dtype, hs);
 }
 
 int zl_decode_attn_causal(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs, const uint16_t* const* v_bufs,
                           const int32_t* valid_lens, uint16_t* out, void* workspace, int64_t b, int64_t len_q, int64_t h, int64_t hkv,
                           int64_t d, float scale, int64_t max_len_buf, int bshd, int dtype, zl_stream_t s) {
-    ZL_CHECK_ARG(q && buf_lens && k_bufs && v_bufs && valid_lens && out && workspace, ZL_EINVAL);
-    ZL_CHECK_ARG(b > 0 && len_q > 0 && h > 0 && hkv > 0 && d > 0 && max_len_buf > 0, ZL_EINVAL);
-    ZL_CHECK_ARG(h % hkv == 0 && d == kMD, ZL_ESHAPE);                                     // the matrix-core kernel
-    ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
+    ZL_ATTN_TRY(attn_check_args(q && buf_lens && k_bufs && v_bufs && valid_lens && out && workspace, b, len_q, h, hkv, d, max_len_buf));
+    ZL_CHECK_ARG(d == kMD, ZL_ESHAPE);                                                     // the matrix-core kernel
+    ZL_CHECK_ARG(attn_dtype_ok(dtype), ZL_EDTYPE);
     ZL_CHECK_ARG(len_q <= 32, ZL_ELIMIT);
     AttnParams p;
-    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.mask = nullptr; p.valid_lens = valid_lens;
-    p.out = out; p.ws = (float*)workspace;
-    p.b = (int)b; p.len_q = (int)len_q; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
-    p.rows = p.len_q * p.n_rep; p.passes = 1;
+    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.valid_lens = valid_lens;
+    p.out = out; p.ws = (float*)workspace; p.scale = scale; p.bshd = bshd; p.passes = 1; p.causal = 1;
     // the split length of zl_decode_attn over the same b tasks: at len_q == 1 the records and the merge are that launch's
-    p.split_len = attn_split_len(b, hkv, max_len_buf);
-    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
-    ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
+    ZL_ATTN_TRY(attn_geometry(p, b, len_q, h, hkv, max_len_buf));
     const int64_t tiles = (p.rows + 15) / 16;
     ZL_CHECK_ARG(b <= 65535 && hkv * tiles <= 65535 && b * len_q * h < ((int64_t)1 << 31), ZL_ELIMIT);
-    p.scale = scale; p.bshd = bshd;
-    p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr; p.causal = 1;
-    hipStream_t hs = (hipStream_t)s;
-    const dim3 grid((unsigned)p.max_splits, (unsigned)(hkv * tiles), (unsigned)b);
-    if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_mfma<ZL_F16, 4, false, 1, false, true>), grid, dim3(256), 0, hs, p);
-    else hipLaunchKernelGGL((k_decode_attn_mfma<ZL_BF16, 4, false, 1, false, true>), grid, dim3(256), 0, hs, p);
-    int e = zl_launch_status();
-    if (e) return e;
-    if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_combine<ZL_F16, kMD>), dim3((unsigned)(b * len_q * h)), dim3(kMD), 0, hs, p);
-    else hipLaunchKernelGGL((k_decode_attn_combine<ZL_BF16, kMD>), dim3((unsigned)(b * len_q * h)), dim3(kMD), 0, hs, p);
-    return zl_launch_status();
+    ZL_ATTN_TRY(launch_mfma<4, false, 1, false, true>(p, dtype, (hipStream_t)s));
+    return launch_combine<kMD>(p, dtype, (hipStream_t)s);
 }
 
 int64_t zl_decode_attn_split_len(int64_t b, int64_t hkv, int64_t max_len_buf) {
@@ -1591,69 +1658,20 @@ int64_t zl_decode_attn_split_len(int64_t b, int64_t hkv, int64_t max_len_buf) {
 int zl_decode_attn_splits(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs,
                           const uint16_t* const* v_bufs, const int32_t* valid_lens, void* workspace, int64_t b, int64_t h,
                           int64_t hkv, int64_t d, float scale, int64_t max_len_buf, int bshd, int dtype, zl_stream_t s) {
-    ZL_CHECK_ARG(q && buf_lens && k_bufs && v_bufs && valid_lens && workspace, ZL_EINVAL);
-    ZL_CHECK_ARG(b > 0 && h > 0 && hkv > 0 && d > 0 && max_len_buf > 0, ZL_EINVAL);
-    ZL_CHECK_ARG(h % hkv == 0 && d == kMD && h / hkv <= 16 && b <= 65535 && hkv <= 65535, ZL_ESHAPE);   // the matrix-core kernel
-    ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
-    AttnParams p;
-    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.mask = nullptr; p.valid_lens = valid_lens;
-    p.out = nullptr; p.ws = (float*)workspace;
-    p.b = (int)b; p.len_q = 1; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
-    p.rows = p.n_rep; p.passes = 1;
-    p.split_len = attn_split_len(b, hkv, max_len_buf);
-    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
-    ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
-    p.scale = scale; p.bshd = bshd;
-    p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
-    const dim3 grid((unsigned)p.max_splits, (unsigned)hkv, (unsigned)b);
-    if (dtype == ZL_F16) hipLaunchKernelGGL(k_decode_attn_mfma<ZL_F16>, grid, dim3(256), 0, (hipStream_t)s, p);
-    else hipLaunchKernelGGL(k_decode_attn_mfma<ZL_BF16>, grid, dim3(256), 0, (hipStream_t)s, p);
-    return zl_launch_status();
+    return attn_splits(q, buf_lens, k_bufs, v_bufs, nullptr, valid_lens, workspace, b, h, hkv, d, scale, max_len_buf, bshd, dtype, 0, s);
 }
 
+// half-precision records (AttnParams::half_partials): fp16 queries only
 int zl_decode_attn_splits_h(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs,
                             const uint16_t* const* v_bufs, const int32_t* valid_lens, void* workspace, int64_t b, int64_t h,
                             int64_t hkv, int64_t d, float scale, int64_t max_len_buf, int bshd, zl_stream_t s) {
-    ZL_CHECK_ARG(q && buf_lens && k_bufs && v_bufs && valid_lens && workspace, ZL_EINVAL);
-    ZL_CHECK_ARG(b > 0 && h > 0 && hkv > 0 && d > 0 && max_len_buf > 0, ZL_EINVAL);
-    ZL_CHECK_ARG(h % hkv == 0 && d == kMD && h / hkv <= 16 && b <= 65535 && hkv <= 65535, ZL_ESHAPE);   // the matrix-core kernel
-    AttnParams p;
-    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.mask = nullptr; p.valid_lens = valid_lens;
-    p.out = nullptr; p.ws = (float*)workspace;
-    p.b = (int)b; p.len_q = 1; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
-    p.rows = p.n_rep; p.passes = 1;
-    p.split_len = attn_split_len(b, hkv, max_len_buf);
-    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
-    ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
-    p.scale = scale; p.bshd = bshd;
-    p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 1; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
-    const dim3 grid((unsigned)p.max_splits, (unsigned)hkv, (unsigned)b);
-    hipLaunchKernelGGL(k_decode_attn_mfma<ZL_F16>, grid, dim3(256), 0, (hipStream_t)s, p);
-    return zl_launch_status();
+    return attn_splits(q, buf_lens, k_bufs, v_bufs, nullptr, valid_lens, workspace, b, h, hkv, d, scale, max_len_buf, bshd, ZL_F16, 1, s);
 }
 
 int zl_decode_attn_splits_h_mask(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs,
                                  const uint16_t* const* v_bufs, const int8_t* mask, void* workspace, int64_t b, int64_t h,
                                  int64_t hkv, int64_t d, float scale, int64_t max_len_buf, int bshd, zl_stream_t s) {
-    ZL_CHECK_ARG(q && buf_lens && k_bufs && v_bufs && mask && workspace, ZL_EINVAL);
-    ZL_CHECK_ARG(b > 0 && h > 0 && hkv > 0 && d > 0 && max_len_buf > 0, ZL_EINVAL);
-    ZL_CHECK_ARG(h % hkv == 0 && d == kMD && h / hkv <= 16 && b <= 65535 && hkv <= 65535, ZL_ESHAPE);   // the matrix-core kernel
-    AttnParams p;
-    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.mask = mask; p.valid_lens = nullptr;
-    p.out = nullptr; p.ws = (float*)workspace;
-    p.b = (int)b; p.len_q = 1; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
-    p.rows = p.n_rep; p.passes = 1;
-    p.split_len = attn_split_len(b, hkv, max_len_buf);
-    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
-    ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
-    p.scale = scale; p.bshd = bshd;
-    p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 1; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
-    const dim3 grid((unsigned)p.max_splits, (unsigned)hkv, (unsigned)b);
-    hipLaunchKernelGGL((k_decode_attn_mfma<ZL_F16, 4, false, 1, true>), grid, dim3(256), 0, (hipStream_t)s, p);
-    return zl_launch_status();
+    return attn_splits(q, buf_lens, k_bufs, v_bufs, mask, nullptr, workspace, b, h, hkv, d, scale, max_len_buf, bshd, ZL_F16, 1, s);
 }
 
 int zl_decode_attn_combine_h(const void* workspace, const int32_t* buf_lens, const int32_t* valid_lens, uint16_t* out, int64_t b,
@@ -1661,15 +1679,8 @@ int zl_decode_attn_combine_h(const void* workspace, const int32_t* buf_lens, con
     ZL_CHECK_ARG(workspace && buf_lens && out, ZL_EINVAL);
     ZL_CHECK_ARG(b > 0 && h > 0 && hkv > 0 && max_len_buf > 0, ZL_EINVAL);
     AttnParams p;
-    p.q = nullptr; p.buf_lens = buf_lens; p.k_bufs = p.v_bufs = nullptr; p.mask = nullptr; p.valid_lens = valid_lens;
-    p.out = out; p.ws = (float*)const_cast<void*>(workspace);
-    p.b = (int)b; p.len_q = 1; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv); p.rows = p.n_rep; p.passes = 1;
-    p.split_len = attn_split_len(b, hkv, max_len_buf);
-    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
-    ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
-    p.scale = 0.f; p.bshd = 1;
-    p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 1; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
+    p.buf_lens = buf_lens; p.valid_lens = valid_lens; p.out = out; p.ws = (float*)const_cast<void*>(workspace);
+    ZL_ATTN_TRY(attn_geometry(p, b, 1, h, hkv, max_len_buf));
     hipLaunchKernelGGL(k_decode_attn_combine_h, dim3((unsigned)(b * h)), dim3(kMD), 0, (hipStream_t)s, p);
     return zl_launch_status();
 }
@@ -1719,72 +1730,44 @@ int64_t zl_decode_attn_la_workspace_bytes(int64_t b, int64_t h, int64_t hkv, int
 int zl_decode_attn_la(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs, const uint16_t* const* v_bufs,
                       const int32_t* valid_lens, uint16_t* out, void* workspace, int64_t b, int64_t h, int64_t hkv, int64_t d,
                       float scale, int64_t max_len_buf, int bshd, int dtype, int64_t split_len, int half_partials, zl_stream_t s) {
-    ZL_CHECK_ARG(q && buf_lens && k_bufs && v_bufs && valid_lens && out && workspace, ZL_EINVAL);
-    ZL_CHECK_ARG(b > 0 && h > 0 && hkv > 0 && d > 0 && max_len_buf > 0, ZL_EINVAL);
-    ZL_CHECK_ARG(h % hkv == 0 && d == kMD && h / hkv <= 16 && b <= 65535 && hkv <= 65535, ZL_ESHAPE);   // the matrix-core kernel
-    ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
+    ZL_ATTN_TRY(attn_check_args(q && buf_lens && k_bufs && v_bufs && valid_lens && out && workspace, b, 1, h, hkv, d, max_len_buf));
+    ZL_CHECK_ARG(attn_mfma_shape_ok(b, h, hkv, d), ZL_ESHAPE);
+    ZL_CHECK_ARG(attn_dtype_ok(dtype), ZL_EDTYPE);
     ZL_CHECK_ARG(!(half_partials & 1) || dtype == ZL_F16, ZL_EDTYPE);
     ZL_CHECK_ARG(split_len >= 0 && split_len % 32 == 0, ZL_EINVAL);
     AttnParams p;
-    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.mask = nullptr; p.valid_lens = valid_lens;
-    p.out = out;
-    p.la = 1; p.la_cnt = reinterpret_cast<int*>(workspace); p.causal = 0;
+    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.valid_lens = valid_lens; p.out = out;
+    p.la = 1; p.la_cnt = reinterpret_cast<int*>(workspace);
     p.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + la_counter_bytes(b, hkv));
-    p.b = (int)b; p.len_q = 1; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
-    p.rows = p.n_rep; p.passes = 1;
-    p.split_len = split_len ? (int)split_len : la_split_len(b, hkv, max_len_buf);
-    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
-    ZL_CHECK_ARG(p.max_splits <= kLaMaxSplits, ZL_ELIMIT);
+    p.scale = scale; p.bshd = bshd; p.passes = 1; p.half_partials = half_partials & 1;
+    ZL_ATTN_TRY(attn_geometry(p, b, 1, h, hkv, max_len_buf, kLaMaxSplits, split_len ? (int)split_len : la_split_len(b, hkv, max_len_buf)));
     ZL_CHECK_ARG((int64_t)b * h * p.max_splits * (kMD + 2) * 4 < ((int64_t)1 << 31), ZL_ELIMIT);
-    p.scale = scale; p.bshd = bshd;
-    p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = (half_partials & 1) ? 1 : 0;
     // bits 8.. of the flags word: waves per workgroup (0 = 8 from 256-key splits on, 4 from 128, else one per 32 keys) -- A/B only
     int nw = p.split_len >= 128 ? 4 : p.split_len / 32;      // (8 waves per workgroup: measured behind 4 at every batch, on request only)
     const int nw_req = (half_partials >> 8) & 0xff;
     if (nw_req == 1 || nw_req == 2 || nw_req == 4 || nw_req == 8) nw = nw_req * 32 <= p.split_len ? nw_req : nw;
-    const dim3 grid((unsigned)p.max_splits, (unsigned)hkv, (unsigned)b);
-    if (nw == 8) {
-        if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_mfma<ZL_F16, 8, true>), grid, dim3(512), 0, (hipStream_t)s, p);
-        else hipLaunchKernelGGL((k_decode_attn_mfma<ZL_BF16, 8, true>), grid, dim3(512), 0, (hipStream_t)s, p);
-    } else {
+    if (nw == 8) return launch_mfma<8, true>(p, dtype, (hipStream_t)s);
 #ifndef ZL_ATTN_LA_PF
 #define ZL_ATTN_LA_PF 2        // (tools/ubench/variant.sh ... -DZL_ATTN_LA_PF=1 rebuilds the one-chunk-ahead launch for A/B runs)
 #endif
-        if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_mfma<ZL_F16, 4, true, ZL_ATTN_LA_PF>), grid, dim3(64 * nw), 0, (hipStream_t)s, p);
-        else hipLaunchKernelGGL((k_decode_attn_mfma<ZL_BF16, 4, true, ZL_ATTN_LA_PF>), grid, dim3(64 * nw), 0, (hipStream_t)s, p);
-    }
-    return zl_launch_status();
+    return launch_mfma<4, true, ZL_ATTN_LA_PF>(p, dtype, (hipStream_t)s, nw);
 }
 
 int zl_decode_attn_fused(const float* cosv, const float* sinv, const uint16_t* qkv, const int32_t* placement,
                          const int32_t* buf_lens, const int32_t* valid_lens, uint16_t* const* k_bufs,
                          uint16_t* const* v_bufs, uint16_t* out, void* workspace, int64_t b, int64_t h, int64_t hkv,
                          int64_t d, float scale, int64_t max_len_buf, int neox, int bshd, int dtype, zl_stream_t s) {
-    ZL_CHECK_ARG(cosv && sinv && qkv && placement && buf_lens && valid_lens && k_bufs && v_bufs && out && workspace, ZL_EINVAL);
-    ZL_CHECK_ARG(b > 0 && h > 0 && hkv > 0 && d > 0 && max_len_buf > 0, ZL_EINVAL);
-    ZL_CHECK_ARG(h % hkv == 0, ZL_ESHAPE);
-    ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
+    ZL_ATTN_TRY(attn_check_args(cosv && sinv && qkv && placement && buf_lens && valid_lens && k_bufs && v_bufs && out && workspace, b, 1, h,
+                                hkv, d, max_len_buf));
+    ZL_CHECK_ARG(attn_dtype_ok(dtype), ZL_EDTYPE);
     AttnParams p;
-    p.q = nullptr; p.buf_lens = buf_lens;
+    p.buf_lens = buf_lens; p.valid_lens = valid_lens; p.out = out; p.ws = (float*)workspace; p.scale = scale; p.bshd = bshd;
     p.k_bufs = reinterpret_cast<const uint16_t* const*>(k_bufs);
     p.v_bufs = reinterpret_cast<const uint16_t* const*>(v_bufs);
-    p.mask = nullptr; p.valid_lens = valid_lens; p.out = out; p.ws = (float*)workspace;
-    p.b = (int)b; p.len_q = 1; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
-    p.rows = p.n_rep;
-    const int rt = p.rows >= 8 ? 8 : (p.rows >= 4 ? 4 : (p.rows >= 2 ? 2 : 1));
-    p.passes = (p.rows + rt - 1) / rt;
-    p.split_len = attn_split_len(b, hkv, max_len_buf);
-    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
-    ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
-    p.scale = scale; p.bshd = bshd;
     p.qkv = qkv; p.cosv = cosv; p.sinv = sinv; p.placement = placement; p.k_bufs_w = k_bufs; p.v_bufs_w = v_bufs; p.neox = neox;
-    p.k_scales = p.v_scales = nullptr; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
-    ZL_CHECK_ARG((int64_t)p.b * p.passes <= 65535 && hkv <= 65535, ZL_ELIMIT);
-    hipStream_t hs = (hipStream_t)s;
-    if (dtype == ZL_F16) { ZL_ATTN_D(ZL_F16, true) }
-    ZL_ATTN_D(ZL_BF16, true)
-#undef ZL_ATTN_D
+    ZL_ATTN_TRY(attn_geometry(p, b, 1, h, hkv, max_len_buf));
+    ZL_ATTN_TRY(attn_set_passes(p, valu_rt(p.rows)));
+    return launch_valu<true>(p, d, dtype, (hipStream_t)s);
 }
 
 int zl_decode_attn_quant(const uint16_t* q, const int32_t* buf_lens, const uint8_t* const* k_bufs,
@@ -1801,44 +1784,25 @@ int zl_decode_attn_quant_ex(const uint16_t* q, const int32_t* buf_lens, const ui
                          const int8_t* mask, const int32_t* valid_lens, uint16_t* out, void* workspace, int64_t b,
                          int64_t len_q, int64_t h, int64_t hkv, int64_t d, float scale, int64_t max_len_buf, int bshd,
                          int dtype, int algo, zl_stream_t s) {
-    ZL_CHECK_ARG(q && buf_lens && k_bufs && v_bufs && k_scales && v_scales && out && workspace, ZL_EINVAL);
-    ZL_CHECK_ARG(mask || valid_lens, ZL_EINVAL);
-    ZL_CHECK_ARG(b > 0 && len_q > 0 && h > 0 && hkv > 0 && d > 0 && max_len_buf > 0, ZL_EINVAL);
-    ZL_CHECK_ARG(h % hkv == 0, ZL_ESHAPE);
-    ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
+    ZL_ATTN_TRY(attn_check_args(q && buf_lens && k_bufs && v_bufs && k_scales && v_scales && out && workspace && (mask || valid_lens), b,
+                                len_q, h, hkv, d, max_len_buf));
+    ZL_CHECK_ARG(attn_dtype_ok(dtype), ZL_EDTYPE);
     AttnParams p;
-    p.q = q; p.buf_lens = buf_lens;
+    p.q = q; p.buf_lens = buf_lens; p.mask = mask; p.valid_lens = valid_lens; p.out = out; p.ws = (float*)workspace;
     p.k_bufs = reinterpret_cast<const uint16_t* const*>(k_bufs);
     p.v_bufs = reinterpret_cast<const uint16_t* const*>(v_bufs);
-    p.k_scales = k_scales; p.v_scales = v_scales; p.half_partials = 0; p.la = 0; p.la_cnt = nullptr; p.causal = 0;
-    p.mask = mask; p.valid_lens = valid_lens; p.out = out; p.ws = (float*)workspace;
-    p.b = (int)b; p.len_q = (int)len_q; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
-    p.rows = p.len_q * p.n_rep;
-    const int rt = p.rows >= 4 ? 4 : (p.rows >= 2 ? 2 : 1);
-    p.passes = (p.rows + rt - 1) / rt;
-    p.split_len = attn_split_len(b, hkv, max_len_buf);
-    p.max_splits = (int)((max_len_buf + p.split_len - 1) / p.split_len);
-    ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
-    p.scale = scale; p.bshd = bshd;
-    ZL_CHECK_ARG((int64_t)p.b * p.passes <= 65535 && hkv <= 65535, ZL_ELIMIT);
-    p.qkv = nullptr; p.cosv = p.sinv = nullptr; p.placement = nullptr; p.k_bufs_w = p.v_bufs_w = nullptr; p.neox = 1;
+    p.k_scales = k_scales; p.v_scales = v_scales; p.scale = scale; p.bshd = bshd;
+    ZL_ATTN_TRY(attn_geometry(p, b, len_q, h, hkv, max_len_buf));
+    ZL_ATTN_TRY(attn_set_passes(p, q8_rt(p.rows)));
     hipStream_t hs = (hipStream_t)s;
-    {   // decode fast path on the matrix cores
-        if (algo != 1 && !mask && dtype == ZL_F16 && d == kMD && p.len_q * p.n_rep <= 16) {
-            p.passes = 1;
-            hipLaunchKernelGGL(k_decode_attn_mfma_q8, dim3((unsigned)p.max_splits, (unsigned)hkv, (unsigned)b), dim3(256), 0, hs, p);
-            int e = zl_launch_status();
-            if (e) return e;
-            hipLaunchKernelGGL((k_decode_attn_combine<ZL_F16, kMD>), dim3((unsigned)(b * len_q * h)), dim3(kMD), 0, hs, p);
-            return zl_launch_status();
-        }
+    // decode fast path on the matrix cores
+    if (algo != 1 && !mask && dtype == ZL_F16 && d == kMD && p.rows <= 16) {
+        p.passes = 1;
+        hipLaunchKernelGGL(k_decode_attn_mfma_q8, dim3((unsigned)p.max_splits, (unsigned)hkv, (unsigned)b), dim3(256), 0, hs, p);
+        ZL_ATTN_TRY(zl_launch_status());
+        return launch_combine<kMD>(p, dtype, hs);
     }
-    switch (d) {
-        case 64: return dtype == ZL_F16 ? launch_q8<ZL_F16, 64>(p, hs) : launch_q8<ZL_BF16, 64>(p, hs);
-        case 128: return dtype == ZL_F16 ? launch_q8<ZL_F16, 128>(p, hs) : launch_q8<ZL_BF16, 128>(p, hs);
-        case 256: return dtype == ZL_F16 ? launch_q8<ZL_F16, 256>(p, hs) : launch_q8<ZL_BF16, 256>(p, hs);
-        default: return ZL_ESHAPE;
-    }
+    return launch_valu_q8(p, d, dtype, hs);
 }
 
 }  // extern "C"
