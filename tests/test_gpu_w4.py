@@ -585,6 +585,16 @@ def test_fused_qkv_rotary_scatter_slab_head_sizes(oracle, dev, m, h, hkv, d, k):
     _fused_qkv_rope_case(oracle, dev, m, False, True, h, hkv, d, k)
 
 
+@pytest.mark.parametrize("m", [5, 17])
+@pytest.mark.parametrize("bshd", [True, False])
+def test_fused_qkv_rotary_scatter_phase_plain_instantiations(oracle, dev, m, bshd, monkeypatch):
+    """the phase kernel's plain rotation instantiations -- what the qkv launch falls back to when the slab launcher declines a
+    shape -- with the slab route switched off: 5 rows = one row block staged through LDS (up to 4 rows with K <= 4096 take the
+    register-resident instantiation), 17 rows = two row blocks.  Bit for bit against the two-call sequence."""
+    monkeypatch.setenv("ZL_W4_SLAB", "-1")
+    _fused_qkv_rope_case(oracle, dev, m, False, bshd, 8, 2, 128, 1024 + 256)
+
+
 def _fused_qkv_rope_case(oracle, dev, m, norm, bshd, h, hkv, d, k):
     from zhilight_amd import ops
     rng = np.random.default_rng(80 + m)

@@ -923,19 +923,6 @@ int launch_engine(const I8Params& p, int grid, int rounds_cap, hipStream_t hs) {
     return zl_launch_status();
 }
 
-I8Params eng_params(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                    const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups, int tiles,
-                    int epilogue, int ld_out, const uint16_t* norm_w, float norm_eps) {
-    I8Params p;
-    p.x = x; p.ldx = ldx; p.qw = reinterpret_cast<const uint4*>(qw); p.meta = meta; p.qw_bytes = qw_bytes; p.meta_bytes = meta_bytes;
-    p.bias = bias; p.residual = residual; p.y = y; p.m = m; p.n = n; p.k = k; p.groups = groups; p.tiles = tiles; p.epi = epilogue;
-    p.ld_out = ld_out; p.norm_w = norm_w; p.norm_eps = norm_eps;
-    p.cosv = p.sinv = nullptr; p.placement = p.buf_lens = nullptr; p.k_bufs = p.v_bufs = nullptr; p.q_out = nullptr;
-    p.h = p.hkv = p.d = p.bshd = 0; p.pair_stride = 1;
-    p.mg_part = nullptr; p.mg_stat = nullptr; p.mg_valid_lens = nullptr; p.mg_split_len = p.mg_max_splits = 0;
-    return p;
-}
-
 }  // namespace
 
 // what the engine covers: the integer-plane kernel's range with whole slots (K a multiple of 1024) and an LDS budget that
@@ -946,22 +933,17 @@ bool zl_w4_engine_covers(int64_t m, int64_t k, int r) {
 }
 
 // internal (called by zl_w4a16_gemm_mfma_ex under zl_w4_opts_t::small_algo == 2)
-int zl_w4a16_gemm_engine(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                         uint32_t meta_bytes, const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k,
-                         int groups, int tiles, int epilogue, int ld_out, const uint16_t* norm_w, float norm_eps, int slots_cap,
-                         hipStream_t hs) {
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
-    int r = (tiles + cus - 1) / cus;
+int zl_w4a16_gemm_engine(const W4Problem& pb, int slots_cap, hipStream_t hs) {
+    const int cus = zl_cu_count();
+    int r = (pb.tiles + cus - 1) / cus;
     if (r > 8) r = 8;
-    if (!zl_w4_engine_covers(m, k, r)) return ZL_ESHAPE;
-    const I8Params p = eng_params(x, ldx, qw, meta, qw_bytes, meta_bytes, bias, residual, y, m, n, k, groups, tiles, epilogue, ld_out,
-                                  norm_w, norm_eps);
-    const int grid = (tiles + r - 1) / r;
-    const bool lk = groups > 4 * kCW;
+    if (!zl_w4_engine_covers(pb.m, pb.k, r)) return ZL_ESHAPE;
+    const I8Params p = i8_params(pb);
+    const int grid = (pb.tiles + r - 1) / r;
+    const bool lk = pb.groups > 4 * kCW;
 #define ZL_ENG(RR)                                                                                           \
     case RR:                                                                                                 \
-        if (norm_w) return lk ? ZL_ESHAPE : launch_engine<RR, false, false, true, false>(p, grid, slots_cap, hs); \
+        if (pb.norm_w) return lk ? ZL_ESHAPE : launch_engine<RR, false, false, true, false>(p, grid, slots_cap, hs); \
         return lk ? launch_engine<RR, true, false, false, false>(p, grid, slots_cap, hs)                     \
                   : launch_engine<RR, false, false, false, false>(p, grid, slots_cap, hs);
     switch (r) { ZL_ENG(1) ZL_ENG(2) ZL_ENG(3) ZL_ENG(4) ZL_ENG(5) ZL_ENG(6) ZL_ENG(7) ZL_ENG(8) }
@@ -969,66 +951,38 @@ int zl_w4a16_gemm_engine(const uint16_t* x, int64_t ldx, const uint32_t* qw, con
     return ZL_EINVAL;
 }
 
-int zl_w4a16_gemm_engine_rope(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                              uint32_t meta_bytes, const uint16_t* bias, int m, int n, int k, int groups, int tiles,
-                              const uint16_t* norm_w, float norm_eps, const float* cosv, const float* sinv,
-                              const int32_t* placement, const int32_t* buf_lens, uint16_t* const* k_bufs,
-                              uint16_t* const* v_bufs, uint16_t* q_out, int h, int hkv, int d, int bshd, hipStream_t hs) {
-    if (!zl_w4_engine_covers(m, k, 2) || k > 4096 || d % 32 != 0 || n != (h + 2 * hkv) * d || tiles * 16 != n) return ZL_ESHAPE;
-    I8Params p = eng_params(x, ldx, qw, meta, qw_bytes, meta_bytes, bias, nullptr, nullptr, m, n, k, groups, tiles,
-                            bias ? ZL_EPI_BIAS : 0, n, norm_w, norm_eps);
-    p.cosv = cosv; p.sinv = sinv; p.placement = placement; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs;
-    p.q_out = q_out; p.h = h; p.hkv = hkv; p.d = d; p.bshd = bshd; p.pair_stride = d / 32;
-    const int grid = tiles / 2;
-    return norm_w ? launch_engine<2, false, true, true, false>(p, grid, 0, hs) : launch_engine<2, false, true, false, false>(p, grid, 0, hs);
+int zl_w4a16_gemm_engine_rope(const W4Problem& pb, const W4Rope& rp, hipStream_t hs) {
+    if (!zl_w4_engine_covers(pb.m, pb.k, 2) || pb.k > 4096 || !zl_w4m_rope_shape_ok(pb, rp)) return ZL_ESHAPE;
+    I8Params p = i8_params(pb);
+    i8_fill_rope(p, rp);
+    const int grid = pb.tiles / 2;
+    return pb.norm_w ? launch_engine<2, false, true, true, false>(p, grid, 0, hs) : launch_engine<2, false, true, false, false>(p, grid, 0, hs);
 }
 
-static I8Params eng_merge_params(const void* ws, const int32_t* buf_lens, const int32_t* valid_lens, int split_len, int max_splits,
-                                 const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                                 const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups,
-                                 int tiles, int epilogue) {
-    I8Params p = eng_params(nullptr, 0, qw, meta, qw_bytes, meta_bytes, bias, residual, y, m, n, k, groups, tiles, epilogue, n, nullptr, 0.f);
-    p.buf_lens = buf_lens;
-    p.mg_part = reinterpret_cast<const uint16_t*>(ws);
-    p.mg_stat = reinterpret_cast<const float*>(ws) + (size_t)m * groups * max_splits * 64;
-    p.mg_valid_lens = valid_lens; p.mg_split_len = split_len; p.mg_max_splits = max_splits;
-    return p;
-}
-
-int zl_w4a16_gemm_engine_merge(const void* ws, const int32_t* buf_lens, const int32_t* valid_lens, int split_len, int max_splits,
-                               const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                               const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups,
-                               int tiles, int epilogue, hipStream_t hs) {
-    if (!zl_w4_engine_covers(m, k, 1) || k > 4096 || max_splits < 1 || max_splits > 16 || split_len < 1) return ZL_ESHAPE;
-    if (epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32)) return ZL_ESHAPE;
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
-    if (tiles > cus) return ZL_ESHAPE;                     // one row tile per workgroup
-    const I8Params p = eng_merge_params(ws, buf_lens, valid_lens, split_len, max_splits, qw, meta, qw_bytes, meta_bytes, bias,
-                                        residual, y, m, n, k, groups, tiles, epilogue);
-    return launch_engine<1, false, false, false, true>(p, tiles, 0, hs);
+int zl_w4a16_gemm_engine_merge(const W4Problem& pb, const W4Merge& mg, hipStream_t hs) {
+    if (!zl_w4_engine_covers(pb.m, pb.k, 1) || pb.k > 4096 || mg.max_splits < 1 || mg.max_splits > 16 || mg.split_len < 1) return ZL_ESHAPE;
+    if (pb.epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32)) return ZL_ESHAPE;
+    if (pb.tiles > zl_cu_count()) return ZL_ESHAPE;        // one row tile per workgroup
+    I8Params p = i8_params(pb);
+    i8_fill_merge(p, mg);
+    return launch_engine<1, false, false, false, true>(p, pb.tiles, 0, hs);
 }
 
 // The fused launch.  Geometry: the first projection has ONE row tile per workgroup (tiles1 = grid <= CUs, every workgroup
 // resident at once: the hand-off is an all-to-all), the second R2 = tiles2 / grid tiles per workgroup.
-int zl_w4_engine_o_gateup_launch(const void* ws, const int32_t* buf_lens, const int32_t* valid_lens, int split_len, int max_splits,
-                                 const uint32_t* qw1, const uint32_t* meta1, uint32_t qw1_bytes, uint32_t meta1_bytes,
-                                 const uint16_t* bias1, uint16_t* hidden, int m, int n1, int k1, int groups1, int tiles1,
-                                 const uint32_t* qw2, const uint32_t* meta2, uint32_t qw2_bytes, uint32_t meta2_bytes,
-                                 const uint16_t* bias2, const uint16_t* norm_w, float norm_eps, uint16_t* act, int n2, int groups2,
-                                 int tiles2, int epilogue2, void* granules, const uint32_t* epoch_ptr, uint32_t epoch_add,
-                                 uint32_t* err, hipStream_t hs) {
-    int cus = zl_device_cu_count();
+int zl_w4_engine_o_gateup_launch(const W4Problem& pb1, const W4Merge& mg, const W4Problem& pb2, void* granules, const uint32_t* epoch_ptr,
+                                 uint32_t epoch_add, uint32_t* err, hipStream_t hs) {
+    const int m = pb1.m, n1 = pb1.n, k1 = pb1.k, groups1 = pb1.groups, tiles1 = pb1.tiles, groups2 = pb2.groups, tiles2 = pb2.tiles;
+    const int cus = zl_device_cu_count();
     if (cus <= 0) return ZL_ELIMIT;
-    if (!zl_w4_engine_covers(m, k1, 1) || k1 > 4096 || n1 > 4096 || n1 % 1024 != 0 || max_splits < 1 || max_splits > 16 || split_len < 1)
+    if (!zl_w4_engine_covers(m, k1, 1) || k1 > 4096 || n1 > 4096 || n1 % 1024 != 0 || mg.max_splits < 1 || mg.max_splits > 16 || mg.split_len < 1)
         return ZL_ESHAPE;
     if (tiles1 > cus || tiles2 % tiles1 != 0) return ZL_ESHAPE;
     const int r2 = tiles2 / tiles1;
-    if (r2 < 1 || r2 > 8 || !(epilogue2 & ZL_EPI_SILU_MUL)) return ZL_ESHAPE;
-    I8Params p1 = eng_merge_params(ws, buf_lens, valid_lens, split_len, max_splits, qw1, meta1, qw1_bytes, meta1_bytes, bias1,
-                                   hidden, hidden, m, n1, k1, groups1, tiles1, ZL_EPI_RESIDUAL | (bias1 ? ZL_EPI_BIAS : 0));
-    I8Params p2 = eng_params(nullptr, 0, qw2, meta2, qw2_bytes, meta2_bytes, bias2, nullptr, act, m, n2, n1, groups2, tiles2,
-                             epilogue2, n2 / 2, norm_w, norm_eps);
+    if (r2 < 1 || r2 > 8 || !(pb2.epilogue & ZL_EPI_SILU_MUL)) return ZL_ESHAPE;
+    I8Params p1 = i8_params(pb1);
+    i8_fill_merge(p1, mg);
+    const I8Params p2 = i8_params(pb2);
     const int gw = (groups1 > groups2 ? groups1 : groups2) / kCW;
     const EngGeom g = eng_geom(gw, m, r2, eng_round(r2), g_dbg_rounds_cap);
     if (g.NB < 2) return ZL_ELIMIT;

@@ -16,7 +16,9 @@
 // ring of non-temporal buffer loads (4 chunks ahead).  Per chunk and wave: 2 x 52 VALU ops of dequant feed
 // 2 x 4 x (BM/16) MFMAs (v_mfma_f32_16x16x32_f16) on 2 x BM/16 independent accumulators.
 #include "zl_common.h"
+#include "w4m_internal.h"
 #include "zl_w4m_dequant.h"
+#include "zl_w4m_epilogue.h"
 
 namespace {
 
@@ -48,7 +50,6 @@ struct TiledParams {
     int ld_ws;
 };
 
-__device__ __forceinline__ float silu_t(float x) { return x / (1.0f + expf(-x)); }
 
 template <int BM>
 __global__ __launch_bounds__(kThreadsT, 2) void k_w4a16_gemm_tiled(const TiledParams p) {
@@ -224,15 +225,7 @@ __global__ __launch_bounds__(kThreadsT, 2) void k_w4a16_gemm_tiled(const TiledPa
                     v += b;
                     const float other = __shfl_xor(v, 1, 64);
                     if ((nrow & 1) == 0 && row < p.m && n + 1 < p.n) {
-                        float gt = v, up = other, ov;
-                        if (p.epi & ZL_EPI_SILU_MUL) {
-                            gt = (float)zl_f32_to_f16(gt);
-                            up = (float)zl_f32_to_f16(up);
-                            ov = silu_t(gt) * up;
-                        } else {
-                            ov = (float)((double)gt / (1.0 + (double)expf(-gt))) * up;
-                        }
-                        p.y[(size_t)row * p.ld_out + n / 2] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(ov));
+                        p.y[(size_t)row * p.ld_out + n / 2] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(zl_w4m_finish_gated(v, other, p.epi)));
                     }
                 }
             }
@@ -410,8 +403,8 @@ __global__ __launch_bounds__(256, ZL_WIDE_OCC) void k_w4a16_gemm_wide(const Tile
     uint32_t bw[2][NT][4];
     auto dequant_half = [&](int set, int j, uint32_t w, int h) {
         const uint32_t ws = h ? (w >> 8) : w;
-        const hv2 lo = (__builtin_bit_cast(hv2, zl_w4m_and_or(ws, mask_lo, magic)) + z1[j]) * s2[j];
-        const hv2 hi = __builtin_elementwise_fma(__builtin_bit_cast(hv2, zl_w4m_and_or(ws, mask_hi, magic)), one16, z16[j]) * s2[j];
+        const hv2 lo = (__builtin_bit_cast(hv2, and_or(ws, mask_lo, magic)) + z1[j]) * s2[j];
+        const hv2 hi = __builtin_elementwise_fma(__builtin_bit_cast(hv2, and_or(ws, mask_hi, magic)), one16, z16[j]) * s2[j];
         bw[set][j][2 * h] = __builtin_bit_cast(uint32_t, lo);
         bw[set][j][2 * h + 1] = __builtin_bit_cast(uint32_t, hi);
     };
@@ -606,7 +599,7 @@ __global__ __launch_bounds__(256, ZL_WIDE_OCC) void k_w4a16_gemm_wide(const Tile
                     const int row = m0 + rb * 16 + 4 * kq + (odd ? 2 + h : h);
                     const float gt = (float)zl_f32_to_f16(gt32), up = (float)zl_f32_to_f16(up32);
                     if (row < p.m && (n | 1) < p.n)
-                        p.y[(size_t)row * p.ld_out + n / 2] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(silu_t(gt) * up));
+                        p.y[(size_t)row * p.ld_out + n / 2] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(silu_f32(gt) * up));
                 }
             }
     } else {
@@ -651,15 +644,7 @@ __global__ __launch_bounds__(256) void k_splitk_epilogue(const float* __restrict
                 gt += (float)__builtin_bit_cast(_Float16, bias[2 * c]);
                 up += (float)__builtin_bit_cast(_Float16, bias[2 * c + 1]);
             }
-            float ov;
-            if (epi & ZL_EPI_SILU_MUL) {
-                gt = (float)zl_f32_to_f16(gt);
-                up = (float)zl_f32_to_f16(up);
-                ov = silu_t(gt) * up;
-            } else {
-                ov = (float)((double)gt / (1.0 + (double)expf(-gt))) * up;
-            }
-            y[(size_t)row * ld_out + c] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(ov));
+            y[(size_t)row * ld_out + c] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(zl_w4m_finish_gated(gt, up, epi)));
         }
     }
 }
@@ -687,12 +672,8 @@ __global__ __launch_bounds__(256) void k_splitk_epilogue_v4(const float* __restr
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float b = ((epi & ZL_EPI_BIAS) && bias) ? (float)__builtin_bit_cast(_Float16, bb[i]) : 0.f;
-            float ov;
-            if (epi & ZL_EPI_ADD_C) ov = ((float)__builtin_bit_cast(_Float16, yy[i]) + v[i]) + b;
-            else ov = v[i] + b;
-            _Float16 y16 = zl_f32_to_f16(ov);
-            if (epi & ZL_EPI_RESIDUAL) y16 = zl_f32_to_f16((float)__builtin_bit_cast(_Float16, rr[i]) + (float)y16);
-            out[i] = __builtin_bit_cast(uint16_t, y16);
+            out[i] = __builtin_bit_cast(uint16_t, zl_w4m_finish(v[i], b, (float)__builtin_bit_cast(_Float16, yy[i]),
+                                                                (float)__builtin_bit_cast(_Float16, rr[i]), epi));
         }
         *reinterpret_cast<uint2*>(y + o) = *reinterpret_cast<uint2*>(out);
     }
@@ -725,8 +706,7 @@ extern "C" int zl_w4a16_gemm_tiled(const uint16_t* x, int64_t ldx, const uint32_
 extern "C" int zl_w4a16_gemm_tiled_ex(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta,
                                       const uint16_t* bias, const uint16_t* residual, uint16_t* y, int64_t m, int64_t n,
                                       int64_t k, int64_t group_size, int epilogue, const zl_w4_opts_t* opts, zl_stream_t s) {
-    static const zl_w4_opts_t kNoOpts = {};
-    const zl_w4_opts_t& o = opts ? *opts : kNoOpts;
+    const zl_w4_opts_t& o = zl_w4_opts_or_default(opts);
     ZL_CHECK_ARG(x && qw && meta && y && m > 0 && n > 0 && k > 0, ZL_EINVAL);
     ZL_CHECK_ARG(ldx >= k && ldx % 8 == 0 && ((uintptr_t)x & 15) == 0 && k % 128 == 0, ZL_ESHAPE);
     // the kernels address the activations with 32-bit byte offsets (buffer descriptors): refuse what would wrap
@@ -751,8 +731,7 @@ extern "C" int zl_w4a16_gemm_tiled_ex(const uint16_t* x, int64_t ldx, const uint
     p.ld_out = (int)(silu ? n / 2 : n);
     const int gx = (int)((L.np + kBN - 1) / kBN);
     hipStream_t hs = (hipStream_t)s;
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
+    const int cus = zl_cu_count();
     // prompt chunks: k_w4a16_gemm_wide<RB, NT> -- 128 / 256 rows x 256 / 192 columns per workgroup
     if (o.tiled_wide >= 0 && o.tiled_bm == 0 && (m >= 128 || (o.tiled_wide > 0 && m > 32)) && L.np >= 192) {
         // tile shape and K splits by a small cost model.  Cycles per 128-k chunk and workgroup ~ 64 RB NT (MFMA) + 281 NT

@@ -23,6 +23,7 @@
 #include "zl_common.h"
 #include "zl_stage.h"
 #include "zl_w4_exact.h"
+#include "zl_w4m_epilogue.h"
 
 // Workgroup = 8 wavefronts (512 threads): the activation row(s) are staged ONCE per workgroup, and one
 // or two workgroups fill a CU, so the L1/TA traffic and the barrier latency of the x staging are paid
@@ -67,8 +68,6 @@ struct W4Params {
 };
 
 using namespace zlx;
-
-__device__ __forceinline__ float silu_f32(float x) { return x / (1.0f + expf(-x)); }
 
 // kRing = weight loads in flight per wave (1 KiB each).
 // XL    = activation loads (16 B) per thread per row held in registers across the weight prologue:
@@ -292,15 +291,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_w4a16_gemm(const W4Params p) {
                     g += (float)__builtin_bit_cast(_Float16, p.bias[2 * pr]);
                     u += (float)__builtin_bit_cast(_Float16, p.bias[2 * pr + 1]);
                 }
-                float o;
-                if (p.epi & ZL_EPI_SILU_MUL) {
-                    g = (float)zl_f32_to_f16(g);  // the two fp16 linear outputs
-                    u = (float)zl_f32_to_f16(u);
-                    o = silu_f32(g) * u;
-                } else {
-                    o = (float)((double)g / (1.0 + (double)expf(-g))) * u;
-                }
-                p.y[orow + pr] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(o));
+                p.y[orow + pr] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(zl_w4m_finish_gated(g, u, p.epi)));
             } else {
                 const int row = 2 * pair0 + lane;
                 if (row >= p.n) continue;
@@ -371,8 +362,7 @@ extern "C" int zl_w4a16_gemm(const uint16_t* x, int64_t ldx, const uint32_t* qw,
 
     // grid: 16 wavefronts per CU (two 8-wave workgroups; ~100 VGPRs -> 4 waves per SIMD), each wave owns
     // a contiguous run of row pairs; small matrices get one workgroup per CU.
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
+    const int cus = zl_cu_count();
     int wgs_per_cu = (p.pairs_total + cus * kWaves - 1) / (cus * kWaves) >= 2 ? 2 : 1;
     int best_ppw = (p.pairs_total + cus * wgs_per_cu * kWaves - 1) / (cus * wgs_per_cu * kWaves);
     if (best_ppw < 1) best_ppw = 1;

@@ -200,23 +200,9 @@ __global__ __launch_bounds__(kT, 2) void k_w4a16_i8p(const I8Params p) {
     }
     // ROPE: what the epilogue of this thread needs from memory (rotation table entries, the task's slot and buffer
     // pointers) is requested now, next to the activations -- in the epilogue these were three dependent round trips
-    float rp_c0 = 0.f, rp_s0 = 0.f, rp_c1 = 0.f, rp_s1 = 0.f;
-    int rp_place = -1, rp_blen = 0;
-    uint16_t* rp_kv = nullptr;
+    ZlRopeOperands rp;
     if constexpr (ROPE) {
-        if ((int)threadIdx.x < 16 * M) {
-            const int m = threadIdx.x >> 4, n0 = tile0 * 16 + (threadIdx.x & 15);
-            const int head = n0 / p.d, dcol = n0 % p.d, half = p.d / 2;
-            if (head < p.h + p.hkv) {
-                rp_c0 = p.cosv[(size_t)m * p.d + dcol]; rp_s0 = p.sinv[(size_t)m * p.d + dcol];
-                rp_c1 = p.cosv[(size_t)m * p.d + dcol + half]; rp_s1 = p.sinv[(size_t)m * p.d + dcol + half];
-            }
-            if (head >= p.h) {
-                rp_place = p.placement[m];
-                rp_blen = p.buf_lens[m];
-                rp_kv = head < p.h + p.hkv ? p.k_bufs[m] : p.v_bufs[m];
-            }
-        }
+        if ((int)threadIdx.x < 16 * M) rp = zl_rope_prefetch(p, threadIdx.x >> 4, tile0 * 16 + (threadIdx.x & 15));
     }
     // the other epilogues: every thread owns at most one output (R * 16 * M <= 512); its bias / residual / previous-output
     // operands are requested now as well (one more round trip at the very end of the kernel otherwise)
@@ -466,62 +452,20 @@ __global__ __launch_bounds__(kT, 2) void k_w4a16_i8p(const I8Params p) {
         return v;
     };
     if constexpr (ROPE) {
-        const int half = p.d / 2;
         if ((int)threadIdx.x < 16 * M) {                 // 16 M <= 64 threads; their table entries / pointers came with the prologue
             const int m = threadIdx.x >> 4, n_local = threadIdx.x & 15;
-            float v0 = total_of(0, n_local, m), v1 = total_of(1, n_local, m);
-            const int n0 = tile0 * 16 + n_local, n1 = n0 + half;       // columns of the fused qkv row
-            if ((p.epi & ZL_EPI_BIAS) && p.bias) {
-                v0 += (float)__builtin_bit_cast(_Float16, p.bias[n0]);
-                v1 += (float)__builtin_bit_cast(_Float16, p.bias[n1]);
-            }
-            const float a = (float)zl_f32_to_f16(v0), bb = (float)zl_f32_to_f16(v1);   // the projection's fp16 outputs
-            const int head = n0 / p.d, dcol = n0 % p.d;                 // dcol < half
-            if (head < p.h + p.hkv) {
-                const uint16_t r0 = __builtin_bit_cast(uint16_t, zl_f32_to_f16(__builtin_fmaf(-bb, rp_s0, a * rp_c0)));
-                const uint16_t r1 = __builtin_bit_cast(uint16_t, zl_f32_to_f16(__builtin_fmaf(a, rp_s1, bb * rp_c1)));
-                if (head < p.h) {
-                    uint16_t* dst = p.q_out + ((size_t)m * p.h + head) * p.d + dcol;
-                    dst[0] = r0;
-                    dst[half] = r1;
-                } else if (rp_place >= 0 && rp_place < rp_blen) {
-                    const int hk = head - p.h;
-                    const size_t row = p.bshd ? (size_t)rp_place * p.hkv + hk : (size_t)hk * rp_blen + rp_place;
-                    uint16_t* dst = rp_kv + row * p.d + dcol;
-                    dst[0] = r0;
-                    dst[half] = r1;
-                }
-            } else if (rp_place >= 0 && rp_place < rp_blen) {
-                const int hk = head - p.h - p.hkv;
-                const size_t row = p.bshd ? (size_t)rp_place * p.hkv + hk : (size_t)hk * rp_blen + rp_place;
-                uint16_t* dst = rp_kv + row * p.d + dcol;
-                dst[0] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(v0));
-                dst[half] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(v1));
-            }
+            zl_rope_store_f16(p, rp, m, tile0 * 16 + n_local, total_of(0, n_local, m), total_of(1, n_local, m));
         }
         ZL_IPROBE(7);
         return;
     }
     if (ep_col >= 0) {
         if (!silu) {
-            const float v = total_of(ep_r, ep_nl, ep_m);
-            float ov;
-            if (p.epi & ZL_EPI_ADD_C) ov = (ep_prev + v) + ep_b0;
-            else ov = v + ep_b0;
-            _Float16 y16 = zl_f32_to_f16(ov);
-            if (p.epi & ZL_EPI_RESIDUAL) y16 = zl_f32_to_f16(ep_res + (float)y16);
+            const _Float16 y16 = zl_w4m_finish(total_of(ep_r, ep_nl, ep_m), ep_b0, ep_prev, ep_res, p.epi);
             p.y[(size_t)ep_m * p.ld_out + ep_col] = __builtin_bit_cast(uint16_t, y16);
         } else {
-            float g = total_of(ep_r, 2 * ep_nl, ep_m) + ep_b0, u = total_of(ep_r, 2 * ep_nl + 1, ep_m) + ep_b1;
-            float ov;
-            if (p.epi & ZL_EPI_SILU_MUL) {
-                g = (float)zl_f32_to_f16(g);
-                u = (float)zl_f32_to_f16(u);
-                ov = silu_f32(g) * u;
-            } else {
-                ov = (float)((double)g / (1.0 + (double)expf(-g))) * u;
-            }
-            p.y[(size_t)ep_m * p.ld_out + ep_col] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(ov));
+            const float g = total_of(ep_r, 2 * ep_nl, ep_m) + ep_b0, u = total_of(ep_r, 2 * ep_nl + 1, ep_m) + ep_b1;
+            p.y[(size_t)ep_m * p.ld_out + ep_col] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(zl_w4m_finish_gated(g, u, p.epi)));
         }
     }
     ZL_IPROBE(7);
@@ -564,24 +508,14 @@ bool zl_w4a16_i8p_covers(int64_t m, int64_t k) {
 }
 
 // internal (called by zl_w4a16_gemm_mfma_ex): zl_w4a16_i8p_covers(m, k)
-int zl_w4a16_gemm_i8p(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                      uint32_t meta_bytes, const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k,
-                      int groups, int tiles, int epilogue, int ld_out, const uint16_t* norm_w, float norm_eps, int rounds_override,
-                      hipStream_t hs) {
-    if (!zl_w4a16_i8p_covers(m, k)) return ZL_ESHAPE;
-    I8Params p;
-    p.x = x; p.ldx = ldx; p.qw = reinterpret_cast<const uint4*>(qw); p.meta = meta; p.qw_bytes = qw_bytes; p.meta_bytes = meta_bytes;
-    p.bias = bias; p.residual = residual; p.y = y; p.m = m; p.n = n; p.k = k; p.groups = groups; p.tiles = tiles; p.epi = epilogue;
-    p.ld_out = ld_out; p.norm_w = norm_w; p.norm_eps = norm_eps;
-    p.cosv = p.sinv = nullptr; p.placement = p.buf_lens = nullptr; p.k_bufs = p.v_bufs = nullptr; p.q_out = nullptr;
-    p.h = p.hkv = p.d = p.bshd = 0; p.pair_stride = 1;
-    p.mg_part = nullptr; p.mg_stat = nullptr; p.mg_valid_lens = nullptr; p.mg_split_len = p.mg_max_splits = 0;
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
-    int r = (tiles + cus - 1) / cus;
+int zl_w4a16_gemm_i8p(const W4Problem& pb, int rounds_override, hipStream_t hs) {
+    if (!zl_w4a16_i8p_covers(pb.m, pb.k)) return ZL_ESHAPE;
+    const I8Params p = i8_params(pb);
+    const int cus = zl_cu_count();
+    int r = (pb.tiles + cus - 1) / cus;
     if (r > 8) r = 8;
     if (rounds_override > 0 && rounds_override <= 8) r = rounds_override;
-    const int grid = (tiles + r - 1) / r;
+    const int grid = (pb.tiles + r - 1) / r;
 #define ZL_I8(RR) case RR: return launch_i8p<RR, false>(p, grid, hs);
     switch (r) { ZL_I8(1) ZL_I8(2) ZL_I8(3) ZL_I8(4) ZL_I8(5) ZL_I8(6) ZL_I8(7) ZL_I8(8) }
 #undef ZL_I8
@@ -589,45 +523,24 @@ int zl_w4a16_gemm_i8p(const uint16_t* x, int64_t ldx, const uint32_t* qw, const 
 }
 
 // internal (called by zl_w4a16_qkv_rope_scatter): the fused qkv projection with the neox rotation and the KV scatter
-int zl_w4a16_gemm_i8p_rope(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                           uint32_t meta_bytes, const uint16_t* bias, int m, int n, int k, int groups, int tiles,
-                           const uint16_t* norm_w, float norm_eps, const float* cosv, const float* sinv,
-                           const int32_t* placement, const int32_t* buf_lens, uint16_t* const* k_bufs,
-                           uint16_t* const* v_bufs, uint16_t* q_out, int h, int hkv, int d, int bshd, hipStream_t hs) {
-    if (!zl_w4a16_i8p_covers(m, k) || d % 32 != 0 || n != (h + 2 * hkv) * d || tiles * 16 != n) return ZL_ESHAPE;
-    I8Params p;
-    p.x = x; p.ldx = ldx; p.qw = reinterpret_cast<const uint4*>(qw); p.meta = meta; p.qw_bytes = qw_bytes; p.meta_bytes = meta_bytes;
-    p.bias = bias; p.residual = nullptr; p.y = nullptr; p.m = m; p.n = n; p.k = k; p.groups = groups; p.tiles = tiles;
-    p.epi = bias ? ZL_EPI_BIAS : 0; p.ld_out = n; p.norm_w = norm_w; p.norm_eps = norm_eps;
-    p.cosv = cosv; p.sinv = sinv; p.placement = placement; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs;
-    p.q_out = q_out; p.h = h; p.hkv = hkv; p.d = d; p.bshd = bshd; p.pair_stride = d / 32;
-    p.mg_part = nullptr; p.mg_stat = nullptr; p.mg_valid_lens = nullptr; p.mg_split_len = p.mg_max_splits = 0;
-    const int grid = tiles / 2;
-    return launch_i8p<2, true>(p, grid, hs);
+int zl_w4a16_gemm_i8p_rope(const W4Problem& pb, const W4Rope& rp, hipStream_t hs) {
+    if (!zl_w4a16_i8p_covers(pb.m, pb.k) || !zl_w4m_rope_shape_ok(pb, rp)) return ZL_ESHAPE;
+    I8Params p = i8_params(pb);
+    i8_fill_rope(p, rp);
+    return launch_i8p<2, true>(p, pb.tiles / 2, hs);
 }
 
 // internal (called by zl_w4a16_gemm_attn_merge_h): the attention output projection of a decode step reading the half-precision
 // split partials of zl_decode_attn_splits_h.  m <= 4, k = heads * 128 <= 4096, max_splits <= 16.
-int zl_w4a16_gemm_i8p_merge(const void* ws, const int32_t* buf_lens, const int32_t* valid_lens, int split_len, int max_splits,
-                            const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                            const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups,
-                            int tiles, int epilogue, hipStream_t hs) {
-    if (m < 1 || m > 4 || k > 4096 || k % 128 != 0 || max_splits < 1 || max_splits > 16 || split_len < 1) return ZL_ESHAPE;
-    if (epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32)) return ZL_ESHAPE;
-    I8Params p;
-    p.x = nullptr; p.ldx = 0; p.qw = reinterpret_cast<const uint4*>(qw); p.meta = meta; p.qw_bytes = qw_bytes; p.meta_bytes = meta_bytes;
-    p.bias = bias; p.residual = residual; p.y = y; p.m = m; p.n = n; p.k = k; p.groups = groups; p.tiles = tiles; p.epi = epilogue;
-    p.ld_out = n; p.norm_w = nullptr; p.norm_eps = 0.f;
-    p.cosv = p.sinv = nullptr; p.placement = nullptr; p.buf_lens = buf_lens; p.k_bufs = p.v_bufs = nullptr; p.q_out = nullptr;
-    p.h = p.hkv = p.d = p.bshd = 0; p.pair_stride = 1;
-    p.mg_part = reinterpret_cast<const uint16_t*>(ws);
-    p.mg_stat = reinterpret_cast<const float*>(ws) + (size_t)m * groups * max_splits * 64;   // behind the fp16 rows (128 halfs each)
-    p.mg_valid_lens = valid_lens; p.mg_split_len = split_len; p.mg_max_splits = max_splits;
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
-    int r = (tiles + cus - 1) / cus;
+int zl_w4a16_gemm_i8p_merge(const W4Problem& pb, const W4Merge& mg, hipStream_t hs) {
+    if (pb.m < 1 || pb.m > 4 || pb.k > 4096 || pb.k % 128 != 0 || mg.max_splits < 1 || mg.max_splits > 16 || mg.split_len < 1) return ZL_ESHAPE;
+    if (pb.epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32)) return ZL_ESHAPE;
+    I8Params p = i8_params(pb);
+    i8_fill_merge(p, mg);
+    const int cus = zl_cu_count();
+    int r = (pb.tiles + cus - 1) / cus;
     if (r > 8) r = 8;
-    const int grid = (tiles + r - 1) / r;
+    const int grid = (pb.tiles + r - 1) / r;
 #define ZL_I8M(RR) case RR: return launch_i8p_n<RR, false, false, false, true>(p, grid, hs);
     switch (r) { ZL_I8M(1) ZL_I8M(2) ZL_I8M(3) ZL_I8M(4) ZL_I8M(5) ZL_I8M(6) ZL_I8M(7) ZL_I8M(8) }
 #undef ZL_I8M

@@ -38,6 +38,9 @@
 #include <stdlib.h>
 #include "zl_common.h"
 #include "zl_stage.h"
+#include "w4m_internal.h"
+#include "zl_w4m_dequant.h"
+#include "zl_w4m_epilogue.h"
 
 namespace {
 
@@ -46,9 +49,7 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kRing = 8;
 constexpr int kMaxRounds = 8;
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-typedef _Float16 hv2 __attribute__((ext_vector_type(2)));
 
 // ---- optional phase-timestamp probe (build with -DZL_W4M_PROBE; tools/ubench/probe_mfma.py) -----------
 #ifdef ZL_W4M_PROBE
@@ -81,28 +82,6 @@ struct MfmaParams {
     int epi, ld_out;
     int lds_stride;          // kp + 8 halfs
 };
-
-__device__ __forceinline__ uint32_t and_or(uint32_t w, uint32_t mask_s, uint32_t magic_v) {
-    uint32_t r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(w), "s"(mask_s), "v"(magic_v));
-    return r;
-}
-
-// word -> 8 fp16 (q - z), exact; natural k order (w0..w7) = MFMA A-fragment element order
-__device__ __forceinline__ h8 dequant_word(uint32_t w, hv2 z1, hv2 z16, uint32_t mask_lo, uint32_t mask_hi,
-                                           uint32_t magic) {
-    const hv2 one16 = {(_Float16)0.0625f, (_Float16)0.0625f};
-    const hv2 d0 = __builtin_bit_cast(hv2, and_or(w, mask_lo, magic)) + z1;
-    const hv2 d1 = __builtin_elementwise_fma(__builtin_bit_cast(hv2, and_or(w, mask_hi, magic)), one16, z16);
-    const uint32_t wb = w >> 8;
-    const hv2 d2 = __builtin_bit_cast(hv2, and_or(wb, mask_lo, magic)) + z1;
-    const hv2 d3 = __builtin_elementwise_fma(__builtin_bit_cast(hv2, and_or(wb, mask_hi, magic)), one16, z16);
-    h8 a;
-    a[0] = d0.x; a[1] = d0.y; a[2] = d1.x; a[3] = d1.y; a[4] = d2.x; a[5] = d2.y; a[6] = d3.x; a[7] = d3.y;
-    return a;
-}
-
-__device__ __forceinline__ float silu_f32(float x) { return x / (1.0f + expf(-x)); }
 
 // Streaming structure = the dense GEMV's (which reaches 6.5 TB/s): every wave runs an 8-deep ring of
 // 1 KiB non-temporal loads over its own (row tile, k-slice) items with NO barrier inside the stream;
@@ -503,15 +482,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_w4a16_mfma(const MfmaParams p) 
                     g += (float)__builtin_bit_cast(_Float16, p.bias[2 * pr]);
                     u += (float)__builtin_bit_cast(_Float16, p.bias[2 * pr + 1]);
                 }
-                float ov;
-                if (p.epi & ZL_EPI_SILU_MUL) {
-                    g = (float)zl_f32_to_f16(g);
-                    u = (float)zl_f32_to_f16(u);
-                    ov = silu_f32(g) * u;
-                } else {
-                    ov = (float)((double)g / (1.0 + (double)expf(-g))) * u;
-                }
-                p.y[(size_t)m * p.ld_out + pr] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(ov));
+                p.y[(size_t)m * p.ld_out + pr] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(zl_w4m_finish_gated(g, u, p.epi)));
             }
         }
     }
@@ -590,84 +561,6 @@ inline int grid_for(int64_t n) {
 
 }  // namespace
 
-// w4_phase.hip: the phase-pipelined streaming kernel for 5..32 rows
-int zl_w4a16_gemm_phase(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                        uint32_t meta_bytes, const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n,
-                        int k, int groups, int tiles, int epilogue, int ld_out, const uint16_t* norm_w, float norm_eps,
-                        const zl_w4_opts_t* opts, hipStream_t hs);
-
-// w4_slab.hip: 9..32 rows on 128-column x K-slice tiles (round 6); ZL_ESHAPE = not this shape / no scratch for the K split
-int zl_w4a16_gemm_slab(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                       const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups, int tiles,
-                       int epilogue, int ld_out, const uint16_t* norm_w, float norm_eps, const zl_w4_opts_t* opts, hipStream_t hs);
-int zl_w4a16_gemm_slab_rope(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                            uint32_t meta_bytes, const uint16_t* bias, int m, int n, int k, int groups, int tiles, const float* cosv,
-                            const float* sinv, const int32_t* placement, const int32_t* buf_lens, uint16_t* const* k_bufs,
-                            uint16_t* const* v_bufs, uint16_t* q_out, int h, int hkv, int d, int bshd, const uint16_t* norm_w,
-                            float norm_eps, const zl_w4_opts_t* opts, hipStream_t hs);
-
-bool zl_w4a16_i8p_covers(int64_t m, int64_t k);
-int zl_w4a16_gemm_i8p(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                      uint32_t meta_bytes, const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k,
-                      int groups, int tiles, int epilogue, int ld_out, const uint16_t* norm_w, float norm_eps, int rounds_override,
-                      hipStream_t hs);
-int zl_w4a16_gemm_i8p_rope(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                           uint32_t meta_bytes, const uint16_t* bias, int m, int n, int k, int groups, int tiles,
-                           const uint16_t* norm_w, float norm_eps, const float* cosv, const float* sinv,
-                           const int32_t* placement, const int32_t* buf_lens, uint16_t* const* k_bufs,
-                           uint16_t* const* v_bufs, uint16_t* q_out, int h, int hkv, int d, int bshd, hipStream_t hs);
-int zl_w4a16_gemm_i8p_merge(const void* ws, const int32_t* buf_lens, const int32_t* valid_lens, int split_len, int max_splits,
-                            const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                            const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups,
-                            int tiles, int epilogue, hipStream_t hs);
-#ifdef ZL_EXPERIMENTAL
-// the loader / consumer engine (w4_engine.hip; experimental build only)
-bool zl_w4_engine_covers(int64_t m, int64_t k, int r);
-int zl_w4a16_gemm_engine(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                         uint32_t meta_bytes, const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k,
-                         int groups, int tiles, int epilogue, int ld_out, const uint16_t* norm_w, float norm_eps, int slots_cap,
-                         hipStream_t hs);
-int zl_w4a16_gemm_engine_rope(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                              uint32_t meta_bytes, const uint16_t* bias, int m, int n, int k, int groups, int tiles,
-                              const uint16_t* norm_w, float norm_eps, const float* cosv, const float* sinv,
-                              const int32_t* placement, const int32_t* buf_lens, uint16_t* const* k_bufs,
-                              uint16_t* const* v_bufs, uint16_t* q_out, int h, int hkv, int d, int bshd, hipStream_t hs);
-int zl_w4a16_gemm_engine_merge(const void* ws, const int32_t* buf_lens, const int32_t* valid_lens, int split_len, int max_splits,
-                               const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                               const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups,
-                               int tiles, int epilogue, hipStream_t hs);
-int zl_w4_engine_o_gateup_launch(const void* ws, const int32_t* buf_lens, const int32_t* valid_lens, int split_len, int max_splits,
-                                 const uint32_t* qw1, const uint32_t* meta1, uint32_t qw1_bytes, uint32_t meta1_bytes,
-                                 const uint16_t* bias1, uint16_t* hidden, int m, int n1, int k1, int groups1, int tiles1,
-                                 const uint32_t* qw2, const uint32_t* meta2, uint32_t qw2_bytes, uint32_t meta2_bytes,
-                                 const uint16_t* bias2, const uint16_t* norm_w, float norm_eps, uint16_t* act, int n2, int groups2,
-                                 int tiles2, int epilogue2, void* granules, const uint32_t* epoch_ptr, uint32_t epoch_add,
-                                 uint32_t* err, hipStream_t hs);
-int zl_engine_epoch_advance_launch(uint32_t* epoch, uint32_t by, hipStream_t hs);
-#endif
-int zl_w4a16_gemm_phase_merge(const float* ws, const int32_t* buf_lens, const int32_t* valid_lens, int split_len,
-                              int max_splits, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                              uint32_t meta_bytes, const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n,
-                              int k, int groups, int tiles, int epilogue, hipStream_t hs);
-
-int zl_w4a16_gemm_phase_rope(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                             uint32_t meta_bytes, const uint16_t* bias, int m, int n, int k, int groups, int tiles,
-                             const uint16_t* norm_w, float norm_eps, const float* cosv, const float* sinv,
-                             const int32_t* placement, const int32_t* buf_lens, uint16_t* const* k_bufs,
-                             uint16_t* const* v_bufs, uint16_t* q_out, int h, int hkv, int d, int bshd, hipStream_t hs);
-
-#ifdef ZL_EXPERIMENTAL
-int64_t zl_w4_planes_bytes_(int64_t m, int64_t k);
-int zl_w4_planes_launch(const uint16_t* x, int64_t ldx, int m, int k, const uint16_t* norm_w, float norm_eps, void* planes, hipStream_t hs);
-int zl_w4a16_gemm_phase_planes(const void* planes, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                               const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups, int tiles,
-                               int epilogue, int ld_out, const zl_w4_opts_t* opts, hipStream_t hs);
-int zl_w4a16_gemm_phase_planes_rope(const void* planes, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                                    const uint16_t* bias, int m, int n, int k, int groups, int tiles, const float* cosv, const float* sinv,
-                                    const int32_t* placement, const int32_t* buf_lens, uint16_t* const* k_bufs, uint16_t* const* v_bufs,
-                                    uint16_t* q_out, int h, int hkv, int d, int bshd, hipStream_t hs);
-#endif
-
 extern "C" {
 
 #ifdef ZL_W4M_PROBE
@@ -737,8 +630,7 @@ int zl_w4a16_gemm_mfma(const uint16_t* x, int64_t ldx, const uint32_t* qw, const
 int zl_w4a16_gemm_mfma_ex(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, const uint16_t* bias,
                           const uint16_t* residual, uint16_t* y, int64_t m, int64_t n, int64_t k, int64_t group_size,
                           const uint16_t* norm_weight, float norm_eps, int epilogue, const zl_w4_opts_t* opts, zl_stream_t s) {
-    static const zl_w4_opts_t kNoOpts = {};
-    const zl_w4_opts_t& o = opts ? *opts : kNoOpts;
+    const zl_w4_opts_t& o = zl_w4_opts_or_default(opts);
     ZL_CHECK_ARG(x && qw && meta && y && m > 0 && n > 0 && k > 0, ZL_EINVAL);
     ZL_CHECK_ARG(ldx >= k && ldx % 8 == 0 && ((uintptr_t)x & 15) == 0, ZL_ESHAPE);
     ZL_CHECK_ARG(!(epilogue & ZL_EPI_RESIDUAL) || residual, ZL_EINVAL);
@@ -748,6 +640,8 @@ int zl_w4a16_gemm_mfma_ex(const uint16_t* x, int64_t ldx, const uint32_t* qw, co
     const bool silu = epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32);
     ZL_CHECK_ARG(!silu || n % 2 == 0, ZL_ESHAPE);
     hipStream_t hs = (hipStream_t)s;
+    // what the streaming launchers take; its 32-bit byte counts hold where the routes below ask for less than 4 GiB of weights
+    const W4Problem pb = zl_w4m_problem(L, x, ldx, qw, meta, bias, residual, y, m, epilogue, norm_weight, norm_eps);
     // more than one 16-row pass: the M-tiled kernel (w4_gemm_tiled.hip; no fused norm prologue) reads the
     // weights once per 32-128 rows; with few rows it splits K over workgroups to fill the chip
     // (M = 32: 82 vs 113 us per Llama-3-8B layer for two passes of this kernel; M = 64: 109 vs 224)
@@ -758,23 +652,18 @@ int zl_w4a16_gemm_mfma_ex(const uint16_t* x, int64_t ldx, const uint32_t* qw, co
     // small_algo == 2: the same arithmetic on the loader / consumer engine (w4_engine.hip) where it applies
 #ifdef ZL_EXPERIMENTAL
     if (o.small_algo == 2 && L.qw_bytes < ((int64_t)1 << 32)) {
-        st = zl_w4a16_gemm_engine(x, ldx, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, residual, y, (int)m, (int)n,
-                                  (int)k, (int)L.q, (int)(L.np / 16), epilogue, (int)(silu ? n / 2 : n), norm_weight, norm_eps,
-                                  o.phase_rounds, hs);
+        st = zl_w4a16_gemm_engine(pb, o.phase_rounds, hs);
         if (st != ZL_ESHAPE && st != ZL_ELIMIT) return st;
     }
 #endif
     if ((o.small_algo == 0 || o.small_algo == 2) && zl_w4a16_i8p_covers(m, k) && L.qw_bytes < ((int64_t)1 << 32))
-        return zl_w4a16_gemm_i8p(x, ldx, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, residual, y, (int)m, (int)n,
-                                 (int)k, (int)L.q, (int)(L.np / 16), epilogue, (int)(silu ? n / 2 : n), norm_weight, norm_eps,
-                                 o.phase_rounds, hs);
+        return zl_w4a16_gemm_i8p(pb, o.phase_rounds, hs);
     // 9..32 rows without a fused norm (round 6): 128-column x K-slice tiles, activation fragments straight from global memory
     // (w4_slab.hip) -- a workgroup's activation bytes ~ its weight bytes instead of M x K per 16 R columns
     // ... and WITH a norm when the caller hands over the rows' statistics (zl_w4_opts_t::row_ss): the slab kernel's NORM instantiations
     if (o.slab >= 0 && (!norm_weight || o.row_ss) && m >= (o.slab_min_m > 0 ? o.slab_min_m : (o.small_algo == 1 ? 5 : 3)) && m <= 32 && k % 128 == 0 &&
         L.qw_bytes < ((int64_t)1 << 32)) {
-        st = zl_w4a16_gemm_slab(x, ldx, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, residual, y, (int)m, (int)n,
-                                (int)k, (int)L.q, (int)(L.np / 16), epilogue, (int)(silu ? n / 2 : n), norm_weight, norm_eps, &o, hs);
+        st = zl_w4a16_gemm_slab(pb, &o, hs);
         if (st != ZL_ESHAPE) return st;
     }
     {
@@ -790,16 +679,13 @@ int zl_w4a16_gemm_mfma_ex(const uint16_t* x, int64_t ldx, const uint32_t* qw, co
         ZL_CHECK_ARG(!(norm_weight && m >= 9 && m <= 32) || o.defer_norm == 1, ZL_ESHAPE);
         const bool rows_9_32_dn = norm_weight && m >= 9 && m <= 32 && k % 128 == 0 && k <= (m <= 16 ? (1 << 30) : 8192);
         if ((rows_5_32 || rows_1_4 || rows_9_32_dn) && L.qw_bytes < ((int64_t)1 << 32))
-            return zl_w4a16_gemm_phase(x, ldx, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, residual, y,
-                                       (int)m, (int)n, (int)k, (int)L.q, (int)(L.np / 16), epilogue, (int)(silu ? n / 2 : n),
-                                       norm_weight, norm_eps, &o, hs);
+            return zl_w4a16_gemm_phase(pb, &o, hs);
     }
     const int tiled_min_m = o.tiled_min_m > 0 ? o.tiled_min_m : 17;
     if (m >= tiled_min_m && !norm_weight && k % 128 == 0)
         return zl_w4a16_gemm_tiled_ex(x, ldx, qw, meta, bias, residual, y, m, n, k, group_size, epilogue, &o, s);
 
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
+    const int cus = zl_cu_count();
     const int64_t ld_out = silu ? n / 2 : n;
     for (int64_t m0 = 0; m0 < m; m0 += 16) {  // <= 16 activation rows per pass (the reference chunks by 16 too)
         const int mm = (int)(m - m0 < 16 ? m - m0 : 16);
@@ -908,29 +794,23 @@ int zl_w4a16_qkv_rope_scatter_ex(const uint16_t* x, int64_t ldx, const uint32_t*
     ZL_CHECK_ARG(m <= 16 || k <= 8192, ZL_ESHAPE);
     ZL_CHECK_ARG(L.qw_bytes < ((int64_t)1 << 32), ZL_ELIMIT);
     const int small_algo = opts ? opts->small_algo : 0;
+    const W4Problem pb = zl_w4m_problem(L, x, ldx, qw, meta, bias, nullptr, nullptr, m, bias ? ZL_EPI_BIAS : 0, norm_weight, norm_eps);
+    const W4Rope rp = {cosv, sinv, placement, buf_lens, k_bufs, v_bufs, q_out, (int)h, (int)hkv, (int)d, bshd};
     if (opts && opts->slab >= 0 && (!norm_weight || opts->row_ss) && m >= (opts->slab_min_m > 0 ? opts->slab_min_m : 5) && k % 128 == 0) {
-        st = zl_w4a16_gemm_slab_rope(x, ldx, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, (int)m, (int)n, (int)k,
-                                     (int)L.q, (int)(L.np / 16), cosv, sinv, placement, buf_lens, k_bufs, v_bufs, q_out, (int)h,
-                                     (int)hkv, (int)d, bshd, norm_weight, norm_eps, opts, (hipStream_t)s);
+        st = zl_w4a16_gemm_slab_rope(pb, rp, opts, (hipStream_t)s);
         if (st != ZL_ESHAPE) return st;
     }
     ZL_CHECK_ARG(!norm_weight || k <= 4096 || m > 8, ZL_ESHAPE);     // <= 8 rows: register-resident staging; 9..32: deferred norm
     ZL_CHECK_ARG(!(norm_weight && m >= 9) || (opts && opts->defer_norm == 1), ZL_ESHAPE);   // the deferred norm: on request only
 #ifdef ZL_EXPERIMENTAL
     if (small_algo == 2) {
-        st = zl_w4a16_gemm_engine_rope(x, ldx, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, (int)m, (int)n, (int)k,
-                                       (int)L.q, (int)(L.np / 16), norm_weight, norm_eps, cosv, sinv, placement, buf_lens, k_bufs,
-                                       v_bufs, q_out, (int)h, (int)hkv, (int)d, bshd, (hipStream_t)s);
+        st = zl_w4a16_gemm_engine_rope(pb, rp, (hipStream_t)s);
         if (st != ZL_ESHAPE && st != ZL_ELIMIT) return st;
     }
 #endif
     if ((small_algo == 0 || small_algo == 2) && zl_w4a16_i8p_covers(m, k))
-        return zl_w4a16_gemm_i8p_rope(x, ldx, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, (int)m, (int)n,
-                                      (int)k, (int)L.q, (int)(L.np / 16), norm_weight, norm_eps, cosv, sinv, placement,
-                                      buf_lens, k_bufs, v_bufs, q_out, (int)h, (int)hkv, (int)d, bshd, (hipStream_t)s);
-    return zl_w4a16_gemm_phase_rope(x, ldx, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, (int)m, (int)n,
-                                    (int)k, (int)L.q, (int)(L.np / 16), norm_weight, norm_eps, cosv, sinv, placement,
-                                    buf_lens, k_bufs, v_bufs, q_out, (int)h, (int)hkv, (int)d, bshd, (hipStream_t)s);
+        return zl_w4a16_gemm_i8p_rope(pb, rp, (hipStream_t)s);
+    return zl_w4a16_gemm_phase_rope(pb, rp, (hipStream_t)s);
 }
 
 #ifdef ZL_EXPERIMENTAL
@@ -956,8 +836,8 @@ int zl_w4a16_gemm_planes(const void* planes, const uint32_t* qw, const uint32_t*
     const bool silu = epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32);
     ZL_CHECK_ARG(!silu || n % 2 == 0, ZL_ESHAPE);
     ZL_CHECK_ARG(L.qw_bytes < ((int64_t)1 << 32), ZL_ELIMIT);
-    return zl_w4a16_gemm_phase_planes(planes, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, residual, y, (int)m, (int)n,
-                                      (int)k, (int)L.q, (int)(L.np / 16), epilogue, (int)(silu ? n / 2 : n), opts, (hipStream_t)s);
+    return zl_w4a16_gemm_phase_planes(planes, zl_w4m_problem(L, nullptr, 0, qw, meta, bias, residual, y, m, epilogue, nullptr, 0.f), opts,
+                                      (hipStream_t)s);
 }
 
 int zl_w4a16_qkv_rope_scatter_planes(const void* planes, const uint32_t* qw, const uint32_t* meta, const uint16_t* bias, const float* cosv,
@@ -973,9 +853,9 @@ int zl_w4a16_qkv_rope_scatter_planes(const void* planes, const uint32_t* qw, con
     if (st) return st;
     ZL_CHECK_ARG(d % 32 == 0 && L.np == n, ZL_ESHAPE);
     ZL_CHECK_ARG(L.qw_bytes < ((int64_t)1 << 32), ZL_ELIMIT);
-    return zl_w4a16_gemm_phase_planes_rope(planes, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, (int)m, (int)n, (int)k,
-                                           (int)L.q, (int)(L.np / 16), cosv, sinv, placement, buf_lens, k_bufs, v_bufs, q_out, (int)h,
-                                           (int)hkv, (int)d, bshd, (hipStream_t)s);
+    const W4Rope rp = {cosv, sinv, placement, buf_lens, k_bufs, v_bufs, q_out, (int)h, (int)hkv, (int)d, bshd};
+    return zl_w4a16_gemm_phase_planes_rope(planes, zl_w4m_problem(L, nullptr, 0, qw, meta, bias, nullptr, nullptr, m, bias ? ZL_EPI_BIAS : 0, nullptr, 0.f),
+                                           rp, (hipStream_t)s);
 }
 
 #endif  // ZL_EXPERIMENTAL (digit-plane entry points)
@@ -995,9 +875,8 @@ int zl_w4a16_gemm_attn_merge(const void* attn_workspace, const int32_t* buf_lens
     int st = zl_w4m_layout(n, k, group_size, &L);
     if (st) return st;
     ZL_CHECK_ARG(L.qw_bytes < ((int64_t)1 << 32), ZL_ELIMIT);
-    return zl_w4a16_gemm_phase_merge(reinterpret_cast<const float*>(attn_workspace), buf_lens, valid_lens, (int)split_len,
-                                     (int)max_splits, qw, meta, (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, residual,
-                                     y, (int)m, (int)n, (int)k, (int)L.q, (int)(L.np / 16), epilogue, (hipStream_t)s);
+    return zl_w4a16_gemm_phase_merge(zl_w4m_problem(L, nullptr, 0, qw, meta, bias, residual, y, m, epilogue, nullptr, 0.f),
+                                     {attn_workspace, buf_lens, valid_lens, (int)split_len, (int)max_splits}, (hipStream_t)s);
 }
 
 int zl_w4a16_gemm_attn_merge_h(const void* attn_workspace, const int32_t* buf_lens, const int32_t* valid_lens,
@@ -1022,17 +901,15 @@ int zl_w4a16_gemm_attn_merge_h_ex(const void* attn_workspace, const int32_t* buf
     int st = zl_w4m_layout(n, k, group_size, &L);
     if (st) return st;
     ZL_CHECK_ARG(L.qw_bytes < ((int64_t)1 << 32), ZL_ELIMIT);
+    const W4Problem pb = zl_w4m_problem(L, nullptr, 0, qw, meta, bias, residual, y, m, epilogue, nullptr, 0.f);
+    const W4Merge mg = {attn_workspace, buf_lens, valid_lens, (int)split_len, (int)max_splits};
 #ifdef ZL_EXPERIMENTAL
     if (opts && opts->small_algo == 2) {
-        st = zl_w4a16_gemm_engine_merge(attn_workspace, buf_lens, valid_lens, (int)split_len, (int)max_splits, qw, meta,
-                                        (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, residual, y, (int)m, (int)n, (int)k,
-                                        (int)L.q, (int)(L.np / 16), epilogue, (hipStream_t)s);
+        st = zl_w4a16_gemm_engine_merge(pb, mg, (hipStream_t)s);
         if (st != ZL_ESHAPE && st != ZL_ELIMIT) return st;
     }
 #endif
-    return zl_w4a16_gemm_i8p_merge(attn_workspace, buf_lens, valid_lens, (int)split_len, (int)max_splits, qw, meta,
-                                   (uint32_t)L.qw_bytes, (uint32_t)L.scales_bytes, bias, residual, y, (int)m, (int)n, (int)k,
-                                   (int)L.q, (int)(L.np / 16), epilogue, (hipStream_t)s);
+    return zl_w4a16_gemm_i8p_merge(pb, mg, (hipStream_t)s);
 }
 
 #ifdef ZL_EXPERIMENTAL
@@ -1052,12 +929,11 @@ int zl_w4a16_attn_out_gate_up(const void* attn_workspace, const int32_t* buf_len
     if (st) return st;
     ZL_CHECK_ARG(L1.np == dim_model && L2.np == n_ff, ZL_ESHAPE);
     ZL_CHECK_ARG(L1.qw_bytes < ((int64_t)1 << 32) && L2.qw_bytes < ((int64_t)1 << 32), ZL_ELIMIT);
-    return zl_w4_engine_o_gateup_launch(attn_workspace, buf_lens, valid_lens, (int)split_len, (int)max_splits, qw_o, meta_o,
-                                        (uint32_t)L1.qw_bytes, (uint32_t)L1.scales_bytes, bias_o, hidden, (int)m, (int)dim_model,
-                                        (int)dim_attn, (int)L1.q, (int)(L1.np / 16), qw_ff, meta_ff, (uint32_t)L2.qw_bytes,
-                                        (uint32_t)L2.scales_bytes, bias_ff, norm_weight, norm_eps, act, (int)n_ff, (int)L2.q,
-                                        (int)(L2.np / 16), ZL_EPI_SILU_MUL | (bias_ff ? ZL_EPI_BIAS : 0), granules, epoch, epoch_add,
-                                        err, (hipStream_t)s);
+    return zl_w4_engine_o_gateup_launch(
+        zl_w4m_problem(L1, nullptr, 0, qw_o, meta_o, bias_o, hidden, hidden, m, ZL_EPI_RESIDUAL | (bias_o ? ZL_EPI_BIAS : 0), nullptr, 0.f),
+        {attn_workspace, buf_lens, valid_lens, (int)split_len, (int)max_splits},
+        zl_w4m_problem(L2, nullptr, 0, qw_ff, meta_ff, bias_ff, nullptr, act, m, ZL_EPI_SILU_MUL | (bias_ff ? ZL_EPI_BIAS : 0), norm_weight, norm_eps),
+        granules, epoch, epoch_add, err, (hipStream_t)s);
 }
 
 int zl_engine_epoch_advance(uint32_t* epoch, uint32_t by, zl_stream_t s) {

@@ -25,6 +25,7 @@
 // the result is bit-identical to zl_w4a16_gemm_tiled run on each expert's gathered rows.
 #include "zl_common.h"
 #include "zl_w4m_dequant.h"
+#include "zl_w4m_epilogue.h"
 
 namespace {
 
@@ -55,7 +56,6 @@ struct GroupedParams {
     int epi;
 };
 
-__device__ __forceinline__ float silu_g(float x) { return x / (1.0f + expf(-x)); }
 
 // PAIRS: the small-M form (rows <= GPTQ_MOE_M_THRES in the driver) -- no sort and no work table: blockIdx.y = (token, slot) pair j,
 // expert ids[j] (outside the stack: dropped), one valid row x[j / in_div] (in_div = 0: x[j]), output row j.  Each output is the same
@@ -254,15 +254,7 @@ __global__ __launch_bounds__(kThreadsG, 2) void k_w4a16_gemm_grouped(const Group
                     // rows of the packed matrix interleave gate (even n) and up (odd n): partner = lane ^ 1
                     const float other = __shfl_xor(v, 1, 64);
                     if ((nrow & 1) == 0 && row >= 0 && n + 1 < p.n) {
-                        float gt = v, up = other, ov;
-                        if (p.epi & ZL_EPI_SILU_MUL) {
-                            gt = (float)zl_f32_to_f16(gt);
-                            up = (float)zl_f32_to_f16(up);
-                            ov = silu_g(gt) * up;
-                        } else {
-                            ov = (float)((double)gt / (1.0 + (double)expf(-gt))) * up;
-                        }
-                        p.y[(size_t)row * p.ld_out + n / 2] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(ov));
+                        p.y[(size_t)row * p.ld_out + n / 2] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(zl_w4m_finish_gated(v, other, p.epi)));
                     }
                 }
             }

@@ -20,6 +20,7 @@
 #include <type_traits>
 #include "zl_common.h"
 #include "w4_i8p_common.h"
+#include "zl_w4m_dequant.h"
 
 #ifdef ZL_PHASE_PROBE
 static int zl_probe_seq = 0;
@@ -31,9 +32,7 @@ constexpr int kT = 512, kW = 8;
 constexpr int kPK = 1024;            // k per phase = kW items of 128
 constexpr int kXS = kPK + 8;         // LDS x row, halfs (padded: conflict-free b128 fragment reads)
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-typedef _Float16 hv2 __attribute__((ext_vector_type(2)));
 
 // ---- optional timeline probe (build with -DZL_PHASE_PROBE; tools/ubench/probe_phase.py) ---------------
 #ifdef ZL_PHASE_PROBE
@@ -59,50 +58,50 @@ __device__ int zl_probe_sel = 0;
 #endif
 
 struct PhaseParams {
-    const uint16_t* x;
-    int64_t ldx;
-    const uint4* qw;
-    const uint32_t* meta;
-    uint32_t qw_bytes, meta_bytes;
-    const uint16_t* bias;
-    const uint16_t* residual;
-    uint16_t* y;
-    int m, n, k;
-    int groups;        // 128-k items per row tile
-    int tiles;         // 16-row tiles
-    int phases;        // ceil(groups / 8)
-    int epi, ld_out;
-    const uint16_t* norm_w;   // NORM instantiations: fused RMSNorm prologue (M <= 4, K <= 4096)
-    float norm_eps;
+    const uint16_t* x = nullptr;
+    int64_t ldx = 0;
+    const uint4* qw = nullptr;
+    const uint32_t* meta = nullptr;
+    uint32_t qw_bytes = 0, meta_bytes = 0;
+    const uint16_t* bias = nullptr;
+    const uint16_t* residual = nullptr;
+    uint16_t* y = nullptr;
+    int m = 0, n = 0, k = 0;
+    int groups = 0;    // 128-k items per row tile
+    int tiles = 0;     // 16-row tiles
+    int phases = 0;    // ceil(groups / 8)
+    int epi = 0, ld_out = 0;
+    const uint16_t* norm_w = nullptr;   // NORM instantiations: fused RMSNorm prologue (M <= 4, K <= 4096)
+    float norm_eps = 0.f;
     // ROPE instantiations (the fused qkv projection of a decode step: rotate q and k, scatter k / v into the ragged
     // KV buffers, q to its own buffer -- rope_qk_cache + copy_to_rag_buffer2 in the GEMV epilogue)
-    const float* cosv;          // (M, D) neox tables
-    const float* sinv;
-    const int32_t* placement;   // (M)
-    const int32_t* buf_lens;    // (M)
-    uint16_t* const* k_bufs;
-    uint16_t* const* v_bufs;
-    uint16_t* q_out;            // (M, H * D)
-    int h, hkv, d, bshd;
-    int pair_stride;            // tiles between a column and its rotation partner: D / 32
+    const float* cosv = nullptr;          // (M, D) neox tables
+    const float* sinv = nullptr;
+    const int32_t* placement = nullptr;   // (M)
+    const int32_t* buf_lens = nullptr;    // (M)
+    uint16_t* const* k_bufs = nullptr;
+    uint16_t* const* v_bufs = nullptr;
+    uint16_t* q_out = nullptr;            // (M, H * D)
+    int h = 0, hkv = 0, d = 0, bshd = 0;
+    int pair_stride = 1;                  // tiles between a column and its rotation partner: D / 32
     // KS > 1 instantiations: K split over KS adjacent workgroups (long K with 17..32 rows: halves / quarters the
     // activation bytes each workgroup pulls through L2); fp32 partials meet in ks_ws, the last arriver sums them in
     // split order and runs the epilogue
-    float* ks_ws;               // [KS][M][N]
-    int* ks_counter;            // one per tile group, zero between launches
+    float* ks_ws = nullptr;               // [KS][M][N]
+    int* ks_counter = nullptr;            // one per tile group, zero between launches
     // MERGE instantiations (the attention output projection of a decode step): the activations are the split-KV
     // partials of the decode attention kernel (attention.hip workspace: [row][head][split][128 acc | max | sum] fp32);
     // the merge of k_decode_attn_combine runs in the prologue, so the step has one launch less.  Uses buf_lens above.
-    const float* mg_ws;
-    const int32_t* mg_valid_lens;
-    int mg_split_len, mg_max_splits;
+    const float* mg_ws = nullptr;
+    const int32_t* mg_valid_lens = nullptr;
+    int mg_split_len = 0, mg_max_splits = 0;
     // I8 instantiations (5..32 rows on the integer matrix cores): the activations arrive as digit planes made ONCE per
     // activation matrix by k_w4_planes (below) instead of fp16 rows staged and dequantised against by every workgroup
-    const unsigned char* planes;   // [group][row block][digit 2 1 0][mfma 0 1][64 lanes][16 bytes]: A operands as they sit in registers
-    const float* pconsts;          // [group][row block][16 rows][xscale, xscale * sum X]
-    uint32_t planes_bytes, pconsts_bytes;
+    const unsigned char* planes = nullptr;   // [group][row block][digit 2 1 0][mfma 0 1][64 lanes][16 bytes]: A operands as they sit in registers
+    const float* pconsts = nullptr;          // [group][row block][16 rows][xscale, xscale * sum X]
+    uint32_t planes_bytes = 0, pconsts_bytes = 0;
 #ifdef ZL_PHASE_PROBE
-    int probe_id;
+    int probe_id = 0;
 #endif
 };
 
@@ -125,24 +124,6 @@ constexpr int ring_depth(int r, bool norm = false) {
 constexpr int x_ahead(int r) { return r <= 4 ? 2 : 1; }
 constexpr int gcd_(int a, int b) { return b == 0 ? a : gcd_(b, a % b); }
 constexpr int lcm_(int a, int b) { return a / gcd_(a, b) * b; }
-
-__device__ __forceinline__ uint32_t and_or(uint32_t w, uint32_t mask_s, uint32_t magic_v) {
-    uint32_t r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(w), "s"(mask_s), "v"(magic_v));
-    return r;
-}
-
-__device__ __forceinline__ h8 dequant_word(uint32_t w, hv2 z1, hv2 z16, uint32_t mask_lo, uint32_t mask_hi, uint32_t magic) {
-    const hv2 one16 = {(_Float16)0.0625f, (_Float16)0.0625f};
-    const hv2 d0 = __builtin_bit_cast(hv2, and_or(w, mask_lo, magic)) + z1;
-    const hv2 d1 = __builtin_elementwise_fma(__builtin_bit_cast(hv2, and_or(w, mask_hi, magic)), one16, z16);
-    const uint32_t wb = w >> 8;
-    const hv2 d2 = __builtin_bit_cast(hv2, and_or(wb, mask_lo, magic)) + z1;
-    const hv2 d3 = __builtin_elementwise_fma(__builtin_bit_cast(hv2, and_or(wb, mask_hi, magic)), one16, z16);
-    h8 a;
-    a[0] = d0.x; a[1] = d0.y; a[2] = d1.x; a[3] = d1.y; a[4] = d2.x; a[5] = d2.y; a[6] = d3.x; a[7] = d3.y;
-    return a;
-}
 
 struct Guard { static constexpr bool value = true; };
 struct NoGuard { static constexpr bool value = false; };
@@ -292,23 +273,9 @@ __global__ __launch_bounds__(kT, (MERGE || I8) ? 1 : 2) void k_w4a16_phase(const
     // ROPE: what this thread's epilogue needs from memory (rotation table entries, the task's slot, buffer length and buffer
     // pointer; 16 m <= 512 outputs, one per thread) is requested here, next to the activations and ahead of the weight ring:
     // in the epilogue they were two dependent round trips at the very end of the launch (w4_i8p.hip does the same)
-    float rp_c0 = 0.f, rp_s0 = 0.f, rp_c1 = 0.f, rp_s1 = 0.f;
-    int rp_place = -1, rp_blen = 0;
-    uint16_t* rp_kv = nullptr;
+    ZlRopeOperands rp;
     if constexpr (ROPE) {
-        if ((int)threadIdx.x < 16 * p.m) {
-            const int m = threadIdx.x >> 4, n0 = tile0 * 16 + (threadIdx.x & 15);
-            const int head = n0 / p.d, dcol = n0 % p.d, half = p.d / 2;
-            if (head < p.h + p.hkv) {
-                rp_c0 = p.cosv[(size_t)m * p.d + dcol]; rp_s0 = p.sinv[(size_t)m * p.d + dcol];
-                rp_c1 = p.cosv[(size_t)m * p.d + dcol + half]; rp_s1 = p.sinv[(size_t)m * p.d + dcol + half];
-            }
-            if (head >= p.h) {
-                rp_place = p.placement[m];
-                rp_blen = p.buf_lens[m];
-                rp_kv = head < p.h + p.hkv ? p.k_bufs[m] : p.v_bufs[m];
-            }
-        }
+        if ((int)threadIdx.x < 16 * p.m) rp = zl_rope_prefetch(p, threadIdx.x >> 4, tile0 * 16 + (threadIdx.x & 15));
     }
     // the plain / bias / residual epilogues: the operands of this thread's FIRST output (its only one up to 512 outputs per
     // workgroup) are requested here as well -- one more round trip at the very end of the launch otherwise
@@ -773,7 +740,7 @@ __global__ __launch_bounds__(kT, (MERGE || I8) ? 1 : 2) void k_w4a16_phase(const
         return;
     }
     if constexpr (ROPE) {
-        const int half = p.d / 2;
+        // (more than one output per thread never happens: 16 m <= 512; the prologue's operands belong to o = threadIdx.x)
         for (int o = threadIdx.x; o < 16 * p.m; o += kT) {
             const int m = o >> 4, n_local = o & 15;
             const int b = m >> 4, ln = ((m & 15) >> 2) * 16 + n_local, i = m & 3;
@@ -783,40 +750,12 @@ __global__ __launch_bounds__(kT, (MERGE || I8) ? 1 : 2) void k_w4a16_phase(const
                 v0 += redf[(((size_t)(0 * MB + b) * kW + w) * 64 + ln) * 4 + i];
                 v1 += redf[(((size_t)(1 * MB + b) * kW + w) * 64 + ln) * 4 + i];
             }
-            const int n0 = tile0 * 16 + n_local, n1 = n0 + half;       // columns of the fused qkv row
             if constexpr (DN) {
                 const float rs = dn_rs(m);
                 v0 *= rs;
                 v1 *= rs;
             }
-            if ((p.epi & ZL_EPI_BIAS) && p.bias) {
-                v0 += (float)__builtin_bit_cast(_Float16, p.bias[n0]);
-                v1 += (float)__builtin_bit_cast(_Float16, p.bias[n1]);
-            }
-            const float a = (float)zl_f32_to_f16(v0), bb = (float)zl_f32_to_f16(v1);   // the projection's fp16 outputs
-            const int head = n0 / p.d, dcol = n0 % p.d;                 // dcol < half
-            // (more than 32 outputs per thread never happens: 16 m <= 512; the prologue's table entries belong to o = threadIdx.x)
-            if (head < p.h + p.hkv) {
-                const uint16_t r0 = __builtin_bit_cast(uint16_t, zl_f32_to_f16(__builtin_fmaf(-bb, rp_s0, a * rp_c0)));
-                const uint16_t r1 = __builtin_bit_cast(uint16_t, zl_f32_to_f16(__builtin_fmaf(a, rp_s1, bb * rp_c1)));
-                if (head < p.h) {
-                    uint16_t* dst = p.q_out + ((size_t)m * p.h + head) * p.d + dcol;
-                    dst[0] = r0;
-                    dst[half] = r1;
-                } else if (rp_place >= 0 && rp_place < rp_blen) {
-                    const int hk = head - p.h;
-                    const size_t row = p.bshd ? (size_t)rp_place * p.hkv + hk : (size_t)hk * rp_blen + rp_place;
-                    uint16_t* dst = rp_kv + row * p.d + dcol;
-                    dst[0] = r0;
-                    dst[half] = r1;
-                }
-            } else if (rp_place >= 0 && rp_place < rp_blen) {
-                const int hk = head - p.h - p.hkv;
-                const size_t row = p.bshd ? (size_t)rp_place * p.hkv + hk : (size_t)hk * rp_blen + rp_place;
-                uint16_t* dst = rp_kv + row * p.d + dcol;
-                dst[0] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(v0));
-                dst[half] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(v1));
-            }
+            zl_rope_store_f16(p, rp, m, tile0 * 16 + n_local, v0, v1);
         }
         ZL_PPROBE(6);
         return;
@@ -866,15 +805,7 @@ __global__ __launch_bounds__(kT, (MERGE || I8) ? 1 : 2) void k_w4a16_phase(const
                     g += (float)__builtin_bit_cast(_Float16, p.bias[2 * pr]);
                     u += (float)__builtin_bit_cast(_Float16, p.bias[2 * pr + 1]);
                 }
-                float ov;
-                if (p.epi & ZL_EPI_SILU_MUL) {
-                    g = (float)zl_f32_to_f16(g);
-                    u = (float)zl_f32_to_f16(u);
-                    ov = silu_f32(g) * u;
-                } else {
-                    ov = (float)((double)g / (1.0 + (double)expf(-g))) * u;
-                }
-                p.y[(size_t)m * p.ld_out + pr] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(ov));
+                p.y[(size_t)m * p.ld_out + pr] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(zl_w4m_finish_gated(g, u, p.epi)));
             }
         }
     }
@@ -1020,29 +951,33 @@ extern "C" int zl_debug_set_probe_p(void* p, int sel) {
 }
 #endif
 
+namespace {
+
+PhaseParams phase_params(const W4Problem& pb) {
+    PhaseParams p;
+    zl_w4m_fill_problem(p, pb);
+    p.phases = (pb.groups + kW - 1) / kW; p.norm_w = pb.norm_w; p.norm_eps = pb.norm_eps;
+    return p;
+}
+void fill_rope(PhaseParams& p, const W4Rope& rp) {
+    zl_w4m_fill_rope(p, rp);
+    p.pair_stride = rp.d / 32;
+}
+
+}  // namespace
+
 // internal (called by zl_w4a16_gemm_mfma): 1 <= m <= 32; norm_w != null (fused RMSNorm): m <= 4 and k <= 4096.
-// rounds_override: 0 = pick
-int zl_w4a16_gemm_phase(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                        uint32_t meta_bytes, const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n,
-                        int k, int groups, int tiles, int epilogue, int ld_out, const uint16_t* norm_w, float norm_eps,
-                        const zl_w4_opts_t* opts, hipStream_t hs) {
-    static const zl_w4_opts_t kNoOpts = {};
-    const zl_w4_opts_t& o = opts ? *opts : kNoOpts;
-    const int rounds_override = o.phase_rounds;
+int zl_w4a16_gemm_phase(const W4Problem& pb, const zl_w4_opts_t* opts, hipStream_t hs) {
+    const zl_w4_opts_t& o = zl_w4_opts_or_default(opts);
+    const int m = pb.m, n = pb.n, k = pb.k, tiles = pb.tiles;
+    const uint16_t* norm_w = pb.norm_w;
     if (norm_w && m <= 8 && k > 4096) return ZL_ESHAPE;        // register-resident staging; 9..32 rows: the deferred norm (DN), any K
     if (norm_w && m > 32) return ZL_ESHAPE;
-    PhaseParams p = {};
-    p.x = x; p.ldx = ldx; p.qw = reinterpret_cast<const uint4*>(qw); p.meta = meta; p.qw_bytes = qw_bytes;
-    p.meta_bytes = meta_bytes; p.bias = bias; p.residual = residual; p.y = y; p.m = m; p.n = n; p.k = k;
-    p.groups = groups; p.tiles = tiles; p.phases = (groups + kW - 1) / kW; p.epi = epilogue; p.ld_out = ld_out; p.norm_w = norm_w; p.norm_eps = norm_eps;
-    p.cosv = p.sinv = nullptr; p.placement = p.buf_lens = nullptr; p.k_bufs = p.v_bufs = nullptr; p.q_out = nullptr;
-    p.h = p.hkv = p.d = p.bshd = 0; p.pair_stride = 1;
-    p.ks_ws = nullptr; p.ks_counter = nullptr;
-    p.mg_ws = nullptr; p.mg_valid_lens = nullptr; p.mg_split_len = p.mg_max_splits = 0;
+    PhaseParams p = phase_params(pb);
     {   // long K with 13..32 rows: K split over 2 or 4 adjacent workgroups (R = KS tiles each, same grid size); the fp32
         // partials and the arrival counters live in the caller's scratch (zl_w4_opts_t)
         const int ksplit = o.phase_ksplit ? o.phase_ksplit : 2;
-        const bool plain = !(epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32)) && !norm_w;
+        const bool plain = !(pb.epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32)) && !norm_w;
         // (K = 14336: 16 rows 14.6 vs 15.9 us, 8 rows 13.4 vs 12.9 us -> from 13 rows on)
         const int ksplit_min_m = o.phase_ksplit_min_m > 0 ? o.phase_ksplit_min_m : 13;
         const int64_t need = ZL_SCRATCH_HEADER + (int64_t)ksplit * m * n * (int64_t)sizeof(float);
@@ -1055,12 +990,11 @@ int zl_w4a16_gemm_phase(const uint16_t* x, int64_t ldx, const uint32_t* qw, cons
             return ksplit == 2 ? launch_phase<2, 2, false, false, 2>(p, grid, hs) : launch_phase<4, 2, false, false, 4>(p, grid, hs);
         }
     }
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
+    const int cus = zl_cu_count();
     // tiles per workgroup: one generation of workgroups when 8 tiles per CU suffice, else full-size workgroups
     int r = (tiles + cus - 1) / cus;
     if (r > 8) r = 8;
-    if (rounds_override > 0 && rounds_override <= 8) r = rounds_override;
+    if (o.phase_rounds > 0 && o.phase_rounds <= 8) r = o.phase_rounds;
     const int grid = (tiles + r - 1) / r;
     const int mb = m <= 16 ? 1 : 2;
 #define ZL_PH(RR)                                                                                              \
@@ -1079,23 +1013,14 @@ int zl_w4a16_gemm_phase(const uint16_t* x, int64_t ldx, const uint32_t* qw, cons
 
 // internal (called by zl_w4a16_qkv_rope_scatter): the fused qkv projection of a decode step with the neox rotation and
 // the KV scatter in the epilogue.  n = (h + 2 hkv) * d, d % 32 == 0, 1 <= m <= 32, norm_w != null: m <= 4 and k <= 4096.
-int zl_w4a16_gemm_phase_rope(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                             uint32_t meta_bytes, const uint16_t* bias, int m, int n, int k, int groups, int tiles,
-                             const uint16_t* norm_w, float norm_eps, const float* cosv, const float* sinv,
-                             const int32_t* placement, const int32_t* buf_lens, uint16_t* const* k_bufs,
-                             uint16_t* const* v_bufs, uint16_t* q_out, int h, int hkv, int d, int bshd, hipStream_t hs) {
-    if (m < 1 || m > 32 || d % 32 != 0 || n != (h + 2 * hkv) * d || tiles * 16 != n) return ZL_ESHAPE;
+int zl_w4a16_gemm_phase_rope(const W4Problem& pb, const W4Rope& rp, hipStream_t hs) {
+    const int m = pb.m, k = pb.k;
+    const uint16_t* norm_w = pb.norm_w;
+    if (m < 1 || m > 32 || !zl_w4m_rope_shape_ok(pb, rp)) return ZL_ESHAPE;
     if (norm_w && m <= 8 && k > 4096) return ZL_ESHAPE;
-    PhaseParams p = {};
-    p.x = x; p.ldx = ldx; p.qw = reinterpret_cast<const uint4*>(qw); p.meta = meta; p.qw_bytes = qw_bytes;
-    p.meta_bytes = meta_bytes; p.bias = bias; p.residual = nullptr; p.y = nullptr; p.m = m; p.n = n; p.k = k;
-    p.groups = groups; p.tiles = tiles; p.phases = (groups + kW - 1) / kW; p.epi = bias ? ZL_EPI_BIAS : 0; p.ld_out = n;
-    p.norm_w = norm_w; p.norm_eps = norm_eps;
-    p.cosv = cosv; p.sinv = sinv; p.placement = placement; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs;
-    p.q_out = q_out; p.h = h; p.hkv = hkv; p.d = d; p.bshd = bshd; p.pair_stride = d / 32;
-    p.ks_ws = nullptr; p.ks_counter = nullptr;
-    p.mg_ws = nullptr; p.mg_valid_lens = nullptr; p.mg_split_len = p.mg_max_splits = 0;
-    const int grid = tiles / 2;
+    PhaseParams p = phase_params(pb);
+    fill_rope(p, rp);
+    const int grid = pb.tiles / 2;
     if (norm_w && m > 8)                               // 9..32 rows: the deferred norm
         return m <= 16 ? launch_phase<2, 1, false, true, 1, false, false, true>(p, grid, hs)
                        : launch_phase<2, 2, false, true, 1, false, false, true>(p, grid, hs);
@@ -1106,26 +1031,16 @@ int zl_w4a16_gemm_phase_rope(const uint16_t* x, int64_t ldx, const uint32_t* qw,
 // internal (called by zl_w4a16_gemm_attn_merge): the attention output projection of a decode step reading the
 // split-KV partials of zl_decode_attn_splits instead of a merged activation row.  m <= 4, k = heads * 128 <= 4096,
 // max_splits <= 16, at most one generation of workgroups (tiles <= 2 * CUs).
-int zl_w4a16_gemm_phase_merge(const float* ws, const int32_t* buf_lens, const int32_t* valid_lens, int split_len,
-                              int max_splits, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                              uint32_t meta_bytes, const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n,
-                              int k, int groups, int tiles, int epilogue, hipStream_t hs) {
-    if (m < 1 || m > 4 || k > 4096 || k % 128 != 0 || max_splits < 1 || max_splits > 16 || split_len < 1) return ZL_ESHAPE;
-    if (epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32)) return ZL_ESHAPE;
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
-    const int r = (tiles + cus - 1) / cus;
+int zl_w4a16_gemm_phase_merge(const W4Problem& pb, const W4Merge& mg, hipStream_t hs) {
+    if (pb.m < 1 || pb.m > 4 || pb.k > 4096 || pb.k % 128 != 0 || mg.max_splits < 1 || mg.max_splits > 16 || mg.split_len < 1) return ZL_ESHAPE;
+    if (pb.epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32)) return ZL_ESHAPE;
+    const int cus = zl_cu_count();
+    const int r = (pb.tiles + cus - 1) / cus;
     if (r > 2) return ZL_ESHAPE;
-    PhaseParams p = {};
-    p.x = nullptr; p.ldx = 0; p.qw = reinterpret_cast<const uint4*>(qw); p.meta = meta; p.qw_bytes = qw_bytes;
-    p.meta_bytes = meta_bytes; p.bias = bias; p.residual = residual; p.y = y; p.m = m; p.n = n; p.k = k;
-    p.groups = groups; p.tiles = tiles; p.phases = (groups + kW - 1) / kW; p.epi = epilogue; p.ld_out = n;
-    p.norm_w = nullptr; p.norm_eps = 0.f;
-    p.cosv = p.sinv = nullptr; p.placement = nullptr; p.buf_lens = buf_lens; p.k_bufs = p.v_bufs = nullptr; p.q_out = nullptr;
-    p.h = p.hkv = p.d = p.bshd = 0; p.pair_stride = 1;
-    p.ks_ws = nullptr; p.ks_counter = nullptr;
-    p.mg_ws = ws; p.mg_valid_lens = valid_lens; p.mg_split_len = split_len; p.mg_max_splits = max_splits;
-    const int grid = (tiles + r - 1) / r;
+    PhaseParams p = phase_params(pb);
+    p.buf_lens = mg.buf_lens;
+    p.mg_ws = reinterpret_cast<const float*>(mg.ws); p.mg_valid_lens = mg.valid_lens; p.mg_split_len = mg.split_len; p.mg_max_splits = mg.max_splits;
+    const int grid = (pb.tiles + r - 1) / r;
     return r == 1 ? launch_phase<1, 1, true, false, 1, true>(p, grid, hs) : launch_phase<2, 1, true, false, 1, true>(p, grid, hs);
 }
 
@@ -1152,38 +1067,29 @@ int zl_w4_planes_launch(const uint16_t* x, int64_t ldx, int m, int k, const uint
     return zl_launch_status();
 }
 
-static void planes_params(PhaseParams& p, const void* planes, int m, int k) {
-    const int mb = m <= 16 ? 1 : 2, groups = k / 128;
-    p.x = nullptr; p.ldx = 0;
+// the block of a problem whose activations arrive as planes (pb.x and pb.norm_w are null)
+static PhaseParams planes_params(const W4Problem& pb, const void* planes) {
+    PhaseParams p = phase_params(pb);
+    const int mb = pb.m <= 16 ? 1 : 2, groups = pb.k / 128;
     p.planes = static_cast<const unsigned char*>(planes);
     p.planes_bytes = (uint32_t)((size_t)groups * mb * 6 * 1024);
     p.pconsts = reinterpret_cast<const float*>(p.planes + p.planes_bytes);
     p.pconsts_bytes = (uint32_t)((size_t)groups * mb * 128);
+    return p;
 }
 
 // internal (called by zl_w4a16_gemm_planes): 5 <= m <= 32 rows as digit planes (zl_w4_planes_launch), k % 128 == 0, k <= 16384
-int zl_w4a16_gemm_phase_planes(const void* planes, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                               const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups, int tiles,
-                               int epilogue, int ld_out, const zl_w4_opts_t* opts, hipStream_t hs) {
-    static const zl_w4_opts_t kNoOpts = {};
-    const zl_w4_opts_t& o = opts ? *opts : kNoOpts;
-    if (zl_w4_planes_bytes_(m, k) < 0 || groups * 128 != k) return ZL_ESHAPE;
-    PhaseParams p = {};
-    planes_params(p, planes, m, k);
-    p.qw = reinterpret_cast<const uint4*>(qw); p.meta = meta; p.qw_bytes = qw_bytes;
-    p.meta_bytes = meta_bytes; p.bias = bias; p.residual = residual; p.y = y; p.m = m; p.n = n; p.k = k;
-    p.groups = groups; p.tiles = tiles; p.phases = (groups + kW - 1) / kW; p.epi = epilogue; p.ld_out = ld_out; p.norm_w = nullptr; p.norm_eps = 0.f;
-    p.cosv = p.sinv = nullptr; p.placement = p.buf_lens = nullptr; p.k_bufs = p.v_bufs = nullptr; p.q_out = nullptr;
-    p.h = p.hkv = p.d = p.bshd = 0; p.pair_stride = 1;
-    p.ks_ws = nullptr; p.ks_counter = nullptr;
-    p.mg_ws = nullptr; p.mg_valid_lens = nullptr; p.mg_split_len = p.mg_max_splits = 0;
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
+int zl_w4a16_gemm_phase_planes(const void* planes, const W4Problem& pb, const zl_w4_opts_t* opts, hipStream_t hs) {
+    const zl_w4_opts_t& o = zl_w4_opts_or_default(opts);
+    const int m = pb.m, n = pb.n, k = pb.k, tiles = pb.tiles;
+    if (zl_w4_planes_bytes_(m, k) < 0 || pb.groups * 128 != k) return ZL_ESHAPE;
+    PhaseParams p = planes_params(pb, planes);
+    const int cus = zl_cu_count();
     const int mb = m <= 16 ? 1 : 2;
     {   // few tiles and a long K (the down projection): K split over 2 / 4 workgroups of 2 / 4 tiles -- a workgroup pulls
         // 1 / KS of the planes through L2 and the grid keeps its size; partials and counters in the caller's scratch
         const int ksplit = o.phase_ksplit ? o.phase_ksplit : 4;
-        const bool plain = !(epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32));
+        const bool plain = !(pb.epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32));
         const int64_t need = ZL_SCRATCH_HEADER + (int64_t)ksplit * m * n * (int64_t)sizeof(float);
         if ((ksplit == 2 || ksplit == 4) && k > 8192 && tiles <= 2 * cus && plain && o.scratch && o.scratch_bytes >= need) {
             p.ks_counter = reinterpret_cast<int*>(o.scratch);
@@ -1208,22 +1114,11 @@ int zl_w4a16_gemm_phase_planes(const void* planes, const uint32_t* qw, const uin
 }
 
 // internal (called by zl_w4a16_qkv_rope_scatter_planes)
-int zl_w4a16_gemm_phase_planes_rope(const void* planes, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                                    const uint16_t* bias, int m, int n, int k, int groups, int tiles, const float* cosv, const float* sinv,
-                                    const int32_t* placement, const int32_t* buf_lens, uint16_t* const* k_bufs, uint16_t* const* v_bufs,
-                                    uint16_t* q_out, int h, int hkv, int d, int bshd, hipStream_t hs) {
-    if (zl_w4_planes_bytes_(m, k) < 0 || groups * 128 != k || d % 32 != 0 || n != (h + 2 * hkv) * d || tiles * 16 != n) return ZL_ESHAPE;
-    PhaseParams p = {};
-    planes_params(p, planes, m, k);
-    p.qw = reinterpret_cast<const uint4*>(qw); p.meta = meta; p.qw_bytes = qw_bytes;
-    p.meta_bytes = meta_bytes; p.bias = bias; p.residual = nullptr; p.y = nullptr; p.m = m; p.n = n; p.k = k;
-    p.groups = groups; p.tiles = tiles; p.phases = (groups + kW - 1) / kW; p.epi = bias ? ZL_EPI_BIAS : 0; p.ld_out = n;
-    p.norm_w = nullptr; p.norm_eps = 0.f;
-    p.cosv = cosv; p.sinv = sinv; p.placement = placement; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs;
-    p.q_out = q_out; p.h = h; p.hkv = hkv; p.d = d; p.bshd = bshd; p.pair_stride = d / 32;
-    p.ks_ws = nullptr; p.ks_counter = nullptr;
-    p.mg_ws = nullptr; p.mg_valid_lens = nullptr; p.mg_split_len = p.mg_max_splits = 0;
-    const int grid = tiles / 2;
-    return m <= 16 ? launch_phase<2, 1, false, true, 1, false, true>(p, grid, hs) : launch_phase<2, 2, false, true, 1, false, true>(p, grid, hs);
+int zl_w4a16_gemm_phase_planes_rope(const void* planes, const W4Problem& pb, const W4Rope& rp, hipStream_t hs) {
+    if (zl_w4_planes_bytes_(pb.m, pb.k) < 0 || pb.groups * 128 != pb.k || !zl_w4m_rope_shape_ok(pb, rp)) return ZL_ESHAPE;
+    PhaseParams p = planes_params(pb, planes);
+    fill_rope(p, rp);
+    const int grid = pb.tiles / 2;
+    return pb.m <= 16 ? launch_phase<2, 1, false, true, 1, false, true>(p, grid, hs) : launch_phase<2, 2, false, true, 1, false, true>(p, grid, hs);
 }
 #endif  // ZL_EXPERIMENTAL

@@ -45,6 +45,7 @@
 #include <type_traits>
 #include "zl_common.h"
 #include "w4_i8p_common.h"
+#include "zl_w4m_dequant.h"
 
 namespace {
 
@@ -71,63 +72,42 @@ __device__ unsigned long long* zl_sprobe_p = nullptr;   // [workgroups * 8 waves
 #define ZL_SPROBE_DUMP() do {} while (0)
 #endif
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-typedef _Float16 hv2 __attribute__((ext_vector_type(2)));
 
 struct SlabParams {
-    const uint16_t* x;
-    int64_t ldx;
-    uint32_t x_bytes;
-    const uint4* qw;
-    const uint32_t* meta;
-    uint32_t qw_bytes, meta_bytes;
-    const uint16_t* bias;
-    const uint16_t* residual;
-    uint16_t* y;
-    int m, n, k;
-    int groups;        // 128-k items per row tile
-    int tiles;         // 16-row tiles
-    int epi, ld_out;
-    int ks;            // K splits (workgroups per tile group)
-    f4* ws;            // [grid][R MB 64] fp32 slabs (ks > 1)
-    int* counters;     // one per tile group, zero between launches
+    const uint16_t* x = nullptr;
+    int64_t ldx = 0;
+    uint32_t x_bytes = 0;
+    const uint4* qw = nullptr;
+    const uint32_t* meta = nullptr;
+    uint32_t qw_bytes = 0, meta_bytes = 0;
+    const uint16_t* bias = nullptr;
+    const uint16_t* residual = nullptr;
+    uint16_t* y = nullptr;
+    int m = 0, n = 0, k = 0;
+    int groups = 0;    // 128-k items per row tile
+    int tiles = 0;     // 16-row tiles
+    int epi = 0, ld_out = 0;
+    int ks = 0;        // K splits (workgroups per tile group)
+    f4* ws = nullptr;  // [grid][R MB 64] fp32 slabs (ks > 1)
+    int* counters = nullptr;   // one per tile group, zero between launches
     // ROPE instantiation (the fused qkv projection of a decode step)
-    const float* cosv;
-    const float* sinv;
-    const int32_t* placement;
-    const int32_t* buf_lens;
-    uint16_t* const* k_bufs;
-    uint16_t* const* v_bufs;
-    uint16_t* q_out;
-    int h, hkv, d, bshd;
-    int tstride;       // tiles between a workgroup's consecutive tiles: 1; ROPE: d / 32 (a column block and its rotation partners)
+    const float* cosv = nullptr;
+    const float* sinv = nullptr;
+    const int32_t* placement = nullptr;
+    const int32_t* buf_lens = nullptr;
+    uint16_t* const* k_bufs = nullptr;
+    uint16_t* const* v_bufs = nullptr;
+    uint16_t* q_out = nullptr;
+    int h = 0, hkv = 0, d = 0, bshd = 0;
+    int tstride = 1;   // tiles between a workgroup's consecutive tiles: 1; ROPE: d / 32 (a column block and its rotation partners)
     // row statistics hand-off (zl_w4_opts_t::row_ss / row_ss_out)
-    const uint16_t* norm_w;   // NORM instantiation: the RMSNorm weight of x ...
-    const float* row_ss;      // ... and its tile sums of squares [m][ss_parts]
-    int ss_parts;             // k / 16
-    float eps;
-    float* ss_out;            // tile sums of the stored rows [m][tiles] (plain epilogues), or null
+    const uint16_t* norm_w = nullptr;   // NORM instantiation: the RMSNorm weight of x ...
+    const float* row_ss = nullptr;      // ... and its tile sums of squares [m][ss_parts]
+    int ss_parts = 0;                   // k / 16
+    float eps = 0.f;
+    float* ss_out = nullptr;            // tile sums of the stored rows [m][tiles] (plain epilogues), or null
 };
-
-__device__ __forceinline__ uint32_t and_or(uint32_t w, uint32_t mask_s, uint32_t magic_v) {
-    uint32_t r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(w), "s"(mask_s), "v"(magic_v));
-    return r;
-}
-
-// eight nibbles of a ZLW4M word -> eight halves (q - z), exact (w4_phase.hip dequant_word)
-__device__ __forceinline__ h8 dequant_word(uint32_t w, hv2 z1, hv2 z16, uint32_t mask_lo, uint32_t mask_hi, uint32_t magic) {
-    const hv2 one16 = {(_Float16)0.0625f, (_Float16)0.0625f};
-    const hv2 d0 = __builtin_bit_cast(hv2, and_or(w, mask_lo, magic)) + z1;
-    const hv2 d1 = __builtin_elementwise_fma(__builtin_bit_cast(hv2, and_or(w, mask_hi, magic)), one16, z16);
-    const uint32_t wb = w >> 8;
-    const hv2 d2 = __builtin_bit_cast(hv2, and_or(wb, mask_lo, magic)) + z1;
-    const hv2 d3 = __builtin_elementwise_fma(__builtin_bit_cast(hv2, and_or(wb, mask_hi, magic)), one16, z16);
-    h8 a;
-    a[0] = d0.x; a[1] = d0.y; a[2] = d1.x; a[3] = d1.y; a[4] = d2.x; a[5] = d2.y; a[6] = d3.x; a[7] = d3.y;
-    return a;
-}
 
 __device__ __forceinline__ void store_sc1(f4* dst, f4 v) {      // write-through 16-byte store
     asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(v) : "memory");
@@ -594,50 +574,14 @@ __global__ __launch_bounds__(512, 2) void k_w4a16_slab(const SlabParams p) {
         }
         __syncthreads();
         const float* finf = reinterpret_cast<const float*>(fin);
-        const int half = p.d >> 1;
         const int nout = 16 * p.m;
         for (int o = (int)threadIdx.x; o < nout; o += bd) {
             const int n_local = o & 15, m = o >> 4;
-            const int tile = tile0;
-            if (tile >= p.tiles) continue;
-            const int b = m >> 4, ln = ((m & 15) >> 2) * 16 + n_local, i = m & 3;
-            float v0 = finf[((size_t)(0 * MB + b) * 64 + ln) * 4 + i], v1 = finf[((size_t)(1 * MB + b) * 64 + ln) * 4 + i];
-            const int n0 = tile * 16 + n_local, n1 = n0 + half;
-            if ((p.epi & ZL_EPI_BIAS) && p.bias) {
-                v0 += (float)__builtin_bit_cast(_Float16, p.bias[n0]);
-                v1 += (float)__builtin_bit_cast(_Float16, p.bias[n1]);
-            }
-            const float a = (float)zl_f32_to_f16(v0), bb = (float)zl_f32_to_f16(v1);
-            const int head = n0 / p.d, dcol = n0 % p.d;
-            if (head < p.h + p.hkv) {
-                const float c0 = p.cosv[(size_t)m * p.d + dcol], s0 = p.sinv[(size_t)m * p.d + dcol];
-                const float c1 = p.cosv[(size_t)m * p.d + dcol + half], s1 = p.sinv[(size_t)m * p.d + dcol + half];
-                const uint16_t r0v = __builtin_bit_cast(uint16_t, zl_f32_to_f16(__builtin_fmaf(-bb, s0, a * c0)));
-                const uint16_t r1v = __builtin_bit_cast(uint16_t, zl_f32_to_f16(__builtin_fmaf(a, s1, bb * c1)));
-                if (head < p.h) {
-                    uint16_t* dst = p.q_out + ((size_t)m * p.h + head) * p.d + dcol;
-                    dst[0] = r0v;
-                    dst[half] = r1v;
-                } else {
-                    const int place = p.placement[m], blen = p.buf_lens[m];
-                    if (place >= 0 && place < blen) {
-                        const int hk = head - p.h;
-                        const size_t row = p.bshd ? (size_t)place * p.hkv + hk : (size_t)hk * blen + place;
-                        uint16_t* dst = p.k_bufs[m] + row * p.d + dcol;
-                        dst[0] = r0v;
-                        dst[half] = r1v;
-                    }
-                }
-            } else {
-                const int place = p.placement[m], blen = p.buf_lens[m];
-                if (place >= 0 && place < blen) {
-                    const int hk = head - p.h - p.hkv;
-                    const size_t row = p.bshd ? (size_t)place * p.hkv + hk : (size_t)hk * blen + place;
-                    uint16_t* dst = p.v_bufs[m] + row * p.d + dcol;
-                    dst[0] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(v0));
-                    dst[half] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(v1));
-                }
-            }
+            if (tile0 >= p.tiles) continue;
+            const int b = m >> 4, ln = ((m & 15) >> 2) * 16 + n_local, i = m & 3, n0 = tile0 * 16 + n_local;
+            // (the operands are asked for here, behind the stream: ahead of the weight ring they would be a different kernel)
+            const ZlRopeOperands rp = zl_rope_prefetch(p, m, n0);
+            zl_rope_store_f16(p, rp, m, n0, finf[((size_t)(0 * MB + b) * 64 + ln) * 4 + i], finf[((size_t)(1 * MB + b) * 64 + ln) * 4 + i]);
         }
         return;
     } else {
@@ -664,16 +608,8 @@ __global__ __launch_bounds__(512, 2) void k_w4a16_slab(const SlabParams p) {
                 for (int i = 0; i < 4; ++i) {
                     const int m = mrow0 + i;
                     if (m >= p.m) continue;
-                    float g = has_bias ? v[i] + bg : v[i], uu = has_bias ? u[i] + bu : u[i];
-                    float ov;
-                    if (p.epi & ZL_EPI_SILU_MUL) {
-                        g = (float)zl_f32_to_f16(g);
-                        uu = (float)zl_f32_to_f16(uu);
-                        ov = silu_f32(g) * uu;
-                    } else {
-                        ov = (float)((double)g / (1.0 + (double)expf(-g))) * uu;
-                    }
-                    p.y[(size_t)m * p.ld_out + prc] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(ov));
+                    const float g = has_bias ? v[i] + bg : v[i], uu = has_bias ? u[i] + bu : u[i];
+                    p.y[(size_t)m * p.ld_out + prc] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(zl_w4m_finish_gated(g, uu, p.epi)));
                 }
                 continue;
             }
@@ -696,11 +632,7 @@ __global__ __launch_bounds__(512, 2) void k_w4a16_slab(const SlabParams p) {
                 const int m = mrow0 + i;
                 sq[i] = 0.f;
                 if (!live || m >= p.m) continue;
-                float ov;
-                if (p.epi & ZL_EPI_ADD_C) ov = (cin[i] + v[i]) + bb;
-                else ov = v[i] + bb;
-                _Float16 y16 = zl_f32_to_f16(ov);
-                if (p.epi & ZL_EPI_RESIDUAL) y16 = zl_f32_to_f16(res[i] + (float)y16);
+                const _Float16 y16 = zl_w4m_finish(v[i], bb, cin[i], res[i], p.epi);
                 p.y[(size_t)m * p.ld_out + col] = __builtin_bit_cast(uint16_t, y16);
                 sq[i] = (float)y16 * (float)y16;      // exact in fp32
             }
@@ -779,8 +711,7 @@ struct SlabPlan {
 bool norm_ok(const zl_w4_opts_t& o, int k) { return o.row_ss != nullptr && k % 1024 == 0 && k <= 8192 && k > 2048; }
 
 bool plan_slab(int m, int tiles, int groups, bool have_scratch, bool rope, bool norm, const zl_w4_opts_t& o, SlabPlan* out) {
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
+    const int cus = zl_cu_count();
     int nw = groups >= 8 ? 8 : 4, gpw = groups > 16 ? 4 : groups > 8 ? 2 : 1;
     if (o.slab_nw) nw = o.slab_nw;
     if (o.slab_gpw) gpw = o.slab_gpw;
@@ -814,15 +745,6 @@ int launch_slab_any(const SlabParams& p, const SlabPlan& pl, int mb, hipStream_t
     }
 }
 
-void fill_common(SlabParams& p, const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                 uint32_t meta_bytes, const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups,
-                 int tiles, int epilogue, int ld_out) {
-    p.x = x; p.ldx = ldx; p.x_bytes = (uint32_t)((((int64_t)m - 1) * ldx + k) * 2);
-    p.qw = reinterpret_cast<const uint4*>(qw); p.meta = meta; p.qw_bytes = qw_bytes; p.meta_bytes = meta_bytes;
-    p.bias = bias; p.residual = residual; p.y = y; p.m = m; p.n = n; p.k = k; p.groups = groups; p.tiles = tiles;
-    p.epi = epilogue; p.ld_out = ld_out;
-}
-
 bool slab_shape_ok(int m, int k, int groups, int tiles, int64_t ldx, uint32_t qw_bytes) {
     if (m < 1 || m > 32 || k % 128 != 0 || groups * 128 != k) return false;
     if ((((int64_t)m - 1) * ldx + k) * 2 >= ((int64_t)1 << 31)) return false;                     // 32-bit lane offsets into x
@@ -838,51 +760,47 @@ bool take_scratch(const zl_w4_opts_t& o, const SlabPlan& pl, int mb, int tiles, 
     return true;
 }
 
+// the block of a planned problem: the common fields, the statistics hand-off, the K split
+SlabParams slab_params(const W4Problem& pb, const zl_w4_opts_t& o, const SlabPlan& pl) {
+    SlabParams p;
+    zl_w4m_fill_problem(p, pb);
+    p.x_bytes = (uint32_t)((((int64_t)pb.m - 1) * pb.ldx + pb.k) * 2);
+    if (pb.norm_w) { p.norm_w = pb.norm_w; p.row_ss = o.row_ss; p.ss_parts = pb.k / 16; p.eps = pb.norm_eps; }
+    p.ks = pl.ks;
+    return p;
+}
+
 }  // namespace
 
 // internal (zl_w4a16_gemm_mfma_ex): rows 1..32 without a fused norm, K a multiple of 128.  Returns ZL_ESHAPE when the shape (or
 // the caller's scratch) does not fit -- the caller then takes the phase kernel.
-int zl_w4a16_gemm_slab(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes, uint32_t meta_bytes,
-                       const uint16_t* bias, const uint16_t* residual, uint16_t* y, int m, int n, int k, int groups, int tiles,
-                       int epilogue, int ld_out, const uint16_t* norm_w, float norm_eps, const zl_w4_opts_t* opts, hipStream_t hs) {
-    static const zl_w4_opts_t kNoOpts = {};
-    const zl_w4_opts_t& o = opts ? *opts : kNoOpts;
-    if (!slab_shape_ok(m, k, groups, tiles, ldx, qw_bytes)) return ZL_ESHAPE;
-    if (norm_w && !norm_ok(o, k)) return ZL_ESHAPE;
+int zl_w4a16_gemm_slab(const W4Problem& pb, const zl_w4_opts_t* opts, hipStream_t hs) {
+    const zl_w4_opts_t& o = zl_w4_opts_or_default(opts);
+    if (!slab_shape_ok(pb.m, pb.k, pb.groups, pb.tiles, pb.ldx, pb.qw_bytes)) return ZL_ESHAPE;
+    if (pb.norm_w && !norm_ok(o, pb.k)) return ZL_ESHAPE;
     SlabPlan pl;
-    if (!plan_slab(m, tiles, groups, o.scratch != nullptr, false, norm_w != nullptr, o, &pl)) return ZL_ESHAPE;
-    SlabParams p = {};
-    fill_common(p, x, ldx, qw, meta, qw_bytes, meta_bytes, bias, residual, y, m, n, k, groups, tiles, epilogue, ld_out);
-    if (norm_w) { p.norm_w = norm_w; p.row_ss = o.row_ss; p.ss_parts = k / 16; p.eps = norm_eps; }
-    if (o.row_ss_out && !(epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32)) && tiles * 16 == n) p.ss_out = o.row_ss_out;
-    const int mb = m <= 16 ? 1 : 2;
-    p.ks = pl.ks;
-    if (pl.ks > 1 && !take_scratch(o, pl, mb, tiles, p)) return ZL_ESHAPE;
+    if (!plan_slab(pb.m, pb.tiles, pb.groups, o.scratch != nullptr, false, pb.norm_w != nullptr, o, &pl)) return ZL_ESHAPE;
+    SlabParams p = slab_params(pb, o, pl);
+    if (o.row_ss_out && !(pb.epilogue & (ZL_EPI_SILU_MUL | ZL_EPI_SILU_MUL_F32)) && pb.tiles * 16 == pb.n) p.ss_out = o.row_ss_out;
+    const int mb = pb.m <= 16 ? 1 : 2;
+    if (pl.ks > 1 && !take_scratch(o, pl, mb, pb.tiles, p)) return ZL_ESHAPE;
     return launch_slab_any<false>(p, pl, mb, hs);
 }
 
 // internal (zl_w4a16_qkv_rope_scatter): the fused qkv projection of a decode step with the neox rotation and the KV scatter in
 // the epilogue; d % 32 == 0 (a workgroup's two tiles are a column block and its rotation partners)
-int zl_w4a16_gemm_slab_rope(const uint16_t* x, int64_t ldx, const uint32_t* qw, const uint32_t* meta, uint32_t qw_bytes,
-                            uint32_t meta_bytes, const uint16_t* bias, int m, int n, int k, int groups, int tiles, const float* cosv,
-                            const float* sinv, const int32_t* placement, const int32_t* buf_lens, uint16_t* const* k_bufs,
-                            uint16_t* const* v_bufs, uint16_t* q_out, int h, int hkv, int d, int bshd, const uint16_t* norm_w,
-                            float norm_eps, const zl_w4_opts_t* opts, hipStream_t hs) {
-    static const zl_w4_opts_t kNoOpts = {};
-    const zl_w4_opts_t& o = opts ? *opts : kNoOpts;
-    if (!slab_shape_ok(m, k, groups, tiles, ldx, qw_bytes)) return ZL_ESHAPE;
-    if (d % 32 != 0 || n != (h + 2 * hkv) * d || tiles * 16 != n) return ZL_ESHAPE;
-    if (norm_w && !norm_ok(o, k)) return ZL_ESHAPE;
+int zl_w4a16_gemm_slab_rope(const W4Problem& pb, const W4Rope& rp, const zl_w4_opts_t* opts, hipStream_t hs) {
+    const zl_w4_opts_t& o = zl_w4_opts_or_default(opts);
+    if (!slab_shape_ok(pb.m, pb.k, pb.groups, pb.tiles, pb.ldx, pb.qw_bytes)) return ZL_ESHAPE;
+    if (!zl_w4m_rope_shape_ok(pb, rp)) return ZL_ESHAPE;
+    if (pb.norm_w && !norm_ok(o, pb.k)) return ZL_ESHAPE;
     SlabPlan pl;
-    if (!plan_slab(m, tiles, groups, o.scratch != nullptr, true, norm_w != nullptr, o, &pl)) return ZL_ESHAPE;
-    SlabParams p = {};
-    fill_common(p, x, ldx, qw, meta, qw_bytes, meta_bytes, bias, nullptr, nullptr, m, n, k, groups, tiles, bias ? ZL_EPI_BIAS : 0, n);
-    if (norm_w) { p.norm_w = norm_w; p.row_ss = o.row_ss; p.ss_parts = k / 16; p.eps = norm_eps; }
-    p.cosv = cosv; p.sinv = sinv; p.placement = placement; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs;
-    p.q_out = q_out; p.h = h; p.hkv = hkv; p.d = d; p.bshd = bshd; p.tstride = d / 32;
-    const int mb = m <= 16 ? 1 : 2;
-    p.ks = pl.ks;
-    if (pl.ks > 1 && !take_scratch(o, pl, mb, tiles, p)) return ZL_ESHAPE;
+    if (!plan_slab(pb.m, pb.tiles, pb.groups, o.scratch != nullptr, true, pb.norm_w != nullptr, o, &pl)) return ZL_ESHAPE;
+    SlabParams p = slab_params(pb, o, pl);
+    zl_w4m_fill_rope(p, rp);
+    p.tstride = rp.d / 32;
+    const int mb = pb.m <= 16 ? 1 : 2;
+    if (pl.ks > 1 && !take_scratch(o, pl, mb, pb.tiles, p)) return ZL_ESHAPE;
     return launch_slab_any<true>(p, pl, mb, hs);
 }
 
@@ -897,8 +815,7 @@ extern "C" int zl_row_ss(const uint16_t* x, int64_t ldx, int64_t m, int64_t k, f
 // the dispatch questions of zl_w4a16_gemm_mfma_ex / zl_w4a16_qkv_rope_scatter_ex, asked without launching (w4_mfma.hip calls the
 // launchers above under the same conditions)
 bool zl_slab_route(int64_t m, int64_t n, int64_t k, int64_t group_size, bool rope, bool norm, bool silu, const zl_w4_opts_t* opts) {
-    static const zl_w4_opts_t kNoOpts = {};
-    const zl_w4_opts_t& o = opts ? *opts : kNoOpts;
+    const zl_w4_opts_t& o = zl_w4_opts_or_default(opts);
     if (o.slab < 0 || group_size <= 0 || group_size % 128 != 0 || k % 128 != 0 || n % 16 != 0) return false;
     if (m < (o.slab_min_m > 0 ? o.slab_min_m : (rope || o.small_algo == 1 ? 5 : 3)) || m > 32) return false;
     if (norm && !(o.row_ss != nullptr && k % 1024 == 0 && k <= 8192 && k > 2048)) return false;

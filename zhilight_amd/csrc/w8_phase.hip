@@ -18,6 +18,7 @@
 //   qw : [N/16][Kp/128][2][64 lanes][16 B]   lane (n = lane & 15, kq = lane >> 4), half j: k = 128 g + 64 j + 16 kq .. +15
 // Kp = K rounded up to 128 (zero padded); row_interleave packs [w_in; w_gated] as (gate_n, up_n) row pairs.
 #include "zl_common.h"
+#include "zl_w4m_epilogue.h"
 
 namespace {
 
@@ -30,26 +31,26 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 enum { kBack = 0, kBackAdd = 1, kActSilu = 2, kActGelu = 3 };
 
 struct W8Params {
-    const int8_t* x;           // (M, K) int8 activations
-    const float* sx;           // (M) activation scales
-    const uint4* qw;
-    uint32_t qw_bytes;
-    const uint16_t* sy;        // (N) weight scales, T (interleaved like the rows for the gated epilogues)
-    const uint16_t* addend;    // (M, N) T   [kBackAdd]
-    uint16_t* y;
-    float scale;               // [kBackAdd]
-    int m, n, k;
-    int groups, tiles, phases;
-    int epi, ld_out, dtype;
+    const int8_t* x = nullptr;           // (M, K) int8 activations
+    const float* sx = nullptr;           // (M) activation scales
+    const uint4* qw = nullptr;
+    uint32_t qw_bytes = 0;
+    const uint16_t* sy = nullptr;        // (N) weight scales, T (interleaved like the rows for the gated epilogues)
+    const uint16_t* addend = nullptr;    // (M, N) T   [kBackAdd]
+    uint16_t* y = nullptr;
+    float scale = 1.f;                   // [kBackAdd]
+    int m = 0, n = 0, k = 0;
+    int groups = 0, tiles = 0, phases = 0;
+    int epi = kBack, ld_out = 0, dtype = 0;
     // ROPE instantiation (fused qkv projection of a decode step: scale back, neox rotation of q and k, KV scatter)
-    const float* cosv;
-    const float* sinv;
-    const int32_t* placement;
-    const int32_t* buf_lens;
-    uint16_t* const* k_bufs;
-    uint16_t* const* v_bufs;
-    uint16_t* q_out;
-    int h, hkv, d, bshd, pair_stride;
+    const float* cosv = nullptr;
+    const float* sinv = nullptr;
+    const int32_t* placement = nullptr;
+    const int32_t* buf_lens = nullptr;
+    uint16_t* const* k_bufs = nullptr;
+    uint16_t* const* v_bufs = nullptr;
+    uint16_t* q_out = nullptr;
+    int h = 0, hkv = 0, d = 0, bshd = 0, pair_stride = 1;
 };
 
 constexpr int ring_depth(int r) { return r == 1 ? 3 : r == 2 ? 4 : r == 3 ? 6 : r == 4 ? 8 : r; }
@@ -104,26 +105,16 @@ __global__ __launch_bounds__(kT, 2) void k_w8a8_phase(const W8Params p) {
     // ROPE: the operands of this thread's epilogue output (16 m <= 512, one per thread: both scales, the rotation table entries,
     // the task's slot / buffer length / buffer pointer) are requested with the activations, ahead of the weight ring -- at the
     // end of the launch they were two dependent round trips (w4_phase.hip, w4_i8p.hip do the same)
-    float rp_sx = 0.f, rp_c0 = 0.f, rp_s0 = 0.f, rp_c1 = 0.f, rp_s1 = 0.f;
+    float rp_sx = 0.f;
     uint16_t rp_sy0 = 0, rp_sy1 = 0;
-    int rp_place = -1, rp_blen = 0;
-    uint16_t* rp_kv = nullptr;
+    ZlRopeOperands rp;
     if constexpr (ROPE) {
         if ((int)threadIdx.x < 16 * p.m) {
-            const int m = threadIdx.x >> 4, n0 = tile0 * 16 + (threadIdx.x & 15), half = p.d / 2;
-            const int head = n0 / p.d, dcol = n0 % p.d;
+            const int m = threadIdx.x >> 4, n0 = tile0 * 16 + (threadIdx.x & 15);
             rp_sx = p.sx[m];
             rp_sy0 = p.sy[n0];
-            rp_sy1 = p.sy[n0 + half];
-            if (head < p.h + p.hkv) {
-                rp_c0 = p.cosv[(size_t)m * p.d + dcol]; rp_s0 = p.sinv[(size_t)m * p.d + dcol];
-                rp_c1 = p.cosv[(size_t)m * p.d + dcol + half]; rp_s1 = p.sinv[(size_t)m * p.d + dcol + half];
-            }
-            if (head >= p.h) {
-                rp_place = p.placement[m];
-                rp_blen = p.buf_lens[m];
-                rp_kv = (head >= p.h + p.hkv ? p.v_bufs : p.k_bufs)[m];
-            }
+            rp_sy1 = p.sy[n0 + p.d / 2];
+            rp = zl_rope_prefetch(p, m, n0);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -239,24 +230,15 @@ __global__ __launch_bounds__(kT, 2) void k_w8a8_phase(const W8Params p) {
                 a16 = ZT<ZL_BF16>::from_f32(back<ZL_BF16>(c0, sx, rp_sy0));
                 b16 = ZT<ZL_BF16>::from_f32(back<ZL_BF16>(c1, sx, rp_sy1));
             }
-            const int head = n0 / p.d, dcol = n0 % p.d;
-            uint16_t* dst = nullptr;
             uint16_t r0 = a16, r1 = b16;
-            if (head < p.h + p.hkv) {
+            if (n0 / p.d < p.h + p.hkv) {
                 const float a = p.dtype == ZL_F16 ? ZT<ZL_F16>::to_f32(a16) : ZT<ZL_BF16>::to_f32(a16);
                 const float bb = p.dtype == ZL_F16 ? ZT<ZL_F16>::to_f32(b16) : ZT<ZL_BF16>::to_f32(b16);
-                const float v0 = __builtin_fmaf(-bb, rp_s0, a * rp_c0), v1 = __builtin_fmaf(a, rp_s1, bb * rp_c1);
+                const float v0 = __builtin_fmaf(-bb, rp.s0, a * rp.c0), v1 = __builtin_fmaf(a, rp.s1, bb * rp.c1);
                 r0 = p.dtype == ZL_F16 ? ZT<ZL_F16>::from_f32(v0) : ZT<ZL_BF16>::from_f32(v0);
                 r1 = p.dtype == ZL_F16 ? ZT<ZL_F16>::from_f32(v1) : ZT<ZL_BF16>::from_f32(v1);
             }
-            if (head < p.h) {
-                dst = p.q_out + ((size_t)m * p.h + head) * p.d + dcol;
-            } else if (rp_place >= 0 && rp_place < rp_blen) {
-                const bool is_v = head >= p.h + p.hkv;
-                const int hk = head - p.h - (is_v ? p.hkv : 0);
-                const size_t row = p.bshd ? (size_t)rp_place * p.hkv + hk : (size_t)hk * rp_blen + rp_place;
-                dst = rp_kv + row * p.d + dcol;
-            }
+            uint16_t* dst = zl_rope_dest(p, rp, m, n0);
             if (dst) {
                 dst[0] = r0;
                 dst[half] = r1;
@@ -356,6 +338,17 @@ __global__ void k_pack_w8m(const int8_t* __restrict__ w, uint32_t* __restrict__ 
     }
 }
 
+// the fields both entry points fill alike; bytes = zl_w8m_bytes(n, k) < 4 GiB
+W8Params w8_params(const int8_t* xq, const float* scale_x, const void* qw, uint32_t bytes, const uint16_t* scale_y, uint16_t* out,
+                   int64_t m, int64_t n, int64_t k, int dtype) {
+    W8Params p;
+    p.x = xq; p.sx = scale_x; p.qw = reinterpret_cast<const uint4*>(qw); p.qw_bytes = bytes; p.sy = scale_y; p.y = out;
+    p.m = (int)m; p.n = (int)n; p.k = (int)k;
+    p.groups = (int)((k + 127) / 128); p.tiles = (int)((n + 15) / 16); p.phases = (p.groups + kW - 1) / kW;
+    p.ld_out = (int)n; p.dtype = dtype;
+    return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -394,15 +387,10 @@ int zl_w8a8_gemm_phase_ex(const int8_t* xq, const float* scale_x, const void* qw
     ZL_CHECK_ARG(!gated || n % 2 == 0, ZL_ESHAPE);
     const int64_t bytes = zl_w8m_bytes(n, k);
     ZL_CHECK_ARG(bytes < ((int64_t)1 << 32), ZL_ELIMIT);
-    W8Params p;
-    p.x = xq; p.sx = scale_x; p.qw = reinterpret_cast<const uint4*>(qw); p.qw_bytes = (uint32_t)bytes; p.sy = scale_y;
-    p.addend = addend; p.y = out; p.scale = scale; p.m = (int)m; p.n = (int)n; p.k = (int)k;
-    p.groups = (int)((k + 127) / 128); p.tiles = (int)((n + 15) / 16); p.phases = (p.groups + kW - 1) / kW;
-    p.epi = epilogue; p.ld_out = (int)(gated ? n / 2 : n); p.dtype = dtype;
-    p.cosv = p.sinv = nullptr; p.placement = p.buf_lens = nullptr; p.k_bufs = p.v_bufs = nullptr; p.q_out = nullptr;
-    p.h = p.hkv = p.d = p.bshd = 0; p.pair_stride = 1;
-    int cus = zl_device_cu_count();
-    if (cus <= 0) cus = 256;
+    W8Params p = w8_params(xq, scale_x, qw, (uint32_t)bytes, scale_y, out, m, n, k, dtype);
+    p.addend = addend; p.scale = scale; p.epi = epilogue;
+    if (gated) p.ld_out = (int)(n / 2);
+    const int cus = zl_cu_count();
     int r = (p.tiles + cus - 1) / cus;
     if (r > 8) r = 8;
     if (rounds >= 1 && rounds <= 8) r = rounds;      // explicit override: the tests sweep the instantiations
@@ -426,11 +414,7 @@ int zl_w8a8_qkv_rope_scatter(const int8_t* xq, const float* scale_x, const void*
     const int64_t n = (h + 2 * hkv) * d;
     const int64_t bytes = zl_w8m_bytes(n, k);
     ZL_CHECK_ARG(bytes < ((int64_t)1 << 32), ZL_ELIMIT);
-    W8Params p;
-    p.x = xq; p.sx = scale_x; p.qw = reinterpret_cast<const uint4*>(qw); p.qw_bytes = (uint32_t)bytes; p.sy = scale_y;
-    p.addend = nullptr; p.y = nullptr; p.scale = 1.f; p.m = (int)m; p.n = (int)n; p.k = (int)k;
-    p.groups = (int)((k + 127) / 128); p.tiles = (int)(n / 16); p.phases = (p.groups + kW - 1) / kW;
-    p.epi = kBack; p.ld_out = (int)n; p.dtype = dtype;
+    W8Params p = w8_params(xq, scale_x, qw, (uint32_t)bytes, scale_y, nullptr, m, n, k, dtype);
     p.cosv = cosv; p.sinv = sinv; p.placement = placement; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs;
     p.q_out = q_out; p.h = (int)h; p.hkv = (int)hkv; p.d = (int)d; p.bshd = bshd; p.pair_stride = (int)(d / 32);
     const int grid = p.tiles / 2;

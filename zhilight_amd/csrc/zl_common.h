@@ -18,6 +18,12 @@ static inline int zl_launch_status() {
     return e == hipSuccess ? ZL_OK : (int)e;
 }
 
+// CUs of the current device for the launch geometry; an MI355X's 256 where the query fails
+static inline int zl_cu_count() {
+    const int cus = zl_device_cu_count();
+    return cus > 0 ? cus : 256;
+}
+
 typedef _Float16 h16;
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
