@@ -1072,6 +1072,24 @@ class _PromptRows:
         return self.k_tab[li], self.v_tab[li]
 
 
+@dataclass(frozen=True)
+class _DecodeRoute:
+    """What every layer of one decode step launches: decided once per call by LLaMA._decode_route, switched on by the three stages of
+    encode's layer body (DESIGN 4 "One route, one layer body" has the condition and the ZL_* switch of every value)."""
+    qkv: str                    # "w4" zl_w4a16_qkv_rope_scatter | "w8" layernorm_quant + w8a8_qkv_rope_scatter | "plain" project_qkv + rope / scatter
+    norm: Optional[str]         # "w4" only, its RMSNorm: "fused" in registers | "launch" of its own | "row_ss" from statistics the projections hand on
+    attn: str                   # "hook" | "la" | "splits" (records left for attn_out) | "mqa" | "valu_fused" (rope / scatter included) | "quant"
+    out: str                    # "merge" w4_attn_out_merge | "merge_gate_up" w4_attn_out_gate_up, "merge" where it declines | "linear" attn_out_add
+    skip_attn: bool             # bench.py's legs, resolved against the route: stage 2 is left out ...
+    skip_proj: bool             # ... stages 1 and 3 are
+    workspace: torch.Tensor     # the split attention's partials
+    scale: float
+    merge_plan: Optional[tuple]
+    la: Optional[tuple]         # (workspace, split, half)
+    stats: Optional[torch.Tensor]   # (2, B, dim_model / 16) fp32
+    hook: object                # LLaMA.verify's attend_rows, carried to the attention stage; never switched on
+
+
 class LLaMA:
     """model::LLaMA (src/model/llama.cpp:11-165) restricted to the dynamic-batch decode step."""
     moe = False                 # any MoEEncoderLayer (set by __init__)
@@ -1310,31 +1328,99 @@ class LLaMA:
         return self._bufs[b]
 
     # ---- one decode step -----------------------------------------------------------------------
-    def encode(self, ctx: DynBatchContext, workspace=None, argmax_ws=None, gemv_only=False, skip_gemv=False, attend_rows=None):
-        """LLaMA::encode for a pure decode ("search") batch: returns logits (B, vocab) fp16.
-        gemv_only (bench.py's roofline leg): issue ONLY the four quantised projections of every layer, exactly as the step
-        launches them (fused norm / rotary + scatter / split merge / gated activation / residual), on whatever the buffers
-        hold -- no embedding, attention or lm_head; returns None.
-        skip_gemv (bench.py again): the complement -- everything BUT those projections (embedding, rope table, attention, lm_head,
-        greedy bookkeeping), so that step time - this = the projections' time inside the step.
-        attend_rows (LLaMA.verify): ctx is a row-expanded view -- several rows of one task posed as tasks of the scatter -- and
-        attend_rows(li, q, out, workspace) is layer li's attention over them, q / out (rows, H * D).  The routes that hard-wire one row
-        per task into the attention (the merging attn_out prologue, the in-launch merge) and the two bench legs are off with it."""
+    def _decode_route(self, ctx: DynBatchContext, b, gemv_only, skip_gemv, attend_rows, workspace=None) -> _DecodeRoute:
+        """The route of one decode step and its per-batch workspaces; refuses what encode cannot run before anything is launched.  Decided
+        anew by every call: the ZL_* switches and the context (max_len_buf, kv_quant, row_expanded) change under a live model."""
         c = self.cfg
-        b = ctx.tokens.numel()
-        if attend_rows is not None and (gemv_only or skip_gemv):
-            raise ops.ZLError("gemv_only / skip_gemv: not with an attention hook")
-        if self.moe and (gemv_only or skip_gemv):
+        if (attend_rows is not None or self.moe) and (gemv_only or skip_gemv):
             # the two legs split a step into "the four W4 projections" and the rest; an MoE layer's feed-forward is a router, a sort
             # and two grouped launches, which belong to neither side
-            raise ops.ZLError("gemv_only / skip_gemv: dense models only")
+            raise ops.ZLError("gemv_only / skip_gemv: " + ("not with an attention hook" if attend_rows is not None else "dense models only"))
         if ctx.steps_left <= 0 and not torch.cuda.is_current_stream_capturing():
             raise ops.ZLError("decode step past the end of the KV buffers (placement >= len_buf): grow the buffers first "
                               "(the reference asserts pos_buf < len_buf, ragged_buffer_kernel.cu:194-222)")
-        bufs = self._buffers(b)
         if workspace is None:
             workspace = self._bufs.setdefault(("ws", b, ctx.max_len_buf),
                                               ops.decode_attn_workspace(b, 1, c.num_heads, c.dim_head, ctx.max_len_buf, self.device))
+        env, first = os.environ.get, self.layers[0]
+        mfma_attn = c.dim_head == 128 and c.num_heads // c.num_kv_heads <= 16 and env("ZL_ATTN_MFMA", "1") != "0"
+        # qkv: the projection with rotary + KV scatter in its epilogue where it applies (zl_w4a16_qkv_rope_scatter; W8A8: the
+        # streaming kernel with the scale-back fused as well), else project_qkv and a rope / scatter launch
+        fuse_rope = mfma_attn and not ctx.kv_quant and not c.qk_norm and env("ZL_FUSE_QKV_ROPE", "1") != "0"
+        qkv, norm = "plain", None
+        if (fuse_rope and all(isinstance(l, EncoderLayer) and l.unfused is None and l.qkv.perm is None
+                              and isinstance(l.qkv.weight, ops.W4MWeight) for l in self.layers)
+                and ops.w4_qkv_rope_scatter_ok(b, c.dim_model, c.dim_head, norm=b <= max(8, _fused_norm_rows(first.qkv.weight)))):
+            qkv = "w4"
+        elif fuse_rope and b <= 32 and c.dim_head % 32 == 0 and all(isinstance(l, Int8EncoderLayer) and l._stream(b) for l in self.layers):
+            qkv = "w8"
+        # a few rows: the split merge of the decode attention rides in the attn_out projection's prologue (one launch less)
+        merge_plan = None
+        if qkv == "w4" and not self.tp and attend_rows is None and env("ZL_ATTN_MERGE", "1") != "0" and all(l.attn_out.perm is None for l in self.layers):
+            merge_plan = ops.attn_merge_plan(b, c.num_heads, c.num_kv_heads, c.dim_head, ctx.max_len_buf, first.attn_out.weight, c.torch_dtype)
+        # the split merge INSIDE the attention launch (last-arriving workgroup of a (task, kv head) pair, zl_decode_attn_la) wherever
+        # the step would otherwise run the two-launch path (split kernel + merge kernel): same records, same merge arithmetic, one
+        # launch less per layer.  Batch 1 keeps the merge in attn_out's prologue: there the in-launch merge was measured 1.4 us per
+        # layer SLOWER at the same split length and worse with finer splits (profiles/r05_attn_la_ab.txt).
+        # ZL_ATTN_LA: auto (default) / 0 off / 1 everywhere; ZL_ATTN_LA_SPLIT = keys per split (multiple of 32, 0 = the two-launch
+        # path's), ZL_ATTN_LA_HALF = 1 half-precision split records
+        la, la_mode = None, env("ZL_ATTN_LA", _ATTN_LA_DEFAULT)
+        if mfma_attn and not ctx.kv_quant and attend_rows is None and (la_mode == "1" or (la_mode == "auto" and merge_plan is None)):
+            la_split = int(env("ZL_ATTN_LA_SPLIT", "0") or 0)
+            eff = la_split or ops.decode_attn_la_split_len(b, c.num_kv_heads, ctx.max_len_buf)
+            if (ctx.max_len_buf + eff - 1) // eff <= 64:
+                # one block per (batch, power-of-two bucket of the buffer length): records are addressed by the launch's own split
+                # count, so a block sized for a longer buffer serves every shorter one; a captured graph keeps its block's address,
+                # hence buckets instead of regrowing in place -- at most log2 blocks per batch, < 2 x the largest (ADVICE r05)
+                key = ("la_ws", b, 1 << max(10, (ctx.max_len_buf - 1).bit_length()))
+                if key not in self._bufs:
+                    self._bufs[key] = ops.decode_attn_la_workspace(b, c.num_heads, c.num_kv_heads, key[2], self.device)
+                la = (self._bufs[key], la_split, env("ZL_ATTN_LA_HALF", "0") == "1" and c.torch_dtype == torch.float16)
+                merge_plan = None
+        # the rows' statistics travel with the residual stream (zl_w4_opts_t::row_ss / row_ss_out): attn_out and w_out leave per row
+        # and 16-column tile the sum of squares of what they store, the normalising projections (qkv, gate|up) read those 256 numbers
+        # per row instead of running -- or waiting for -- an RMSNorm pass over the rows: no stand-alone norm launch from 9 rows on, no
+        # register-resident norm prologue below.  ZL_ROW_SS=0 off; ZL_ROW_SS_MIN_M: rows it starts at
+        # (not with MoE layers: their feed-forward has no w_out to produce the statistics nor a gate|up projection to consume them)
+        stats = None
+        if (qkv == "w4" and (la is not None or attend_rows is not None) and not self.tp and not self.moe
+                and env("ZL_ROW_SS", "1") != "0" and int(env("ZL_ROW_SS_MIN_M", "8")) <= b <= 32 and c.dim_model % 1024 == 0
+                and all(l.attn_out.perm is None and l.w_out.perm is None and l.w_in_gated.perm is None for l in self.layers)
+                and ops.w4_row_ss_routes(b, [first.attn_out.weight, first.w_out.weight],
+                                         [(first.qkv.weight, True), (first.w_in_gated.weight, False)], self.device)):
+            stats = self._bufs.get(("row_ss", b))
+            if stats is None:
+                stats = self._bufs[("row_ss", b)] = torch.empty((2, b, c.dim_model // 16), dtype=torch.float32, device=self.device)
+        # attention split merge + attn_out + residual and ln_ff + gate|up + silu.mul in ONE launch (w4_engine.hip)
+        # (off for MoE models: the fused launch ends in the dense gate|up projection)
+        fuse_o_ff = (merge_plan is not None and merge_plan[2] and not self.moe and env("ZL_FUSE_O_GATEUP", "0") == "1" and ops.experimental_build()
+                     and all(l.w_in_gated.perm is None and isinstance(l.w_in_gated.weight, ops.W4MWeight) for l in self.layers))
+        # the two bench legs split the W4 route's step; the W8 route runs the whole step under either, the plain route under skip_gemv
+        if gemv_only and qkv == "plain":
+            raise ops.ZLError("gemv_only: the fused W4 decode route only")
+        if skip_gemv and qkv == "w4" and la is None and merge_plan is None:
+            raise ops.ZLError("skip_gemv: the fused W4 decode route with the merging attn_out projection only")
+        if qkv == "w4":                                   # 9..32 rows without the statistics: a launch of its own, or the deferred norm (ZL_DEFER_NORM)
+            norm = "row_ss" if stats is not None else "fused" if b <= max(8, _fused_norm_rows(first.qkv.weight)) else "launch"
+        if ctx.kv_quant or attend_rows is not None:
+            attn = "quant" if ctx.kv_quant else "hook"
+        elif la is not None or merge_plan is not None:
+            attn = "la" if la is not None else "splits"
+        else:                                             # never "valu_fused" for a row-expanded view: that launch orders a row's own K/V only
+            attn = "mqa" if qkv != "plain" or mfma_attn or ctx.row_expanded else "valu_fused"
+        return _DecodeRoute(qkv, norm, attn, "merge_gate_up" if fuse_o_ff else "merge" if merge_plan is not None else "linear", skip_attn=gemv_only and qkv == "w4" and not skip_gemv, skip_proj=skip_gemv and qkv == "w4",
+                            workspace=workspace, scale=1.0 / math.sqrt(c.dim_head), merge_plan=merge_plan, la=la, stats=stats, hook=attend_rows)
+
+    def encode(self, ctx: DynBatchContext, workspace=None, argmax_ws=None, gemv_only=False, skip_gemv=False, attend_rows=None):
+        """LLaMA::encode for a pure decode ("search") batch: returns logits (B, vocab) fp16.  The route is decided once (_decode_route), then
+        every layer runs three stages: qkv, attention, output + feed-forward.  gemv_only / skip_gemv (bench.py's legs, W4 route; DESIGN 4 has
+        the others): ONLY the four quantised projections of every layer, on whatever the buffers hold, returns None / all BUT those.
+        attend_rows (LLaMA.verify): ctx is a row-expanded view -- several rows of one task posed as tasks of the scatter -- and
+        attend_rows(li, q, out, workspace) is layer li's attention over them, q / out (rows, H * D)."""
+        c = self.cfg
+        b = ctx.tokens.numel()
+        r = self._decode_route(ctx, b, gemv_only, skip_gemv, attend_rows, workspace)
+        bufs = self._buffers(b)
         rs = c.rope_scaling
         kind = rs.get("rope_type", rs.get("type")) if rs else None
         if gemv_only:
@@ -1347,173 +1433,92 @@ class LLaMA:
         else:
             hidden = ops.embedding(ctx.tokens, self.token_embedding, c.scale_emb)  # token_embedding
             cos, sin = self._rope_tables(ctx.positions)                            # RopePreparer
-        scale = 1.0 / math.sqrt(c.dim_head)
-        mfma_attn = (c.dim_head == 128 and c.num_heads // c.num_kv_heads <= 16
-                     and os.environ.get("ZL_ATTN_MFMA", "1") != "0")
-        # fused qkv projection + rotary + KV scatter in the GEMV epilogue (zl_w4a16_qkv_rope_scatter) where it applies
-        fuse_qkv_rope = (mfma_attn and not ctx.kv_quant and os.environ.get("ZL_FUSE_QKV_ROPE", "1") != "0"
-                         and not c.qk_norm
-                         and all(isinstance(l, EncoderLayer) and l.unfused is None and l.qkv.perm is None
-                                 and isinstance(l.qkv.weight, ops.W4MWeight)
-                                 for l in self.layers)
-                         and ops.w4_qkv_rope_scatter_ok(b, c.dim_model, c.dim_head, norm=b <= max(8, _fused_norm_rows(self.layers[0].qkv.weight))))
-        fuse_qkv_rope_i8 = (mfma_attn and not ctx.kv_quant and b <= 32 and c.dim_head % 32 == 0 and not c.qk_norm
-                            and os.environ.get("ZL_FUSE_QKV_ROPE", "1") != "0"
-                            and all(isinstance(l, Int8EncoderLayer) and l._stream(b) for l in self.layers))
-        # a few rows: the split merge of the decode attention rides in the attn_out projection's prologue (one launch less)
-        merge_plan = None
-        if (fuse_qkv_rope and not self.tp and attend_rows is None and os.environ.get("ZL_ATTN_MERGE", "1") != "0"
-                and all(l.attn_out.perm is None for l in self.layers)):
-            merge_plan = ops.attn_merge_plan(b, c.num_heads, c.num_kv_heads, c.dim_head, ctx.max_len_buf,
-                                             self.layers[0].attn_out.weight, c.torch_dtype)
-        # round 5: the split merge INSIDE the attention launch (last-arriving workgroup of a (task, kv head) pair, zl_decode_attn_la)
-        # wherever the step would otherwise run the two-launch path (split kernel + merge kernel): same records, same merge
-        # arithmetic, one launch less per layer.  Batch 1 keeps the merge in attn_out's prologue: there the in-launch merge was
-        # measured 1.4 us per layer SLOWER at the same split length and worse with finer splits (profiles/r05_attn_la_ab.txt).
-        # ZL_ATTN_LA: auto (default) / 0 off / 1 everywhere; ZL_ATTN_LA_SPLIT = keys per split (multiple of 32, 0 = the two-launch
-        # path's), ZL_ATTN_LA_HALF = 1 half-precision split records
-        la = None
-        la_mode = os.environ.get("ZL_ATTN_LA", _ATTN_LA_DEFAULT)
-        if (mfma_attn and not ctx.kv_quant and c.dim_head == 128 and attend_rows is None
-                and (la_mode == "1" or (la_mode == "auto" and merge_plan is None))):
-            la_split = int(os.environ.get("ZL_ATTN_LA_SPLIT", "0") or 0)
-            la_half = os.environ.get("ZL_ATTN_LA_HALF", "0") == "1" and c.torch_dtype == torch.float16
-            eff = la_split or ops.decode_attn_la_split_len(b, c.num_kv_heads, ctx.max_len_buf)
-            if (ctx.max_len_buf + eff - 1) // eff <= 64:
-                # one block per (batch, power-of-two bucket of the buffer length): records are addressed by the launch's own split
-                # count, so a block sized for a longer buffer serves every shorter one; a captured graph keeps its block's address,
-                # hence buckets instead of regrowing in place -- at most log2 blocks per batch, < 2 x the largest
-                bucket = 1 << max(10, (ctx.max_len_buf - 1).bit_length())
-                key = ("la_ws", b, bucket)
-                if key not in self._bufs:
-                    self._bufs[key] = ops.decode_attn_la_workspace(b, c.num_heads, c.num_kv_heads, bucket, self.device)
-                la = (self._bufs[key], la_split, la_half)
-                merge_plan = None
-
-        # round 6: the rows' statistics travel with the residual stream (zl_w4_opts_t::row_ss / row_ss_out): attn_out and w_out leave
-        # per row and 16-column tile the sum of squares of what they store, the normalising projections (qkv, gate|up) read those
-        # 256 numbers per row instead of running -- or waiting for -- an RMSNorm pass over the rows: no stand-alone norm launch from
-        # 9 rows on, no register-resident norm prologue below.  ZL_ROW_SS=0 off; ZL_ROW_SS_MIN_M: rows it starts at
-        # (not with MoE layers: their feed-forward has no w_out to produce the statistics nor a gate|up projection to consume them)
-        stats = None
-        if (fuse_qkv_rope and (la is not None or attend_rows is not None) and not self.tp and not self.moe
-                and os.environ.get("ZL_ROW_SS", "1") != "0"
-                and int(os.environ.get("ZL_ROW_SS_MIN_M", "8")) <= b <= 32 and c.dim_model % 1024 == 0
-                and all(l.attn_out.perm is None and l.w_out.perm is None and l.w_in_gated.perm is None for l in self.layers)
-                and ops.w4_row_ss_routes(b, [self.layers[0].attn_out.weight, self.layers[0].w_out.weight],
-                                         [(self.layers[0].qkv.weight, True), (self.layers[0].w_in_gated.weight, False)], self.device)):
-            key = ("row_ss", b)
-            if key not in self._bufs:
-                self._bufs[key] = torch.empty((2, b, c.dim_model // 16), dtype=torch.float32, device=self.device)
-            stats = self._bufs[key]
-
-        def attend(li, out):
-            """decode attention of layer li over the tasks' buffers: bufs["q"] -> out (B, H * D)"""
-            if attend_rows is not None:
-                return attend_rows(li, bufs["q"], out, workspace)
-            q4 = bufs["q"].view(b, 1, c.num_heads, c.dim_head)
-            if la is not None:
-                return ops.decode_attention_la(q4, ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li], ctx.valid_lens, scale, ctx.max_len_buf,
-                                               c.num_kv_heads, la[0], out=out.view(b, 1, c.num_heads, c.dim_head), split_len=la[1], half=la[2])
-            return ops.multi_query_attention_rag_buffer(q4, ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li], None, scale, ctx.max_len_buf,
-                                                        c.num_kv_heads, valid_lens=ctx.valid_lens, out=out.view(b, 1, c.num_heads, c.dim_head),
-                                                        workspace=workspace)
-        # attention split merge + attn_out + residual and ln_ff + gate|up + silu.mul in ONE launch (w4_engine.hip)
-        # (off for MoE models: the fused launch ends in the dense gate|up projection)
-        fuse_o_ff = (merge_plan is not None and merge_plan[2] and not self.moe and os.environ.get("ZL_FUSE_O_GATEUP", "0") == "1"
-                     and ops.experimental_build()
-                     and all(l.w_in_gated.perm is None and isinstance(l.w_in_gated.weight, ops.W4MWeight) for l in self.layers))
-        if fuse_o_ff:
+        if r.out == "merge_gate_up":
             ops.engine_epoch_advance(self.device)
         trace = getattr(self, "trace_hidden", None)          # parity tests: the hidden rows entering every layer (eager runs only)
         for li, layer in enumerate(self.layers):
             if trace is not None and not torch.cuda.is_current_stream_capturing():
                 trace.append(hidden.clone())
-            if fuse_qkv_rope_i8:
-                # INT8 route: layernorm_quant, then the streaming W8A8 kernel with scale-back + rotary + KV scatter fused
-                _, xq, sx = ops.layernorm_quant(hidden, layer.ln_attn, c.eps)
-                ops.w8a8_qkv_rope_scatter(xq, sx, layer.qkv.stream_weight(), cos, sin, ctx.placement, ctx.buf_lens, ctx.k_addrs[li],
-                                          ctx.v_addrs[li], c.num_heads, c.num_kv_heads, c.dim_head, q_out=bufs["q"])
-                attend(li, bufs["attn"])
-                layer.attn_out_add(bufs["attn"], hidden)
-                layer.ff_add(hidden, c.eps, bufs["act"])
-                continue
-            if fuse_qkv_rope and skip_gemv and la is not None:
-                attend(li, bufs["attn"])
-                continue
-            if fuse_qkv_rope and skip_gemv:
-                if not merge_plan:
-                    raise ops.ZLError("skip_gemv: the fused W4 decode route with the merging attn_out projection only")
-                ops.decode_attention_splits(bufs["q"].view(b, c.num_heads, c.dim_head), ctx.buf_lens, ctx.k_addrs[li],
-                                            ctx.v_addrs[li], ctx.valid_lens, scale, ctx.max_len_buf, c.num_kv_heads, workspace)
-                continue
-            if fuse_qkv_rope and stats is not None:
-                if li == 0:
-                    ops.row_ss(hidden, out=stats[0])          # (the embedding's rows: the only statistics no projection produced)
-                ops.w4_qkv_rope_scatter(hidden, layer.qkv.weight, cos, sin, ctx.placement, ctx.buf_lens, ctx.k_addrs[li],
-                                        ctx.v_addrs[li], c.num_heads, c.num_kv_heads, c.dim_head, bias=layer.qkv.bias,
-                                        norm_weight=layer.ln_attn, norm_eps=c.eps, q_out=bufs["q"], row_ss=stats[0])
-                if not gemv_only:
-                    attend(li, bufs["attn"])
-                layer.attn_out.forward(bufs["attn"], residual=hidden, out=hidden, epilogue=ops.EPI_RESIDUAL, row_ss_out=stats[1])
-                ops.w4_linear(hidden, layer.w_in_gated.weight, bias=layer.w_in_gated.bias, out=bufs["act"], norm_weight=layer.ln_ff,
-                              norm_eps=c.eps, epilogue=ops.EPI_SILU_MUL, row_ss=stats[1])
-                layer.w_out.forward(bufs["act"], residual=hidden, out=hidden, epilogue=ops.EPI_RESIDUAL, row_ss_out=stats[0])
-                continue
-            if fuse_qkv_rope:
-                fused_norm = b <= max(8, _fused_norm_rows(layer.qkv.weight))    # 9..32 rows: the deferred norm (ZL_DEFER_NORM)
-                xin = hidden if fused_norm else ops.rmsnorm(hidden, layer.ln_attn, c.eps)
-                ops.w4_qkv_rope_scatter(xin, layer.qkv.weight, cos, sin, ctx.placement, ctx.buf_lens, ctx.k_addrs[li],
-                                        ctx.v_addrs[li], c.num_heads, c.num_kv_heads, c.dim_head, bias=layer.qkv.bias,
-                                        norm_weight=layer.ln_attn if fused_norm else None, norm_eps=c.eps, q_out=bufs["q"])
-                if merge_plan:
-                    if not gemv_only:
-                        ops.decode_attention_splits(bufs["q"].view(b, c.num_heads, c.dim_head), ctx.buf_lens, ctx.k_addrs[li],
-                                                    ctx.v_addrs[li], ctx.valid_lens, scale, ctx.max_len_buf, c.num_kv_heads, workspace)
-                    if fuse_o_ff and ops.w4_attn_out_gate_up(workspace, ctx.buf_lens, ctx.valid_lens, merge_plan, b, layer.attn_out.weight,
-                                                             hidden, layer.w_in_gated.weight, layer.ln_ff, c.eps, bufs["act"], li,
-                                                             bias_o=layer.attn_out.bias, bias_ff=layer.w_in_gated.bias):
-                        layer.w_out.forward(bufs["act"], residual=hidden, out=hidden, epilogue=ops.EPI_RESIDUAL)
-                        continue
-                    ops.w4_attn_out_merge(workspace, ctx.buf_lens, ctx.valid_lens, merge_plan, b, layer.attn_out.weight,
-                                          bias=layer.attn_out.bias, residual=hidden, out=hidden, epilogue=ops.EPI_RESIDUAL)
-                    layer.ff_add(hidden, c.eps, bufs["act"])
-                    continue
-                if not gemv_only:
-                    attend(li, bufs["attn"])
-                layer.attn_out_add(bufs["attn"], hidden)
-                layer.ff_add(hidden, c.eps, bufs["act"])
-                continue
-            if gemv_only:
-                raise ops.ZLError("gemv_only: the fused W4 decode route only")
-            layer.project_qkv(hidden, c.eps, out=bufs["qkv"])
-            self.apply_qk_norm(layer, bufs["qkv"])
-            if ctx.kv_quant:
-                # attention.cpp:652-676 + :725-745: rotate, quantise the new K/V rows into the u8 cache, attend over codes
-                ops.rope_quant_scatter_decode(cos, sin, bufs["qkv"], ctx.placement, ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li],
-                                              ctx.ks_addrs[li], ctx.vs_addrs[li], c.num_heads, c.num_kv_heads, c.dim_head,
-                                              q_out=bufs["q"])
-                ops.multi_query_attention_rag_buffer_quant(
-                    bufs["q"].view(b, 1, c.num_heads, c.dim_head), ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li], ctx.ks_addrs[li],
-                    ctx.vs_addrs[li], None, scale, ctx.max_len_buf, c.num_kv_heads, valid_lens=ctx.valid_lens,
-                    out=bufs["attn"].view(b, 1, c.num_heads, c.dim_head), workspace=workspace)
-            elif mfma_attn or attend_rows is not None or ctx.row_expanded:
-                # (a row-expanded view always comes here: the fused launch below orders a row's own K/V only)
-                # rope + KV scatter in one small launch, then the matrix-core decode attention (attention.hip:
-                # k_decode_attn_mfma; 11.0 / 18.7 / 39.8 us vs 11.9 / 24.0 / 49.7 us for the fused VALU kernel at batch 1 / 8 / 32)
-                ops.rope_scatter_decode(cos, sin, bufs["qkv"], ctx.placement, ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li],
-                                        c.num_heads, c.num_kv_heads, c.dim_head, q_out=bufs["q"])
-                attend(li, bufs["attn"])
-            else:
-                ops.decode_attention_fused(cos, sin, bufs["qkv"], ctx.placement, ctx.buf_lens, ctx.valid_lens, ctx.k_addrs[li],
-                                           ctx.v_addrs[li], c.num_heads, c.num_kv_heads, c.dim_head, scale, ctx.max_len_buf,
-                                           out=bufs["attn"], workspace=workspace)
-            layer.attn_out_add(bufs["attn"], hidden)
-            layer.ff_add(hidden, c.eps, bufs["act"])
+            if not r.skip_proj:
+                self._decode_qkv(r, ctx, bufs, li, layer, hidden, cos, sin)
+            if not r.skip_attn:
+                self._decode_attend(r, ctx, bufs, li, cos, sin)
+            if not r.skip_proj:
+                self._decode_out_ff(r, ctx, bufs, li, layer, hidden)
         if gemv_only:
             return None
         self.last_hidden = hidden                      # (B, dim_model) before the output norm: the parity tests read it
         return self._logits(hidden, bufs["logits"], argmax_ws)
+
+    def _decode_qkv(self, r, ctx, bufs, li, layer, hidden, cos, sin):
+        """stage 1: hidden -> rotated q in bufs["q"], the rows' K / V in the cache ("valu_fused": unrotated bufs["qkv"])"""
+        c = self.cfg
+        slots, heads = (ctx.placement, ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li]), (c.num_heads, c.num_kv_heads, c.dim_head)
+        if r.qkv == "w4":
+            if r.norm == "row_ss" and li == 0:
+                ops.row_ss(hidden, out=r.stats[0])          # (the embedding's rows: the only statistics no projection produced)
+            own = r.norm != "launch"                        # the launch normalises: in registers, or from the statistics
+            ops.w4_qkv_rope_scatter(hidden if own else ops.rmsnorm(hidden, layer.ln_attn, c.eps), layer.qkv.weight, cos, sin, *slots,
+                                    *heads, bias=layer.qkv.bias, norm_weight=layer.ln_attn if own else None, norm_eps=c.eps,
+                                    q_out=bufs["q"], row_ss=r.stats[0] if r.norm == "row_ss" else None)
+        elif r.qkv == "w8":
+            # layernorm_quant, then the streaming W8A8 kernel with scale-back + rotary + KV scatter fused
+            _, xq, sx = ops.layernorm_quant(hidden, layer.ln_attn, c.eps)
+            ops.w8a8_qkv_rope_scatter(xq, sx, layer.qkv.stream_weight(), cos, sin, *slots, *heads, q_out=bufs["q"])
+        else:
+            layer.project_qkv(hidden, c.eps, out=bufs["qkv"])
+            self.apply_qk_norm(layer, bufs["qkv"])
+            if r.attn == "quant":
+                # attention.cpp:652-676 + :725-745: rotate, quantise the new K/V rows into the u8 cache (the attention reads codes)
+                ops.rope_quant_scatter_decode(cos, sin, bufs["qkv"], *slots, ctx.ks_addrs[li], ctx.vs_addrs[li], *heads, q_out=bufs["q"])
+            elif r.attn != "valu_fused":
+                ops.rope_scatter_decode(cos, sin, bufs["qkv"], *slots, *heads, q_out=bufs["q"])
+
+    def _decode_attend(self, r, ctx, bufs, li, cos, sin):
+        """stage 2, the decode attention of layer li over the tasks' buffers: bufs["q"] -> bufs["attn"] (B, H * D); "splits": records in
+        the workspace, which the attn_out projection merges; "valu_fused": from bufs["qkv"], with the rope / scatter"""
+        c = self.cfg
+        k, v, shape = ctx.k_addrs[li], ctx.v_addrs[li], (bufs["q"].shape[0], 1, c.num_heads, c.dim_head)
+        if r.attn == "hook":
+            r.hook(li, bufs["q"], bufs["attn"], r.workspace)
+        elif r.attn == "la":
+            ops.decode_attention_la(bufs["q"].view(shape), ctx.buf_lens, k, v, ctx.valid_lens, r.scale, ctx.max_len_buf, c.num_kv_heads,
+                                    r.la[0], out=bufs["attn"].view(shape), split_len=r.la[1], half=r.la[2])
+        elif r.attn == "splits":
+            ops.decode_attention_splits(bufs["q"].view(shape[0], c.num_heads, c.dim_head), ctx.buf_lens, k, v, ctx.valid_lens, r.scale,
+                                        ctx.max_len_buf, c.num_kv_heads, r.workspace)
+        elif r.attn == "mqa":
+            # the matrix-core decode attention (attention.hip: k_decode_attn_mfma; 11.0 / 18.7 / 39.8 us vs 11.9 / 24.0 / 49.7 us for
+            # the fused VALU kernel at batch 1 / 8 / 32)
+            ops.multi_query_attention_rag_buffer(bufs["q"].view(shape), ctx.buf_lens, k, v, None, r.scale, ctx.max_len_buf, c.num_kv_heads,
+                                                 valid_lens=ctx.valid_lens, out=bufs["attn"].view(shape), workspace=r.workspace)
+        elif r.attn == "quant":
+            ops.multi_query_attention_rag_buffer_quant(bufs["q"].view(shape), ctx.buf_lens, k, v, ctx.ks_addrs[li], ctx.vs_addrs[li], None,
+                                                       r.scale, ctx.max_len_buf, c.num_kv_heads, valid_lens=ctx.valid_lens,
+                                                       out=bufs["attn"].view(shape), workspace=r.workspace)
+        else:
+            ops.decode_attention_fused(cos, sin, bufs["qkv"], ctx.placement, ctx.buf_lens, ctx.valid_lens, k, v, c.num_heads, c.num_kv_heads,
+                                       c.dim_head, r.scale, ctx.max_len_buf, out=bufs["attn"], workspace=r.workspace)
+
+    def _decode_out_ff(self, r, ctx, bufs, li, layer, hidden):
+        """stage 3: hidden += attn_out(attention), hidden += feed-forward(hidden)"""
+        if r.norm == "row_ss":                              # the three projections hand the rows' statistics on
+            layer.attn_out.forward(bufs["attn"], residual=hidden, out=hidden, epilogue=ops.EPI_RESIDUAL, row_ss_out=r.stats[1])
+            ops.w4_linear(hidden, layer.w_in_gated.weight, bias=layer.w_in_gated.bias, out=bufs["act"], norm_weight=layer.ln_ff,
+                          norm_eps=self.cfg.eps, epilogue=ops.EPI_SILU_MUL, row_ss=r.stats[1])
+            layer.w_out.forward(bufs["act"], residual=hidden, out=hidden, epilogue=ops.EPI_RESIDUAL, row_ss_out=r.stats[0])
+            return
+        if r.out == "linear":
+            layer.attn_out_add(bufs["attn"], hidden)
+        elif r.out == "merge_gate_up" and ops.w4_attn_out_gate_up(r.workspace, ctx.buf_lens, ctx.valid_lens, r.merge_plan, bufs["q"].shape[0],
+                                                                   layer.attn_out.weight, hidden, layer.w_in_gated.weight, layer.ln_ff, self.cfg.eps,
+                                                                   bufs["act"], li, bias_o=layer.attn_out.bias, bias_ff=layer.w_in_gated.bias):
+            layer.w_out.forward(bufs["act"], residual=hidden, out=hidden, epilogue=ops.EPI_RESIDUAL)
+            return
+        else:
+            ops.w4_attn_out_merge(r.workspace, ctx.buf_lens, ctx.valid_lens, r.merge_plan, bufs["q"].shape[0], layer.attn_out.weight,
+                                  bias=layer.attn_out.bias, residual=hidden, out=hidden, epilogue=ops.EPI_RESIDUAL)
+        layer.ff_add(hidden, self.cfg.eps, bufs["act"])
 
     def _logits(self, hidden, out=None, argmax_ws=None):
         """output_layernorm + lm_head (get_logits, src/model/llama.cpp:150-165).  MiniCPM divides the normalised
