@@ -968,6 +968,28 @@ int zl_spec_accept(const void* logits, int type, int64_t b, int64_t len_q, int64
  * ONE launch, one 1024-thread workgroup per task; ordinary vector stores only; no allocation, no sync, no workspace. */
 int zl_lookup_draft(int32_t* history, int64_t cap, int32_t* hist_lens, const int32_t* new_tokens, int64_t n_new, int64_t b, int64_t k,
                     int max_ngram, int min_ngram, int32_t* drafts, int32_t* match, zl_stream_t s);
+/* The stochastic pick of a decode step + zl_argmax_advance's bookkeeping in one launch (csrc/sample_rows.hip): temperature, top-k and
+ * top-p sampling per row under the reference's rule (src/generator/random_util.cu:83-199, which its scheduler runs on the host),
+ * evaluated in fp32 on fp32 probabilities.  logits (rows, n), row stride ld elements, type = ZL_T_F16 / ZL_T_BF16 (ZL_T_F32: ZL_EDTYPE
+ * -- the kernel selects on the 16-bit pattern); temperature / top_k / top_p (rows) fp32 / int32 / fp32.  Row r, T = temperature[r]:
+ *   T <= 0, or a row holding a NaN or an infinite maximum: zl_argmax_advance's pick.
+ *   otherwise p_i = exp((x_i - max) / T); the classes ordered by p descending, ties to the lower index (-0.0 == +0.0); c = the
+ *   inclusive running sum in that order, Z = c[n-1]; k = top_k[r] (k <= 0 or k >= n: off); cap = min(top_p[r], c[k-1] / Z) with
+ *   top-k on, top_p[r] without; v = u * cap * Z; the pick is the class at the first position i with c[i] >= v.  u = 0, top_p = 0 and
+ *   top_k = 1 give the arg-max; a class with p = 0 (a -inf logit) is never picked; the pick is always in [0, n).
+ * u: u_in[r] where u_in is given (fp32 in [0, 1); draws is left alone), else (w >> 8) * 2^-24 with w = word 0 of Philox4x32-10 under
+ * key (seeds[r] lo32, hi32) and counter (draws[r] lo32, hi32, 0, 0), and draws[r] += 1: a row's stream depends on its seed and the
+ * number of its draws alone.  seeds / draws (rows) int64.  u_out (rows, may be NULL) receives the u that was used.
+ * tokens[r] = next_tokens[r] = the pick, positions / placement / valid_lens += 1 (any of the five may be NULL; tokens or next_tokens
+ * must be given); logprobs[r] (may be NULL) = (x_pick - max) / T - log Z, the tempered, untruncated log-probability (T <= 0: with
+ * T = 1; a NaN / infinite row: NaN).
+ * Deterministic: masses are integer fixed point, histograms integer LDS atomics -- the pick does not depend on arrival order.
+ * ZL_EINVAL: null logits / temperature / top_k / top_p, neither seeds + draws nor u_in, neither tokens nor next_tokens;
+ * ZL_ESHAPE: rows < 1, n < 1, ld < n, n or rows >= 2^31; ZL_EDTYPE: not fp16 / bf16.
+ * ONE launch, one 1024-thread workgroup per row, no sort; ordinary vector stores only; no allocation, no sync, no workspace. */
+int zl_sample_advance(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
+                      const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
+                      int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out, zl_stream_t s);
 /* The logit post-processing of the reference's batch generator (src/generator/beam_util.cu, 3rd/bmengine/bmengine/functions/{softmax,topk}.cu):
  * what src/generator/batch_generator.cpp calls between a decode step and its host-side search, so that the py_export surface (zhilight.C)
  * links against this boundary.  Rows of n logits of type ZL_T_F16 / ZL_T_BF16 / ZL_T_F32; fp32 arithmetic, one rounding to T.

@@ -1,0 +1,139 @@
+"""The device sampler's cost (profiles/sample_rows.txt is this tool's output).
+
+  1. the launch alone (zl_sample_advance) at 1, 8 and 32 rows of 128 256 fp16 logits, next to zl_argmax_advance on the same rows:
+     every cell is a captured graph of `--launches` calls on the same logits -- WARM: a row is 250 KB and stays in L2 between the
+     calls of one replay, as it is behind the lm_head in a step -- the cells' replays alternated, device events around each.
+     Parameter sets: top-k 40 + top-p 0.95 at T = 0.8 (every pass runs), top-p alone (no count select), T = 0 with log-probabilities
+     (the arg-max and the Z pass), T = 0 without (the arg-max pass alone).
+  2. the whole step on the synthetic 32-layer model, 1 024 tokens of history, at batch 1, 8 and 32: a captured step_sample against a
+     captured step_greedy, replays alternated.  Neither step_greedy nor anything it runs is changed by the sampler, so the
+     step_greedy measured here is the one of the commit before it.
+
+usage: python tools/bench_sample.py [--launch-only | --step-only] [--reps 30] [--launches 100]"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from zhilight_amd import ops  # noqa: E402
+
+VOCAB = 128256
+SETS = [("T 0.8, top-k 40, top-p 0.95", 0.8, 40, 0.95, True), ("T 0.8, top-p 0.95", 0.8, 0, 0.95, True),
+        ("T 0, log-probabilities", 0.0, 0, 1.0, True), ("T 0, none", 0.0, 0, 1.0, False)]
+
+
+def _graph(fn):
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    g.replay()
+    torch.cuda.synchronize()
+    return g
+
+
+def _alternate(graphs, reps, warm=3):
+    """replays of the named graphs in turn, one pair of device events around each -> {name: [ms per replay]}"""
+    times = {n: [] for n in graphs}
+    for r in range(warm + reps):
+        for n, g in graphs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            g.replay()
+            e1.record()
+            e1.synchronize()
+            if r >= warm:
+                times[n].append(e0.elapsed_time(e1))
+    return times
+
+
+def _stats(ms, per):
+    us = sorted(t * 1e3 / per for t in ms)
+    return statistics.median(us), us[len(us) // 10], us[-1 - len(us) // 10]
+
+
+def launch_leg(dev, reps, launches):
+    print("# the launch alone, warm rows of %d fp16 logits (normal, sigma 2): us per launch, median [p10 .. p90] over %d alternated "
+          "replays of %d launches" % (VOCAB, reps, launches))
+    graphs, keep = {}, []
+    for rows in (1, 8, 32):
+        gen = torch.Generator(device="cpu").manual_seed(rows)
+        logits = (torch.randn((rows, VOCAB), generator=gen) * 2).to(torch.float16).to(dev)
+        tok = torch.zeros(rows, dtype=torch.int32, device=dev)
+
+        def greedy(logits=logits, tok=tok):
+            for _ in range(launches):
+                ops.argmax_advance(logits, tokens=tok)
+        graphs[(rows, "argmax_advance")] = _graph(greedy)
+        for name, t, k, p, lp in SETS:
+            f32 = dict(dtype=torch.float32, device=dev)
+            args = dict(temperature=torch.full((rows,), t, **f32), top_k=torch.full((rows,), k, dtype=torch.int32, device=dev),
+                        top_p=torch.full((rows,), p, **f32), seeds=torch.arange(rows, dtype=torch.int64, device=dev),
+                        draws=torch.zeros(rows, dtype=torch.int64, device=dev), tokens=tok,
+                        logprobs=torch.empty(rows, **f32) if lp else None)
+
+            def sample(logits=logits, args=args):
+                for _ in range(launches):
+                    ops.sample_advance(logits, **args)
+            graphs[(rows, name)] = _graph(sample)
+            keep.append(args)
+        keep.append((logits, tok))
+    t = _alternate(graphs, reps)
+    print("# rows | %-30s | us per launch" % "launch")
+    for (rows, name), ms in t.items():
+        print("  %4d | %-30s | %7.2f [%7.2f .. %7.2f]" % ((rows, name) + _stats(ms, launches)), flush=True)
+
+
+def step_leg(dev, reps):
+    from zhilight_amd.llama import LLaMA, ModelConfig, QuantConfig
+    cfg = ModelConfig.llama3_8b()
+    model = LLaMA(cfg, QuantConfig(5, 128), dev)
+    model.init_synthetic(seed=1234)
+    seq = 1024
+    print("# whole step, synthetic Llama-3-8B GPTQ, 32 layers, %d tokens of history; step_sample at T 0.8, top-k 40, top-p 0.95; ms per step, "
+          "median [p10 .. p90] over %d alternated replays" % (seq, reps))
+    print("#  B | step_greedy             | step_sample             | ratio of the medians | difference, us")
+    for b in (1, 8, 32):
+        len_buf = (seq + reps + 16 + 63) // 64 * 64
+        torch.manual_seed(7)
+        ctxs = {n: model.new_context(b, len_buf, seq, fill_random=True) for n in ("greedy", "sample")}
+        tok = torch.randint(0, cfg.vocab_size, (b,), device=dev, dtype=torch.int32)
+        for c in ctxs.values():
+            c.tokens.copy_(tok)
+        for t, src in zip(ctxs["sample"].kv, ctxs["greedy"].kv):
+            t.copy_(src)
+        state = model.new_sampler(ctxs["sample"], temperature=0.8, top_k=40, top_p=0.95, seed=5)
+        graphs = {"greedy": _graph(lambda: model.step_greedy(ctxs["greedy"])),
+                  "sample": _graph(lambda: model.step_sample(ctxs["sample"], state))}
+        t = _alternate(graphs, reps)
+        assert int(state.draws.min()) == 2 + 3 + reps                             # _graph's eager call and replay, the warm and timed replays
+        st = {n: tuple(v / 1e3 for v in _stats(t[n], 1)) for n in graphs}
+        cell = lambda s: "%7.3f [%6.3f .. %6.3f]" % s                            # noqa: E731
+        print("  %2d | %s | %s |        %6.4f        | %7.1f" % (b, cell(st["greedy"]), cell(st["sample"]), st["sample"][0] / st["greedy"][0],
+                                                                  (st["sample"][0] - st["greedy"][0]) * 1e3), flush=True)
+        del graphs, ctxs, state
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launch-only", action="store_true")
+    ap.add_argument("--step-only", action="store_true")
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--launches", type=int, default=100)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_sample: needs a GPU")
+    dev = torch.device("cuda:0")
+    if not a.step_only:
+        launch_leg(dev, a.reps, a.launches)
+    if not a.launch_only:
+        step_leg(dev, a.reps)
+
+
+if __name__ == "__main__":
+    main()

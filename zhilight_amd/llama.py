@@ -962,6 +962,19 @@ class LookupState:
     min_ngram: int
 
 
+@dataclass
+class SamplerState:
+    """The device-resident state of LLaMA.step_sample (LLaMA.new_sampler builds it; ops.sample_advance states the rule): per-task
+    sampling parameters, each task's generator -- its seed and the number of uniforms it has drawn -- and the last step's results."""
+    temperature: torch.Tensor   # (B) fp32    <= 0: greedy
+    top_k: torch.Tensor         # (B) int32   <= 0 or >= vocab: off
+    top_p: torch.Tensor         # (B) fp32    in [0, 1]
+    seeds: torch.Tensor         # (B) int64   the Philox key of the task
+    draws: torch.Tensor         # (B) int64   uniforms drawn so far = the Philox counter; bumped by the kernel
+    logprobs: torch.Tensor      # (B) fp32    the last step's picks' tempered log-probabilities
+    u: torch.Tensor             # (B) fp32    the last step's uniforms
+
+
 class _PromptRows:
     """The rows of one prompt-encode call -- one task's piece, or the pieces of several tasks back to back -- as the layer loop, the
     K/V scatter, the attention and the tail see them.  Built once per call, and the only place that knows whether the call has one
@@ -2066,7 +2079,7 @@ class LLaMA:
         (ops.lookup_draft) appends the tokens the step emitted to the tasks' histories and drafts the next step's tokens into
         state.drafts.  No host round trip; capturable after one eager call (verify's rule), and a replay carries ctx and state
         forward together.  Returns verify's SpecResult.
-        A caller that interleaves step_greedy keeps the state in step by feeding the token that step left pending:
+        A caller that interleaves step_greedy or step_sample keeps the state in step by feeding the token that step left pending:
         ops.lookup_draft(state.history, state.hist_lens, state.k, state.max_ngram, state.min_ngram,
         new_tokens=ctx.tokens.view(B, 1), drafts=state.drafts, match=state.match)."""
         b = ctx.tokens.numel()
@@ -2098,6 +2111,79 @@ class LLaMA:
         stats = {"steps": steps, "emitted": [len(o) for o in out], "accepted": accepted,
                  "mean_accepted": sum(accepted) / (steps * b) if steps else 0.0}
         return [o[:max_new_tokens] for o in out], stats
+
+    # ---- sampling steps -----------------------------------------------------------------------------
+    def new_sampler(self, ctx: DynBatchContext, temperature=1.0, top_k=0, top_p=1.0, seed=0) -> SamplerState:
+        """The state for step_sample.  temperature / top_k / top_p / seed: a scalar for every task or a sequence of B values.
+        temperature 0 = greedy; top_k 0 = off; top_p 1 = off; a scalar seed s gives task j the seed s + j, so the tasks draw different
+        streams and a task's stream does not depend on the rest of the batch."""
+        b, dev = ctx.tokens.numel(), ctx.tokens.device
+
+        def per_task(v, what):
+            if torch.is_tensor(v):
+                v = v.tolist()
+            if isinstance(v, (list, tuple, np.ndarray)):
+                v = [x.item() if hasattr(x, "item") else x for x in v]
+                if len(v) != b:
+                    raise ops.ZLError(f"new_sampler: {b} tasks, {len(v)} values of {what}")
+                return v, False
+            return [v] * b, True
+
+        t, _ = per_task(temperature, "temperature")
+        k, _ = per_task(top_k, "top_k")
+        p, _ = per_task(top_p, "top_p")
+        sd, scalar_seed = per_task(seed, "seed")
+        if any(not (float(v) >= 0.0 and math.isfinite(float(v))) for v in t):
+            raise ops.ZLError("new_sampler: temperature >= 0 (0 = greedy)")
+        if any(int(v) != v or int(v) < 0 or int(v) >= 1 << 31 for v in k):
+            raise ops.ZLError("new_sampler: top_k is an integer >= 0 (0 = off)")
+        if any(not 0.0 <= float(v) <= 1.0 for v in p):
+            raise ops.ZLError("new_sampler: top_p in [0, 1]")
+        if any(int(v) != v for v in sd):
+            raise ops.ZLError("new_sampler: seed is an integer")
+        sd = [int(v) + (j if scalar_seed else 0) for j, v in enumerate(sd)]
+        sd = [((v + (1 << 63)) % (1 << 64)) - (1 << 63) for v in sd]        # the 64 bits of the key, as int64
+        return SamplerState(temperature=torch.tensor([float(v) for v in t], dtype=torch.float32, device=dev),
+                            top_k=torch.tensor([int(v) for v in k], dtype=torch.int32, device=dev),
+                            top_p=torch.tensor([float(v) for v in p], dtype=torch.float32, device=dev),
+                            seeds=torch.tensor(sd, dtype=torch.int64, device=dev), draws=torch.zeros(b, dtype=torch.int64, device=dev),
+                            logprobs=torch.zeros(b, dtype=torch.float32, device=dev), u=torch.zeros(b, dtype=torch.float32, device=dev))
+
+    def step_sample(self, ctx: DynBatchContext, state: SamplerState):
+        """One sampling decode step entirely on the device (graph-capturable after one eager call, no host round trip): encode, then
+        ONE launch (ops.sample_advance) picks every task's token under its temperature / top-k / top-p from its own Philox stream
+        and advances the batch state, as step_greedy's pick + advance launch does above four rows -- here at every batch size and
+        under TP, where every rank samples the same gathered rows with the same generator state.  state.logprobs / state.u hold the
+        picks' tempered log-probabilities and the uniforms used; state.draws has advanced by one.  Returns (logits, next_tokens
+        int64).  Penalties are the caller's (ops.repetition_penalty on the returned logits changes the NEXT call's input only)."""
+        b = ctx.tokens.numel()
+        if state.temperature.numel() != b:
+            raise ops.ZLError("step_sample: the state belongs to another batch size")
+        logits = self.encode(ctx)
+        key = ("next", b)
+        if key not in self._bufs:
+            self._bufs[key] = torch.empty(b, dtype=torch.int64, device=self.device)
+        nxt = self._bufs[key]
+        ops.sample_advance(logits, state.temperature, state.top_k, state.top_p, seeds=state.seeds, draws=state.draws, tokens=ctx.tokens,
+                           positions=ctx.positions, placement=ctx.placement, valid_lens=ctx.valid_lens, next_tokens=nxt,
+                           logprobs=state.logprobs, u_out=state.u)
+        ctx.steps_left -= 1
+        return logits, nxt
+
+    def generate_sample(self, ctx: DynBatchContext, state: SamplerState, max_new_tokens):
+        """The eager convenience loop around step_sample: up to max_new_tokens steps, fewer where the KV buffers run out
+        (ctx.steps_left).  Returns (tokens (B, steps) int64, logprobs (B, steps) fp32): what every task emitted behind its pending
+        ctx.tokens entry of the time of the call, and each token's tempered log-probability.  One read-back at the end."""
+        b = ctx.tokens.numel()
+        toks, lps = [], []
+        for _ in range(max(0, min(int(max_new_tokens), ctx.steps_left))):
+            _, nxt = self.step_sample(ctx, state)
+            toks.append(nxt.clone())
+            lps.append(state.logprobs.clone())
+        if not toks:
+            return (torch.empty((b, 0), dtype=torch.int64, device=ctx.tokens.device),
+                    torch.empty((b, 0), dtype=torch.float32, device=ctx.tokens.device))
+        return torch.stack(toks, dim=1), torch.stack(lps, dim=1)
 
     def advance(self, ctx: DynBatchContext, next_tokens: torch.Tensor):
         """Device-side bookkeeping between steps (what fill_search_tokens does on the host in the

@@ -901,6 +901,63 @@ def lookup_draft(history, hist_lens, k, max_ngram=3, min_ngram=1, new_tokens=Non
     return drafts.view(b, k), match.view(b, 2)
 
 
+def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=None, tokens=None, positions=None, placement=None,
+                   valid_lens=None, next_tokens=None, logprobs=None, u_out=None):
+    """The stochastic pick over whole logit rows and the batch state's advance in one launch (zl_sample_advance): logits (rows, n)
+    fp16 / bf16 with unit column stride; temperature (rows) fp32, top_k (rows) int32 (<= 0 or >= n: off), top_p (rows) fp32 in [0, 1]
+    -- per row.  A row with temperature <= 0 takes argmax_advance's pick; otherwise p = exp((x - max) / T), the classes ordered by p
+    descending (ties to the lower index), c their running sum, Z its end, cap = min(top_p, c[k-1] / Z) (top_p without top-k), and the
+    pick is the first class of the order with c >= u * cap * Z.  u (rows) fp32 in [0, 1) gives the uniforms; without it they are
+    Philox4x32-10 words keyed by seeds[r] (int64) and counted by draws[r] (int64), and draws += 1.  tokens <- pick (int32),
+    next_tokens <- pick (int64), positions / placement / valid_lens += 1 (each optional, tokens or next_tokens required); logprobs
+    (rows) fp32 <- the pick's tempered log-probability (T <= 0: at T = 1); u_out (rows) fp32 <- the uniforms used.  Returns
+    next_tokens if given, else tokens."""
+    if not all(torch.is_tensor(t) for t in (logits, temperature, top_k, top_p)):
+        raise ZLError("sample_advance: logits, temperature, top_k and top_p are tensors")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise ZLError("sample_advance: (rows, n) logits with unit column stride")
+    if logits.dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError(f"sample_advance: fp16 or bf16 logits, not {logits.dtype} (the selection works on the 16-bit pattern)")
+    rows, n = logits.shape
+    if n >= 1 << 31:
+        raise ZLError("sample_advance: a row holds fewer than 2^31 classes")
+
+    def per_row(t, dtype, what):
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.dim() == 1 and t.numel() == rows and t.is_contiguous()):
+            raise ZLError(f"sample_advance: {what}: contiguous {str(dtype).replace('torch.', '')} of length rows")
+
+    per_row(temperature, torch.float32, "temperature")
+    per_row(top_k, torch.int32, "top_k")
+    per_row(top_p, torch.float32, "top_p")
+    if u is not None:
+        per_row(u, torch.float32, "u")
+    elif seeds is None or draws is None:
+        raise ZLError("sample_advance: give seeds and draws, or u")
+    if u is None or seeds is not None:
+        per_row(seeds, torch.int64, "seeds")
+    if u is None or draws is not None:
+        per_row(draws, torch.int64, "draws")
+    if tokens is None and next_tokens is None:
+        raise ZLError("sample_advance: give tokens or next_tokens")
+    for t, what in ((tokens, "tokens"), (positions, "positions"), (placement, "placement"), (valid_lens, "valid_lens")):
+        if t is not None:
+            per_row(t, torch.int32, what)
+    if next_tokens is not None:
+        per_row(next_tokens, torch.int64, "next_tokens")
+    if logprobs is not None:
+        per_row(logprobs, torch.float32, "logprobs")
+    if u_out is not None:
+        per_row(u_out, torch.float32, "u_out")
+    others = (temperature, top_k, top_p, seeds, draws, u, tokens, positions, placement, valid_lens, next_tokens, logprobs, u_out)
+    if not logits.is_cuda or any(t is not None and t.device != logits.device for t in others):
+        raise ZLError("sample_advance: CUDA logits, every other tensor on the logits' device")
+    code = 2 if logits.dtype == torch.float16 else 6
+    check(lib().zl_sample_advance(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k), _p(top_p),
+                                  _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement), _p(valid_lens), _p(next_tokens),
+                                  _p(logprobs), _p(u_out), _stream()), "sample_advance")
+    return next_tokens if next_tokens is not None else tokens
+
+
 # --------------------------------------------------------------------------------------------------
 # scoring: functions::Gemm + nn::log_prob_raw / greedy_match_raw (src/nn/functions/cross_entropy.cu:7-69, 358-403) without the
 # (M, N) logits: csrc/lm_head_score.hip
