@@ -990,6 +990,31 @@ int zl_lookup_draft(int32_t* history, int64_t cap, int32_t* hist_lens, const int
 int zl_sample_advance(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
                       const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
                       int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out, zl_stream_t s);
+/* The acceptance of a speculative step under sampling + the roll-back of the batch state (csrc/sample_rows.hip): zl_spec_accept with
+ * zl_sample_advance's pick in the arg-max's place.  The drafter is deterministic, so its proposal distribution is a point mass on the
+ * draft d and the optimal speculative-sampling rule -- accept d with probability p(d), on rejection draw from p with d removed and
+ * renormalised -- is: draw x ~ p with the task's next uniform, accept iff x == d, otherwise emit x.  No new probability arithmetic.
+ * logits: (b * len_q, n) rows, task-major, row stride ld elements, type = ZL_T_F16 / ZL_T_BF16; drafts (b, len_q - 1) int32,
+ * 2 <= len_q <= 32.  temperature / top_k / top_p / seeds / draws are PER TASK (b); u_in, u_out, out_tokens, out_logprobs are PER ROW
+ * (b, len_q); accepted, logprobs and the four state arrays are per task.
+ * picks[t, i] = zl_sample_advance's pick of row (t, i) under task t's parameters -- every branch of that rule unchanged -- with the
+ * uniform u_in[t, i] where u_in is given (draws is left alone), else the Philox word under key seeds[t] and counter draws[t] + i.
+ * accepted[t] = the largest a <= len_q - 1 with drafts[t, j] == picks[t, j] for all j < a (a draft outside [0, n), the drafter's -1,
+ * is never accepted: a pick lies in [0, n)).  out_tokens[t] = picks[t, :a + 1], -1 behind; out_logprobs[t, i] = the tempered,
+ * untruncated log-probability of picks[t, i] (zl_sample_advance's definition) for i <= a, NaN behind; logprobs[t] = out_logprobs[t, a];
+ * tokens[t] = picks[t, a]; positions / placement / valid_lens += a + 1; draws[t] += a + 1 where the generator was used: the step
+ * consumes one draw per emitted token, so the emitted sequence is the same function of (logits, seed, tokens emitted so far) as
+ * zl_sample_advance's, step by step.  u_out[t, i] = the uniform of every row, the rows behind the rejection included.
+ * The four state arrays, out_logprobs, logprobs and u_out may be NULL -- logprobs is read from out_logprobs and needs it.
+ * ZL_EINVAL: null logits / temperature / top_k / top_p / drafts / accepted / out_tokens, neither seeds + draws nor u_in, logprobs
+ * without out_logprobs; ZL_ESHAPE: b < 1, len_q < 2, len_q > 32, n < 1, ld < n, n or b * len_q >= 2^31; ZL_EDTYPE: not fp16 / bf16.
+ * TWO launches, as zl_spec_accept and for its reason: zl_sample_advance's kernel in its per-row form over b * len_q workgroups (it
+ * writes neither draws nor the state), then one thread per task for the prefix match, the padding, the state and the draws.
+ * Ordinary vector stores only; no allocation, no sync, no workspace. */
+int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
+                          const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
+                          const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
+                          int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out, zl_stream_t s);
 /* The logit post-processing of the reference's batch generator (src/generator/beam_util.cu, 3rd/bmengine/bmengine/functions/{softmax,topk}.cu):
  * what src/generator/batch_generator.cpp calls between a decode step and its host-side search, so that the py_export surface (zhilight.C)
  * links against this boundary.  Rows of n logits of type ZL_T_F16 / ZL_T_BF16 / ZL_T_F32; fp32 arithmetic, one rounding to T.

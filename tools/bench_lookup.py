@@ -11,8 +11,17 @@
      launches) against verify on fixed drafts and against step_greedy, captured graphs, replays alternated.  Break-even accepted
      drafts per step = t / t_step_greedy - 1.  The histories repeat a 64-id motif, so the drafter matches (and extends to max_ngram)
      at every step; what the synthetic weights then accept is printed for what it is -- it says nothing about real text.
+  --sampler: the speculative SAMPLING step instead (profiles/spec_sample.txt is this leg's output), at the same (B, K) rows:
+  3. the accept alone: ops.spec_sample_accept (T 0.8, top-k 40, top-p 0.95, log-probabilities and uniforms written) against
+     ops.spec_accept and against ops.sample_advance on the same B x (K + 1) warm rows of 128 256 fp16 logits, captured graphs of
+     `--launches` calls, replays alternated.
+  4. the whole step: step_lookup(sampler=) against step_sample -- what a sampling user runs today -- and against the greedy
+     step_lookup and step_greedy, all four in ONE alternated run.  Break-even accepted drafts per step under sampling =
+     t(step_lookup(sampler)) / t(step_sample) - 1, beside the greedy t(step_lookup) / t(step_greedy) - 1.  Under T > 0 a lookup
+     draft is accepted with probability p(draft) per position, so the synthetic weights accept next to nothing here; that figure
+     says nothing about real text either way.
 
-usage: python tools/bench_lookup.py [--launch-only | --step-only] [--reps 30] [--launches 200]"""
+usage: python tools/bench_lookup.py [--launch-only | --step-only] [--sampler] [--reps 30] [--launches 200]"""
 import argparse
 import os
 import statistics
@@ -139,16 +148,131 @@ def step_leg(dev, reps, rows):
           % (worst, "met" if worst < 1.0 else "MISSED"))
 
 
+VOCAB = 128256
+SAMPLER = dict(temperature=0.8, top_k=40, top_p=0.95)
+
+
+def accept_leg(dev, reps, launches, rows):
+    print("# the accept alone, warm rows of %d fp16 logits (normal, sigma 2): us per call, median [p10 .. p90] over %d alternated replays of %d "
+          "calls; spec_sample_accept and sample_advance at T %.1f, top-k %d, top-p %.2f with log-probabilities"
+          % (VOCAB, reps, launches, SAMPLER["temperature"], SAMPLER["top_k"], SAMPLER["top_p"]))
+    print("#  B  K rows | spec_accept (2 launches)   | sample_advance (1 launch)  | spec_sample_accept (2)     | over spec_accept, us | over "
+          "sample_advance, us")
+    i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+    graphs, keep = {}, []
+    for b, k in rows:
+        len_q = k + 1
+        m = b * len_q
+        gen = torch.Generator(device="cpu").manual_seed(100 * b + k)
+        logits = (torch.randn((m, VOCAB), generator=gen) * 2).to(torch.float16).to(dev)
+        drafts = logits.view(b, len_q, VOCAB)[:, :k].float().argmax(dim=2).to(torch.int32).contiguous()     # the greedy path accepts every draft
+        acc, out, tok = torch.empty(b, **i32), torch.empty((b, len_q), **i32), torch.zeros(b, **i32)
+        per = lambda count: dict(temperature=torch.full((count,), SAMPLER["temperature"], **f32),           # noqa: E731
+                                 top_k=torch.full((count,), SAMPLER["top_k"], **i32), top_p=torch.full((count,), SAMPLER["top_p"], **f32),
+                                 seeds=torch.arange(count, dtype=torch.int64, device=dev), draws=torch.zeros(count, dtype=torch.int64, device=dev))
+        task, row = per(b), per(m)
+        row.update(tokens=torch.zeros(m, **i32), logprobs=torch.empty(m, **f32), u_out=torch.empty(m, **f32))
+        task.update(tokens=tok, accepted=acc, out_tokens=out, out_logprobs=torch.empty((b, len_q), **f32), logprobs=torch.empty(b, **f32),
+                    u_out=torch.empty((b, len_q), **f32))
+
+        def greedy(logits=logits, drafts=drafts, tok=tok, acc=acc, out=out):
+            for _ in range(launches):
+                ops.spec_accept(logits, drafts, tokens=tok, accepted=acc, out_tokens=out)
+
+        def plain(logits=logits, row=row):
+            for _ in range(launches):
+                ops.sample_advance(logits, **row)
+
+        def sampled(logits=logits, drafts=drafts, task=task):
+            for _ in range(launches):
+                ops.spec_sample_accept(logits, drafts, **task)
+        graphs[(b, k, "greedy")], graphs[(b, k, "plain")], graphs[(b, k, "sampled")] = _graph(greedy), _graph(plain), _graph(sampled)
+        keep.append((logits, drafts, task, row))
+    t = _alternate(graphs, reps)
+    for b, k in rows:
+        st = {n: _stats(t[(b, k, n)], launches) for n in ("greedy", "plain", "sampled")}
+        cell = lambda s: "%7.2f [%7.2f .. %7.2f]" % s                                # noqa: E731
+        print("  %2d %2d  %3d | %s | %s | %s |       %7.2f        |      %7.2f" % (
+            b, k, b * (k + 1), cell(st["greedy"]), cell(st["plain"]), cell(st["sampled"]), st["sampled"][0] - st["greedy"][0],
+            st["sampled"][0] - st["plain"][0]), flush=True)
+
+
+def sampler_step_leg(dev, reps, rows):
+    from zhilight_amd.llama import LLaMA, ModelConfig, QuantConfig
+    cfg = ModelConfig.llama3_8b()
+    model = LLaMA(cfg, QuantConfig(5, 128), dev)
+    model.init_synthetic(seed=1234)
+    seq = 1024
+    print("# whole step, synthetic Llama-3-8B GPTQ, 32 layers, %d tokens of history (a 64-id motif repeated); verify(attn=\"auto\"); sampler: "
+          "T %.1f, top-k %d, top-p %.2f; ms per step, median [p10 .. p90] over %d alternated replays of the four steps"
+          % (seq, SAMPLER["temperature"], SAMPLER["top_k"], SAMPLER["top_p"], reps))
+    print("#  B  K rows | step_greedy             | step_sample             | step_lookup             | step_lookup(sampler)    | sampler over "
+          "greedy lookup, us | break-even accepted drafts: greedy  sampling | accepted per step by the synthetic weights: greedy  sampling")
+    worst = {"greedy": (0.0, None), "sampling": (0.0, None)}
+    missed = []
+    for b, k in rows:
+        len_q = k + 1
+        len_buf = (seq + (reps + 8) * len_q + 63) // 64 * 64
+        torch.manual_seed(7)
+        names = ("step", "sample", "lookup", "lookup_s")
+        ctxs = {n: model.new_context(b, len_buf, seq, fill_random=True) for n in names}
+        motif = torch.randint(0, cfg.vocab_size, (b, 64), dtype=torch.int32)
+        for c in ctxs.values():
+            c.tokens.copy_(motif[:, 0])                                              # the pending token continues the motif
+        for n in names[1:]:
+            for t, src in zip(ctxs[n].kv, ctxs["step"].kv):
+                t.copy_(src)
+        hist = [motif[j].repeat(seq // 64) for j in range(b)]
+        look = {n: model.new_lookup(ctxs[n], hist, k) for n in ("lookup", "lookup_s")}
+        len0 = look["lookup"].hist_lens.clone()
+        samp = {n: model.new_sampler(ctxs[n], seed=5, **SAMPLER) for n in ("sample", "lookup_s")}
+        model.step_lookup(ctxs["lookup"], look["lookup"])                            # eager: the row-expanded tables, the sampler's row buffers
+        model.step_lookup(ctxs["lookup_s"], look["lookup_s"], sampler=samp["lookup_s"])
+        graphs = {"step": _graph(lambda: model.step_greedy(ctxs["step"])),
+                  "sample": _graph(lambda: model.step_sample(ctxs["sample"], samp["sample"])),
+                  "lookup": _graph(lambda: model.step_lookup(ctxs["lookup"], look["lookup"])),
+                  "lookup_s": _graph(lambda: model.step_lookup(ctxs["lookup_s"], look["lookup_s"], sampler=samp["lookup_s"]))}
+        t = _alternate(graphs, reps)
+        calls = 1 + 2 + 3 + reps                                                     # eager, _graph's two, the warm and timed replays
+        acc = {n: float((look[n].hist_lens - len0).sum()) / (calls * b) - 1 for n in look}
+        assert int(samp["lookup_s"].draws.sum()) == int((look["lookup_s"].hist_lens - len0).sum())      # one draw per emitted token
+        st = {n: tuple(v / 1e3 for v in _stats(t[n], 1)) for n in graphs}
+        cell = lambda s: "%7.3f [%6.3f .. %6.3f]" % s                                # noqa: E731
+        be = {"greedy": st["lookup"][0] / st["step"][0] - 1, "sampling": st["lookup_s"][0] / st["sample"][0] - 1}
+        for n in be:
+            if be[n] > worst[n][0]:
+                worst[n] = (be[n], (b, k))
+        if be["sampling"] >= 1.0:
+            missed.append((b, k))
+        print("  %2d %2d  %3d | %s | %s | %s | %s |            %7.1f          |                            %5.2f   %5.2f     |"
+              "                                              %.2f    %.2f" % (
+                  b, k, b * len_q, cell(st["step"]), cell(st["sample"]), cell(st["lookup"]), cell(st["lookup_s"]),
+                  (st["lookup_s"][0] - st["lookup"][0]) * 1e3, be["greedy"], be["sampling"], acc["lookup"], acc["lookup_s"]), flush=True)
+        del graphs, ctxs, look, samp
+        torch.cuda.empty_cache()
+    print("# break-even accepted drafts per step under sampling, t(step_lookup(sampler)) / t(step_sample) - 1: at most %.2f at (B, K) = %s; "
+          "greedy, t(step_lookup) / t(step_greedy) - 1: at most %.2f at %s" % (worst["sampling"] + worst["greedy"]))
+    print("# the yardstick, below 1.0 at every shape: %s" % ("met" if not missed else "MISSED at (B, K) = %s: speculative sampling should not be "
+                                                             "used there" % missed))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launch-only", action="store_true")
     ap.add_argument("--step-only", action="store_true")
+    ap.add_argument("--sampler", action="store_true", help="the speculative sampling legs (3 and 4) instead of the greedy ones")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--launches", type=int, default=200)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_lookup: needs a GPU")
     dev = torch.device("cuda:0")
+    if a.sampler:
+        if not a.step_only:
+            accept_leg(dev, a.reps, a.launches, STEP_ROWS)
+        if not a.launch_only:
+            sampler_step_leg(dev, a.reps, STEP_ROWS)
+        return
     if not a.step_only:
         launch_leg(dev, a.reps, a.launches)
     if not a.launch_only:

@@ -3,6 +3,15 @@
 //                       (src/generator/random_util.cu:83-199: sort the probabilities descending, stable; cap = min(top_p, c[k-1] / Z);
 //                       the first sorted class whose running sum reaches u * cap * Z), a Philox4x32-10 uniform per row and call, the
 //                       pick's log-probability, and zl_argmax_advance's bookkeeping -- one launch.
+//   zl_spec_sample_accept   the acceptance of a speculative step under sampling.  The drafter is deterministic, so its proposal is a
+//                       point mass on the draft d, and the optimal speculative-sampling rule (Leviathan et al., ICML'23; Chen et al.,
+//                       2023) reduces to: accept d with probability p(d), on rejection draw from p with d removed and renormalised
+//                       -- which is: draw x ~ p with the task's next uniform, accept iff x == d, otherwise emit x.  So every row
+//                       (t, i) of the step takes zl_sample_advance's pick under task t's parameters with the uniform of counter
+//                       draws[t] + i, and the step consumes accepted + 1 draws: the emitted tokens are the same function of
+//                       (logits, seed, tokens emitted so far) as without speculation.  TWO launches, as zl_spec_accept and for its
+//                       reason: the sampling kernel in its per-row form (SPEC: no state, no draws written), then one thread per task
+//                       for the prefix match, the padding, the state and the draws.
 // The reference sorts on the host.  Nothing is sorted here: the logits are 16-bit, so a row holds at most 65 536 distinct values, a
 // class's probability depends on its value alone, and the sorted order is "larger value, then lower index".  Both selections are
 // radix selects on the monotone 16-bit key of the value, high byte then low byte: top-k selects by count, the nucleus by mass, and the
@@ -245,8 +254,11 @@ __device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n
     }
 }
 
-template <bool BF>
-__global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __restrict__ x, int64_t ld, int n, const float* __restrict__ temperature,
+// SPEC (zl_spec_sample_accept's first launch): row r belongs to task r / len_q -- its parameters, seed and draw count are the task's,
+// its counter is draws[task] + r % len_q -- and the epilogue writes the row's pick, log-probability and uniform only: draws and the
+// batch state are the second launch's.  u_in / u_out / tokens / logprobs stay per row.  !SPEC: len_q is not read
+template <bool BF, bool SPEC>
+__global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __restrict__ x, int64_t ld, int n, int len_q, const float* __restrict__ temperature,
                                                              const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
                                                              const int64_t* __restrict__ seeds, int64_t* __restrict__ draws,
                                                              const float* __restrict__ u_in, int32_t* __restrict__ tokens,
@@ -262,6 +274,7 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
     __shared__ u64 s_z, s_ck, s_v;
     __shared__ int s_j, s_pick;
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int pr = SPEC ? r / len_q : r;                                // the row of the parameters and of the generator
     const uint16_t* row = x + (size_t)r * ld;
 
     // ---- the uniform of this row and call ---------------------------------------------------------------------------------------
@@ -270,9 +283,9 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
         if (u_in) {
             u = u_in[r];
         } else {
-            const u64 seed = (u64)seeds[r], ctr = (u64)draws[r];
+            const u64 seed = (u64)seeds[pr], ctr = (u64)draws[pr] + (SPEC ? (u64)(r - pr * len_q) : 0);
             u = (float)(philox_word0((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)seed, (uint32_t)(seed >> 32)) >> 8) * 0x1p-24f;
-            draws[r] = (int64_t)(ctr + 1);
+            if (!SPEC) draws[r] = (int64_t)(ctr + 1);
         }
         if (u_out) u_out[r] = u;
         u = u >= 0.f ? (u < 1.f ? u : 1.f - 0x1p-24f) : 0.f;            // a caller's u outside [0, 1) (or a NaN) is clamped, never trusted
@@ -298,7 +311,7 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
     const uint32_t kmax = (uint32_t)(best >> 32);
     const int amax = (int)~(uint32_t)best;
 
-    const float t_in = temperature[r];
+    const float t_in = temperature[pr];
     const bool greedy = !(t_in > 0.f);
     const float t = greedy ? 1.0f : t_in;
     // a row whose largest value is a NaN, +inf or -inf has no distribution: the arg-max pick, a NaN log-probability
@@ -310,7 +323,7 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
 
     if (!plain && !(greedy && logprobs == nullptr)) {                   // uniform over the workgroup, as every branch below
         // ---- pass 2: the high byte's histogram, Z ---------------------------------------------------------------------------------
-        const int k = greedy ? 0 : top_k[r];
+        const int k = greedy ? 0 : top_k[pr];
         const bool k_on = k > 0 && k < n;
         hist_zero(hist);
         for_each(row, n, [&](uint16_t h, int) {
@@ -353,7 +366,7 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
                 __syncthreads();
             }
             if (tid == 0) {                                             // v = ceil(u * cap * Z) in fixed point: c >= v  <=>  c >= ceil(v)
-                float tp = top_p[r];
+                float tp = top_p[pr];
                 tp = tp >= 0.f ? (tp < 1.f ? tp : 1.f) : 0.f;
                 double lim = (double)tp * (double)z;
                 if (k_on) lim = fmin(lim, (double)s_ck);
@@ -391,12 +404,43 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
         int pick = s_pick;
         pick = pick >= 0 && pick < n ? pick : amax;
         if (tokens) tokens[r] = pick;
-        if (next_tokens) next_tokens[r] = pick;
-        if (positions) positions[r] += 1;
-        if (placement) placement[r] += 1;
-        if (valid_lens) valid_lens[r] += 1;
+        if (!SPEC) {
+            if (next_tokens) next_tokens[r] = pick;
+            if (positions) positions[r] += 1;
+            if (placement) placement[r] += 1;
+            if (valid_lens) valid_lens[r] += 1;
+        }
         if (logprobs) logprobs[r] = plain ? __builtin_nanf("") : (H16<BF>::f32(row[pick]) - vmax) / t - lse;
     }
+}
+
+// zl_spec_sample_accept's second launch: out_tokens / out_logprobs hold the picks of the (b, len_q) rows and their log-probabilities
+// (k_sample_advance<.., SPEC> left them); one thread per task finds the longest prefix of its drafts that the picks confirm (a draft
+// outside [0, n) equals no pick), pads the rows behind the bonus token with -1 / NaN, advances the task's state by accepted + 1 and
+// -- where the generator gave the uniforms -- its draw count by as much: the rows behind the rejection drew nothing that counts
+__global__ void k_spec_sample_accept(const int32_t* __restrict__ drafts, int32_t* __restrict__ out_tokens, float* __restrict__ out_logprobs,
+                                     int32_t* __restrict__ accepted, int32_t* __restrict__ tokens, int32_t* __restrict__ positions,
+                                     int32_t* __restrict__ placement, int32_t* __restrict__ valid_lens, float* __restrict__ logprobs,
+                                     int64_t* __restrict__ draws, int b, int len_q) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= b) return;
+    int32_t* pk = out_tokens + (int64_t)t * len_q;
+    float* lp = out_logprobs ? out_logprobs + (int64_t)t * len_q : nullptr;
+    const int32_t* dr = drafts + (int64_t)t * (len_q - 1);
+    int a = 0;
+    while (a < len_q - 1 && dr[a] == pk[a]) ++a;
+    const int32_t last = pk[a];
+    for (int j = a + 1; j < len_q; ++j) {
+        pk[j] = -1;
+        if (lp) lp[j] = __builtin_nanf("");
+    }
+    accepted[t] = a;
+    if (tokens) tokens[t] = last;
+    if (positions) positions[t] += a + 1;
+    if (placement) placement[t] += a + 1;
+    if (valid_lens) valid_lens[t] += a + 1;
+    if (logprobs) logprobs[t] = lp[a];
+    if (draws) draws[t] += a + 1;
 }
 
 }  // namespace
@@ -414,11 +458,38 @@ int zl_sample_advance(const void* logits, int type, int64_t rows, int64_t n, int
     const dim3 g((unsigned)rows), b(kThreads);
     hipStream_t hs = (hipStream_t)s;
     if (type == ZL_T_F16)
-        hipLaunchKernelGGL(k_sample_advance<false>, g, b, 0, hs, (const uint16_t*)logits, ld, (int)n, temperature, top_k, top_p, seeds, draws,
+        hipLaunchKernelGGL((k_sample_advance<false, false>), g, b, 0, hs, (const uint16_t*)logits, ld, (int)n, 1, temperature, top_k, top_p, seeds, draws,
                            u_in, tokens, positions, placement, valid_lens, next_tokens, logprobs, u_out);
     else
-        hipLaunchKernelGGL(k_sample_advance<true>, g, b, 0, hs, (const uint16_t*)logits, ld, (int)n, temperature, top_k, top_p, seeds, draws,
+        hipLaunchKernelGGL((k_sample_advance<true, false>), g, b, 0, hs, (const uint16_t*)logits, ld, (int)n, 1, temperature, top_k, top_p, seeds, draws,
                            u_in, tokens, positions, placement, valid_lens, next_tokens, logprobs, u_out);
+    return zl_launch_status();
+}
+
+int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
+                          const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
+                          const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
+                          int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out, zl_stream_t s) {
+    ZL_CHECK_ARG(logits && temperature && top_k && top_p && drafts && accepted && out_tokens, ZL_EINVAL);
+    ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
+    ZL_CHECK_ARG(out_logprobs || !logprobs, ZL_EINVAL);                 // the task's log-probability is read from its rows'
+    ZL_CHECK_ARG(b >= 1 && len_q >= 2 && len_q <= 32 && n >= 1 && ld >= n && n < ((int64_t)1 << 31) && b < ((int64_t)1 << 31) &&
+                     b * len_q < ((int64_t)1 << 31),
+                 ZL_ESHAPE);
+    ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
+    // the picks: one 1024-thread workgroup per logit row, zl_sample_advance's kernel under the task's parameters, into out_tokens
+    const dim3 g((unsigned)(b * len_q)), blk(kThreads);
+    hipStream_t hs = (hipStream_t)s;
+    if (type == ZL_T_F16)
+        hipLaunchKernelGGL((k_sample_advance<false, true>), g, blk, 0, hs, (const uint16_t*)logits, ld, (int)n, (int)len_q, temperature, top_k,
+                           top_p, seeds, draws, u_in, out_tokens, nullptr, nullptr, nullptr, nullptr, out_logprobs, u_out);
+    else
+        hipLaunchKernelGGL((k_sample_advance<true, true>), g, blk, 0, hs, (const uint16_t*)logits, ld, (int)n, (int)len_q, temperature, top_k,
+                           top_p, seeds, draws, u_in, out_tokens, nullptr, nullptr, nullptr, nullptr, out_logprobs, u_out);
+    const int e = zl_launch_status();
+    if (e) return e;
+    hipLaunchKernelGGL(k_spec_sample_accept, dim3((unsigned)((b + 63) / 64)), dim3(64), 0, hs, drafts, out_tokens, out_logprobs, accepted, tokens,
+                       positions, placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q);
     return zl_launch_status();
 }
 

@@ -964,15 +964,21 @@ class LookupState:
 
 @dataclass
 class SamplerState:
-    """The device-resident state of LLaMA.step_sample (LLaMA.new_sampler builds it; ops.sample_advance states the rule): per-task
-    sampling parameters, each task's generator -- its seed and the number of uniforms it has drawn -- and the last step's results."""
+    """The device-resident state of LLaMA.step_sample and of verify / step_lookup(sampler=...) (LLaMA.new_sampler builds it;
+    ops.sample_advance and ops.spec_sample_accept state the rules): per-task sampling parameters, each task's generator -- its seed
+    and the number of uniforms it has drawn = tokens it has emitted -- and the last step's results."""
     temperature: torch.Tensor   # (B) fp32    <= 0: greedy
     top_k: torch.Tensor         # (B) int32   <= 0 or >= vocab: off
     top_p: torch.Tensor         # (B) fp32    in [0, 1]
     seeds: torch.Tensor         # (B) int64   the Philox key of the task
     draws: torch.Tensor         # (B) int64   uniforms drawn so far = the Philox counter; bumped by the kernel
-    logprobs: torch.Tensor      # (B) fp32    the last step's picks' tempered log-probabilities
-    u: torch.Tensor             # (B) fp32    the last step's uniforms
+    logprobs: torch.Tensor      # (B) fp32    the last step's picks' tempered log-probabilities: of the token now pending in ctx.tokens
+    u: torch.Tensor             # (B) fp32    the last step_sample's uniforms
+    # verify(sampler=...): the last speculative step's rows, (B, len_q) fp32 each -- the log-probabilities of the emitted tokens (NaN
+    # behind the bonus token) and the uniform of every row.  Allocated by the first eager call per len_q (row_bufs keeps them)
+    row_logprobs: Optional[torch.Tensor] = None
+    row_u: Optional[torch.Tensor] = None
+    row_bufs: Optional[Dict[int, tuple]] = None
 
 
 class _PromptRows:
@@ -1952,10 +1958,10 @@ class LLaMA:
         everywhere: the rows route is ahead by 0.7 - 1.2 % of the step at B <= 2 and by 4 - 9 % at B >= 4"""
         return "causal" if b * len_q <= 4 else "rows"
 
-    def verify(self, ctx: DynBatchContext, drafts: torch.Tensor, attn="auto"):
+    def verify(self, ctx: DynBatchContext, drafts: torch.Tensor, attn="auto", sampler: Optional[SamplerState] = None):
         """One speculative step on the device (graph-capturable, no host round trip): check the K = drafts.shape[1] draft tokens of
         every task in ONE pass of the decode layer loop over len_q = K + 1 rows per task, keep the longest prefix the model's own
-        greedy picks confirm plus one token of its own, and roll the batch state back to there -- SessionGenerator.feed +
+        picks confirm plus one token of its own, and roll the batch state back to there -- SessionGenerator.feed +
         rollback_speculative (zhilight/session_generator.py:25-66), which the reference runs through its prompt path.
         State as step_greedy leaves it (ctx.tokens not yet in the cache).  Row (b, i) carries ctx.tokens[b] (i = 0) or
         drafts[b, i - 1] at position positions[b] + i, writes its K / V to slot placement[b] + i and sees the keys
@@ -1970,6 +1976,14 @@ class LLaMA:
         with the pick uses the id as given.  The row-expanded view and the result buffers are allocated on the first eager call
         per K (run one before capturing); its pointer tables and buffer lengths are re-read from ctx by every call, replays
         included, so a caller may swap a task's buffers in place between calls.
+        sampler: None = the picks are greedy (ops.spec_accept).  A SamplerState = the picks are step_sample's (ops.spec_sample_accept):
+        row (b, i) samples under task b's temperature / top-k / top-p with the uniform of counter draws[b] + i, a draft is accepted
+        iff the pick equals it -- for a deterministic drafter exactly the speculative-sampling rule -- and draws += accepted + 1,
+        so the tokens a task emits are the same function of (logits, seed, tokens emitted so far) as step_sample's: speculation
+        changes the speed, not the sample.  Everything up to the logits is the same.  sampler.row_logprobs / row_u (B, len_q) hold
+        the emitted tokens' tempered log-probabilities (NaN behind the bonus token) and every row's uniform; sampler.logprobs[b]
+        keeps step_sample's meaning, the log-probability of the token now pending in ctx.tokens[b].  The two row buffers follow
+        the view's rule: the first eager call per K allocates them.
         Returns SpecResult(logits (B * len_q, vocab), accepted (B) int32, tokens (B, len_q) int32); the three are reused by the next
         call with the same K."""
         c, dev = self.cfg, self.device
@@ -1985,6 +1999,8 @@ class LLaMA:
         if not (torch.is_tensor(drafts) and drafts.dim() == 2 and drafts.shape[0] == b and drafts.shape[1] >= 1
                 and drafts.dtype == torch.int32 and drafts.device == ctx.tokens.device and drafts.is_contiguous()):
             raise ops.ZLError("verify: drafts are (B, K) contiguous int32 on the context's device, K >= 1")
+        if sampler is not None and sampler.temperature.numel() != b:
+            raise ops.ZLError("verify: the sampler state belongs to another batch size")
         len_q = drafts.shape[1] + 1
         m = b * len_q
         if attn == "auto":
@@ -2007,6 +2023,14 @@ class LLaMA:
             ctx.spec[len_q] = (rows, torch.arange(len_q, **i32).view(1, len_q), torch.empty(b, **i32), torch.empty((b, len_q), **i32),
                                torch.arange(b, device=dev).view(b, 1).expand(b, len_q).reshape(m))
         rows, ar, accepted, out_tokens, task_of_row = ctx.spec[len_q]
+        if sampler is not None:
+            if sampler.row_bufs is None:
+                sampler.row_bufs = {}
+            if len_q not in sampler.row_bufs:
+                if capturing:
+                    raise ops.ZLError("verify: run one eager call with this sampler before capturing (it allocates the row results)")
+                sampler.row_bufs[len_q] = tuple(torch.full((b, len_q), float("nan"), dtype=torch.float32, device=dev) for _ in range(2))
+            sampler.row_logprobs, sampler.row_u = sampler.row_bufs[len_q]
         # the view's tables from the context as it is NOW (a swapped buffer, a regrown table), then the rows of this call: tokens
         # (draft ids clamped into the vocabulary), and the three counters of task b + 0 .. K
         torch.index_select(ctx.buf_lens, 0, task_of_row, out=rows.buf_lens)
@@ -2029,7 +2053,13 @@ class LLaMA:
                 return ops.decode_attention_causal(q.view(shape), ctx.buf_lens, ctx.k_addrs[li], ctx.v_addrs[li], ctx.valid_lens, scale,
                                                    ctx.max_len_buf, c.num_kv_heads, out=out.view(shape), workspace=workspace)
         logits = self.encode(rows, attend_rows=hook)
-        ops.spec_accept(logits, drafts, ctx.tokens, ctx.positions, ctx.placement, ctx.valid_lens, accepted=accepted, out_tokens=out_tokens)
+        if sampler is None:
+            ops.spec_accept(logits, drafts, ctx.tokens, ctx.positions, ctx.placement, ctx.valid_lens, accepted=accepted, out_tokens=out_tokens)
+        else:
+            ops.spec_sample_accept(logits, drafts, sampler.temperature, sampler.top_k, sampler.top_p, seeds=sampler.seeds, draws=sampler.draws,
+                                   tokens=ctx.tokens, positions=ctx.positions, placement=ctx.placement, valid_lens=ctx.valid_lens,
+                                   accepted=accepted, out_tokens=out_tokens, out_logprobs=sampler.row_logprobs, logprobs=sampler.logprobs,
+                                   u_out=sampler.row_u)
         ctx.steps_left -= len_q
         return SpecResult(logits, accepted, out_tokens)
 
@@ -2074,42 +2104,51 @@ class LLaMA:
                          drafts=state.drafts, match=state.match)
         return state
 
-    def step_lookup(self, ctx: DynBatchContext, state: LookupState, attn="auto"):
-        """One speculative step with the drafter inside, all on the device: verify(ctx, state.drafts, attn), then ONE launch
+    def step_lookup(self, ctx: DynBatchContext, state: LookupState, attn="auto", sampler: Optional[SamplerState] = None):
+        """One speculative step with the drafter inside, all on the device: verify(ctx, state.drafts, attn, sampler), then ONE launch
         (ops.lookup_draft) appends the tokens the step emitted to the tasks' histories and drafts the next step's tokens into
-        state.drafts.  No host round trip; capturable after one eager call (verify's rule), and a replay carries ctx and state
-        forward together.  Returns verify's SpecResult.
-        A caller that interleaves step_greedy or step_sample keeps the state in step by feeding the token that step left pending:
+        state.drafts.  No host round trip; capturable after one eager call (verify's rule), and a replay carries ctx, state and the
+        sampler forward together.  Returns verify's SpecResult.
+        sampler: a SamplerState makes the step a SAMPLING step (verify's sampler=): the tokens are step_sample's for the same seed,
+        however many drafts are accepted; None = greedy.  Sampling and lookup need no interleaving by hand.
+        A caller that does interleave step_greedy or step_sample keeps the state in step by feeding the token that step left pending:
         ops.lookup_draft(state.history, state.hist_lens, state.k, state.max_ngram, state.min_ngram,
         new_tokens=ctx.tokens.view(B, 1), drafts=state.drafts, match=state.match)."""
         b = ctx.tokens.numel()
         if state.drafts.shape != (b, state.k) or state.history.shape[0] != b:
             raise ops.ZLError("step_lookup: the state belongs to another batch size")
-        res = self.verify(ctx, state.drafts, attn)
+        res = self.verify(ctx, state.drafts, attn, sampler)
         ops.lookup_draft(state.history, state.hist_lens, state.k, state.max_ngram, state.min_ngram, new_tokens=res.tokens,
                          drafts=state.drafts, match=state.match)
         return res
 
-    def generate_lookup(self, ctx: DynBatchContext, state: LookupState, max_new_tokens):
+    def generate_lookup(self, ctx: DynBatchContext, state: LookupState, max_new_tokens, sampler: Optional[SamplerState] = None):
         """The eager convenience loop around step_lookup -- the NON-captured path: it reads accepted / tokens back to the host once per
         round.  Runs rounds until every task has emitted max_new_tokens tokens or the KV buffers have no room for another step
         (ctx.steps_left < k + 1); the batch moves in lock step, so tasks that are done keep running until the last one is.
         Returns (tokens, stats): tokens[j] = the ids task j emitted behind its pending ctx.tokens[j] of the time of the call, cut to
         max_new_tokens; stats = {"steps", "emitted": ids per task before the cut (= steps + accepted), "accepted": accepted drafts per
-        task, "mean_accepted": accepted drafts per task and step}."""
+        task, "mean_accepted": accepted drafts per task and step}.  With a sampler (step_lookup's sampler=) the steps sample, and
+        stats gains "logprobs": per task the emitted ids' tempered log-probabilities, cut as the ids are."""
         b = ctx.tokens.numel()
         out = [[] for _ in range(b)]
+        lps = [[] for _ in range(b)]
         accepted = [0] * b
         steps = 0
         while min(len(o) for o in out) < max_new_tokens and ctx.steps_left >= state.k + 1:
-            res = self.step_lookup(ctx, state)
+            res = self.step_lookup(ctx, state, sampler=sampler)
             acc, tok = res.accepted.tolist(), res.tokens.tolist()
+            lp = sampler.row_logprobs.tolist() if sampler is not None else None
             for j in range(b):
                 out[j] += tok[j][:acc[j] + 1]
                 accepted[j] += acc[j]
+                if lp is not None:
+                    lps[j] += lp[j][:acc[j] + 1]
             steps += 1
         stats = {"steps": steps, "emitted": [len(o) for o in out], "accepted": accepted,
                  "mean_accepted": sum(accepted) / (steps * b) if steps else 0.0}
+        if sampler is not None:
+            stats["logprobs"] = [l[:max_new_tokens] for l in lps]
         return [o[:max_new_tokens] for o in out], stats
 
     # ---- sampling steps -----------------------------------------------------------------------------
@@ -2153,7 +2192,8 @@ class LLaMA:
         """One sampling decode step entirely on the device (graph-capturable after one eager call, no host round trip): encode, then
         ONE launch (ops.sample_advance) picks every task's token under its temperature / top-k / top-p from its own Philox stream
         and advances the batch state, as step_greedy's pick + advance launch does above four rows -- here at every batch size and
-        under TP, where every rank samples the same gathered rows with the same generator state.  state.logprobs / state.u hold the
+        under TP, where every rank samples the same gathered rows with the same generator state.  (Speculative steps under the
+        same sampler: verify / step_lookup(sampler=state); they emit this method's tokens.)  state.logprobs / state.u hold the
         picks' tempered log-probabilities and the uniforms used; state.draws has advanced by one.  Returns (logits, next_tokens
         int64).  Penalties are the caller's (ops.repetition_penalty on the returned logits changes the NEXT call's input only)."""
         b = ctx.tokens.numel()

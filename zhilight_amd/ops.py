@@ -958,8 +958,83 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
     return next_tokens if next_tokens is not None else tokens
 
 
+def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, draws=None, u=None, tokens=None, positions=None,
+                       placement=None, valid_lens=None, accepted=None, out_tokens=None, out_logprobs=None, logprobs=None, u_out=None):
+    """The acceptance of a speculative step under sampling (zl_spec_sample_accept, two launches): spec_accept with sample_advance's
+    pick in the arg-max's place.  logits (B * len_q, n) fp16 / bf16 rows, task-major, unit column stride; drafts (B, K) int32,
+    len_q = K + 1 <= 32.  temperature / top_k / top_p / seeds / draws are per task (B); u, u_out and out_logprobs per row (B, len_q).
+    picks[b, i] = sample_advance's pick of row (b, i) under task b's parameters with the uniform u[b, i], or without u the Philox
+    word of seeds[b] at counter draws[b] + i.  The drafter's proposal is a point mass, so "draw x ~ p, accept iff x == draft, else
+    emit x" IS the optimal speculative-sampling rule: accepted[b] = length of the longest prefix of drafts[b] the picks confirm,
+    out_tokens[b] = picks[b, :accepted + 1], -1 behind them; tokens <- picks[b, accepted], positions / placement / valid_lens +=
+    accepted + 1, draws += accepted + 1 (only where the generator gave the uniforms): one draw per emitted token, so the emitted
+    sequence is what sample_advance emits step by step.  out_logprobs <- the picks' tempered log-probabilities, NaN behind the
+    bonus token; logprobs (B) <- that of picks[b, accepted] (needs out_logprobs); u_out <- the uniform of every row.  Returns
+    (accepted (B) int32, out_tokens (B, len_q) int32); accepted / out_tokens: buffers to write into (a captured call)."""
+    if not all(torch.is_tensor(t) for t in (logits, drafts, temperature, top_k, top_p)):
+        raise ZLError("spec_sample_accept: logits, drafts, temperature, top_k and top_p are tensors")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise ZLError("spec_sample_accept: (B * len_q, n) logits with unit column stride")
+    if logits.dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError(f"spec_sample_accept: fp16 or bf16 logits, not {logits.dtype} (the selection works on the 16-bit pattern)")
+    if drafts.dim() != 2 or drafts.shape[1] < 1 or drafts.dtype != torch.int32 or not drafts.is_contiguous():
+        raise ZLError("spec_sample_accept: drafts are (B, K) contiguous int32, K >= 1")
+    b, len_q, n = drafts.shape[0], drafts.shape[1] + 1, logits.shape[1]
+    if len_q > 32:
+        raise ZLError("spec_sample_accept: at most 32 rows per task (K <= 31)")
+    if b < 1 or logits.shape[0] != b * len_q:
+        raise ZLError("spec_sample_accept: one logit row per task and draft position: B * (K + 1) rows")
+    if n >= 1 << 31:
+        raise ZLError("spec_sample_accept: a row holds fewer than 2^31 classes")
+
+    def sized(t, dtype, count, what, shape):
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.numel() == count and t.is_contiguous()):
+            raise ZLError(f"spec_sample_accept: {what}: contiguous {str(dtype).replace('torch.', '')} {shape}")
+
+    per_task = lambda t, dtype, what: sized(t, dtype, b, what, "of length B")                       # noqa: E731
+    per_row = lambda t, dtype, what: sized(t, dtype, b * len_q, what, "(B, K + 1)")                  # noqa: E731
+    per_task(temperature, torch.float32, "temperature")
+    per_task(top_k, torch.int32, "top_k")
+    per_task(top_p, torch.float32, "top_p")
+    if u is not None:
+        per_row(u, torch.float32, "u")
+    elif seeds is None or draws is None:
+        raise ZLError("spec_sample_accept: give seeds and draws, or u")
+    if u is None or seeds is not None:
+        per_task(seeds, torch.int64, "seeds")
+    if u is None or draws is not None:
+        per_task(draws, torch.int64, "draws")
+    for t, what in ((tokens, "tokens"), (positions, "positions"), (placement, "placement"), (valid_lens, "valid_lens"), (accepted, "accepted")):
+        if t is not None:
+            per_task(t, torch.int32, what)
+    if logprobs is not None:
+        per_task(logprobs, torch.float32, "logprobs")
+        if out_logprobs is None:
+            raise ZLError("spec_sample_accept: logprobs is read from out_logprobs: give both")
+    if out_tokens is not None:
+        per_row(out_tokens, torch.int32, "out_tokens")
+    if out_logprobs is not None:
+        per_row(out_logprobs, torch.float32, "out_logprobs")
+    if u_out is not None:
+        per_row(u_out, torch.float32, "u_out")
+    others = (drafts, temperature, top_k, top_p, seeds, draws, u, tokens, positions, placement, valid_lens, accepted, out_tokens, out_logprobs,
+              logprobs, u_out)
+    if not logits.is_cuda or any(t is not None and t.device != logits.device for t in others):
+        raise ZLError("spec_sample_accept: CUDA logits, every other tensor on the logits' device")
+    if accepted is None:
+        accepted = torch.empty(b, dtype=torch.int32, device=logits.device)
+    if out_tokens is None:
+        out_tokens = torch.empty((b, len_q), dtype=torch.int32, device=logits.device)
+    code = 2 if logits.dtype == torch.float16 else 6
+    check(lib().zl_spec_sample_accept(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts), _p(temperature),
+                                      _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement),
+                                      _p(valid_lens), _p(accepted), _p(out_tokens), _p(out_logprobs), _p(logprobs), _p(u_out), _stream()),
+          "spec_sample_accept")
+    return accepted, out_tokens.view(b, len_q)
+
+
 # --------------------------------------------------------------------------------------------------
-# scoring: functions::Gemm + nn::log_prob_raw / greedy_match_raw (src/nn/functions/cross_entropy.cu:7-69, 358-403) without the
+# scoring:functions::Gemm + nn::log_prob_raw / greedy_match_raw (src/nn/functions/cross_entropy.cu:7-69, 358-403) without the
 # (M, N) logits: csrc/lm_head_score.hip
 # --------------------------------------------------------------------------------------------------
 ScoreRows = collections.namedtuple("ScoreRows", "lse label_logit logprob greedy greedy_logit")
