@@ -1015,6 +1015,39 @@ int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q
                           const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
                           const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
                           int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out, zl_stream_t s);
+/* Repetition and presence penalties inside the sampling step (csrc/sample_rows.hip): the reference generator's per-task knobs
+ * (src/generator/batch_generator.cpp:1670-1692), applied while the kernel reads the row instead of by a launch in front of it.
+ * A task owns a set of token ids, a BITMAP: seen (b, seen_ld) uint32, seen_ld >= ceil(n / 32), token i of task t = bit i & 31 of
+ * seen[t * seen_ld + (i >> 5)]; bits at or above n are never read as classes.  A class of the set is read as pen(x_i), every other
+ * class as x_i, and pen is zl_repetition_penalty's expression, one rounding to the logits' type T:
+ *   presence[t] != 0 ? x - T(presence[t]) : (x < 0 ? x * T(rep_penalty[t]) : x / T(rep_penalty[t]))     (presence takes precedence)
+ * Everything behind that -- arg-max, the plain-row test, max, Z, top-k, top-p, the pick, the log-probability -- is zl_sample_advance's
+ * rule on the penalised row: the results equal zl_repetition_penalty over the set followed by zl_sample_advance, bit for bit.  The
+ * logits in memory are NOT modified.  rep_penalty / presence: fp32, per row (zl_sample_advance_ex) or per task (zl_spec_sample_accept_ex).
+ *   zl_sample_advance_ex      zl_sample_advance + the four arguments.  Row r uses seen row r; after the pick, bit `pick` of that row is
+ *                             set (a row with factor 1 and presence 0 records its pick too).  One launch.
+ *   zl_spec_sample_accept_ex  zl_spec_sample_accept + the four arguments.  Row (t, i) is penalised by seen[t] and the drafts
+ *                             drafts[t, j], j < i, that lie in [0, n): the row counts only if those drafts were emitted, so the step
+ *                             stays the same function of (logits, seed, tokens emitted so far) as zl_sample_advance_ex's, step by
+ *                             step.  The first launch does not write seen; the second sets the bits of out_tokens[t, 0 .. accepted[t]]
+ *                             -- the rejected drafts are not recorded.  Two launches.
+ *   zl_seen_mark              sets the bits of the ids of tokens[t, :n_tok] (int32 rows of stride tok_ld) that lie in [0, n); others
+ *                             (-1 padding, rows of zl_spec_accept's out_tokens) are skipped.  Seeds a set from a prompt or a history.
+ *                             One launch, vector atomics (or).
+ * seen == NULL: the _ex calls ARE the plain ones and rep_penalty / presence may be NULL.
+ * ZL_EINVAL: seen without both parameter arrays (zl_seen_mark: a null seen / tokens); ZL_ESHAPE: seen_ld < ceil(n / 32)
+ * (zl_seen_mark: also b < 1, n < 1, n >= 2^31, n_tok < 1, tok_ld < n_tok); otherwise the plain calls' codes.
+ * Ordinary vector stores and vector atomics only; no allocation, no sync, no workspace; deterministic. */
+int zl_sample_advance_ex(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
+                         const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
+                         int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
+                         const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s);
+int zl_spec_sample_accept_ex(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
+                             const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
+                             const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
+                             int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
+                             const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s);
+int zl_seen_mark(uint32_t* seen, int64_t seen_ld, int64_t b, int64_t n, const int32_t* tokens, int64_t n_tok, int64_t tok_ld, zl_stream_t s);
 /* The logit post-processing of the reference's batch generator (src/generator/beam_util.cu, 3rd/bmengine/bmengine/functions/{softmax,topk}.cu):
  * what src/generator/batch_generator.cpp calls between a decode step and its host-side search, so that the py_export surface (zhilight.C)
  * links against this boundary.  Rows of n logits of type ZL_T_F16 / ZL_T_BF16 / ZL_T_F32; fp32 arithmetic, one rounding to T.

@@ -9,8 +9,17 @@
      captured step_greedy, replays alternated.  Neither step_greedy nor anything it runs is changed by the sampler, so the
      step_greedy measured here is the one of the commit before it.
 
-usage: python tools/bench_sample.py [--launch-only | --step-only] [--reps 30] [--launches 100]"""
+  3. --penalties (profiles/sample_penalties.txt): the launch alone at the same rows and parameter sets, three ways on the same logits --
+     zl_sample_advance; zl_sample_advance_ex with a bitmap of about 1 % of the vocabulary per row; and what a caller had before the
+     penalty moved into the kernel, zl_repetition_penalty over that token list followed by zl_sample_advance, two launches.  The
+     factor is 1.0 (presence 0): the arithmetic per penalised class is the same division, and the two-launch form, which rewrites the
+     logits on every call, then leaves them as they are, so that all cells see the same rows throughout.  --parent-so PATH: a library
+     built from the commit before this one; its zl_sample_advance and its two-launch form are measured in the same process,
+     replays alternated with this commit's.
+
+usage: python tools/bench_sample.py [--launch-only | --step-only | --penalties [--parent-so PATH]] [--reps 30] [--launches 100]"""
 import argparse
+import ctypes as C
 import os
 import statistics
 import sys
@@ -119,16 +128,74 @@ def step_leg(dev, reps):
         torch.cuda.empty_cache()
 
 
+def penalty_leg(dev, reps, launches, parent_so):
+    from zhilight_amd._lib import lib
+    libs = {"this": lib()}
+    if parent_so:
+        libs["parent"] = C.CDLL(parent_so)
+    p = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)           # noqa: E731
+    i64 = C.c_int64
+    words = ops.seen_words(VOCAB)
+    print("# the launch alone with and without penalties, warm rows of %d fp16 logits (normal, sigma 2), %d ids (about 1 %%) per row in the set, "
+          "factor 1.0: us per call, median [p10 .. p90] over %d alternated replays of %d calls" % (VOCAB, VOCAB // 100, reps, launches))
+    graphs, keep = {}, []
+    for rows in (1, 8, 32):
+        gen = torch.Generator(device="cpu").manual_seed(rows)
+        logits = (torch.randn((rows, VOCAB), generator=gen) * 2).to(torch.float16).to(dev)
+        ids = torch.stack([torch.randperm(VOCAB, generator=gen)[:VOCAB // 100] for _ in range(rows)]).to(torch.int32).to(dev)
+        bid = torch.arange(rows, dtype=torch.int32, device=dev).view(rows, 1).expand(rows, ids.shape[1]).contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        one, zero = torch.ones(ids.numel(), **f32), torch.zeros(ids.numel(), **f32)
+        tok = torch.zeros(rows, dtype=torch.int32, device=dev)
+        for name, t, k, tp, lp in SETS:
+            a = dict(T=torch.full((rows,), t, **f32), k=torch.full((rows,), k, dtype=torch.int32, device=dev), p=torch.full((rows,), tp, **f32),
+                     seeds=torch.arange(rows, dtype=torch.int64, device=dev), draws=torch.zeros(rows, dtype=torch.int64, device=dev),
+                     lp=torch.empty(rows, **f32) if lp else None, seen=torch.zeros((rows, words), dtype=torch.int32, device=dev))
+            ops.seen_mark(a["seen"], ids, VOCAB)
+            head = lambda a=a: (p(logits), C.c_int(2), i64(rows), i64(VOCAB), i64(VOCAB), p(a["T"]), p(a["k"]), p(a["p"]), p(a["seeds"]),   # noqa: E731
+                                p(a["draws"]), p(None), p(tok), p(None), p(None), p(None), p(None), p(a["lp"]), p(None))
+            stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)                                                             # noqa: E731
+
+            def plain(l, head=head):
+                for _ in range(launches):
+                    assert l.zl_sample_advance(*head(), stream()) == 0
+
+            def two(l, head=head):
+                for _ in range(launches):
+                    assert l.zl_repetition_penalty(p(one), p(zero), p(ids), p(bid), p(logits), i64(ids.numel()), i64(VOCAB), C.c_int(2), stream()) == 0
+                    assert l.zl_sample_advance(*head(), stream()) == 0
+
+            def fused(a=a, head=head):
+                for _ in range(launches):
+                    assert libs["this"].zl_sample_advance_ex(*head(), p(one), p(zero), p(a["seen"]), i64(words), stream()) == 0
+            for which, l in libs.items():
+                l.zl_sample_advance.argtypes = libs["this"].zl_sample_advance.argtypes
+                graphs[(rows, name, which + ": sample_advance")] = _graph(lambda l=l, plain=plain: plain(l))
+                graphs[(rows, name, which + ": repetition_penalty + sample_advance")] = _graph(lambda l=l, two=two: two(l))
+            graphs[(rows, name, "this: sample_advance_ex")] = _graph(fused)
+            keep.append(a)
+        keep.append((logits, ids, bid, one, zero, tok))
+    t = _alternate(graphs, reps)
+    print("# rows | %-30s | %-44s | us per call" % ("parameters", "call"))
+    for (rows, name, which), ms in t.items():
+        print("  %4d | %-30s | %-44s | %7.2f [%7.2f .. %7.2f]" % ((rows, name, which) + _stats(ms, launches)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launch-only", action="store_true")
     ap.add_argument("--step-only", action="store_true")
+    ap.add_argument("--penalties", action="store_true")
+    ap.add_argument("--parent-so", default=None)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--launches", type=int, default=100)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sample: needs a GPU")
     dev = torch.device("cuda:0")
+    if a.penalties:
+        penalty_leg(dev, a.reps, a.launches, a.parent_so)
+        return
     if not a.step_only:
         launch_leg(dev, a.reps, a.launches)
     if not a.launch_only:

@@ -27,7 +27,20 @@
 //      exactly -> v = ceil(u * min(top_p Z, c[k-1]))
 //   4  the same inside the bin where the running mass reaches v (skipped when it is pass 3's bin) -> the value, j
 //   5  per-wave counts of the classes equal to that value, then one wave walks its 1/16 of the row to the j-th
+//   zl_sample_advance_ex / zl_spec_sample_accept_ex / zl_seen_mark   the same picks with the reference generator's repetition and
+//                       presence penalties (src/generator/batch_generator.cpp:1670-1692) applied INSIDE the walk: a task's emitted tokens
+//                       are a bitmap in global memory (bit i & 31 of word i >> 5), a class whose bit is set is read as
+//                       zl_repetition_penalty's value of it -- again a 16-bit pattern -- and everything above selects on that pattern.
+//                       The logits in memory are left alone.  Pass 1 and the last walk of pass 5 stream the row with the set's classes
+//                       masked (a 16-byte lane of eight classes fetches the one or two bitmap words that cover it; a row of a
+//                       speculative step adds the drafts in front of it through a 256-bit LDS filter keyed by i & 255, and compares
+//                       ids only where the filter hits) and take the set's classes from a walk over the bitmap itself.  The histogram
+//                       passes stream the STORED row exactly as without a penalty and then move each class of the set from the bin of
+//                       its stored pattern to the bin of its penalised one -- the histograms are integers, so this is exact -- which
+//                       costs them a walk over the bitmap (n / 32 words) and nothing per class.  PEN = false compiles none of it.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "zl_common.h"
 
@@ -67,22 +80,145 @@ __device__ __forceinline__ u64 mass_of(uint32_t key, float vmax, float t, float 
     return (u64)(p * scale);
 }
 
+// float -> the 16-bit pattern, one rounding to nearest even: the instructions of sampling_ops.hip's ET<>::cvt, so that a penalised
+// class has the pattern zl_repetition_penalty would have stored
+template <bool BF>
+__device__ __forceinline__ uint16_t cvt16(float f) {
+    if (BF) {
+        uint32_t u = __builtin_bit_cast(uint32_t, f);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+        u += 0x7fffu + ((u >> 16) & 1u);
+        return (uint16_t)(u >> 16);
+    }
+    asm volatile("" : "+v"(f));
+    return __builtin_bit_cast(uint16_t, (_Float16)f);
+}
+
+constexpr int kFilt = 256;         // bits of the draft filter of a speculative row
+constexpr int kMaxDrafts = 31;     // zl_spec_sample_accept's row limit - 1
+
+struct NoPen {                      // PEN = false: a class is read as it is stored, and nothing below is compiled
+    static constexpr bool on = false;
+};
+// the row's view of its penalty: the set = the task's bitmap, and for row i of a speculative step the in-range drafts 0 .. i - 1
+template <bool BF, bool SPEC>
+struct Pen {
+    static constexpr bool on = true;
+    const uint32_t* seen;           // the task's bitmap row (global)
+    const uint32_t* filt;           // SPEC: kFilt bits, bit (id & 255) of every draft in front of the row (LDS)
+    const int32_t* ids;             // SPEC: those drafts, -1 where out of range (LDS)
+    int nd;                         // SPEC: how many
+    float f, tp;                    // T(factor), T(presence) widened
+    bool sub;                       // presence != 0: it takes precedence
+
+    // k_repetition_penalty's expression
+    __device__ __forceinline__ uint16_t apply(uint16_t h) const {
+        const float l = H16<BF>::f32(h);
+        const float r = sub ? l - tp : (l < 0.f ? l * f : l / f);
+        return cvt16<BF>(r);
+    }
+    __device__ __forceinline__ bool draft(int i) const {
+        bool hit = false;
+        for (int j = 0; j < nd; ++j) hit |= ids[j] == i;
+        return hit;
+    }
+    // bit e <=> class i0 + e is in the set, e < 8; the caller has i0 + 7 < n, so both words lie inside the row's ceil(n / 32)
+    __device__ __forceinline__ uint32_t mask8(int i0) const {
+        const uint32_t lo = seen[i0 >> 5], hi = seen[(i0 + 7) >> 5];    // the same word twice where the lane does not straddle
+        uint32_t m = (uint32_t)((((u64)hi << 32) | lo) >> (i0 & 31)) & 0xffu;
+        if constexpr (SPEC) {
+            const int p = i0 & (kFilt - 1);
+            const uint32_t flo = filt[p >> 5], fhi = filt[((p + 7) >> 5) & (kFilt / 32 - 1)];
+            uint32_t fm = (uint32_t)((((u64)fhi << 32) | flo) >> (p & 31)) & 0xffu & ~m;
+            while (fm) {
+                const int e = __ffs((int)fm) - 1;
+                fm &= fm - 1;
+                if (draft(i0 + e)) m |= 1u << e;
+            }
+        }
+        return m;
+    }
+    // the set classes of one 16-byte lane, one at a time: sets are sparse (a task's emitted tokens), so a wave takes the loop once or
+    // twice where eight predicated copies of the arithmetic would cost every lane of every pass
+    __device__ __forceinline__ void apply8(uint4& d, uint32_t m) const {
+        while (m) {
+            const int e = __ffs((int)m) - 1;
+            m &= m - 1;
+            const int wi = e >> 1, sft = 16 * (e & 1);
+            const uint32_t w = wi == 0 ? d.x : (wi == 1 ? d.y : (wi == 2 ? d.z : d.w));
+            const uint32_t nw = (w & ~(0xffffu << sft)) | ((uint32_t)apply((uint16_t)(w >> sft)) << sft);
+            d.x = wi == 0 ? nw : d.x;
+            d.y = wi == 1 ? nw : d.y;
+            d.z = wi == 2 ? nw : d.z;
+            d.w = wi == 3 ? nw : d.w;
+        }
+    }
+    // one class, i < n
+    __device__ __forceinline__ bool has(int i) const {
+        bool in = seen[i >> 5] >> (i & 31) & 1u;
+        if constexpr (SPEC)
+            if (!in && (filt[(i & (kFilt - 1)) >> 5] >> (i & 31) & 1u)) in = draft(i);
+        return in;
+    }
+    __device__ __forceinline__ uint16_t one(uint16_t h, int i) const { return has(i) ? apply(h) : h; }
+    // g(stored pattern, penalised pattern, index) for every class of the set, each once, in no particular order: the bitmap's words
+    // below n over the threads -- 4 loads per thread at 128 256 classes, and as many trips as a task has emitted tokens there --
+    // then (SPEC) the drafts in front of the row that the bitmap does not hold, one thread each
+    template <class G>
+    __device__ __forceinline__ void for_set(const uint16_t* __restrict__ row, int n, G&& g) const {
+        const int nw = (n + 31) >> 5;
+        for (int w = threadIdx.x; w < nw; w += kThreads) {
+            uint32_t bits = seen[w];
+            if (w == nw - 1 && (n & 31)) bits &= (1u << (n & 31)) - 1u;
+            while (bits) {
+                const int i = w * 32 + __ffs((int)bits) - 1;
+                bits &= bits - 1;
+                const uint16_t h = row[i];
+                g(h, apply(h), i);
+            }
+        }
+        if constexpr (SPEC) {
+            const int t = threadIdx.x;
+            if (t < nd) {
+                const int id = ids[t];
+                bool fresh = id >= 0;
+                if (fresh) fresh = !(seen[id >> 5] >> (id & 31) & 1u);
+                for (int j = 0; j < t; ++j) fresh &= ids[j] != id;
+                if (fresh) {
+                    const uint16_t h = row[id];
+                    g(h, apply(h), id);
+                }
+            }
+        }
+    }
+};
+
 // f(pattern, index) for every element of the row, in no particular order: up to 7 elements in front of the first 16-byte boundary,
-// 16-byte lanes with kLoads loads in flight, up to 7 elements behind the last whole lane
-template <class F>
-__device__ __forceinline__ void for_each(const uint16_t* __restrict__ row, int n, F&& f) {
+// 16-byte lanes with kLoads loads in flight, up to 7 elements behind the last whole lane.  pen.on: the pattern is the penalised one --
+// the streaming loop leaves the set's classes out (the mask of a lane is one or two bitmap words) and pen.for_set brings them in
+template <class P, class F>
+__device__ __forceinline__ void for_each(const uint16_t* __restrict__ row, int n, const P& pen, F&& f) {
     const int tid = threadIdx.x;
     int head = (int)(((16 - ((uintptr_t)row & 15)) & 15) >> 1);
     head = head < n ? head : n;
-    if (tid < head) f(row[tid], tid);
+    auto one = [&](int i) {
+        if constexpr (P::on) {
+            if (!pen.has(i)) f(row[i], i);
+        } else {
+            f(row[i], i);
+        }
+    };
+    if (tid < head) one(tid);
     const uint4* body = reinterpret_cast<const uint4*>(row + head);
     const int nv = (n - head) >> 3;
     for (int c0 = tid; c0 < nv; c0 += kLoads * kThreads) {
         uint4 v4[kLoads];
+        uint32_t m8[kLoads];
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
             const int c = c0 + u * kThreads;
             v4[u] = body[c < nv ? c : c0];
+            if constexpr (P::on) m8[u] = pen.mask8(head + (c < nv ? c : c0) * 8);
         }
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
@@ -90,11 +226,18 @@ __device__ __forceinline__ void for_each(const uint16_t* __restrict__ row, int n
             if (c < nv) {
                 const uint32_t w[4] = {v4[u].x, v4[u].y, v4[u].z, v4[u].w};
 #pragma unroll
-                for (int e = 0; e < 8; ++e) f((uint16_t)(w[e >> 1] >> (16 * (e & 1))), head + c * 8 + e);
+                for (int e = 0; e < 8; ++e) {
+                    if constexpr (P::on) {
+                        if (!(m8[u] >> e & 1u)) f((uint16_t)(w[e >> 1] >> (16 * (e & 1))), head + c * 8 + e);
+                    } else {
+                        f((uint16_t)(w[e >> 1] >> (16 * (e & 1))), head + c * 8 + e);
+                    }
+                }
             }
         }
     }
-    for (int i = head + nv * 8 + tid; i < n; i += kThreads) f(row[i], i);
+    for (int i = head + nv * 8 + tid; i < n; i += kThreads) one(i);
+    if constexpr (P::on) pen.for_set(row, n, [&](uint16_t, uint16_t ph, int i) { f(ph, i); });
 }
 
 struct Hist {                       // 48 KB: kCopies interleaved copies of a 256-bin (count, mass) histogram
@@ -114,6 +257,14 @@ __device__ __forceinline__ void hist_count(Hist& h, uint32_t bin) {
 }
 __device__ __forceinline__ void hist_mass(Hist& h, uint32_t bin, u64 q) {
     if (q) atomicAdd(&h.mass[(int)bin * kCopies + (threadIdx.x & (kCopies - 1))], q);
+}
+// a class moves from the bin of its stored pattern to the bin of its penalised one: integers modulo 2^32 / 2^64, so a copy may wrap
+// below zero while the sum over the copies that hist_take forms is exact
+__device__ __forceinline__ void hist_uncount(Hist& h, uint32_t bin) {
+    atomicAdd(&h.cnt[(int)bin * kCopies + (threadIdx.x & (kCopies - 1))], 0xffffffffu);
+}
+__device__ __forceinline__ void hist_unmass(Hist& h, uint32_t bin, u64 q) {
+    if (q) atomicAdd(&h.mass[(int)bin * kCopies + (threadIdx.x & (kCopies - 1))], (u64)0 - q);
 }
 // thread t < 256 takes bin 255 - t: the scan over threads runs from the largest key down
 __device__ __forceinline__ void hist_take(const Hist& h, uint32_t& c, u64& m) {
@@ -189,8 +340,10 @@ __device__ __forceinline__ int count8(const uint4& d, uint32_t key) {
 }
 
 // the j-th (1-based) class of the row, in index order, whose key is `key` -> *pick (left alone if there are fewer: never the case for a
-// j taken from the histograms).  Order = for_each's three pieces; the 16-byte lanes are cut into one contiguous piece per wave
-__device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n, uint32_t key, int j, int* wcnt, int* pick) {
+// j taken from the histograms).  Order = for_each's three pieces; the 16-byte lanes are cut into one contiguous piece per wave.
+// pen.on: the keys are the penalised patterns', as in for_each
+template <class P>
+__device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n, const P& pen, uint32_t key, int j, int* wcnt, int* pick) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int head = (int)(((16 - ((uintptr_t)row & 15)) & 15) >> 1);
     head = head < n ? head : n;
@@ -198,18 +351,34 @@ __device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n
     const int nv = (n - head) >> 3, tail = head + nv * 8;
     const int vpw = (nv + kWaves - 1) / kWaves;
     const int v0 = wave * vpw < nv ? wave * vpw : nv, v1 = v0 + vpw < nv ? v0 + vpw : nv;
+    auto at = [&](int i) -> uint16_t {
+        if constexpr (P::on) return pen.one(row[i], i);
+        else return row[i];
+    };
+    auto lane8 = [&](int v) -> uint4 {
+        uint4 d = body[v];
+        if constexpr (P::on) pen.apply8(d, pen.mask8(head + v * 8));
+        return d;
+    };
     int c = 0;
-    for (int v = v0 + lane; v < v1; v += 64) c += count8(body[v], key);
+    for (int v = v0 + lane; v < v1; v += 64) c += count8(body[v], key);        // the stored patterns; pen.on: corrected below
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
     if (lane == 0) wcnt[wave] = c;
     __syncthreads();
+    if constexpr (P::on) {
+        pen.for_set(row, n, [&](uint16_t raw, uint16_t ph, int i) {
+            const int d = (int)(key16(ph) == key) - (int)(key16(raw) == key);
+            if (d != 0 && i >= head && i < tail) atomicAdd(&wcnt[((i - head) >> 3) / vpw], d);
+        });
+        __syncthreads();
+    }
     int hc = 0;
-    for (int i = 0; i < head; ++i) hc += key16(row[i]) == key;
+    for (int i = 0; i < head; ++i) hc += key16(at(i)) == key;
     if (j <= hc) {
         if (tid == 0)
             for (int i = 0; i < head; ++i)
-                if (key16(row[i]) == key && --j == 0) *pick = i;
+                if (key16(at(i)) == key && --j == 0) *pick = i;
         return;
     }
     j -= hc;
@@ -221,7 +390,7 @@ __device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n
     if (w == kWaves) {
         if (tid == 0)
             for (int i = tail; i < n; ++i)
-                if (key16(row[i]) == key && --j == 0) *pick = i;
+                if (key16(at(i)) == key && --j == 0) *pick = i;
         return;
     }
     if (wave != w) return;
@@ -230,7 +399,7 @@ __device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n
         uint4 d = make_uint4(0, 0, 0, 0);
         int own = 0;
         if (v < v1) {
-            d = body[v];
+            d = lane8(v);
             own = count8(d, key);
         }
         int incl = own;
@@ -257,14 +426,19 @@ __device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n
 // SPEC (zl_spec_sample_accept's first launch): row r belongs to task r / len_q -- its parameters, seed and draw count are the task's,
 // its counter is draws[task] + r % len_q -- and the epilogue writes the row's pick, log-probability and uniform only: draws and the
 // batch state are the second launch's.  u_in / u_out / tokens / logprobs stay per row.  !SPEC: len_q is not read
-template <bool BF, bool SPEC>
+// PEN (the _ex entry points): the row's classes are read through Pen -- rep_penalty / presence / seen row pr, and under SPEC the
+// drafts in front of the row -- and !SPEC sets the pick's bit in the row's bitmap: one workgroup owns the row, every read of it lies
+// in front of a barrier that thread 0 has passed.  !PEN: the four arguments and drafts are not read
+template <bool BF, bool SPEC, bool PEN>
 __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __restrict__ x, int64_t ld, int n, int len_q, const float* __restrict__ temperature,
                                                              const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
                                                              const int64_t* __restrict__ seeds, int64_t* __restrict__ draws,
                                                              const float* __restrict__ u_in, int32_t* __restrict__ tokens,
                                                              int32_t* __restrict__ positions, int32_t* __restrict__ placement,
                                                              int32_t* __restrict__ valid_lens, int64_t* __restrict__ next_tokens,
-                                                             float* __restrict__ logprobs, float* __restrict__ u_out) {
+                                                             float* __restrict__ logprobs, float* __restrict__ u_out,
+                                                             const float* __restrict__ rep_penalty, const float* __restrict__ presence,
+                                                             uint32_t* seen, int64_t seen_ld, const int32_t* __restrict__ drafts) {
     __shared__ Hist hist;
     __shared__ u64 red[kWaves];
     __shared__ u64 wm[kBins / 64];
@@ -276,6 +450,34 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int pr = SPEC ? r / len_q : r;                                // the row of the parameters and of the generator
     const uint16_t* row = x + (size_t)r * ld;
+
+    typedef typename std::conditional<PEN, Pen<BF, SPEC>, NoPen>::type P;
+    P pen;
+    if constexpr (PEN) {
+        __shared__ uint32_t s_filt[kFilt / 32];
+        __shared__ int32_t s_ids[kMaxDrafts];
+        const float pp = presence[pr];
+        pen.seen = seen + (size_t)pr * seen_ld;
+        pen.filt = s_filt;
+        pen.ids = s_ids;
+        pen.nd = 0;
+        pen.sub = pp != 0.f;
+        pen.tp = H16<BF>::f32(cvt16<BF>(pp));
+        pen.f = H16<BF>::f32(cvt16<BF>(rep_penalty[pr]));
+        if constexpr (SPEC) {
+            const int i = r - pr * len_q;                               // <= kMaxDrafts: the launcher's len_q <= 32
+            pen.nd = i;
+            if (tid < kFilt / 32) s_filt[tid] = 0;
+            __syncthreads();
+            if (tid < i) {
+                const int32_t d = drafts[(size_t)pr * (len_q - 1) + tid];
+                const bool in = d >= 0 && d < n;
+                s_ids[tid] = in ? d : -1;
+                if (in) atomicOr(&s_filt[(d & (kFilt - 1)) >> 5], 1u << (d & 31));
+            }
+            __syncthreads();
+        }
+    }
 
     // ---- the uniform of this row and call ---------------------------------------------------------------------------------------
     float u = 0.f;
@@ -293,7 +495,7 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
 
     // ---- pass 1: zl_argmax_advance's pick -----------------------------------------------------------------------------------------
     u64 best = 0;
-    for_each(row, n, [&](uint16_t h, int i) {
+    for_each(row, n, pen, [&](uint16_t h, int i) {
         const uint32_t k = (h & 0x7fffu) > H16<BF>::kInf ? 0xffffffffu : key16(h);       // a NaN is the largest value, the first one wins
         const u64 key = ((u64)k << 32) | (uint32_t)~(uint32_t)i;
         best = key > best ? key : best;
@@ -326,11 +528,23 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
         const int k = greedy ? 0 : top_k[pr];
         const bool k_on = k > 0 && k < n;
         hist_zero(hist);
-        for_each(row, n, [&](uint16_t h, int) {
+        // PEN, here and in the low byte's pass: the stored row as it is, then the set's classes move to their penalised bins
+        for_each(row, n, NoPen(), [&](uint16_t h, int) {
             const uint32_t kk = key16(h);
             if (k_on) hist_count(hist, kk >> 8);                        // the count select is top-k's alone
             hist_mass(hist, kk >> 8, mass_of<BF>(kk, vmax, t, scale));
         });
+        if constexpr (PEN)
+            pen.for_set(row, n, [&](uint16_t raw, uint16_t ph, int) {
+                const uint32_t kr = key16(raw), kp = key16(ph);
+                if (kr == kp) return;
+                if (k_on) {
+                    hist_uncount(hist, kr >> 8);
+                    hist_count(hist, kp >> 8);
+                }
+                hist_unmass(hist, kr >> 8, mass_of<BF>(kr, vmax, t, scale));
+                hist_mass(hist, kp >> 8, mass_of<BF>(kp, vmax, t, scale));
+            });
         uint32_t c1, c1_above;
         u64 m1, m1_above;
         hist_take(hist, c1, m1);
@@ -347,10 +561,17 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
             // count x mass_of(key), one exponential per bin instead of one per class, and sums to the level-1 bin exactly
             auto low_byte = [&](int bin) {
                 hist_zero(hist);
-                for_each(row, n, [&](uint16_t h, int) {
+                for_each(row, n, NoPen(), [&](uint16_t h, int) {
                     const uint32_t kk = key16(h);
                     if ((int)(kk >> 8) == bin) hist_count(hist, kk & 0xffu);
                 });
+                if constexpr (PEN)
+                    pen.for_set(row, n, [&](uint16_t raw, uint16_t ph, int) {
+                        const uint32_t kr = key16(raw), kp = key16(ph);
+                        if (kr == kp) return;
+                        if ((int)(kr >> 8) == bin) hist_uncount(hist, kr & 0xffu);
+                        if ((int)(kp >> 8) == bin) hist_count(hist, kp & 0xffu);
+                    });
                 hist_take(hist, c2, m2);
                 q2 = mass_of<BF>((uint32_t)(bin << 8) | (uint32_t)((kBins - 1 - tid) & 0xff), vmax, t, scale);
                 m2 = (u64)c2 * q2;
@@ -394,7 +615,7 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
                 }
                 __syncthreads();
                 // ---- pass 5: the j-th class with that value, in index order ------------------------------------------------------------
-                find_jth(row, n, (uint32_t)sel_key.bin, s_j, wcnt, &s_pick);
+                find_jth(row, n, pen, (uint32_t)sel_key.bin, s_j, wcnt, &s_pick);
                 __syncthreads();
             }
         }
@@ -410,18 +631,22 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
             if (placement) placement[r] += 1;
             if (valid_lens) valid_lens[r] += 1;
         }
-        if (logprobs) logprobs[r] = plain ? __builtin_nanf("") : (H16<BF>::f32(row[pick]) - vmax) / t - lse;
+        uint16_t hp = row[pick];
+        if constexpr (PEN) hp = pen.one(hp, pick);
+        if (logprobs) logprobs[r] = plain ? __builtin_nanf("") : (H16<BF>::f32(hp) - vmax) / t - lse;
+        if constexpr (PEN && !SPEC) seen[(size_t)r * seen_ld + (pick >> 5)] |= 1u << (pick & 31);
     }
 }
 
 // zl_spec_sample_accept's second launch: out_tokens / out_logprobs hold the picks of the (b, len_q) rows and their log-probabilities
 // (k_sample_advance<.., SPEC> left them); one thread per task finds the longest prefix of its drafts that the picks confirm (a draft
 // outside [0, n) equals no pick), pads the rows behind the bonus token with -1 / NaN, advances the task's state by accepted + 1 and
-// -- where the generator gave the uniforms -- its draw count by as much: the rows behind the rejection drew nothing that counts
+// -- where the generator gave the uniforms -- its draw count by as much: the rows behind the rejection drew nothing that counts.
+// seen (zl_spec_sample_accept_ex): the emitted tokens' bits are set in the task's bitmap; the rejected drafts' are not
 __global__ void k_spec_sample_accept(const int32_t* __restrict__ drafts, int32_t* __restrict__ out_tokens, float* __restrict__ out_logprobs,
                                      int32_t* __restrict__ accepted, int32_t* __restrict__ tokens, int32_t* __restrict__ positions,
                                      int32_t* __restrict__ placement, int32_t* __restrict__ valid_lens, float* __restrict__ logprobs,
-                                     int64_t* __restrict__ draws, int b, int len_q) {
+                                     int64_t* __restrict__ draws, int b, int len_q, uint32_t* __restrict__ seen, int64_t seen_ld) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= b) return;
     int32_t* pk = out_tokens + (int64_t)t * len_q;
@@ -441,6 +666,83 @@ __global__ void k_spec_sample_accept(const int32_t* __restrict__ drafts, int32_t
     if (valid_lens) valid_lens[t] += a + 1;
     if (logprobs) logprobs[t] = lp[a];
     if (draws) draws[t] += a + 1;
+    if (seen)
+        for (int j = 0; j <= a; ++j) seen[(int64_t)t * seen_ld + (pk[j] >> 5)] |= 1u << (pk[j] & 31);     // picks lie in [0, n)
+}
+
+// zl_seen_mark: one thread per (task, position); ids outside [0, n) are skipped
+__global__ void k_seen_mark(uint32_t* __restrict__ seen, int64_t seen_ld, int64_t b, int n, const int32_t* __restrict__ tokens, int64_t n_tok,
+                            int64_t tok_ld) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= b * n_tok) return;
+    const int64_t t = i / n_tok;
+    const int32_t id = tokens[t * tok_ld + (i - t * n_tok)];
+    if (id >= 0 && id < n) atomicOr(&seen[t * seen_ld + (id >> 5)], 1u << (id & 31));
+}
+
+// the two launchers: PEN <=> seen != NULL, so the plain entry points launch the instantiations without a penalty
+int sample_advance_launch(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
+                          const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
+                          int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
+                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
+    ZL_CHECK_ARG(logits && temperature && top_k && top_p, ZL_EINVAL);
+    ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
+    ZL_CHECK_ARG(tokens || next_tokens, ZL_EINVAL);
+    ZL_CHECK_ARG(!seen || (rep_penalty && presence), ZL_EINVAL);
+    ZL_CHECK_ARG(rows >= 1 && n >= 1 && ld >= n && n < ((int64_t)1 << 31) && rows < ((int64_t)1 << 31), ZL_ESHAPE);
+    ZL_CHECK_ARG(!seen || seen_ld >= (n + 31) / 32, ZL_ESHAPE);
+    ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
+    const dim3 g((unsigned)rows), b(kThreads);
+    hipStream_t hs = (hipStream_t)s;
+#define ZL_SAMPLE(BF, PEN)                                                                                                                     \
+    hipLaunchKernelGGL((k_sample_advance<BF, false, PEN>), g, b, 0, hs, (const uint16_t*)logits, ld, (int)n, 1, temperature, top_k, top_p, seeds, \
+                       draws, u_in, tokens, positions, placement, valid_lens, next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld,  \
+                       (const int32_t*)nullptr)
+    if (type == ZL_T_F16) {
+        if (seen) ZL_SAMPLE(false, true);
+        else ZL_SAMPLE(false, false);
+    } else {
+        if (seen) ZL_SAMPLE(true, true);
+        else ZL_SAMPLE(true, false);
+    }
+#undef ZL_SAMPLE
+    return zl_launch_status();
+}
+
+int spec_sample_accept_launch(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
+                              const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
+                              const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
+                              int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
+                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
+    ZL_CHECK_ARG(logits && temperature && top_k && top_p && drafts && accepted && out_tokens, ZL_EINVAL);
+    ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
+    ZL_CHECK_ARG(out_logprobs || !logprobs, ZL_EINVAL);                 // the task's log-probability is read from its rows'
+    ZL_CHECK_ARG(!seen || (rep_penalty && presence), ZL_EINVAL);
+    ZL_CHECK_ARG(b >= 1 && len_q >= 2 && len_q <= kMaxDrafts + 1 && n >= 1 && ld >= n && n < ((int64_t)1 << 31) && b < ((int64_t)1 << 31) &&
+                     b * len_q < ((int64_t)1 << 31),
+                 ZL_ESHAPE);
+    ZL_CHECK_ARG(!seen || seen_ld >= (n + 31) / 32, ZL_ESHAPE);
+    ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
+    // the picks: one 1024-thread workgroup per logit row, zl_sample_advance's kernel under the task's parameters, into out_tokens
+    const dim3 g((unsigned)(b * len_q)), blk(kThreads);
+    hipStream_t hs = (hipStream_t)s;
+#define ZL_SAMPLE(BF, PEN)                                                                                                                  \
+    hipLaunchKernelGGL((k_sample_advance<BF, true, PEN>), g, blk, 0, hs, (const uint16_t*)logits, ld, (int)n, (int)len_q, temperature, top_k,   \
+                       top_p, seeds, draws, u_in, out_tokens, nullptr, nullptr, nullptr, nullptr, out_logprobs, u_out, rep_penalty, presence,  \
+                       seen, seen_ld, drafts)
+    if (type == ZL_T_F16) {
+        if (seen) ZL_SAMPLE(false, true);
+        else ZL_SAMPLE(false, false);
+    } else {
+        if (seen) ZL_SAMPLE(true, true);
+        else ZL_SAMPLE(true, false);
+    }
+#undef ZL_SAMPLE
+    const int e = zl_launch_status();
+    if (e) return e;
+    hipLaunchKernelGGL(k_spec_sample_accept, dim3((unsigned)((b + 63) / 64)), dim3(64), 0, hs, drafts, out_tokens, out_logprobs, accepted, tokens,
+                       positions, placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q, seen, seen_ld);
+    return zl_launch_status();
 }
 
 }  // namespace
@@ -450,46 +752,43 @@ extern "C" {
 int zl_sample_advance(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
                       const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
                       int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out, zl_stream_t s) {
-    ZL_CHECK_ARG(logits && temperature && top_k && top_p, ZL_EINVAL);
-    ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
-    ZL_CHECK_ARG(tokens || next_tokens, ZL_EINVAL);
-    ZL_CHECK_ARG(rows >= 1 && n >= 1 && ld >= n && n < ((int64_t)1 << 31) && rows < ((int64_t)1 << 31), ZL_ESHAPE);
-    ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
-    const dim3 g((unsigned)rows), b(kThreads);
-    hipStream_t hs = (hipStream_t)s;
-    if (type == ZL_T_F16)
-        hipLaunchKernelGGL((k_sample_advance<false, false>), g, b, 0, hs, (const uint16_t*)logits, ld, (int)n, 1, temperature, top_k, top_p, seeds, draws,
-                           u_in, tokens, positions, placement, valid_lens, next_tokens, logprobs, u_out);
-    else
-        hipLaunchKernelGGL((k_sample_advance<true, false>), g, b, 0, hs, (const uint16_t*)logits, ld, (int)n, 1, temperature, top_k, top_p, seeds, draws,
-                           u_in, tokens, positions, placement, valid_lens, next_tokens, logprobs, u_out);
-    return zl_launch_status();
+    return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
+                                 next_tokens, logprobs, u_out, nullptr, nullptr, nullptr, 0, s);
+}
+
+int zl_sample_advance_ex(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
+                         const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
+                         int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
+                         const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
+    return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
+                                 next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld, s);
 }
 
 int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
                           const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
                           const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
                           int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out, zl_stream_t s) {
-    ZL_CHECK_ARG(logits && temperature && top_k && top_p && drafts && accepted && out_tokens, ZL_EINVAL);
-    ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
-    ZL_CHECK_ARG(out_logprobs || !logprobs, ZL_EINVAL);                 // the task's log-probability is read from its rows'
-    ZL_CHECK_ARG(b >= 1 && len_q >= 2 && len_q <= 32 && n >= 1 && ld >= n && n < ((int64_t)1 << 31) && b < ((int64_t)1 << 31) &&
-                     b * len_q < ((int64_t)1 << 31),
+    return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
+                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, nullptr, nullptr, nullptr, 0, s);
+}
+
+int zl_spec_sample_accept_ex(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
+                             const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
+                             const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
+                             int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
+                             const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
+    return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
+                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, rep_penalty, presence, seen,
+                                     seen_ld, s);
+}
+
+int zl_seen_mark(uint32_t* seen, int64_t seen_ld, int64_t b, int64_t n, const int32_t* tokens, int64_t n_tok, int64_t tok_ld, zl_stream_t s) {
+    ZL_CHECK_ARG(seen && tokens, ZL_EINVAL);
+    ZL_CHECK_ARG(b >= 1 && n >= 1 && n < ((int64_t)1 << 31) && n_tok >= 1 && tok_ld >= n_tok && seen_ld >= (n + 31) / 32 &&
+                     b * n_tok < ((int64_t)1 << 39),
                  ZL_ESHAPE);
-    ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
-    // the picks: one 1024-thread workgroup per logit row, zl_sample_advance's kernel under the task's parameters, into out_tokens
-    const dim3 g((unsigned)(b * len_q)), blk(kThreads);
-    hipStream_t hs = (hipStream_t)s;
-    if (type == ZL_T_F16)
-        hipLaunchKernelGGL((k_sample_advance<false, true>), g, blk, 0, hs, (const uint16_t*)logits, ld, (int)n, (int)len_q, temperature, top_k,
-                           top_p, seeds, draws, u_in, out_tokens, nullptr, nullptr, nullptr, nullptr, out_logprobs, u_out);
-    else
-        hipLaunchKernelGGL((k_sample_advance<true, true>), g, blk, 0, hs, (const uint16_t*)logits, ld, (int)n, (int)len_q, temperature, top_k,
-                           top_p, seeds, draws, u_in, out_tokens, nullptr, nullptr, nullptr, nullptr, out_logprobs, u_out);
-    const int e = zl_launch_status();
-    if (e) return e;
-    hipLaunchKernelGGL(k_spec_sample_accept, dim3((unsigned)((b + 63) / 64)), dim3(64), 0, hs, drafts, out_tokens, out_logprobs, accepted, tokens,
-                       positions, placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q);
+    hipLaunchKernelGGL(k_seen_mark, dim3((unsigned)((b * n_tok + 255) / 256)), dim3(256), 0, (hipStream_t)s, seen, seen_ld, b, (int)n, tokens, n_tok,
+                       tok_ld);
     return zl_launch_status();
 }
 

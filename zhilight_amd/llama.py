@@ -979,6 +979,11 @@ class SamplerState:
     row_logprobs: Optional[torch.Tensor] = None
     row_u: Optional[torch.Tensor] = None
     row_bufs: Optional[Dict[int, tuple]] = None
+    # penalties inside the sampling launch (new_sampler's repetition_penalty / presence_penalty): all three set, or all None = off.
+    # seen: the bitmap of the ids each task has emitted (and the caller's penalty_tokens); the sampling kernels read and extend it
+    repetition_penalty: Optional[torch.Tensor] = None   # (B) fp32
+    presence_penalty: Optional[torch.Tensor] = None     # (B) fp32    != 0: takes precedence over the factor
+    seen: Optional[torch.Tensor] = None                 # (B, ceil(vocab / 32)) int32: token i = bit i & 31 of word i >> 5
 
 
 class _PromptRows:
@@ -1980,7 +1985,8 @@ class LLaMA:
         row (b, i) samples under task b's temperature / top-k / top-p with the uniform of counter draws[b] + i, a draft is accepted
         iff the pick equals it -- for a deterministic drafter exactly the speculative-sampling rule -- and draws += accepted + 1,
         so the tokens a task emits are the same function of (logits, seed, tokens emitted so far) as step_sample's: speculation
-        changes the speed, not the sample.  Everything up to the logits is the same.  sampler.row_logprobs / row_u (B, len_q) hold
+        changes the speed, not the sample -- with the sampler's penalties too: row i is penalised by the task's emitted tokens and
+        the drafts in front of it, and only the emitted tokens enter sampler.seen.  Everything up to the logits is the same.  sampler.row_logprobs / row_u (B, len_q) hold
         the emitted tokens' tempered log-probabilities (NaN behind the bonus token) and every row's uniform; sampler.logprobs[b]
         keeps step_sample's meaning, the log-probability of the token now pending in ctx.tokens[b].  The two row buffers follow
         the view's rule: the first eager call per K allocates them.
@@ -2059,7 +2065,8 @@ class LLaMA:
             ops.spec_sample_accept(logits, drafts, sampler.temperature, sampler.top_k, sampler.top_p, seeds=sampler.seeds, draws=sampler.draws,
                                    tokens=ctx.tokens, positions=ctx.positions, placement=ctx.placement, valid_lens=ctx.valid_lens,
                                    accepted=accepted, out_tokens=out_tokens, out_logprobs=sampler.row_logprobs, logprobs=sampler.logprobs,
-                                   u_out=sampler.row_u)
+                                   u_out=sampler.row_u, rep_penalty=sampler.repetition_penalty, presence=sampler.presence_penalty,
+                                   seen=sampler.seen)
         ctx.steps_left -= len_q
         return SpecResult(logits, accepted, out_tokens)
 
@@ -2152,10 +2159,16 @@ class LLaMA:
         return [o[:max_new_tokens] for o in out], stats
 
     # ---- sampling steps -----------------------------------------------------------------------------
-    def new_sampler(self, ctx: DynBatchContext, temperature=1.0, top_k=0, top_p=1.0, seed=0) -> SamplerState:
+    def new_sampler(self, ctx: DynBatchContext, temperature=1.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0, presence_penalty=0.0,
+                    penalty_tokens=None) -> SamplerState:
         """The state for step_sample.  temperature / top_k / top_p / seed: a scalar for every task or a sequence of B values.
         temperature 0 = greedy; top_k 0 = off; top_p 1 = off; a scalar seed s gives task j the seed s + j, so the tasks draw different
-        streams and a task's stream does not depend on the rest of the batch."""
+        streams and a task's stream does not depend on the rest of the batch.
+        repetition_penalty (> 0, 1 = off) / presence_penalty (0 = off; it takes precedence): the reference generator's knobs, a scalar
+        or B values, applied inside the sampling launch to the ids a task has emitted: the pending ctx.tokens entry and every pick
+        from here on (the reference penalises generated tokens only).  penalty_tokens: B sequences of further ids to penalise from
+        the start, such as the prompts.  With every task at (1, 0) and no penalty_tokens the state carries no bitmap and the steps
+        are the unpenalised ones."""
         b, dev = ctx.tokens.numel(), ctx.tokens.device
 
         def per_task(v, what):
@@ -2182,7 +2195,33 @@ class LLaMA:
             raise ops.ZLError("new_sampler: seed is an integer")
         sd = [int(v) + (j if scalar_seed else 0) for j, v in enumerate(sd)]
         sd = [((v + (1 << 63)) % (1 << 64)) - (1 << 63) for v in sd]        # the 64 bits of the key, as int64
-        return SamplerState(temperature=torch.tensor([float(v) for v in t], dtype=torch.float32, device=dev),
+        rp, _ = per_task(repetition_penalty, "repetition_penalty")
+        pp, _ = per_task(presence_penalty, "presence_penalty")
+        if any(not (float(v) > 0.0 and math.isfinite(float(v))) for v in rp):
+            raise ops.ZLError("new_sampler: repetition_penalty > 0 and finite (1 = off)")
+        if any(not math.isfinite(float(v)) for v in pp):
+            raise ops.ZLError("new_sampler: presence_penalty is finite (0 = off)")
+        if penalty_tokens is not None and len(penalty_tokens) != b:
+            raise ops.ZLError(f"new_sampler: {b} tasks, {len(penalty_tokens)} sequences of penalty_tokens")
+        pen = {}
+        if penalty_tokens is not None or any(float(v) != 1.0 for v in rp) or any(float(v) != 0.0 for v in pp):
+            vocab = self.cfg.vocab_size
+            seen = torch.zeros((b, ops.seen_words(vocab)), dtype=torch.int32, device=dev)
+            ops.seen_mark(seen, ctx.tokens.view(b, 1), vocab)               # the pending token is an emitted one
+            if penalty_tokens is not None:
+                rows = [np.asarray(h.cpu() if torch.is_tensor(h) else h, dtype=np.int64).reshape(-1) for h in penalty_tokens]
+                for j, h in enumerate(rows):
+                    if h.size and (h.min() < 0 or h.max() >= vocab):
+                        raise ops.ZLError(f"new_sampler: task {j}: penalty_tokens outside [0, {vocab})")
+                width = max(h.size for h in rows)
+                if width:
+                    ids = np.full((b, width), -1, np.int32)                 # -1: skipped by the kernel
+                    for j, h in enumerate(rows):
+                        ids[j, :h.size] = h
+                    ops.seen_mark(seen, torch.from_numpy(ids).to(dev), vocab)
+            pen = dict(repetition_penalty=torch.tensor([float(v) for v in rp], dtype=torch.float32, device=dev),
+                       presence_penalty=torch.tensor([float(v) for v in pp], dtype=torch.float32, device=dev), seen=seen)
+        return SamplerState(**pen, temperature=torch.tensor([float(v) for v in t], dtype=torch.float32, device=dev),
                             top_k=torch.tensor([int(v) for v in k], dtype=torch.int32, device=dev),
                             top_p=torch.tensor([float(v) for v in p], dtype=torch.float32, device=dev),
                             seeds=torch.tensor(sd, dtype=torch.int64, device=dev), draws=torch.zeros(b, dtype=torch.int64, device=dev),
@@ -2195,7 +2234,9 @@ class LLaMA:
         under TP, where every rank samples the same gathered rows with the same generator state.  (Speculative steps under the
         same sampler: verify / step_lookup(sampler=state); they emit this method's tokens.)  state.logprobs / state.u hold the
         picks' tempered log-probabilities and the uniforms used; state.draws has advanced by one.  Returns (logits, next_tokens
-        int64).  Penalties are the caller's (ops.repetition_penalty on the returned logits changes the NEXT call's input only)."""
+        int64).  Penalties: a state built with new_sampler's repetition_penalty / presence_penalty applies them inside that launch --
+        the kernel reads the classes of state.seen as ops.repetition_penalty would have left them and records its pick there; the
+        returned logits are the raw ones.  The launch count and the host work per step are the same."""
         b = ctx.tokens.numel()
         if state.temperature.numel() != b:
             raise ops.ZLError("step_sample: the state belongs to another batch size")
@@ -2206,7 +2247,8 @@ class LLaMA:
         nxt = self._bufs[key]
         ops.sample_advance(logits, state.temperature, state.top_k, state.top_p, seeds=state.seeds, draws=state.draws, tokens=ctx.tokens,
                            positions=ctx.positions, placement=ctx.placement, valid_lens=ctx.valid_lens, next_tokens=nxt,
-                           logprobs=state.logprobs, u_out=state.u)
+                           logprobs=state.logprobs, u_out=state.u, rep_penalty=state.repetition_penalty, presence=state.presence_penalty,
+                           seen=state.seen)
         ctx.steps_left -= 1
         return logits, nxt
 

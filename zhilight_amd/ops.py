@@ -901,8 +901,47 @@ def lookup_draft(history, hist_lens, k, max_ngram=3, min_ngram=1, new_tokens=Non
     return drafts.view(b, k), match.view(b, 2)
 
 
+def seen_words(n):
+    """The uint32 words of one task's row of a penalty bitmap over n token ids: ceil(n / 32)."""
+    return (int(n) + 31) // 32
+
+
+def seen_mark(seen, tokens, n):
+    """Set the bits of the ids tokens[t, :] (int32 (B, n_tok), unit column stride) that lie in [0, n) in the penalty bitmap seen (B, seen_ld)
+    uint32-sized words (int32 storage), in place (zl_seen_mark, one launch): token i of task t is bit i & 31 of seen[t, i >> 5].  Ids
+    outside [0, n) -- -1 padding -- are skipped.  Seeds a task's set from its prompt or history."""
+    if not (torch.is_tensor(seen) and torch.is_tensor(tokens)):
+        raise ZLError("seen_mark: seen and tokens are tensors")
+    if seen.dtype != torch.int32 or seen.dim() != 2 or not seen.is_contiguous() or seen.shape[1] < seen_words(n) or n < 1:
+        raise ZLError("seen_mark: seen is (B, >= ceil(n / 32)) contiguous int32")
+    if tokens.dtype != torch.int32 or tokens.dim() != 2 or tokens.shape[0] != seen.shape[0] or tokens.shape[1] < 1 or tokens.stride(1) != 1 \
+            or tokens.stride(0) < tokens.shape[1]:
+        raise ZLError("seen_mark: tokens are (B, n_tok >= 1) int32 with unit column stride")
+    if not seen.is_cuda or tokens.device != seen.device:
+        raise ZLError("seen_mark: CUDA tensors on one device")
+    check(lib().zl_seen_mark(_p(seen), _i(seen.shape[1]), _i(seen.shape[0]), _i(n), _p(tokens), _i(tokens.shape[1]), _i(tokens.stride(0)),
+                             _stream()), "seen_mark")
+    return seen
+
+
+def _penalty_args(what, count, n, device, rep_penalty, presence, seen):
+    """The checks of (rep_penalty, presence, seen) of sample_advance / spec_sample_accept; count = the rows / tasks they are per."""
+    if seen is None:
+        if rep_penalty is not None or presence is not None:
+            raise ZLError(f"{what}: rep_penalty / presence act on the classes of seen: give the bitmap")
+        return
+    for t, name in ((rep_penalty, "rep_penalty"), (presence, "presence")):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.numel() == count and t.is_contiguous()):
+            raise ZLError(f"{what}: {name}: contiguous float32 of length {count}, given with seen")
+    if not (torch.is_tensor(seen) and seen.dtype == torch.int32 and seen.dim() == 2 and seen.shape[0] == count and seen.is_contiguous()
+            and seen.shape[1] >= seen_words(n)):
+        raise ZLError(f"{what}: seen: contiguous int32 ({count}, >= ceil(n / 32))")
+    if any(t.device != device for t in (rep_penalty, presence, seen)):
+        raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
+
+
 def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=None, tokens=None, positions=None, placement=None,
-                   valid_lens=None, next_tokens=None, logprobs=None, u_out=None):
+                   valid_lens=None, next_tokens=None, logprobs=None, u_out=None, rep_penalty=None, presence=None, seen=None):
     """The stochastic pick over whole logit rows and the batch state's advance in one launch (zl_sample_advance): logits (rows, n)
     fp16 / bf16 with unit column stride; temperature (rows) fp32, top_k (rows) int32 (<= 0 or >= n: off), top_p (rows) fp32 in [0, 1]
     -- per row.  A row with temperature <= 0 takes argmax_advance's pick; otherwise p = exp((x - max) / T), the classes ordered by p
@@ -911,7 +950,12 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
     Philox4x32-10 words keyed by seeds[r] (int64) and counted by draws[r] (int64), and draws += 1.  tokens <- pick (int32),
     next_tokens <- pick (int64), positions / placement / valid_lens += 1 (each optional, tokens or next_tokens required); logprobs
     (rows) fp32 <- the pick's tempered log-probability (T <= 0: at T = 1); u_out (rows) fp32 <- the uniforms used.  Returns
-    next_tokens if given, else tokens."""
+    next_tokens if given, else tokens.
+    seen (rows, >= ceil(n / 32)) int32, a bitmap of token ids per row (seen_words, seen_mark), with rep_penalty / presence (rows) fp32:
+    zl_sample_advance_ex -- a class whose bit is set is read as repetition_penalty's value of it (presence != 0 ? x - T(presence) :
+    x < 0 ? x * T(factor) : x / T(factor)), the rule above runs on that row, logprobs is the penalised distribution's, the logits in
+    memory stay as they are, and the pick's bit is set in seen: the same results as repetition_penalty over the set + this call
+    without seen, in the one launch."""
     if not all(torch.is_tensor(t) for t in (logits, temperature, top_k, top_p)):
         raise ZLError("sample_advance: logits, temperature, top_k and top_p are tensors")
     if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
@@ -951,7 +995,14 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
     others = (temperature, top_k, top_p, seeds, draws, u, tokens, positions, placement, valid_lens, next_tokens, logprobs, u_out)
     if not logits.is_cuda or any(t is not None and t.device != logits.device for t in others):
         raise ZLError("sample_advance: CUDA logits, every other tensor on the logits' device")
+    _penalty_args("sample_advance", rows, n, logits.device, rep_penalty, presence, seen)
     code = 2 if logits.dtype == torch.float16 else 6
+    if seen is not None:
+        check(lib().zl_sample_advance_ex(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k),
+                                         _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement), _p(valid_lens),
+                                         _p(next_tokens), _p(logprobs), _p(u_out), _p(rep_penalty), _p(presence), _p(seen),
+                                         _i(seen.shape[1]), _stream()), "sample_advance")
+        return next_tokens if next_tokens is not None else tokens
     check(lib().zl_sample_advance(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k), _p(top_p),
                                   _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement), _p(valid_lens), _p(next_tokens),
                                   _p(logprobs), _p(u_out), _stream()), "sample_advance")
@@ -959,7 +1010,8 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
 
 
 def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, draws=None, u=None, tokens=None, positions=None,
-                       placement=None, valid_lens=None, accepted=None, out_tokens=None, out_logprobs=None, logprobs=None, u_out=None):
+                       placement=None, valid_lens=None, accepted=None, out_tokens=None, out_logprobs=None, logprobs=None, u_out=None,
+                       rep_penalty=None, presence=None, seen=None):
     """The acceptance of a speculative step under sampling (zl_spec_sample_accept, two launches): spec_accept with sample_advance's
     pick in the arg-max's place.  logits (B * len_q, n) fp16 / bf16 rows, task-major, unit column stride; drafts (B, K) int32,
     len_q = K + 1 <= 32.  temperature / top_k / top_p / seeds / draws are per task (B); u, u_out and out_logprobs per row (B, len_q).
@@ -970,7 +1022,10 @@ def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, dr
     accepted + 1, draws += accepted + 1 (only where the generator gave the uniforms): one draw per emitted token, so the emitted
     sequence is what sample_advance emits step by step.  out_logprobs <- the picks' tempered log-probabilities, NaN behind the
     bonus token; logprobs (B) <- that of picks[b, accepted] (needs out_logprobs); u_out <- the uniform of every row.  Returns
-    (accepted (B) int32, out_tokens (B, len_q) int32); accepted / out_tokens: buffers to write into (a captured call)."""
+    (accepted (B) int32, out_tokens (B, len_q) int32); accepted / out_tokens: buffers to write into (a captured call).
+    seen (B, >= ceil(n / 32)) int32 with rep_penalty / presence (B) fp32, per task: zl_spec_sample_accept_ex -- row (b, i) is
+    sample_advance(seen=)'s pick under the set seen[b] + the in-range drafts[b, :i] (the row counts only if they were emitted), and
+    the bits of the emitted tokens out_tokens[b, :accepted + 1] are set in seen[b]; the rejected drafts' are not."""
     if not all(torch.is_tensor(t) for t in (logits, drafts, temperature, top_k, top_p)):
         raise ZLError("spec_sample_accept: logits, drafts, temperature, top_k and top_p are tensors")
     if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
@@ -1021,11 +1076,19 @@ def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, dr
               logprobs, u_out)
     if not logits.is_cuda or any(t is not None and t.device != logits.device for t in others):
         raise ZLError("spec_sample_accept: CUDA logits, every other tensor on the logits' device")
+    _penalty_args("spec_sample_accept", b, n, logits.device, rep_penalty, presence, seen)
     if accepted is None:
         accepted = torch.empty(b, dtype=torch.int32, device=logits.device)
     if out_tokens is None:
         out_tokens = torch.empty((b, len_q), dtype=torch.int32, device=logits.device)
     code = 2 if logits.dtype == torch.float16 else 6
+    if seen is not None:
+        check(lib().zl_spec_sample_accept_ex(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts),
+                                             _p(temperature), _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions),
+                                             _p(placement), _p(valid_lens), _p(accepted), _p(out_tokens), _p(out_logprobs), _p(logprobs),
+                                             _p(u_out), _p(rep_penalty), _p(presence), _p(seen), _i(seen.shape[1]), _stream()),
+              "spec_sample_accept")
+        return accepted, out_tokens.view(b, len_q)
     check(lib().zl_spec_sample_accept(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts), _p(temperature),
                                       _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement),
                                       _p(valid_lens), _p(accepted), _p(out_tokens), _p(out_logprobs), _p(logprobs), _p(u_out), _stream()),
