@@ -395,6 +395,161 @@ def test_flash_mla_binding_through_the_cpp_names(dev):
     assert np.array_equal(lse, wlse.cpu().numpy())
 
 
+# ---- MLA routes the tests above do not reach ----------------------------------------------------------------------------------------
+def _mla_split_len(b, h, max_len, algo):
+    """mla_split_len (csrc/mla_attn.hip) restated: keys per split of the 16-heads-per-workgroup kernels (algo 0 / 1) and the wide one (2)"""
+    if algo == 2:
+        want = max(1, min(8, (256 + b - 1) // b))
+    else:
+        want = max(1, ((512 if algo == 1 else 256) + b * ((h + 15) // 16) - 1) // (b * ((h + 15) // 16)))
+    return max(64, ((max_len + want - 1) // want + 63) // 64 * 64)
+
+
+def _mla_vals(bits, code):
+    import attn_profiles as ap
+    return ap.from_bits(bits, code)
+
+
+def _mla_bar_ok(g, E, code):
+    ulp = 2.0 ** (-10 if code == 0 else -7)                               # the bar of test_mla_decode_attention_over_the_latent_cache
+    assert np.isfinite(g).all()
+    assert (np.abs(g - E) <= ulp * np.abs(E) + 2e-5 * np.abs(E).max()).all(), float((np.abs(g - E) / (ulp * np.abs(E) + 2e-5 * np.abs(E).max())).max())
+
+
+def _mla_iid(rng, b, h, max_len, dtype):
+    q = torch.from_numpy((rng.standard_normal((b, h, 576)) * 0.4).astype(np.float32)).to(dtype)
+    bufs = [torch.from_numpy((rng.standard_normal((max_len, 576)) * 0.6).astype(np.float32)).to(dtype) for _ in range(b)]
+    return q, bufs
+
+
+def _mla_fp64(q, bufs, lens, scale):
+    """numpy fp64 statement: (out (b, h, 512), lse (b, h)); a task without keys: zeros, -inf"""
+    out, lse = np.zeros((len(bufs), q.shape[1], 512)), np.full((len(bufs), q.shape[1]), -np.inf)
+    for i, n in enumerate(lens):
+        if n:
+            kv = bufs[i][:n].double().numpy()
+            s = (q[i].double().numpy() @ kv.T) * scale
+            m = s.max(1, keepdims=True)
+            p = np.exp(s - m)
+            out[i] = (p @ kv[:, :512]) / p.sum(1, keepdims=True)
+            lse[i] = m[:, 0] + np.log(p.sum(1))
+    return out, lse
+
+
+@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("dtype,code", [(torch.float16, 0), (torch.bfloat16, 1)])
+@pytest.mark.parametrize("data", ["iid", "stairs"])
+def test_mla_combine_with_more_than_64_records(oracle, dev, dtype, code, data, algo):
+    """k_mla_combine's second block of records: ONE task, 16 heads, a 4288-slot buffer.  One head group, so the launcher wants 256
+    (VALU kernel: 512) splits, ceil(4288 / 256) = 17 keys rounds up to the 64-key minimum: 4288 / 64 = 67 records, 64 + 3.  Visible
+    lengths around record 64's edge (4095: 64 records, 4096: 64 full ones, 4097: a 65th with one key) and the whole buffer; i.i.d. rows
+    and `stairs` (one level per 64-key record, neighbours 30-110 apart: records of weight exactly 0 on both sides of the block edge)."""
+    from zhilight_amd import ops
+    import attn_profiles as ap
+    h, max_len, scale = 16, 4288, 0.1147
+    assert _mla_split_len(1, h, max_len, algo) == 64 and (max_len + 63) // 64 == 67
+    rng = np.random.default_rng(4288 + code)
+    for n in (4095, 4096, 4097, 4288):
+        if data == "iid":
+            q, bufs = _mla_iid(rng, 1, h, max_len, dtype)
+            qb, kvb = _bits(q), [_bits(bufs[0])]
+        else:
+            c = ap.build_mla("stairs", rng, max_len, [n], h, code, scale)
+            qb, kvb = c.q, c.kv
+        qd = _t(qb.view(np.int16), dev, dtype)
+        dbuf = _t(kvb[0].view(np.int16), dev, dtype)
+        addrs = torch.tensor([dbuf.data_ptr()], dtype=torch.int64, device=dev)
+        got = ops.mla_decode_attention(qd, torch.tensor([max_len], dtype=torch.int32, device=dev), addrs, scale, max_len,
+                                       torch.tensor([n], dtype=torch.int32, device=dev), algo=algo)
+        E = _mla_vals(oracle.mla_decode_attn(qb, [max_len], [n], kvb, scale=scale, dtype=code, flavour="E"), code)
+        _mla_bar_ok(_mla_vals(_bits(got), code), E, code)
+
+
+def _paged(rng, bufs, b, page, max_blocks, spare, dtype, dev):
+    num_blocks = b * max_blocks + spare
+    order = rng.permutation(num_blocks)[: b * max_blocks].astype(np.int32).reshape(b, max_blocks)
+    kcache = torch.full((num_blocks, page, 1, 576), float("nan"), dtype=dtype, device=dev)       # the spare blocks stay NaN
+    for i in range(b):
+        kcache[torch.from_numpy(order[i].astype(np.int64)).to(dev), :, 0, :] = bufs[i].view(max_blocks, page, 576)
+    return kcache, torch.from_numpy(order).to(dev)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("b,h,page,max_blocks", [(16, 128, 64, 32), (4, 16, 128, 3), (32, 128, 64, 16)],
+                         ids=["wide_b16_h128_page64", "b4_h16_page128", "one_split_b32_h128"])
+def test_flash_mla_paged_routes(dev, dtype, b, h, page, max_blocks):
+    """ds::mha_fwd_kvcache_mla beyond the small geometry of test_flash_mla_binding_over_a_paged_cache: the WIDE kernel's paged form
+    (16 tasks x 128 heads over 2048 keys: zl_mla_decode_attn_paged picks it), 128-key pages, and the single-split route that writes
+    rows and softmax_lse without a combine launch (32 tasks x 8 head groups = 256 workgroups already: one split of 16 * 64 = 1024 keys).
+    Bits equal to the contiguous call's (the same plan); lse against the fp64 log-sum-exp, -inf for a task without keys."""
+    from zhilight_amd import ops
+    rng = np.random.default_rng(b * h + page)
+    max_len, scale = page * max_blocks, 0.1147
+    if b == 16:
+        assert _mla_split_len(b, h, max_len, 2) == 256           # min(8, 256 / 16) = 8 splits of 2048 / 8 keys
+    if b == 32:
+        assert _mla_split_len(b, h, max_len, 0) == max_len       # 256 / (32 * 8) = 1 split
+    pool = [1, 16, 17, 63, 64, 65, 129, max_len // 2 + 1, max_len - 1, max_len - 2, 0]
+    lens = [1, 64, 65, 300] if b == 4 else [pool[i % len(pool)] if i < len(pool) else int(rng.integers(1, max_len)) for i in range(b)]
+    q, bufs = _mla_iid(rng, b, h, max_len, dtype)
+    q, bufs = q.to(dev), [t.to(dev) for t in bufs]
+    kcache, table = _paged(rng, bufs, b, page, max_blocks, 3, dtype, dev)
+    seqlens = torch.tensor(lens, dtype=torch.int32, device=dev)
+    out, lse = ops.mha_fwd_kvcache_mla(q.view(b, 1, h, 576), kcache, 512, seqlens, table, scale)
+    addrs = torch.tensor([t.data_ptr() for t in bufs], dtype=torch.int64, device=dev)
+    want = ops.mla_decode_attention(q, seqlens, addrs, scale, max_len, algo=0)
+    assert torch.isfinite(out.float()).all()
+    assert torch.equal(out.view(b, h, 512).view(torch.int16), want.view(torch.int16))
+    _, ref_lse = _mla_fp64(q.cpu(), [t.cpu() for t in bufs], lens, scale)
+    got_lse = lse[:, 0].double().cpu().numpy()
+    live = np.array(lens) > 0
+    assert np.abs(got_lse[live] - ref_lse[live]).max() <= 2e-5, np.abs(got_lse[live] - ref_lse[live]).max()
+    assert np.isneginf(got_lse[~live]).all()
+    for i in np.nonzero(~live)[0]:
+        assert float(out[i].float().abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("algo", [0, 1, 2])
+@pytest.mark.parametrize("dtype,code", [(torch.float16, 0), (torch.bfloat16, 1)])
+def test_mla_length_clamps(dev, dtype, code, algo):
+    """visibility is min(buf_lens, valid_lens): with valid_lens = None the buffer length alone decides, with valid_lens past the buffer
+    the clamp does.  The slots behind buf_lens hold finite rows that score 125 above every visible key and carry a value part of 1e4
+    (attn_profiles hidden_spike): one of them in the maximum or in the sum is not subtle."""
+    from zhilight_amd import ops
+    import attn_profiles as ap
+    h, buf, vis = 128, 768, [1, 700, 767]
+    c = ap.build_mla("hidden_spike", np.random.default_rng(768 + code), buf, vis, h, code, ap.MLA_SCALE)
+    dbufs = [_t(a.view(np.int16), dev, dtype) for a in c.kv]
+    addrs = torch.tensor([t.data_ptr() for t in dbufs], dtype=torch.int64, device=dev)
+    qd = _t(c.q.view(np.int16), dev, dtype)
+    buf_lens = torch.tensor(vis, dtype=torch.int32, device=dev)
+    for valid in (None, torch.tensor([buf, 1 << 20, vis[2] + 1], dtype=torch.int32, device=dev)):
+        got = ops.mla_decode_attention(qd, buf_lens, addrs, ap.MLA_SCALE, buf, valid, algo=algo)
+        _mla_bar_ok(_mla_vals(_bits(got), code), c.ref, code)
+
+
+@pytest.mark.parametrize("dtype,code", [(torch.float16, 0), (torch.bfloat16, 1)])
+@pytest.mark.parametrize("h,b,max_len", [(4, 3, 768), (12, 3, 768), (256, 16, 2048)])
+def test_mla_head_counts(oracle, dev, dtype, code, h, b, max_len):
+    """fewer heads than one 16-head group (4, 12), and 256 (two query rows folded over 128 heads) at 16 tasks x 2048 keys, where 128
+    heads would go to the wide kernel: 256 must not.  Against flavour E (256 heads: the numpy fp64 statement, E before its rounding)."""
+    from zhilight_amd import ops
+    rng = np.random.default_rng(h)
+    pool = [1, 65, 700, 16, 17, 63, 64, 129, max_len // 2 + 1, max_len - 1, max_len - 2]
+    lens = [pool[i % len(pool)] for i in range(b)]
+    q, bufs = _mla_iid(rng, b, h, max_len, dtype)
+    dbufs = [t.to(dev) for t in bufs]
+    addrs = torch.tensor([t.data_ptr() for t in dbufs], dtype=torch.int64, device=dev)
+    scale = 0.1147
+    got = ops.mla_decode_attention(q.to(dev), torch.tensor([max_len] * b, dtype=torch.int32, device=dev), addrs, scale, max_len,
+                                   torch.tensor(lens, dtype=torch.int32, device=dev))
+    if h <= 16:
+        E = _mla_vals(oracle.mla_decode_attn(_bits(q), [max_len] * b, lens, [_bits(t) for t in bufs], scale=scale, dtype=code, flavour="E"), code)
+    else:
+        E, _ = _mla_fp64(q, bufs, lens, scale)
+    _mla_bar_ok(_mla_vals(_bits(got), code), E, code)
+
+
 @pytest.mark.parametrize("tokens", [3, 37])
 @pytest.mark.parametrize("router,dtype", [("top_k", torch.bfloat16), ("group", torch.bfloat16), ("top_k", torch.float16)])
 def test_moe_feed_forward_flow_equals_the_per_token_sum(dev, tokens, router, dtype):
