@@ -467,6 +467,24 @@ int zl_copy_to_rag_buffer2(const int32_t* placement, const int32_t* buf_lens, co
  * reference issues them one after the other (zl_quant_copy_to_rag_buffer is the fused form). */
 int zl_copy_to_rag_buffer_bytes(const int32_t* placement, const int32_t* buf_lens, const void* k_src, const void* v_src, void* const* k_bufs,
                                 void* const* v_bufs, int64_t b, int64_t len_q, int64_t hkv, int64_t row_bytes, int bshd, zl_stream_t s);
+/* Block copies between the ragged buffers and a prefix-cache pool, ONE launch for every descriptor, every layer and both K and V
+ * (the reference moves the same blocks with one memcpy per layer, K/V and block: TransformerBuffer::dump_slice / load_slice under
+ * generator::PrefixCache, src/generator/prefix_cache.hpp).  desc (n, 3) int32 on the device: task, first slot, pool block;
+ * k_bufs / v_bufs (layers, B) DEVICE pointer tables (DynBatchContext.k_addrs / v_addrs; the INT8 cache's scales: ks_addrs /
+ * vs_addrs); to_pool = 1 copies the `block` rows from `first slot` of the task's buffers into the pool block, 0 copies them back.
+ * pool: (num_blocks, layers, 2, block, hkv, row_bytes) bytes under BSHD, (num_blocks, layers, 2, hkv, block, row_bytes) under BHSD:
+ * one block's bytes are contiguous, a run keeps the buffers' own order.  row_bytes % 4 == 0 as in zl_copy_to_rag_buffer_bytes: 16-bit
+ * rows (2 * dim_head), u8 code rows (dim_head), fp32 scale "rows" (4).  Runs whose two addresses and length are 16-byte aligned move
+ * as 16-byte vectors, others as dwords.  A descriptor whose rows do not lie inside buf_lens[task] is dropped by the kernel (never a
+ * stray access); pool block ids are the CALLER's to bound, and so is keeping the destinations of one call distinct -- no pool block
+ * written twice, no buffer row loaded twice (ops.kv_blocks_copy checks all three on the host).  No allocation, no synchronisation; n == 0: ZL_OK without a launch.  ZL_EINVAL: null pointer, non-positive size;
+ * ZL_ESHAPE: row_bytes % 4, piece_bytes % 16; ZL_ELIMIT: beyond the grid.
+ * _ex: piece_bytes = bytes of a run that one workgroup moves (0 = the default, 8 KiB; tools/bench_prefix_cache.py sweeps it). */
+int zl_kv_blocks_copy(const int32_t* desc, int64_t n, void* const* k_bufs, void* const* v_bufs, const int32_t* buf_lens, void* pool,
+                      int64_t layers, int64_t b, int64_t block, int64_t hkv, int64_t row_bytes, int bshd, int to_pool, zl_stream_t s);
+int zl_kv_blocks_copy_ex(const int32_t* desc, int64_t n, void* const* k_bufs, void* const* v_bufs, const int32_t* buf_lens, void* pool,
+                         int64_t layers, int64_t b, int64_t block, int64_t hkv, int64_t row_bytes, int bshd, int to_pool,
+                         int64_t piece_bytes, zl_stream_t s);
 
 /* Fused decode-step front end: split fused qkv rows, rotate q and k with cached cos/sin, write q
  * and scatter k,v straight into the ragged buffers (rope_qk_cache + copy_to_rag_buffer2 in one

@@ -1776,6 +1776,67 @@ class LLaMA:
             self._check_prompt_piece(what, ctx, t, int(pr.numel()), p0, q8_history)
         return tasks, pos0, q8_history
 
+    def new_prefix_cache(self, ctx: DynBatchContext, num_blocks, block_size=128, max_prefix=4096):
+        """A prompt prefix cache (prefix_cache.PrefixCache) for contexts like ctx: a pool of num_blocks blocks of block_size
+        tokens, every layer's K and V, in the context's element type -- model-dtype rows, or for kv_cache_dtype="int8" a u8 code
+        plane and an fp32 scale plane -- and the index over it; at most max_prefix tokens of a prompt are cached.  The defaults
+        are the reference's CACHE_BLOCK_SIZE and CACHE_MAX_PREFIX (src/generator/prefix_cache.hpp).  The cache serves contexts of
+        this kind on this device, on the stream current now (PrefixCache has the rule)."""
+        from .prefix_cache import PrefixCache
+        c = self.cfg
+        if int(num_blocks) < 1 or int(block_size) < 1 or int(max_prefix) < 0:
+            raise ops.ZLError("new_prefix_cache: num_blocks >= 1, block_size >= 1, max_prefix >= 0")
+        return PrefixCache(self.device, c.num_layers, c.num_kv_heads, c.dim_head, c.torch_dtype, ctx.kv_quant, num_blocks, block_size,
+                           max_prefix)
+
+    def prefill_cached(self, ctx: DynBatchContext, cache, tasks, prompts, kv_history=None):
+        """prefill_batch through a prefix cache (the reference's scheduler with enable_prompt_caching, batch_generator.cpp:626-648,
+        1033-1045) -> (logits, matched): matched[j] tokens of prompts[j] -- a multiple of cache.block_size, or 0 -- came from the
+        cache and only the rest was encoded.  In order: every prompt is matched against the index; ONE ops.kv_blocks_copy launch
+        loads all tasks' matched blocks into their buffers (two on an INT8 cache: codes, scales); prefill_batch(ctx, tasks,
+        remainders, pos0=matched, kv_history=kv_history) encodes what is left -- at least one token per task, so logits (n, vocab)
+        and the context are exactly prefill_batch's; ONE save launch (two for INT8) copies every full block of the prompts that
+        the cache does not hold yet into the pool, after which they enter the index.  A block common to two tasks of the call is
+        saved once, from the first of them; when the pool is full the least recently used blocks go, never one this call matched
+        or reserved, and a prompt's blocks are saved only as far as the pool has room.
+        A cached block is identified by ALL the tokens up to its end (prefix_cache.py), so the loaded rows are the rows this
+        prompt would have computed: bit for bit where the prompt kernels are reproducible at the shape.
+        Arguments are prefill_batch's (without pos0: the prompts are whole) and so are its checks; the cache must fit ctx
+        (PrefixCache.fits).  An INT8 context needs kv_history="cache" and head size 128 -- a continued prompt has no other route
+        there -- whether or not anything matches.  Tensor parallelism is not supported.  All of this raises ZLError before any
+        launch and before the index changes.  Prompts are read on the host to be matched: give host tensors (device prompts cost a
+        synchronising copy, as in score)."""
+        if self.tp:
+            raise ops.ZLError("prefill_cached: tensor parallelism is not supported")
+        tasks, _, _ = self._check_prompt_batch("prefill_cached", ctx, tasks, prompts, None, kv_history)
+        if ctx.kv_quant and (kv_history != "cache" or self.cfg.dim_head != 128):
+            raise ops.ZLError("prefill_cached: an INT8 KV cache needs kv_history='cache' and head size 128")
+        c = self.cfg
+        why = cache.fits(ctx)
+        if why is None and (cache.layers, cache.hkv, cache.dim_head, cache.dtype) != (c.num_layers, c.num_kv_heads, c.dim_head, c.torch_dtype):
+            why = "the cache was built for another geometry (layers, KV heads, head size or element type)"
+        if why is not None:
+            raise ops.ZLError(f"prefill_cached: {why}")
+        index, bs = cache.index, cache.block_size
+        toks = [pr.reshape(-1).tolist() for pr in prompts]
+        chains = [index.match(t) for t in toks]
+        matched = [len(ch) * bs for ch in chains]
+        cache.load(ctx, [(t, i * bs, pb) for t, ch in zip(tasks, chains) for i, pb in enumerate(ch)])
+        logits = self.prefill_batch(ctx, tasks, [pr.reshape(-1)[m:] for pr, m in zip(prompts, matched)], pos0=matched, kv_history=kv_history)
+        keep, new, desc = {pb for ch in chains for pb in ch}, [], []
+        try:
+            for t, tk in zip(tasks, toks):
+                pairs = index.reserve(tk, keep)
+                keep.update(pb for _, pb in pairs)
+                new += [pb for _, pb in pairs]
+                desc += [(t, i * bs, pb) for i, pb in pairs]
+            cache.save(ctx, desc)
+        except Exception:
+            index.abort(new)
+            raise
+        index.commit(new)
+        return logits, matched
+
     def score(self, ctx: DynBatchContext, tasks, prompts, pos0=None, labels=None, kv_history=None):
         """prefill_batch that also scores EVERY prompt row against the lm_head (LLaMA::calc_log_prob / calc_greedy_match,
         src/model/llama.cpp:194-244, over nn::log_prob_raw / greedy_match_raw, src/nn/functions/cross_entropy.cu:7-69, 358-403):

@@ -1414,6 +1414,63 @@ def copy_to_rag_buffer2(placement, buf_lens, k_src, v_src, k_addrs, v_addrs, bsh
           "copy_to_rag_buffer2")
 
 
+def kv_blocks_copy(desc, k_addrs, v_addrs, buf_lens, pool, block, hkv, row_bytes, to_pool, bshd=True, buf_lens_host=None,
+                   piece_bytes=0):
+    """zl_kv_blocks_copy: ONE launch that copies, for every descriptor (task, first slot, pool block) of `desc`, every layer and both
+    K and V, `block` rows of the task's buffers into the pool block (to_pool) or back.  desc: a HOST sequence of int triples (it is
+    checked here and uploaded); k_addrs / v_addrs (layers, B) device pointer tables (DynBatchContext.k_addrs / v_addrs, or ks_addrs /
+    vs_addrs for the INT8 cache's scales); buf_lens (B) int32 on the device, buf_lens_host the same numbers where the caller holds
+    them (else they are read back: a synchronisation); pool: a contiguous tensor of num_blocks = pool.shape[0] blocks of
+    layers * 2 * block * hkv * row_bytes bytes each, laid out (layers, 2, block, hkv, row) under BSHD and (layers, 2, hkv, block, row)
+    under BHSD; row_bytes % 4 == 0.  Raises ZLError before any launch for a descriptor whose rows do not fit its task's buffer, a pool
+    block id out of range, or a destination that occurs twice in the call: a pool block when saving, overlapping rows of one task
+    when loading (one pool block may be LOADED into several tasks by one call: two prompts that share a prefix).  An empty desc
+    launches nothing."""
+    _chk_cuda(k_addrs, v_addrs, buf_lens, pool)
+    if k_addrs.dim() != 2 or k_addrs.shape != v_addrs.shape or k_addrs.dtype != torch.int64 or v_addrs.dtype != torch.int64:
+        raise ZLError("kv_blocks_copy: k_addrs / v_addrs are (layers, B) int64 pointer tables")
+    layers, b = k_addrs.shape
+    block, hkv, row_bytes = int(block), int(hkv), int(row_bytes)
+    if buf_lens.dtype != torch.int32 or buf_lens.numel() != b:
+        raise ZLError("kv_blocks_copy: buf_lens is (B) int32")
+    if block < 1 or hkv < 1 or row_bytes < 4 or row_bytes % 4:
+        raise ZLError("kv_blocks_copy: block, hkv >= 1 and row_bytes a positive multiple of 4")
+    block_bytes = layers * 2 * block * hkv * row_bytes
+    num_blocks = pool.shape[0] if pool.dim() else 0
+    if num_blocks < 1 or pool.numel() * pool.element_size() != num_blocks * block_bytes:
+        raise ZLError(f"kv_blocks_copy: the pool does not hold {num_blocks} blocks of {block_bytes} bytes")
+    desc = [tuple(int(x) for x in d) for d in (desc.tolist() if hasattr(desc, "tolist") else desc)]
+    if not desc:
+        check(lib().zl_kv_blocks_copy(None, _i(0), _p(k_addrs), _p(v_addrs), _p(buf_lens), _p(pool), _i(layers), _i(b), _i(block),
+                                      _i(hkv), _i(row_bytes), C.c_int(int(bshd)), C.c_int(int(to_pool)), _stream()), "kv_blocks_copy")
+        return None
+    lens = buf_lens.tolist() if buf_lens_host is None else [int(x) for x in buf_lens_host]
+    if len(lens) != b:
+        raise ZLError("kv_blocks_copy: one buffer length per task")
+    seen, rows = set(), {}
+    for d in desc:
+        if len(d) != 3:
+            raise ZLError("kv_blocks_copy: a descriptor is (task, first slot, pool block)")
+        task, slot, pb = d
+        if not 0 <= task < b or slot < 0 or slot + block > lens[task]:
+            raise ZLError(f"kv_blocks_copy: rows {slot} .. {slot + block - 1} of task {task} lie outside its buffer")
+        if not 0 <= pb < num_blocks:
+            raise ZLError(f"kv_blocks_copy: pool block {pb} outside the pool's {num_blocks}")
+        if to_pool:
+            if pb in seen:
+                raise ZLError(f"kv_blocks_copy: pool block {pb} is written twice in one call")
+            seen.add(pb)
+        else:
+            if any(abs(slot - other) < block for other in rows.get(task, ())):
+                raise ZLError(f"kv_blocks_copy: rows {slot} .. {slot + block - 1} of task {task} are written twice in one call")
+            rows.setdefault(task, []).append(slot)
+    desc_dev = torch.tensor(desc, dtype=torch.int32).to(pool.device)
+    fn, extra = (lib().zl_kv_blocks_copy_ex, (_i(piece_bytes),)) if piece_bytes else (lib().zl_kv_blocks_copy, ())
+    check(fn(_p(desc_dev), _i(len(desc)), _p(k_addrs), _p(v_addrs), _p(buf_lens), _p(pool), _i(layers), _i(b), _i(block), _i(hkv),
+             _i(row_bytes), C.c_int(int(bshd)), C.c_int(int(to_pool)), *extra, _stream()), "kv_blocks_copy")
+    return desc_dev
+
+
 def rope_scatter_decode(cos, sin, qkv, placement, buf_lens, k_addrs, v_addrs, num_heads, num_kv_heads, dim_head,
                         neox=True, bshd=True, q_out=None):
     """rope_qk_cache + copy_to_rag_buffer2 fused for len_q == 1 decode rows."""
