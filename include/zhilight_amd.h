@@ -1066,6 +1066,44 @@ int zl_spec_sample_accept_ex(const void* logits, int type, int64_t b, int64_t le
                              int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s);
 int zl_seen_mark(uint32_t* seen, int64_t seen_ld, int64_t b, int64_t n, const int32_t* tokens, int64_t n_tok, int64_t tok_ld, zl_stream_t s);
+/* Logit bias and top-N log-probabilities inside the sampling step (csrc/sample_rows.hip): the two remaining per-task knobs of the
+ * reference's GeneratorArg (zhilight/dynamic_batch.py:91-119).  The _ex calls' arguments, then nine more.
+ * BIAS (SearcherImplV1::add_logit_bias, src/generator/batch_generator.cpp:1709-1729, applied behind the repetition penalty, then
+ * pick_top_k :1765-1766).  A task owns at most 1024 distinct ids with an fp32 bias each: bias_ids / bias_vals (rows or b, bias_ld),
+ * row t's first bias_cnt[t] ids ascending and distinct, 0 <= bias_cnt[t] <= bias_ld <= 1024, and bias_bits (rows or b, bias_bits_ld >=
+ * ceil(n / 32)), the ids as a bitmap in seen's layout (zl_seen_mark builds it).  A class i of the set is read as
+ *   T(f32(y_i) + f32(T(bias_i)))        zl_scatter_logits' add expression, one rounding to the logits' type T
+ * where y_i is what the row holds for the class AFTER the penalty: pen(x_i) if i is in the task's seen set (or, in a speculative
+ * step, a draft in front of the row), x_i otherwise.  Everything behind it is zl_sample_advance's rule on that row, unchanged: every
+ * output equals zl_repetition_penalty over the set, then zl_scatter_logits(add), then the plain call on the modified copy, bit for
+ * bit.  The logits in memory are NOT modified.  A bias of -inf bans the class (p = 0, never picked); a row whose largest value
+ * becomes -inf is a plain row.  NaN / +inf biases are the caller's to refuse (ops.logit_bias_pack does).  A bias entry does not
+ * enter seen; seen == NULL with a bias is legal (no penalty, no drafts' penalty, no bit set).  A bias bit without a list entry
+ * reads the class unbiased, a list entry without a bit is ignored, and nothing is read beyond the row, the bitmaps' ceil(n / 32)
+ * words and the first bias_cnt[t] (clamped to bias_ld) list entries, whatever they hold.  Per row in zl_sample_advance_opts, per task
+ * in zl_spec_sample_accept_opts, like the penalty arguments.
+ * TOP-N (record_top_logprobs, src/generator/batch_generator.cpp:923-948: log_softmax_bias with the task's temperature, then TopK,
+ * over the penalised and biased logits), 1 <= top_n <= 32: top_ids / top_logprobs (rows, top_n), or (b, len_q, top_n) in the
+ * speculative call, <- per row the first min(top_n, n) classes of the kernel's order over the row as the pick saw it -- larger
+ * value first, then lower index, -0.0 and +0.0 one value -- each with (y_i - max) / t - lse, the pick's own fp32 instructions:
+ * where the pick is among them its entry is bit-equal to logprobs[r].  Slots at or behind n, every slot of a plain row (largest
+ * value NaN or +-inf), and in the speculative call the rows behind the bonus token: id -1, NaN.  A greedy row (T <= 0) uses t = 1.
+ * All nine NULL / 0: the calls ARE the _ex ones.  ZL_EINVAL: some but not all of the four bias pointers; top_n > 0 without both
+ * outputs.  ZL_ESHAPE: bias_ld > 1024 or < 1, bias_bits_ld < ceil(n / 32) (with a bias given); top_n < 0 or > 32.  Otherwise the _ex
+ * calls' codes.  Launches, stores and determinism as the _ex calls. */
+int zl_sample_advance_opts(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
+                           const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
+                           int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
+                           const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
+                           const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits, int64_t bias_bits_ld,
+                           int top_n, int32_t* top_ids, float* top_logprobs, zl_stream_t s);
+int zl_spec_sample_accept_opts(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
+                               const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
+                               const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
+                               int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
+                               const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
+                               const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits,
+                               int64_t bias_bits_ld, int top_n, int32_t* top_ids, float* top_logprobs, zl_stream_t s);
 /* The logit post-processing of the reference's batch generator (src/generator/beam_util.cu, 3rd/bmengine/bmengine/functions/{softmax,topk}.cu):
  * what src/generator/batch_generator.cpp calls between a decode step and its host-side search, so that the py_export surface (zhilight.C)
  * links against this boundary.  Rows of n logits of type ZL_T_F16 / ZL_T_BF16 / ZL_T_F32; fp32 arithmetic, one rounding to T.

@@ -17,7 +17,15 @@
      built from the commit before this one; its zl_sample_advance and its two-launch form are measured in the same process,
      replays alternated with this commit's.
 
-usage: python tools/bench_sample.py [--launch-only | --step-only | --penalties [--parent-so PATH]] [--reps 30] [--launches 100]"""
+  4. --bias / --top-n (profiles/sample_opts.txt): the launch alone with a logit bias (1 and 300 entries per row, all 0.0, so that the
+     host forms leave the rows as they are), with top-N (5 and 20), and with both on top of the 1 % penalty bitmap -- each next to the
+     same call without the option, and next to the host forms: zl_scatter_logits(add) + zl_sample_advance, and zl_repetition_penalty +
+     zl_scatter_logits(add) + zl_sample_advance.  The OFF path -- zl_sample_advance and zl_sample_advance_ex as they are called today --
+     is measured from this library and from --parent-so in the same process.  With --step: the whole step_sample with both options
+     against the plain one at batch 1, 8 and 32.
+
+usage: python tools/bench_sample.py [--launch-only | --step-only | --penalties | --bias | --top-n [--step]] [--parent-so PATH] [--reps 30]
+       [--launches 100]"""
 import argparse
 import ctypes as C
 import os
@@ -181,11 +189,123 @@ def penalty_leg(dev, reps, launches, parent_so):
         print("  %4d | %-30s | %-44s | %7.2f [%7.2f .. %7.2f]" % ((rows, name, which) + _stats(ms, launches)), flush=True)
 
 
+def opts_leg(dev, reps, launches, parent_so, with_bias, with_top, rows_list=(1, 8)):
+    from zhilight_amd._lib import lib
+    libs = {"this": lib()}
+    if parent_so:
+        libs["parent"] = C.CDLL(parent_so)
+    p = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)           # noqa: E731
+    i64 = C.c_int64
+    words = ops.seen_words(VOCAB)
+    print("# the launch alone with a logit bias / top-N, warm rows of %d fp16 logits (normal, sigma 2); the penalty set holds %d ids per row "
+          "(factor 1.0), the biases are 0.0: us per call, median [p10 .. p90] over %d alternated replays of %d calls"
+          % (VOCAB, VOCAB // 100, reps, launches))
+    graphs, keep = {}, []
+    for rows in rows_list:
+        gen = torch.Generator(device="cpu").manual_seed(rows)
+        logits = (torch.randn((rows, VOCAB), generator=gen) * 2).to(torch.float16).to(dev)
+        ids = torch.stack([torch.randperm(VOCAB, generator=gen)[:VOCAB // 100] for _ in range(rows)]).to(torch.int32).to(dev)
+        bid = torch.arange(rows, dtype=torch.int32, device=dev).view(rows, 1).expand(rows, ids.shape[1]).contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        one, zero = torch.ones(ids.numel(), **f32), torch.zeros(ids.numel(), **f32)
+        tok = torch.zeros(rows, dtype=torch.int32, device=dev)
+        bias = {}
+        for cnt in (1, 300):
+            maps = [{int(i): 0.0 for i in torch.randperm(VOCAB, generator=gen)[:cnt]} for _ in range(rows)]
+            b_ids, b_vals, b_cnt, b_bits = ops.logit_bias_pack(maps, VOCAB, dev)
+            flat_ids = b_ids.reshape(-1).contiguous()
+            b_bid = torch.arange(rows, dtype=torch.int32, device=dev).view(rows, 1).expand(rows, cnt).reshape(-1).contiguous()
+            bias[cnt] = (b_ids, b_vals, b_cnt, b_bits, flat_ids, b_bid, torch.zeros(rows * cnt, **f32))
+        top = {n: (torch.empty((rows, n), dtype=torch.int32, device=dev), torch.empty((rows, n), **f32)) for n in (5, 20)}
+        for name, t, k, tp, lp in (SETS[0], SETS[3]):
+            a = dict(T=torch.full((rows,), t, **f32), k=torch.full((rows,), k, dtype=torch.int32, device=dev), p=torch.full((rows,), tp, **f32),
+                     seeds=torch.arange(rows, dtype=torch.int64, device=dev), draws=torch.zeros(rows, dtype=torch.int64, device=dev),
+                     lp=torch.empty(rows, **f32) if lp else None, seen=torch.zeros((rows, words), dtype=torch.int32, device=dev))
+            ops.seen_mark(a["seen"], ids, VOCAB)
+            head = lambda a=a: (p(logits), C.c_int(2), i64(rows), i64(VOCAB), i64(VOCAB), p(a["T"]), p(a["k"]), p(a["p"]), p(a["seeds"]),   # noqa: E731
+                                p(a["draws"]), p(None), p(tok), p(None), p(None), p(None), p(None), p(a["lp"]), p(None))
+            stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)                                                             # noqa: E731
+            pen = lambda a=a: (p(one), p(zero), p(a["seen"]), i64(words))                                                                    # noqa: E731
+            nopen = lambda: (p(None), p(None), p(None), i64(0))                                                                              # noqa: E731
+
+            def nine(cnt, n):
+                b = bias.get(cnt)
+                t_ = top.get(n)
+                return ((p(b[0]), p(b[1]), p(b[2]), i64(cnt), p(b[3]), i64(words)) if b else (p(None), p(None), p(None), i64(0), p(None), i64(0))) + \
+                       ((C.c_int(n), p(t_[0]), p(t_[1])) if t_ else (C.c_int(0), p(None), p(None)))
+
+            def cell(fn):
+                def run():
+                    for _ in range(launches):
+                        r = fn()
+                        assert (r[-1] if isinstance(r, tuple) else r) == 0
+                return _graph(run)
+
+            def scatter(l, cnt):
+                b = bias[cnt]
+                assert l.zl_scatter_logits(p(b[6]), p(b[4]), p(b[5]), p(logits), i64(b[4].numel()), i64(VOCAB), C.c_int(1), C.c_int(2), stream()) == 0
+
+            def penalise(l):
+                assert l.zl_repetition_penalty(p(one), p(zero), p(ids), p(bid), p(logits), i64(ids.numel()), i64(VOCAB), C.c_int(2), stream()) == 0
+            this = libs["this"]
+            for which, l in libs.items():                                                # the off path, both libraries
+                l.zl_sample_advance.argtypes = this.zl_sample_advance.argtypes
+                l.zl_sample_advance_ex.argtypes = this.zl_sample_advance_ex.argtypes
+                graphs[(rows, name, which + ": sample_advance")] = cell(lambda l=l, head=head: l.zl_sample_advance(*head(), stream()))
+                graphs[(rows, name, which + ": sample_advance_ex (seen)")] = cell(lambda l=l, head=head, pen=pen: l.zl_sample_advance_ex(*head(), *pen(), stream()))
+            opts = lambda pn, cnt, n, head=head: this.zl_sample_advance_opts(*head(), *pn(), *nine(cnt, n), stream())                        # noqa: E731
+            if with_bias:
+                for cnt in (1, 300):
+                    graphs[(rows, name, "opts: bias %d" % cnt)] = cell(lambda cnt=cnt, opts=opts: opts(nopen, cnt, 0))
+                    graphs[(rows, name, "host: scatter_logits %d + sample_advance" % cnt)] = cell(
+                        lambda cnt=cnt, head=head: (scatter(this, cnt), this.zl_sample_advance(*head(), stream())))
+            if with_top:
+                for n in (5, 20):
+                    graphs[(rows, name, "opts: top-N %d" % n)] = cell(lambda n=n, opts=opts: opts(nopen, 0, n))
+            if with_bias and with_top:
+                graphs[(rows, name, "opts: seen + bias 300 + top-N 5")] = cell(lambda opts=opts, pen=pen: opts(pen, 300, 5))
+                graphs[(rows, name, "host: repetition_penalty + scatter_logits 300 + sample_advance")] = cell(
+                    lambda head=head: (penalise(this), scatter(this, 300), this.zl_sample_advance(*head(), stream())))
+            keep.append(a)
+        keep.append((logits, ids, bid, one, zero, tok, bias, top))
+    t = _alternate(graphs, reps)
+    print("# rows | %-30s | %-62s | us per call" % ("parameters", "call"))
+    for (rows, name, which), ms in t.items():
+        print("  %4d | %-30s | %-62s | %7.2f [%7.2f .. %7.2f]" % ((rows, name, which) + _stats(ms, launches)), flush=True)
+
+
+def opts_step_leg(dev, reps):
+    from zhilight_amd.llama import LLaMA, ModelConfig, QuantConfig
+    cfg = ModelConfig.llama3_8b()
+    model = LLaMA(cfg, QuantConfig(5, 128), dev)
+    model.init_synthetic(seed=1234)
+    seq = 1024
+    print("# whole step_sample (T 0.8, top-k 40, top-p 0.95), synthetic Llama-3-8B GPTQ, %d tokens of history: plain against logit_bias of 300 "
+          "ids + top_logprobs 5; ms per step, median [p10 .. p90] over %d alternated replays" % (seq, reps))
+    for b in (1, 8, 32):
+        len_buf = (seq + reps + 16 + 63) // 64 * 64
+        torch.manual_seed(7)
+        ctxs = {n: model.new_context(b, len_buf, seq, fill_random=True) for n in ("plain", "opts")}
+        kw = dict(temperature=0.8, top_k=40, top_p=0.95, seed=5)
+        states = {"plain": model.new_sampler(ctxs["plain"], **kw),
+                  "opts": model.new_sampler(ctxs["opts"], **kw, logit_bias={i * 7: 0.5 for i in range(300)}, top_logprobs=5)}
+        graphs = {n: _graph(lambda n=n: model.step_sample(ctxs[n], states[n])) for n in ctxs}
+        t = _alternate(graphs, reps)
+        st = {n: tuple(v / 1e3 for v in _stats(t[n], 1)) for n in graphs}
+        print("  %2d | plain %7.3f [%6.3f .. %6.3f] | bias + top-N %7.3f [%6.3f .. %6.3f] | difference %7.1f us"
+              % ((b,) + st["plain"] + st["opts"] + ((st["opts"][0] - st["plain"][0]) * 1e3,)), flush=True)
+        del graphs, ctxs, states
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launch-only", action="store_true")
     ap.add_argument("--step-only", action="store_true")
     ap.add_argument("--penalties", action="store_true")
+    ap.add_argument("--bias", action="store_true")
+    ap.add_argument("--top-n", action="store_true")
+    ap.add_argument("--step", action="store_true")
     ap.add_argument("--parent-so", default=None)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--launches", type=int, default=100)
@@ -195,6 +315,11 @@ def main():
     dev = torch.device("cuda:0")
     if a.penalties:
         penalty_leg(dev, a.reps, a.launches, a.parent_so)
+        return
+    if a.bias or a.top_n:
+        opts_leg(dev, a.reps, a.launches, a.parent_so, a.bias, a.top_n)
+        if a.step:
+            opts_step_leg(dev, a.reps)
         return
     if not a.step_only:
         launch_leg(dev, a.reps, a.launches)

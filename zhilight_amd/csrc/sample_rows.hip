@@ -38,6 +38,15 @@
 //                       passes stream the STORED row exactly as without a penalty and then move each class of the set from the bin of
 //                       its stored pattern to the bin of its penalised one -- the histograms are integers, so this is exact -- which
 //                       costs them a walk over the bitmap (n / 32 words) and nothing per class.  PEN = false compiles none of it.
+//   zl_sample_advance_opts / zl_spec_sample_accept_opts   the same picks with the reference generator's logit bias
+//                       (src/generator/batch_generator.cpp:1709-1729) added behind the penalty, and the top-N classes of every row with
+//                       their log-probabilities (:923-948).  The bias set is a second bitmap beside seen plus an ascending id list:
+//                       the "set" of everything above becomes the union of the two bitmaps, and a class of it is read as "penalised
+//                       if in seen, then T(f32(y) + f32(T(bias))) if its bias bit is set and the list holds it" (a binary search, only
+//                       where a bit hits) -- again a 16-bit pattern.  Top-N is one more COUNT select on the same histograms (the key
+//                       of the N-th class), find_jth only where the N-th place cuts a run of equal values, one gather stream into an
+//                       LDS list of min(N, n) candidates, and a rank by counting.  sample_row<.., MODE 2> below; MODE 0 / 1 are the
+//                       kernels above, unchanged.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -100,11 +109,32 @@ constexpr int kMaxDrafts = 31;     // zl_spec_sample_accept's row limit - 1
 struct NoPen {                      // PEN = false: a class is read as it is stored, and nothing below is compiled
     static constexpr bool on = false;
 };
+// what the _opts entry points add to a launch (one kernel argument; the instantiations without OPT never read it)
+struct Opts {
+    const int32_t* bias_ids;        // (rows or b, bias_ld): a row's first bias_cnt ids, ascending
+    const float* bias_vals;
+    const int32_t* bias_cnt;
+    int64_t bias_ld;
+    const uint32_t* bias_bits;      // (rows or b, bias_bits_ld): seen's layout
+    int64_t bias_bits_ld;
+    int top_n;
+    int32_t* top_ids;               // (rows, top_n)
+    float* top_lp;
+};
+constexpr int kMaxTop = 32;        // top_n's limit: one candidate per lane of half a wave
+
 // the row's view of its penalty: the set = the task's bitmap, and for row i of a speculative step the in-range drafts 0 .. i - 1
-template <bool BF, bool SPEC>
+// OPT (the _opts entry points): the set is the union of that and of the task's BIAS bitmap; a class of the set is read as "the
+// penalty if it is in seen or a draft, then + bias if its bias bit is set and the task's id list holds it" (a binary search, paid only
+// where the bit hits).  Either bitmap may be missing (NULL): a bias needs no penalty, top-N needs neither
+template <bool BF, bool SPEC, bool OPT>
 struct Pen {
     static constexpr bool on = true;
-    const uint32_t* seen;           // the task's bitmap row (global)
+    const uint32_t* seen;           // the task's bitmap row (global); OPT: or NULL
+    const uint32_t* bbits;          // OPT: the task's bias bitmap row (global) or NULL
+    const int32_t* bids;            // OPT: the task's bias ids, bcnt of them ascending
+    const float* bvals;
+    int bcnt;
     const uint32_t* filt;           // SPEC: kFilt bits, bit (id & 255) of every draft in front of the row (LDS)
     const int32_t* ids;             // SPEC: those drafts, -1 where out of range (LDS)
     int nd;                         // SPEC: how many
@@ -117,6 +147,34 @@ struct Pen {
         const float r = sub ? l - tp : (l < 0.f ? l * f : l / f);
         return cvt16<BF>(r);
     }
+    // word w of the set's bitmap
+    __device__ __forceinline__ uint32_t sw(int w) const {
+        if constexpr (OPT) return seen ? seen[w] : 0u;
+        else return seen[w];
+    }
+    __device__ __forceinline__ uint32_t bw(int w) const { return bbits ? bbits[w] : 0u; }
+    __device__ __forceinline__ uint32_t uw(int w) const {
+        if constexpr (OPT) return sw(w) | bw(w);
+        else return seen[w];
+    }
+    // OPT: the class as the pick sees it -- k_repetition_penalty's expression where the penalty's set holds it, then k_scatter_logits'
+    // add, T(f32(y) + f32(T(bias))), where the bias set does.  A bias bit without a list entry leaves the class unbiased
+    __device__ __forceinline__ uint16_t modified(uint16_t h, int i) const {
+        bool in = sw(i >> 5) >> (i & 31) & 1u;
+        if constexpr (SPEC)
+            if (!in && (filt[(i & (kFilt - 1)) >> 5] >> (i & 31) & 1u)) in = draft(i);
+        uint16_t y = in ? apply(h) : h;
+        if (bw(i >> 5) >> (i & 31) & 1u) {
+            int lo = 0, hi = bcnt;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (bids[mid] < i) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo < bcnt && bids[lo] == i) y = cvt16<BF>(H16<BF>::f32(y) + H16<BF>::f32(cvt16<BF>(bvals[lo])));
+        }
+        return y;
+    }
     __device__ __forceinline__ bool draft(int i) const {
         bool hit = false;
         for (int j = 0; j < nd; ++j) hit |= ids[j] == i;
@@ -124,7 +182,7 @@ struct Pen {
     }
     // bit e <=> class i0 + e is in the set, e < 8; the caller has i0 + 7 < n, so both words lie inside the row's ceil(n / 32)
     __device__ __forceinline__ uint32_t mask8(int i0) const {
-        const uint32_t lo = seen[i0 >> 5], hi = seen[(i0 + 7) >> 5];    // the same word twice where the lane does not straddle
+        const uint32_t lo = uw(i0 >> 5), hi = uw((i0 + 7) >> 5);        // the same word twice where the lane does not straddle
         uint32_t m = (uint32_t)((((u64)hi << 32) | lo) >> (i0 & 31)) & 0xffu;
         if constexpr (SPEC) {
             const int p = i0 & (kFilt - 1);
@@ -140,13 +198,16 @@ struct Pen {
     }
     // the set classes of one 16-byte lane, one at a time: sets are sparse (a task's emitted tokens), so a wave takes the loop once or
     // twice where eight predicated copies of the arithmetic would cost every lane of every pass
-    __device__ __forceinline__ void apply8(uint4& d, uint32_t m) const {
+    __device__ __forceinline__ void apply8(uint4& d, uint32_t m, int i0) const {
         while (m) {
             const int e = __ffs((int)m) - 1;
             m &= m - 1;
             const int wi = e >> 1, sft = 16 * (e & 1);
             const uint32_t w = wi == 0 ? d.x : (wi == 1 ? d.y : (wi == 2 ? d.z : d.w));
-            const uint32_t nw = (w & ~(0xffffu << sft)) | ((uint32_t)apply((uint16_t)(w >> sft)) << sft);
+            uint16_t y;
+            if constexpr (OPT) y = modified((uint16_t)(w >> sft), i0 + e);
+            else y = apply((uint16_t)(w >> sft));
+            const uint32_t nw = (w & ~(0xffffu << sft)) | ((uint32_t)y << sft);
             d.x = wi == 0 ? nw : d.x;
             d.y = wi == 1 ? nw : d.y;
             d.z = wi == 2 ? nw : d.z;
@@ -155,12 +216,15 @@ struct Pen {
     }
     // one class, i < n
     __device__ __forceinline__ bool has(int i) const {
-        bool in = seen[i >> 5] >> (i & 31) & 1u;
+        bool in = uw(i >> 5) >> (i & 31) & 1u;
         if constexpr (SPEC)
             if (!in && (filt[(i & (kFilt - 1)) >> 5] >> (i & 31) & 1u)) in = draft(i);
         return in;
     }
-    __device__ __forceinline__ uint16_t one(uint16_t h, int i) const { return has(i) ? apply(h) : h; }
+    __device__ __forceinline__ uint16_t one(uint16_t h, int i) const {
+        if constexpr (OPT) return modified(h, i);
+        else return has(i) ? apply(h) : h;
+    }
     // g(stored pattern, penalised pattern, index) for every class of the set, each once, in no particular order: the bitmap's words
     // below n over the threads -- 4 loads per thread at 128 256 classes, and as many trips as a task has emitted tokens there --
     // then (SPEC) the drafts in front of the row that the bitmap does not hold, one thread each
@@ -168,13 +232,14 @@ struct Pen {
     __device__ __forceinline__ void for_set(const uint16_t* __restrict__ row, int n, G&& g) const {
         const int nw = (n + 31) >> 5;
         for (int w = threadIdx.x; w < nw; w += kThreads) {
-            uint32_t bits = seen[w];
+            uint32_t bits = uw(w);
             if (w == nw - 1 && (n & 31)) bits &= (1u << (n & 31)) - 1u;
             while (bits) {
                 const int i = w * 32 + __ffs((int)bits) - 1;
                 bits &= bits - 1;
                 const uint16_t h = row[i];
-                g(h, apply(h), i);
+                if constexpr (OPT) g(h, modified(h, i), i);
+                else g(h, apply(h), i);
             }
         }
         if constexpr (SPEC) {
@@ -182,7 +247,7 @@ struct Pen {
             if (t < nd) {
                 const int id = ids[t];
                 bool fresh = id >= 0;
-                if (fresh) fresh = !(seen[id >> 5] >> (id & 31) & 1u);
+                if (fresh) fresh = !(uw(id >> 5) >> (id & 31) & 1u);    // OPT: a draft with a bias bit came with the bitmaps' walk
                 for (int j = 0; j < t; ++j) fresh &= ids[j] != id;
                 if (fresh) {
                     const uint16_t h = row[id];
@@ -357,7 +422,7 @@ __device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n
     };
     auto lane8 = [&](int v) -> uint4 {
         uint4 d = body[v];
-        if constexpr (P::on) pen.apply8(d, pen.mask8(head + v * 8));
+        if constexpr (P::on) pen.apply8(d, pen.mask8(head + v * 8), head + v * 8);
         return d;
     };
     int c = 0;
@@ -429,16 +494,27 @@ __device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n
 // PEN (the _ex entry points): the row's classes are read through Pen -- rep_penalty / presence / seen row pr, and under SPEC the
 // drafts in front of the row -- and !SPEC sets the pick's bit in the row's bitmap: one workgroup owns the row, every read of it lies
 // in front of a barrier that thread 0 has passed.  !PEN: the four arguments and drafts are not read
-template <bool BF, bool SPEC, bool PEN>
-__global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __restrict__ x, int64_t ld, int n, int len_q, const float* __restrict__ temperature,
-                                                             const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
-                                                             const int64_t* __restrict__ seeds, int64_t* __restrict__ draws,
-                                                             const float* __restrict__ u_in, int32_t* __restrict__ tokens,
-                                                             int32_t* __restrict__ positions, int32_t* __restrict__ placement,
-                                                             int32_t* __restrict__ valid_lens, int64_t* __restrict__ next_tokens,
-                                                             float* __restrict__ logprobs, float* __restrict__ u_out,
-                                                             const float* __restrict__ rep_penalty, const float* __restrict__ presence,
-                                                             uint32_t* seen, int64_t seen_ld, const int32_t* __restrict__ drafts) {
+// MODE 2 (the _opts entry points with a bias or top_n > 0): MODE 1's reading through Pen<.., OPT> -- seen may be NULL then: no penalty,
+// no drafts, no bit set -- and, top_n > 0, the row's first min(top_n, n) classes of the order with their log-probabilities into
+// o.top_ids / o.top_lp (row r's top_n slots; -1 / NaN behind min(top_n, n) and on a plain row):
+//   2   counts the high byte whenever top-N is on, and runs for a greedy row without logprobs too
+//   3n  the low-byte count pass inside the bin of the N-th class (shared with pass 3 where that is top-k's bin) -> the key k_N of the
+//       N-th class, the count above it (< N) and how many classes of k_N belong to the N
+//   5n  only where fewer than all classes of k_N belong: find_jth, the index of the last one that does
+//   6n  one stream: the classes above k_N and those of k_N up to that index into an LDS list of exactly min(top_n, n) entries (the
+//       arrival order does not matter); a candidate's slot is the number of candidates in front of it by (key descending, index
+//       ascending), its log-probability the pick's expression on its pattern
+// The body of both kernels below: k_sample_advance keeps the argument list it always had, k_sample_advance_opts adds o
+template <bool BF, bool SPEC, int MODE>
+__device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64_t ld, int n, int len_q, const float* __restrict__ temperature,
+                                           const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                           const int64_t* __restrict__ seeds, int64_t* __restrict__ draws, const float* __restrict__ u_in,
+                                           int32_t* __restrict__ tokens, int32_t* __restrict__ positions, int32_t* __restrict__ placement,
+                                           int32_t* __restrict__ valid_lens, int64_t* __restrict__ next_tokens, float* __restrict__ logprobs,
+                                           float* __restrict__ u_out, const float* __restrict__ rep_penalty,
+                                           const float* __restrict__ presence, uint32_t* seen, int64_t seen_ld,
+                                           const int32_t* __restrict__ drafts, const Opts& o) {
+    constexpr bool PEN = MODE >= 1, OPT = MODE == 2;
     __shared__ Hist hist;
     __shared__ u64 red[kWaves];
     __shared__ u64 wm[kBins / 64];
@@ -451,21 +527,36 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
     const int pr = SPEC ? r / len_q : r;                                // the row of the parameters and of the generator
     const uint16_t* row = x + (size_t)r * ld;
 
-    typedef typename std::conditional<PEN, Pen<BF, SPEC>, NoPen>::type P;
+    typedef typename std::conditional<PEN, Pen<BF, SPEC, OPT>, NoPen>::type P;
     P pen;
+    const bool sn = !OPT || seen != nullptr;                            // a penalty set: always under MODE 1
     if constexpr (PEN) {
         __shared__ uint32_t s_filt[kFilt / 32];
         __shared__ int32_t s_ids[kMaxDrafts];
-        const float pp = presence[pr];
-        pen.seen = seen + (size_t)pr * seen_ld;
+        const float pp = sn ? presence[pr] : 0.f;
+        pen.seen = sn ? seen + (size_t)pr * seen_ld : nullptr;
         pen.filt = s_filt;
         pen.ids = s_ids;
         pen.nd = 0;
         pen.sub = pp != 0.f;
         pen.tp = H16<BF>::f32(cvt16<BF>(pp));
-        pen.f = H16<BF>::f32(cvt16<BF>(rep_penalty[pr]));
+        pen.f = H16<BF>::f32(cvt16<BF>(sn ? rep_penalty[pr] : 1.f));
+        if constexpr (OPT) {
+            const bool bs = o.bias_ids != nullptr;                      // the launcher: all four bias pointers or none
+            int bc = bs ? o.bias_cnt[pr] : 0;
+            bc = bc < 0 ? 0 : (bc > (int)o.bias_ld ? (int)o.bias_ld : bc);      // never past the task's list
+            pen.bbits = bs ? o.bias_bits + (size_t)pr * o.bias_bits_ld : nullptr;
+            pen.bids = bs ? o.bias_ids + (size_t)pr * o.bias_ld : nullptr;
+            pen.bvals = bs ? o.bias_vals + (size_t)pr * o.bias_ld : nullptr;
+            pen.bcnt = bc;
+        } else {
+            pen.bbits = nullptr;
+            pen.bids = nullptr;
+            pen.bvals = nullptr;
+            pen.bcnt = 0;
+        }
         if constexpr (SPEC) {
-            const int i = r - pr * len_q;                               // <= kMaxDrafts: the launcher's len_q <= 32
+            const int i = sn ? r - pr * len_q : 0;                      // <= kMaxDrafts: the launcher's len_q <= 32; no set, no drafts
             pen.nd = i;
             if (tid < kFilt / 32) s_filt[tid] = 0;
             __syncthreads();
@@ -523,22 +614,26 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
     const float scale = __builtin_bit_cast(float, (uint32_t)(127 + sh) << 23);
     float lse = __builtin_nanf("");
 
-    if (!plain && !(greedy && logprobs == nullptr)) {                   // uniform over the workgroup, as every branch below
+    (void)sn;
+    bool topn_on = false;
+    if constexpr (OPT) topn_on = o.top_n > 0;
+    if (!plain && !(greedy && logprobs == nullptr && !topn_on)) {       // uniform over the workgroup, as every branch below
         // ---- pass 2: the high byte's histogram, Z ---------------------------------------------------------------------------------
         const int k = greedy ? 0 : top_k[pr];
         const bool k_on = k > 0 && k < n;
+        const bool c_on = k_on || topn_on;                              // the count selects: top-k's and top-N's
         hist_zero(hist);
         // PEN, here and in the low byte's pass: the stored row as it is, then the set's classes move to their penalised bins
         for_each(row, n, NoPen(), [&](uint16_t h, int) {
             const uint32_t kk = key16(h);
-            if (k_on) hist_count(hist, kk >> 8);                        // the count select is top-k's alone
+            if (c_on) hist_count(hist, kk >> 8);
             hist_mass(hist, kk >> 8, mass_of<BF>(kk, vmax, t, scale));
         });
         if constexpr (PEN)
             pen.for_set(row, n, [&](uint16_t raw, uint16_t ph, int) {
                 const uint32_t kr = key16(raw), kp = key16(ph);
                 if (kr == kp) return;
-                if (k_on) {
+                if (c_on) {
                     hist_uncount(hist, kr >> 8);
                     hist_count(hist, kp >> 8);
                 }
@@ -554,37 +649,107 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
         const u64 z = s_z;                                              // >= 2^sh: the largest value's own mass
         lse = logf((float)((double)z * (double)__builtin_bit_cast(float, (uint32_t)(127 - sh) << 23)));
 
-        if (!greedy) {
-            uint32_t c2 = 0, c2_above = 0;
-            u64 m2 = 0, m2_above = 0, q2 = 0;
-            // the low byte inside one high-byte bin: COUNTS only -- every class of a key has the key's mass, so a bin's mass is
-            // count x mass_of(key), one exponential per bin instead of one per class, and sums to the level-1 bin exactly
-            auto low_byte = [&](int bin) {
-                hist_zero(hist);
-                for_each(row, n, NoPen(), [&](uint16_t h, int) {
-                    const uint32_t kk = key16(h);
-                    if ((int)(kk >> 8) == bin) hist_count(hist, kk & 0xffu);
+        uint32_t c2 = 0, c2_above = 0;
+        u64 m2 = 0, m2_above = 0, q2 = 0;
+        // the low byte inside one high-byte bin: COUNTS only -- every class of a key has the key's mass, so a bin's mass is
+        // count x mass_of(key), one exponential per bin instead of one per class, and sums to the level-1 bin exactly
+        auto low_byte = [&](int bin) {
+            hist_zero(hist);
+            for_each(row, n, NoPen(), [&](uint16_t h, int) {
+                const uint32_t kk = key16(h);
+                if ((int)(kk >> 8) == bin) hist_count(hist, kk & 0xffu);
+            });
+            if constexpr (PEN)
+                pen.for_set(row, n, [&](uint16_t raw, uint16_t ph, int) {
+                    const uint32_t kr = key16(raw), kp = key16(ph);
+                    if (kr == kp) return;
+                    if ((int)(kr >> 8) == bin) hist_uncount(hist, kr & 0xffu);
+                    if ((int)(kp >> 8) == bin) hist_count(hist, kp & 0xffu);
                 });
-                if constexpr (PEN)
-                    pen.for_set(row, n, [&](uint16_t raw, uint16_t ph, int) {
-                        const uint32_t kr = key16(raw), kp = key16(ph);
-                        if (kr == kp) return;
-                        if ((int)(kr >> 8) == bin) hist_uncount(hist, kr & 0xffu);
-                        if ((int)(kp >> 8) == bin) hist_count(hist, kp & 0xffu);
-                    });
-                hist_take(hist, c2, m2);
-                q2 = mass_of<BF>((uint32_t)(bin << 8) | (uint32_t)((kBins - 1 - tid) & 0xff), vmax, t, scale);
-                m2 = (u64)c2 * q2;
-                scan_from_top(c2, m2, c2_above, m2_above, wc, wm);
-            };
+            hist_take(hist, c2, m2);
+            q2 = mass_of<BF>((uint32_t)(bin << 8) | (uint32_t)((kBins - 1 - tid) & 0xff), vmax, t, scale);
+            m2 = (u64)c2 * q2;
+            scan_from_top(c2, m2, c2_above, m2_above, wc, wm);
+        };
+        int cur = -1;                                                   // OPT: the bin that c2 / m2 / q2 describe now
+        // OPT, top_n > 0: passes 3n, 5n and 6n; behind pass 3 on a sampling row, on its own on a greedy one
+        auto top_rows = [&]() __attribute__((always_inline)) {
+            if constexpr (OPT) {
+                __shared__ Sel sel_n;
+                __shared__ uint32_t s_kn, c_key[kMaxTop];
+                __shared__ int s_need, s_all, s_last, s_nc, c_idx[kMaxTop];
+                __shared__ uint16_t c_pat[kMaxTop];
+                const int top = o.top_n;                                // 1 .. kMaxTop: the launcher
+                const uint32_t ne = (uint32_t)(top < n ? top : n);
+                // ---- pass 3n: the key of the N-th class of the order, by count -------------------------------------------------------
+                if (tid < kBins && c1_above < ne && ne <= c1_above + c1) sel_n = Sel{kBins - 1 - tid, c1_above, 0};
+                if (tid == 0) {
+                    s_nc = 0;
+                    s_last = n;                                         // every class of k_N belongs, unless pass 5n says otherwise
+                }
+                __syncthreads();
+                if (sel_n.bin != cur) {
+                    low_byte(sel_n.bin);
+                    cur = sel_n.bin;
+                }
+                const uint32_t ca = sel_n.c_above + c2_above;
+                if (tid < kBins && ca < ne && ne <= ca + c2) {
+                    s_kn = (uint32_t)(sel_n.bin << 8) | (uint32_t)(kBins - 1 - tid);
+                    s_need = (int)(ne - ca);
+                    s_all = ne - ca == c2;
+                }
+                __syncthreads();
+                const uint32_t kn = s_kn;
+                if (!s_all) {
+                    // ---- pass 5n: the run of k_N is cut: the index of its last class that belongs ---------------------------------------
+                    find_jth(row, n, pen, kn, s_need, wcnt, &s_last);
+                    __syncthreads();
+                }
+                const int last = s_last;
+                // ---- pass 6n: the candidates, exactly ne of them ----------------------------------------------------------------------
+                for_each(row, n, pen, [&](uint16_t h, int i) {
+                    const uint32_t kk = key16(h);
+                    if (kk > kn || (kk == kn && i <= last)) {
+                        const int at = atomicAdd(&s_nc, 1);
+                        if (at < kMaxTop) {
+                            c_key[at] = kk;
+                            c_idx[at] = i;
+                            c_pat[at] = h;
+                        }
+                    }
+                });
+                __syncthreads();
+                if (tid < top) {
+                    const int nc = s_nc < top ? s_nc : top;             // == ne; the clamp keeps every slot below inside the row's top
+                    int32_t* ti = o.top_ids + (size_t)r * top;
+                    float* tl = o.top_lp + (size_t)r * top;
+                    if (tid < nc) {
+                        const uint32_t mk = c_key[tid];
+                        const int mi = c_idx[tid];
+                        int rank = 0;
+                        for (int j = 0; j < nc; ++j) rank += c_key[j] > mk || (c_key[j] == mk && c_idx[j] < mi);
+                        ti[rank] = mi;
+                        tl[rank] = (H16<BF>::f32(c_pat[tid]) - vmax) / t - lse;        // the pick's expression
+                    } else {
+                        ti[tid] = -1;
+                        tl[tid] = __builtin_nanf("");
+                    }
+                }
+            }
+        };
+        if (!greedy) {
             if (k_on) {
-                // ---- pass 3: c[k-1], the running mass at the k-th class ---------------------------------------------------------------
+                // ---- pass 3: c[k-1], the running mass at the k-th class -----------------------------------------------------------------
                 if (tid < kBins && c1_above < (uint32_t)k && (uint32_t)k <= c1_above + c1) sel_k = Sel{kBins - 1 - tid, c1_above, m1_above};
                 __syncthreads();
                 low_byte(sel_k.bin);
                 const uint32_t ca = sel_k.c_above + c2_above;
                 if (tid < kBins && ca < (uint32_t)k && (uint32_t)k <= ca + c2) s_ck = sel_k.m_above + m2_above + (u64)((uint32_t)k - ca) * q2;
                 __syncthreads();
+            }
+            if constexpr (OPT) {
+                if (k_on) cur = sel_k.bin;
+                if (topn_on) top_rows();
             }
             if (tid == 0) {                                             // v = ceil(u * cap * Z) in fixed point: c >= v  <=>  c >= ceil(v)
                 float tp = top_p[pr];
@@ -603,7 +768,9 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
                 if (tid < kBins && m1_above < v && v <= m1_above + m1) sel_v = Sel{kBins - 1 - tid, c1_above, m1_above};
                 __syncthreads();
                 const int bin = sel_v.bin;
-                if (!(k_on && bin == sel_k.bin)) {
+                bool have = k_on && bin == sel_k.bin;                   // pass 3 counted this bin
+                if constexpr (OPT) have = bin == cur;                   // ... or pass 3n did, after it
+                if (!have) {
                     // ---- pass 4: the low byte's histogram inside the bin where the running mass reaches v -----------------------------
                     low_byte(bin);
                 }
@@ -618,6 +785,8 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
                 find_jth(row, n, pen, (uint32_t)sel_key.bin, s_j, wcnt, &s_pick);
                 __syncthreads();
             }
+        } else if constexpr (OPT) {
+            if (topn_on) top_rows();
         }
     }
 
@@ -634,8 +803,42 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
         uint16_t hp = row[pick];
         if constexpr (PEN) hp = pen.one(hp, pick);
         if (logprobs) logprobs[r] = plain ? __builtin_nanf("") : (H16<BF>::f32(hp) - vmax) / t - lse;
-        if constexpr (PEN && !SPEC) seen[(size_t)r * seen_ld + (pick >> 5)] |= 1u << (pick & 31);
+        if constexpr (PEN && !SPEC)
+            if (sn) seen[(size_t)r * seen_ld + (pick >> 5)] |= 1u << (pick & 31);       // a bias entry does not enter the set
     }
+    if constexpr (OPT)
+        if (topn_on && plain && tid < o.top_n) {                        // no distribution, no alternatives
+            o.top_ids[(size_t)r * o.top_n + tid] = -1;
+            o.top_lp[(size_t)r * o.top_n + tid] = __builtin_nanf("");
+        }
+}
+
+template <bool BF, bool SPEC, bool PEN>
+__global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __restrict__ x, int64_t ld, int n, int len_q, const float* __restrict__ temperature,
+                                                             const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                             const int64_t* __restrict__ seeds, int64_t* __restrict__ draws,
+                                                             const float* __restrict__ u_in, int32_t* __restrict__ tokens,
+                                                             int32_t* __restrict__ positions, int32_t* __restrict__ placement,
+                                                             int32_t* __restrict__ valid_lens, int64_t* __restrict__ next_tokens,
+                                                             float* __restrict__ logprobs, float* __restrict__ u_out,
+                                                             const float* __restrict__ rep_penalty, const float* __restrict__ presence,
+                                                             uint32_t* seen, int64_t seen_ld, const int32_t* __restrict__ drafts) {
+    sample_row<BF, SPEC, PEN ? 1 : 0>(x, ld, n, len_q, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
+                                      next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld, drafts, Opts{});
+}
+
+template <bool BF, bool SPEC>
+__global__ __launch_bounds__(kThreads) void k_sample_advance_opts(const uint16_t* __restrict__ x, int64_t ld, int n, int len_q, const float* __restrict__ temperature,
+                                                                  const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                                  const int64_t* __restrict__ seeds, int64_t* __restrict__ draws,
+                                                                  const float* __restrict__ u_in, int32_t* __restrict__ tokens,
+                                                                  int32_t* __restrict__ positions, int32_t* __restrict__ placement,
+                                                                  int32_t* __restrict__ valid_lens, int64_t* __restrict__ next_tokens,
+                                                                  float* __restrict__ logprobs, float* __restrict__ u_out,
+                                                                  const float* __restrict__ rep_penalty, const float* __restrict__ presence,
+                                                                  uint32_t* seen, int64_t seen_ld, const int32_t* __restrict__ drafts, const Opts o) {
+    sample_row<BF, SPEC, 2>(x, ld, n, len_q, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens, next_tokens,
+                            logprobs, u_out, rep_penalty, presence, seen, seen_ld, drafts, o);
 }
 
 // zl_spec_sample_accept's second launch: out_tokens / out_logprobs hold the picks of the (b, len_q) rows and their log-probabilities
@@ -643,13 +846,33 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
 // outside [0, n) equals no pick), pads the rows behind the bonus token with -1 / NaN, advances the task's state by accepted + 1 and
 // -- where the generator gave the uniforms -- its draw count by as much: the rows behind the rejection drew nothing that counts.
 // seen (zl_spec_sample_accept_ex): the emitted tokens' bits are set in the task's bitmap; the rejected drafts' are not
+// TOP (zl_spec_sample_accept_opts with top_n > 0): one 64-thread workgroup per task instead of one thread -- thread 0 does the above,
+// then all 64 pad the top-N slots of the rows behind the bonus token, up to 31 x 32 ids and log-probabilities, with -1 / NaN
+template <bool TOP>
 __global__ void k_spec_sample_accept(const int32_t* __restrict__ drafts, int32_t* __restrict__ out_tokens, float* __restrict__ out_logprobs,
                                      int32_t* __restrict__ accepted, int32_t* __restrict__ tokens, int32_t* __restrict__ positions,
                                      int32_t* __restrict__ placement, int32_t* __restrict__ valid_lens, float* __restrict__ logprobs,
-                                     int64_t* __restrict__ draws, int b, int len_q, uint32_t* __restrict__ seen, int64_t seen_ld) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= b) return;
+                                     int64_t* __restrict__ draws, int b, int len_q, uint32_t* __restrict__ seen, int64_t seen_ld, int top_n,
+                                     int32_t* __restrict__ top_ids, float* __restrict__ top_lp) {
+    const int t = TOP ? blockIdx.x : blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= b) return;                                                 // TOP: uniform over the workgroup
     int32_t* pk = out_tokens + (int64_t)t * len_q;
+    if constexpr (TOP) {
+        __shared__ int s_a;
+        if (threadIdx.x == 0) {
+            const int32_t* dr = drafts + (int64_t)t * (len_q - 1);
+            int a = 0;
+            while (a < len_q - 1 && dr[a] == pk[a]) ++a;
+            s_a = a;
+        }
+        __syncthreads();                                                // thread 0 rewrites pk behind the bonus token only below
+        const int first = (s_a + 1) * top_n, end = len_q * top_n;       // the task's (len_q, top_n) slots behind row s_a
+        for (int i = first + (int)threadIdx.x; i < end; i += (int)blockDim.x) {
+            top_ids[(int64_t)t * end + i] = -1;
+            top_lp[(int64_t)t * end + i] = __builtin_nanf("");
+        }
+        if (threadIdx.x != 0) return;
+    }
     float* lp = out_logprobs ? out_logprobs + (int64_t)t * len_q : nullptr;
     const int32_t* dr = drafts + (int64_t)t * (len_q - 1);
     int a = 0;
@@ -680,11 +903,22 @@ __global__ void k_seen_mark(uint32_t* __restrict__ seen, int64_t seen_ld, int64_
     if (id >= 0 && id < n) atomicOr(&seen[t * seen_ld + (id >> 5)], 1u << (id & 31));
 }
 
-// the two launchers: PEN <=> seen != NULL, so the plain entry points launch the instantiations without a penalty
+// the _opts arguments' own refusals (0 = fine), behind the plain calls' checks
+int opts_check(const Opts& o, int64_t n) {
+    const int given = (o.bias_ids != nullptr) + (o.bias_vals != nullptr) + (o.bias_cnt != nullptr) + (o.bias_bits != nullptr);
+    ZL_CHECK_ARG(given == 0 || given == 4, ZL_EINVAL);
+    ZL_CHECK_ARG(o.top_n <= 0 || (o.top_ids && o.top_lp), ZL_EINVAL);
+    ZL_CHECK_ARG(given == 0 || (o.bias_ld >= 1 && o.bias_ld <= 1024 && o.bias_bits_ld >= (n + 31) / 32), ZL_ESHAPE);
+    ZL_CHECK_ARG(o.top_n >= 0 && o.top_n <= kMaxTop, ZL_ESHAPE);
+    return 0;
+}
+
+// the two launchers.  MODE: 2 where a bias or top-N is asked for, else 1 <=> seen != NULL, else 0 -- so the plain and _ex entry
+// points, and an _opts call with its nine arguments NULL / 0, launch the instantiations they always have
 int sample_advance_launch(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
                           const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
                           int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
-                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
+                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const Opts& o, zl_stream_t s) {
     ZL_CHECK_ARG(logits && temperature && top_k && top_p, ZL_EINVAL);
     ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
     ZL_CHECK_ARG(tokens || next_tokens, ZL_EINVAL);
@@ -692,20 +926,27 @@ int sample_advance_launch(const void* logits, int type, int64_t rows, int64_t n,
     ZL_CHECK_ARG(rows >= 1 && n >= 1 && ld >= n && n < ((int64_t)1 << 31) && rows < ((int64_t)1 << 31), ZL_ESHAPE);
     ZL_CHECK_ARG(!seen || seen_ld >= (n + 31) / 32, ZL_ESHAPE);
     ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
+    if (const int e = opts_check(o, n)) return e;
     const dim3 g((unsigned)rows), b(kThreads);
     hipStream_t hs = (hipStream_t)s;
-#define ZL_SAMPLE(BF, PEN)                                                                                                                     \
-    hipLaunchKernelGGL((k_sample_advance<BF, false, PEN>), g, b, 0, hs, (const uint16_t*)logits, ld, (int)n, 1, temperature, top_k, top_p, seeds, \
-                       draws, u_in, tokens, positions, placement, valid_lens, next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld,  \
-                       (const int32_t*)nullptr)
+    const int mode = (o.bias_ids || o.top_n > 0) ? 2 : (seen ? 1 : 0);
+#define ZL_ARGS                                                                                                                              \
+    (const uint16_t*)logits, ld, (int)n, 1, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens, next_tokens, \
+        logprobs, u_out, rep_penalty, presence, seen, seen_ld, (const int32_t*)nullptr
+#define ZL_SAMPLE(BF, PEN) hipLaunchKernelGGL((k_sample_advance<BF, false, PEN>), g, b, 0, hs, ZL_ARGS)
+#define ZL_SAMPLE_OPTS(BF) hipLaunchKernelGGL((k_sample_advance_opts<BF, false>), g, b, 0, hs, ZL_ARGS, o)
     if (type == ZL_T_F16) {
-        if (seen) ZL_SAMPLE(false, true);
+        if (mode == 2) ZL_SAMPLE_OPTS(false);
+        else if (mode == 1) ZL_SAMPLE(false, true);
         else ZL_SAMPLE(false, false);
     } else {
-        if (seen) ZL_SAMPLE(true, true);
+        if (mode == 2) ZL_SAMPLE_OPTS(true);
+        else if (mode == 1) ZL_SAMPLE(true, true);
         else ZL_SAMPLE(true, false);
     }
 #undef ZL_SAMPLE
+#undef ZL_SAMPLE_OPTS
+#undef ZL_ARGS
     return zl_launch_status();
 }
 
@@ -713,7 +954,7 @@ int spec_sample_accept_launch(const void* logits, int type, int64_t b, int64_t l
                               const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
                               const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
                               int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
-                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
+                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const Opts& o, zl_stream_t s) {
     ZL_CHECK_ARG(logits && temperature && top_k && top_p && drafts && accepted && out_tokens, ZL_EINVAL);
     ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
     ZL_CHECK_ARG(out_logprobs || !logprobs, ZL_EINVAL);                 // the task's log-probability is read from its rows'
@@ -723,25 +964,38 @@ int spec_sample_accept_launch(const void* logits, int type, int64_t b, int64_t l
                  ZL_ESHAPE);
     ZL_CHECK_ARG(!seen || seen_ld >= (n + 31) / 32, ZL_ESHAPE);
     ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
+    if (const int e = opts_check(o, n)) return e;
     // the picks: one 1024-thread workgroup per logit row, zl_sample_advance's kernel under the task's parameters, into out_tokens
     const dim3 g((unsigned)(b * len_q)), blk(kThreads);
     hipStream_t hs = (hipStream_t)s;
-#define ZL_SAMPLE(BF, PEN)                                                                                                                  \
-    hipLaunchKernelGGL((k_sample_advance<BF, true, PEN>), g, blk, 0, hs, (const uint16_t*)logits, ld, (int)n, (int)len_q, temperature, top_k,   \
-                       top_p, seeds, draws, u_in, out_tokens, nullptr, nullptr, nullptr, nullptr, out_logprobs, u_out, rep_penalty, presence,  \
-                       seen, seen_ld, drafts)
+    const int mode = (o.bias_ids || o.top_n > 0) ? 2 : (seen ? 1 : 0);
+#define ZL_ARGS                                                                                                                          \
+    (const uint16_t*)logits, ld, (int)n, (int)len_q, temperature, top_k, top_p, seeds, draws, u_in, out_tokens, nullptr, nullptr, nullptr, nullptr, \
+        out_logprobs, u_out, rep_penalty, presence, seen, seen_ld, drafts
+#define ZL_SAMPLE(BF, PEN) hipLaunchKernelGGL((k_sample_advance<BF, true, PEN>), g, blk, 0, hs, ZL_ARGS)
+#define ZL_SAMPLE_OPTS(BF) hipLaunchKernelGGL((k_sample_advance_opts<BF, true>), g, blk, 0, hs, ZL_ARGS, o)
     if (type == ZL_T_F16) {
-        if (seen) ZL_SAMPLE(false, true);
+        if (mode == 2) ZL_SAMPLE_OPTS(false);
+        else if (mode == 1) ZL_SAMPLE(false, true);
         else ZL_SAMPLE(false, false);
     } else {
-        if (seen) ZL_SAMPLE(true, true);
+        if (mode == 2) ZL_SAMPLE_OPTS(true);
+        else if (mode == 1) ZL_SAMPLE(true, true);
         else ZL_SAMPLE(true, false);
     }
 #undef ZL_SAMPLE
+#undef ZL_SAMPLE_OPTS
+#undef ZL_ARGS
     const int e = zl_launch_status();
     if (e) return e;
-    hipLaunchKernelGGL(k_spec_sample_accept, dim3((unsigned)((b + 63) / 64)), dim3(64), 0, hs, drafts, out_tokens, out_logprobs, accepted, tokens,
-                       positions, placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q, seen, seen_ld);
+    if (o.top_n > 0)
+        hipLaunchKernelGGL(k_spec_sample_accept<true>, dim3((unsigned)b), dim3(64), 0, hs, drafts, out_tokens, out_logprobs, accepted, tokens,
+                           positions, placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q, seen, seen_ld, o.top_n,
+                           o.top_ids, o.top_lp);
+    else
+        hipLaunchKernelGGL(k_spec_sample_accept<false>, dim3((unsigned)((b + 63) / 64)), dim3(64), 0, hs, drafts, out_tokens, out_logprobs,
+                           accepted, tokens, positions, placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q, seen,
+                           seen_ld, 0, (int32_t*)nullptr, (float*)nullptr);
     return zl_launch_status();
 }
 
@@ -753,7 +1007,7 @@ int zl_sample_advance(const void* logits, int type, int64_t rows, int64_t n, int
                       const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
                       int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out, zl_stream_t s) {
     return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
-                                 next_tokens, logprobs, u_out, nullptr, nullptr, nullptr, 0, s);
+                                 next_tokens, logprobs, u_out, nullptr, nullptr, nullptr, 0, Opts{}, s);
 }
 
 int zl_sample_advance_ex(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
@@ -761,7 +1015,7 @@ int zl_sample_advance_ex(const void* logits, int type, int64_t rows, int64_t n, 
                          int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
     return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
-                                 next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld, s);
+                                 next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld, Opts{}, s);
 }
 
 int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
@@ -769,7 +1023,7 @@ int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q
                           const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
                           int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out, zl_stream_t s) {
     return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
-                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, nullptr, nullptr, nullptr, 0, s);
+                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, nullptr, nullptr, nullptr, 0, Opts{}, s);
 }
 
 int zl_spec_sample_accept_ex(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
@@ -779,7 +1033,31 @@ int zl_spec_sample_accept_ex(const void* logits, int type, int64_t b, int64_t le
                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
     return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
                                      placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, rep_penalty, presence, seen,
-                                     seen_ld, s);
+                                     seen_ld, Opts{}, s);
+}
+
+int zl_sample_advance_opts(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
+                           const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
+                           int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
+                           const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
+                           const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits, int64_t bias_bits_ld,
+                           int top_n, int32_t* top_ids, float* top_logprobs, zl_stream_t s) {
+    return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
+                                 next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld,
+                                 Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs}, s);
+}
+
+int zl_spec_sample_accept_opts(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
+                               const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
+                               const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
+                               int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
+                               const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
+                               const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits,
+                               int64_t bias_bits_ld, int top_n, int32_t* top_ids, float* top_logprobs, zl_stream_t s) {
+    return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
+                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, rep_penalty, presence, seen,
+                                     seen_ld, Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs},
+                                     s);
 }
 
 int zl_seen_mark(uint32_t* seen, int64_t seen_ld, int64_t b, int64_t n, const int32_t* tokens, int64_t n_tok, int64_t tok_ld, zl_stream_t s) {

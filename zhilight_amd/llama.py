@@ -984,6 +984,30 @@ class SamplerState:
     repetition_penalty: Optional[torch.Tensor] = None   # (B) fp32
     presence_penalty: Optional[torch.Tensor] = None     # (B) fp32    != 0: takes precedence over the factor
     seen: Optional[torch.Tensor] = None                 # (B, ceil(vocab / 32)) int32: token i = bit i & 31 of word i >> 5
+    # logit bias inside the sampling launch (new_sampler's logit_bias): ops.logit_bias_pack's four tensors, or all None = off
+    bias_ids: Optional[torch.Tensor] = None             # (B, ld) int32     a task's first bias_cnt ids, ascending
+    bias_vals: Optional[torch.Tensor] = None            # (B, ld) fp32
+    bias_cnt: Optional[torch.Tensor] = None             # (B) int32
+    bias_bits: Optional[torch.Tensor] = None            # (B, ceil(vocab / 32)) int32: the ids as a bitmap, seen's layout
+    # top-N alternatives of every pick (new_sampler's top_logprobs = N): top_n = 0 and the tensors None = off.  top_ids / top_logprobs:
+    # step_sample's, the alternatives of the step that produced the token now pending in ctx.tokens.  row_top_ids / row_top_logprobs
+    # (B, len_q, N): verify(sampler=...)'s, beside row_logprobs and allocated the same way (row_top_bufs keeps them); the pending
+    # token's alternatives after a speculative step are row (b, accepted[b])
+    top_n: int = 0
+    top_ids: Optional[torch.Tensor] = None              # (B, N) int32      -1 behind the vocabulary's end / on a row without a distribution
+    top_logprobs: Optional[torch.Tensor] = None         # (B, N) fp32       NaN there
+    row_top_ids: Optional[torch.Tensor] = None
+    row_top_logprobs: Optional[torch.Tensor] = None
+    row_top_bufs: Optional[Dict[int, tuple]] = None
+
+    def opts(self):
+        """the bias / top-N keyword arguments of ops.sample_advance: none at all with both options off"""
+        kw = {}
+        if self.bias_ids is not None:
+            kw["bias"] = (self.bias_ids, self.bias_vals, self.bias_cnt, self.bias_bits)
+        if self.top_n:
+            kw.update(top_n=self.top_n, top_ids=self.top_ids, top_logprobs=self.top_logprobs)
+        return kw
 
 
 class _PromptRows:
@@ -2050,7 +2074,14 @@ class LLaMA:
         the drafts in front of it, and only the emitted tokens enter sampler.seen.  Everything up to the logits is the same.  sampler.row_logprobs / row_u (B, len_q) hold
         the emitted tokens' tempered log-probabilities (NaN behind the bonus token) and every row's uniform; sampler.logprobs[b]
         keeps step_sample's meaning, the log-probability of the token now pending in ctx.tokens[b].  The two row buffers follow
-        the view's rule: the first eager call per K allocates them.
+        the view's rule: the first eager call per K allocates them.  A sampler with a logit bias applies task b's bias to every row
+        (b, i); one with top_logprobs = N leaves the rows' alternatives in sampler.row_top_ids / row_top_logprobs (B, len_q, N), -1 / NaN
+        behind the bonus token -- per emitted token the same function of the row's logits that step_sample leaves in sampler.top_ids /
+        top_logprobs.  The SAME VALUES only as far as the logits are: a verify row's logits come from another GEMM route than a
+        one-row step's, so with d = the largest difference between the two (modified) rows, the class in a slot has a value within
+        2 d of step_sample's class there and a log-probability within 2 d / T; equal logits give equal ids.  sampler.top_ids /
+        top_logprobs (B, N) are NOT written by this call (the C call has no per-task output for them) and keep the last
+        step_sample's values: after a speculative step the pending token's alternatives are sampler.row_top_ids[b, accepted[b]].
         Returns SpecResult(logits (B * len_q, vocab), accepted (B) int32, tokens (B, len_q) int32); the three are reused by the next
         call with the same K."""
         c, dev = self.cfg, self.device
@@ -2098,6 +2129,15 @@ class LLaMA:
                     raise ops.ZLError("verify: run one eager call with this sampler before capturing (it allocates the row results)")
                 sampler.row_bufs[len_q] = tuple(torch.full((b, len_q), float("nan"), dtype=torch.float32, device=dev) for _ in range(2))
             sampler.row_logprobs, sampler.row_u = sampler.row_bufs[len_q]
+            if sampler.top_n:
+                if sampler.row_top_bufs is None:
+                    sampler.row_top_bufs = {}
+                if len_q not in sampler.row_top_bufs:
+                    if capturing:
+                        raise ops.ZLError("verify: run one eager call with this sampler before capturing (it allocates the row results)")
+                    sampler.row_top_bufs[len_q] = (torch.full((b, len_q, sampler.top_n), -1, dtype=torch.int32, device=dev),
+                                                   torch.full((b, len_q, sampler.top_n), float("nan"), dtype=torch.float32, device=dev))
+                sampler.row_top_ids, sampler.row_top_logprobs = sampler.row_top_bufs[len_q]
         # the view's tables from the context as it is NOW (a swapped buffer, a regrown table), then the rows of this call: tokens
         # (draft ids clamped into the vocabulary), and the three counters of task b + 0 .. K
         torch.index_select(ctx.buf_lens, 0, task_of_row, out=rows.buf_lens)
@@ -2123,11 +2163,14 @@ class LLaMA:
         if sampler is None:
             ops.spec_accept(logits, drafts, ctx.tokens, ctx.positions, ctx.placement, ctx.valid_lens, accepted=accepted, out_tokens=out_tokens)
         else:
+            opts = sampler.opts()                                           # the task's bias; the rows' top-N into the row buffers
+            if sampler.top_n:
+                opts.update(top_ids=sampler.row_top_ids, top_logprobs=sampler.row_top_logprobs)
             ops.spec_sample_accept(logits, drafts, sampler.temperature, sampler.top_k, sampler.top_p, seeds=sampler.seeds, draws=sampler.draws,
                                    tokens=ctx.tokens, positions=ctx.positions, placement=ctx.placement, valid_lens=ctx.valid_lens,
                                    accepted=accepted, out_tokens=out_tokens, out_logprobs=sampler.row_logprobs, logprobs=sampler.logprobs,
                                    u_out=sampler.row_u, rep_penalty=sampler.repetition_penalty, presence=sampler.presence_penalty,
-                                   seen=sampler.seen)
+                                   seen=sampler.seen, **opts)
         ctx.steps_left -= len_q
         return SpecResult(logits, accepted, out_tokens)
 
@@ -2197,31 +2240,41 @@ class LLaMA:
         Returns (tokens, stats): tokens[j] = the ids task j emitted behind its pending ctx.tokens[j] of the time of the call, cut to
         max_new_tokens; stats = {"steps", "emitted": ids per task before the cut (= steps + accepted), "accepted": accepted drafts per
         task, "mean_accepted": accepted drafts per task and step}.  With a sampler (step_lookup's sampler=) the steps sample, and
-        stats gains "logprobs": per task the emitted ids' tempered log-probabilities, cut as the ids are."""
+        stats gains "logprobs": per task the emitted ids' tempered log-probabilities, cut as the ids are; a sampler with top_logprobs
+        = N adds "top_ids" / "top_logprobs": per task and emitted id the N alternatives (lists of N), cut the same way."""
         b = ctx.tokens.numel()
         out = [[] for _ in range(b)]
         lps = [[] for _ in range(b)]
+        tis, tls = [[] for _ in range(b)], [[] for _ in range(b)]
+        top = sampler is not None and sampler.top_n > 0
         accepted = [0] * b
         steps = 0
         while min(len(o) for o in out) < max_new_tokens and ctx.steps_left >= state.k + 1:
             res = self.step_lookup(ctx, state, sampler=sampler)
             acc, tok = res.accepted.tolist(), res.tokens.tolist()
             lp = sampler.row_logprobs.tolist() if sampler is not None else None
+            ti, tl = (sampler.row_top_ids.tolist(), sampler.row_top_logprobs.tolist()) if top else (None, None)
             for j in range(b):
                 out[j] += tok[j][:acc[j] + 1]
                 accepted[j] += acc[j]
                 if lp is not None:
                     lps[j] += lp[j][:acc[j] + 1]
+                if top:
+                    tis[j] += ti[j][:acc[j] + 1]
+                    tls[j] += tl[j][:acc[j] + 1]
             steps += 1
         stats = {"steps": steps, "emitted": [len(o) for o in out], "accepted": accepted,
                  "mean_accepted": sum(accepted) / (steps * b) if steps else 0.0}
         if sampler is not None:
             stats["logprobs"] = [l[:max_new_tokens] for l in lps]
+        if top:
+            stats["top_ids"] = [l[:max_new_tokens] for l in tis]
+            stats["top_logprobs"] = [l[:max_new_tokens] for l in tls]
         return [o[:max_new_tokens] for o in out], stats
 
     # ---- sampling steps -----------------------------------------------------------------------------
     def new_sampler(self, ctx: DynBatchContext, temperature=1.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0, presence_penalty=0.0,
-                    penalty_tokens=None) -> SamplerState:
+                    penalty_tokens=None, logit_bias=None, top_logprobs=0) -> SamplerState:
         """The state for step_sample.  temperature / top_k / top_p / seed: a scalar for every task or a sequence of B values.
         temperature 0 = greedy; top_k 0 = off; top_p 1 = off; a scalar seed s gives task j the seed s + j, so the tasks draw different
         streams and a task's stream does not depend on the rest of the batch.
@@ -2229,7 +2282,12 @@ class LLaMA:
         or B values, applied inside the sampling launch to the ids a task has emitted: the pending ctx.tokens entry and every pick
         from here on (the reference penalises generated tokens only).  penalty_tokens: B sequences of further ids to penalise from
         the start, such as the prompts.  With every task at (1, 0) and no penalty_tokens the state carries no bitmap and the steps
-        are the unpenalised ones."""
+        are the unpenalised ones.
+        logit_bias: the reference's per-task {token id: bias} map -- one dict for every task, or a sequence of B dicts / Nones; at most
+        1024 ids per task, values finite or -inf (a ban).  Added inside the sampling launch behind the penalty (ops.sample_advance's
+        bias=).  top_logprobs: N in 0 .. 32, one value for the state: every step also returns the N most likely tokens of the
+        penalised and biased distribution with their log-probabilities (state.top_ids / top_logprobs).  With both off the state and
+        the calls are the ones without them."""
         b, dev = ctx.tokens.numel(), ctx.tokens.device
 
         def per_task(v, what):
@@ -2282,6 +2340,18 @@ class LLaMA:
                     ops.seen_mark(seen, torch.from_numpy(ids).to(dev), vocab)
             pen = dict(repetition_penalty=torch.tensor([float(v) for v in rp], dtype=torch.float32, device=dev),
                        presence_penalty=torch.tensor([float(v) for v in pp], dtype=torch.float32, device=dev), seen=seen)
+        if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, (int, np.integer)) or not 0 <= int(top_logprobs) <= ops.TOP_LOGPROBS_MAX:
+            raise ops.ZLError(f"new_sampler: top_logprobs is an integer in 0 .. {ops.TOP_LOGPROBS_MAX}")
+        if logit_bias is not None:
+            maps = [logit_bias] * b if isinstance(logit_bias, dict) else list(logit_bias)
+            if len(maps) != b:
+                raise ops.ZLError(f"new_sampler: {b} tasks, {len(maps)} maps of logit_bias")
+            if any(maps):                                                   # nothing but empty maps: off
+                ids, vals, cnt, bits = ops.logit_bias_pack(maps, self.cfg.vocab_size, dev)
+                pen.update(bias_ids=ids, bias_vals=vals, bias_cnt=cnt, bias_bits=bits)
+        if int(top_logprobs):
+            pen.update(top_n=int(top_logprobs), top_ids=torch.full((b, int(top_logprobs)), -1, dtype=torch.int32, device=dev),
+                       top_logprobs=torch.full((b, int(top_logprobs)), float("nan"), dtype=torch.float32, device=dev))
         return SamplerState(**pen, temperature=torch.tensor([float(v) for v in t], dtype=torch.float32, device=dev),
                             top_k=torch.tensor([int(v) for v in k], dtype=torch.int32, device=dev),
                             top_p=torch.tensor([float(v) for v in p], dtype=torch.float32, device=dev),
@@ -2297,7 +2367,8 @@ class LLaMA:
         picks' tempered log-probabilities and the uniforms used; state.draws has advanced by one.  Returns (logits, next_tokens
         int64).  Penalties: a state built with new_sampler's repetition_penalty / presence_penalty applies them inside that launch --
         the kernel reads the classes of state.seen as ops.repetition_penalty would have left them and records its pick there; the
-        returned logits are the raw ones.  The launch count and the host work per step are the same."""
+        returned logits are the raw ones.  The launch count and the host work per step are the same.  A logit bias and the top-N
+        alternatives (new_sampler's logit_bias / top_logprobs) ride in the same launch: state.top_ids / top_logprobs (B, N)."""
         b = ctx.tokens.numel()
         if state.temperature.numel() != b:
             raise ops.ZLError("step_sample: the state belongs to another batch size")
@@ -2309,23 +2380,32 @@ class LLaMA:
         ops.sample_advance(logits, state.temperature, state.top_k, state.top_p, seeds=state.seeds, draws=state.draws, tokens=ctx.tokens,
                            positions=ctx.positions, placement=ctx.placement, valid_lens=ctx.valid_lens, next_tokens=nxt,
                            logprobs=state.logprobs, u_out=state.u, rep_penalty=state.repetition_penalty, presence=state.presence_penalty,
-                           seen=state.seen)
+                           seen=state.seen, **state.opts())
         ctx.steps_left -= 1
         return logits, nxt
 
     def generate_sample(self, ctx: DynBatchContext, state: SamplerState, max_new_tokens):
         """The eager convenience loop around step_sample: up to max_new_tokens steps, fewer where the KV buffers run out
         (ctx.steps_left).  Returns (tokens (B, steps) int64, logprobs (B, steps) fp32): what every task emitted behind its pending
-        ctx.tokens entry of the time of the call, and each token's tempered log-probability.  One read-back at the end."""
-        b = ctx.tokens.numel()
-        toks, lps = [], []
+        ctx.tokens entry of the time of the call, and each token's tempered log-probability.  One read-back at the end.  A state with
+        top_logprobs = N > 0 returns a third element, (top_ids (B, steps, N) int32, top_logprobs (B, steps, N) fp32)."""
+        b, dev = ctx.tokens.numel(), ctx.tokens.device
+        toks, lps, tis, tls = [], [], [], []
         for _ in range(max(0, min(int(max_new_tokens), ctx.steps_left))):
             _, nxt = self.step_sample(ctx, state)
             toks.append(nxt.clone())
             lps.append(state.logprobs.clone())
+            if state.top_n:
+                tis.append(state.top_ids.clone())
+                tls.append(state.top_logprobs.clone())
         if not toks:
-            return (torch.empty((b, 0), dtype=torch.int64, device=ctx.tokens.device),
-                    torch.empty((b, 0), dtype=torch.float32, device=ctx.tokens.device))
+            out = (torch.empty((b, 0), dtype=torch.int64, device=dev), torch.empty((b, 0), dtype=torch.float32, device=dev))
+            if state.top_n:
+                out += ((torch.empty((b, 0, state.top_n), dtype=torch.int32, device=dev),
+                         torch.empty((b, 0, state.top_n), dtype=torch.float32, device=dev)),)
+            return out
+        if state.top_n:
+            return torch.stack(toks, dim=1), torch.stack(lps, dim=1), (torch.stack(tis, dim=1), torch.stack(tls, dim=1))
         return torch.stack(toks, dim=1), torch.stack(lps, dim=1)
 
     def advance(self, ctx: DynBatchContext, next_tokens: torch.Tensor):

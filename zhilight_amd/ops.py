@@ -13,6 +13,7 @@ import ctypes as C
 import os
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -940,8 +941,101 @@ def _penalty_args(what, count, n, device, rep_penalty, presence, seen):
         raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
 
 
+LOGIT_BIAS_MAX = 1024      # bias entries per task
+TOP_LOGPROBS_MAX = 32      # top-N alternatives per row
+
+
+def logit_bias_rows(maps, n):
+    """The host half of logit_bias_pack, numpy only: maps = B dicts {token id: bias} (or None = no bias) over n classes ->
+    (ids (B, ld) int32, each row's first cnt ascending and -1 behind them; vals (B, ld) float32; cnt (B) int32; bits (B, ceil(n / 32))
+    uint32, bit i & 31 of word i >> 5 per id), ld = the longest list, at least 1.  Refuses (ZLError) ids that repeat after int(),
+    ids outside [0, n), more than 1024 entries, NaN and +inf values, and finite values beyond float32's range on either side (they
+    would turn into +inf or into a ban); -inf is legal and bans the class."""
+    n = int(n)
+    if n < 1 or n >= 1 << 31:
+        raise ZLError("logit_bias_pack: 1 <= n < 2^31 classes")
+    maps = [({} if m is None else m) for m in maps]
+    if not maps or not all(isinstance(m, dict) for m in maps):
+        raise ZLError("logit_bias_pack: one dict {token id: bias} (or None) per task")
+    rows = []
+    for t, m in enumerate(maps):
+        if len(m) > LOGIT_BIAS_MAX:
+            raise ZLError(f"logit_bias_pack: task {t}: {len(m)} entries, at most {LOGIT_BIAS_MAX}")
+        try:
+            pairs = sorted((int(i), float(v)) for i, v in m.items())
+        except (TypeError, ValueError):
+            raise ZLError(f"logit_bias_pack: task {t}: integer ids and real values") from None
+        ids = [i for i, _ in pairs]
+        if len(set(ids)) != len(ids):
+            raise ZLError(f"logit_bias_pack: task {t}: an id is given twice")
+        if ids and (ids[0] < 0 or ids[-1] >= n):
+            raise ZLError(f"logit_bias_pack: task {t}: ids outside [0, {n})")
+        if any(v != v or v == float("inf") for _, v in pairs):
+            raise ZLError(f"logit_bias_pack: task {t}: a bias is finite or -inf (a ban), not NaN or +inf")
+        rows.append(pairs)
+    ld = max([1] + [len(r) for r in rows])
+    ids = np.full((len(rows), ld), -1, np.int32)
+    vals = np.zeros((len(rows), ld), np.float32)
+    bits = np.zeros((len(rows), seen_words(n)), np.uint32)
+    for t, r in enumerate(rows):
+        if r:
+            i = np.asarray([p[0] for p in r], np.int64)
+            ids[t, :i.size] = i
+            v64 = np.asarray([p[1] for p in r], np.float64)
+            with np.errstate(over="ignore"):
+                vals[t, :i.size] = v64.astype(np.float32)
+            if (np.isinf(vals[t, :i.size]) & np.isfinite(v64)).any():                   # a finite value must not turn into a ban
+                raise ZLError(f"logit_bias_pack: task {t}: a finite bias lies within float32's range")
+            np.bitwise_or.at(bits[t], i >> 5, np.uint32(1) << (i & 31).astype(np.uint32))
+    return ids, vals, np.asarray([len(r) for r in rows], np.int32), bits
+
+
+def logit_bias_pack(maps, n, device):
+    """B dicts {token id: bias} (None = none for that task) -> the bias argument of sample_advance / spec_sample_accept: the tuple
+    (ids (B, ld) int32, vals (B, ld) float32, cnt (B) int32, bits (B, ceil(n / 32)) int32) on `device`; logit_bias_rows states the
+    layout and the refusals."""
+    ids, vals, cnt, bits = logit_bias_rows(maps, n)
+    return (torch.from_numpy(ids).to(device), torch.from_numpy(vals).to(device), torch.from_numpy(cnt).to(device),
+            torch.from_numpy(bits.view(np.int32)).to(device))
+
+
+def _opts_args(what, count, top_shape, n, device, bias, top_n, top_ids, top_logprobs):
+    """The checks of (bias, top_n, top_ids, top_logprobs) of sample_advance / spec_sample_accept -> the nine C arguments; count = the
+    rows / tasks the bias is per, top_shape = the leading shape of the top-N outputs."""
+    if bias is not None:
+        if not (isinstance(bias, (tuple, list)) and len(bias) == 4 and all(torch.is_tensor(t) for t in bias)):
+            raise ZLError(f"{what}: bias is logit_bias_pack's (ids, vals, cnt, bits)")
+        ids, vals, cnt, bits = bias
+        if not (ids.dtype == torch.int32 and ids.dim() == 2 and ids.shape[0] == count and ids.is_contiguous()
+                and 1 <= ids.shape[1] <= LOGIT_BIAS_MAX):
+            raise ZLError(f"{what}: bias ids: contiguous int32 ({count}, 1 .. {LOGIT_BIAS_MAX})")
+        if not (vals.dtype == torch.float32 and vals.shape == ids.shape and vals.is_contiguous()):
+            raise ZLError(f"{what}: bias vals: contiguous float32 of the ids' shape")
+        if not (cnt.dtype == torch.int32 and cnt.dim() == 1 and cnt.numel() == count and cnt.is_contiguous()):
+            raise ZLError(f"{what}: bias cnt: contiguous int32 of length {count}")
+        if not (bits.dtype == torch.int32 and bits.dim() == 2 and bits.shape[0] == count and bits.is_contiguous()
+                and bits.shape[1] >= seen_words(n)):
+            raise ZLError(f"{what}: bias bits: contiguous int32 ({count}, >= ceil(n / 32))")
+        if any(t.device != device for t in bias):
+            raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
+        args = [_p(ids), _p(vals), _p(cnt), _i(ids.shape[1]), _p(bits), _i(bits.shape[1])]
+    else:
+        args = [_p(None), _p(None), _p(None), _i(0), _p(None), _i(0)]
+    top_n = int(top_n)
+    if not 0 <= top_n <= TOP_LOGPROBS_MAX:
+        raise ZLError(f"{what}: top_n in 0 .. {TOP_LOGPROBS_MAX}")
+    if top_n:
+        shape = tuple(top_shape) + (top_n,)
+        for t, dtype, name in ((top_ids, torch.int32, "top_ids"), (top_logprobs, torch.float32, "top_logprobs")):
+            if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == device):
+                raise ZLError(f"{what}: {name}: contiguous {str(dtype).replace('torch.', '')} {shape} on the logits' device, given with top_n")
+        return args + [C.c_int(top_n), _p(top_ids), _p(top_logprobs)]
+    return args + [C.c_int(0), _p(None), _p(None)]
+
+
 def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=None, tokens=None, positions=None, placement=None,
-                   valid_lens=None, next_tokens=None, logprobs=None, u_out=None, rep_penalty=None, presence=None, seen=None):
+                   valid_lens=None, next_tokens=None, logprobs=None, u_out=None, rep_penalty=None, presence=None, seen=None,
+                   bias=None, top_n=0, top_ids=None, top_logprobs=None):
     """The stochastic pick over whole logit rows and the batch state's advance in one launch (zl_sample_advance): logits (rows, n)
     fp16 / bf16 with unit column stride; temperature (rows) fp32, top_k (rows) int32 (<= 0 or >= n: off), top_p (rows) fp32 in [0, 1]
     -- per row.  A row with temperature <= 0 takes argmax_advance's pick; otherwise p = exp((x - max) / T), the classes ordered by p
@@ -955,7 +1049,13 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
     zl_sample_advance_ex -- a class whose bit is set is read as repetition_penalty's value of it (presence != 0 ? x - T(presence) :
     x < 0 ? x * T(factor) : x / T(factor)), the rule above runs on that row, logprobs is the penalised distribution's, the logits in
     memory stay as they are, and the pick's bit is set in seen: the same results as repetition_penalty over the set + this call
-    without seen, in the one launch."""
+    without seen, in the one launch.
+    bias = logit_bias_pack's tuple, per row: zl_sample_advance_opts -- a class of the row's bias set is read as T(f32(y) + f32(T(bias))),
+    y = the class after the penalty (scatter_logits(add=True)'s expression; -inf bans the class); the bias enters neither seen nor the
+    logits in memory, and needs no seen.  top_n = N in 1 .. 32 with top_ids (rows, N) int32 / top_logprobs (rows, N) fp32: the first
+    min(N, n) classes of the row AS THE PICK SAW IT, larger value first, then lower index, with their tempered log-probabilities
+    (the pick's entry is bit-equal to logprobs); -1 / NaN behind n and on a row whose largest value is NaN or +-inf.  The same
+    results as repetition_penalty + scatter_logits(add=True) + this call without them, in the one launch."""
     if not all(torch.is_tensor(t) for t in (logits, temperature, top_k, top_p)):
         raise ZLError("sample_advance: logits, temperature, top_k and top_p are tensors")
     if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
@@ -997,6 +1097,13 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
         raise ZLError("sample_advance: CUDA logits, every other tensor on the logits' device")
     _penalty_args("sample_advance", rows, n, logits.device, rep_penalty, presence, seen)
     code = 2 if logits.dtype == torch.float16 else 6
+    if bias is not None or top_n != 0:
+        opts = _opts_args("sample_advance", rows, (rows,), n, logits.device, bias, top_n, top_ids, top_logprobs)
+        check(lib().zl_sample_advance_opts(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k),
+                                           _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement), _p(valid_lens),
+                                           _p(next_tokens), _p(logprobs), _p(u_out), _p(rep_penalty), _p(presence), _p(seen),
+                                           _i(seen.shape[1] if seen is not None else 0), *opts, _stream()), "sample_advance")
+        return next_tokens if next_tokens is not None else tokens
     if seen is not None:
         check(lib().zl_sample_advance_ex(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k),
                                          _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement), _p(valid_lens),
@@ -1011,7 +1118,7 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
 
 def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, draws=None, u=None, tokens=None, positions=None,
                        placement=None, valid_lens=None, accepted=None, out_tokens=None, out_logprobs=None, logprobs=None, u_out=None,
-                       rep_penalty=None, presence=None, seen=None):
+                       rep_penalty=None, presence=None, seen=None, bias=None, top_n=0, top_ids=None, top_logprobs=None):
     """The acceptance of a speculative step under sampling (zl_spec_sample_accept, two launches): spec_accept with sample_advance's
     pick in the arg-max's place.  logits (B * len_q, n) fp16 / bf16 rows, task-major, unit column stride; drafts (B, K) int32,
     len_q = K + 1 <= 32.  temperature / top_k / top_p / seeds / draws are per task (B); u, u_out and out_logprobs per row (B, len_q).
@@ -1025,7 +1132,10 @@ def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, dr
     (accepted (B) int32, out_tokens (B, len_q) int32); accepted / out_tokens: buffers to write into (a captured call).
     seen (B, >= ceil(n / 32)) int32 with rep_penalty / presence (B) fp32, per task: zl_spec_sample_accept_ex -- row (b, i) is
     sample_advance(seen=)'s pick under the set seen[b] + the in-range drafts[b, :i] (the row counts only if they were emitted), and
-    the bits of the emitted tokens out_tokens[b, :accepted + 1] are set in seen[b]; the rejected drafts' are not."""
+    the bits of the emitted tokens out_tokens[b, :accepted + 1] are set in seen[b]; the rejected drafts' are not.
+    bias (logit_bias_pack's tuple, per task) / top_n with top_ids (B, K + 1, N) int32 and top_logprobs (B, K + 1, N) fp32:
+    zl_spec_sample_accept_opts -- every row (b, i) is sample_advance(bias=, top_n=)'s under task b's bias (the drafts in front of a row
+    change its penalty set only), the rows behind the bonus token hold -1 / NaN."""
     if not all(torch.is_tensor(t) for t in (logits, drafts, temperature, top_k, top_p)):
         raise ZLError("spec_sample_accept: logits, drafts, temperature, top_k and top_p are tensors")
     if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
@@ -1082,6 +1192,14 @@ def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, dr
     if out_tokens is None:
         out_tokens = torch.empty((b, len_q), dtype=torch.int32, device=logits.device)
     code = 2 if logits.dtype == torch.float16 else 6
+    if bias is not None or top_n != 0:
+        opts = _opts_args("spec_sample_accept", b, (b, len_q), n, logits.device, bias, top_n, top_ids, top_logprobs)
+        check(lib().zl_spec_sample_accept_opts(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts),
+                                               _p(temperature), _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions),
+                                               _p(placement), _p(valid_lens), _p(accepted), _p(out_tokens), _p(out_logprobs), _p(logprobs),
+                                               _p(u_out), _p(rep_penalty), _p(presence), _p(seen),
+                                               _i(seen.shape[1] if seen is not None else 0), *opts, _stream()), "spec_sample_accept")
+        return accepted, out_tokens.view(b, len_q)
     if seen is not None:
         check(lib().zl_spec_sample_accept_ex(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts),
                                              _p(temperature), _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions),
