@@ -986,6 +986,43 @@ int zl_spec_accept(const void* logits, int type, int64_t b, int64_t len_q, int64
  * ONE launch, one 1024-thread workgroup per task; ordinary vector stores only; no allocation, no sync, no workspace. */
 int zl_lookup_draft(int32_t* history, int64_t cap, int32_t* hist_lens, const int32_t* new_tokens, int64_t n_new, int64_t b, int64_t k,
                     int max_ngram, int min_ngram, int32_t* drafts, int32_t* match, zl_stream_t s);
+/* The stop conditions of a decode step (csrc/stop_rows.hip): stop ids, multi-token stop sequences and a length limit per task, applied
+ * to the ids a step emitted, directly behind the step's advance / accept call (zl_argmax_advance, zl_greedy_advance, zl_sample_advance*,
+ * zl_spec_accept, zl_spec_sample_accept*) and, in a lookup step, before zl_lookup_draft.  The reference tests these on the host between
+ * steps; here a captured step carries them and a caller polls `live`.
+ * PARAMETERS, read only, per task t of b:  stop_ids (b, n_ids <= 16) int32, -1 = unused;  stop_seqs (b, n_seqs <= 8, seq_ld <= 16) int32
+ * with seq_lens (b, n_seqs), a length outside [1, seq_ld] = unused;  max_new (b), <= 0 = no limit.  stop_ids with n_ids = 0, stop_seqs
+ * + seq_lens with n_seqs = seq_ld = 0, and max_new may be NULL.
+ * STATE, updated in place:  gen_lens (b) ids emitted since the state was made;  tail (b, 15) the last 15 of them, oldest first, -1 where
+ * there are none yet (a caller seeds tail[t, 14] with the pending token so that a sequence may begin with it);  last_token (b);
+ * finished (b): 0 = live, 1 = stop id, 2 = stop sequence, 3 = length.
+ * THE STEP'S RESULTS, patched in place:  new_tokens (b, n_new) int32, 1 <= n_new <= 32 -- a task's emitted ids e[0 .. m - 1] are the ids
+ * before the row's first negative one, as in zl_lookup_draft; at n_new = 1 new_tokens may be `tokens` itself (a task's row is read
+ * before anything of that task is written);  accepted (b) int32, next_tokens (b) int64, tokens / positions / placement / valid_lens (b)
+ * int32: each may be NULL.  OUTPUTS: emit_lens (b) int32, live (1) int32 = the tasks with finished == 0 after the call.
+ * A LIVE task with m >= 1: position j = 0 .. m - 1 is a hit, the first case that applies giving the reason,
+ *   1  if e[j] is one of the task's stop ids;
+ *   2  if for some sequence q the last seq_lens[q] ids of (tail ++ e[0 .. j]) equal it (a -1 of the tail matches nothing; a sequence may
+ *      span any number of earlier calls);
+ *   3  if max_new[t] > 0 and gen_lens[t] + j + 1 >= max_new[t].
+ * c = (first hit) + 1, or m without a hit.  The row keeps its first c ids and holds -1 behind them; emit_lens[t] = c; gen_lens[t] += c;
+ * the tail takes the c ids; accepted[t] = c - 1; positions / placement / valid_lens -= m - c (the advance had added m: the batch state
+ * is what a step that emitted c ids leaves); tokens[t] = next_tokens[t] = last_token[t] = e[c - 1]; finished[t] = the reason or 0.
+ * A FINISHED task (frozen) with m >= 1: emit_lens[t] = 0, the row all -1, accepted[t] = next_tokens[t] = -1, positions / placement /
+ * valid_lens -= m, tokens[t] = last_token[t]: every later step re-feeds the same token at the same position into the same slot, the
+ * task's context never moves again.  m = 0: emit_lens[t] = 0, nothing else of the task is written.
+ * NOT restored: a sampler's draws and seen bitmap and a speculative step's per-row results (log-probabilities, uniforms, top-N) -- they
+ * are valid for a task's first emit_lens entries, and seen may hold ids the step accepted behind the cut: resuming a finished task
+ * under penalties is not covered.
+ * ZL_EINVAL: a null gen_lens / tail / last_token / finished / new_tokens / emit_lens / live, b < 1, n_new < 1, a negative count, a
+ * parameter array that is null with a count > 0 or given with a count of 0, new_tokens == tokens with n_new > 1;
+ * ZL_ESHAPE: n_ids > 16, n_seqs > 8, seq_ld > 16, n_new > 32, b >= 2^31.
+ * ONE launch of one workgroup (a wave per task, 16 waves striding over the tasks; any b, meant for b <= 1024); ordinary vector stores
+ * only, no atomics; no allocation, no sync, no workspace; deterministic. */
+int zl_stop_advance(const int32_t* stop_ids, int64_t n_ids, const int32_t* stop_seqs, const int32_t* seq_lens, int64_t n_seqs, int64_t seq_ld,
+                    const int32_t* max_new, int32_t* gen_lens, int32_t* tail, int32_t* last_token, int32_t* finished, int32_t* new_tokens,
+                    int64_t n_new, int64_t b, int32_t* accepted, int64_t* next_tokens, int32_t* tokens, int32_t* positions,
+                    int32_t* placement, int32_t* valid_lens, int32_t* emit_lens, int32_t* live, zl_stream_t s);
 /* The stochastic pick of a decode step + zl_argmax_advance's bookkeeping in one launch (csrc/sample_rows.hip): temperature, top-k and
  * top-p sampling per row under the reference's rule (src/generator/random_util.cu:83-199, which its scheduler runs on the host),
  * evaluated in fp32 on fp32 probabilities.  logits (rows, n), row stride ld elements, type = ZL_T_F16 / ZL_T_BF16 (ZL_T_F32: ZL_EDTYPE

@@ -21,7 +21,12 @@
      draft is accepted with probability p(draft) per position, so the synthetic weights accept next to nothing here; that figure
      says nothing about real text either way.
 
-usage: python tools/bench_lookup.py [--launch-only | --step-only] [--sampler] [--reps 30] [--launches 200]"""
+  --stop: the stop conditions inside the speculative step (profiles/stop_step.txt, with tools/bench_sample.py --stop):
+  5. the whole captured step_lookup with and without a stop state whose stops never hit (two stop ids, two four-id stop sequences and a
+     length limit per task), replays alternated, at (B, K) = (1, 3), (8, 3) and (16, 1) -- a speculative step holds at most 32 rows, so
+     16 tasks are the most it takes.  The step without stop= issues exactly the launches of the commit before the stop conditions.
+
+usage: python tools/bench_lookup.py [--launch-only | --step-only] [--sampler | --stop] [--reps 30] [--launches 200]"""
 import argparse
 import os
 import statistics
@@ -256,17 +261,63 @@ def sampler_step_leg(dev, reps, rows):
                                                              "used there" % missed))
 
 
+STOPS = dict(stop_ids=[128001, 128009], stop_sequences=[[198, 198, 198, 198], [13, 13, 271, 271]], max_new_tokens=1 << 20)
+STOP_ROWS = [(1, 3), (8, 3), (16, 1)]
+
+
+def stop_step_leg(dev, reps, rows):
+    from zhilight_amd.llama import LLaMA, ModelConfig, QuantConfig
+    cfg = ModelConfig.llama3_8b()
+    model = LLaMA(cfg, QuantConfig(5, 128), dev)
+    model.init_synthetic(seed=1234)
+    seq = 1024
+    print("# whole greedy step_lookup, synthetic Llama-3-8B GPTQ, 32 layers, %d tokens of history (a 64-id motif repeated): without stop= against a "
+          "stop state whose stops never hit; ms per step, median [p10 .. p90] over %d alternated replays" % (seq, reps))
+    for b, k in rows:
+        len_q = k + 1
+        len_buf = (seq + (reps + 8) * len_q + 63) // 64 * 64
+        torch.manual_seed(7)
+        ctxs = {n: model.new_context(b, len_buf, seq, fill_random=True) for n in ("plain", "stop")}
+        motif = torch.randint(0, cfg.vocab_size, (b, 64), dtype=torch.int32)
+        for c in ctxs.values():
+            c.tokens.copy_(motif[:, 0])                                              # the pending token continues the motif
+        for t, src in zip(ctxs["stop"].kv, ctxs["plain"].kv):
+            t.copy_(src)
+        hist = [motif[j].repeat(seq // 64) for j in range(b)]
+        look = {n: model.new_lookup(ctxs[n], hist, k) for n in ctxs}
+        stop = model.new_stopper(ctxs["stop"], **STOPS)
+        model.step_lookup(ctxs["plain"], look["plain"])                              # eager: the row-expanded tables
+        model.step_lookup(ctxs["stop"], look["stop"], stop=stop)
+        graphs = {"plain": _graph(lambda: model.step_lookup(ctxs["plain"], look["plain"])),
+                  "stop": _graph(lambda: model.step_lookup(ctxs["stop"], look["stop"], stop=stop))}
+        t = _alternate(graphs, reps)
+        same = all(torch.equal(getattr(ctxs["plain"], n), getattr(ctxs["stop"], n)) for n in ("tokens", "positions")) and \
+            torch.equal(look["plain"].hist_lens, look["stop"].hist_lens)
+        st = {n: tuple(v / 1e3 for v in _stats(t[n], 1)) for n in graphs}
+        spread = (st["plain"][2] - st["plain"][1]) * 1e3
+        print("  %2d %2d | without %7.3f [%6.3f .. %6.3f] | with stop %7.3f [%6.3f .. %6.3f] | difference %6.1f us | the plain step's p10 .. p90 spread "
+              "%6.1f us | live %d of %d, emitted %d .. %d ids per task, both runs in the same state: %s"
+              % ((b, k) + st["plain"] + st["stop"] + ((st["stop"][0] - st["plain"][0]) * 1e3, spread, int(stop.live), b, int(stop.gen_lens.min()),
+                                                     int(stop.gen_lens.max()), same)), flush=True)
+        del graphs, ctxs, look, stop
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launch-only", action="store_true")
     ap.add_argument("--step-only", action="store_true")
     ap.add_argument("--sampler", action="store_true", help="the speculative sampling legs (3 and 4) instead of the greedy ones")
+    ap.add_argument("--stop", action="store_true", help="step_lookup with and without the stop conditions (leg 5) instead")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--launches", type=int, default=200)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_lookup: needs a GPU")
     dev = torch.device("cuda:0")
+    if a.stop:
+        stop_step_leg(dev, a.reps, STOP_ROWS)
+        return
     if a.sampler:
         if not a.step_only:
             accept_leg(dev, a.reps, a.launches, STEP_ROWS)

@@ -24,8 +24,13 @@
      is measured from this library and from --parent-so in the same process.  With --step: the whole step_sample with both options
      against the plain one at batch 1, 8 and 32.
 
-usage: python tools/bench_sample.py [--launch-only | --step-only | --penalties | --bias | --top-n [--step]] [--parent-so PATH] [--reps 30]
-       [--launches 100]"""
+  5. --stop (profiles/stop_step.txt, with tools/bench_lookup.py --stop): the stop conditions' launch (zl_stop_advance) alone at 1, 8 and 32
+     tasks behind a one-token and a four-token step, and the whole captured step_sample with and without a stop state whose stops never
+     hit (two stop ids, two four-id stop sequences and a length limit per task) at batch 1, 8 and 32, replays alternated.  The step
+     without stop= issues exactly the launches of the commit before the stop conditions: it is the yardstick.
+
+usage: python tools/bench_sample.py [--launch-only | --step-only | --penalties | --bias | --top-n [--step] | --stop] [--parent-so PATH]
+       [--reps 30] [--launches 100]"""
 import argparse
 import ctypes as C
 import os
@@ -298,6 +303,66 @@ def opts_step_leg(dev, reps):
         torch.cuda.empty_cache()
 
 
+STOPS = dict(stop_ids=[128001, 128009], stop_sequences=[[198, 198, 198, 198], [13, 13, 271, 271]], max_new_tokens=1 << 20)
+
+
+def stop_launch_leg(dev, reps, launches):
+    print("# zl_stop_advance alone, stops that never hit (2 stop ids, 2 stop sequences of 4 ids, a length limit; every task emits n_new ids per "
+          "call): us per launch, median [p10 .. p90] over %d alternated replays of %d launches" % (reps, launches))
+    i32 = dict(dtype=torch.int32, device=dev)
+    graphs, keep = {}, []
+    for b in (1, 8, 32):
+        for n_new in (1, 4):
+            ids, seqs, lens = ops.stop_pack([(STOPS["stop_ids"], STOPS["stop_sequences"])] * b, VOCAB, dev)
+            st = dict(max_new=torch.full((b,), 1 << 30, **i32), gen_lens=torch.zeros(b, **i32), tail=torch.full((b, ops.STOP_TAIL), -1, **i32),
+                      last_token=torch.zeros(b, **i32), finished=torch.zeros(b, **i32))
+            new = torch.randint(1000, 2000, (b, n_new), **i32)
+            out = dict(accepted=torch.zeros(b, **i32), tokens=torch.zeros(b, **i32), positions=torch.zeros(b, **i32),
+                       placement=torch.zeros(b, **i32), valid_lens=torch.zeros(b, **i32), emit_lens=torch.zeros(b, **i32), live=torch.zeros(1, **i32))
+
+            def run(ids=ids, seqs=seqs, lens=lens, st=st, new=new, out=out):
+                for _ in range(launches):
+                    ops.stop_advance(ids, seqs, lens, new_tokens=new, **st, **out)
+            graphs[(b, n_new)] = _graph(run)
+            keep.append((ids, seqs, lens, st, new, out))
+    t = _alternate(graphs, reps)
+    print("#  B  n_new | us per launch            | live at the end")
+    for ((b, n_new), ms), k in zip(t.items(), keep):
+        print("  %2d  %5d | %7.2f [%7.2f .. %7.2f] | %d of %d" % ((b, n_new) + _stats(ms, launches) + (int(k[5]["live"]), b)), flush=True)
+
+
+def stop_step_leg(dev, reps):
+    from zhilight_amd.llama import LLaMA, ModelConfig, QuantConfig
+    cfg = ModelConfig.llama3_8b()
+    model = LLaMA(cfg, QuantConfig(5, 128), dev)
+    model.init_synthetic(seed=1234)
+    seq = 1024
+    print("# whole step_sample (T 0.8, top-k 40, top-p 0.95), synthetic Llama-3-8B GPTQ, %d tokens of history: without stop= against a stop state "
+          "whose stops never hit; ms per step, median [p10 .. p90] over %d alternated replays" % (seq, reps))
+    for b in (1, 8, 32):
+        len_buf = (seq + reps + 16 + 63) // 64 * 64
+        torch.manual_seed(7)
+        ctxs = {n: model.new_context(b, len_buf, seq, fill_random=True) for n in ("plain", "stop")}
+        for t, src in zip(ctxs["stop"].kv, ctxs["plain"].kv):
+            t.copy_(src)
+        ctxs["stop"].tokens.copy_(ctxs["plain"].tokens)
+        kw = dict(temperature=0.8, top_k=40, top_p=0.95, seed=5)
+        states = {n: model.new_sampler(ctxs[n], **kw) for n in ctxs}
+        stop = model.new_stopper(ctxs["stop"], **STOPS)
+        graphs = {"plain": _graph(lambda: model.step_sample(ctxs["plain"], states["plain"])),
+                  "stop": _graph(lambda: model.step_sample(ctxs["stop"], states["stop"], stop=stop))}
+        t = _alternate(graphs, reps)
+        same = torch.equal(ctxs["plain"].tokens, ctxs["stop"].tokens) and torch.equal(ctxs["plain"].positions, ctxs["stop"].positions)
+        st = {n: tuple(v / 1e3 for v in _stats(t[n], 1)) for n in graphs}
+        spread = (st["plain"][2] - st["plain"][1]) * 1e3
+        print("  %2d | without %7.3f [%6.3f .. %6.3f] | with stop %7.3f [%6.3f .. %6.3f] | difference %6.1f us | the plain step's p10 .. p90 spread "
+              "%6.1f us | live %d of %d, emitted %d ids per task, both runs in the same state: %s"
+              % ((b,) + st["plain"] + st["stop"] + ((st["stop"][0] - st["plain"][0]) * 1e3, spread, int(stop.live), b, int(stop.gen_lens.min()), same)),
+              flush=True)
+        del graphs, ctxs, states, stop
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launch-only", action="store_true")
@@ -306,6 +371,7 @@ def main():
     ap.add_argument("--bias", action="store_true")
     ap.add_argument("--top-n", action="store_true")
     ap.add_argument("--step", action="store_true")
+    ap.add_argument("--stop", action="store_true", help="the stop conditions' launch alone and inside step_sample (leg 5)")
     ap.add_argument("--parent-so", default=None)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--launches", type=int, default=100)
@@ -315,6 +381,12 @@ def main():
     dev = torch.device("cuda:0")
     if a.penalties:
         penalty_leg(dev, a.reps, a.launches, a.parent_so)
+        return
+    if a.stop:
+        if not a.step_only:
+            stop_launch_leg(dev, a.reps, a.launches)
+        if not a.launch_only:
+            stop_step_leg(dev, a.reps)
         return
     if a.bias or a.top_n:
         opts_leg(dev, a.reps, a.launches, a.parent_so, a.bias, a.top_n)

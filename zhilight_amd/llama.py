@@ -1010,6 +1010,29 @@ class SamplerState:
         return kw
 
 
+@dataclass
+class StopState:
+    """The device-resident stop conditions of a batch (LLaMA.new_stopper builds it; ops.stop_advance states the rule) for the stop= keyword
+    of step_greedy / step_sample / verify / step_lookup: per-task parameters, what each task has emitted since the state was made, and
+    the last step's outcome."""
+    stop_ids: torch.Tensor      # (B, n_ids <= 16) int32        ids that end the task, -1 = unused
+    stop_seqs: torch.Tensor     # (B, n_seqs <= 8, ld <= 16) int32   multi-token stop sequences
+    seq_lens: torch.Tensor      # (B, n_seqs) int32             0 = unused
+    max_new: torch.Tensor       # (B) int32                     the task's length limit, <= 0 = none
+    gen_lens: torch.Tensor      # (B) int32                     ids emitted since the state was made
+    tail: torch.Tensor          # (B, 15) int32                 the last 15 of them (seeded with the pending token), -1 = none yet
+    last_token: torch.Tensor    # (B) int32                     the last emitted id: what a finished task re-feeds
+    finished: torch.Tensor      # (B) int32                     0 = live, 1 = stop id, 2 = stop sequence, 3 = length
+    emit_lens: torch.Tensor     # (B) int32                     ids each task emitted in the last step (0: finished before it)
+    live: torch.Tensor          # (1) int32                     tasks still live after the last step
+
+    def advance(self, new_tokens, ctx, accepted=None, next_tokens=None):
+        """the one launch behind a step's advance / accept launch"""
+        ops.stop_advance(self.stop_ids, self.stop_seqs, self.seq_lens, self.max_new, self.gen_lens, self.tail, self.last_token, self.finished,
+                         new_tokens, accepted=accepted, next_tokens=next_tokens, tokens=ctx.tokens, positions=ctx.positions,
+                         placement=ctx.placement, valid_lens=ctx.valid_lens, emit_lens=self.emit_lens, live=self.live)
+
+
 class _PromptRows:
     """The rows of one prompt-encode call -- one task's piece, or the pieces of several tasks back to back -- as the layer loop, the
     K/V scatter, the attention and the tail see them.  Built once per call, and the only place that knows whether the call has one
@@ -2015,11 +2038,15 @@ class LLaMA:
         ops.greedy_advance(ws, n, self.cfg.vocab_size, tokens=picks)
         return logits
 
-    def step_greedy(self, ctx: DynBatchContext, skip_gemv=False):
+    def step_greedy(self, ctx: DynBatchContext, skip_gemv=False, stop: Optional[StopState] = None):
         """One greedy decode step entirely on the device (graph-capturable): encode, pick the arg-max token
         inside the lm_head launch + one small reduction, and advance the batch state.  Returns
-        (logits, next_tokens int64)."""
+        (logits, next_tokens int64).  stop: a StopState (new_stopper) adds one launch behind the advance that tests the picks against
+        the tasks' stop conditions (ops.stop_advance): a task that finished in an earlier step is frozen -- its next_tokens entry is -1
+        and its context stays where it ended; stop.finished / gen_lens / live tell.  None: the launches of before."""
         b = ctx.tokens.numel()
+        if stop is not None and stop.finished.numel() != b:
+            raise ops.ZLError("step_greedy: the stop state belongs to another batch size")
         if b > 4 or self.tp:   # the in-launch pick rides the small-M GEMV; bigger batches / TP: one pick + advance launch over the logits
             logits = self.encode(ctx)
             key = ("next", b)
@@ -2028,6 +2055,8 @@ class LLaMA:
             nxt = self._bufs[key]
             ops.argmax_advance(logits, tokens=ctx.tokens, positions=ctx.positions, placement=ctx.placement, valid_lens=ctx.valid_lens,
                                next_tokens=nxt)
+            if stop is not None:
+                stop.advance(ctx.tokens.view(b, 1), ctx, next_tokens=nxt)
             ctx.steps_left -= 1
             return logits, nxt
         key = ("argmax", b)
@@ -2037,6 +2066,8 @@ class LLaMA:
         ws, nxt = self._bufs[key]
         logits = self.encode(ctx, argmax_ws=ws, skip_gemv=skip_gemv)
         ops.greedy_advance(ws, b, self.cfg.vocab_size, ctx.tokens, ctx.positions, ctx.placement, ctx.valid_lens, nxt)
+        if stop is not None:
+            stop.advance(ctx.tokens.view(b, 1), ctx, next_tokens=nxt)
         ctx.steps_left -= 1
         return logits, nxt
 
@@ -2048,7 +2079,8 @@ class LLaMA:
         everywhere: the rows route is ahead by 0.7 - 1.2 % of the step at B <= 2 and by 4 - 9 % at B >= 4"""
         return "causal" if b * len_q <= 4 else "rows"
 
-    def verify(self, ctx: DynBatchContext, drafts: torch.Tensor, attn="auto", sampler: Optional[SamplerState] = None):
+    def verify(self, ctx: DynBatchContext, drafts: torch.Tensor, attn="auto", sampler: Optional[SamplerState] = None,
+               stop: Optional[StopState] = None):
         """One speculative step on the device (graph-capturable, no host round trip): check the K = drafts.shape[1] draft tokens of
         every task in ONE pass of the decode layer loop over len_q = K + 1 rows per task, keep the longest prefix the model's own
         picks confirm plus one token of its own, and roll the batch state back to there -- SessionGenerator.feed +
@@ -2082,6 +2114,11 @@ class LLaMA:
         2 d of step_sample's class there and a log-probability within 2 d / T; equal logits give equal ids.  sampler.top_ids /
         top_logprobs (B, N) are NOT written by this call (the C call has no per-task output for them) and keep the last
         step_sample's values: after a speculative step the pending token's alternatives are sampler.row_top_ids[b, accepted[b]].
+        stop: a StopState (new_stopper) adds one launch behind the accept launch (ops.stop_advance): the emitted ids are cut behind the
+        first stop id / stop sequence / length limit -- tokens holds -1 there, accepted = ids kept - 1, and tokens / positions / placement /
+        valid_lens of the context are what a step that emitted only those leaves, so the ids accepted behind a stop are undone.  A
+        task finished earlier is frozen: accepted = -1, its row -1, its context unmoved.  The sampler's draws, seen and row buffers
+        are NOT cut: they are valid for a task's first stop.emit_lens entries.  None: the launches of before.
         Returns SpecResult(logits (B * len_q, vocab), accepted (B) int32, tokens (B, len_q) int32); the three are reused by the next
         call with the same K."""
         c, dev = self.cfg, self.device
@@ -2099,6 +2136,8 @@ class LLaMA:
             raise ops.ZLError("verify: drafts are (B, K) contiguous int32 on the context's device, K >= 1")
         if sampler is not None and sampler.temperature.numel() != b:
             raise ops.ZLError("verify: the sampler state belongs to another batch size")
+        if stop is not None and stop.finished.numel() != b:
+            raise ops.ZLError("verify: the stop state belongs to another batch size")
         len_q = drafts.shape[1] + 1
         m = b * len_q
         if attn == "auto":
@@ -2171,6 +2210,8 @@ class LLaMA:
                                    accepted=accepted, out_tokens=out_tokens, out_logprobs=sampler.row_logprobs, logprobs=sampler.logprobs,
                                    u_out=sampler.row_u, rep_penalty=sampler.repetition_penalty, presence=sampler.presence_penalty,
                                    seen=sampler.seen, **opts)
+        if stop is not None:
+            stop.advance(out_tokens, ctx, accepted=accepted)
         ctx.steps_left -= len_q
         return SpecResult(logits, accepted, out_tokens)
 
@@ -2215,7 +2256,8 @@ class LLaMA:
                          drafts=state.drafts, match=state.match)
         return state
 
-    def step_lookup(self, ctx: DynBatchContext, state: LookupState, attn="auto", sampler: Optional[SamplerState] = None):
+    def step_lookup(self, ctx: DynBatchContext, state: LookupState, attn="auto", sampler: Optional[SamplerState] = None,
+                    stop: Optional[StopState] = None):
         """One speculative step with the drafter inside, all on the device: verify(ctx, state.drafts, attn, sampler), then ONE launch
         (ops.lookup_draft) appends the tokens the step emitted to the tasks' histories and drafts the next step's tokens into
         state.drafts.  No host round trip; capturable after one eager call (verify's rule), and a replay carries ctx, state and the
@@ -2224,16 +2266,19 @@ class LLaMA:
         however many drafts are accepted; None = greedy.  Sampling and lookup need no interleaving by hand.
         A caller that does interleave step_greedy or step_sample keeps the state in step by feeding the token that step left pending:
         ops.lookup_draft(state.history, state.hist_lens, state.k, state.max_ngram, state.min_ngram,
-        new_tokens=ctx.tokens.view(B, 1), drafts=state.drafts, match=state.match)."""
+        new_tokens=ctx.tokens.view(B, 1), drafts=state.drafts, match=state.match).
+        stop: verify's stop=.  Its launch runs BEFORE the drafter's, so ids behind a stop never enter the history, and a finished task's
+        history stands still (its row is -1)."""
         b = ctx.tokens.numel()
         if state.drafts.shape != (b, state.k) or state.history.shape[0] != b:
             raise ops.ZLError("step_lookup: the state belongs to another batch size")
-        res = self.verify(ctx, state.drafts, attn, sampler)
+        res = self.verify(ctx, state.drafts, attn, sampler, stop)
         ops.lookup_draft(state.history, state.hist_lens, state.k, state.max_ngram, state.min_ngram, new_tokens=res.tokens,
                          drafts=state.drafts, match=state.match)
         return res
 
-    def generate_lookup(self, ctx: DynBatchContext, state: LookupState, max_new_tokens, sampler: Optional[SamplerState] = None):
+    def generate_lookup(self, ctx: DynBatchContext, state: LookupState, max_new_tokens, sampler: Optional[SamplerState] = None,
+                        stop: Optional[StopState] = None):
         """The eager convenience loop around step_lookup -- the NON-captured path: it reads accepted / tokens back to the host once per
         round.  Runs rounds until every task has emitted max_new_tokens tokens or the KV buffers have no room for another step
         (ctx.steps_left < k + 1); the batch moves in lock step, so tasks that are done keep running until the last one is.
@@ -2241,7 +2286,11 @@ class LLaMA:
         max_new_tokens; stats = {"steps", "emitted": ids per task before the cut (= steps + accepted), "accepted": accepted drafts per
         task, "mean_accepted": accepted drafts per task and step}.  With a sampler (step_lookup's sampler=) the steps sample, and
         stats gains "logprobs": per task the emitted ids' tempered log-probabilities, cut as the ids are; a sampler with top_logprobs
-        = N adds "top_ids" / "top_logprobs": per task and emitted id the N alternatives (lists of N), cut the same way."""
+        = N adds "top_ids" / "top_logprobs": per task and emitted id the N alternatives (lists of N), cut the same way.
+        stop: a StopState (new_stopper; step_lookup's stop=).  A task then ends at its stop as well: the rounds' results are sliced by
+        stop.emit_lens, the loop runs until every task has emitted max_new_tokens ids OR has finished, and stats gains "finished": per
+        task 0 (not finished), 1 (stop id), 2 (stop sequence) or 3 (the state's own length limit).  ctx.steps_left keeps its
+        conservative host-side count (k + 1 slots per round and task), finished tasks included."""
         b = ctx.tokens.numel()
         out = [[] for _ in range(b)]
         lps = [[] for _ in range(b)]
@@ -2249,14 +2298,17 @@ class LLaMA:
         top = sampler is not None and sampler.top_n > 0
         accepted = [0] * b
         steps = 0
-        while min(len(o) for o in out) < max_new_tokens and ctx.steps_left >= state.k + 1:
-            res = self.step_lookup(ctx, state, sampler=sampler)
+        done = [0] * b
+        while min(max_new_tokens if d else len(o) for o, d in zip(out, done)) < max_new_tokens and ctx.steps_left >= state.k + 1:
+            res = self.step_lookup(ctx, state, sampler=sampler, stop=stop)
             acc, tok = res.accepted.tolist(), res.tokens.tolist()
+            if stop is not None:
+                acc, done = [n - 1 for n in stop.emit_lens.tolist()], stop.finished.tolist()      # a frozen task: -1, an empty slice
             lp = sampler.row_logprobs.tolist() if sampler is not None else None
             ti, tl = (sampler.row_top_ids.tolist(), sampler.row_top_logprobs.tolist()) if top else (None, None)
             for j in range(b):
                 out[j] += tok[j][:acc[j] + 1]
-                accepted[j] += acc[j]
+                accepted[j] += max(acc[j], 0)
                 if lp is not None:
                     lps[j] += lp[j][:acc[j] + 1]
                 if top:
@@ -2265,6 +2317,8 @@ class LLaMA:
             steps += 1
         stats = {"steps": steps, "emitted": [len(o) for o in out], "accepted": accepted,
                  "mean_accepted": sum(accepted) / (steps * b) if steps else 0.0}
+        if stop is not None:
+            stats["finished"] = done
         if sampler is not None:
             stats["logprobs"] = [l[:max_new_tokens] for l in lps]
         if top:
@@ -2358,7 +2412,53 @@ class LLaMA:
                             seeds=torch.tensor(sd, dtype=torch.int64, device=dev), draws=torch.zeros(b, dtype=torch.int64, device=dev),
                             logprobs=torch.zeros(b, dtype=torch.float32, device=dev), u=torch.zeros(b, dtype=torch.float32, device=dev))
 
-    def step_sample(self, ctx: DynBatchContext, state: SamplerState):
+    def new_stopper(self, ctx: DynBatchContext, stop_ids=None, stop_sequences=None, max_new_tokens=0) -> StopState:
+        """The state for the stop= keyword of step_greedy / step_sample / verify / step_lookup and the generate loops.  stop_ids: ids that
+        end a task (EOS ids, stop token ids), at most 16 -- one int or one list of ints for every task, or a sequence of B lists / Nones.
+        stop_sequences: multi-token stops, at most 8 per task of 1 .. 16 ids each -- one list of id lists for every task, or a sequence
+        of B such lists / Nones.  max_new_tokens: a task's length limit, 0 = none -- one int or B ints.  (new_sampler's convention; a
+        flat list of ints as stop_ids is the one list for every task, and B lists are per task.)
+        The state counts and tests the ids emitted AFTER its creation, as the generate_* results do.  The token pending in ctx.tokens
+        seeds the memory of the last ids, so a stop sequence may begin with it; it is not itself tested or counted: a pending EOS does
+        not finish the task.  With nothing set for any task the state is still valid and no task ever finishes."""
+        b, dev = ctx.tokens.numel(), ctx.tokens.device
+
+        def ints(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+        if stop_ids is None or ints(stop_ids):
+            ids = [[] if stop_ids is None else [stop_ids]] * b
+        else:
+            ids = list(stop_ids)
+            if all(ints(v) for v in ids):                                   # one flat list: every task's
+                ids = [ids] * b
+            elif len(ids) != b:
+                raise ops.ZLError(f"new_stopper: {b} tasks, {len(ids)} lists of stop_ids")
+        if stop_sequences is None:
+            seqs = [[]] * b
+        else:
+            seqs = list(stop_sequences)
+            if seqs and all(v is not None and len(v) and all(ints(i) for i in v) for v in seqs):       # id lists: every task's sequences
+                seqs = [seqs] * b
+            elif len(seqs) != b:
+                raise ops.ZLError(f"new_stopper: {b} tasks, {len(seqs)} lists of stop_sequences")
+        lim = max_new_tokens
+        if torch.is_tensor(lim):
+            lim = lim.tolist()
+        lim = list(lim) if isinstance(lim, (list, tuple, np.ndarray)) else [lim] * b
+        if len(lim) != b:
+            raise ops.ZLError(f"new_stopper: {b} tasks, {len(lim)} values of max_new_tokens")
+        if any(not ints(v) or not 0 <= int(v) < 1 << 31 for v in lim):
+            raise ops.ZLError("new_stopper: max_new_tokens is an integer >= 0 (0 = no limit)")
+        sid, ssq, sln = ops.stop_pack(list(zip(ids, seqs)), self.cfg.vocab_size, dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        tail = torch.full((b, ops.STOP_TAIL), -1, **i32)
+        tail[:, ops.STOP_TAIL - 1].copy_(ctx.tokens)
+        return StopState(stop_ids=sid, stop_seqs=ssq, seq_lens=sln, max_new=torch.tensor([int(v) for v in lim], **i32),
+                         gen_lens=torch.zeros(b, **i32), tail=tail, last_token=ctx.tokens.clone(), finished=torch.zeros(b, **i32),
+                         emit_lens=torch.zeros(b, **i32), live=torch.full((1,), b, **i32))
+
+    def step_sample(self, ctx: DynBatchContext, state: SamplerState, stop: Optional[StopState] = None):
         """One sampling decode step entirely on the device (graph-capturable after one eager call, no host round trip): encode, then
         ONE launch (ops.sample_advance) picks every task's token under its temperature / top-k / top-p from its own Philox stream
         and advances the batch state, as step_greedy's pick + advance launch does above four rows -- here at every batch size and
@@ -2368,10 +2468,14 @@ class LLaMA:
         int64).  Penalties: a state built with new_sampler's repetition_penalty / presence_penalty applies them inside that launch --
         the kernel reads the classes of state.seen as ops.repetition_penalty would have left them and records its pick there; the
         returned logits are the raw ones.  The launch count and the host work per step are the same.  A logit bias and the top-N
-        alternatives (new_sampler's logit_bias / top_logprobs) ride in the same launch: state.top_ids / top_logprobs (B, N)."""
+        alternatives (new_sampler's logit_bias / top_logprobs) ride in the same launch: state.top_ids / top_logprobs (B, N).
+        stop: step_greedy's stop= -- one launch behind the sampling launch; a finished task's next_tokens entry is -1, its context
+        stands still, and the sampler's draws / seen / logprobs of such a task go on changing and mean nothing."""
         b = ctx.tokens.numel()
         if state.temperature.numel() != b:
             raise ops.ZLError("step_sample: the state belongs to another batch size")
+        if stop is not None and stop.finished.numel() != b:
+            raise ops.ZLError("step_sample: the stop state belongs to another batch size")
         logits = self.encode(ctx)
         key = ("next", b)
         if key not in self._bufs:
@@ -2381,18 +2485,30 @@ class LLaMA:
                            positions=ctx.positions, placement=ctx.placement, valid_lens=ctx.valid_lens, next_tokens=nxt,
                            logprobs=state.logprobs, u_out=state.u, rep_penalty=state.repetition_penalty, presence=state.presence_penalty,
                            seen=state.seen, **state.opts())
+        if stop is not None:
+            stop.advance(ctx.tokens.view(b, 1), ctx, next_tokens=nxt)
         ctx.steps_left -= 1
         return logits, nxt
 
-    def generate_sample(self, ctx: DynBatchContext, state: SamplerState, max_new_tokens):
+    def generate_sample(self, ctx: DynBatchContext, state: SamplerState, max_new_tokens, stop: Optional[StopState] = None, poll=8):
         """The eager convenience loop around step_sample: up to max_new_tokens steps, fewer where the KV buffers run out
         (ctx.steps_left).  Returns (tokens (B, steps) int64, logprobs (B, steps) fp32): what every task emitted behind its pending
         ctx.tokens entry of the time of the call, and each token's tempered log-probability.  One read-back at the end.  A state with
-        top_logprobs = N > 0 returns a third element, (top_ids (B, steps, N) int32, top_logprobs (B, steps, N) fp32)."""
+        top_logprobs = N > 0 returns a third element, (top_ids (B, steps, N) int32, top_logprobs (B, steps, N) fp32).
+        stop: a StopState (new_stopper) ends tasks on the device (step_sample's stop=).  The loop then reads stop.live back every `poll`
+        steps and ends once no task is live, at most poll - 1 steps behind the last finish; the token matrix holds -1 behind a task's
+        end (the other results are not cut there), and stop.gen_lens / stop.finished give the lengths and the reasons.  ctx.steps_left
+        keeps its conservative host-side count of one slot per step and task: a finished task uses no more of its buffer, but the
+        host does not know that without a read-back.  None: the loop of before, no read-back but the last."""
         b, dev = ctx.tokens.numel(), ctx.tokens.device
+        poll = int(poll)
+        if stop is not None and poll < 1:
+            raise ops.ZLError("generate_sample: poll >= 1")
         toks, lps, tis, tls = [], [], [], []
-        for _ in range(max(0, min(int(max_new_tokens), ctx.steps_left))):
-            _, nxt = self.step_sample(ctx, state)
+        for step in range(max(0, min(int(max_new_tokens), ctx.steps_left))):
+            if stop is not None and step and step % poll == 0 and int(stop.live) == 0:
+                break
+            _, nxt = self.step_sample(ctx, state, stop)
             toks.append(nxt.clone())
             lps.append(state.logprobs.clone())
             if state.top_n:

@@ -902,6 +902,124 @@ def lookup_draft(history, hist_lens, k, max_ngram=3, min_ngram=1, new_tokens=Non
     return drafts.view(b, k), match.view(b, 2)
 
 
+STOP_IDS_MAX = 16          # stop ids per task
+STOP_SEQS_MAX = 8          # stop sequences per task
+STOP_SEQ_LEN_MAX = 16      # ids per stop sequence
+STOP_TAIL = 15             # emitted ids a task remembers: a sequence's ids but its last
+STOP_NEW_MAX = 32          # ids a step emits per task
+
+
+def stop_rows(stops, vocab):
+    """The host half of stop_pack, numpy only: stops = B pairs (stop_ids, stop_sequences) -- a list of ids and a list of id lists, either
+    None or empty for none -- over a vocabulary of `vocab` ids -> (stop_ids (B, n_ids) int32, -1 behind a task's ids; stop_seqs
+    (B, n_seqs, ld) int32, -1 behind a sequence's ids; seq_lens (B, n_seqs) int32, 0 = unused), each width the longest list's, at least 1.
+    Refuses (ZLError) more than 16 ids or 8 sequences per task, a sequence that is empty or longer than 16, and ids outside [0, vocab)."""
+    vocab = int(vocab)
+    if vocab < 1 or vocab >= 1 << 31:
+        raise ZLError("stop_pack: 1 <= vocab < 2^31")
+    rows = []
+    try:
+        for t, pair in enumerate(stops):
+            ids, seqs = (None, None) if pair is None else pair
+            ids = [] if ids is None else [int(i) for i in ids]
+            seqs = [] if seqs is None else [[int(i) for i in s] for s in seqs]
+            rows.append((ids, seqs))
+    except (TypeError, ValueError):
+        raise ZLError("stop_pack: one pair (stop ids, stop sequences) of integer ids per task") from None
+    if not rows:
+        raise ZLError("stop_pack: one pair (stop ids, stop sequences) of integer ids per task")
+    for t, (ids, seqs) in enumerate(rows):
+        if len(ids) > STOP_IDS_MAX:
+            raise ZLError(f"stop_pack: task {t}: {len(ids)} stop ids, at most {STOP_IDS_MAX}")
+        if len(seqs) > STOP_SEQS_MAX:
+            raise ZLError(f"stop_pack: task {t}: {len(seqs)} stop sequences, at most {STOP_SEQS_MAX}")
+        if any(not 1 <= len(s) <= STOP_SEQ_LEN_MAX for s in seqs):
+            raise ZLError(f"stop_pack: task {t}: a stop sequence has 1 .. {STOP_SEQ_LEN_MAX} ids")
+        if any(not 0 <= i < vocab for i in ids) or any(not 0 <= i < vocab for s in seqs for i in s):
+            raise ZLError(f"stop_pack: task {t}: ids outside [0, {vocab})")
+    b = len(rows)
+    ids = np.full((b, max([1] + [len(i) for i, _ in rows])), -1, np.int32)
+    seqs = np.full((b, max([1] + [len(s) for _, s in rows]), max([1] + [len(q) for _, s in rows for q in s])), -1, np.int32)
+    lens = np.zeros(seqs.shape[:2], np.int32)
+    for t, (i, s) in enumerate(rows):
+        ids[t, :len(i)] = i
+        for q, sq in enumerate(s):
+            seqs[t, q, :len(sq)], lens[t, q] = sq, len(sq)
+    return ids, seqs, lens
+
+
+def stop_pack(stops, vocab, device):
+    """B pairs (stop_ids, stop_sequences) (None = none for that task) -> stop_advance's padded parameter tensors (stop_ids (B, n_ids),
+    stop_seqs (B, n_seqs, ld), seq_lens (B, n_seqs)), int32 on `device`; stop_rows states the layout and the refusals."""
+    return tuple(torch.from_numpy(a).to(device) for a in stop_rows(stops, vocab))
+
+
+def stop_advance(stop_ids, stop_seqs, seq_lens, max_new, gen_lens, tail, last_token, finished, new_tokens, accepted=None, next_tokens=None,
+                 tokens=None, positions=None, placement=None, valid_lens=None, emit_lens=None, live=None):
+    """The stop conditions of a decode step (zl_stop_advance, one launch), directly behind the step's advance / accept call: per task,
+    test the ids the step emitted -- new_tokens (B, n_new <= 32) int32, a row's ids before its first negative one; at n_new = 1 it may be
+    tokens.view(B, 1) itself -- against the task's stop ids (stop_ids (B, <= 16) int32, -1 = unused), its stop sequences (stop_seqs
+    (B, <= 8, <= 16) int32 with seq_lens (B, <= 8), 0 = unused; matched against the task's last 15 emitted ids and the new ones, so across
+    steps) and its length limit (max_new (B) int32, <= 0 = none); each of the three may be None.  The first hit ends the task: its row
+    keeps the ids up to and including the hit and -1 behind, accepted / tokens / next_tokens and positions / placement / valid_lens
+    (each optional) become what a step that emitted only those ids leaves, and finished[b] = 1 (stop id), 2 (stop sequence) or 3
+    (length).  A task already finished is frozen: its row becomes -1, accepted and next_tokens -1, the three counters drop by what the
+    step added and tokens[b] = last_token[b], so it re-feeds the same token at the same position for good.  State, in place: gen_lens
+    (B), tail (B, 15), last_token (B), finished (B), all int32.  Returns (emit_lens (B) int32 = ids each task emitted in this step,
+    live (1) int32 = tasks still live); emit_lens / live: buffers to write into (a captured call)."""
+    if not (torch.is_tensor(new_tokens) and new_tokens.dim() == 2 and new_tokens.dtype == torch.int32 and new_tokens.is_contiguous()
+            and new_tokens.shape[0] >= 1 and new_tokens.shape[1] >= 1):
+        raise ZLError("stop_advance: new_tokens is (B, n_new) contiguous int32, n_new >= 1")
+    b, n_new = new_tokens.shape
+    if n_new > STOP_NEW_MAX:
+        raise ZLError(f"stop_advance: at most {STOP_NEW_MAX} new ids per task and step")
+    dev = new_tokens.device
+    if not new_tokens.is_cuda:
+        raise ZLError("stop_advance: CUDA new_tokens, every other tensor on its device")
+
+    def i32(t, shape, what, dtype=torch.int32):
+        if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
+            raise ZLError(f"stop_advance: {what}: contiguous {str(dtype).replace('torch.', '')} {shape} on new_tokens' device"
+                          + (" (the state belongs to another batch size?)" if what in ("gen_lens", "tail", "last_token", "finished") else ""))
+
+    for t, shape, what in ((gen_lens, (b,), "gen_lens"), (tail, (b, STOP_TAIL), "tail"), (last_token, (b,), "last_token"),
+                           (finished, (b,), "finished")):
+        i32(t, shape, what)
+    n_ids = n_seqs = ld = 0
+    if stop_ids is not None:
+        if not (torch.is_tensor(stop_ids) and stop_ids.dim() == 2 and 1 <= stop_ids.shape[1] <= STOP_IDS_MAX):
+            raise ZLError(f"stop_advance: stop_ids is (B, 1 .. {STOP_IDS_MAX}) int32")
+        n_ids = stop_ids.shape[1]
+        i32(stop_ids, (b, n_ids), "stop_ids")
+    if (stop_seqs is None) != (seq_lens is None):
+        raise ZLError("stop_advance: stop_seqs and seq_lens come together")
+    if stop_seqs is not None:
+        if not (torch.is_tensor(stop_seqs) and stop_seqs.dim() == 3 and 1 <= stop_seqs.shape[1] <= STOP_SEQS_MAX
+                and 1 <= stop_seqs.shape[2] <= STOP_SEQ_LEN_MAX):
+            raise ZLError(f"stop_advance: stop_seqs is (B, 1 .. {STOP_SEQS_MAX}, 1 .. {STOP_SEQ_LEN_MAX}) int32")
+        n_seqs, ld = stop_seqs.shape[1:]
+        i32(stop_seqs, (b, n_seqs, ld), "stop_seqs")
+        i32(seq_lens, (b, n_seqs), "seq_lens")
+    for t, what in ((max_new, "max_new"), (accepted, "accepted"), (tokens, "tokens"), (positions, "positions"), (placement, "placement"),
+                    (valid_lens, "valid_lens"), (emit_lens, "emit_lens")):
+        if t is not None:
+            i32(t, (b,), what)
+    if next_tokens is not None:
+        i32(next_tokens, (b,), "next_tokens", torch.int64)
+    if live is not None:
+        i32(live, (1,), "live")
+    if tokens is not None and tokens.data_ptr() == new_tokens.data_ptr() and n_new != 1:
+        raise ZLError("stop_advance: new_tokens may be tokens itself at n_new = 1 only")
+    if emit_lens is None:
+        emit_lens = torch.empty(b, dtype=torch.int32, device=dev)
+    if live is None:
+        live = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().zl_stop_advance(_p(stop_ids), _i(n_ids), _p(stop_seqs), _p(seq_lens), _i(n_seqs), _i(ld), _p(max_new), _p(gen_lens), _p(tail),
+                                _p(last_token), _p(finished), _p(new_tokens), _i(n_new), _i(b), _p(accepted), _p(next_tokens), _p(tokens),
+                                _p(positions), _p(placement), _p(valid_lens), _p(emit_lens), _p(live), _stream()), "stop_advance")
+    return emit_lens, live
+
+
 def seen_words(n):
     """The uint32 words of one task's row of a penalty bitmap over n token ids: ceil(n / 32)."""
     return (int(n) + 31) // 32
