@@ -1023,6 +1023,46 @@ int zl_stop_advance(const int32_t* stop_ids, int64_t n_ids, const int32_t* stop_
                     const int32_t* max_new, int32_t* gen_lens, int32_t* tail, int32_t* last_token, int32_t* finished, int32_t* new_tokens,
                     int64_t n_new, int64_t b, int32_t* accepted, int64_t* next_tokens, int32_t* tokens, int32_t* positions,
                     int32_t* placement, int32_t* valid_lens, int32_t* emit_lens, int32_t* live, zl_stream_t s);
+/* Slot admission (csrc/slot_rows.hip): re-initialise, in place and in ONE launch, every per-task state row of n >= 1 distinct slots of
+ * a batch of b -- the sampler's, the stop state's and the lookup drafter's -- for new requests, while every other slot's rows are
+ * neither read-modified nor written.  It replaces SearcherImplV1's per-task set-up on the host (src/generator/batch_generator.cpp, where a
+ * new task's SearchTask fields, its random generator and its stop lists are built when it enters max_batch_active) and the part of
+ * fill_search_tokens that seeds a new task's first token.  It runs behind the prompt encode that left the slot's first token in
+ * tokens[s]: that token is the slot's PENDING token below.
+ * blob: ONE packed int32 array on the device, built on the host (ops.slots_pack): 16 header words (the host's: magic, n, vocab, flags,
+ * widths, sizes), then n records of rec_words = 16 + n_ids + n_seqs + n_seqs * seq_ld words each, then the variable part the records
+ * point into.  A record:  [0] slot  [1] kind: 1 = admit, 0 = park  [2] temperature (fp32 bits)  [3] top_k  [4] top_p (fp32 bits)
+ * [5] [6] seed, low / high word  [7] repetition penalty  [8] presence penalty (fp32 bits)  [9] max_new  [10] [11] penalty ids: word offset
+ * into the blob, count  [12] [13] bias: offset, count -- count ascending ids, then count fp32 values  [14] [15] history: offset, length;
+ * then the slot's stop_ids row, its seq_lens row and its stop_seqs rows at the state's widths, -1 / 0 in the unused entries.
+ * ADMIT, slot s (each group below is skipped when its pointers are NULL):
+ *   sampler:  temperature / top_k / top_p / seeds [s] <- the record's;  draws[s] = 0, logprobs[s] = 0, u[s] = 0.
+ *   bitmap (rep_penalty, presence, seen (b, seen_ld) all given):  the two scalars <- the record's;  row s of seen <- exactly the bits of
+ *     {pending token} + the penalty ids, ids outside [0, vocab) skipped, duplicates allowed, every other word of the row 0.
+ *   bias (bias_ids, bias_vals (b, bias_ld), bias_cnt, bias_bits (b, bits_ld)):  row s <- the count ids, -1 behind;  the values, 0 behind;
+ *     the count;  the ids as a bitmap (zl_sample_advance_opts' layout).
+ *   top-N (top_ids, top_logprobs (b, top_n)):  row s <- -1 / NaN (0x7fc00000).
+ *   stop:  rows s of stop_ids / seq_lens / stop_seqs <- the record's;  max_new[s] <- the record's;  gen_lens[s] = 0;  tail[s] = -1 but
+ *     tail[s, 14] = pending;  last_token[s] = pending;  finished[s] = 0;  emit_lens[s] = 0.
+ *   lookup:  history[s, 0 .. len - 1] <- the record's ids (the rest of the row is not written), hist_lens[s] = len;  the caller's
+ *     zl_lookup_draft launch follows with draft_new as its new_tokens.
+ * PARK, slot s:  tokens[s] = 0, positions[s] = placement[s] = 0, valid_lens[s] = 1;  last_token[s] = 0, tail[s] = -1, emit_lens[s] = 0;
+ *   finished[s] stays (the host parks finished slots only): the slot re-feeds token 0 at position 0 and attends over one key.
+ * live[0] (with the stop group) = tasks with finished == 0 after the call: the admitted slots + the live ones among the rest, whose
+ *   finished entries this launch does not write.  draft_new (b) int32, optional: pending for admitted slots, -1 everywhere else.
+ * A record whose slot lies outside [0, b) is dropped.  Duplicate slots are the caller's to refuse.
+ * ZL_EINVAL: a null blob / tokens, n < 1, b < 1, vocab < 1, a group given in part, park without positions / placement / valid_lens,
+ * rec_words that does not fit the stop widths;  ZL_ESHAPE: b > 131072, n > b, vocab >= 2^31, bias_ld > 1024, n_ids > 16, n_seqs > 8,
+ * seq_ld > 16, top_n > 32, a bitmap row narrower than ceil(vocab / 32) words.
+ * ONE launch, one 256-thread workgroup per record; the bitmap rows are built in 16 KB of LDS (LDS atomics) and stored with 16-byte
+ * vector stores where the row is aligned; ordinary vector stores only, no global atomics, no workspace; deterministic. */
+int zl_slots_admit(const int32_t* blob, int64_t n, int64_t rec_words, int64_t b, int64_t vocab, int32_t* tokens, int32_t* positions,
+                   int32_t* placement, int32_t* valid_lens, float* temperature, int32_t* top_k, float* top_p, int64_t* seeds, int64_t* draws,
+                   float* logprobs, float* u, float* rep_penalty, float* presence, int32_t* seen, int64_t seen_ld, int32_t* bias_ids,
+                   float* bias_vals, int32_t* bias_cnt, int32_t* bias_bits, int64_t bias_ld, int64_t bits_ld, int32_t* top_ids,
+                   float* top_logprobs, int64_t top_n, int32_t* stop_ids, int32_t* stop_seqs, int32_t* seq_lens, int64_t n_ids, int64_t n_seqs,
+                   int64_t seq_ld, int32_t* max_new, int32_t* gen_lens, int32_t* tail, int32_t* last_token, int32_t* finished,
+                   int32_t* emit_lens, int32_t* live, int32_t* history, int64_t cap, int32_t* hist_lens, int32_t* draft_new, zl_stream_t s);
 /* The stochastic pick of a decode step + zl_argmax_advance's bookkeeping in one launch (csrc/sample_rows.hip): temperature, top-k and
  * top-p sampling per row under the reference's rule (src/generator/random_util.cu:83-199, which its scheduler runs on the host),
  * evaluated in fp32 on fp32 probabilities.  logits (rows, n), row stride ld elements, type = ZL_T_F16 / ZL_T_BF16 (ZL_T_F32: ZL_EDTYPE

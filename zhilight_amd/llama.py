@@ -942,6 +942,14 @@ class DynBatchContext:
     # that other rows of the same call write -- encode() must scatter every row before any row attends (never the launch that
     # scatters and attends at once)
     row_expanded: bool = False
+    # LLaMA.admit / park: slot -> the KV rows the slot can ever use (prompt + clamped length limit + draft rows + 1 <= len_buf; 0 = parked).
+    # Such a slot is kept inside its buffer by the device-side length stop, so it does not bound steps_left; a plain prefill of the
+    # slot takes it out again
+    slot_guard: Dict[int, int] = field(default_factory=dict)
+    # slot -> (room, at): the host's bound of a slot that is NOT guarded -- a prompt encode left it `room` decode steps while steps_left
+    # stood at `at`, so it has room - (at - steps_left) left now; admit / park take the minimum of these when a guarded slot replaces
+    # the one that bounded steps_left.  A slot in neither table is bounded by steps_left as it stands
+    slot_room: Dict[int, tuple] = field(default_factory=dict)
 
 
 # LLaMA.verify's result: the (B * len_q, vocab) logits of the step's rows, accepted (B) int32 drafts per task, tokens (B, len_q) int32 =
@@ -2018,6 +2026,9 @@ class LLaMA:
             ctx.placement.index_copy_(0, r.tasks_dev, r.ends_dev)
             ctx.valid_lens.index_copy_(0, r.tasks_dev, r.ends_dev + 1)
         ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - max(r.ends))
+        for t, end in zip(r.tasks, r.ends):
+            ctx.slot_guard.pop(t, None)
+            ctx.slot_room[t] = (ctx.max_len_buf - end, ctx.steps_left)
         return logits
 
     def _prompt_logits_and_pick(self, last_hidden, picks):
@@ -2328,7 +2339,7 @@ class LLaMA:
 
     # ---- sampling steps -----------------------------------------------------------------------------
     def new_sampler(self, ctx: DynBatchContext, temperature=1.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0, presence_penalty=0.0,
-                    penalty_tokens=None, logit_bias=None, top_logprobs=0) -> SamplerState:
+                    penalty_tokens=None, logit_bias=None, top_logprobs=0, penalties=False, bias_ld=0) -> SamplerState:
         """The state for step_sample.  temperature / top_k / top_p / seed: a scalar for every task or a sequence of B values.
         temperature 0 = greedy; top_k 0 = off; top_p 1 = off; a scalar seed s gives task j the seed s + j, so the tasks draw different
         streams and a task's stream does not depend on the rest of the batch.
@@ -2341,8 +2352,14 @@ class LLaMA:
         1024 ids per task, values finite or -inf (a ban).  Added inside the sampling launch behind the penalty (ops.sample_advance's
         bias=).  top_logprobs: N in 0 .. 32, one value for the state: every step also returns the N most likely tokens of the
         penalised and biased distribution with their log-probabilities (state.top_ids / top_logprobs).  With both off the state and
-        the calls are the ones without them."""
+        the calls are the ones without them.
+        penalties=True / bias_ld=N (1 .. 1024): carry the bitmap / bias rows of width N whatever the tasks ask for now, so that later
+        requests may use them (LLaMA.admit rewrites a slot's rows in place and cannot widen a state).  bias_ld below the longest map
+        raises.  The defaults (False, 0) build exactly the states of before."""
         b, dev = ctx.tokens.numel(), ctx.tokens.device
+        bias_ld = int(bias_ld)
+        if not 0 <= bias_ld <= ops.LOGIT_BIAS_MAX:
+            raise ops.ZLError(f"new_sampler: bias_ld in 0 .. {ops.LOGIT_BIAS_MAX}")
 
         def per_task(v, what):
             if torch.is_tensor(v):
@@ -2377,7 +2394,7 @@ class LLaMA:
         if penalty_tokens is not None and len(penalty_tokens) != b:
             raise ops.ZLError(f"new_sampler: {b} tasks, {len(penalty_tokens)} sequences of penalty_tokens")
         pen = {}
-        if penalty_tokens is not None or any(float(v) != 1.0 for v in rp) or any(float(v) != 0.0 for v in pp):
+        if penalties or penalty_tokens is not None or any(float(v) != 1.0 for v in rp) or any(float(v) != 0.0 for v in pp):
             vocab = self.cfg.vocab_size
             seen = torch.zeros((b, ops.seen_words(vocab)), dtype=torch.int32, device=dev)
             ops.seen_mark(seen, ctx.tokens.view(b, 1), vocab)               # the pending token is an emitted one
@@ -2396,13 +2413,21 @@ class LLaMA:
                        presence_penalty=torch.tensor([float(v) for v in pp], dtype=torch.float32, device=dev), seen=seen)
         if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, (int, np.integer)) or not 0 <= int(top_logprobs) <= ops.TOP_LOGPROBS_MAX:
             raise ops.ZLError(f"new_sampler: top_logprobs is an integer in 0 .. {ops.TOP_LOGPROBS_MAX}")
-        if logit_bias is not None:
-            maps = [logit_bias] * b if isinstance(logit_bias, dict) else list(logit_bias)
+        if logit_bias is not None or bias_ld:
+            maps = [logit_bias] * b if logit_bias is None or isinstance(logit_bias, dict) else list(logit_bias)
             if len(maps) != b:
                 raise ops.ZLError(f"new_sampler: {b} tasks, {len(maps)} maps of logit_bias")
-            if any(maps):                                                   # nothing but empty maps: off
-                ids, vals, cnt, bits = ops.logit_bias_pack(maps, self.cfg.vocab_size, dev)
-                pen.update(bias_ids=ids, bias_vals=vals, bias_cnt=cnt, bias_bits=bits)
+            if any(maps) or bias_ld:                                        # nothing but empty maps and no forced width: off
+                ids, vals, cnt, bits = ops.logit_bias_rows(maps, self.cfg.vocab_size)
+                if bias_ld:
+                    if int(cnt.max()) > bias_ld:
+                        raise ops.ZLError(f"new_sampler: a logit_bias map has {int(cnt.max())} ids, bias_ld = {bias_ld}")
+                    wide_ids, wide_vals = np.full((b, bias_ld), -1, np.int32), np.zeros((b, bias_ld), np.float32)
+                    keep = min(bias_ld, ids.shape[1])                       # columns behind the longest list hold -1 / 0 already
+                    wide_ids[:, :keep], wide_vals[:, :keep] = ids[:, :keep], vals[:, :keep]
+                    ids, vals = wide_ids, wide_vals
+                pen.update(bias_ids=torch.from_numpy(ids).to(dev), bias_vals=torch.from_numpy(vals).to(dev),
+                           bias_cnt=torch.from_numpy(cnt).to(dev), bias_bits=torch.from_numpy(bits.view(np.int32)).to(dev))
         if int(top_logprobs):
             pen.update(top_n=int(top_logprobs), top_ids=torch.full((b, int(top_logprobs)), -1, dtype=torch.int32, device=dev),
                        top_logprobs=torch.full((b, int(top_logprobs)), float("nan"), dtype=torch.float32, device=dev))
@@ -2412,7 +2437,7 @@ class LLaMA:
                             seeds=torch.tensor(sd, dtype=torch.int64, device=dev), draws=torch.zeros(b, dtype=torch.int64, device=dev),
                             logprobs=torch.zeros(b, dtype=torch.float32, device=dev), u=torch.zeros(b, dtype=torch.float32, device=dev))
 
-    def new_stopper(self, ctx: DynBatchContext, stop_ids=None, stop_sequences=None, max_new_tokens=0) -> StopState:
+    def new_stopper(self, ctx: DynBatchContext, stop_ids=None, stop_sequences=None, max_new_tokens=0, widths=None) -> StopState:
         """The state for the stop= keyword of step_greedy / step_sample / verify / step_lookup and the generate loops.  stop_ids: ids that
         end a task (EOS ids, stop token ids), at most 16 -- one int or one list of ints for every task, or a sequence of B lists / Nones.
         stop_sequences: multi-token stops, at most 8 per task of 1 .. 16 ids each -- one list of id lists for every task, or a sequence
@@ -2420,7 +2445,9 @@ class LLaMA:
         flat list of ints as stop_ids is the one list for every task, and B lists are per task.)
         The state counts and tests the ids emitted AFTER its creation, as the generate_* results do.  The token pending in ctx.tokens
         seeds the memory of the last ids, so a stop sequence may begin with it; it is not itself tested or counted: a pending EOS does
-        not finish the task.  With nothing set for any task the state is still valid and no task ever finishes."""
+        not finish the task.  With nothing set for any task the state is still valid and no task ever finishes.
+        widths = (n_ids, n_seqs, ld): the widths of the three parameter tensors, at least the longest lists' -- (16, 8, 16) holds any
+        later request (LLaMA.admit rewrites a slot's rows in place).  None: the longest lists', as before."""
         b, dev = ctx.tokens.numel(), ctx.tokens.device
 
         def ints(v):
@@ -2450,7 +2477,20 @@ class LLaMA:
             raise ops.ZLError(f"new_stopper: {b} tasks, {len(lim)} values of max_new_tokens")
         if any(not ints(v) or not 0 <= int(v) < 1 << 31 for v in lim):
             raise ops.ZLError("new_stopper: max_new_tokens is an integer >= 0 (0 = no limit)")
-        sid, ssq, sln = ops.stop_pack(list(zip(ids, seqs)), self.cfg.vocab_size, dev)
+        sid, ssq, sln = ops.stop_rows(list(zip(ids, seqs)), self.cfg.vocab_size)
+        if widths is not None:
+            try:
+                n_ids, n_seqs, ld = (int(v) for v in widths)
+            except (TypeError, ValueError):
+                raise ops.ZLError("new_stopper: widths = (n_ids, n_seqs, ld)") from None
+            if not (sid.shape[1] <= n_ids <= ops.STOP_IDS_MAX and ssq.shape[1] <= n_seqs <= ops.STOP_SEQS_MAX
+                    and ssq.shape[2] <= ld <= ops.STOP_SEQ_LEN_MAX):
+                raise ops.ZLError(f"new_stopper: widths hold the longest lists and are at most ({ops.STOP_IDS_MAX}, {ops.STOP_SEQS_MAX}, "
+                                  f"{ops.STOP_SEQ_LEN_MAX})")
+            wid, wsq, wln = np.full((b, n_ids), -1, np.int32), np.full((b, n_seqs, ld), -1, np.int32), np.zeros((b, n_seqs), np.int32)
+            wid[:, :sid.shape[1]], wsq[:, :ssq.shape[1], :ssq.shape[2]], wln[:, :sln.shape[1]] = sid, ssq, sln
+            sid, ssq, sln = wid, wsq, wln
+        sid, ssq, sln = (torch.from_numpy(a).to(dev) for a in (sid, ssq, sln))
         i32 = dict(dtype=torch.int32, device=dev)
         tail = torch.full((b, ops.STOP_TAIL), -1, **i32)
         tail[:, ops.STOP_TAIL - 1].copy_(ctx.tokens)
@@ -2523,6 +2563,132 @@ class LLaMA:
         if state.top_n:
             return torch.stack(toks, dim=1), torch.stack(lps, dim=1), (torch.stack(tis, dim=1), torch.stack(tls, dim=1))
         return torch.stack(toks, dim=1), torch.stack(lps, dim=1)
+
+    # ---- slot admission: keep a running batch full ---------------------------------------------------------------------------------
+    @staticmethod
+    def slot_widths(sampler: Optional[SamplerState], stop: Optional[StopState], lookup: Optional[LookupState]):
+        """what the states carry, as ops.slots_pack takes it"""
+        return ops.slot_widths(penalties=sampler is not None and sampler.seen is not None,
+                               bias_ld=sampler.bias_ids.shape[1] if sampler is not None and sampler.bias_ids is not None else 0,
+                               n_ids=stop.stop_ids.shape[1] if stop is not None else 0, n_seqs=stop.stop_seqs.shape[1] if stop is not None else 0,
+                               seq_ld=stop.stop_seqs.shape[2] if stop is not None else 0,
+                               hist_cap=lookup.history.shape[1] if lookup is not None else 0)
+
+    def _slot_states(self, what, ctx, sampler, stop, lookup):
+        b = ctx.tokens.numel()
+        if self.tp:
+            raise ops.ZLError(f"{what}: tensor parallelism is not supported")
+        if lookup is not None and ctx.kv_quant:
+            raise ops.ZLError(f"{what}: lookup: not on the INT8 KV cache")
+        if not isinstance(sampler, SamplerState) or sampler.temperature.numel() != b:
+            raise ops.ZLError(f"{what}: the sampler state belongs to another batch size")
+        if stop is not None and stop.finished.numel() != b:
+            raise ops.ZLError(f"{what}: the stop state belongs to another batch size")
+        if lookup is not None and (lookup.history.shape[0] != b or lookup.drafts.shape != (b, lookup.k)):
+            raise ops.ZLError(f"{what}: the lookup state belongs to another batch size")
+        return b
+
+    def _slots_launch(self, ctx, blob, sampler, stop, lookup, parked_ok=None):
+        b = ctx.tokens.numel()
+        new = None
+        if lookup is not None:
+            key = ("draft_new", b)
+            if key not in self._bufs:
+                self._bufs[key] = torch.empty(b, dtype=torch.int32, device=self.device)
+            new = self._bufs[key]
+        ops.slots_admit(blob, ctx.tokens, ctx.positions, ctx.placement, ctx.valid_lens, sampler=sampler, stop=stop, lookup=lookup,
+                        draft_new=new, parked_ok=parked_ok)
+        if lookup is not None:
+            ops.lookup_draft(lookup.history, lookup.hist_lens, lookup.k, lookup.max_ngram, lookup.min_ngram, new_tokens=new.view(b, 1),
+                             drafts=lookup.drafts, match=lookup.match)
+
+    def _steps_left_after_admission(self, ctx, before):
+        """steps_left from the slots' host-known bounds, `before` = its value before the call's prompt encode: a guarded slot
+        (ctx.slot_guard) never leaves its buffer and bounds nothing; every other slot has what its last prompt encode left it minus
+        the steps counted since (ctx.slot_room), or `before` where the host has no record of the slot.  steps_left = the minimum --
+        it RISES when the slot that bounded it has been replaced by a guarded one -- and 1 << 60 with every slot guarded."""
+        left = {}
+        for t in range(ctx.tokens.numel()):
+            if t in ctx.slot_guard:
+                ctx.slot_room.pop(t, None)
+                continue
+            room, at = ctx.slot_room.get(t, (before, before))
+            left[t] = max(before, room - (at - before)) if at >= before else before        # a counter set by hand: no record to trust
+        ctx.steps_left = min(left.values()) if left else 1 << 60
+        ctx.slot_room.update({t: (v, ctx.steps_left) for t, v in left.items()})
+
+    def admit(self, ctx: DynBatchContext, slots, prompts, requests, sampler: SamplerState, stop: Optional[StopState] = None,
+              lookup: Optional[LookupState] = None, cache=None, kv_history=None):
+        """Put new requests into slots of a running batch, in place (the reference's scheduler moving a task into max_batch_active,
+        src/generator/batch_generator.cpp, where SearcherImplV1 builds the task's state on the host).  In order: prefill_batch(ctx,
+        slots, prompts) -- prefill_cached when a prefix cache is given --; ONE upload and ONE launch (ops.slots_pack / slots_admit)
+        that re-initialise the slots' rows of sampler, stop and lookup for requests[j] (a dict over ops.SLOT_REQUEST_KEYS, None = the
+        defaults; history defaults to the prompt); the drafter's launch when lookup is given.  Returns the prompts' last-row logits
+        (with a cache: (logits, matched)).  The first token is the greedy pick prefill leaves pending in ctx.tokens, as for new_sampler
+        behind a prefill: a request admitted into a slot is the same function of (prompt, parameters, seed) as one set up through
+        prefill_batch + new_sampler + new_stopper + new_lookup.  Every other slot's rows are untouched bit for bit and no tensor is
+        reallocated, so a graph captured over step_sample / step_lookup stays valid.
+        The states must carry what the requests use (new_sampler's penalties= / bias_ld=, new_stopper's widths=).  With a stop state
+        the slot's length limit is clamped (ops.slot_max_new) so that the device-side length stop keeps the task inside its buffer,
+        and ctx.steps_left is set from the slots' host-known bounds: such a slot no longer bounds it, the other slots count with
+        what their own prompt encode left them (ctx.slot_room).  The guard rests on the limit: it holds while every later step of the
+        context passes this stop state and, with a drafter, drafts of this K; a step without stop= or with more drafts is the
+        caller's to bound.
+        Refused before any launch, with nothing changed: what prefill_batch / prefill_cached refuse, tensor parallelism, lookup on an
+        INT8 cache, states of another batch size, what ops.slots_pack refuses, and (with a stop state) a prompt that leaves no room
+        for one generated token."""
+        b = self._slot_states("admit", ctx, sampler, stop, lookup)
+        slots, _, _ = self._check_prompt_batch("admit", ctx, slots, prompts, None, kv_history)
+        if len(requests) != len(slots):
+            raise ops.ZLError("admit: one request per slot")
+        k = lookup.k if lookup is not None else 0
+        entries, guards = [], {}
+        for s, pr, rq in zip(slots, prompts, requests):
+            rq = dict(rq or {})
+            n = int(pr.numel())
+            if stop is not None:
+                raw = rq.get("max_new_tokens", 0)
+                if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or not 0 <= int(raw) < 1 << 31:
+                    raise ops.ZLError(f"admit: slot {s}: max_new_tokens is an integer >= 0 (0 = no limit)")
+                lim = ops.slot_max_new(n, int(raw), ctx.max_len_buf, k)
+                if lim < 1:
+                    raise ops.ZLError(f"admit: prompt of slot {s} ({n} tokens) leaves no room for one generated token")
+                rq["max_new_tokens"] = lim
+                guards[s] = n + lim + k + 1
+            if lookup is not None and rq.get("history") is None:
+                rq["history"] = pr.reshape(-1)
+            entries.append((s, rq))
+        blob, _ = ops.slots_pack(entries, self.cfg.vocab_size, self.slot_widths(sampler, stop, lookup))
+        before = ctx.steps_left
+        if cache is None:
+            out = self.prefill_batch(ctx, slots, prompts, kv_history=kv_history)
+        else:
+            out = self.prefill_cached(ctx, cache, slots, prompts, kv_history=kv_history)
+        self._slots_launch(ctx, blob, sampler, stop, lookup)
+        if guards:
+            ctx.slot_guard.update(guards)
+            self._steps_left_after_admission(ctx, before)
+        return out
+
+    def park(self, ctx: DynBatchContext, slots, sampler: SamplerState, stop: StopState, lookup: Optional[LookupState] = None, finished=None):
+        """Park finished slots while nothing waits for them (one upload, one launch, the drafter's with lookup): a parked slot re-feeds
+        token 0 at position 0 and attends over one key instead of its whole history; stop.finished keeps its value, so the slot stays
+        frozen.  finished: the caller's host copy of stop.finished -- a slot that it does not show as finished is refused, as is
+        anything admit refuses of the states."""
+        b = self._slot_states("park", ctx, sampler, stop, lookup)
+        slots = [int(s) for s in slots]
+        if stop is None:
+            raise ops.ZLError("park: needs the stop state (only a finished slot is parked)")
+        if not slots or len(set(slots)) != len(slots) or any(s < 0 or s >= b for s in slots):
+            raise ops.ZLError("park: slots must be distinct indices of the batch")
+        done = [] if finished is None else [int(v) for v in (finished.tolist() if hasattr(finished, "tolist") else finished)]
+        if len(done) != b or any(done[s] == 0 for s in slots):
+            raise ops.ZLError("park: only a slot known to be finished is parked (finished = the host copy of stop.finished)")
+        blob, _ = ops.slots_pack([(s, None) for s in slots], self.cfg.vocab_size, self.slot_widths(sampler, stop, lookup))
+        self._slots_launch(ctx, blob, sampler, stop, lookup, parked_ok=set(slots))
+        before = ctx.steps_left
+        ctx.slot_guard.update({s: 0 for s in slots})
+        self._steps_left_after_admission(ctx, before)
 
     def advance(self, ctx: DynBatchContext, next_tokens: torch.Tensor):
         """Device-side bookkeeping between steps (what fill_search_tokens does on the host in the

@@ -1117,6 +1117,311 @@ def logit_bias_pack(maps, n, device):
             torch.from_numpy(bits.view(np.int32)).to(device))
 
 
+# ---- slot admission: new requests into slots of a running batch (zl_slots_admit) ---------------------------------------------------
+SLOT_MAGIC = 0x534C4F54    # "SLOT"
+SLOT_HDR = 16              # header words of the blob
+SLOT_REC = 16              # fixed words of a record; the slot's stop rows follow them
+SLOT_REQUEST_KEYS = ("temperature", "top_k", "top_p", "seed", "repetition_penalty", "presence_penalty", "penalty_tokens", "logit_bias",
+                     "stop_ids", "stop_sequences", "max_new_tokens", "history")
+
+
+def slot_widths(penalties=False, bias_ld=0, n_ids=0, n_seqs=0, seq_ld=0, hist_cap=0):
+    """What the states of a batch carry, as slots_pack needs it: penalties = the sampler has a bitmap; bias_ld = the width of its bias
+    rows, 0 = no bias; n_ids / n_seqs / seq_ld = the stop state's widths, all 0 = no stop state; hist_cap = ids a lookup history row
+    holds, 0 = no drafter."""
+    w = dict(penalties=bool(penalties), bias_ld=int(bias_ld), n_ids=int(n_ids), n_seqs=int(n_seqs), seq_ld=int(seq_ld), hist_cap=int(hist_cap))
+    stop = (w["n_ids"], w["n_seqs"], w["seq_ld"])
+    if not 0 <= w["bias_ld"] <= LOGIT_BIAS_MAX:
+        raise ZLError(f"slots_pack: bias_ld in 0 .. {LOGIT_BIAS_MAX}")
+    if stop != (0, 0, 0) and not (1 <= stop[0] <= STOP_IDS_MAX and 1 <= stop[1] <= STOP_SEQS_MAX and 1 <= stop[2] <= STOP_SEQ_LEN_MAX):
+        raise ZLError(f"slots_pack: stop widths within (1 .. {STOP_IDS_MAX}, 1 .. {STOP_SEQS_MAX}, 1 .. {STOP_SEQ_LEN_MAX}), or all 0")
+    if w["hist_cap"] != 0 and not 2 <= w["hist_cap"] < 1 << 31:
+        raise ZLError("slots_pack: hist_cap >= 2, or 0")
+    return w
+
+
+def _f32_bits(v):
+    return int(np.float32(v).view(np.int32))
+
+
+def slot_max_new(prompt_len, max_new, len_buf, k=0):
+    """The length limit LLaMA.admit gives a slot: the request's max_new (0 = none) cut so that prompt_len + max_new + k + 1 <= len_buf,
+    k = the drafter's K or 0.  A task writes the K/V row of its pending token at prompt_len, one row per emitted id behind it, re-feeds
+    its last id at prompt_len + max_new once it has finished, and a speculative step writes k draft rows behind that: the device-side
+    length stop (zl_stop_advance, reason 3) then keeps the task inside its buffer with no host count.  < 1: the prompt leaves no room
+    for one generated token."""
+    room = int(len_buf) - int(prompt_len) - int(k) - 1
+    return room if int(max_new) <= 0 else min(int(max_new), room)
+
+
+def slots_pack(entries, vocab, widths):
+    """The host half of an admission, numpy only: entries = (slot, request | None) pairs -- a request is a dict over SLOT_REQUEST_KEYS
+    (new_sampler's temperature / top_k / top_p / seed / repetition_penalty / presence_penalty / penalty_tokens / logit_bias, new_stopper's
+    stop_ids / stop_sequences / max_new_tokens, new_lookup's history; each optional, with those calls' defaults), None parks the slot --
+    over a vocabulary of `vocab` ids, for states of the widths `widths` (slot_widths) -> (blob, header): blob = ONE contiguous int32
+    array, include/zhilight_amd.h states its layout at zl_slots_admit; header = its first 16 words as a dict (magic, n, vocab, flags,
+    bias_ld, n_ids, n_seqs, seq_ld, rec, var, total, hist_cap).  The checks are new_sampler's, new_stopper's and new_lookup's, raised as
+    ZLError before anything is launched; a request that uses an option the states do not carry is refused: penalties without a bitmap,
+    a bias without bias rows or with more ids than bias_ld, stop conditions without a stop state or beyond its widths, a history
+    without a drafter or longer than hist_cap - 1.  Slots are distinct and >= 0 (slots_admit checks them against the batch)."""
+    vocab = int(vocab)
+    if vocab < 1 or vocab >= 1 << 31:
+        raise ZLError("slots_pack: 1 <= vocab < 2^31")
+    w = slot_widths(**widths)
+    entries = list(entries)
+    if not entries:
+        raise ZLError("slots_pack: at least one (slot, request) entry")
+    has_stop = w["n_ids"] > 0
+    rec = SLOT_REC + w["n_ids"] + w["n_seqs"] + w["n_seqs"] * w["seq_ld"]
+    recs, var, slots = [], [], []
+    off = SLOT_HDR + len(entries) * rec
+
+    def ints(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+    def id_array(v, what, s):
+        a = np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= vocab):
+            raise ZLError(f"slots_pack: slot {s}: {what} outside [0, {vocab})")
+        return a.astype(np.int32)
+
+    for ent in entries:
+        try:
+            s, req = ent
+        except (TypeError, ValueError):
+            raise ZLError("slots_pack: an entry is (slot, request | None)") from None
+        if not ints(s) or int(s) < 0 or int(s) >= 1 << 31:
+            raise ZLError("slots_pack: a slot is an integer >= 0")
+        s = int(s)
+        if s in slots:
+            raise ZLError(f"slots_pack: slot {s} is given twice")
+        slots.append(s)
+        r = np.zeros(rec, np.int32)
+        r[0] = s
+        if has_stop:
+            r[SLOT_REC:SLOT_REC + w["n_ids"]] = -1
+            r[SLOT_REC + w["n_ids"] + w["n_seqs"]:] = -1
+        if req is None:
+            recs.append(r)
+            continue
+        if not isinstance(req, dict) or any(k not in SLOT_REQUEST_KEYS for k in req):
+            raise ZLError(f"slots_pack: slot {s}: a request is a dict over {', '.join(SLOT_REQUEST_KEYS)}")
+        t, k, p, sd = req.get("temperature", 1.0), req.get("top_k", 0), req.get("top_p", 1.0), req.get("seed", 0)
+        rp, pp = req.get("repetition_penalty", 1.0), req.get("presence_penalty", 0.0)
+        try:
+            if not (float(t) >= 0.0 and math.isfinite(float(t))):
+                raise ZLError(f"slots_pack: slot {s}: temperature >= 0 (0 = greedy)")
+            if int(k) != k or int(k) < 0 or int(k) >= 1 << 31:
+                raise ZLError(f"slots_pack: slot {s}: top_k is an integer >= 0 (0 = off)")
+            if not 0.0 <= float(p) <= 1.0:
+                raise ZLError(f"slots_pack: slot {s}: top_p in [0, 1]")
+            if int(sd) != sd:
+                raise ZLError(f"slots_pack: slot {s}: seed is an integer")
+            if not (float(rp) > 0.0 and math.isfinite(float(rp))):
+                raise ZLError(f"slots_pack: slot {s}: repetition_penalty > 0 and finite (1 = off)")
+            if not math.isfinite(float(pp)):
+                raise ZLError(f"slots_pack: slot {s}: presence_penalty is finite (0 = off)")
+        except (TypeError, ValueError):
+            raise ZLError(f"slots_pack: slot {s}: temperature, top_k, top_p, seed and the penalties are numbers") from None
+        sd = int(sd) % (1 << 64)                                            # the 64 bits of the key
+        r[1] = 1
+        r[2], r[3], r[4] = _f32_bits(t), int(k), _f32_bits(p)
+        r[5:7] = np.array([sd & 0xFFFFFFFF, sd >> 32], np.uint32).view(np.int32)
+        r[7], r[8] = _f32_bits(rp), _f32_bits(pp)
+        pen = req.get("penalty_tokens")
+        if not w["penalties"] and (pen is not None or float(rp) != 1.0 or float(pp) != 0.0):
+            raise ZLError(f"slots_pack: slot {s}: penalties, but the sampler state has no bitmap")
+        pen = np.zeros(0, np.int32) if pen is None else id_array(pen, "penalty_tokens", s)
+        r[10], r[11] = off, pen.size
+        var.append(pen)
+        off += pen.size
+        bias = req.get("logit_bias")
+        if bias is not None and not isinstance(bias, dict):
+            raise ZLError(f"slots_pack: slot {s}: logit_bias is one dict {{token id: bias}}")
+        if bias:
+            if not w["bias_ld"]:
+                raise ZLError(f"slots_pack: slot {s}: a logit bias, but the sampler state has no bias rows")
+            try:
+                ids, vals, cnt, _ = logit_bias_rows([bias], vocab)
+            except ZLError as e:
+                raise ZLError(f"slots_pack: slot {s}: {e}") from None
+            if int(cnt[0]) > w["bias_ld"]:
+                raise ZLError(f"slots_pack: slot {s}: {int(cnt[0])} bias ids, the sampler state holds {w['bias_ld']}")
+            r[12], r[13] = off, int(cnt[0])
+            var += [ids[0, :cnt[0]], vals[0, :cnt[0]].view(np.int32)]
+            off += 2 * int(cnt[0])
+        else:
+            r[12], r[13] = off, 0
+        sid, ssq, lim = req.get("stop_ids"), req.get("stop_sequences"), req.get("max_new_tokens", 0)
+        if not ints(lim) or not 0 <= int(lim) < 1 << 31:
+            raise ZLError(f"slots_pack: slot {s}: max_new_tokens is an integer >= 0 (0 = no limit)")
+        sid = [sid] if ints(sid) else sid
+        if not has_stop and (sid or ssq or int(lim)):
+            raise ZLError(f"slots_pack: slot {s}: stop conditions, but there is no stop state")
+        if has_stop:
+            try:
+                ids, seqs, lens = stop_rows([(sid, ssq)], vocab)
+            except ZLError as e:
+                raise ZLError(f"slots_pack: slot {s}: {e}") from None
+            if len(sid or []) > w["n_ids"] or len(ssq or []) > w["n_seqs"] or (len(ssq or []) and seqs.shape[2] > w["seq_ld"]):
+                raise ZLError(f"slots_pack: slot {s}: stop conditions beyond the stop state's widths "
+                              f"({w['n_ids']} ids, {w['n_seqs']} sequences of {w['seq_ld']} ids)")
+            q = SLOT_REC
+            r[q:q + len(sid or [])] = ids[0, :len(sid or [])]
+            q += w["n_ids"]
+            r[q:q + len(ssq or [])] = lens[0, :len(ssq or [])]
+            q += w["n_seqs"]
+            sq = r[q:].reshape(w["n_seqs"], w["seq_ld"])
+            for j in range(len(ssq or [])):
+                sq[j, :lens[0, j]] = seqs[0, j, :lens[0, j]]
+            r[9] = int(lim)
+        hist = req.get("history")
+        if hist is not None and not w["hist_cap"]:
+            raise ZLError(f"slots_pack: slot {s}: a history, but there is no lookup state")
+        hist = np.zeros(0, np.int32) if hist is None else id_array(hist, "history ids", s)
+        if w["hist_cap"] and hist.size > w["hist_cap"] - 1:
+            raise ZLError(f"slots_pack: slot {s}: {hist.size} ids and the pending token do not fit cap = {w['hist_cap']}")
+        r[14], r[15] = off, hist.size
+        var.append(hist)
+        off += hist.size
+        recs.append(r)
+    if off >= 1 << 31:
+        raise ZLError("slots_pack: the blob holds fewer than 2^31 words")
+    flags = (1 if w["penalties"] else 0) | (2 if w["bias_ld"] else 0) | (4 if has_stop else 0) | (8 if w["hist_cap"] else 0)
+    hdr = np.zeros(SLOT_HDR, np.int32)
+    hdr[:12] = [SLOT_MAGIC, len(entries), vocab, flags, w["bias_ld"], w["n_ids"], w["n_seqs"], w["seq_ld"], rec,
+                SLOT_HDR + len(entries) * rec, off, w["hist_cap"]]
+    blob = np.ascontiguousarray(np.concatenate([hdr] + recs + [np.asarray(v, np.int32) for v in var]))
+    assert blob.size == off
+    return blob, slots_header(blob)
+
+
+def slots_header(blob):
+    """the header of a slots_pack blob as a dict; refuses (ZLError) what is not such a blob"""
+    names = ("magic", "n", "vocab", "flags", "bias_ld", "n_ids", "n_seqs", "seq_ld", "rec", "var", "total", "hist_cap")
+    if not (isinstance(blob, np.ndarray) and blob.dtype == np.int32 and blob.ndim == 1 and blob.size >= SLOT_HDR and blob.flags.c_contiguous):
+        raise ZLError("slots_admit: the blob is slots_pack's contiguous int32 array")
+    h = dict(zip(names, (int(v) for v in blob[:12])))
+    if (h["magic"] != SLOT_MAGIC or h["total"] != blob.size or h["n"] < 1 or h["rec"] < SLOT_REC
+            or h["var"] != SLOT_HDR + h["n"] * h["rec"] or h["var"] > h["total"]
+            or h["rec"] != SLOT_REC + h["n_ids"] + h["n_seqs"] + h["n_seqs"] * h["seq_ld"]):
+        raise ZLError("slots_admit: the blob is slots_pack's contiguous int32 array")
+    return h
+
+
+def slots_records(blob):
+    """the records of a slots_pack blob: (n, rec) int32, a view"""
+    h = slots_header(blob)
+    return blob[SLOT_HDR:h["var"]].reshape(h["n"], h["rec"])
+
+
+def slots_admit(blob, tokens, positions, placement, valid_lens, sampler=None, stop=None, lookup=None, draft_new=None, parked_ok=None):
+    """Admit requests into slots of a running batch (zl_slots_admit: one upload of the blob, ONE launch): blob = slots_pack's array
+    (a numpy array: uploaded here; or a (device int32 tensor, numpy array) pair from an earlier upload, for a captured launch);
+    tokens / positions / placement / valid_lens (B) int32 = the batch state, tokens[s] holding the pending token the prompt encode
+    left.  sampler / stop / lookup: objects with LLaMA's SamplerState / StopState / LookupState fields (None = that group is skipped);
+    their optional tensors and widths must be those the blob was packed for (ZLError otherwise, and for slots outside [0, B)).
+    draft_new (B) int32, optional: receives the drafter's new_tokens column (pending for admitted slots, -1 elsewhere).
+    parked_ok: the slots the caller knows to be finished; parking any other slot is refused.  The rule: include/zhilight_amd.h."""
+    dev_blob = None
+    if isinstance(blob, (tuple, list)):
+        dev_blob, blob = blob
+    h = slots_header(blob)
+    recs = slots_records(blob)
+    if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dtype == torch.int32 and tokens.dim() == 1 and tokens.is_contiguous()):
+        raise ZLError("slots_admit: tokens is (B) contiguous int32 on the device")
+    b, dev = tokens.numel(), tokens.device
+
+    def chk(t, shape, dtype, what):
+        if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == dev):
+            raise ZLError(f"slots_admit: {what}: contiguous {str(dtype).replace('torch.', '')} {tuple(shape)} on the tokens' device")
+
+    for t, what in ((positions, "positions"), (placement, "placement"), (valid_lens, "valid_lens")):
+        chk(t, (b,), torch.int32, what)
+    if recs[:, 0].min() < 0 or recs[:, 0].max() >= b or len(set(recs[:, 0].tolist())) != h["n"]:
+        raise ZLError(f"slots_admit: slots must be distinct indices of the batch of {b}")
+    parks = recs[recs[:, 1] == 0, 0].tolist()
+    if parks and (parked_ok is None or any(s not in parked_ok for s in parks)):
+        raise ZLError("slots_admit: only a slot known to be finished is parked")
+    words = seen_words(h["vocab"])
+    i32, f32, i64 = torch.int32, torch.float32, torch.int64
+    args = []
+    sm = sampler
+    if sm is not None:
+        for name, dt in (("temperature", f32), ("top_k", i32), ("top_p", f32), ("seeds", i64), ("draws", i64), ("logprobs", f32), ("u", f32)):
+            chk(getattr(sm, name), (b,), dt, name)
+        args += [sm.temperature, sm.top_k, sm.top_p, sm.seeds, sm.draws, sm.logprobs, sm.u]
+    else:
+        args += [None] * 7
+    has_pen = sm is not None and sm.seen is not None
+    if has_pen != bool(h["flags"] & 1):
+        raise ZLError("slots_admit: the blob and the sampler state differ in the penalty bitmap")
+    if has_pen:
+        chk(sm.repetition_penalty, (b,), f32, "repetition_penalty")
+        chk(sm.presence_penalty, (b,), f32, "presence_penalty")
+        if not (sm.seen.dim() == 2 and sm.seen.shape[1] >= words):
+            raise ZLError("slots_admit: seen: contiguous int32 (B, >= ceil(vocab / 32))")
+        chk(sm.seen, (b, sm.seen.shape[1]), i32, "seen")
+        args += [sm.repetition_penalty, sm.presence_penalty, sm.seen, sm.seen.shape[1]]
+    else:
+        args += [None, None, None, 0]
+    has_bias = sm is not None and sm.bias_ids is not None
+    if (sm.bias_ids.shape[1] if has_bias and sm.bias_ids.dim() == 2 else 0) != h["bias_ld"]:
+        raise ZLError("slots_admit: the blob and the sampler state differ in the bias width")
+    if has_bias:
+        chk(sm.bias_ids, (b, h["bias_ld"]), i32, "bias_ids")
+        chk(sm.bias_vals, (b, h["bias_ld"]), f32, "bias_vals")
+        chk(sm.bias_cnt, (b,), i32, "bias_cnt")
+        if not (torch.is_tensor(sm.bias_bits) and sm.bias_bits.dim() == 2 and sm.bias_bits.shape[1] >= words):
+            raise ZLError("slots_admit: bias_bits: contiguous int32 (B, >= ceil(vocab / 32))")
+        chk(sm.bias_bits, (b, sm.bias_bits.shape[1]), i32, "bias_bits")
+        args += [sm.bias_ids, sm.bias_vals, sm.bias_cnt, sm.bias_bits, h["bias_ld"], sm.bias_bits.shape[1]]
+    else:
+        args += [None, None, None, None, 0, 0]
+    top_n = int(sm.top_n) if sm is not None and sm.top_n else 0
+    if top_n:
+        chk(sm.top_ids, (b, top_n), i32, "top_ids")
+        chk(sm.top_logprobs, (b, top_n), f32, "top_logprobs")
+        args += [sm.top_ids, sm.top_logprobs, top_n]
+    else:
+        args += [None, None, 0]
+    if (stop is not None) != bool(h["flags"] & 4):
+        raise ZLError("slots_admit: the blob and the stop state differ")
+    if stop is not None:
+        if (tuple(stop.stop_ids.shape[1:]), tuple(stop.stop_seqs.shape[1:])) != ((h["n_ids"],), (h["n_seqs"], h["seq_ld"])):
+            raise ZLError("slots_admit: the blob and the stop state differ in their widths")
+        chk(stop.stop_ids, (b, h["n_ids"]), i32, "stop_ids")
+        chk(stop.stop_seqs, (b, h["n_seqs"], h["seq_ld"]), i32, "stop_seqs")
+        chk(stop.seq_lens, (b, h["n_seqs"]), i32, "seq_lens")
+        chk(stop.tail, (b, STOP_TAIL), i32, "tail")
+        chk(stop.live, (1,), i32, "live")
+        for name in ("max_new", "gen_lens", "last_token", "finished", "emit_lens"):
+            chk(getattr(stop, name), (b,), i32, name)
+        args += [stop.stop_ids, stop.stop_seqs, stop.seq_lens, h["n_ids"], h["n_seqs"], h["seq_ld"], stop.max_new, stop.gen_lens, stop.tail,
+                 stop.last_token, stop.finished, stop.emit_lens, stop.live]
+    else:
+        args += [None, None, None, 0, 0, 0] + [None] * 7
+    if (lookup.history.shape[1] if lookup is not None else 0) != h["hist_cap"]:
+        raise ZLError("slots_admit: the blob and the lookup state differ in the history's cap")
+    if lookup is not None:
+        chk(lookup.history, (b, h["hist_cap"]), i32, "history")
+        chk(lookup.hist_lens, (b,), i32, "hist_lens")
+        args += [lookup.history, h["hist_cap"], lookup.hist_lens]
+    else:
+        args += [None, 0, None]
+    if draft_new is not None:
+        chk(draft_new, (b,), i32, "draft_new")
+    if dev_blob is None:
+        dev_blob = torch.from_numpy(blob).to(dev)
+    elif not (torch.is_tensor(dev_blob) and dev_blob.dtype == i32 and dev_blob.numel() == blob.size and dev_blob.is_contiguous()
+              and dev_blob.device == dev):
+        raise ZLError("slots_admit: the uploaded blob is the int32 tensor of the numpy blob, on the tokens' device")
+    cargs = [_i(v) if isinstance(v, int) else _p(v) for v in args]
+    check(lib().zl_slots_admit(_p(dev_blob), _i(h["n"]), _i(h["rec"]), _i(b), _i(h["vocab"]), _p(tokens), _p(positions), _p(placement),
+                               _p(valid_lens), *cargs, _p(draft_new), _stream()), "slots_admit")
+    return dev_blob
+
+
 def _opts_args(what, count, top_shape, n, device, bias, top_n, top_ids, top_logprobs):
     """The checks of (bias, top_n, top_ids, top_logprobs) of sample_advance / spec_sample_accept -> the nine C arguments; count = the
     rows / tasks the bias is per, top_shape = the leading shape of the top-N outputs."""

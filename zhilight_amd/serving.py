@@ -1,0 +1,201 @@
+"""A small serving loop that keeps a decode batch full: requests wait in a queue, LLaMA.admit puts them into the slots that finished
+tasks leave, and the steps between two looks at the device are the captured-or-eager steps of LLaMA.step_sample / step_lookup.
+
+The reference's scheduler (src/generator/batch_generator.cpp: BatchGenerator::run moves tasks from its queue into max_batch_active as
+slots free up, SearcherImplV1 keeps the per-task state on the host) does this per step on the host; here the per-task state lives on
+the device, a request's whole life runs inside the step, and the host looks once every `poll` steps."""
+import collections
+
+import torch
+
+from . import ops
+
+REASONS = {1: "stop id", 2: "stop sequence", 3: "length"}
+
+
+class BatchServer:
+    """BatchServer(model, batch, len_buf, ...) owns ONE context of `batch` slots with len_buf KV rows each and the full-width states:
+    a sampler with the penalty bitmap (penalties=True), bias rows of bias_ld ids (0 = no logit bias) and top_logprobs alternatives, a
+    stop state of the widths (16, 8, 16), and with lookup_k = K > 0 the prompt-lookup drafter (steps are step_lookup(sampler=)).
+    prefix_blocks = N > 0: the server builds a prompt prefix cache of N blocks for its context (LLaMA.new_prefix_cache(ctx, N,
+    prefix_block_size)) and the prompts go through it; prefix_cache: a PrefixCache made elsewhere instead -- one cache may serve several
+    servers -- which must fit this server's context (PrefixCache.fits: geometry, KV element type, device, stream); build it
+    with LLaMA.new_prefix_cache from any context of the same model and KV cache type.  capture=True: the steps are replays of one graph
+    captured after the first eager step.  poll: steps between two read-backs.
+
+    submit(prompt, **request) -> id; request = ops.SLOT_REQUEST_KEYS (temperature, top_k, top_p, seed, repetition_penalty,
+    presence_penalty, penalty_tokens, logit_bias, stop_ids, stop_sequences, max_new_tokens, history).  A request is checked when it is
+    submitted, against the states' widths and the buffer's length.
+
+    run() serves the queue until it and the batch are empty and returns {id: dict(tokens, logprobs, reason, round, first_token,
+    clamped, [top_ids, top_logprobs])}: tokens = the ids emitted behind first_token (the greedy pick the prompt encode leaves
+    pending, LLaMA.admit's convention), logprobs = their tempered log-probabilities, reason = 1 (stop id) / 2 (stop sequence) / 3 (length),
+    round = the admission round, clamped = the length limit the slot ran under.  self.log = the admission groups (round, [(slot, id),
+    ...]); self.matched = {id: tokens the prefix cache supplied}; self.stats counts steps and slot-steps."""
+
+    def __init__(self, model, batch, len_buf, penalties=True, bias_ld=0, top_logprobs=0, lookup_k=0, prefix_cache=None, capture=False,
+                 poll=8, kv_history=None, prefix_blocks=0, prefix_block_size=128):
+        if int(poll) < 1 or int(batch) < 1:
+            raise ops.ZLError("BatchServer: batch >= 1 and poll >= 1")
+        self.model, self.b, self.len_buf, self.poll, self.capture = model, int(batch), int(len_buf), int(poll), bool(capture)
+        self.cache, self.kv_history = prefix_cache, kv_history
+        self.ctx = ctx = model.new_context(self.b, self.len_buf, 0)
+        if int(prefix_blocks):
+            if prefix_cache is not None:
+                raise ops.ZLError("BatchServer: prefix_blocks builds the cache, prefix_cache brings one: give one of them")
+            self.cache = model.new_prefix_cache(ctx, int(prefix_blocks), int(prefix_block_size))
+        self.sampler = model.new_sampler(ctx, penalties=bool(penalties), bias_ld=int(bias_ld), top_logprobs=int(top_logprobs))
+        self.stop = model.new_stopper(ctx, widths=(ops.STOP_IDS_MAX, ops.STOP_SEQS_MAX, ops.STOP_SEQ_LEN_MAX))
+        self.lookup = model.new_lookup(ctx, [[] for _ in range(self.b)], int(lookup_k)) if int(lookup_k) else None
+        self.k = int(lookup_k)
+        self.width = self.k + 1                                            # ids a step emits per slot at most
+        self.stop.finished.fill_(3)                                        # nothing runs yet: every slot is a finished one
+        self.stop.live.zero_()
+        self.finished = [3] * self.b                                       # the host's copy of stop.finished
+        self.queue = collections.deque()
+        self.requests, self.results, self.log, self.matched = {}, {}, [], {}
+        self.active, self.parked = {}, set()                               # slot -> id; slots parked since they finished
+        self.round = 0
+        self.graph = self._graph_out = None
+        self.stats = dict(steps=0, live_slot_steps=0, finished_slot_steps=0, parked_slot_steps=0, admissions=0, parks=0)
+        n, w, top = self.poll * self.b * self.width, self.width, int(top_logprobs)
+        # one read-back: the rounds' token rows, their log-probabilities (as bits), finished and the first tokens, in ONE int32 buffer
+        self._rb = torch.empty(2 * n + 2 * self.b + 2 * n * top, dtype=torch.int32, device=model.device)
+        self._tok = self._rb[:n].view(self.poll, self.b, w)
+        self._lp = self._rb[n:2 * n].view(torch.float32).view(self.poll, self.b, w)
+        self._fin = self._rb[2 * n:2 * n + self.b]
+        self._first = self._rb[2 * n + self.b:2 * n + 2 * self.b]
+        self._first.zero_()
+        self._tid = self._rb[2 * n + 2 * self.b:2 * n + 2 * self.b + n * top].view(self.poll, self.b, w, top) if top else None
+        self._tlp = self._rb[2 * n + 2 * self.b + n * top:].view(torch.float32).view(self.poll, self.b, w, top) if top else None
+        self.top = top
+
+    # ---- the queue --------------------------------------------------------------------------------------------------------------
+    def submit(self, prompt, **request):
+        prompt = torch.as_tensor(prompt).reshape(-1).to(torch.int32).cpu()
+        n = int(prompt.numel())
+        if n < 1 or n + 1 > self.len_buf:
+            raise ops.ZLError(f"submit: a prompt of {n} tokens does not fit the KV buffer of {self.len_buf}")
+        probe = dict(request)
+        if self.lookup is not None and probe.get("history") is None:
+            probe["history"] = prompt
+        ops.slots_pack([(0, probe)], self.model.cfg.vocab_size, self.model.slot_widths(self.sampler, self.stop, self.lookup))
+        if ops.slot_max_new(n, request.get("max_new_tokens", 0), self.len_buf, self.k) < 1:
+            raise ops.ZLError(f"submit: a prompt of {n} tokens leaves no room for one generated token")
+        rid = len(self.requests)
+        self.requests[rid] = (prompt, dict(request))
+        self.queue.append(rid)
+        return rid
+
+    # ---- one step ---------------------------------------------------------------------------------------------------------------
+    def _step(self):
+        if self.lookup is not None:
+            res = self.model.step_lookup(self.ctx, self.lookup, sampler=self.sampler, stop=self.stop)
+            out = [res.tokens, self.sampler.row_logprobs]
+            return out + ([self.sampler.row_top_ids, self.sampler.row_top_logprobs] if self.top else [])
+        _, nxt = self.model.step_sample(self.ctx, self.sampler, stop=self.stop)
+        out = [nxt, self.sampler.logprobs]
+        return out + ([self.sampler.top_ids, self.sampler.top_logprobs] if self.top else [])
+
+    def _run_step(self, i):
+        if self.graph is not None:
+            self.graph.replay()
+            out = self._graph_out
+        else:
+            out = self._step()
+            if self.capture:                                                # the first eager step has allocated what a step allocates
+                torch.cuda.synchronize()
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self._graph_out = self._step()
+                # the capture enqueued nothing: `out` is still the eager step's, in the buffers the replays will write
+        self._tok[i].copy_(out[0].view(self.b, self.width))
+        self._lp[i].copy_(out[1].view(self.b, self.width))
+        if self.top:
+            self._tid[i].copy_(out[2].view(self.b, self.width, self.top))
+            self._tlp[i].copy_(out[3].view(self.b, self.width, self.top))
+
+    # ---- the loop ---------------------------------------------------------------------------------------------------------------
+    def _admit(self):
+        free = [s for s in range(self.b) if s not in self.active]
+        group = []
+        while self.queue and free:
+            group.append((free.pop(0), self.queue.popleft()))
+        if not group:
+            return
+        self.round += 1
+        slots = [s for s, _ in group]
+        prompts = [self.requests[r][0] for _, r in group]
+        reqs = [self.requests[r][1] for _, r in group]
+        out = self.model.admit(self.ctx, slots, prompts, reqs, self.sampler, self.stop, self.lookup, cache=self.cache,
+                               kv_history=self.kv_history)
+        if self.cache is not None:
+            for (_, r), m in zip(group, out[1]):
+                self.matched[r] = int(m)
+        self._first.copy_(self.ctx.tokens)
+        self.log.append((self.round, list(group)))
+        self.stats["admissions"] += 1
+        for s, r in group:
+            self.active[s] = r
+            self.parked.discard(s)
+            self.finished[s] = 0
+            n = int(self.requests[r][0].numel())
+            self.results[r] = dict(tokens=[], logprobs=[], reason=0, round=self.round, first_token=None,
+                                   clamped=ops.slot_max_new(n, self.requests[r][1].get("max_new_tokens", 0) or 0, self.len_buf, self.k))
+            if self.top:
+                self.results[r].update(top_ids=[], top_logprobs=[])
+
+    def _park(self):
+        idle = [s for s in range(self.b) if s not in self.active and s not in self.parked]
+        if idle and self.active:                                            # nothing active: the loop is about to end
+            self.model.park(self.ctx, idle, self.sampler, self.stop, self.lookup, finished=self.finished)
+            self.parked.update(idle)
+            self.stats["parks"] += 1
+
+    def run(self):
+        while self.queue or self.active:
+            self._admit()
+            self._park()
+            for i in range(self.poll):
+                self._run_step(i)
+            self._fin.copy_(self.stop.finished)
+            rb = self._rb.cpu()                                             # the one read-back of the round
+            n, bw = self.poll * self.b * self.width, self.b
+            tok = rb[:n].view(self.poll, self.b, self.width).tolist()
+            lp = rb[n:2 * n].view(torch.float32).view(self.poll, self.b, self.width).tolist()
+            fin = rb[2 * n:2 * n + bw].tolist()
+            first = rb[2 * n + bw:2 * n + 2 * bw].tolist()
+            if self.top:
+                t0 = 2 * n + 2 * bw
+                tid = rb[t0:t0 + n * self.top].view(self.poll, self.b, self.width, self.top).tolist()
+                tlp = rb[t0 + n * self.top:].view(torch.float32).view(self.poll, self.b, self.width, self.top).tolist()
+            self.stats["steps"] += self.poll
+            for i in range(self.poll):
+                for s in range(self.b):
+                    row = tok[i][s]
+                    m = next((j for j, v in enumerate(row) if v < 0), len(row))
+                    if s in self.parked:
+                        self.stats["parked_slot_steps"] += 1
+                    elif m == 0:
+                        self.stats["finished_slot_steps"] += 1
+                    else:
+                        self.stats["live_slot_steps"] += 1
+                    if m == 0:
+                        continue
+                    if s not in self.active:
+                        raise ops.ZLError(f"BatchServer: slot {s} emitted ids without a request")
+                    res = self.results[self.active[s]]
+                    res["tokens"] += row[:m]
+                    res["logprobs"] += lp[i][s][:m]
+                    if self.top:
+                        res["top_ids"] += tid[i][s][:m]
+                        res["top_logprobs"] += tlp[i][s][:m]
+            for s in list(self.active):
+                res = self.results[self.active[s]]
+                if res["first_token"] is None:
+                    res["first_token"] = first[s]
+                self.finished[s] = fin[s]
+                if fin[s]:
+                    res["reason"] = fin[s]
+                    del self.active[s]
+        return self.results
