@@ -1181,6 +1181,68 @@ int zl_spec_sample_accept_opts(const void* logits, int type, int64_t b, int64_t 
                                const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
                                const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits,
                                int64_t bias_bits_ld, int top_n, int32_t* top_ids, float* top_logprobs, zl_stream_t s);
+/* A token automaton inside the sampling step (csrc/sample_rows.hip): constrained output -- a choice list, a number, a JSON shape --
+ * without a host round trip.  The reference's answer is logits_processors, Python callbacks between steps; a captured step cannot
+ * call back per token, so the constraint is a DFA over token ids resident on the device, shared by every row.  The _opts calls'
+ * arguments, then the tables, the state and (speculative) row_states.
+ * TABLES, read only, over S states and the n classes:
+ *   fsm_mask (S, mask_ld) uint32, mask_ld >= ceil(n / 32), seen's bit layout: bit i of state s set <=> token i is allowed in s; bits
+ *     at or above n are never read as classes.
+ *   fsm_default (S) int32: the next state of an allowed token that has no exception entry.
+ *   fsm_exc_off (S + 1), fsm_exc_tok (E), fsm_exc_next (E) int32: per-state exception lists in CSR form, token ids ascending and
+ *     distinct inside a state (a string-body state is "default: stay" plus a few hundred exceptions, not n edges).
+ * STATE: fsm_state int32, read and written in place, per row (zl_sample_advance_fsm) or per task (zl_spec_sample_accept_fsm).  A state
+ * outside [0, S) means UNCONSTRAINED: the row is read as stored and the state is not changed -- which is also "grammar finished, free
+ * text from here": a transition target outside [0, S) is stored as it is.
+ *   delta(s, tok), s in [0, S):  tok outside [0, n) or its bit in s clear -> s;  else the exception's target if the list of s holds
+ *   tok, else fsm_default[s].
+ * MASKING: a constrained row sees class i as -inf of the logits' type (0xfc00 / 0xff80) where bit i of its state's mask is clear,
+ * whatever the stored pattern is (a NaN included), applied to the STORED pattern in front of the penalty and the bias.  Everything
+ * behind that -- arg-max and the plain-row test, max and Z, top-k and top-p, the pick and its log-probability, penalties and bias,
+ * the top-N list -- is zl_sample_advance_opts' rule on that row: every output equals masked_fill(-inf) on a copy of the logits, then
+ * the _opts call on the copy, bit for bit.  The logits in memory are NOT modified.  After the pick, fsm_state[r] = delta(fsm_state[r],
+ * pick); a plain row (every allowed class -inf) picks zl_argmax_advance's token, which may be disallowed: delta leaves the state.
+ * SPECULATIVE: row (t, i) uses s_i, s_0 = fsm_state[t], s_{j+1} = delta(s_j, drafts[t, j]); the first launch writes row_states[t, i] =
+ * delta(s_i, pick_i) (row_states (b, len_q) int32, the caller's: no workspace), the second sets fsm_state[t] = row_states[t,
+ * accepted[t]].  Accepted drafts equal the picks, so the task's state is delta* over exactly the emitted tokens and the emitted
+ * sequence stays the same function of (logits, seed, tokens emitted so far) as zl_sample_advance_fsm's, step by step.
+ * zl_stop_advance restores neither the state nor draws nor seen (a cut task has finished; admission rewrites the state).  An accepting
+ * state allows the EOS id, one of the task's stop ids: no new stop reason.
+ * ZL_EINVAL: some but not all of the five tables and fsm_state; the speculative call with tables but without row_states.  ZL_ESHAPE:
+ * S < 1, mask_ld < ceil(n / 32), S or E >= 2^31 (E < 0).  All six NULL: the calls ARE the _opts ones.  Otherwise their codes.
+ * Launches as the _opts calls; one wave per row advances the state (a 64-way search of the exception list); ordinary vector stores
+ * only, no global atomics; no allocation, no sync, no workspace; deterministic. */
+int zl_sample_advance_fsm(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
+                          const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
+                          int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
+                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
+                          const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits, int64_t bias_bits_ld,
+                          int top_n, int32_t* top_ids, float* top_logprobs, const uint32_t* fsm_mask, int64_t mask_ld,
+                          const int32_t* fsm_default, const int32_t* fsm_exc_off, const int32_t* fsm_exc_tok, const int32_t* fsm_exc_next,
+                          int64_t S, int64_t E, int32_t* fsm_state, zl_stream_t s);
+int zl_spec_sample_accept_fsm(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
+                              const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
+                              const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
+                              int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
+                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
+                              const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits,
+                              int64_t bias_bits_ld, int top_n, int32_t* top_ids, float* top_logprobs, const uint32_t* fsm_mask,
+                              int64_t mask_ld, const int32_t* fsm_default, const int32_t* fsm_exc_off, const int32_t* fsm_exc_tok,
+                              const int32_t* fsm_exc_next, int64_t S, int64_t E, int32_t* fsm_state, int32_t* row_states, zl_stream_t s);
+/* zl_slots_admit with the sampler's automaton state: fsm_state (b) int32 (NULL: the call IS zl_slots_admit).  Blob: header flag 16
+ * (flags & 16) says that header word 12 holds the word offset of an (n, 2) int32 array in the variable part -- per record the start
+ * state (-1 = unconstrained) and a pending-token override (-1 = none).  A blob without grammar requests is bit-identical to
+ * zl_slots_admit's.  ADMIT: fsm_state[s] <- the start state (-1 without the array); with an override in [0, vocab), tokens[s] <- it, and
+ * every place of the rule above that says "pending" uses it: the bitmap's seed, tail[s, 14], last_token, draft_new.  PARK:
+ * fsm_state[s] = -1.  ZL_EINVAL: fsm_state without the sampler group; otherwise zl_slots_admit's codes, launch and stores. */
+int zl_slots_admit_fsm(const int32_t* blob, int64_t n, int64_t rec_words, int64_t b, int64_t vocab, int32_t* tokens, int32_t* positions,
+                       int32_t* placement, int32_t* valid_lens, float* temperature, int32_t* top_k, float* top_p, int64_t* seeds,
+                       int64_t* draws, float* logprobs, float* u, float* rep_penalty, float* presence, int32_t* seen, int64_t seen_ld,
+                       int32_t* bias_ids, float* bias_vals, int32_t* bias_cnt, int32_t* bias_bits, int64_t bias_ld, int64_t bits_ld,
+                       int32_t* top_ids, float* top_logprobs, int64_t top_n, int32_t* stop_ids, int32_t* stop_seqs, int32_t* seq_lens,
+                       int64_t n_ids, int64_t n_seqs, int64_t seq_ld, int32_t* max_new, int32_t* gen_lens, int32_t* tail, int32_t* last_token,
+                       int32_t* finished, int32_t* emit_lens, int32_t* live, int32_t* history, int64_t cap, int32_t* hist_lens,
+                       int32_t* draft_new, int32_t* fsm_state, zl_stream_t s);
 /* The logit post-processing of the reference's batch generator (src/generator/beam_util.cu, 3rd/bmengine/bmengine/functions/{softmax,topk}.cu):
  * what src/generator/batch_generator.cpp calls between a decode step and its host-side search, so that the py_export surface (zhilight.C)
  * links against this boundary.  Rows of n logits of type ZL_T_F16 / ZL_T_BF16 / ZL_T_F32; fp32 arithmetic, one rounding to T.

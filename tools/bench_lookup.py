@@ -26,7 +26,12 @@
      length limit per task), replays alternated, at (B, K) = (1, 3), (8, 3) and (16, 1) -- a speculative step holds at most 32 rows, so
      16 tasks are the most it takes.  The step without stop= issues exactly the launches of the commit before the stop conditions.
 
-usage: python tools/bench_lookup.py [--launch-only | --step-only] [--sampler | --stop] [--reps 30] [--launches 200]"""
+  --grammar: the token automaton inside the speculative sampling step (profiles/sample_grammar.txt, with tools/bench_sample.py --grammar):
+  6. the whole captured step_lookup(sampler=) without automaton tables, with tables and every task unconstrained, and with every task
+     in a state that allows every other class, replays alternated, at --stop's (B, K) rows.  The zl_* calls of an eager step are
+     counted and must be as many with the grammar as without.
+
+usage: python tools/bench_lookup.py [--launch-only | --step-only] [--sampler | --stop | --grammar] [--reps 30] [--launches 200]"""
 import argparse
 import os
 import statistics
@@ -303,12 +308,79 @@ def stop_step_leg(dev, reps, rows):
         torch.cuda.empty_cache()
 
 
+class _Count:
+    """stands where ops.lib() returns the C library: counts the zl_* calls"""
+
+    def __init__(self, real):
+        self._real, self.n = real, 0
+
+    def __getattr__(self, name):
+        f = getattr(self._real, name)
+        if not name.startswith("zl_"):
+            return f
+
+        def call(*args):
+            self.n += 1
+            return f(*args)
+        return call
+
+
+def grammar_step_leg(dev, reps, rows):
+    from zhilight_amd import _lib
+    from zhilight_amd.grammar import TokenAutomaton
+    from zhilight_amd.llama import LLaMA, ModelConfig, QuantConfig
+    cfg = ModelConfig.llama3_8b()
+    model = LLaMA(cfg, QuantConfig(5, 128), dev)
+    model.init_synthetic(seed=1234)
+    seq = 1024
+    auto = TokenAutomaton(cfg.vocab_size, [{i: 0 for i in range(0, cfg.vocab_size, 2)}])
+    print("# whole step_lookup(sampler=) (T 0.8, top-k 40, top-p 0.95), synthetic Llama-3-8B GPTQ, %d tokens of history (a 64-id motif repeated): no "
+          "tables / tables, every task unconstrained / every task in a state that allows every other class; ms per step, median [p10 .. p90] over "
+          "%d alternated replays" % (seq, reps))
+    names = ("plain", "tables", "grammar")
+    for b, k in rows:
+        len_q = k + 1
+        len_buf = (seq + (reps + 8) * len_q + 63) // 64 * 64
+        torch.manual_seed(7)
+        ctxs = {n: model.new_context(b, len_buf, seq, fill_random=True) for n in names}
+        motif = torch.randint(0, cfg.vocab_size, (b, 64), dtype=torch.int32)
+        for c in ctxs.values():
+            c.tokens.copy_(motif[:, 0])
+        hist = [motif[j].repeat(seq // 64) for j in range(b)]
+        look = {n: model.new_lookup(ctxs[n], hist, k) for n in names}
+        kw = dict(seed=5, **SAMPLER)
+        samp = {"plain": model.new_sampler(ctxs["plain"], **kw), "tables": model.new_sampler(ctxs["tables"], **kw, grammar_states=8, grammar_edges=8),
+                "grammar": model.new_sampler(ctxs["grammar"], **kw, grammar=[auto] * b)}
+        calls = {}
+        for n in names:                                                          # eager: the row-expanded tables; then the count
+            model.step_lookup(ctxs[n], look[n], sampler=samp[n])
+            real = ops.lib
+            counter = _Count(_lib.lib())
+            ops.lib = lambda counter=counter: counter
+            try:
+                model.step_lookup(ctxs[n], look[n], sampler=samp[n])
+            finally:
+                ops.lib = real
+            calls[n] = counter.n
+        assert calls["plain"] == calls["tables"] == calls["grammar"], calls
+        graphs = {n: _graph(lambda n=n: model.step_lookup(ctxs[n], look[n], sampler=samp[n])) for n in names}
+        t = _alternate(graphs, reps)
+        st = {n: tuple(v / 1e3 for v in _stats(t[n], 1)) for n in graphs}
+        print("  %2d %2d | plain %7.3f [%6.3f .. %6.3f] | tables, unconstrained %7.3f [%6.3f .. %6.3f] | constrained %7.3f [%6.3f .. %6.3f] | "
+              "difference %6.1f / %6.1f us | %d zl_* calls per step in all three"
+              % ((b, k) + st["plain"] + st["tables"] + st["grammar"] + ((st["tables"][0] - st["plain"][0]) * 1e3,
+                                                                        (st["grammar"][0] - st["plain"][0]) * 1e3, calls["plain"])), flush=True)
+        del graphs, ctxs, look, samp
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launch-only", action="store_true")
     ap.add_argument("--step-only", action="store_true")
     ap.add_argument("--sampler", action="store_true", help="the speculative sampling legs (3 and 4) instead of the greedy ones")
     ap.add_argument("--stop", action="store_true", help="step_lookup with and without the stop conditions (leg 5) instead")
+    ap.add_argument("--grammar", action="store_true", help="step_lookup(sampler=) with and without the token automaton (leg 6) instead")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--launches", type=int, default=200)
     a = ap.parse_args()
@@ -317,6 +389,9 @@ def main():
     dev = torch.device("cuda:0")
     if a.stop:
         stop_step_leg(dev, a.reps, STOP_ROWS)
+        return
+    if a.grammar:
+        grammar_step_leg(dev, a.reps, STOP_ROWS)
         return
     if a.sampler:
         if not a.step_only:

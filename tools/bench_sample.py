@@ -29,8 +29,16 @@
      hit (two stop ids, two four-id stop sequences and a length limit per task) at batch 1, 8 and 32, replays alternated.  The step
      without stop= issues exactly the launches of the commit before the stop conditions: it is the yardstick.
 
-usage: python tools/bench_sample.py [--launch-only | --step-only | --penalties | --bias | --top-n [--step] | --stop] [--parent-so PATH]
-       [--reps 30] [--launches 100]"""
+  6. --grammar (profiles/sample_grammar.txt, with tools/bench_lookup.py --grammar): the token automaton.  (a) the OFF path --
+     zl_sample_advance, zl_sample_advance_ex and zl_sample_advance_opts as they are called today -- from this library and from
+     --parent-so in the same process, replays alternated.  (b) the launch alone at 1, 8 and 32 rows, masked (zl_sample_advance_fsm, every
+     row in a state that allows every other class and owns a 5000-entry exception list) against the same call unmasked;
+     the speculative call (both launches) at K = 4 and K = 31 with every draft walking a 5000-entry exception list, against the call
+     without tables.  With --step: the whole captured step_sample without tables, with tables and every task unconstrained, and with
+     every task constrained; the zl_* calls of an eager step are counted and must be as many with the grammar as without.
+
+usage: python tools/bench_sample.py [--launch-only | --step-only | --penalties | --bias | --top-n [--step] | --stop | --grammar [--step]]
+       [--parent-so PATH] [--reps 30] [--launches 100]"""
 import argparse
 import ctypes as C
 import os
@@ -363,6 +371,171 @@ def stop_step_leg(dev, reps):
         torch.cuda.empty_cache()
 
 
+def _bench_automaton(n, dev):
+    """two states that allow every other class each (even / odd ids); 5000 of a state's ids, evenly spread, are exceptions that lead to
+    the other state, the rest default to the state itself -> ops.grammar_tables' tuple"""
+    import numpy as np
+    from zhilight_amd.grammar import TokenAutomaton
+    trans = []
+    for s in (0, 1):
+        ids = np.arange(s, n, 2)
+        nxt = np.full(ids.size, s)
+        nxt[np.linspace(0, ids.size - 1, 5000).astype(np.int64)] = 1 - s
+        trans.append(dict(zip(ids.tolist(), nxt.tolist())))
+    return ops.grammar_tables(TokenAutomaton(n, trans).pack(), dev)
+
+
+def grammar_leg(dev, reps, launches, parent_so):
+    from zhilight_amd._lib import lib
+    libs = {"this": lib()}
+    if parent_so:
+        libs["parent"] = C.CDLL(parent_so)
+    p = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)           # noqa: E731
+    i64 = C.c_int64
+    words = ops.seen_words(VOCAB)
+    fsm = _bench_automaton(VOCAB, dev)
+    print("# the token automaton: warm rows of %d fp16 logits (normal, sigma 2), T 0.8, top-k 40, top-p 0.95; a state allows every other class, "
+          "%d exception entries per state: us per call, median [p10 .. p90] over %d alternated replays of %d calls"
+          % (VOCAB, int(fsm[3].numel()) // 2, reps, launches))
+    graphs, keep = {}, []
+    f32 = dict(dtype=torch.float32, device=dev)
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)        # noqa: E731
+    for rows in (1, 8, 32):
+        gen = torch.Generator(device="cpu").manual_seed(rows)
+        logits = (torch.randn((rows, VOCAB), generator=gen) * 2).to(torch.float16).to(dev)
+        ids = torch.stack([torch.randperm(VOCAB, generator=gen)[:VOCAB // 100] for _ in range(rows)]).to(torch.int32).to(dev)
+        tok = torch.zeros(rows, dtype=torch.int32, device=dev)
+        one, zero = torch.ones(rows, **f32), torch.zeros(rows, **f32)
+        a = dict(T=torch.full((rows,), 0.8, **f32), k=torch.full((rows,), 40, dtype=torch.int32, device=dev), p=torch.full((rows,), 0.95, **f32),
+                 seeds=torch.arange(rows, dtype=torch.int64, device=dev), draws=torch.zeros(rows, dtype=torch.int64, device=dev),
+                 lp=torch.empty(rows, **f32), seen=torch.zeros((rows, words), dtype=torch.int32, device=dev))
+        ops.seen_mark(a["seen"], ids, VOCAB)
+        head = lambda a=a, logits=logits, tok=tok, rows=rows: (p(logits), C.c_int(2), i64(rows), i64(VOCAB), i64(VOCAB), p(a["T"]), p(a["k"]),   # noqa: E731
+                                                                p(a["p"]), p(a["seeds"]), p(a["draws"]), p(None), p(tok), p(None), p(None), p(None),
+                                                                p(None), p(a["lp"]), p(None))
+        pen = lambda a=a, one=one, zero=zero: (p(one), p(zero), p(a["seen"]), i64(words))                                                        # noqa: E731
+        nopen = (p(None), p(None), p(None), i64(0))
+        nine = (p(None), p(None), p(None), i64(0), p(None), i64(0), C.c_int(0), p(None), p(None))
+
+        def cell(fn):
+            def run():
+                for _ in range(launches):
+                    assert fn() == 0
+            return _graph(run)
+        this = libs["this"]
+        for which, l in libs.items():                                        # (a) the off path, both libraries
+            for name in ("zl_sample_advance", "zl_sample_advance_ex", "zl_sample_advance_opts"):
+                getattr(l, name).argtypes = getattr(this, name).argtypes
+            graphs[(rows, which + ": sample_advance")] = cell(lambda l=l, head=head: l.zl_sample_advance(*head(), stream()))
+            graphs[(rows, which + ": sample_advance_ex (seen)")] = cell(lambda l=l, head=head, pen=pen: l.zl_sample_advance_ex(*head(), *pen(), stream()))
+            graphs[(rows, which + ": sample_advance_opts (seen, all nine off)")] = cell(
+                lambda l=l, head=head, pen=pen: l.zl_sample_advance_opts(*head(), *pen(), *nine, stream()))
+        st = torch.zeros(rows, dtype=torch.int32, device=dev)                # (b) masked: the rows start in state 0 and move between the two
+        tables = lambda st=st: (p(fsm[0]), i64(fsm[0].shape[1]), p(fsm[1]), p(fsm[2]), p(fsm[3]), p(fsm[4]), i64(fsm[0].shape[0]),            # noqa: E731
+                                i64(fsm[3].numel()), p(st))
+        graphs[(rows, "fsm: masked")] = cell(lambda head=head, tables=tables: this.zl_sample_advance_fsm(*head(), *nopen, *nine, *tables(), stream()))
+        graphs[(rows, "fsm: masked + seen")] = cell(lambda head=head, pen=pen, tables=tables: this.zl_sample_advance_fsm(*head(), *pen(), *nine, *tables(),
+                                                                                                                        stream()))
+        free = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+        graphs[(rows, "fsm: tables, every row unconstrained")] = cell(
+            lambda head=head, tables=tables, free=free: this.zl_sample_advance_fsm(*head(), *nopen, *nine, *tables(free), stream()))
+        keep.append((logits, ids, tok, one, zero, a, st, free))
+    t = _alternate(graphs, reps)
+    print("# rows | %-50s | us per call" % "call")
+    for (rows, which), ms in t.items():
+        print("  %4d | %-50s | %7.2f [%7.2f .. %7.2f]" % ((rows, which) + _stats(ms, launches)), flush=True)
+    # the speculative call: the chain's worst case, every draft allowed and an exception of its state
+    chain = fsm
+    print("# zl_spec_sample_accept(_fsm), B = 1, both launches: every draft hits a 5000-entry exception list (the states alternate); us per call")
+    graphs, keep = {}, []
+    for K in (4, 31):
+        len_q = K + 1
+        gen = torch.Generator(device="cpu").manual_seed(K)
+        logits = (torch.randn((len_q, VOCAB), generator=gen) * 2).to(torch.float16).to(dev)
+        exc, off = chain[3].tolist(), chain[2].tolist()
+        drafts = torch.tensor([[exc[off[j % 2] + 17 * j + 4000] for j in range(K)]], dtype=torch.int32, device=dev)   # deep in the lists
+        kw = dict(temperature=torch.full((1,), 0.8, **f32), top_k=torch.full((1,), 40, dtype=torch.int32, device=dev), top_p=torch.full((1,), 0.95, **f32),
+                  seeds=torch.zeros(1, dtype=torch.int64, device=dev), draws=torch.zeros(1, dtype=torch.int64, device=dev),
+                  accepted=torch.zeros(1, dtype=torch.int32, device=dev), out_tokens=torch.zeros((1, len_q), dtype=torch.int32, device=dev))
+        st, rs = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros((1, len_q), dtype=torch.int32, device=dev)
+
+        def masked(logits=logits, drafts=drafts, kw=kw, st=st, rs=rs):
+            for _ in range(launches):
+                st.zero_()
+                ops.spec_sample_accept(logits, drafts, **kw, fsm=chain, fsm_state=st, row_states=rs)
+
+        def plain_zero(logits=logits, drafts=drafts, kw=kw, st=st):
+            for _ in range(launches):
+                st.zero_()
+                ops.spec_sample_accept(logits, drafts, **kw)
+        graphs[(K, "without tables (+ the state's reset)")] = _graph(plain_zero)
+        graphs[(K, "fsm: every draft an exception")] = _graph(masked)
+        keep.append((logits, drafts, kw, st, rs))
+    t = _alternate(graphs, reps)
+    for (K, which), ms in t.items():
+        print("  K = %2d | %-40s | %7.2f [%7.2f .. %7.2f]" % ((K, which) + _stats(ms, launches)), flush=True)
+
+
+class _Count:
+    """stands where ops.lib() returns the C library: counts the zl_* calls"""
+
+    def __init__(self, real):
+        self._real, self.n = real, 0
+
+    def __getattr__(self, name):
+        f = getattr(self._real, name)
+        if not name.startswith("zl_"):
+            return f
+
+        def call(*args):
+            self.n += 1
+            return f(*args)
+        return call
+
+
+def grammar_step_leg(dev, reps):
+    from zhilight_amd import _lib
+    from zhilight_amd.grammar import TokenAutomaton
+    from zhilight_amd.llama import LLaMA, ModelConfig, QuantConfig
+    cfg = ModelConfig.llama3_8b()
+    model = LLaMA(cfg, QuantConfig(5, 128), dev)
+    model.init_synthetic(seed=1234)
+    seq = 1024
+    auto = TokenAutomaton(cfg.vocab_size, [{i: 0 for i in range(0, cfg.vocab_size, 2)}])
+    print("# whole step_sample (T 0.8, top-k 40, top-p 0.95), synthetic Llama-3-8B GPTQ, %d tokens of history: no tables / tables, every task "
+          "unconstrained / every task in a state that allows every other class; ms per step, median [p10 .. p90] over %d alternated replays" % (seq, reps))
+    for b in (1, 8, 32):
+        len_buf = (seq + reps + 16 + 63) // 64 * 64
+        torch.manual_seed(7)
+        names = ("plain", "tables", "grammar")
+        ctxs = {n: model.new_context(b, len_buf, seq, fill_random=True) for n in names}
+        kw = dict(temperature=0.8, top_k=40, top_p=0.95, seed=5)
+        states = {"plain": model.new_sampler(ctxs["plain"], **kw), "tables": model.new_sampler(ctxs["tables"], **kw, grammar_states=8, grammar_edges=8),
+                  "grammar": model.new_sampler(ctxs["grammar"], **kw, grammar=[auto] * b)}
+        calls = {}
+        for n in names:                                                      # the launch count: the zl_* calls of the second eager step
+            model.step_sample(ctxs[n], states[n])
+            real = ops.lib
+            counter = _Count(_lib.lib())
+            ops.lib = lambda counter=counter: counter
+            try:
+                model.step_sample(ctxs[n], states[n])
+            finally:
+                ops.lib = real
+            calls[n] = counter.n
+        assert calls["plain"] == calls["tables"] == calls["grammar"], calls
+        graphs = {n: _graph(lambda n=n: model.step_sample(ctxs[n], states[n])) for n in names}
+        t = _alternate(graphs, reps)
+        st = {n: tuple(v / 1e3 for v in _stats(t[n], 1)) for n in graphs}
+        ok = bool((ctxs["grammar"].tokens % 2 == 0).all())
+        print("  %2d | plain %7.3f [%6.3f .. %6.3f] | tables, unconstrained %7.3f [%6.3f .. %6.3f] | constrained %7.3f [%6.3f .. %6.3f] | "
+              "difference %6.1f / %6.1f us | %d zl_* calls per step in all three | every constrained pick allowed: %s"
+              % ((b,) + st["plain"] + st["tables"] + st["grammar"] + ((st["tables"][0] - st["plain"][0]) * 1e3, (st["grammar"][0] - st["plain"][0]) * 1e3,
+                                                                        calls["plain"], ok)), flush=True)
+        del graphs, ctxs, states
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launch-only", action="store_true")
@@ -372,6 +545,7 @@ def main():
     ap.add_argument("--top-n", action="store_true")
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--stop", action="store_true", help="the stop conditions' launch alone and inside step_sample (leg 5)")
+    ap.add_argument("--grammar", action="store_true", help="the token automaton: the off path against --parent-so, masked against unmasked (leg 6)")
     ap.add_argument("--parent-so", default=None)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--launches", type=int, default=100)
@@ -381,6 +555,12 @@ def main():
     dev = torch.device("cuda:0")
     if a.penalties:
         penalty_leg(dev, a.reps, a.launches, a.parent_so)
+        return
+    if a.grammar:
+        if not a.step_only:
+            grammar_leg(dev, a.reps, a.launches, a.parent_so)
+        if a.step or a.step_only:
+            grammar_step_leg(dev, a.reps)
         return
     if a.stop:
         if not a.step_only:

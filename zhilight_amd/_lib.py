@@ -23,7 +23,7 @@ SYMBOLS = [
     "zl_moe_fill_m_indices",
     "zl_embedding_rope",
     "zl_fp8_per_token_cast", "zl_fp8_block_dequant", "zl_fp8_block_gemm_group", "zl_fp8_block_packed_bytes", "zl_fp8_block_pack", "zl_fp8_block_gemm_group_packed", "zl_moe_top_k_softmax", "zl_moe_group_topk",
-    "zl_cast", "zl_copy_2d", "zl_index_select", "zl_argmax_advance", "zl_arange_i32", "zl_divide_i32", "zl_scatter_update_dim0", "zl_sort_pairs_i32", "zl_log_softmax_bias", "zl_softmax_rows", "zl_topk_rows", "zl_gather_logits", "zl_scatter_logits", "zl_repetition_penalty", "zl_spec_accept", "zl_lookup_draft", "zl_stop_advance", "zl_slots_admit", "zl_sample_advance", "zl_spec_sample_accept", "zl_sample_advance_ex", "zl_spec_sample_accept_ex", "zl_seen_mark", "zl_sample_advance_opts", "zl_spec_sample_accept_opts", "zl_reduce_abs_max", "zl_binary_op", "zl_scale", "zl_act_inplace",
+    "zl_cast", "zl_copy_2d", "zl_index_select", "zl_argmax_advance", "zl_arange_i32", "zl_divide_i32", "zl_scatter_update_dim0", "zl_sort_pairs_i32", "zl_log_softmax_bias", "zl_softmax_rows", "zl_topk_rows", "zl_gather_logits", "zl_scatter_logits", "zl_repetition_penalty", "zl_spec_accept", "zl_lookup_draft", "zl_stop_advance", "zl_slots_admit", "zl_sample_advance", "zl_spec_sample_accept", "zl_sample_advance_ex", "zl_spec_sample_accept_ex", "zl_seen_mark", "zl_sample_advance_opts", "zl_spec_sample_accept_opts", "zl_sample_advance_fsm", "zl_spec_sample_accept_fsm", "zl_slots_admit_fsm", "zl_reduce_abs_max", "zl_binary_op", "zl_scale", "zl_act_inplace",
     "zl_count_nonfinite", "zl_perm_narrow_u16", "zl_perm_reverse_u16", "zl_permute_input_u16", "zl_gptq_permute_rows",
     "zl_version", "zl_status_string", "zl_device_cu_count",
     "zl_gptq_shuffle", "zl_gptq_increase_zero", "zl_gptq_q4_to_q8", "zl_transpose_2d", "zl_gptq_reconstruct",
@@ -117,6 +117,13 @@ def lib():
         l.zl_sample_advance_opts.argtypes = [C.c_void_p, C.c_int] + [C.c_int64] * 3 + [C.c_void_p] * 16 + [C.c_int64] + opts + [C.c_void_p]
         l.zl_spec_sample_accept_opts.restype = C.c_int
         l.zl_spec_sample_accept_opts.argtypes = [C.c_void_p, C.c_int] + [C.c_int64] * 4 + [C.c_void_p] * 19 + [C.c_int64] + opts + [C.c_void_p]
+        fsm = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 2 + [C.c_void_p]      # the tables, S, E and fsm_state of the _fsm calls
+        l.zl_sample_advance_fsm.restype = C.c_int
+        l.zl_sample_advance_fsm.argtypes = ([C.c_void_p, C.c_int] + [C.c_int64] * 3 + [C.c_void_p] * 16 + [C.c_int64] + opts + fsm
+                                            + [C.c_void_p])
+        l.zl_spec_sample_accept_fsm.restype = C.c_int
+        l.zl_spec_sample_accept_fsm.argtypes = ([C.c_void_p, C.c_int] + [C.c_int64] * 4 + [C.c_void_p] * 19 + [C.c_int64] + opts + fsm
+                                                + [C.c_void_p] * 2)
         l.zl_stop_advance.restype = C.c_int
         l.zl_stop_advance.argtypes = ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_int64] * 2
                                       + [C.c_void_p] * 9)
@@ -124,6 +131,8 @@ def lib():
         l.zl_slots_admit.argtypes = ([C.c_void_p] + [C.c_int64] * 4 + [C.c_void_p] * 14 + [C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 2
                                      + [C.c_void_p] * 2 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_void_p] * 8
                                      + [C.c_int64] + [C.c_void_p] * 3)
+        l.zl_slots_admit_fsm.restype = C.c_int
+        l.zl_slots_admit_fsm.argtypes = l.zl_slots_admit.argtypes[:-1] + [C.c_void_p] * 2
         l.zl_seen_mark.restype = C.c_int
         l.zl_seen_mark.argtypes = [C.c_void_p] + [C.c_int64] * 3 + [C.c_void_p] + [C.c_int64] * 2 + [C.c_void_p]
         _lib = l

@@ -47,6 +47,15 @@
 //                       of the N-th class), find_jth only where the N-th place cuts a run of equal values, one gather stream into an
 //                       LDS list of min(N, n) candidates, and a rank by counting.  sample_row<.., MODE 2> below; MODE 0 / 1 are the
 //                       kernels above, unchanged.
+//   zl_sample_advance_fsm / zl_spec_sample_accept_fsm   the same picks under a TOKEN AUTOMATON: a DFA over token ids, resident on the
+//                       device and shared by every row -- per state a dense allow-bitmap over the vocabulary (seen's layout), a
+//                       default next state and an ascending exception list (CSR).  A row owns one int32, its state; a class whose
+//                       bit is clear in the state's bitmap is read as -inf WHEREVER a stored pattern is loaded (Mask below: a 16-byte
+//                       lane fetches the one or two bitmap words that cover it and selects branchlessly -- the disallowed set is
+//                       dense, so nothing loops per bit), in front of the penalty and the bias; after the pick one wave advances the
+//                       state (fsm_delta: a 64-ary search of the exception list, a few dependent loads).  A row of a speculative
+//                       step first walks its task's state over the drafts in front of it.  sample_row<.., MODE 3>; a state outside
+//                       [0, S) leaves the row unconstrained.  MODE 0 / 1 / 2 never see a Mask.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -122,6 +131,82 @@ struct Opts {
     float* top_lp;
 };
 constexpr int kMaxTop = 32;        // top_n's limit: one candidate per lane of half a wave
+// what the _fsm entry points add to a launch (one kernel argument of the MODE 3 kernels alone)
+struct Fsm {
+    const uint32_t* mask;           // (S, mask_ld): bit i of state s set <=> token i is allowed in s
+    int64_t mask_ld;
+    const int32_t* dflt;            // (S): the next state of an allowed token without an exception entry
+    const int32_t* exc_off;         // (S + 1): state s owns the entries exc_off[s] .. exc_off[s + 1] - 1
+    const int32_t* exc_tok;         // (E): ascending and distinct inside a state
+    const int32_t* exc_next;        // (E)
+    int S, E;
+    int32_t* state;                 // (rows or b), in place
+    int32_t* row_states;            // SPEC: (b, len_q), the state behind every row's pick
+};
+
+struct NoMask {                     // MODE 0 / 1 / 2: a stored pattern is what the row holds
+    static constexpr bool on = false;
+};
+// MODE 3: the row's view of its stored patterns under its state's allow-bitmap; bits == NULL: an unconstrained row (uniform over the
+// workgroup), read as stored
+template <bool BF>
+struct Mask {
+    static constexpr bool on = true;
+    static constexpr uint32_t kNeg = H16<BF>::kInf | 0x8000u;
+    const uint32_t* bits;
+    __device__ __forceinline__ uint16_t at(uint16_t h, int i) const {
+        if (!bits) return h;
+        return (bits[i >> 5] >> (i & 31) & 1u) ? h : (uint16_t)kNeg;
+    }
+    // the eight classes i0 .. i0 + 7 of one 16-byte lane; the caller has i0 + 7 < n, so both words lie inside ceil(n / 32)
+    __device__ __forceinline__ uint4 lane(uint4 d, int i0) const {
+        if (!bits) return d;
+        const uint32_t lo = bits[i0 >> 5], hi = bits[(i0 + 7) >> 5];
+        const uint32_t m = (uint32_t)((((u64)hi << 32) | lo) >> (i0 & 31));
+        auto sel = [](uint32_t w, uint32_t b2) {
+            const uint32_t keep = ((0u - (b2 & 1u)) & 0xffffu) | ((0u - ((b2 >> 1) & 1u)) & 0xffff0000u);
+            return (w & keep) | ((kNeg | (kNeg << 16)) & ~keep);
+        };
+        return make_uint4(sel(d.x, m), sel(d.y, m >> 2), sel(d.z, m >> 4), sel(d.w, m >> 6));
+    }
+};
+// every read of a stored pattern goes through these two
+template <class M>
+__device__ __forceinline__ uint16_t ld1(const uint16_t* __restrict__ row, int i, const M& mk) {
+    if constexpr (M::on) return mk.at(row[i], i);
+    else return row[i];
+}
+template <class M>
+__device__ __forceinline__ uint4 ld8(const uint4* __restrict__ body, int v, int i0, const M& mk) {
+    if constexpr (M::on) return mk.lane(body[v], i0);
+    else return body[v];
+}
+
+// delta(s, tok) by ONE WHOLE WAVE (every lane calls it with the same arguments and gets the same result): s outside [0, S), tok outside
+// [0, n) or not allowed in s -> s; else the exception's target where the list of s holds tok, else the default.  The list is searched
+// 64 ways at a time: 5000 entries take three dependent loads where a binary search takes thirteen
+__device__ __forceinline__ int fsm_delta(const Fsm& a, int s, int tok, int n) {
+    if (s < 0 || s >= a.S || tok < 0 || tok >= n) return s;
+    if (!(a.mask[(size_t)s * a.mask_ld + (tok >> 5)] >> (tok & 31) & 1u)) return s;
+    const int lane = threadIdx.x & 63;
+    int lo = a.exc_off[s], hi = a.exc_off[s + 1];
+    lo = lo < 0 ? 0 : (lo > a.E ? a.E : lo);                            // never outside the lists, whatever the offsets hold
+    hi = hi < lo ? lo : (hi > a.E ? a.E : hi);
+    while (hi - lo > 64) {
+        const int step = (hi - lo + 63) >> 6;
+        const int idx = lo + lane * step;
+        bool le = false;
+        if (idx < hi) le = a.exc_tok[idx] <= tok;
+        const int c = __popcll(__ballot(le));                           // ascending: a prefix of the lanes
+        if (c == 0) return a.dflt[s];
+        lo += (c - 1) * step;
+        hi = lo + step < hi ? lo + step : hi;
+    }
+    bool eq = false;
+    if (lo + lane < hi) eq = a.exc_tok[lo + lane] == tok;
+    const u64 hit = __ballot(eq);
+    return hit ? a.exc_next[lo + __ffsll((unsigned long long)hit) - 1] : a.dflt[s];
+}
 
 // the row's view of its penalty: the set = the task's bitmap, and for row i of a speculative step the in-range drafts 0 .. i - 1
 // OPT (the _opts entry points): the set is the union of that and of the task's BIAS bitmap; a class of the set is read as "the
@@ -228,8 +313,8 @@ struct Pen {
     // g(stored pattern, penalised pattern, index) for every class of the set, each once, in no particular order: the bitmap's words
     // below n over the threads -- 4 loads per thread at 128 256 classes, and as many trips as a task has emitted tokens there --
     // then (SPEC) the drafts in front of the row that the bitmap does not hold, one thread each
-    template <class G>
-    __device__ __forceinline__ void for_set(const uint16_t* __restrict__ row, int n, G&& g) const {
+    template <class M, class G>
+    __device__ __forceinline__ void for_set(const uint16_t* __restrict__ row, int n, const M& mk, G&& g) const {
         const int nw = (n + 31) >> 5;
         for (int w = threadIdx.x; w < nw; w += kThreads) {
             uint32_t bits = uw(w);
@@ -237,7 +322,7 @@ struct Pen {
             while (bits) {
                 const int i = w * 32 + __ffs((int)bits) - 1;
                 bits &= bits - 1;
-                const uint16_t h = row[i];
+                const uint16_t h = ld1(row, i, mk);
                 if constexpr (OPT) g(h, modified(h, i), i);
                 else g(h, apply(h), i);
             }
@@ -250,7 +335,7 @@ struct Pen {
                 if (fresh) fresh = !(uw(id >> 5) >> (id & 31) & 1u);    // OPT: a draft with a bias bit came with the bitmaps' walk
                 for (int j = 0; j < t; ++j) fresh &= ids[j] != id;
                 if (fresh) {
-                    const uint16_t h = row[id];
+                    const uint16_t h = ld1(row, id, mk);
                     g(h, apply(h), id);
                 }
             }
@@ -261,16 +346,17 @@ struct Pen {
 // f(pattern, index) for every element of the row, in no particular order: up to 7 elements in front of the first 16-byte boundary,
 // 16-byte lanes with kLoads loads in flight, up to 7 elements behind the last whole lane.  pen.on: the pattern is the penalised one --
 // the streaming loop leaves the set's classes out (the mask of a lane is one or two bitmap words) and pen.for_set brings them in
-template <class P, class F>
-__device__ __forceinline__ void for_each(const uint16_t* __restrict__ row, int n, const P& pen, F&& f) {
+// mk.on (MODE 3): every pattern is loaded through the row's allow-bitmap first
+template <class P, class M, class F>
+__device__ __forceinline__ void for_each(const uint16_t* __restrict__ row, int n, const P& pen, const M& mk, F&& f) {
     const int tid = threadIdx.x;
     int head = (int)(((16 - ((uintptr_t)row & 15)) & 15) >> 1);
     head = head < n ? head : n;
     auto one = [&](int i) {
         if constexpr (P::on) {
-            if (!pen.has(i)) f(row[i], i);
+            if (!pen.has(i)) f(ld1(row, i, mk), i);
         } else {
-            f(row[i], i);
+            f(ld1(row, i, mk), i);
         }
     };
     if (tid < head) one(tid);
@@ -282,7 +368,7 @@ __device__ __forceinline__ void for_each(const uint16_t* __restrict__ row, int n
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
             const int c = c0 + u * kThreads;
-            v4[u] = body[c < nv ? c : c0];
+            v4[u] = ld8(body, c < nv ? c : c0, head + (c < nv ? c : c0) * 8, mk);
             if constexpr (P::on) m8[u] = pen.mask8(head + (c < nv ? c : c0) * 8);
         }
 #pragma unroll
@@ -302,7 +388,7 @@ __device__ __forceinline__ void for_each(const uint16_t* __restrict__ row, int n
         }
     }
     for (int i = head + nv * 8 + tid; i < n; i += kThreads) one(i);
-    if constexpr (P::on) pen.for_set(row, n, [&](uint16_t, uint16_t ph, int i) { f(ph, i); });
+    if constexpr (P::on) pen.for_set(row, n, mk, [&](uint16_t, uint16_t ph, int i) { f(ph, i); });
 }
 
 struct Hist {                       // 48 KB: kCopies interleaved copies of a 256-bin (count, mass) histogram
@@ -407,8 +493,9 @@ __device__ __forceinline__ int count8(const uint4& d, uint32_t key) {
 // the j-th (1-based) class of the row, in index order, whose key is `key` -> *pick (left alone if there are fewer: never the case for a
 // j taken from the histograms).  Order = for_each's three pieces; the 16-byte lanes are cut into one contiguous piece per wave.
 // pen.on: the keys are the penalised patterns', as in for_each
-template <class P>
-__device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n, const P& pen, uint32_t key, int j, int* wcnt, int* pick) {
+template <class P, class M>
+__device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n, const P& pen, const M& mk, uint32_t key, int j, int* wcnt,
+                                         int* pick) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int head = (int)(((16 - ((uintptr_t)row & 15)) & 15) >> 1);
     head = head < n ? head : n;
@@ -417,22 +504,22 @@ __device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n
     const int vpw = (nv + kWaves - 1) / kWaves;
     const int v0 = wave * vpw < nv ? wave * vpw : nv, v1 = v0 + vpw < nv ? v0 + vpw : nv;
     auto at = [&](int i) -> uint16_t {
-        if constexpr (P::on) return pen.one(row[i], i);
-        else return row[i];
+        if constexpr (P::on) return pen.one(ld1(row, i, mk), i);
+        else return ld1(row, i, mk);
     };
     auto lane8 = [&](int v) -> uint4 {
-        uint4 d = body[v];
+        uint4 d = ld8(body, v, head + v * 8, mk);
         if constexpr (P::on) pen.apply8(d, pen.mask8(head + v * 8), head + v * 8);
         return d;
     };
     int c = 0;
-    for (int v = v0 + lane; v < v1; v += 64) c += count8(body[v], key);        // the stored patterns; pen.on: corrected below
+    for (int v = v0 + lane; v < v1; v += 64) c += count8(ld8(body, v, head + v * 8, mk), key);        // the stored patterns; pen.on: corrected below
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
     if (lane == 0) wcnt[wave] = c;
     __syncthreads();
     if constexpr (P::on) {
-        pen.for_set(row, n, [&](uint16_t raw, uint16_t ph, int i) {
+        pen.for_set(row, n, mk, [&](uint16_t raw, uint16_t ph, int i) {
             const int d = (int)(key16(ph) == key) - (int)(key16(raw) == key);
             if (d != 0 && i >= head && i < tail) atomicAdd(&wcnt[((i - head) >> 3) / vpw], d);
         });
@@ -504,7 +591,10 @@ __device__ __forceinline__ void find_jth(const uint16_t* __restrict__ row, int n
 //   6n  one stream: the classes above k_N and those of k_N up to that index into an LDS list of exactly min(top_n, n) entries (the
 //       arrival order does not matter); a candidate's slot is the number of candidates in front of it by (key descending, index
 //       ascending), its log-probability the pick's expression on its pattern
-// The body of both kernels below: k_sample_advance keeps the argument list it always had, k_sample_advance_opts adds o
+// MODE 3 (the _fsm entry points with an automaton): MODE 2's reading of a row whose stored patterns pass through Mask first.  Wave 0
+// reads the row's state -- SPEC: the task's state walked over the drafts in front of the row -- before pass 1, and advances it over
+// the pick behind the epilogue: !SPEC into fa.state[r], SPEC into fa.row_states[r] (the second launch picks the accepted row's)
+// The body of the kernels below: k_sample_advance keeps the argument list it always had, k_sample_advance_opts adds o, _fsm adds fa
 template <bool BF, bool SPEC, int MODE>
 __device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64_t ld, int n, int len_q, const float* __restrict__ temperature,
                                            const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
@@ -513,8 +603,8 @@ __device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64
                                            int32_t* __restrict__ valid_lens, int64_t* __restrict__ next_tokens, float* __restrict__ logprobs,
                                            float* __restrict__ u_out, const float* __restrict__ rep_penalty,
                                            const float* __restrict__ presence, uint32_t* seen, int64_t seen_ld,
-                                           const int32_t* __restrict__ drafts, const Opts& o) {
-    constexpr bool PEN = MODE >= 1, OPT = MODE == 2;
+                                           const int32_t* __restrict__ drafts, const Opts& o, const Fsm& fa) {
+    constexpr bool PEN = MODE >= 1, OPT = MODE >= 2, FSM = MODE == 3;
     __shared__ Hist hist;
     __shared__ u64 red[kWaves];
     __shared__ u64 wm[kBins / 64];
@@ -528,7 +618,24 @@ __device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64
     const uint16_t* row = x + (size_t)r * ld;
 
     typedef typename std::conditional<PEN, Pen<BF, SPEC, OPT>, NoPen>::type P;
+    typedef typename std::conditional<FSM, Mask<BF>, NoMask>::type M;
     P pen;
+    M mk;
+    int st = -1;                                                        // FSM: the row's state
+    bool con = false;                                                   // ... and whether it constrains the row
+    if constexpr (FSM) {
+        __shared__ int s_state;
+        if (wave == 0) {
+            int s = fa.state[pr];
+            if constexpr (SPEC)
+                for (int j = 0; j < r - pr * len_q; ++j) s = fsm_delta(fa, s, drafts[(size_t)pr * (len_q - 1) + j], n);
+            if (lane == 0) s_state = s;
+        }
+        __syncthreads();
+        st = s_state;
+        con = st >= 0 && st < fa.S;
+        mk.bits = con ? fa.mask + (size_t)st * fa.mask_ld : nullptr;
+    }
     const bool sn = !OPT || seen != nullptr;                            // a penalty set: always under MODE 1
     if constexpr (PEN) {
         __shared__ uint32_t s_filt[kFilt / 32];
@@ -586,7 +693,7 @@ __device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64
 
     // ---- pass 1: zl_argmax_advance's pick -----------------------------------------------------------------------------------------
     u64 best = 0;
-    for_each(row, n, pen, [&](uint16_t h, int i) {
+    for_each(row, n, pen, mk, [&](uint16_t h, int i) {
         const uint32_t k = (h & 0x7fffu) > H16<BF>::kInf ? 0xffffffffu : key16(h);       // a NaN is the largest value, the first one wins
         const u64 key = ((u64)k << 32) | (uint32_t)~(uint32_t)i;
         best = key > best ? key : best;
@@ -624,13 +731,13 @@ __device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64
         const bool c_on = k_on || topn_on;                              // the count selects: top-k's and top-N's
         hist_zero(hist);
         // PEN, here and in the low byte's pass: the stored row as it is, then the set's classes move to their penalised bins
-        for_each(row, n, NoPen(), [&](uint16_t h, int) {
+        for_each(row, n, NoPen(), mk, [&](uint16_t h, int) {
             const uint32_t kk = key16(h);
             if (c_on) hist_count(hist, kk >> 8);
             hist_mass(hist, kk >> 8, mass_of<BF>(kk, vmax, t, scale));
         });
         if constexpr (PEN)
-            pen.for_set(row, n, [&](uint16_t raw, uint16_t ph, int) {
+            pen.for_set(row, n, mk, [&](uint16_t raw, uint16_t ph, int) {
                 const uint32_t kr = key16(raw), kp = key16(ph);
                 if (kr == kp) return;
                 if (c_on) {
@@ -655,12 +762,12 @@ __device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64
         // count x mass_of(key), one exponential per bin instead of one per class, and sums to the level-1 bin exactly
         auto low_byte = [&](int bin) {
             hist_zero(hist);
-            for_each(row, n, NoPen(), [&](uint16_t h, int) {
+            for_each(row, n, NoPen(), mk, [&](uint16_t h, int) {
                 const uint32_t kk = key16(h);
                 if ((int)(kk >> 8) == bin) hist_count(hist, kk & 0xffu);
             });
             if constexpr (PEN)
-                pen.for_set(row, n, [&](uint16_t raw, uint16_t ph, int) {
+                pen.for_set(row, n, mk, [&](uint16_t raw, uint16_t ph, int) {
                     const uint32_t kr = key16(raw), kp = key16(ph);
                     if (kr == kp) return;
                     if ((int)(kr >> 8) == bin) hist_uncount(hist, kr & 0xffu);
@@ -702,12 +809,12 @@ __device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64
                 const uint32_t kn = s_kn;
                 if (!s_all) {
                     // ---- pass 5n: the run of k_N is cut: the index of its last class that belongs ---------------------------------------
-                    find_jth(row, n, pen, kn, s_need, wcnt, &s_last);
+                    find_jth(row, n, pen, mk, kn, s_need, wcnt, &s_last);
                     __syncthreads();
                 }
                 const int last = s_last;
                 // ---- pass 6n: the candidates, exactly ne of them ----------------------------------------------------------------------
-                for_each(row, n, pen, [&](uint16_t h, int i) {
+                for_each(row, n, pen, mk, [&](uint16_t h, int i) {
                     const uint32_t kk = key16(h);
                     if (kk > kn || (kk == kn && i <= last)) {
                         const int at = atomicAdd(&s_nc, 1);
@@ -782,7 +889,7 @@ __device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64
                 }
                 __syncthreads();
                 // ---- pass 5: the j-th class with that value, in index order ------------------------------------------------------------
-                find_jth(row, n, pen, (uint32_t)sel_key.bin, s_j, wcnt, &s_pick);
+                find_jth(row, n, pen, mk, (uint32_t)sel_key.bin, s_j, wcnt, &s_pick);
                 __syncthreads();
             }
         } else if constexpr (OPT) {
@@ -800,7 +907,7 @@ __device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64
             if (placement) placement[r] += 1;
             if (valid_lens) valid_lens[r] += 1;
         }
-        uint16_t hp = row[pick];
+        uint16_t hp = ld1(row, pick, mk);
         if constexpr (PEN) hp = pen.one(hp, pick);
         if (logprobs) logprobs[r] = plain ? __builtin_nanf("") : (H16<BF>::f32(hp) - vmax) / t - lse;
         if constexpr (PEN && !SPEC)
@@ -810,6 +917,13 @@ __device__ __forceinline__ void sample_row(const uint16_t* __restrict__ x, int64
         if (topn_on && plain && tid < o.top_n) {                        // no distribution, no alternatives
             o.top_ids[(size_t)r * o.top_n + tid] = -1;
             o.top_lp[(size_t)r * o.top_n + tid] = __builtin_nanf("");
+        }
+    if constexpr (FSM)
+        if (wave == 0 && (SPEC || con)) {                               // s_pick: final behind the barriers every path above ends with
+            int pick = s_pick;
+            pick = pick >= 0 && pick < n ? pick : amax;
+            const int ns = fsm_delta(fa, st, pick, n);                  // an unconstrained state stays what it is
+            if (lane == 0) (SPEC ? fa.row_states : fa.state)[r] = ns;
         }
 }
 
@@ -824,7 +938,7 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance(const uint16_t* __r
                                                              const float* __restrict__ rep_penalty, const float* __restrict__ presence,
                                                              uint32_t* seen, int64_t seen_ld, const int32_t* __restrict__ drafts) {
     sample_row<BF, SPEC, PEN ? 1 : 0>(x, ld, n, len_q, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
-                                      next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld, drafts, Opts{});
+                                      next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld, drafts, Opts{}, Fsm{});
 }
 
 template <bool BF, bool SPEC>
@@ -838,7 +952,22 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance_opts(const uint16_t
                                                                   const float* __restrict__ rep_penalty, const float* __restrict__ presence,
                                                                   uint32_t* seen, int64_t seen_ld, const int32_t* __restrict__ drafts, const Opts o) {
     sample_row<BF, SPEC, 2>(x, ld, n, len_q, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens, next_tokens,
-                            logprobs, u_out, rep_penalty, presence, seen, seen_ld, drafts, o);
+                            logprobs, u_out, rep_penalty, presence, seen, seen_ld, drafts, o, Fsm{});
+}
+
+template <bool BF, bool SPEC>
+__global__ __launch_bounds__(kThreads) void k_sample_advance_fsm(const uint16_t* __restrict__ x, int64_t ld, int n, int len_q, const float* __restrict__ temperature,
+                                                                 const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                                 const int64_t* __restrict__ seeds, int64_t* __restrict__ draws,
+                                                                 const float* __restrict__ u_in, int32_t* __restrict__ tokens,
+                                                                 int32_t* __restrict__ positions, int32_t* __restrict__ placement,
+                                                                 int32_t* __restrict__ valid_lens, int64_t* __restrict__ next_tokens,
+                                                                 float* __restrict__ logprobs, float* __restrict__ u_out,
+                                                                 const float* __restrict__ rep_penalty, const float* __restrict__ presence,
+                                                                 uint32_t* seen, int64_t seen_ld, const int32_t* __restrict__ drafts, const Opts o,
+                                                                 const Fsm fa) {
+    sample_row<BF, SPEC, 3>(x, ld, n, len_q, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens, next_tokens,
+                            logprobs, u_out, rep_penalty, presence, seen, seen_ld, drafts, o, fa);
 }
 
 // zl_spec_sample_accept's second launch: out_tokens / out_logprobs hold the picks of the (b, len_q) rows and their log-probabilities
@@ -848,12 +977,15 @@ __global__ __launch_bounds__(kThreads) void k_sample_advance_opts(const uint16_t
 // seen (zl_spec_sample_accept_ex): the emitted tokens' bits are set in the task's bitmap; the rejected drafts' are not
 // TOP (zl_spec_sample_accept_opts with top_n > 0): one 64-thread workgroup per task instead of one thread -- thread 0 does the above,
 // then all 64 pad the top-N slots of the rows behind the bonus token, up to 31 x 32 ids and log-probabilities, with -1 / NaN
-template <bool TOP>
+// FSM (zl_spec_sample_accept_fsm with an automaton): the task's state <- the state behind its last emitted row (the first launch left
+// one per row in row_states)
+template <bool TOP, bool FSM>
 __global__ void k_spec_sample_accept(const int32_t* __restrict__ drafts, int32_t* __restrict__ out_tokens, float* __restrict__ out_logprobs,
                                      int32_t* __restrict__ accepted, int32_t* __restrict__ tokens, int32_t* __restrict__ positions,
                                      int32_t* __restrict__ placement, int32_t* __restrict__ valid_lens, float* __restrict__ logprobs,
                                      int64_t* __restrict__ draws, int b, int len_q, uint32_t* __restrict__ seen, int64_t seen_ld, int top_n,
-                                     int32_t* __restrict__ top_ids, float* __restrict__ top_lp) {
+                                     int32_t* __restrict__ top_ids, float* __restrict__ top_lp, int32_t* __restrict__ fsm_state,
+                                     const int32_t* __restrict__ row_states) {
     const int t = TOP ? blockIdx.x : blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= b) return;                                                 // TOP: uniform over the workgroup
     int32_t* pk = out_tokens + (int64_t)t * len_q;
@@ -889,6 +1021,7 @@ __global__ void k_spec_sample_accept(const int32_t* __restrict__ drafts, int32_t
     if (valid_lens) valid_lens[t] += a + 1;
     if (logprobs) logprobs[t] = lp[a];
     if (draws) draws[t] += a + 1;
+    if constexpr (FSM) fsm_state[t] = row_states[(int64_t)t * len_q + a];
     if (seen)
         for (int j = 0; j <= a; ++j) seen[(int64_t)t * seen_ld + (pk[j] >> 5)] |= 1u << (pk[j] & 31);     // picks lie in [0, n)
 }
@@ -913,12 +1046,24 @@ int opts_check(const Opts& o, int64_t n) {
     return 0;
 }
 
+// the _fsm arguments' own refusals (0 = fine); E arrives as the caller's int64
+int fsm_check(const Fsm& fa, int64_t S, int64_t E, int64_t n, bool spec) {
+    const int given = (fa.mask != nullptr) + (fa.dflt != nullptr) + (fa.exc_off != nullptr) + (fa.exc_tok != nullptr) + (fa.exc_next != nullptr) +
+                      (fa.state != nullptr);
+    ZL_CHECK_ARG(given == 0 || given == 6, ZL_EINVAL);
+    if (given == 0) return 0;
+    ZL_CHECK_ARG(!spec || fa.row_states, ZL_EINVAL);
+    ZL_CHECK_ARG(S >= 1 && S < ((int64_t)1 << 31) && E >= 0 && E < ((int64_t)1 << 31) && fa.mask_ld >= (n + 31) / 32, ZL_ESHAPE);
+    return 0;
+}
+
 // the two launchers.  MODE: 2 where a bias or top-N is asked for, else 1 <=> seen != NULL, else 0 -- so the plain and _ex entry
 // points, and an _opts call with its nine arguments NULL / 0, launch the instantiations they always have
 int sample_advance_launch(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
                           const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
                           int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
-                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const Opts& o, zl_stream_t s) {
+                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const Opts& o, Fsm fa, int64_t S,
+                          int64_t E, zl_stream_t s) {
     ZL_CHECK_ARG(logits && temperature && top_k && top_p, ZL_EINVAL);
     ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
     ZL_CHECK_ARG(tokens || next_tokens, ZL_EINVAL);
@@ -927,25 +1072,31 @@ int sample_advance_launch(const void* logits, int type, int64_t rows, int64_t n,
     ZL_CHECK_ARG(!seen || seen_ld >= (n + 31) / 32, ZL_ESHAPE);
     ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
     if (const int e = opts_check(o, n)) return e;
+    if (const int e = fsm_check(fa, S, E, n, false)) return e;
+    fa.S = (int)S, fa.E = (int)E;
     const dim3 g((unsigned)rows), b(kThreads);
     hipStream_t hs = (hipStream_t)s;
-    const int mode = (o.bias_ids || o.top_n > 0) ? 2 : (seen ? 1 : 0);
+    const int mode = fa.mask ? 3 : (o.bias_ids || o.top_n > 0) ? 2 : (seen ? 1 : 0);
 #define ZL_ARGS                                                                                                                              \
     (const uint16_t*)logits, ld, (int)n, 1, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens, next_tokens, \
         logprobs, u_out, rep_penalty, presence, seen, seen_ld, (const int32_t*)nullptr
 #define ZL_SAMPLE(BF, PEN) hipLaunchKernelGGL((k_sample_advance<BF, false, PEN>), g, b, 0, hs, ZL_ARGS)
 #define ZL_SAMPLE_OPTS(BF) hipLaunchKernelGGL((k_sample_advance_opts<BF, false>), g, b, 0, hs, ZL_ARGS, o)
+#define ZL_SAMPLE_FSM(BF) hipLaunchKernelGGL((k_sample_advance_fsm<BF, false>), g, b, 0, hs, ZL_ARGS, o, fa)
     if (type == ZL_T_F16) {
-        if (mode == 2) ZL_SAMPLE_OPTS(false);
+        if (mode == 3) ZL_SAMPLE_FSM(false);
+        else if (mode == 2) ZL_SAMPLE_OPTS(false);
         else if (mode == 1) ZL_SAMPLE(false, true);
         else ZL_SAMPLE(false, false);
     } else {
-        if (mode == 2) ZL_SAMPLE_OPTS(true);
+        if (mode == 3) ZL_SAMPLE_FSM(true);
+        else if (mode == 2) ZL_SAMPLE_OPTS(true);
         else if (mode == 1) ZL_SAMPLE(true, true);
         else ZL_SAMPLE(true, false);
     }
 #undef ZL_SAMPLE
 #undef ZL_SAMPLE_OPTS
+#undef ZL_SAMPLE_FSM
 #undef ZL_ARGS
     return zl_launch_status();
 }
@@ -954,7 +1105,8 @@ int spec_sample_accept_launch(const void* logits, int type, int64_t b, int64_t l
                               const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
                               const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
                               int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
-                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const Opts& o, zl_stream_t s) {
+                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const Opts& o, Fsm fa,
+                              int64_t S, int64_t E, zl_stream_t s) {
     ZL_CHECK_ARG(logits && temperature && top_k && top_p && drafts && accepted && out_tokens, ZL_EINVAL);
     ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
     ZL_CHECK_ARG(out_logprobs || !logprobs, ZL_EINVAL);                 // the task's log-probability is read from its rows'
@@ -965,37 +1117,48 @@ int spec_sample_accept_launch(const void* logits, int type, int64_t b, int64_t l
     ZL_CHECK_ARG(!seen || seen_ld >= (n + 31) / 32, ZL_ESHAPE);
     ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
     if (const int e = opts_check(o, n)) return e;
+    if (const int e = fsm_check(fa, S, E, n, true)) return e;
+    fa.S = (int)S, fa.E = (int)E;
     // the picks: one 1024-thread workgroup per logit row, zl_sample_advance's kernel under the task's parameters, into out_tokens
     const dim3 g((unsigned)(b * len_q)), blk(kThreads);
     hipStream_t hs = (hipStream_t)s;
-    const int mode = (o.bias_ids || o.top_n > 0) ? 2 : (seen ? 1 : 0);
+    const int mode = fa.mask ? 3 : (o.bias_ids || o.top_n > 0) ? 2 : (seen ? 1 : 0);
 #define ZL_ARGS                                                                                                                          \
     (const uint16_t*)logits, ld, (int)n, (int)len_q, temperature, top_k, top_p, seeds, draws, u_in, out_tokens, nullptr, nullptr, nullptr, nullptr, \
         out_logprobs, u_out, rep_penalty, presence, seen, seen_ld, drafts
 #define ZL_SAMPLE(BF, PEN) hipLaunchKernelGGL((k_sample_advance<BF, true, PEN>), g, blk, 0, hs, ZL_ARGS)
 #define ZL_SAMPLE_OPTS(BF) hipLaunchKernelGGL((k_sample_advance_opts<BF, true>), g, blk, 0, hs, ZL_ARGS, o)
+#define ZL_SAMPLE_FSM(BF) hipLaunchKernelGGL((k_sample_advance_fsm<BF, true>), g, blk, 0, hs, ZL_ARGS, o, fa)
     if (type == ZL_T_F16) {
-        if (mode == 2) ZL_SAMPLE_OPTS(false);
+        if (mode == 3) ZL_SAMPLE_FSM(false);
+        else if (mode == 2) ZL_SAMPLE_OPTS(false);
         else if (mode == 1) ZL_SAMPLE(false, true);
         else ZL_SAMPLE(false, false);
     } else {
-        if (mode == 2) ZL_SAMPLE_OPTS(true);
+        if (mode == 3) ZL_SAMPLE_FSM(true);
+        else if (mode == 2) ZL_SAMPLE_OPTS(true);
         else if (mode == 1) ZL_SAMPLE(true, true);
         else ZL_SAMPLE(true, false);
     }
 #undef ZL_SAMPLE
 #undef ZL_SAMPLE_OPTS
+#undef ZL_SAMPLE_FSM
 #undef ZL_ARGS
     const int e = zl_launch_status();
     if (e) return e;
-    if (o.top_n > 0)
-        hipLaunchKernelGGL(k_spec_sample_accept<true>, dim3((unsigned)b), dim3(64), 0, hs, drafts, out_tokens, out_logprobs, accepted, tokens,
-                           positions, placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q, seen, seen_ld, o.top_n,
-                           o.top_ids, o.top_lp);
-    else
-        hipLaunchKernelGGL(k_spec_sample_accept<false>, dim3((unsigned)((b + 63) / 64)), dim3(64), 0, hs, drafts, out_tokens, out_logprobs,
-                           accepted, tokens, positions, placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q, seen,
-                           seen_ld, 0, (int32_t*)nullptr, (float*)nullptr);
+#define ZL_ACCEPT(TOP, FSM, grid, tn, ti, tl)                                                                                                  \
+    hipLaunchKernelGGL((k_spec_sample_accept<TOP, FSM>), grid, dim3(64), 0, hs, drafts, out_tokens, out_logprobs, accepted, tokens, positions,   \
+                       placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q, seen, seen_ld, tn, ti, tl, fa.state,        \
+                       (const int32_t*)fa.row_states)
+    const dim3 per_task((unsigned)b), per_lane((unsigned)((b + 63) / 64));
+    if (o.top_n > 0) {
+        if (mode == 3) ZL_ACCEPT(true, true, per_task, o.top_n, o.top_ids, o.top_lp);
+        else ZL_ACCEPT(true, false, per_task, o.top_n, o.top_ids, o.top_lp);
+    } else {
+        if (mode == 3) ZL_ACCEPT(false, true, per_lane, 0, (int32_t*)nullptr, (float*)nullptr);
+        else ZL_ACCEPT(false, false, per_lane, 0, (int32_t*)nullptr, (float*)nullptr);
+    }
+#undef ZL_ACCEPT
     return zl_launch_status();
 }
 
@@ -1007,7 +1170,7 @@ int zl_sample_advance(const void* logits, int type, int64_t rows, int64_t n, int
                       const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
                       int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out, zl_stream_t s) {
     return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
-                                 next_tokens, logprobs, u_out, nullptr, nullptr, nullptr, 0, Opts{}, s);
+                                 next_tokens, logprobs, u_out, nullptr, nullptr, nullptr, 0, Opts{}, Fsm{}, 0, 0, s);
 }
 
 int zl_sample_advance_ex(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
@@ -1015,7 +1178,7 @@ int zl_sample_advance_ex(const void* logits, int type, int64_t rows, int64_t n, 
                          int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
     return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
-                                 next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld, Opts{}, s);
+                                 next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld, Opts{}, Fsm{}, 0, 0, s);
 }
 
 int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
@@ -1023,7 +1186,7 @@ int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q
                           const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
                           int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out, zl_stream_t s) {
     return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
-                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, nullptr, nullptr, nullptr, 0, Opts{}, s);
+                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, nullptr, nullptr, nullptr, 0, Opts{}, Fsm{}, 0, 0, s);
 }
 
 int zl_spec_sample_accept_ex(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
@@ -1033,7 +1196,7 @@ int zl_spec_sample_accept_ex(const void* logits, int type, int64_t b, int64_t le
                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
     return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
                                      placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, rep_penalty, presence, seen,
-                                     seen_ld, Opts{}, s);
+                                     seen_ld, Opts{}, Fsm{}, 0, 0, s);
 }
 
 int zl_sample_advance_opts(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
@@ -1044,7 +1207,7 @@ int zl_sample_advance_opts(const void* logits, int type, int64_t rows, int64_t n
                            int top_n, int32_t* top_ids, float* top_logprobs, zl_stream_t s) {
     return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
                                  next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld,
-                                 Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs}, s);
+                                 Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs}, Fsm{}, 0, 0, s);
 }
 
 int zl_spec_sample_accept_opts(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
@@ -1057,6 +1220,36 @@ int zl_spec_sample_accept_opts(const void* logits, int type, int64_t b, int64_t 
     return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
                                      placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, rep_penalty, presence, seen,
                                      seen_ld, Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs},
+                                     Fsm{}, 0, 0, s);
+}
+
+int zl_sample_advance_fsm(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
+                          const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
+                          int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
+                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
+                          const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits, int64_t bias_bits_ld,
+                          int top_n, int32_t* top_ids, float* top_logprobs, const uint32_t* fsm_mask, int64_t mask_ld,
+                          const int32_t* fsm_default, const int32_t* fsm_exc_off, const int32_t* fsm_exc_tok, const int32_t* fsm_exc_next,
+                          int64_t S, int64_t E, int32_t* fsm_state, zl_stream_t s) {
+    return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
+                                 next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld,
+                                 Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs},
+                                 Fsm{fsm_mask, mask_ld, fsm_default, fsm_exc_off, fsm_exc_tok, fsm_exc_next, 0, 0, fsm_state, nullptr}, S, E, s);
+}
+
+int zl_spec_sample_accept_fsm(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
+                              const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
+                              const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
+                              int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
+                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
+                              const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits,
+                              int64_t bias_bits_ld, int top_n, int32_t* top_ids, float* top_logprobs, const uint32_t* fsm_mask,
+                              int64_t mask_ld, const int32_t* fsm_default, const int32_t* fsm_exc_off, const int32_t* fsm_exc_tok,
+                              const int32_t* fsm_exc_next, int64_t S, int64_t E, int32_t* fsm_state, int32_t* row_states, zl_stream_t s) {
+    return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
+                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, rep_penalty, presence, seen,
+                                     seen_ld, Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs},
+                                     Fsm{fsm_mask, mask_ld, fsm_default, fsm_exc_off, fsm_exc_tok, fsm_exc_next, 0, 0, fsm_state, row_states}, S, E,
                                      s);
 }
 

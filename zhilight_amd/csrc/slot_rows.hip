@@ -5,6 +5,9 @@
 //                    state on the host when the task enters the active batch (SearcherImplV1, src/generator/batch_generator.cpp) and
 //                    seeds its first token in fill_search_tokens; here the states live on the device under a captured step, so their
 //                    rows are rewritten where they are.  A record without a request parks the slot (token 0, position 0, one key).
+//   zl_slots_admit_fsm   the same with the sampler's token-automaton state: header flag 16 says that header word 12 points at an (n, 2)
+//                    array of (start state, pending-token override) per record; an admitted slot's fsm_state row takes the start
+//                    state, and an override >= 0 replaces the pending token wherever the rule above uses it.  A parked slot: -1.
 // Exact integer / bit work: one 256-thread workgroup per record.  The bitmap rows (16 KB each at 128 256 ids) are built in LDS with LDS
 // atomics and leave with 16-byte stores; everything else is a handful of dword stores.  No global atomics, no workspace; rows of slots
 // that are not in the blob are neither read-modified nor written (workgroup 0 READS their `finished` entries to recount `live`).
@@ -47,6 +50,7 @@ struct SlotArgs {
     int32_t* history;
     int64_t cap;
     int32_t *hist_lens, *draft_new;
+    int32_t* fsm_state;
 };
 
 // row[0 .. ld) <- the bitmap of the ids[0 .. cnt) and of `extra` that lie in [0, vocab), 0 everywhere else: built piece by piece in lds
@@ -119,14 +123,26 @@ __global__ __launch_bounds__(kThreads) void k_slots_admit(const SlotArgs a) {
                 a.last_token[s] = 0;
                 a.emit_lens[s] = 0;
             }
+            if (a.fsm_state) a.fsm_state[s] = -1;
         }
         if (a.tail && tid < kTail) a.tail[(int64_t)s * kTail + tid] = -1;
         return;
     }
-    const int32_t pending = a.tokens[s];
     // the record's ranges of the variable part: inside the blob (header word 10 = its words), else read as empty
     const int64_t total = a.blob[10];
     auto inside = [&](int32_t off, int64_t cnt) { return off >= kHdr && cnt >= 0 && off + cnt <= total; };
+    // the grammar side array (flag 16, header word 12): this record's start state and pending-token override, -1 / -1 without one
+    int32_t start = -1, ovr = -1;
+    if (a.fsm_state && (a.blob[3] & 16) && inside(a.blob[12], 2 * (int64_t)a.n)) {
+        start = a.blob[a.blob[12] + 2 * (int64_t)blockIdx.x];
+        ovr = a.blob[a.blob[12] + 2 * (int64_t)blockIdx.x + 1];
+    }
+    const bool over = ovr >= 0 && ovr < a.vocab;
+    const int32_t pending = over ? ovr : a.tokens[s];                 // tokens[s] is rewritten with the same value below
+    if (tid == 0) {
+        if (over) a.tokens[s] = pending;
+        if (a.fsm_state) a.fsm_state[s] = start;
+    }
     const int pen_cnt = inside(r[10], r[11]) ? r[11] : 0;
     const int bias_n = inside(r[12], 2 * (int64_t)r[13]) ? r[13] : 0;
     const int hist_n = inside(r[14], r[15]) ? r[15] : 0;
@@ -191,17 +207,15 @@ __global__ __launch_bounds__(kThreads) void k_slots_admit(const SlotArgs a) {
     }
     if (a.draft_new && tid == 0) a.draft_new[s] = pending;
 }
-}  // namespace
-
-extern "C" {
-
-int zl_slots_admit(const int32_t* blob, int64_t n, int64_t rec_words, int64_t b, int64_t vocab, int32_t* tokens, int32_t* positions,
+// the checks and the launch of both entry points; fsm_state == NULL: zl_slots_admit
+int slots_admit_launch(const int32_t* blob, int64_t n, int64_t rec_words, int64_t b, int64_t vocab, int32_t* tokens, int32_t* positions,
                    int32_t* placement, int32_t* valid_lens, float* temperature, int32_t* top_k, float* top_p, int64_t* seeds, int64_t* draws,
                    float* logprobs, float* u, float* rep_penalty, float* presence, int32_t* seen, int64_t seen_ld, int32_t* bias_ids,
                    float* bias_vals, int32_t* bias_cnt, int32_t* bias_bits, int64_t bias_ld, int64_t bits_ld, int32_t* top_ids,
                    float* top_logprobs, int64_t top_n, int32_t* stop_ids, int32_t* stop_seqs, int32_t* seq_lens, int64_t n_ids, int64_t n_seqs,
                    int64_t seq_ld, int32_t* max_new, int32_t* gen_lens, int32_t* tail, int32_t* last_token, int32_t* finished,
-                   int32_t* emit_lens, int32_t* live, int32_t* history, int64_t cap, int32_t* hist_lens, int32_t* draft_new, zl_stream_t s) {
+                   int32_t* emit_lens, int32_t* live, int32_t* history, int64_t cap, int32_t* hist_lens, int32_t* draft_new,
+                   int32_t* fsm_state, zl_stream_t s) {
     ZL_CHECK_ARG(blob && tokens && positions && placement && valid_lens && n >= 1 && b >= 1 && vocab >= 1, ZL_EINVAL);
     const bool sampler = temperature != nullptr;
     ZL_CHECK_ARG(sampler == (top_k != nullptr) && sampler == (top_p != nullptr) && sampler == (seeds != nullptr) &&
@@ -236,8 +250,41 @@ int zl_slots_admit(const int32_t* blob, int64_t n, int64_t rec_words, int64_t b,
     a.max_new = max_new, a.gen_lens = gen_lens, a.tail = tail, a.last_token = last_token, a.finished = finished;
     a.emit_lens = emit_lens, a.live = live;
     a.history = history, a.cap = cap, a.hist_lens = hist_lens, a.draft_new = draft_new;
+    a.fsm_state = fsm_state;
     hipLaunchKernelGGL(k_slots_admit, dim3((unsigned)n), dim3(kThreads), 0, (hipStream_t)s, a);
     return zl_launch_status();
 }
+
+}  // namespace
+
+extern "C" {
+
+#define ZL_SLOT_ARGS                                                                                                                       \
+    blob, n, rec_words, b, vocab, tokens, positions, placement, valid_lens, temperature, top_k, top_p, seeds, draws, logprobs, u, rep_penalty, \
+        presence, seen, seen_ld, bias_ids, bias_vals, bias_cnt, bias_bits, bias_ld, bits_ld, top_ids, top_logprobs, top_n, stop_ids, stop_seqs,   \
+        seq_lens, n_ids, n_seqs, seq_ld, max_new, gen_lens, tail, last_token, finished, emit_lens, live, history, cap, hist_lens, draft_new
+
+int zl_slots_admit(const int32_t* blob, int64_t n, int64_t rec_words, int64_t b, int64_t vocab, int32_t* tokens, int32_t* positions,
+                   int32_t* placement, int32_t* valid_lens, float* temperature, int32_t* top_k, float* top_p, int64_t* seeds, int64_t* draws,
+                   float* logprobs, float* u, float* rep_penalty, float* presence, int32_t* seen, int64_t seen_ld, int32_t* bias_ids,
+                   float* bias_vals, int32_t* bias_cnt, int32_t* bias_bits, int64_t bias_ld, int64_t bits_ld, int32_t* top_ids,
+                   float* top_logprobs, int64_t top_n, int32_t* stop_ids, int32_t* stop_seqs, int32_t* seq_lens, int64_t n_ids, int64_t n_seqs,
+                   int64_t seq_ld, int32_t* max_new, int32_t* gen_lens, int32_t* tail, int32_t* last_token, int32_t* finished,
+                   int32_t* emit_lens, int32_t* live, int32_t* history, int64_t cap, int32_t* hist_lens, int32_t* draft_new, zl_stream_t s) {
+    return slots_admit_launch(ZL_SLOT_ARGS, nullptr, s);
+}
+
+int zl_slots_admit_fsm(const int32_t* blob, int64_t n, int64_t rec_words, int64_t b, int64_t vocab, int32_t* tokens, int32_t* positions,
+                       int32_t* placement, int32_t* valid_lens, float* temperature, int32_t* top_k, float* top_p, int64_t* seeds,
+                       int64_t* draws, float* logprobs, float* u, float* rep_penalty, float* presence, int32_t* seen, int64_t seen_ld,
+                       int32_t* bias_ids, float* bias_vals, int32_t* bias_cnt, int32_t* bias_bits, int64_t bias_ld, int64_t bits_ld,
+                       int32_t* top_ids, float* top_logprobs, int64_t top_n, int32_t* stop_ids, int32_t* stop_seqs, int32_t* seq_lens,
+                       int64_t n_ids, int64_t n_seqs, int64_t seq_ld, int32_t* max_new, int32_t* gen_lens, int32_t* tail, int32_t* last_token,
+                       int32_t* finished, int32_t* emit_lens, int32_t* live, int32_t* history, int64_t cap, int32_t* hist_lens,
+                       int32_t* draft_new, int32_t* fsm_state, zl_stream_t s) {
+    ZL_CHECK_ARG(!fsm_state || temperature, ZL_EINVAL);                 // the state belongs to a sampler
+    return slots_admit_launch(ZL_SLOT_ARGS, fsm_state, s);
+}
+#undef ZL_SLOT_ARGS
 
 }  // extern "C"

@@ -1007,14 +1007,24 @@ class SamplerState:
     row_top_ids: Optional[torch.Tensor] = None
     row_top_logprobs: Optional[torch.Tensor] = None
     row_top_bufs: Optional[Dict[int, tuple]] = None
+    # the token automaton inside the sampling launch (new_sampler's grammar_states / grammar_edges / grammar): fsm = the five tables of
+    # ops.sample_advance's fsm=, allocated ONCE at that capacity and shared by the tasks -- LLaMA.load_grammar copies automata into their
+    # free tail, the pointers never change -- and fsm_state, a task's state in them (outside [0, capacity): unconstrained).  None = off
+    fsm: Optional[tuple] = None                         # mask (S, ceil(vocab / 32)), default (S), exc_off (S + 1), exc_tok (E), exc_next (E) int32
+    fsm_state: Optional[torch.Tensor] = None            # (B) int32
+    fsm_used: Optional[list] = None                     # [states, exception entries] that load_grammar has given out
+    row_states: Optional[torch.Tensor] = None           # verify(sampler=...): (B, len_q) int32, the state behind every row's pick
+    row_state_bufs: Optional[Dict[int, torch.Tensor]] = None
 
     def opts(self):
-        """the bias / top-N keyword arguments of ops.sample_advance: none at all with both options off"""
+        """the bias / top-N / automaton keyword arguments of ops.sample_advance: none at all with the options off"""
         kw = {}
         if self.bias_ids is not None:
             kw["bias"] = (self.bias_ids, self.bias_vals, self.bias_cnt, self.bias_bits)
         if self.top_n:
             kw.update(top_n=self.top_n, top_ids=self.top_ids, top_logprobs=self.top_logprobs)
+        if self.fsm is not None:
+            kw.update(fsm=self.fsm, fsm_state=self.fsm_state)
         return kw
 
 
@@ -2179,6 +2189,14 @@ class LLaMA:
                     raise ops.ZLError("verify: run one eager call with this sampler before capturing (it allocates the row results)")
                 sampler.row_bufs[len_q] = tuple(torch.full((b, len_q), float("nan"), dtype=torch.float32, device=dev) for _ in range(2))
             sampler.row_logprobs, sampler.row_u = sampler.row_bufs[len_q]
+            if sampler.fsm is not None:
+                if sampler.row_state_bufs is None:
+                    sampler.row_state_bufs = {}
+                if len_q not in sampler.row_state_bufs:
+                    if capturing:
+                        raise ops.ZLError("verify: run one eager call with this sampler before capturing (it allocates the row results)")
+                    sampler.row_state_bufs[len_q] = torch.full((b, len_q), -1, dtype=torch.int32, device=dev)
+                sampler.row_states = sampler.row_state_bufs[len_q]
             if sampler.top_n:
                 if sampler.row_top_bufs is None:
                     sampler.row_top_bufs = {}
@@ -2216,6 +2234,8 @@ class LLaMA:
             opts = sampler.opts()                                           # the task's bias; the rows' top-N into the row buffers
             if sampler.top_n:
                 opts.update(top_ids=sampler.row_top_ids, top_logprobs=sampler.row_top_logprobs)
+            if sampler.fsm is not None:                                     # the task's state walks over the drafts in front of a row
+                opts.update(row_states=sampler.row_states)
             ops.spec_sample_accept(logits, drafts, sampler.temperature, sampler.top_k, sampler.top_p, seeds=sampler.seeds, draws=sampler.draws,
                                    tokens=ctx.tokens, positions=ctx.positions, placement=ctx.placement, valid_lens=ctx.valid_lens,
                                    accepted=accepted, out_tokens=out_tokens, out_logprobs=sampler.row_logprobs, logprobs=sampler.logprobs,
@@ -2339,7 +2359,8 @@ class LLaMA:
 
     # ---- sampling steps -----------------------------------------------------------------------------
     def new_sampler(self, ctx: DynBatchContext, temperature=1.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0, presence_penalty=0.0,
-                    penalty_tokens=None, logit_bias=None, top_logprobs=0, penalties=False, bias_ld=0) -> SamplerState:
+                    penalty_tokens=None, logit_bias=None, top_logprobs=0, penalties=False, bias_ld=0, grammar_states=0, grammar_edges=0,
+                    grammar=None) -> SamplerState:
         """The state for step_sample.  temperature / top_k / top_p / seed: a scalar for every task or a sequence of B values.
         temperature 0 = greedy; top_k 0 = off; top_p 1 = off; a scalar seed s gives task j the seed s + j, so the tasks draw different
         streams and a task's stream does not depend on the rest of the batch.
@@ -2355,8 +2376,27 @@ class LLaMA:
         the calls are the ones without them.
         penalties=True / bias_ld=N (1 .. 1024): carry the bitmap / bias rows of width N whatever the tasks ask for now, so that later
         requests may use them (LLaMA.admit rewrites a slot's rows in place and cannot widen a state).  bias_ld below the longest map
-        raises.  The defaults (False, 0) build exactly the states of before."""
+        raises.  The defaults (False, 0) build exactly the states of before.
+        grammar_states = S / grammar_edges = E: carry the tables of a token automaton (zhilight_amd.grammar) of S states and E exception
+        entries in all, shared by the tasks, with every task unconstrained (state -1); load_grammar copies automata into them and
+        returns the start state a request names (LLaMA.admit's "grammar").  Every sampling step then masks a constrained task's row by
+        its state's allow-bitmap and advances the state over the pick, inside the sampling launch.  grammar = [automaton | None per
+        task]: the convenience without a server -- the tables are sized for the distinct automata (or at the given capacities) and
+        task j starts in its automaton's start state.  NOTE the pending ctx.tokens entry is not constrained: it is the prompt
+        encode's pick (LLaMA.admit with a "grammar" request re-feeds the prompt's last token instead, so that the first generated
+        token is drawn under the grammar).  Without the three arguments the state carries no tables."""
         b, dev = ctx.tokens.numel(), ctx.tokens.device
+        if grammar is not None:
+            grammar = list(grammar)
+            if len(grammar) != b:
+                raise ops.ZLError(f"new_sampler: {b} tasks, {len(grammar)} entries of grammar")
+            distinct = list({id(g): g for g in grammar if g is not None}.values())
+            packs = {id(g): g.pack() for g in distinct}
+            grammar_states = int(grammar_states) or max(1, sum(g.states for g in distinct))
+            grammar_edges = int(grammar_edges) or sum(int(pk.exc_tok.size) for pk in packs.values())
+        grammar_states, grammar_edges = int(grammar_states), int(grammar_edges)
+        if not (0 <= grammar_states < 1 << 31 and 0 <= grammar_edges < 1 << 31) or (grammar_edges and not grammar_states):
+            raise ops.ZLError("new_sampler: 0 <= grammar_states, grammar_edges < 2^31, and edges only with states")
         bias_ld = int(bias_ld)
         if not 0 <= bias_ld <= ops.LOGIT_BIAS_MAX:
             raise ops.ZLError(f"new_sampler: bias_ld in 0 .. {ops.LOGIT_BIAS_MAX}")
@@ -2431,11 +2471,63 @@ class LLaMA:
         if int(top_logprobs):
             pen.update(top_n=int(top_logprobs), top_ids=torch.full((b, int(top_logprobs)), -1, dtype=torch.int32, device=dev),
                        top_logprobs=torch.full((b, int(top_logprobs)), float("nan"), dtype=torch.float32, device=dev))
-        return SamplerState(**pen, temperature=torch.tensor([float(v) for v in t], dtype=torch.float32, device=dev),
-                            top_k=torch.tensor([int(v) for v in k], dtype=torch.int32, device=dev),
-                            top_p=torch.tensor([float(v) for v in p], dtype=torch.float32, device=dev),
-                            seeds=torch.tensor(sd, dtype=torch.int64, device=dev), draws=torch.zeros(b, dtype=torch.int64, device=dev),
-                            logprobs=torch.zeros(b, dtype=torch.float32, device=dev), u=torch.zeros(b, dtype=torch.float32, device=dev))
+        if grammar_states:
+            i32 = dict(dtype=torch.int32, device=dev)
+            # an unused state allows nothing and leads nowhere; the exception arrays hold one entry at least (never read while empty)
+            pen.update(fsm=(torch.zeros((grammar_states, ops.seen_words(self.cfg.vocab_size)), **i32), torch.full((grammar_states,), -1, **i32),
+                            torch.zeros(grammar_states + 1, **i32), torch.zeros(max(1, grammar_edges), **i32),
+                            torch.full((max(1, grammar_edges),), -1, **i32)),
+                       fsm_state=torch.full((b,), -1, **i32), fsm_used=[0, 0])
+        state = SamplerState(**pen, temperature=torch.tensor([float(v) for v in t], dtype=torch.float32, device=dev),
+                             top_k=torch.tensor([int(v) for v in k], dtype=torch.int32, device=dev),
+                             top_p=torch.tensor([float(v) for v in p], dtype=torch.float32, device=dev),
+                             seeds=torch.tensor(sd, dtype=torch.int64, device=dev), draws=torch.zeros(b, dtype=torch.int64, device=dev),
+                             logprobs=torch.zeros(b, dtype=torch.float32, device=dev), u=torch.zeros(b, dtype=torch.float32, device=dev))
+        if grammar is not None and distinct:
+            starts = {id(g): self.load_grammar(state, g, packed=packs[id(g)]) for g in distinct}
+            state.fsm_state.copy_(torch.tensor([-1 if g is None else starts[id(g)] for g in grammar], dtype=torch.int32))
+        return state
+
+    def load_grammar(self, sampler: SamplerState, automaton, packed=None) -> int:
+        """Copy a grammar.TokenAutomaton into the free tail of the sampler's automaton tables (new_sampler's grammar_states /
+        grammar_edges), its state numbers rebased, and return its start state there: the handle a request's "grammar" names
+        (LLaMA.admit) and the value fsm_state takes.  Plain copies into tensors whose pointers and shapes never change: a graph
+        captured over the steps goes on reading them, so a grammar may be loaded between replays.  ZLError: a sampler without tables,
+        an automaton over more ids than the model's vocabulary, tables that are full (clear_grammars empties them)."""
+        if not isinstance(sampler, SamplerState) or sampler.fsm is None:
+            raise ops.ZLError("load_grammar: the sampler carries no automaton tables (new_sampler's grammar_states)")
+        vocab = self.cfg.vocab_size
+        if getattr(automaton, "vocab", vocab + 1) > vocab:
+            raise ops.ZLError(f"load_grammar: a grammar.TokenAutomaton over at most the model's {vocab} ids")
+        mask, default, exc_off, exc_tok, exc_next = packed if packed is not None else automaton.pack()
+        d_mask, d_default, d_off, d_tok, d_next = sampler.fsm
+        base, ebase = sampler.fsm_used
+        ns, ne = int(default.size), int(exc_tok.size)
+        if base + ns > d_default.numel() or ebase + ne > (d_tok.numel() if ebase + ne else 0):
+            raise ops.ZLError(f"load_grammar: the tables are full ({base} + {ns} of {d_default.numel()} states, {ebase} + {ne} exception "
+                              "entries): size them with new_sampler's grammar_states / grammar_edges, or clear_grammars")
+        rows = np.zeros((ns, d_mask.shape[1]), np.uint32)
+        rows[:, :mask.shape[1]] = mask
+        shift = lambda a: np.where(a >= 0, a.astype(np.int64) + base, a).astype(np.int32)                 # noqa: E731
+        dev = d_mask.device
+        d_mask[base:base + ns].copy_(torch.from_numpy(rows.view(np.int32)).to(dev))
+        d_default[base:base + ns].copy_(torch.from_numpy(shift(default)).to(dev))
+        d_off[base:base + ns + 1].copy_(torch.from_numpy((exc_off.astype(np.int64) + ebase).astype(np.int32)).to(dev))
+        d_off[base + ns:].fill_(ebase + ne)                                 # the states behind it own empty lists
+        if ne:
+            d_tok[ebase:ebase + ne].copy_(torch.from_numpy(np.ascontiguousarray(exc_tok)).to(dev))
+            d_next[ebase:ebase + ne].copy_(torch.from_numpy(shift(exc_next)).to(dev))
+        sampler.fsm_used = [base + ns, ebase + ne]
+        return base + int(automaton.start)
+
+    def clear_grammars(self, sampler: SamplerState):
+        """Forget every loaded grammar: the next load_grammar starts at state 0.  Refused while any task is constrained (one read-back
+        of fsm_state): its state would name another grammar's rows."""
+        if not isinstance(sampler, SamplerState) or sampler.fsm is None:
+            raise ops.ZLError("clear_grammars: the sampler carries no automaton tables")
+        if bool((sampler.fsm_state >= 0).any()):
+            raise ops.ZLError("clear_grammars: a task is still inside a grammar (fsm_state >= 0)")
+        sampler.fsm_used = [0, 0]
 
     def new_stopper(self, ctx: DynBatchContext, stop_ids=None, stop_sequences=None, max_new_tokens=0, widths=None) -> StopState:
         """The state for the stop= keyword of step_greedy / step_sample / verify / step_lookup and the generate loops.  stop_ids: ids that
@@ -2572,7 +2664,8 @@ class LLaMA:
                                bias_ld=sampler.bias_ids.shape[1] if sampler is not None and sampler.bias_ids is not None else 0,
                                n_ids=stop.stop_ids.shape[1] if stop is not None else 0, n_seqs=stop.stop_seqs.shape[1] if stop is not None else 0,
                                seq_ld=stop.stop_seqs.shape[2] if stop is not None else 0,
-                               hist_cap=lookup.history.shape[1] if lookup is not None else 0)
+                               hist_cap=lookup.history.shape[1] if lookup is not None else 0,
+                               grammar=sampler is not None and sampler.fsm is not None)
 
     def _slot_states(self, what, ctx, sampler, stop, lookup):
         b = ctx.tokens.numel()
@@ -2636,15 +2729,32 @@ class LLaMA:
         caller's to bound.
         Refused before any launch, with nothing changed: what prefill_batch / prefill_cached refuse, tensor parallelism, lookup on an
         INT8 cache, states of another batch size, what ops.slots_pack refuses, and (with a stop state) a prompt that leaves no room
-        for one generated token."""
+        for one generated token.
+        A request with "grammar" (load_grammar's handle; the sampler carries the tables): the slot's first generated token must obey
+        the grammar too, so the prompt is encoded WITHOUT its last token, which becomes the slot's pending token in the prompt pick's
+        place; the first step then draws the first token under sampler and grammar.  Such a slot's prompt counts as len - 1 for the
+        length limit and the guard, the returned logits row is that of prompt[:-1], the default history is prompt[:-1] (the pending
+        token enters it through the drafter's append, which makes it the full prompt), and a 1-token prompt is refused."""
         b = self._slot_states("admit", ctx, sampler, stop, lookup)
+        prompts = list(prompts)
+        requests = [dict(rq or {}) for rq in requests]
+        for j, rq in enumerate(requests if len(requests) == len(prompts) else []):      # a count that is off is refused below
+            if rq.get("grammar") is not None:
+                pr = torch.as_tensor(prompts[j]).reshape(-1)
+                g = rq["grammar"]
+                if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+                    raise ops.ZLError("admit: grammar is load_grammar's start state")
+                if sampler.fsm is None or not 0 <= int(g) < sampler.fsm_used[0]:
+                    raise ops.ZLError("admit: grammar names no loaded automaton of this sampler")
+                if pr.numel() < 2:
+                    raise ops.ZLError("admit: a request with a grammar needs a prompt of 2 tokens at least (the last one is re-fed)")
+                prompts[j], rq["grammar"] = pr[:-1], (int(g), int(pr[-1]))
         slots, _, _ = self._check_prompt_batch("admit", ctx, slots, prompts, None, kv_history)
         if len(requests) != len(slots):
             raise ops.ZLError("admit: one request per slot")
         k = lookup.k if lookup is not None else 0
         entries, guards = [], {}
         for s, pr, rq in zip(slots, prompts, requests):
-            rq = dict(rq or {})
             n = int(pr.numel())
             if stop is not None:
                 raw = rq.get("max_new_tokens", 0)

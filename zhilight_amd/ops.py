@@ -1122,14 +1122,15 @@ SLOT_MAGIC = 0x534C4F54    # "SLOT"
 SLOT_HDR = 16              # header words of the blob
 SLOT_REC = 16              # fixed words of a record; the slot's stop rows follow them
 SLOT_REQUEST_KEYS = ("temperature", "top_k", "top_p", "seed", "repetition_penalty", "presence_penalty", "penalty_tokens", "logit_bias",
-                     "stop_ids", "stop_sequences", "max_new_tokens", "history")
+                     "stop_ids", "stop_sequences", "max_new_tokens", "history", "grammar")
 
 
-def slot_widths(penalties=False, bias_ld=0, n_ids=0, n_seqs=0, seq_ld=0, hist_cap=0):
+def slot_widths(penalties=False, bias_ld=0, n_ids=0, n_seqs=0, seq_ld=0, hist_cap=0, grammar=False):
     """What the states of a batch carry, as slots_pack needs it: penalties = the sampler has a bitmap; bias_ld = the width of its bias
     rows, 0 = no bias; n_ids / n_seqs / seq_ld = the stop state's widths, all 0 = no stop state; hist_cap = ids a lookup history row
-    holds, 0 = no drafter."""
-    w = dict(penalties=bool(penalties), bias_ld=int(bias_ld), n_ids=int(n_ids), n_seqs=int(n_seqs), seq_ld=int(seq_ld), hist_cap=int(hist_cap))
+    holds, 0 = no drafter; grammar = the sampler carries a token-automaton state."""
+    w = dict(penalties=bool(penalties), bias_ld=int(bias_ld), n_ids=int(n_ids), n_seqs=int(n_seqs), seq_ld=int(seq_ld), hist_cap=int(hist_cap),
+             grammar=bool(grammar))
     stop = (w["n_ids"], w["n_seqs"], w["seq_ld"])
     if not 0 <= w["bias_ld"] <= LOGIT_BIAS_MAX:
         raise ZLError(f"slots_pack: bias_ld in 0 .. {LOGIT_BIAS_MAX}")
@@ -1163,7 +1164,12 @@ def slots_pack(entries, vocab, widths):
     bias_ld, n_ids, n_seqs, seq_ld, rec, var, total, hist_cap).  The checks are new_sampler's, new_stopper's and new_lookup's, raised as
     ZLError before anything is launched; a request that uses an option the states do not carry is refused: penalties without a bitmap,
     a bias without bias rows or with more ids than bias_ld, stop conditions without a stop state or beyond its widths, a history
-    without a drafter or longer than hist_cap - 1.  Slots are distinct and >= 0 (slots_admit checks them against the batch)."""
+    without a drafter or longer than hist_cap - 1, a grammar without an automaton state.  Slots are distinct and >= 0 (slots_admit
+    checks them against the batch).
+    "grammar": the slot's start state in the sampler's automaton tables (LLaMA.load_grammar's handle), or a (start state, pending token)
+    pair whose second entry replaces the slot's pending token at admission (LLaMA.admit gives the prompt's last id: the first
+    generated token is then drawn under the grammar).  Only a blob with such a request carries header flag 16 and the (n, 2) side array
+    at the word offset of header word 12; without one the blob is what it always was."""
     vocab = int(vocab)
     if vocab < 1 or vocab >= 1 << 31:
         raise ZLError("slots_pack: 1 <= vocab < 2^31")
@@ -1174,6 +1180,8 @@ def slots_pack(entries, vocab, widths):
     has_stop = w["n_ids"] > 0
     rec = SLOT_REC + w["n_ids"] + w["n_seqs"] + w["n_seqs"] * w["seq_ld"]
     recs, var, slots = [], [], []
+    gram = np.full((len(entries), 2), -1, np.int32)                         # (start state, pending-token override) per record
+    any_gram = False
     off = SLOT_HDR + len(entries) * rec
 
     def ints(v):
@@ -1284,11 +1292,30 @@ def slots_pack(entries, vocab, widths):
         r[14], r[15] = off, hist.size
         var.append(hist)
         off += hist.size
+        g = req.get("grammar")
+        if g is not None:
+            if not w["grammar"]:
+                raise ZLError(f"slots_pack: slot {s}: a grammar, but the sampler state has no automaton")
+            g = (g, -1) if ints(g) else g
+            if not (isinstance(g, (tuple, list)) and len(g) == 2 and ints(g[0]) and (g[1] is None or ints(g[1]))):
+                raise ZLError(f"slots_pack: slot {s}: grammar is a start state or a (start state, pending token) pair")
+            st, pend = int(g[0]), -1 if g[1] is None else int(g[1])
+            if not 0 <= st < 1 << 31 or not -1 <= pend < vocab:
+                raise ZLError(f"slots_pack: slot {s}: grammar: a start state >= 0 and a pending token in [0, {vocab}) or -1")
+            gram[len(recs)] = (st, pend)
+            any_gram = True
         recs.append(r)
+    gram_off = 0
+    if any_gram:
+        gram_off = off
+        var.append(gram.reshape(-1))
+        off += gram.size
     if off >= 1 << 31:
         raise ZLError("slots_pack: the blob holds fewer than 2^31 words")
-    flags = (1 if w["penalties"] else 0) | (2 if w["bias_ld"] else 0) | (4 if has_stop else 0) | (8 if w["hist_cap"] else 0)
+    flags = ((1 if w["penalties"] else 0) | (2 if w["bias_ld"] else 0) | (4 if has_stop else 0) | (8 if w["hist_cap"] else 0)
+             | (16 if any_gram else 0))
     hdr = np.zeros(SLOT_HDR, np.int32)
+    hdr[12] = gram_off
     hdr[:12] = [SLOT_MAGIC, len(entries), vocab, flags, w["bias_ld"], w["n_ids"], w["n_seqs"], w["seq_ld"], rec,
                 SLOT_HDR + len(entries) * rec, off, w["hist_cap"]]
     blob = np.ascontiguousarray(np.concatenate([hdr] + recs + [np.asarray(v, np.int32) for v in var]))
@@ -1306,6 +1333,10 @@ def slots_header(blob):
             or h["var"] != SLOT_HDR + h["n"] * h["rec"] or h["var"] > h["total"]
             or h["rec"] != SLOT_REC + h["n_ids"] + h["n_seqs"] + h["n_seqs"] * h["seq_ld"]):
         raise ZLError("slots_admit: the blob is slots_pack's contiguous int32 array")
+    if h["flags"] & 16:                                                     # the (n, 2) grammar side array
+        h["grammar"] = int(blob[12])
+        if not h["var"] <= h["grammar"] <= h["total"] - 2 * h["n"]:
+            raise ZLError("slots_admit: the blob is slots_pack's contiguous int32 array")
     return h
 
 
@@ -1322,6 +1353,8 @@ def slots_admit(blob, tokens, positions, placement, valid_lens, sampler=None, st
     left.  sampler / stop / lookup: objects with LLaMA's SamplerState / StopState / LookupState fields (None = that group is skipped);
     their optional tensors and widths must be those the blob was packed for (ZLError otherwise, and for slots outside [0, B)).
     draft_new (B) int32, optional: receives the drafter's new_tokens column (pending for admitted slots, -1 elsewhere).
+    A sampler that carries an automaton state (fsm_state (B) int32) goes through zl_slots_admit_fsm: an admitted slot's state <- its
+    request's start state (-1 without a grammar), a (start, pending) grammar also replaces the pending token, a parked slot's <- -1.
     parked_ok: the slots the caller knows to be finished; parking any other slot is refused.  The rule: include/zhilight_amd.h."""
     dev_blob = None
     if isinstance(blob, (tuple, list)):
@@ -1411,12 +1444,21 @@ def slots_admit(blob, tokens, positions, placement, valid_lens, sampler=None, st
         args += [None, 0, None]
     if draft_new is not None:
         chk(draft_new, (b,), i32, "draft_new")
+    fsm_state = getattr(sm, "fsm_state", None) if sm is not None else None
+    if fsm_state is None and h["flags"] & 16:
+        raise ZLError("slots_admit: the blob carries grammar requests, the sampler state has no automaton")
+    if fsm_state is not None:
+        chk(fsm_state, (b,), i32, "fsm_state")
     if dev_blob is None:
         dev_blob = torch.from_numpy(blob).to(dev)
     elif not (torch.is_tensor(dev_blob) and dev_blob.dtype == i32 and dev_blob.numel() == blob.size and dev_blob.is_contiguous()
               and dev_blob.device == dev):
         raise ZLError("slots_admit: the uploaded blob is the int32 tensor of the numpy blob, on the tokens' device")
     cargs = [_i(v) if isinstance(v, int) else _p(v) for v in args]
+    if fsm_state is not None:
+        check(lib().zl_slots_admit_fsm(_p(dev_blob), _i(h["n"]), _i(h["rec"]), _i(b), _i(h["vocab"]), _p(tokens), _p(positions), _p(placement),
+                                       _p(valid_lens), *cargs, _p(draft_new), _p(fsm_state), _stream()), "slots_admit")
+        return dev_blob
     check(lib().zl_slots_admit(_p(dev_blob), _i(h["n"]), _i(h["rec"]), _i(b), _i(h["vocab"]), _p(tokens), _p(positions), _p(placement),
                                _p(valid_lens), *cargs, _p(draft_new), _stream()), "slots_admit")
     return dev_blob
@@ -1456,9 +1498,38 @@ def _opts_args(what, count, top_shape, n, device, bias, top_n, top_ids, top_logp
     return args + [C.c_int(0), _p(None), _p(None)]
 
 
+def grammar_tables(packed, device):
+    """grammar.TokenAutomaton.pack()'s five arrays as the `fsm` tuple of sample_advance / spec_sample_accept: int32 tensors on the device
+    (the bitmap's uint32 words viewed as int32, as seen)"""
+    mask, default, exc_off, exc_tok, exc_next = packed
+    return (torch.from_numpy(np.ascontiguousarray(mask).view(np.int32)).to(device), torch.from_numpy(np.ascontiguousarray(default)).to(device),
+            torch.from_numpy(np.ascontiguousarray(exc_off)).to(device), torch.from_numpy(np.ascontiguousarray(exc_tok)).to(device),
+            torch.from_numpy(np.ascontiguousarray(exc_next)).to(device))
+
+
+def _fsm_args(what, count, n, device, fsm, fsm_state):
+    """The checks of (fsm, fsm_state) of sample_advance / spec_sample_accept -> zl_*_fsm's nine C arguments behind the _opts ones."""
+    if not (isinstance(fsm, (tuple, list)) and len(fsm) == 5 and all(torch.is_tensor(t) and t.dtype == torch.int32 and t.is_contiguous()
+                                                                     for t in fsm)):
+        raise ZLError(f"{what}: fsm is (mask, default, exc_off, exc_tok, exc_next), contiguous int32 tensors (grammar_tables)")
+    mask, default, exc_off, exc_tok, exc_next = fsm
+    if not (mask.dim() == 2 and default.dim() == 1 and exc_off.dim() == 1 and exc_tok.dim() == 1 and exc_next.dim() == 1
+            and mask.shape[0] >= 1 and default.numel() == mask.shape[0] and exc_off.numel() == mask.shape[0] + 1
+            and exc_next.numel() == exc_tok.numel() and mask.shape[1] >= seen_words(n)):
+        raise ZLError(f"{what}: fsm: mask (S, >= ceil(n / 32)), default (S), exc_off (S + 1), exc_tok / exc_next (E)")
+    if not (torch.is_tensor(fsm_state) and fsm_state.dtype == torch.int32 and fsm_state.dim() == 1 and fsm_state.numel() == count
+            and fsm_state.is_contiguous()):
+        raise ZLError(f"{what}: fsm_state: contiguous int32 of length {count}, given with fsm")
+    if any(t.device != device for t in tuple(fsm) + (fsm_state,)):
+        raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
+    empty = exc_tok.numel() == 0                                            # no exception anywhere: the lists are never read
+    return [_p(mask), _i(mask.shape[1]), _p(default), _p(exc_off), _p(exc_off if empty else exc_tok), _p(exc_off if empty else exc_next),
+            _i(mask.shape[0]), _i(exc_tok.numel()), _p(fsm_state)]
+
+
 def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=None, tokens=None, positions=None, placement=None,
                    valid_lens=None, next_tokens=None, logprobs=None, u_out=None, rep_penalty=None, presence=None, seen=None,
-                   bias=None, top_n=0, top_ids=None, top_logprobs=None):
+                   bias=None, top_n=0, top_ids=None, top_logprobs=None, fsm=None, fsm_state=None):
     """The stochastic pick over whole logit rows and the batch state's advance in one launch (zl_sample_advance): logits (rows, n)
     fp16 / bf16 with unit column stride; temperature (rows) fp32, top_k (rows) int32 (<= 0 or >= n: off), top_p (rows) fp32 in [0, 1]
     -- per row.  A row with temperature <= 0 takes argmax_advance's pick; otherwise p = exp((x - max) / T), the classes ordered by p
@@ -1478,7 +1549,14 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
     logits in memory, and needs no seen.  top_n = N in 1 .. 32 with top_ids (rows, N) int32 / top_logprobs (rows, N) fp32: the first
     min(N, n) classes of the row AS THE PICK SAW IT, larger value first, then lower index, with their tempered log-probabilities
     (the pick's entry is bit-equal to logprobs); -1 / NaN behind n and on a row whose largest value is NaN or +-inf.  The same
-    results as repetition_penalty + scatter_logits(add=True) + this call without them, in the one launch."""
+    results as repetition_penalty + scatter_logits(add=True) + this call without them, in the one launch.
+    fsm = grammar_tables' five tensors with fsm_state (rows) int32: zl_sample_advance_fsm -- a row whose state s lies in [0, S) reads
+    every class whose bit is clear in mask[s] as -inf (in front of the penalty and the bias; the logits in memory stay), everything
+    above runs on that row, and fsm_state <- delta(s, pick): the exception's target where exc_tok[exc_off[s] : exc_off[s + 1]] holds the
+    pick, else default[s].  A state outside [0, S) leaves the row unconstrained and is not changed.  The same results as
+    masked_fill(-inf) on a copy + this call without fsm."""
+    if (fsm is None) != (fsm_state is None):
+        raise ZLError("sample_advance: fsm and fsm_state are given together")
     if not all(torch.is_tensor(t) for t in (logits, temperature, top_k, top_p)):
         raise ZLError("sample_advance: logits, temperature, top_k and top_p are tensors")
     if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
@@ -1520,6 +1598,14 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
         raise ZLError("sample_advance: CUDA logits, every other tensor on the logits' device")
     _penalty_args("sample_advance", rows, n, logits.device, rep_penalty, presence, seen)
     code = 2 if logits.dtype == torch.float16 else 6
+    if fsm is not None:
+        opts = _opts_args("sample_advance", rows, (rows,), n, logits.device, bias, top_n, top_ids, top_logprobs)
+        fargs = _fsm_args("sample_advance", rows, n, logits.device, fsm, fsm_state)
+        check(lib().zl_sample_advance_fsm(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k),
+                                          _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement), _p(valid_lens),
+                                          _p(next_tokens), _p(logprobs), _p(u_out), _p(rep_penalty), _p(presence), _p(seen),
+                                          _i(seen.shape[1] if seen is not None else 0), *opts, *fargs, _stream()), "sample_advance")
+        return next_tokens if next_tokens is not None else tokens
     if bias is not None or top_n != 0:
         opts = _opts_args("sample_advance", rows, (rows,), n, logits.device, bias, top_n, top_ids, top_logprobs)
         check(lib().zl_sample_advance_opts(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k),
@@ -1541,7 +1627,8 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
 
 def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, draws=None, u=None, tokens=None, positions=None,
                        placement=None, valid_lens=None, accepted=None, out_tokens=None, out_logprobs=None, logprobs=None, u_out=None,
-                       rep_penalty=None, presence=None, seen=None, bias=None, top_n=0, top_ids=None, top_logprobs=None):
+                       rep_penalty=None, presence=None, seen=None, bias=None, top_n=0, top_ids=None, top_logprobs=None, fsm=None,
+                       fsm_state=None, row_states=None):
     """The acceptance of a speculative step under sampling (zl_spec_sample_accept, two launches): spec_accept with sample_advance's
     pick in the arg-max's place.  logits (B * len_q, n) fp16 / bf16 rows, task-major, unit column stride; drafts (B, K) int32,
     len_q = K + 1 <= 32.  temperature / top_k / top_p / seeds / draws are per task (B); u, u_out and out_logprobs per row (B, len_q).
@@ -1558,7 +1645,12 @@ def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, dr
     the bits of the emitted tokens out_tokens[b, :accepted + 1] are set in seen[b]; the rejected drafts' are not.
     bias (logit_bias_pack's tuple, per task) / top_n with top_ids (B, K + 1, N) int32 and top_logprobs (B, K + 1, N) fp32:
     zl_spec_sample_accept_opts -- every row (b, i) is sample_advance(bias=, top_n=)'s under task b's bias (the drafts in front of a row
-    change its penalty set only), the rows behind the bonus token hold -1 / NaN."""
+    change its penalty set only), the rows behind the bonus token hold -1 / NaN.
+    fsm (grammar_tables' tensors) with fsm_state (B) int32 and row_states (B, K + 1) int32: zl_spec_sample_accept_fsm -- row (b, i) is
+    sample_advance(fsm=)'s under the state s_i, s_0 = fsm_state[b], s_{j+1} = delta(s_j, drafts[b, j]); row_states[b, i] <- delta(s_i,
+    picks[b, i]) and fsm_state[b] <- row_states[b, accepted[b]]: the state has moved over exactly the emitted tokens."""
+    if (fsm is None) != (fsm_state is None) or (fsm is None) != (row_states is None):
+        raise ZLError("spec_sample_accept: fsm, fsm_state and row_states are given together")
     if not all(torch.is_tensor(t) for t in (logits, drafts, temperature, top_k, top_p)):
         raise ZLError("spec_sample_accept: logits, drafts, temperature, top_k and top_p are tensors")
     if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
@@ -1615,6 +1707,19 @@ def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, dr
     if out_tokens is None:
         out_tokens = torch.empty((b, len_q), dtype=torch.int32, device=logits.device)
     code = 2 if logits.dtype == torch.float16 else 6
+    if fsm is not None:
+        per_row(row_states, torch.int32, "row_states")
+        if row_states.device != logits.device:
+            raise ZLError("spec_sample_accept: CUDA logits, every other tensor on the logits' device")
+        opts = _opts_args("spec_sample_accept", b, (b, len_q), n, logits.device, bias, top_n, top_ids, top_logprobs)
+        fargs = _fsm_args("spec_sample_accept", b, n, logits.device, fsm, fsm_state)
+        check(lib().zl_spec_sample_accept_fsm(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts),
+                                              _p(temperature), _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions),
+                                              _p(placement), _p(valid_lens), _p(accepted), _p(out_tokens), _p(out_logprobs), _p(logprobs),
+                                              _p(u_out), _p(rep_penalty), _p(presence), _p(seen),
+                                              _i(seen.shape[1] if seen is not None else 0), *opts, *fargs, _p(row_states), _stream()),
+              "spec_sample_accept")
+        return accepted, out_tokens.view(b, len_q)
     if bias is not None or top_n != 0:
         opts = _opts_args("spec_sample_accept", b, (b, len_q), n, logits.device, bias, top_n, top_ids, top_logprobs)
         check(lib().zl_spec_sample_accept_opts(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts),

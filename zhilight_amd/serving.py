@@ -21,11 +21,15 @@ class BatchServer:
     prefix_block_size)) and the prompts go through it; prefix_cache: a PrefixCache made elsewhere instead -- one cache may serve several
     servers -- which must fit this server's context (PrefixCache.fits: geometry, KV element type, device, stream); build it
     with LLaMA.new_prefix_cache from any context of the same model and KV cache type.  capture=True: the steps are replays of one graph
-    captured after the first eager step.  poll: steps between two read-backs.
+    captured after the first eager step.  poll: steps between two read-backs.  grammar_states = S / grammar_edges = E: the sampler carries
+    token-automaton tables of that capacity (LLaMA.new_sampler); load_grammar(automaton) copies a grammar.TokenAutomaton into them --
+    before run() or between two runs, the captured graph stays valid -- and returns the handle that submit(..., grammar=handle) names.
 
     submit(prompt, **request) -> id; request = ops.SLOT_REQUEST_KEYS (temperature, top_k, top_p, seed, repetition_penalty,
-    presence_penalty, penalty_tokens, logit_bias, stop_ids, stop_sequences, max_new_tokens, history).  A request is checked when it is
-    submitted, against the states' widths and the buffer's length.
+    presence_penalty, penalty_tokens, logit_bias, stop_ids, stop_sequences, max_new_tokens, history, grammar).  A request is checked when
+    it is submitted, against the states' widths and the buffer's length.  A request with a grammar needs a prompt of two tokens at
+    least: its last token is re-fed so that the first generated token is drawn under the grammar (LLaMA.admit); its first_token is None
+    and tokens holds every generated id.
 
     run() serves the queue until it and the batch are empty and returns {id: dict(tokens, logprobs, reason, round, first_token,
     clamped, [top_ids, top_logprobs])}: tokens = the ids emitted behind first_token (the greedy pick the prompt encode leaves
@@ -34,7 +38,7 @@ class BatchServer:
     ...]); self.matched = {id: tokens the prefix cache supplied}; self.stats counts steps and slot-steps."""
 
     def __init__(self, model, batch, len_buf, penalties=True, bias_ld=0, top_logprobs=0, lookup_k=0, prefix_cache=None, capture=False,
-                 poll=8, kv_history=None, prefix_blocks=0, prefix_block_size=128):
+                 poll=8, kv_history=None, prefix_blocks=0, prefix_block_size=128, grammar_states=0, grammar_edges=0):
         if int(poll) < 1 or int(batch) < 1:
             raise ops.ZLError("BatchServer: batch >= 1 and poll >= 1")
         self.model, self.b, self.len_buf, self.poll, self.capture = model, int(batch), int(len_buf), int(poll), bool(capture)
@@ -44,7 +48,8 @@ class BatchServer:
             if prefix_cache is not None:
                 raise ops.ZLError("BatchServer: prefix_blocks builds the cache, prefix_cache brings one: give one of them")
             self.cache = model.new_prefix_cache(ctx, int(prefix_blocks), int(prefix_block_size))
-        self.sampler = model.new_sampler(ctx, penalties=bool(penalties), bias_ld=int(bias_ld), top_logprobs=int(top_logprobs))
+        self.sampler = model.new_sampler(ctx, penalties=bool(penalties), bias_ld=int(bias_ld), top_logprobs=int(top_logprobs),
+                                         grammar_states=int(grammar_states), grammar_edges=int(grammar_edges))
         self.stop = model.new_stopper(ctx, widths=(ops.STOP_IDS_MAX, ops.STOP_SEQS_MAX, ops.STOP_SEQ_LEN_MAX))
         self.lookup = model.new_lookup(ctx, [[] for _ in range(self.b)], int(lookup_k)) if int(lookup_k) else None
         self.k = int(lookup_k)
@@ -71,11 +76,23 @@ class BatchServer:
         self.top = top
 
     # ---- the queue --------------------------------------------------------------------------------------------------------------
+    def load_grammar(self, automaton):
+        """-> the handle of submit's grammar= (LLaMA.load_grammar on the server's sampler)"""
+        return self.model.load_grammar(self.sampler, automaton)
+
+    def _prompt_len(self, prompt, request):
+        """the tokens the prompt encode sees: all of them, or all but the re-fed last one of a request with a grammar"""
+        return int(prompt.numel()) - (1 if request.get("grammar") is not None else 0)
+
     def submit(self, prompt, **request):
         prompt = torch.as_tensor(prompt).reshape(-1).to(torch.int32).cpu()
-        n = int(prompt.numel())
+        n = self._prompt_len(prompt, request)
         if n < 1 or n + 1 > self.len_buf:
-            raise ops.ZLError(f"submit: a prompt of {n} tokens does not fit the KV buffer of {self.len_buf}")
+            raise ops.ZLError(f"submit: a prompt of {int(prompt.numel())} tokens does not fit the KV buffer of {self.len_buf}"
+                              if n >= 1 else "submit: a prompt of one token at least, two with a grammar")
+        if request.get("grammar") is not None and not (self.sampler.fsm is not None and isinstance(request["grammar"], int)
+                                                      and 0 <= request["grammar"] < self.sampler.fsm_used[0]):
+            raise ops.ZLError("submit: grammar is a handle of this server's load_grammar")
         probe = dict(request)
         if self.lookup is not None and probe.get("history") is None:
             probe["history"] = prompt
@@ -139,7 +156,7 @@ class BatchServer:
             self.active[s] = r
             self.parked.discard(s)
             self.finished[s] = 0
-            n = int(self.requests[r][0].numel())
+            n = self._prompt_len(*self.requests[r])
             self.results[r] = dict(tokens=[], logprobs=[], reason=0, round=self.round, first_token=None,
                                    clamped=ops.slot_max_new(n, self.requests[r][1].get("max_new_tokens", 0) or 0, self.len_buf, self.k))
             if self.top:
@@ -192,7 +209,7 @@ class BatchServer:
                         res["top_logprobs"] += tlp[i][s][:m]
             for s in list(self.active):
                 res = self.results[self.active[s]]
-                if res["first_token"] is None:
+                if res["first_token"] is None and self.requests[self.active[s]][1].get("grammar") is None:
                     res["first_token"] = first[s]
                 self.finished[s] = fin[s]
                 if fin[s]:
