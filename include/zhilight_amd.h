@@ -485,6 +485,31 @@ int zl_kv_blocks_copy(const int32_t* desc, int64_t n, void* const* k_bufs, void*
 int zl_kv_blocks_copy_ex(const int32_t* desc, int64_t n, void* const* k_bufs, void* const* v_bufs, const int32_t* buf_lens, void* pool,
                          int64_t layers, int64_t b, int64_t block, int64_t hkv, int64_t row_bytes, int bshd, int to_pool,
                          int64_t piece_bytes, zl_stream_t s);
+/* Fork prefilled tasks, ONE launch for every descriptor, every layer and both K and V: n samples of one prompt cost one prompt encode
+ * and n - 1 copies (the reference copies a task's buffers per beam or result on the host side of batch_search: one copy call per
+ * layer, K/V and result; num_results, src/generator/batch_generator.cpp).  desc (n, 4) int32 on the device: src, dst, rows, token;
+ * k_bufs / v_bufs (layers, B) DEVICE pointer tables as for zl_kv_blocks_copy (the INT8 cache's scale plane: ks_addrs / vs_addrs with
+ * row_bytes = 4).  Copy (src != dst): rows [0, rows) of the destination task's buffer become the source's, every layer, K and V -- one
+ * run of rows * hkv * row_bytes bytes under BSHD, hkv runs of rows * row_bytes under BHSD with each side's head stride from its own
+ * buf_lens entry; rows >= `rows` of the destination, the source and every other task are not touched.  Bookkeeping (tokens, positions,
+ * placement, valid_lens (B) int32: all four, or all four NULL -- the second call for a scale plane): src != dst: positions[dst],
+ * placement[dst], valid_lens[dst] <- the source's, tokens[dst] <- token if token >= 0 else tokens[src]; src == dst: nothing is copied,
+ * tokens[src] <- token if token >= 0; one thread writes a descriptor's four words.  A descriptor with src or dst outside [0, b),
+ * rows < 0, rows > max_rows, rows > buf_lens[src] or rows > buf_lens[dst] is dropped whole, bookkeeping included, before any access
+ * through the tables (never a stray access).  The CALLER's to keep (ops.kv_fork checks them on the host): no task is a destination
+ * twice, no destination is also a source, and a source whose self-descriptor overrides its token names that override in each of its
+ * other descriptors, so that no tokens[src] is read that the same launch writes.  row_bytes % 4 == 0; runs whose two addresses and
+ * length are 16-byte aligned move as 16-byte vectors, others as dwords.  The grid is sized from max_rows (>= every descriptor's rows);
+ * the destinations of one source, neighbours in desc, work on one source piece side by side.  No atomics, no workspace, no allocation,
+ * no synchronisation: the launch can be captured.  n == 0: ZL_OK without a launch.  ZL_EINVAL: null table, non-positive size, the
+ * bookkeeping pointers given in part; ZL_ESHAPE: row_bytes % 4, piece_bytes % 16; ZL_ELIMIT: beyond the grid.
+ * _ex: piece_bytes = bytes of a run that one workgroup moves (0 = the default, 16 KiB; tools/bench_fork.py sweeps it). */
+int zl_kv_fork(const int32_t* desc, int64_t n, void* const* k_bufs, void* const* v_bufs, const int32_t* buf_lens, int64_t layers, int64_t b,
+               int64_t max_rows, int64_t hkv, int64_t row_bytes, int bshd, int32_t* tokens, int32_t* positions, int32_t* placement,
+               int32_t* valid_lens, zl_stream_t s);
+int zl_kv_fork_ex(const int32_t* desc, int64_t n, void* const* k_bufs, void* const* v_bufs, const int32_t* buf_lens, int64_t layers,
+                  int64_t b, int64_t max_rows, int64_t hkv, int64_t row_bytes, int bshd, int32_t* tokens, int32_t* positions,
+                  int32_t* placement, int32_t* valid_lens, int64_t piece_bytes, zl_stream_t s);
 
 /* Fused decode-step front end: split fused qkv rows, rotate q and k with cached cos/sin, write q
  * and scatter k,v straight into the ragged buffers (rope_qk_cache + copy_to_rag_buffer2 in one

@@ -34,7 +34,7 @@ SYMBOLS = [
     "zl_lm_head_score_ws_bytes", "zl_lm_head_score", "zl_lm_head_score_ex",
     "zl_rmsnorm",
     "zl_w4a16_moe_up", "zl_w4a16_moe_down", "zl_moe_grouped_bm", "zl_moe_grouped_tiles", "zl_w4a16_gemm_grouped", "zl_w4a16_gemm_pairs", "zl_rope_cos_sin", "zl_rope_cos_sin_llama3", "zl_rope_cos_sin_dynamic", "zl_rope_cos_sin_yarn", "zl_head_norm", "zl_rotary_embedding_qk", "zl_rope_qk_cache", "zl_rope_rotate", "zl_mask_valid_lens",
-    "zl_copy_to_rag_buffer2", "zl_copy_to_rag_buffer_bytes", "zl_kv_blocks_copy", "zl_kv_blocks_copy_ex", "zl_rope_scatter_decode", "zl_w4a16_qkv_rope_scatter", "zl_w4a16_qkv_rope_scatter_ex", "zl_decode_attn_splits_h", "zl_decode_attn_splits_h_mask", "zl_decode_attn_combine_h", "zl_w4a16_gemm_attn_merge_h", "zl_w4a16_gemm_attn_merge_h_ex",
+    "zl_copy_to_rag_buffer2", "zl_copy_to_rag_buffer_bytes", "zl_kv_blocks_copy", "zl_kv_blocks_copy_ex", "zl_kv_fork", "zl_kv_fork_ex", "zl_rope_scatter_decode", "zl_w4a16_qkv_rope_scatter", "zl_w4a16_qkv_rope_scatter_ex", "zl_decode_attn_splits_h", "zl_decode_attn_splits_h_mask", "zl_decode_attn_combine_h", "zl_w4a16_gemm_attn_merge_h", "zl_w4a16_gemm_attn_merge_h_ex",
     "zl_quant_group_32", "zl_dequant_sum_quant_g32", "zl_dequant_group_32",
     "zl_fp8_calc_scale", "zl_fp8_cvt_half", "zl_fp8_gemm_nt",
     "zl_decode_attn_workspace_bytes", "zl_decode_attn", "zl_decode_attn_ex", "zl_decode_attn_causal", "zl_decode_attn_fused",

@@ -2741,17 +2741,39 @@ class LLaMA:
         for j, rq in enumerate(requests if len(requests) == len(prompts) else []):      # a count that is off is refused below
             if rq.get("grammar") is not None:
                 pr = torch.as_tensor(prompts[j]).reshape(-1)
-                g = rq["grammar"]
-                if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
-                    raise ops.ZLError("admit: grammar is load_grammar's start state")
-                if sampler.fsm is None or not 0 <= int(g) < sampler.fsm_used[0]:
-                    raise ops.ZLError("admit: grammar names no loaded automaton of this sampler")
+                g = self._grammar_start("admit", sampler, rq["grammar"])
                 if pr.numel() < 2:
                     raise ops.ZLError("admit: a request with a grammar needs a prompt of 2 tokens at least (the last one is re-fed)")
-                prompts[j], rq["grammar"] = pr[:-1], (int(g), int(pr[-1]))
+                prompts[j], rq["grammar"] = pr[:-1], (g, int(pr[-1]))
         slots, _, _ = self._check_prompt_batch("admit", ctx, slots, prompts, None, kv_history)
         if len(requests) != len(slots):
             raise ops.ZLError("admit: one request per slot")
+        entries, guards = self._slot_entries("admit", ctx, slots, prompts, requests, stop, lookup)
+        blob, _ = ops.slots_pack(entries, self.cfg.vocab_size, self.slot_widths(sampler, stop, lookup))
+        before = ctx.steps_left
+        if cache is None:
+            out = self.prefill_batch(ctx, slots, prompts, kv_history=kv_history)
+        else:
+            out = self.prefill_cached(ctx, cache, slots, prompts, kv_history=kv_history)
+        self._slots_launch(ctx, blob, sampler, stop, lookup)
+        if guards:
+            ctx.slot_guard.update(guards)
+            self._steps_left_after_admission(ctx, before)
+        return out
+
+    @staticmethod
+    def _grammar_start(what, sampler, g):
+        """a request's grammar= as admit / admit_samples take it: load_grammar's handle of this sampler -> int"""
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+            raise ops.ZLError(f"{what}: grammar is load_grammar's start state")
+        if sampler.fsm is None or not 0 <= int(g) < sampler.fsm_used[0]:
+            raise ops.ZLError(f"{what}: grammar names no loaded automaton of this sampler")
+        return int(g)
+
+    def _slot_entries(self, what, ctx, slots, prompts, requests, stop, lookup):
+        """the per-slot half of an admission, host only: prompts[j] = the tokens the prompt encode sees for slots[j]; with a stop state
+        the request's length limit is clamped and the slot's guard computed, with a drafter the history defaults to those tokens
+        -> (slots_pack's entries, {slot: guard})"""
         k = lookup.k if lookup is not None else 0
         entries, guards = [], {}
         for s, pr, rq in zip(slots, prompts, requests):
@@ -2759,21 +2781,90 @@ class LLaMA:
             if stop is not None:
                 raw = rq.get("max_new_tokens", 0)
                 if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or not 0 <= int(raw) < 1 << 31:
-                    raise ops.ZLError(f"admit: slot {s}: max_new_tokens is an integer >= 0 (0 = no limit)")
+                    raise ops.ZLError(f"{what}: slot {s}: max_new_tokens is an integer >= 0 (0 = no limit)")
                 lim = ops.slot_max_new(n, int(raw), ctx.max_len_buf, k)
                 if lim < 1:
-                    raise ops.ZLError(f"admit: prompt of slot {s} ({n} tokens) leaves no room for one generated token")
+                    raise ops.ZLError(f"{what}: prompt of slot {s} ({n} tokens) leaves no room for one generated token")
                 rq["max_new_tokens"] = lim
                 guards[s] = n + lim + k + 1
             if lookup is not None and rq.get("history") is None:
                 rq["history"] = pr.reshape(-1)
             entries.append((s, rq))
+        return entries, guards
+
+    @staticmethod
+    def fork_descriptors(groups):
+        """ops.kv_fork's descriptors of an admit_samples call, host only: groups = [(slots, prompt)] -> for every group (src, dst,
+        len(prompt) - 1, prompt[-1]) for each slot behind slots[0] = src, then the self-descriptor (src, src, 0, prompt[-1]); the
+        destinations of one source stay neighbours"""
+        desc = []
+        for slots, prompt in groups:
+            toks = torch.as_tensor(prompt).reshape(-1)
+            n, last, src = int(toks.numel()), int(toks[-1]), int(slots[0])
+            desc += [(src, int(d), n - 1, last) for d in slots[1:]]
+            desc.append((src, src, 0, last))
+        return desc
+
+    def admit_samples(self, ctx: DynBatchContext, groups, sampler: SamplerState, stop: Optional[StopState] = None,
+                      lookup: Optional[LookupState] = None, cache=None, kv_history=None):
+        """Admit several samples of one prompt for ONE prompt encode (the reference's num_results: batch_generator.cpp gives a task's
+        first step num_results rows and copies its buffers per result on the host): groups = [(slots, prompt, requests)], slots[0] the
+        group's source, requests[j] the request of slots[j] (dicts over ops.SLOT_REQUEST_KEYS, None = the defaults).  In order:
+        prefill_batch -- prefill_cached with a prefix cache -- of every group's prompt[:-1] into its source slot, all groups in one
+        call; ONE ops.kv_fork launch (a second one for the INT8 cache's scale plane) that copies the source's rows [0, len - 1) into
+        the group's other slots, hands them its position, placement and valid length and gives EVERY slot of the group prompt[-1] as
+        its pending token (LLaMA.fork_descriptors); the upload and launch of admit (ops.slots_pack / slots_admit) over all slots of
+        all groups, which read that pending token; the drafter's launch when lookup is given.  The first step then re-feeds
+        prompt[-1] in every slot and draws each slot's first token under its own sampler row: n samples with n seeds start with n
+        draws of the true distribution, where admit leaves the prompt's greedy pick pending.  A group of one slot copies nothing: it
+        is the admission with a sampled first token.
+        The conventions are those of a request with a grammar in admit: a prompt has 2 tokens at least and counts as len - 1 for the
+        length limit and the guard (every slot of a group gets the guard its source would get), the default history is prompt[:-1],
+        a request's grammar handle travels as (start, prompt[-1]), and the result is the prompt encode's: the logits row of
+        prompt[:-1] per GROUP (with a cache: (logits, matched)).  Every other slot's rows are untouched and no tensor is reallocated.
+        Refused before any launch, with nothing changed: everything admit refuses, and a slot that occurs twice across the groups."""
+        self._slot_states("admit_samples", ctx, sampler, stop, lookup)
+        what = "admit_samples"
+        gs = []
+        for g in groups:
+            try:
+                slots, prompt, requests = g
+                slots, requests = [int(s) for s in slots], [dict(rq or {}) for rq in requests]
+            except (TypeError, ValueError):
+                raise ops.ZLError(f"{what}: a group is (slots, prompt, requests)") from None
+            prompt = torch.as_tensor(prompt).reshape(-1)
+            if not slots or len(requests) != len(slots):
+                raise ops.ZLError(f"{what}: one request per slot, one slot at least per group")
+            if prompt.numel() < 2:
+                raise ops.ZLError(f"{what}: a prompt of 2 tokens at least (the last one is re-fed)")
+            for rq in requests:
+                if rq.get("grammar") is not None:
+                    rq["grammar"] = (self._grammar_start(what, sampler, rq["grammar"]), int(prompt[-1]))
+            gs.append((slots, prompt, requests))
+        if not gs:
+            raise ops.ZLError(f"{what}: one group at least")
+        flat = [s for slots, _, _ in gs for s in slots]
+        heads = [pr[:-1] for slots, pr, _ in gs for _ in slots]
+        self._check_prompt_batch(what, ctx, flat, heads, None, kv_history)         # every slot: distinct, inside the batch, the rows fit
+        entries, guards = self._slot_entries(what, ctx, flat, heads, [rq for _, _, rqs in gs for rq in rqs], stop, lookup)
         blob, _ = ops.slots_pack(entries, self.cfg.vocab_size, self.slot_widths(sampler, stop, lookup))
+        b = ctx.tokens.numel()
+        lens = [ctx.max_len_buf] * b
+        desc, _ = ops.kv_fork_check(self.fork_descriptors([(slots, pr) for slots, pr, _ in gs]), lens, b, self.cfg.vocab_size)
         before = ctx.steps_left
+        sources, prompts = [slots[0] for slots, _, _ in gs], [pr[:-1] for _, pr, _ in gs]
         if cache is None:
-            out = self.prefill_batch(ctx, slots, prompts, kv_history=kv_history)
+            out = self.prefill_batch(ctx, sources, prompts, kv_history=kv_history)
         else:
-            out = self.prefill_cached(ctx, cache, slots, prompts, kv_history=kv_history)
+            out = self.prefill_cached(ctx, cache, sources, prompts, kv_history=kv_history)
+        ops.kv_fork(desc, ctx.k_addrs, ctx.v_addrs, ctx.buf_lens, self.cfg.num_kv_heads, self.cfg.dim_head * ctx.kv[0].element_size(),
+                    buf_lens_host=lens, ctx_rows=(ctx.tokens, ctx.positions, ctx.placement, ctx.valid_lens))
+        if ctx.kv_quant:
+            ops.kv_fork(desc, ctx.ks_addrs, ctx.vs_addrs, ctx.buf_lens, self.cfg.num_kv_heads, 4, buf_lens_host=lens)
+        for slots, _, _ in gs:                                                # the copies stand where their source stands
+            for d in slots[1:]:
+                ctx.slot_guard.pop(d, None)
+                ctx.slot_room[d] = ctx.slot_room[slots[0]]
         self._slots_launch(ctx, blob, sampler, stop, lookup)
         if guards:
             ctx.slot_guard.update(guards)

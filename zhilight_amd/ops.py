@@ -2117,6 +2117,89 @@ def kv_blocks_copy(desc, k_addrs, v_addrs, buf_lens, pool, block, hkv, row_bytes
     return desc_dev
 
 
+def kv_fork_check(desc, buf_lens_host, b, vocab=None):
+    """The host half of kv_fork, numpy only: desc = (src, dst, rows, token) int quadruples, buf_lens_host = the b tasks' buffer
+    lengths -> (the descriptors as a list of int 4-tuples, the largest rows).  Raises ZLError for a descriptor that is not four
+    ints, a task outside the batch, rows outside either buffer, a task that is a destination twice (a self-descriptor src == dst
+    counts for its task's token), a destination that is also a source, a source whose self-descriptor overrides its token (token >=
+    0) while one of its other descriptors names another token -- that destination would read a tokens[src] the same launch writes --,
+    and with `vocab` a token >= vocab.  token < 0 = no override."""
+    b = int(b)
+    lens = [int(x) for x in (buf_lens_host.tolist() if hasattr(buf_lens_host, "tolist") else buf_lens_host)]
+    if len(lens) != b:
+        raise ZLError("kv_fork: one buffer length per task")
+    rows_in = desc.tolist() if hasattr(desc, "tolist") else list(desc)
+    out = []
+    for d in rows_in:
+        try:
+            d = tuple(d)
+        except TypeError:
+            d = ()
+        if len(d) != 4 or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in d):
+            raise ZLError("kv_fork: a descriptor is (src, dst, rows, token), four integers")
+        out.append(tuple(int(x) for x in d))
+    dests, selfs, sources = set(), {}, set()
+    for src, dst, rows, token in out:
+        if not (0 <= src < b and 0 <= dst < b):
+            raise ZLError(f"kv_fork: tasks {src} -> {dst} lie outside the batch of {b}")
+        if not 0 <= rows <= min(lens[src], lens[dst]):
+            raise ZLError(f"kv_fork: rows 0 .. {rows - 1} of tasks {src} -> {dst} lie outside a buffer ({lens[src]}, {lens[dst]} rows)")
+        if not -(1 << 31) <= token < (1 << 31) or (vocab is not None and token >= int(vocab)):
+            raise ZLError(f"kv_fork: token {token} of tasks {src} -> {dst} lies outside the vocabulary")
+        if dst in dests or dst in selfs:
+            raise ZLError(f"kv_fork: task {dst} is a destination twice in one call")
+        if src == dst:
+            selfs[src] = token
+        else:
+            dests.add(dst)
+        sources.add(src)
+    for src, dst, rows, token in out:
+        if src != dst and dst in sources:
+            raise ZLError(f"kv_fork: task {dst} is a destination and a source in one call")
+        if src != dst and selfs.get(src, -1) >= 0 and token != selfs[src]:
+            raise ZLError(f"kv_fork: task {src} overrides its token with {selfs[src]}, its descriptor to task {dst} names {token}")
+    return out, max((d[2] for d in out), default=0)
+
+
+def kv_fork(desc, k_addrs, v_addrs, buf_lens, hkv, row_bytes, bshd=True, buf_lens_host=None, ctx_rows=None, piece_bytes=0, vocab=None):
+    """zl_kv_fork: ONE launch that, for every descriptor (src, dst, rows, token) of `desc`, every layer and both K and V, copies rows
+    [0, rows) of task src's buffers into task dst's and, with ctx_rows = (tokens, positions, placement, valid_lens) (B) int32, hands
+    dst the source's position, placement and valid length and the pending token `token` (token < 0: the source's); a self-descriptor
+    (src == dst) copies nothing and only sets the task's own pending token.  desc: a HOST sequence, checked here (kv_fork_check states
+    the refusals, all raised before any launch) and uploaded once; k_addrs / v_addrs (layers, B) device pointer tables
+    (DynBatchContext.k_addrs / v_addrs, or ks_addrs / vs_addrs with row_bytes = 4 and ctx_rows = None for the INT8 cache's scales);
+    buf_lens (B) int32 on the device, buf_lens_host the same numbers where the caller holds them (else they are read back: a
+    synchronisation); row_bytes % 4 == 0.  An empty desc launches nothing.  Returns the uploaded descriptors, or None."""
+    _chk_cuda(k_addrs, v_addrs, buf_lens)
+    if k_addrs.dim() != 2 or k_addrs.shape != v_addrs.shape or k_addrs.dtype != torch.int64 or v_addrs.dtype != torch.int64:
+        raise ZLError("kv_fork: k_addrs / v_addrs are (layers, B) int64 pointer tables")
+    layers, b = k_addrs.shape
+    hkv, row_bytes, piece_bytes = int(hkv), int(row_bytes), int(piece_bytes)
+    if buf_lens.dtype != torch.int32 or buf_lens.numel() != b:
+        raise ZLError("kv_fork: buf_lens is (B) int32")
+    if hkv < 1 or row_bytes < 4 or row_bytes % 4 or piece_bytes < 0 or piece_bytes % 16:
+        raise ZLError("kv_fork: hkv >= 1, row_bytes a positive multiple of 4, piece_bytes a multiple of 16")
+    if ctx_rows is not None:
+        if len(ctx_rows) != 4:
+            raise ZLError("kv_fork: ctx_rows is (tokens, positions, placement, valid_lens)")
+        for t in ctx_rows:
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.numel() == b and t.is_contiguous()
+                    and t.device == k_addrs.device):
+                raise ZLError("kv_fork: ctx_rows: four contiguous (B) int32 tensors on the tables' device")
+    rows4 = [_p(t) for t in ctx_rows] if ctx_rows is not None else [_p(None)] * 4
+    n_desc = len(desc)
+    if not n_desc:
+        check(lib().zl_kv_fork(None, _i(0), _p(k_addrs), _p(v_addrs), _p(buf_lens), _i(layers), _i(b), _i(0), _i(hkv), _i(row_bytes),
+                               C.c_int(int(bshd)), *rows4, _stream()), "kv_fork")
+        return None
+    desc, max_rows = kv_fork_check(desc, buf_lens.tolist() if buf_lens_host is None else buf_lens_host, b, vocab)
+    desc_dev = torch.tensor(desc, dtype=torch.int32).to(k_addrs.device)
+    fn, extra = (lib().zl_kv_fork_ex, (_i(piece_bytes),)) if piece_bytes else (lib().zl_kv_fork, ())
+    check(fn(_p(desc_dev), _i(len(desc)), _p(k_addrs), _p(v_addrs), _p(buf_lens), _i(layers), _i(b), _i(max_rows), _i(hkv), _i(row_bytes),
+             C.c_int(int(bshd)), *rows4, *extra, _stream()), "kv_fork")
+    return desc_dev
+
+
 def rope_scatter_decode(cos, sin, qkv, placement, buf_lens, k_addrs, v_addrs, num_heads, num_kv_heads, dim_head,
                         neox=True, bshd=True, q_out=None):
     """rope_qk_cache + copy_to_rag_buffer2 fused for len_q == 1 decode rows."""

@@ -11,6 +11,19 @@ import torch
 from . import ops
 
 REASONS = {1: "stop id", 2: "stop sequence", 3: "length"}
+SEED_MIN, SEED_END = -(1 << 63), 1 << 64       # the seeds ops.slots_pack keeps apart: the 64 bits of the key, read signed or unsigned
+
+
+def rank_samples(samples, n):
+    """The samples a request with best_of = len(samples) returns, host only: every dict gains cum_logprob = the sum of its
+    logprobs; best_of > n: the n samples of largest cum_logprob, largest first, ties to the lower sample index; best_of == n: all of
+    them by sample index."""
+    for sm in samples:
+        sm["cum_logprob"] = float(sum(sm["logprobs"]))
+    if len(samples) <= n:
+        return list(samples)
+    order = sorted(range(len(samples)), key=lambda j: (-samples[j]["cum_logprob"], j))
+    return [samples[j] for j in order[:n]]
 
 
 class BatchServer:
@@ -31,11 +44,20 @@ class BatchServer:
     least: its last token is re-fed so that the first generated token is drawn under the grammar (LLaMA.admit); its first_token is None
     and tokens holds every generated id.
 
+    submit(prompt, n=, best_of=, sample_first=): n samples of one prompt for ONE prompt encode (LLaMA.admit_samples: the prompt without
+    its last token is encoded into one slot, one launch copies its K/V rows into best_of - 1 other slots, every slot re-feeds the last
+    token and draws its first token under its own sampler row).  best_of (default n) samples run, sample j with seed + j; 1 <= n <=
+    best_of <= batch.  best_of > 1 or sample_first=True takes that route and needs a prompt of two tokens at least; with best_of == 1
+    the result is the plain one, first_token None as for a grammar.  With best_of > 1 results[id] = dict(samples=[...], round=...): n
+    dicts of the plain shape plus seed and cum_logprob (rank_samples has the order).  Admission is FIFO and all-or-nothing: the head of
+    the queue waits until best_of slots are free and nothing overtakes it.
+
     run() serves the queue until it and the batch are empty and returns {id: dict(tokens, logprobs, reason, round, first_token,
     clamped, [top_ids, top_logprobs])}: tokens = the ids emitted behind first_token (the greedy pick the prompt encode leaves
     pending, LLaMA.admit's convention), logprobs = their tempered log-probabilities, reason = 1 (stop id) / 2 (stop sequence) / 3 (length),
     round = the admission round, clamped = the length limit the slot ran under.  self.log = the admission groups (round, [(slot, id),
-    ...]); self.matched = {id: tokens the prefix cache supplied}; self.stats counts steps and slot-steps."""
+    ...]), the samples of one request in sample order; self.matched = {id: tokens the prefix cache supplied}; self.stats counts steps,
+    slot-steps and forks (destinations copied)."""
 
     def __init__(self, model, batch, len_buf, penalties=True, bias_ld=0, top_logprobs=0, lookup_k=0, prefix_cache=None, capture=False,
                  poll=8, kv_history=None, prefix_blocks=0, prefix_block_size=128, grammar_states=0, grammar_edges=0):
@@ -60,9 +82,10 @@ class BatchServer:
         self.queue = collections.deque()
         self.requests, self.results, self.log, self.matched = {}, {}, [], {}
         self.active, self.parked = {}, set()                               # slot -> id; slots parked since they finished
+        self.meta, self.sample_of, self._pending = {}, {}, {}              # id -> (n, best_of, re-fed); slot -> sample index; id -> samples running
         self.round = 0
         self.graph = self._graph_out = None
-        self.stats = dict(steps=0, live_slot_steps=0, finished_slot_steps=0, parked_slot_steps=0, admissions=0, parks=0)
+        self.stats = dict(steps=0, live_slot_steps=0, finished_slot_steps=0, parked_slot_steps=0, admissions=0, parks=0, forks=0)
         n, w, top = self.poll * self.b * self.width, self.width, int(top_logprobs)
         # one read-back: the rounds' token rows, their log-probabilities (as bits), finished and the first tokens, in ONE int32 buffer
         self._rb = torch.empty(2 * n + 2 * self.b + 2 * n * top, dtype=torch.int32, device=model.device)
@@ -80,16 +103,26 @@ class BatchServer:
         """-> the handle of submit's grammar= (LLaMA.load_grammar on the server's sampler)"""
         return self.model.load_grammar(self.sampler, automaton)
 
-    def _prompt_len(self, prompt, request):
-        """the tokens the prompt encode sees: all of them, or all but the re-fed last one of a request with a grammar"""
-        return int(prompt.numel()) - (1 if request.get("grammar") is not None else 0)
+    def _prompt_len(self, prompt, request, refed=False):
+        """the tokens the prompt encode sees: all of them, or all but the re-fed last one of a request with a grammar or of one that
+        goes through admit_samples"""
+        return int(prompt.numel()) - (1 if refed or request.get("grammar") is not None else 0)
 
-    def submit(self, prompt, **request):
+    def submit(self, prompt, n=1, best_of=None, sample_first=False, **request):
         prompt = torch.as_tensor(prompt).reshape(-1).to(torch.int32).cpu()
-        n = self._prompt_len(prompt, request)
+        ints = lambda v: isinstance(v, int) and not isinstance(v, bool)                                      # noqa: E731
+        best_of = n if best_of is None else best_of
+        if not (ints(n) and ints(best_of) and 1 <= n <= best_of <= self.b):
+            raise ops.ZLError(f"submit: 1 <= n <= best_of <= batch ({self.b}), integers")
+        samples, refed = (n, best_of), best_of > 1 or bool(sample_first)
+        if best_of > 1:
+            seed = request.get("seed", 0)
+            if not (isinstance(seed, int) and SEED_MIN <= seed and seed + best_of - 1 < SEED_END):
+                raise ops.ZLError(f"submit: seeds seed .. seed + {best_of - 1} of the samples within [-2^63, 2^64)")
+        n = self._prompt_len(prompt, request, refed)
         if n < 1 or n + 1 > self.len_buf:
             raise ops.ZLError(f"submit: a prompt of {int(prompt.numel())} tokens does not fit the KV buffer of {self.len_buf}"
-                              if n >= 1 else "submit: a prompt of one token at least, two with a grammar")
+                              if n >= 1 else "submit: a prompt of one token at least, two with a grammar, n > 1 or sample_first")
         if request.get("grammar") is not None and not (self.sampler.fsm is not None and isinstance(request["grammar"], int)
                                                       and 0 <= request["grammar"] < self.sampler.fsm_used[0]):
             raise ops.ZLError("submit: grammar is a handle of this server's load_grammar")
@@ -101,6 +134,7 @@ class BatchServer:
             raise ops.ZLError(f"submit: a prompt of {n} tokens leaves no room for one generated token")
         rid = len(self.requests)
         self.requests[rid] = (prompt, dict(request))
+        self.meta[rid] = samples + (refed,)
         self.queue.append(rid)
         return rid
 
@@ -136,31 +170,63 @@ class BatchServer:
     def _admit(self):
         free = [s for s in range(self.b) if s not in self.active]
         group = []
-        while self.queue and free:
-            group.append((free.pop(0), self.queue.popleft()))
+        while self.queue and len(free) >= self.meta[self.queue[0]][1]:      # FIFO, all-or-nothing: the head waits, nothing overtakes it
+            rid = self.queue.popleft()
+            group += [(free.pop(0), rid) for _ in range(self.meta[rid][1])]
         if not group:
             return
         self.round += 1
-        slots = [s for s, _ in group]
-        prompts = [self.requests[r][0] for _, r in group]
-        reqs = [self.requests[r][1] for _, r in group]
-        out = self.model.admit(self.ctx, slots, prompts, reqs, self.sampler, self.stop, self.lookup, cache=self.cache,
-                               kv_history=self.kv_history)
-        if self.cache is not None:
-            for (_, r), m in zip(group, out[1]):
-                self.matched[r] = int(m)
+        plain = [(s, r) for s, r in group if not self.meta[r][2]]
+        forked = {}
+        for s, r in group:
+            if self.meta[r][2]:
+                forked.setdefault(r, []).append(s)
+        if plain:
+            out = self.model.admit(self.ctx, [s for s, _ in plain], [self.requests[r][0] for _, r in plain],
+                                   [self.requests[r][1] for _, r in plain], self.sampler, self.stop, self.lookup, cache=self.cache,
+                                   kv_history=self.kv_history)
+            if self.cache is not None:
+                for (_, r), m in zip(plain, out[1]):
+                    self.matched[r] = int(m)
+        if forked:
+            groups = [(slots, self.requests[r][0], [dict(self.requests[r][1], seed=self.requests[r][1].get("seed", 0) + j)
+                                                    if len(slots) > 1 else self.requests[r][1] for j in range(len(slots))])
+                      for r, slots in forked.items()]
+            out = self.model.admit_samples(self.ctx, groups, self.sampler, self.stop, self.lookup, cache=self.cache,
+                                           kv_history=self.kv_history)
+            if self.cache is not None:
+                for r, m in zip(forked, out[1]):
+                    self.matched[r] = int(m)
+            self.stats["forks"] += sum(len(slots) - 1 for slots in forked.values())
         self._first.copy_(self.ctx.tokens)
         self.log.append((self.round, list(group)))
         self.stats["admissions"] += 1
+        seen = {}
         for s, r in group:
             self.active[s] = r
             self.parked.discard(s)
             self.finished[s] = 0
-            n = self._prompt_len(*self.requests[r])
-            self.results[r] = dict(tokens=[], logprobs=[], reason=0, round=self.round, first_token=None,
-                                   clamped=ops.slot_max_new(n, self.requests[r][1].get("max_new_tokens", 0) or 0, self.len_buf, self.k))
+            prompt, request = self.requests[r]
+            res = dict(tokens=[], logprobs=[], reason=0, round=self.round, first_token=None,
+                       clamped=ops.slot_max_new(self._prompt_len(prompt, request, self.meta[r][2]), request.get("max_new_tokens", 0) or 0,
+                                                self.len_buf, self.k))
             if self.top:
-                self.results[r].update(top_ids=[], top_logprobs=[])
+                res.update(top_ids=[], top_logprobs=[])
+            if self.meta[r][1] > 1:                                         # a sample: its dict lives in the request's list until all are done
+                j = seen[r] = seen.get(r, -1) + 1
+                self.sample_of[s] = j
+                res["seed"] = request.get("seed", 0) + j
+                if j == 0:
+                    self.results[r] = dict(samples=[], round=self.round)
+                    self._pending[r] = self.meta[r][1]
+                self.results[r]["samples"].append(res)
+            else:
+                self.results[r] = res
+
+    def _res(self, s):
+        """the result dict that slot s fills"""
+        res = self.results[self.active[s]]
+        return res["samples"][self.sample_of[s]] if s in self.sample_of else res
 
     def _park(self):
         idle = [s for s in range(self.b) if s not in self.active and s not in self.parked]
@@ -201,18 +267,24 @@ class BatchServer:
                         continue
                     if s not in self.active:
                         raise ops.ZLError(f"BatchServer: slot {s} emitted ids without a request")
-                    res = self.results[self.active[s]]
+                    res = self._res(s)
                     res["tokens"] += row[:m]
                     res["logprobs"] += lp[i][s][:m]
                     if self.top:
                         res["top_ids"] += tid[i][s][:m]
                         res["top_logprobs"] += tlp[i][s][:m]
             for s in list(self.active):
-                res = self.results[self.active[s]]
-                if res["first_token"] is None and self.requests[self.active[s]][1].get("grammar") is None:
+                rid = self.active[s]
+                res = self._res(s)
+                if res["first_token"] is None and self.requests[rid][1].get("grammar") is None and not self.meta[rid][2]:
                     res["first_token"] = first[s]
                 self.finished[s] = fin[s]
                 if fin[s]:
                     res["reason"] = fin[s]
                     del self.active[s]
+                    if self.sample_of.pop(s, None) is not None:
+                        self._pending[rid] -= 1
+                        if self._pending[rid] == 0:                       # the request's last sample: rank them
+                            del self._pending[rid]
+                            self.results[rid]["samples"] = rank_samples(self.results[rid]["samples"], self.meta[rid][0])
         return self.results
