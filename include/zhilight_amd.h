@@ -16,11 +16,11 @@
  * ZhiLight tree).
  *
  * Entry points that come in pairs (round 3 VERDICT item 9):
- *   NAME / NAME_ex   -- NAME_ex is the implementation and takes the launcher options (zl_w4_opts_t, or a tuning struct of its
- *       own) as one more argument; NAME is `return NAME_ex(..., NULL, s)`: the launcher's own choices, no scratch (K-split routes
+ *   NAME / NAME_ex   -- NAME_ex is the implementation and takes the launcher options (zl_w4_opts_t, zl_sample_opts_t, or a tuning
+ *       struct of its own) as one more argument; NAME is `return NAME_ex(..., NULL, s)`: the launcher's own choices, no scratch (K-split routes
  *       off).  Both stay: NAME is what a binding written against the reference's operator signature calls
  *       (zl_w4a16_gemm_mfma, zl_w4a16_gemm_tiled, zl_w4a16_qkv_rope_scatter, zl_decode_attn, zl_decode_attn_quant,
- *       zl_w8a8_gemm_phase, zl_mla_decode_attn), NAME_ex what a host that owns scratch memory and knobs calls (ops.py does).
+ *       zl_w8a8_gemm_phase, zl_mla_decode_attn, zl_sample_advance, zl_spec_sample_accept), NAME_ex what a host that owns scratch memory and knobs calls (ops.py does).
  *   NAME / NAME_h    -- two FORMATS of the same hand-over, not two versions: zl_decode_attn_splits leaves fp32 split partials
  *       (130 floats per record; consumed by zl_w4a16_gemm_attn_merge, the fp16-dequant route, and by zl_decode_attn's own merge),
  *       zl_decode_attn_splits_h half-precision ones (256 B + an 8-byte (max, sum) pair; consumed by
@@ -1065,7 +1065,7 @@ int zl_stop_advance(const int32_t* stop_ids, int64_t n_ids, const int32_t* stop_
  *   bitmap (rep_penalty, presence, seen (b, seen_ld) all given):  the two scalars <- the record's;  row s of seen <- exactly the bits of
  *     {pending token} + the penalty ids, ids outside [0, vocab) skipped, duplicates allowed, every other word of the row 0.
  *   bias (bias_ids, bias_vals (b, bias_ld), bias_cnt, bias_bits (b, bits_ld)):  row s <- the count ids, -1 behind;  the values, 0 behind;
- *     the count;  the ids as a bitmap (zl_sample_advance_opts' layout).
+ *     the count;  the ids as a bitmap (zl_sample_opts_t::bias_bits' layout).
  *   top-N (top_ids, top_logprobs (b, top_n)):  row s <- -1 / NaN (0x7fc00000).
  *   stop:  rows s of stop_ids / seq_lens / stop_seqs <- the record's;  max_new[s] <- the record's;  gen_lens[s] = 0;  tail[s] = -1 but
  *     tail[s, 14] = pending;  last_token[s] = pending;  finished[s] = 0;  emit_lens[s] = 0.
@@ -1135,125 +1135,99 @@ int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q
                           const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
                           const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
                           int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out, zl_stream_t s);
-/* Repetition and presence penalties inside the sampling step (csrc/sample_rows.hip): the reference generator's per-task knobs
- * (src/generator/batch_generator.cpp:1670-1692), applied while the kernel reads the row instead of by a launch in front of it.
- * A task owns a set of token ids, a BITMAP: seen (b, seen_ld) uint32, seen_ld >= ceil(n / 32), token i of task t = bit i & 31 of
- * seen[t * seen_ld + (i >> 5)]; bits at or above n are never read as classes.  A class of the set is read as pen(x_i), every other
- * class as x_i, and pen is zl_repetition_penalty's expression, one rounding to the logits' type T:
- *   presence[t] != 0 ? x - T(presence[t]) : (x < 0 ? x * T(rep_penalty[t]) : x / T(rep_penalty[t]))     (presence takes precedence)
- * Everything behind that -- arg-max, the plain-row test, max, Z, top-k, top-p, the pick, the log-probability -- is zl_sample_advance's
- * rule on the penalised row: the results equal zl_repetition_penalty over the set followed by zl_sample_advance, bit for bit.  The
- * logits in memory are NOT modified.  rep_penalty / presence: fp32, per row (zl_sample_advance_ex) or per task (zl_spec_sample_accept_ex).
- *   zl_sample_advance_ex      zl_sample_advance + the four arguments.  Row r uses seen row r; after the pick, bit `pick` of that row is
- *                             set (a row with factor 1 and presence 0 records its pick too).  One launch.
- *   zl_spec_sample_accept_ex  zl_spec_sample_accept + the four arguments.  Row (t, i) is penalised by seen[t] and the drafts
- *                             drafts[t, j], j < i, that lie in [0, n): the row counts only if those drafts were emitted, so the step
- *                             stays the same function of (logits, seed, tokens emitted so far) as zl_sample_advance_ex's, step by
- *                             step.  The first launch does not write seen; the second sets the bits of out_tokens[t, 0 .. accepted[t]]
- *                             -- the rejected drafts are not recorded.  Two launches.
- *   zl_seen_mark              sets the bits of the ids of tokens[t, :n_tok] (int32 rows of stride tok_ld) that lie in [0, n); others
- *                             (-1 padding, rows of zl_spec_accept's out_tokens) are skipped.  Seeds a set from a prompt or a history.
- *                             One launch, vector atomics (or).
- * seen == NULL: the _ex calls ARE the plain ones and rep_penalty / presence may be NULL.
- * ZL_EINVAL: seen without both parameter arrays (zl_seen_mark: a null seen / tokens); ZL_ESHAPE: seen_ld < ceil(n / 32)
- * (zl_seen_mark: also b < 1, n < 1, n >= 2^31, n_tok < 1, tok_ld < n_tok); otherwise the plain calls' codes.
- * Ordinary vector stores and vector atomics only; no allocation, no sync, no workspace; deterministic. */
+/* The options of the sampling step (csrc/sample_rows.hip): penalties, logit bias, top-N log-probabilities and a token automaton,
+ * applied while the kernel reads the row instead of by launches in front of it.  One struct for both operations, passed to
+ * zl_sample_advance_ex / zl_spec_sample_accept_ex; every field is 8 bytes wide (a pointer or an int64_t), 23 fields, 184 bytes.  A
+ * GROUP is on when its pointers are given; opts == NULL and an all-zero struct are the plain call.  The arrays of a group are PER
+ * ROW (rows) in zl_sample_advance_ex and PER TASK (b) in zl_spec_sample_accept_ex.  A row is read in this order -- the automaton's
+ * mask on the stored pattern, then the penalty, then the bias -- and everything behind that (arg-max, the plain-row test, max, Z,
+ * top-k, top-p, the pick, the log-probability) is zl_sample_advance's rule on the row so read: every output equals masked_fill(-inf),
+ * zl_repetition_penalty and zl_scatter_logits(add) on a copy followed by the plain call, bit for bit.  The logits in memory are NOT
+ * modified.  The kernel instantiation follows the groups: the automaton's where fsm_mask is given, else the bias / top-N one where
+ * bias_ids or top_n > 0 is, else the penalty one where seen is, else the plain one.
+ * Every refusal returns before anything is launched; otherwise the plain calls' codes.  Launches as the plain calls (one / two);
+ * ordinary vector stores and vector atomics only; no allocation, no sync, no workspace; deterministic. */
+typedef struct {
+    /* PENALTIES (the reference generator's per-task knobs, src/generator/batch_generator.cpp:1670-1692): all three pointers or none
+     * (seen == NULL: the group is off, rep_penalty / presence are not read).  A task owns a set of token ids, a BITMAP: seen (rows or b, seen_ld) uint32, seen_ld >= ceil(n / 32), token i of task t = bit
+     * i & 31 of seen[t * seen_ld + (i >> 5)]; bits at or above n are never read as classes.  A class of the set is read as pen(x_i),
+     * zl_repetition_penalty's expression, one rounding to the logits' type T:
+     *   presence[t] != 0 ? x - T(presence[t]) : (x < 0 ? x * T(rep_penalty[t]) : x / T(rep_penalty[t]))     (presence takes precedence)
+     * rep_penalty / presence: fp32.  zl_sample_advance_ex: row r uses seen row r; after the pick, bit `pick` of that row is set (a row
+     * with factor 1 and presence 0 records its pick too).  zl_spec_sample_accept_ex: row (t, i) is penalised by seen[t] and the drafts
+     * drafts[t, j], j < i, that lie in [0, n) -- the row counts only if those drafts were emitted, so the step stays the same function
+     * of (logits, seed, tokens emitted so far) as zl_sample_advance_ex's, step by step; the first launch does not write seen, the
+     * second sets the bits of out_tokens[t, 0 .. accepted[t]]: the rejected drafts are not recorded.  zl_seen_mark seeds a set.
+     * ZL_EINVAL: seen without both parameter arrays.  ZL_ESHAPE: seen_ld < ceil(n / 32) (with seen given). */
+    const float* rep_penalty; const float* presence; uint32_t* seen; int64_t seen_ld;
+    /* LOGIT BIAS (SearcherImplV1::add_logit_bias, src/generator/batch_generator.cpp:1709-1729, applied behind the repetition penalty,
+     * then pick_top_k :1765-1766): all four pointers or none.  A task owns at most 1024 distinct ids with an fp32 bias each: bias_ids /
+     * bias_vals (rows or b, bias_ld), row t's first bias_cnt[t] ids ascending and distinct, 0 <= bias_cnt[t] <= bias_ld <= 1024, and
+     * bias_bits (rows or b, bias_bits_ld >= ceil(n / 32)), the ids as a bitmap in seen's layout (zl_seen_mark builds it).  A class i
+     * of the set is read as
+     *   T(f32(y_i) + f32(T(bias_i)))        zl_scatter_logits' add expression, one rounding to the logits' type T
+     * where y_i is what the row holds for the class AFTER the penalty.  A bias of -inf bans the class (p = 0, never picked); a row
+     * whose largest value becomes -inf is a plain row.  NaN / +inf biases are the caller's to refuse (ops.logit_bias_pack does).  A
+     * bias entry does not enter seen; a bias without seen is legal (no penalty, no drafts' penalty, no bit set).  A bias bit without a
+     * list entry reads the class unbiased, a list entry without a bit is ignored, and nothing is read beyond the row, the bitmaps'
+     * ceil(n / 32) words and the first bias_cnt[t] (clamped to bias_ld) list entries, whatever they hold.
+     * ZL_EINVAL: some but not all of the four pointers.  ZL_ESHAPE: bias_ld > 1024 or < 1, bias_bits_ld < ceil(n / 32) (with a bias). */
+    const int32_t* bias_ids; const float* bias_vals; const int32_t* bias_cnt; int64_t bias_ld;
+    const uint32_t* bias_bits; int64_t bias_bits_ld;
+    /* TOP-N (record_top_logprobs, src/generator/batch_generator.cpp:923-948: log_softmax_bias with the task's temperature, then TopK,
+     * over the penalised and biased logits), 1 <= top_n <= 32, 0 = off: top_ids / top_logprobs (rows, top_n), or (b, len_q, top_n) in
+     * the speculative call, <- per row the first min(top_n, n) classes of the kernel's order over the row as the pick saw it --
+     * larger value first, then lower index, -0.0 and +0.0 one value -- each with (y_i - max) / t - lse, the pick's own fp32
+     * instructions: where the pick is among them its entry is bit-equal to logprobs[r].  Slots at or behind n, every slot of a plain
+     * row (largest value NaN or +-inf), and in the speculative call the rows behind the bonus token: id -1, NaN.  A greedy row
+     * (T <= 0) uses t = 1.  ZL_EINVAL: top_n > 0 without both outputs.  ZL_ESHAPE: top_n < 0 or > 32. */
+    int64_t top_n; int32_t* top_ids; float* top_logprobs;
+    /* TOKEN AUTOMATON: constrained output -- a choice list, a number, a JSON shape -- without a host round trip (the reference's
+     * answer is logits_processors, Python callbacks between steps; a captured step cannot call back per token): a DFA over token ids
+     * resident on the device, shared by every row.  All six pointers (five tables and fsm_state) or none.
+     * TABLES, read only, over fsm_states = S states, fsm_exceptions = E entries and the n classes:
+     *   fsm_mask (S, fsm_mask_ld) uint32, fsm_mask_ld >= ceil(n / 32), seen's bit layout: bit i of state s set <=> token i is allowed
+     *     in s; bits at or above n are never read as classes.
+     *   fsm_default (S) int32: the next state of an allowed token that has no exception entry.
+     *   fsm_exc_off (S + 1), fsm_exc_tok (E), fsm_exc_next (E) int32: per-state exception lists in CSR form, token ids ascending and
+     *     distinct inside a state (a string-body state is "default: stay" plus a few hundred exceptions, not n edges).
+     * STATE: fsm_state int32 (rows or b), read and written in place.  A state outside [0, S) means UNCONSTRAINED: the row is read as
+     * stored and the state is not changed -- which is also "grammar finished, free text from here": a transition target outside
+     * [0, S) is stored as it is.
+     *   delta(s, tok), s in [0, S):  tok outside [0, n) or its bit in s clear -> s;  else the exception's target if the list of s holds
+     *   tok, else fsm_default[s].
+     * MASKING: a constrained row sees class i as -inf of the logits' type (0xfc00 / 0xff80) where bit i of its state's mask is clear,
+     * whatever the stored pattern is (a NaN included).  After the pick, fsm_state[r] = delta(fsm_state[r], pick); a plain row (every
+     * allowed class -inf) picks zl_argmax_advance's token, which may be disallowed: delta leaves the state.  One wave per row advances
+     * the state (a 64-way search of the exception list), no global atomics.
+     * zl_stop_advance restores neither the state nor draws nor seen (a cut task has finished; admission rewrites the state).  An
+     * accepting state allows the EOS id, one of the task's stop ids: no new stop reason.
+     * ZL_EINVAL: some but not all of the six pointers.  ZL_ESHAPE: S < 1, fsm_mask_ld < ceil(n / 32), S or E >= 2^31, E < 0. */
+    const uint32_t* fsm_mask; int64_t fsm_mask_ld; const int32_t* fsm_default; const int32_t* fsm_exc_off;
+    const int32_t* fsm_exc_tok; const int32_t* fsm_exc_next; int64_t fsm_states; int64_t fsm_exceptions;
+    int32_t* fsm_state;
+    /* zl_spec_sample_accept_ex only (zl_sample_advance_ex does not read it): row (t, i) uses s_i, s_0 = fsm_state[t], s_{j+1} =
+     * delta(s_j, drafts[t, j]); the first launch writes fsm_row_states[t, i] = delta(s_i, pick_i) ((b, len_q) int32, the caller's: no
+     * workspace), the second sets fsm_state[t] = fsm_row_states[t, accepted[t]].  Accepted drafts equal the picks, so the task's state
+     * is delta* over exactly the emitted tokens.  ZL_EINVAL: the speculative call with the automaton but without fsm_row_states. */
+    int32_t* fsm_row_states;
+} zl_sample_opts_t;
+/* zl_sample_advance / zl_spec_sample_accept with the options above: the plain calls' arguments, then opts.  The plain calls are
+ * `return NAME_ex(..., NULL, s)`. */
 int zl_sample_advance_ex(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
                          const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
                          int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
-                         const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s);
+                         const zl_sample_opts_t* opts, zl_stream_t s);
 int zl_spec_sample_accept_ex(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
                              const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
                              const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
                              int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
-                             const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s);
+                             const zl_sample_opts_t* opts, zl_stream_t s);
+/* sets the bits of the ids of tokens[t, :n_tok] (int32 rows of stride tok_ld) that lie in [0, n) in seen (b, seen_ld), the penalty
+ * group's bitmap; others (-1 padding, rows of zl_spec_accept's out_tokens) are skipped.  Seeds a set from a prompt or a history.  One
+ * launch, vector atomics (or).  ZL_EINVAL: a null seen / tokens; ZL_ESHAPE: b < 1, n < 1, n >= 2^31, n_tok < 1, tok_ld < n_tok,
+ * seen_ld < ceil(n / 32). */
 int zl_seen_mark(uint32_t* seen, int64_t seen_ld, int64_t b, int64_t n, const int32_t* tokens, int64_t n_tok, int64_t tok_ld, zl_stream_t s);
-/* Logit bias and top-N log-probabilities inside the sampling step (csrc/sample_rows.hip): the two remaining per-task knobs of the
- * reference's GeneratorArg (zhilight/dynamic_batch.py:91-119).  The _ex calls' arguments, then nine more.
- * BIAS (SearcherImplV1::add_logit_bias, src/generator/batch_generator.cpp:1709-1729, applied behind the repetition penalty, then
- * pick_top_k :1765-1766).  A task owns at most 1024 distinct ids with an fp32 bias each: bias_ids / bias_vals (rows or b, bias_ld),
- * row t's first bias_cnt[t] ids ascending and distinct, 0 <= bias_cnt[t] <= bias_ld <= 1024, and bias_bits (rows or b, bias_bits_ld >=
- * ceil(n / 32)), the ids as a bitmap in seen's layout (zl_seen_mark builds it).  A class i of the set is read as
- *   T(f32(y_i) + f32(T(bias_i)))        zl_scatter_logits' add expression, one rounding to the logits' type T
- * where y_i is what the row holds for the class AFTER the penalty: pen(x_i) if i is in the task's seen set (or, in a speculative
- * step, a draft in front of the row), x_i otherwise.  Everything behind it is zl_sample_advance's rule on that row, unchanged: every
- * output equals zl_repetition_penalty over the set, then zl_scatter_logits(add), then the plain call on the modified copy, bit for
- * bit.  The logits in memory are NOT modified.  A bias of -inf bans the class (p = 0, never picked); a row whose largest value
- * becomes -inf is a plain row.  NaN / +inf biases are the caller's to refuse (ops.logit_bias_pack does).  A bias entry does not
- * enter seen; seen == NULL with a bias is legal (no penalty, no drafts' penalty, no bit set).  A bias bit without a list entry
- * reads the class unbiased, a list entry without a bit is ignored, and nothing is read beyond the row, the bitmaps' ceil(n / 32)
- * words and the first bias_cnt[t] (clamped to bias_ld) list entries, whatever they hold.  Per row in zl_sample_advance_opts, per task
- * in zl_spec_sample_accept_opts, like the penalty arguments.
- * TOP-N (record_top_logprobs, src/generator/batch_generator.cpp:923-948: log_softmax_bias with the task's temperature, then TopK,
- * over the penalised and biased logits), 1 <= top_n <= 32: top_ids / top_logprobs (rows, top_n), or (b, len_q, top_n) in the
- * speculative call, <- per row the first min(top_n, n) classes of the kernel's order over the row as the pick saw it -- larger
- * value first, then lower index, -0.0 and +0.0 one value -- each with (y_i - max) / t - lse, the pick's own fp32 instructions:
- * where the pick is among them its entry is bit-equal to logprobs[r].  Slots at or behind n, every slot of a plain row (largest
- * value NaN or +-inf), and in the speculative call the rows behind the bonus token: id -1, NaN.  A greedy row (T <= 0) uses t = 1.
- * All nine NULL / 0: the calls ARE the _ex ones.  ZL_EINVAL: some but not all of the four bias pointers; top_n > 0 without both
- * outputs.  ZL_ESHAPE: bias_ld > 1024 or < 1, bias_bits_ld < ceil(n / 32) (with a bias given); top_n < 0 or > 32.  Otherwise the _ex
- * calls' codes.  Launches, stores and determinism as the _ex calls. */
-int zl_sample_advance_opts(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
-                           const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
-                           int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
-                           const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
-                           const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits, int64_t bias_bits_ld,
-                           int top_n, int32_t* top_ids, float* top_logprobs, zl_stream_t s);
-int zl_spec_sample_accept_opts(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
-                               const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
-                               const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
-                               int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
-                               const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
-                               const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits,
-                               int64_t bias_bits_ld, int top_n, int32_t* top_ids, float* top_logprobs, zl_stream_t s);
-/* A token automaton inside the sampling step (csrc/sample_rows.hip): constrained output -- a choice list, a number, a JSON shape --
- * without a host round trip.  The reference's answer is logits_processors, Python callbacks between steps; a captured step cannot
- * call back per token, so the constraint is a DFA over token ids resident on the device, shared by every row.  The _opts calls'
- * arguments, then the tables, the state and (speculative) row_states.
- * TABLES, read only, over S states and the n classes:
- *   fsm_mask (S, mask_ld) uint32, mask_ld >= ceil(n / 32), seen's bit layout: bit i of state s set <=> token i is allowed in s; bits
- *     at or above n are never read as classes.
- *   fsm_default (S) int32: the next state of an allowed token that has no exception entry.
- *   fsm_exc_off (S + 1), fsm_exc_tok (E), fsm_exc_next (E) int32: per-state exception lists in CSR form, token ids ascending and
- *     distinct inside a state (a string-body state is "default: stay" plus a few hundred exceptions, not n edges).
- * STATE: fsm_state int32, read and written in place, per row (zl_sample_advance_fsm) or per task (zl_spec_sample_accept_fsm).  A state
- * outside [0, S) means UNCONSTRAINED: the row is read as stored and the state is not changed -- which is also "grammar finished, free
- * text from here": a transition target outside [0, S) is stored as it is.
- *   delta(s, tok), s in [0, S):  tok outside [0, n) or its bit in s clear -> s;  else the exception's target if the list of s holds
- *   tok, else fsm_default[s].
- * MASKING: a constrained row sees class i as -inf of the logits' type (0xfc00 / 0xff80) where bit i of its state's mask is clear,
- * whatever the stored pattern is (a NaN included), applied to the STORED pattern in front of the penalty and the bias.  Everything
- * behind that -- arg-max and the plain-row test, max and Z, top-k and top-p, the pick and its log-probability, penalties and bias,
- * the top-N list -- is zl_sample_advance_opts' rule on that row: every output equals masked_fill(-inf) on a copy of the logits, then
- * the _opts call on the copy, bit for bit.  The logits in memory are NOT modified.  After the pick, fsm_state[r] = delta(fsm_state[r],
- * pick); a plain row (every allowed class -inf) picks zl_argmax_advance's token, which may be disallowed: delta leaves the state.
- * SPECULATIVE: row (t, i) uses s_i, s_0 = fsm_state[t], s_{j+1} = delta(s_j, drafts[t, j]); the first launch writes row_states[t, i] =
- * delta(s_i, pick_i) (row_states (b, len_q) int32, the caller's: no workspace), the second sets fsm_state[t] = row_states[t,
- * accepted[t]].  Accepted drafts equal the picks, so the task's state is delta* over exactly the emitted tokens and the emitted
- * sequence stays the same function of (logits, seed, tokens emitted so far) as zl_sample_advance_fsm's, step by step.
- * zl_stop_advance restores neither the state nor draws nor seen (a cut task has finished; admission rewrites the state).  An accepting
- * state allows the EOS id, one of the task's stop ids: no new stop reason.
- * ZL_EINVAL: some but not all of the five tables and fsm_state; the speculative call with tables but without row_states.  ZL_ESHAPE:
- * S < 1, mask_ld < ceil(n / 32), S or E >= 2^31 (E < 0).  All six NULL: the calls ARE the _opts ones.  Otherwise their codes.
- * Launches as the _opts calls; one wave per row advances the state (a 64-way search of the exception list); ordinary vector stores
- * only, no global atomics; no allocation, no sync, no workspace; deterministic. */
-int zl_sample_advance_fsm(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
-                          const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
-                          int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
-                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
-                          const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits, int64_t bias_bits_ld,
-                          int top_n, int32_t* top_ids, float* top_logprobs, const uint32_t* fsm_mask, int64_t mask_ld,
-                          const int32_t* fsm_default, const int32_t* fsm_exc_off, const int32_t* fsm_exc_tok, const int32_t* fsm_exc_next,
-                          int64_t S, int64_t E, int32_t* fsm_state, zl_stream_t s);
-int zl_spec_sample_accept_fsm(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
-                              const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
-                              const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
-                              int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
-                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
-                              const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits,
-                              int64_t bias_bits_ld, int top_n, int32_t* top_ids, float* top_logprobs, const uint32_t* fsm_mask,
-                              int64_t mask_ld, const int32_t* fsm_default, const int32_t* fsm_exc_off, const int32_t* fsm_exc_tok,
-                              const int32_t* fsm_exc_next, int64_t S, int64_t E, int32_t* fsm_state, int32_t* row_states, zl_stream_t s);
 /* zl_slots_admit with the sampler's automaton state: fsm_state (b) int32 (NULL: the call IS zl_slots_admit).  Blob: header flag 16
  * (flags & 16) says that header word 12 holds the word offset of an (n, 2) int32 array in the variable part -- per record the start
  * state (-1 = unconstrained) and a pending-token override (-1 = none).  A blob without grammar requests is bit-identical to

@@ -413,24 +413,28 @@ def test_abi_refusals(dev):
     p = lambda name: C.c_void_p(0 if name is None else t[name].data_ptr())   # noqa: E731
     i = C.c_int64
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    opts = [p(None)] * 3 + [i(0), p(None), i(0), C.c_int(0), p(None), p(None)]
     six = ["mask", "dflt", "off", "etok", "enext", "state"]
+    ptr = lambda name: None if name is None else t[name].data_ptr()          # noqa: E731
 
-    def plain(names=six, mask_ld=3, s=S, e=1):
+    def fsm_opts(names, mask_ld, s, e, rs=None):
         m, d, o, et, en, st = names
-        return lib.zl_sample_advance_fsm(C.c_void_p(logits.data_ptr()), C.c_int(2), i(rows), i(n), i(n), p("T"), p("k"), p("p"), p(None),
-                                         p(None), p("u"), p("tok"), *[p(None)] * 9, i(0), *opts, p(m), i(mask_ld), p(d), p(o), p(et), p(en),
-                                         i(s), i(e), p(st), stream)
+        return C.byref(_lib.SampleOpts(fsm_mask=ptr(m), fsm_mask_ld=mask_ld, fsm_default=ptr(d), fsm_exc_off=ptr(o), fsm_exc_tok=ptr(et),
+                                       fsm_exc_next=ptr(en), fsm_states=s, fsm_exceptions=e, fsm_state=ptr(st), fsm_row_states=ptr(rs)))
 
-    def spec(names=six, rs="rs", mask_ld=3, s=S, e=1):
-        m, d, o, et, en, st = names
-        return lib.zl_spec_sample_accept_fsm(C.c_void_p(logits.data_ptr()), C.c_int(2), i(1), i(2), i(n), i(n), p("drafts"), p("T"), p("k"), p("p"),
-                                             p(None), p(None), p("u"), *[p(None)] * 4, p("acc"), p("out"), *[p(None)] * 6, i(0), *opts, p(m), i(mask_ld), p(d), p(o), p(et), p(en), i(s),
-                                             i(e), p(st), p(rs), stream)
+    def plain(names=six, mask_ld=3, s=S, e=1, null_opts=False):
+        opts = None if null_opts else fsm_opts(names, mask_ld, s, e)
+        return lib.zl_sample_advance_ex(C.c_void_p(logits.data_ptr()), C.c_int(2), i(rows), i(n), i(n), p("T"), p("k"), p("p"), p(None),
+                                        p(None), p("u"), p("tok"), *[p(None)] * 6, opts, stream)
+
+    def spec(names=six, rs="rs", mask_ld=3, s=S, e=1, null_opts=False):
+        opts = None if null_opts else fsm_opts(names, mask_ld, s, e, rs)
+        return lib.zl_spec_sample_accept_ex(C.c_void_p(logits.data_ptr()), C.c_int(2), i(1), i(2), i(n), i(n), p("drafts"), p("T"), p("k"), p("p"),
+                                            p(None), p(None), p("u"), *[p(None)] * 4, p("acc"), p("out"), *[p(None)] * 3, opts, stream)
 
     EINVAL, ESHAPE = -1, -2
     assert plain() == 0 and spec() == 0
-    assert plain([None] * 6) == 0 and spec([None] * 6, rs=None) == 0        # all NULL: the _opts calls
+    assert plain([None] * 6) == 0 and spec([None] * 6, rs=None) == 0        # no pointer of the group: the plain calls
+    assert plain(null_opts=True) == 0 and spec(null_opts=True) == 0         # ... as NULL opts is
     for drop in range(6):                                                   # some but not all of the six
         names = list(six)
         names[drop] = None

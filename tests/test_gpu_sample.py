@@ -311,6 +311,64 @@ def test_distribution(dev):
     call.intact()
 
 
+def test_plain_entry_null_opts_and_zeroed_struct_are_one_call(dev):
+    """zl_sample_advance, zl_sample_advance_ex with opts = NULL and with a zeroed zl_sample_opts_t give bit-equal tokens, logprobs
+    and u_out on one greedy and two sampled rows under given uniforms; the speculative pair likewise in accepted, out_tokens and
+    out_logprobs at B = 2, K = 2"""
+    import ctypes as C
+    from zhilight_amd import _lib
+    lib = _lib.lib()
+    rng = np.random.default_rng(41)
+    n = 70
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())                                                        # noqa: E731
+    dev_of = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)                          # noqa: E731
+    i32, f32 = torch.int32, torch.float32
+    ways = (lambda f, f_ex, a: f(*a, stream), lambda f, f_ex, a: f_ex(*a, None, stream), lambda f, f_ex, a: f_ex(*a, C.byref(_lib.SampleOpts()), stream))
+
+    rows = 3
+    _, logits = _logits_dev(_make_rows(rng, rows, n, False), n, False, dev)
+    T, k, pp = dev_of(np.array([0.0, 0.8, 1.3], np.float32)), dev_of(np.array([0, 5, 0], np.int32)), dev_of(np.array([1.0, 0.9, 0.7], np.float32))
+    u = dev_of(np.array([0.3, 0.55, 0.9], np.float32))
+    got = []
+    for way in ways:
+        tok, lp, u_out = torch.full((rows,), -7, dtype=i32, device=dev), torch.full((rows,), -77.0, device=dev), torch.full((rows,), -77.0, device=dev)
+        args = [p(logits), 2, rows, n, n, p(T), p(k), p(pp), None, None, p(u), p(tok), None, None, None, None, p(lp), p(u_out)]
+        assert way(lib.zl_sample_advance, lib.zl_sample_advance_ex, args) == 0
+        torch.cuda.synchronize()
+        got.append([_np(tok), _np(lp).view(np.uint32), _np(u_out).view(np.uint32)])
+    assert ((0 <= got[0][0]) & (got[0][0] < n)).all() and np.isfinite(got[0][1].view(np.float32)).all()
+    assert np.array_equal(got[0][2], _np(u).view(np.uint32))
+    for other in got[1:]:
+        assert all(np.array_equal(a, b) for a, b in zip(got[0], other))
+
+    b, len_q = 2, 3
+    _, logits = _logits_dev(_make_rows(rng, b * len_q, n, False), n, False, dev)
+    T, k, pp = dev_of(np.array([0.0, 0.9], np.float32)), dev_of(np.array([0, 8], np.int32)), dev_of(np.array([1.0, 0.95], np.float32))
+    u = dev_of(rng.random((b, len_q)).astype(np.float32))
+    first = torch.full((b, len_q), -7, dtype=i32, device=dev)           # the picks under these uniforms, for drafts that are partly accepted
+    acc0 = torch.zeros(b, dtype=i32, device=dev)
+    none = dev_of(np.full((b, len_q - 1), -1, np.int32))
+    assert lib.zl_spec_sample_accept(p(logits), 2, b, len_q, n, n, p(none), p(T), p(k), p(pp), None, None, p(u), None, None, None, None, p(acc0),
+                                     p(first), None, None, None, stream) == 0
+    torch.cuda.synchronize()
+    drafts = _np(none).copy()
+    drafts[0, 0] = _np(first)[0, 0]                                     # task 0: its first draft is what the greedy row picks
+    drafts = dev_of(drafts)
+    got = []
+    for way in ways:
+        acc, out = torch.full((b,), -7, dtype=i32, device=dev), torch.full((b, len_q), -7, dtype=i32, device=dev)
+        out_lp = torch.full((b, len_q), -77.0, dtype=f32, device=dev)
+        args = [p(logits), 2, b, len_q, n, n, p(drafts), p(T), p(k), p(pp), None, None, p(u), None, None, None, None, p(acc), p(out), p(out_lp),
+                None, None]
+        assert way(lib.zl_spec_sample_accept, lib.zl_spec_sample_accept_ex, args) == 0
+        torch.cuda.synchronize()
+        got.append([_np(acc), _np(out), _np(out_lp).view(np.uint32)])
+    assert got[0][0][0] >= 1 and got[0][0][1] == 0 and (got[0][1][:, 0] >= 0).all()
+    for other in got[1:]:
+        assert all(np.array_equal(a, b) for a, b in zip(got[0], other))
+
+
 # ---- the model ----------------------------------------------------------------------------------------------------------------------
 LEN_BUF = sv.LEN_BUF
 PROMPT_LENS = [5, 40, 17, 9, 33, 1, 26, 12]

@@ -416,7 +416,7 @@ def test_deterministic_under_repetition_and_replay(dev):
 # ---- 5. refusals ---------------------------------------------------------------------------------------------------------------------
 def test_abi_refusals(dev):
     from zhilight_amd import ops
-    from zhilight_amd._lib import lib
+    from zhilight_amd._lib import SampleOpts, lib
     n = 40
     logits = torch.zeros((2, n), dtype=torch.float16, device=dev)
     f32 = lambda v: torch.full((2,), v, dtype=torch.float32, device=dev)                # noqa: E731
@@ -427,11 +427,15 @@ def test_abi_refusals(dev):
     p = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)                   # noqa: E731
     i = C.c_int64
 
-    def call(b_ids, b_vals, b_cnt, b_ld, b_bits, b_bits_ld, top_n, t_ids, t_lp):
-        return lib().zl_sample_advance_opts(p(logits), C.c_int(2), i(2), i(n), i(n), p(kw["temperature"]), p(kw["top_k"]), p(kw["top_p"]), p(None),
-                                            p(None), p(kw["u"]), p(kw["tokens"]), p(None), p(None), p(None), p(None), p(None), p(None), p(None),
-                                            p(None), p(None), i(0), p(b_ids), p(b_vals), p(b_cnt), i(b_ld), p(b_bits), i(b_bits_ld), C.c_int(top_n),
-                                            p(t_ids), p(t_lp), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    ptr = lambda t: None if t is None else t.data_ptr()                                 # noqa: E731
+
+    def call(b_ids, b_vals, b_cnt, b_ld, b_bits, b_bits_ld, top_n, t_ids, t_lp, null_opts=False):
+        opts = None if null_opts else C.byref(SampleOpts(bias_ids=ptr(b_ids), bias_vals=ptr(b_vals), bias_cnt=ptr(b_cnt), bias_ld=b_ld,
+                                                         bias_bits=ptr(b_bits), bias_bits_ld=b_bits_ld, top_n=top_n, top_ids=ptr(t_ids),
+                                                         top_logprobs=ptr(t_lp)))
+        return lib().zl_sample_advance_ex(p(logits), C.c_int(2), i(2), i(n), i(n), p(kw["temperature"]), p(kw["top_k"]), p(kw["top_p"]), p(None),
+                                          p(None), p(kw["u"]), p(kw["tokens"]), p(None), p(None), p(None), p(None), p(None), p(None), opts,
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
     einval = [call(ids, None, cnt, 1, bb, 2, 0, None, None), call(None, vals, None, 1, None, 2, 0, None, None),
               call(ids, vals, cnt, 1, None, 2, 0, None, None), call(None, None, None, 0, None, 0, 4, ti, None),
               call(None, None, None, 0, None, 0, 4, None, tl)]
@@ -439,7 +443,8 @@ def test_abi_refusals(dev):
               call(ids, vals, cnt, 1, bb, 1, 0, None, None), call(None, None, None, 0, None, 0, -1, ti, tl),
               call(None, None, None, 0, None, 0, 33, ti, tl)]
     assert len(set(einval)) == 1 and len(set(eshape)) == 1 and einval[0] != 0 and eshape[0] != 0 and einval[0] != eshape[0]
-    assert call(None, None, None, 0, None, 0, 0, None, None) == 0                       # all nine NULL / 0: the _ex call
+    assert call(None, None, None, 0, None, 0, 0, None, None) == 0                       # a zeroed struct ...
+    assert call(None, None, None, 0, None, 0, 0, None, None, null_opts=True) == 0       # ... and NULL opts: the plain call
     assert call(ids, vals, cnt, 1, bb, 2, 4, ti, tl) == 0                               # seen == NULL with a bias is legal
     torch.cuda.synchronize()
     # the wrappers

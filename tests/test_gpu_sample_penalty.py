@@ -184,18 +184,20 @@ def test_abi_refusals(dev):
     with pytest.raises(ops.ZLError, match="seen"):
         ops.sample_advance(logits, **kw, rep_penalty=f32(1.0), presence=f32(0.0), seen=seen[:, :1].contiguous())
     # the C ABI's own codes
-    from zhilight_amd._lib import lib
+    from zhilight_amd._lib import SampleOpts, lib
     import ctypes as C
     p = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)                   # noqa: E731
     i = C.c_int64
+    ptr = lambda t: None if t is None else t.data_ptr()                                 # noqa: E731
 
-    def call(rep, pres, sn, seen_ld):
+    def call(rep, pres, sn, seen_ld, null_opts=False):
+        opts = None if null_opts else C.byref(SampleOpts(rep_penalty=ptr(rep), presence=ptr(pres), seen=ptr(sn), seen_ld=seen_ld))
         return lib().zl_sample_advance_ex(p(logits), C.c_int(2), i(2), i(n), i(n), p(kw["temperature"]), p(kw["top_k"]), p(kw["top_p"]), p(None),
-                                          p(None), p(kw["u"]), p(kw["tokens"]), p(None), p(None), p(None), p(None), p(None), p(None), p(rep),
-                                          p(pres), p(sn), i(seen_ld), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+                                          p(None), p(kw["u"]), p(kw["tokens"]), p(None), p(None), p(None), p(None), p(None), p(None), opts,
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
     einval, eshape = call(None, kw["u"], seen, 2), call(kw["u"], kw["u"], seen, 1)
     assert einval != 0 and eshape != 0 and einval != eshape
-    assert call(None, None, None, 0) == 0                                               # seen == NULL: the plain call
+    assert call(None, None, None, 0) == 0 and call(None, None, None, 0, null_opts=True) == 0       # a zeroed struct / NULL opts: the plain call
     assert call(f32(1.0), f32(0.0), seen, 2) == 0
     torch.cuda.synchronize()
     assert ops.seen_words(1) == 1 and ops.seen_words(32) == 1 and ops.seen_words(33) == 2 and ops.seen_words(128256) == 4008

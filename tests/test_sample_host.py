@@ -1,6 +1,7 @@
 """Host-side pieces of the device sampler: the Philox4x32-10 of tests/sample_ref.py against the Random123 known answers, the
 sampling rule's invariants on hand cases, the kernel's sort-free procedure against the sorting rule, and every argument check of
 ops.sample_advance and LLaMA.new_sampler that needs no device."""
+import ctypes as C
 import math
 import types
 
@@ -193,6 +194,79 @@ def test_entry_point_refusals_without_a_launch():
     assert call(type=1) == EDTYPE and call(type=0) == EDTYPE and call(type=5) == EDTYPE
     assert call(seeds=None, draws=None, u=P, type=1) == EDTYPE              # u alone is a complete generator: past the EINVAL checks
     assert call(tokens=None, nxt=P, type=1) == EDTYPE
+
+
+def test_sample_opts_refusals_without_a_launch():
+    """zl_sample_opts_t through zl_sample_advance_ex / zl_spec_sample_accept_ex: every refusal of the penalty, bias / top-N and
+    automaton groups with its code, and every field set alone.  Each returns before anything is launched, so no GPU is needed."""
+    from zhilight_amd import _lib
+    lib, SampleOpts = _lib.lib(), _lib.SampleOpts
+    P = 0x1000                                                              # a non-null pointer that is never dereferenced
+    EINVAL, ESHAPE, EDTYPE = -1, -2, -3
+
+    def advance(n, type=2, **fields):
+        return lib.zl_sample_advance_ex(P, type, 2, n, n, P, P, P, None, None, P, P, None, None, None, None, None, None, C.byref(SampleOpts(**fields)), None)
+
+    def spec(n, type=2, **fields):
+        return lib.zl_spec_sample_accept_ex(P, type, 1, 2, n, n, P, P, P, P, None, None, P, None, None, None, None, P, P, None, None, None,
+                                            C.byref(SampleOpts(**fields)), None)
+
+    def both(n, **fields):
+        a, s = advance(n, **fields), spec(n, **fields)
+        assert a == s, fields
+        return a
+
+    # the penalty group (tests/test_gpu_sample_penalty.py), n = 40
+    assert both(40, presence=P, seen=P, seen_ld=2) == EINVAL and both(40, rep_penalty=P, seen=P, seen_ld=2) == EINVAL
+    assert both(40, rep_penalty=P, presence=P, seen=P, seen_ld=1) == ESHAPE
+    # the bias / top-N group (tests/test_gpu_sample_opts.py), n = 40
+    bias = dict(bias_ids=P, bias_vals=P, bias_cnt=P, bias_ld=1, bias_bits=P, bias_bits_ld=2)
+    assert both(40, **{**bias, "bias_vals": None}) == EINVAL and both(40, bias_vals=P, bias_ld=1, bias_bits_ld=2) == EINVAL
+    assert both(40, **{**bias, "bias_bits": None}) == EINVAL
+    assert both(40, top_n=4, top_ids=P) == EINVAL and both(40, top_n=4, top_logprobs=P) == EINVAL
+    assert both(40, **{**bias, "bias_ld": 1025}) == ESHAPE and both(40, **{**bias, "bias_ld": 0}) == ESHAPE
+    assert both(40, **{**bias, "bias_bits_ld": 1}) == ESHAPE
+    assert both(40, top_n=-1, top_ids=P, top_logprobs=P) == ESHAPE and both(40, top_n=33, top_ids=P, top_logprobs=P) == ESHAPE
+    assert both(40, top_n=(1 << 32) + 4, top_ids=P, top_logprobs=P) == ESHAPE                      # all 64 bits of top_n count
+    # the automaton group (tests/test_gpu_fsm.py), n = 70: three mask words
+    six = ("fsm_mask", "fsm_default", "fsm_exc_off", "fsm_exc_tok", "fsm_exc_next", "fsm_state")
+    fsm = dict({name: P for name in six}, fsm_mask_ld=3, fsm_states=3, fsm_exceptions=1, fsm_row_states=P)
+    for drop in six:                                                        # some but not all of the six
+        assert both(70, **{**fsm, drop: None}) == EINVAL, drop
+    assert both(70, fsm_state=P, fsm_mask_ld=3, fsm_states=3, fsm_exceptions=1) == EINVAL
+    assert spec(70, **{**fsm, "fsm_row_states": None}) == EINVAL            # tables without row_states: the speculative call alone
+    assert advance(70, type=1, **{**fsm, "fsm_row_states": None}) == EDTYPE  # ... zl_sample_advance_ex does not ask for them
+    for change in (dict(fsm_states=0), dict(fsm_mask_ld=2), dict(fsm_states=1 << 31), dict(fsm_exceptions=1 << 31), dict(fsm_exceptions=-1)):
+        assert both(70, **{**fsm, **change}) == ESHAPE, change
+    # every field alone: a pointer of a group is refused by its group's check (type = 2, so the dtype check is passed); a field that
+    # is legal alone -- a leading dimension or a count without its pointers, an output without top_n, parameters without seen --
+    # reaches the dtype check, which type = 1 fails
+    alone = dict(rep_penalty=EDTYPE, presence=EDTYPE, seen=EINVAL, seen_ld=EDTYPE, bias_ids=EINVAL, bias_vals=EINVAL, bias_cnt=EINVAL,
+                 bias_ld=EDTYPE, bias_bits=EINVAL, bias_bits_ld=EDTYPE, top_n=EINVAL, top_ids=EDTYPE, top_logprobs=EDTYPE, fsm_mask=EINVAL,
+                 fsm_mask_ld=EDTYPE, fsm_default=EINVAL, fsm_exc_off=EINVAL, fsm_exc_tok=EINVAL, fsm_exc_next=EINVAL, fsm_states=EDTYPE,
+                 fsm_exceptions=EDTYPE, fsm_state=EINVAL, fsm_row_states=EDTYPE)
+    assert list(alone) == [name for name, _ in SampleOpts._fields_] and len(alone) == 23
+    for (name, ctype), code in zip(SampleOpts._fields_, alone.values()):
+        value = {name: P if ctype is C.c_void_p else 4}
+        type = 1 if code == EDTYPE else 2
+        assert advance(40, type=type, **value) == code and spec(40, type=type, **value) == code, name
+    # NULL opts and a zeroed struct are the plain call: past every option's check, to the dtype's
+    assert advance(40, type=1) == EDTYPE and spec(40, type=1) == EDTYPE
+    assert lib.zl_sample_advance_ex(P, 1, 2, 40, 40, P, P, P, None, None, P, P, None, None, None, None, None, None, None, None) == EDTYPE
+
+
+def test_option_struct_layouts_match_the_header():
+    """the ctypes mirrors of zl_sample_opts_t and zl_w4_opts_t against the C compiler's sizeof / offsetof (zl_internals.struct_layouts):
+    a mirror that disagrees would hand the launchers wild pointers"""
+    from zhilight_amd import _lib, zl_internals
+    layouts = zl_internals.struct_layouts()
+    assert sorted(layouts) == ["zl_sample_opts_t", "zl_w4_opts_t"]
+    for name, mirror in (("zl_sample_opts_t", _lib.SampleOpts), ("zl_w4_opts_t", _lib.W4Opts)):
+        size, fields = layouts[name]
+        assert [f for f, _ in fields] == [f for f, _ in mirror._fields_], name
+        assert [(f, off) for f, off in fields] == [(f, getattr(mirror, f).offset) for f, _ in mirror._fields_], name
+        assert C.sizeof(mirror) == size, name
+    assert layouts["zl_sample_opts_t"][0] == 184 and len(_lib.SampleOpts._fields_) == 23
 
 
 def test_new_sampler_argument_checks():

@@ -4,13 +4,16 @@
      every cell is a captured graph of `--launches` calls on the same logits -- WARM: a row is 250 KB and stays in L2 between the
      calls of one replay, as it is behind the lm_head in a step -- the cells' replays alternated, device events around each.
      Parameter sets: top-k 40 + top-p 0.95 at T = 0.8 (every pass runs), top-p alone (no count select), T = 0 with log-probabilities
-     (the arg-max and the Z pass), T = 0 without (the arg-max pass alone).
+     (the arg-max and the Z pass), T = 0 without (the arg-max pass alone).  With --launch-only --parent-so PATH
+     (profiles/sample_opts_struct.txt): zl_sample_advance itself from this library and from the parent's, replays alternated, and
+     whether each cell's median lies inside the parent's own p10 .. p90 band.
   2. the whole step on the synthetic 32-layer model, 1 024 tokens of history, at batch 1, 8 and 32: a captured step_sample against a
      captured step_greedy, replays alternated.  Neither step_greedy nor anything it runs is changed by the sampler, so the
      step_greedy measured here is the one of the commit before it.
 
   3. --penalties (profiles/sample_penalties.txt): the launch alone at the same rows and parameter sets, three ways on the same logits --
-     zl_sample_advance; zl_sample_advance_ex with a bitmap of about 1 % of the vocabulary per row; and what a caller had before the
+     zl_sample_advance; zl_sample_advance_ex with a bitmap of about 1 % of the vocabulary per row (the options of every leg travel
+     as one zl_sample_opts_t; a --parent-so that still has the tiered entry points is measured on zl_sample_advance alone); and what a caller had before the
      penalty moved into the kernel, zl_repetition_penalty over that token list followed by zl_sample_advance, two launches.  The
      factor is 1.0 (presence 0): the arithmetic per penalised class is the same division, and the two-launch form, which rewrites the
      logits on every call, then leaves them as they are, so that all cells see the same rows throughout.  --parent-so PATH: a library
@@ -30,8 +33,8 @@
      without stop= issues exactly the launches of the commit before the stop conditions: it is the yardstick.
 
   6. --grammar (profiles/sample_grammar.txt, with tools/bench_lookup.py --grammar): the token automaton.  (a) the OFF path --
-     zl_sample_advance, zl_sample_advance_ex and zl_sample_advance_opts as they are called today -- from this library and from
-     --parent-so in the same process, replays alternated.  (b) the launch alone at 1, 8 and 32 rows, masked (zl_sample_advance_fsm, every
+     zl_sample_advance and zl_sample_advance_ex with the penalty group alone, as they are called today -- from this library and from
+     --parent-so in the same process, replays alternated.  (b) the launch alone at 1, 8 and 32 rows, masked (the automaton group, every
      row in a state that allows every other class and owns a 5000-entry exception list) against the same call unmasked;
      the speculative call (both launches) at K = 4 and K = 31 with every draft walking a 5000-entry exception list, against the call
      without tables.  With --step: the whole captured step_sample without tables, with tables and every task unconstrained, and with
@@ -86,9 +89,43 @@ def _stats(ms, per):
     return statistics.median(us), us[len(us) // 10], us[-1 - len(us) // 10]
 
 
-def launch_leg(dev, reps, launches):
+def _p(t):
+    return C.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _opts(**fields):
+    """a zl_sample_opts_t by reference: tensors give their addresses, integers go in as they are"""
+    from zhilight_amd._lib import SampleOpts
+    return C.byref(SampleOpts(**{name: v.data_ptr() if torch.is_tensor(v) else v for name, v in fields.items()}))
+
+
+def _libs(parent_so):
+    """this library and, with --parent-so, the parent's -> ({"this": .., "parent": ..}, whether the parent's _ex entry points can be
+    called).  A parent that still exports zl_sample_advance_opts has the tiered ABI from before zl_sample_opts_t: its zl_sample_advance,
+    whose signature did not change, is measured and its other sampling entry points are skipped."""
+    from zhilight_amd._lib import lib
+    libs, parent_ex = {"this": lib()}, False
+    if parent_so:
+        parent = libs["parent"] = C.CDLL(parent_so)
+        parent.zl_sample_advance.argtypes = libs["this"].zl_sample_advance.argtypes
+        parent_ex = not hasattr(parent, "zl_sample_advance_opts")
+        if parent_ex:
+            parent.zl_sample_advance_ex.argtypes = libs["this"].zl_sample_advance_ex.argtypes
+        else:
+            print("# --parent-so has the tiered sampling ABI (it exports zl_sample_advance_opts): only its zl_sample_advance is measured, "
+                  "its _ex / _opts / _fsm entry points are skipped")
+    return libs, parent_ex
+
+
+def launch_leg(dev, reps, launches, parent_so=None):
     print("# the launch alone, warm rows of %d fp16 logits (normal, sigma 2): us per launch, median [p10 .. p90] over %d alternated "
           "replays of %d launches" % (VOCAB, reps, launches))
+    if parent_so:
+        return plain_entry_leg(dev, reps, launches, parent_so)
     graphs, keep = {}, []
     for rows in (1, 8, 32):
         gen = torch.Generator(device="cpu").manual_seed(rows)
@@ -116,6 +153,44 @@ def launch_leg(dev, reps, launches):
     print("# rows | %-30s | us per launch" % "launch")
     for (rows, name), ms in t.items():
         print("  %4d | %-30s | %7.2f [%7.2f .. %7.2f]" % ((rows, name) + _stats(ms, launches)), flush=True)
+
+
+def plain_entry_leg(dev, reps, launches, parent_so):
+    """--launch-only --parent-so: zl_sample_advance itself from this library and from the parent's, the same rows and parameter sets,
+    replays alternated; says per cell whether this library's median lies inside the parent's own p10 .. p90 band"""
+    libs, _ = _libs(parent_so)
+    i64 = C.c_int64
+    graphs, keep = {}, []
+    for rows in (1, 8, 32):
+        gen = torch.Generator(device="cpu").manual_seed(rows)
+        logits = (torch.randn((rows, VOCAB), generator=gen) * 2).to(torch.float16).to(dev)
+        tok = torch.zeros(rows, dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        for name, t, k, tp, lp in SETS:
+            a = dict(T=torch.full((rows,), t, **f32), k=torch.full((rows,), k, dtype=torch.int32, device=dev), p=torch.full((rows,), tp, **f32),
+                     seeds=torch.arange(rows, dtype=torch.int64, device=dev), draws=torch.zeros(rows, dtype=torch.int64, device=dev),
+                     lp=torch.empty(rows, **f32) if lp else None)
+
+            def plain(l, a=a, logits=logits, tok=tok, rows=rows):
+                for _ in range(launches):
+                    assert l.zl_sample_advance(_p(logits), C.c_int(2), i64(rows), i64(VOCAB), i64(VOCAB), _p(a["T"]), _p(a["k"]), _p(a["p"]),
+                                               _p(a["seeds"]), _p(a["draws"]), _p(None), _p(tok), _p(None), _p(None), _p(None), _p(None),
+                                               _p(a["lp"]), _p(None), _stream()) == 0
+            for which, l in libs.items():
+                graphs[(rows, name, which)] = _graph(lambda l=l, plain=plain: plain(l))
+            keep.append(a)
+        keep.append((logits, tok))
+    t = _alternate(graphs, reps)
+    print("# rows | %-30s | this: zl_sample_advance     | parent: zl_sample_advance   | this median inside the parent's band" % "parameters")
+    inside = True
+    for rows in (1, 8, 32):
+        for name, *_ in SETS:
+            this, parent = _stats(t[(rows, name, "this")], launches), _stats(t[(rows, name, "parent")], launches)
+            ok = parent[1] <= this[0] <= parent[2]
+            inside = inside and ok
+            print("  %4d | %-30s | %7.2f [%7.2f .. %7.2f] | %7.2f [%7.2f .. %7.2f] | %s"
+                  % ((rows, name) + this + parent + ("yes" if ok else "NO",)), flush=True)
+    print("# every cell inside: %s" % ("yes" if inside else "NO"))
 
 
 def step_leg(dev, reps):
@@ -150,12 +225,8 @@ def step_leg(dev, reps):
 
 
 def penalty_leg(dev, reps, launches, parent_so):
-    from zhilight_amd._lib import lib
-    libs = {"this": lib()}
-    if parent_so:
-        libs["parent"] = C.CDLL(parent_so)
-    p = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)           # noqa: E731
-    i64 = C.c_int64
+    libs, _ = _libs(parent_so)
+    p, i64 = _p, C.c_int64
     words = ops.seen_words(VOCAB)
     print("# the launch alone with and without penalties, warm rows of %d fp16 logits (normal, sigma 2), %d ids (about 1 %%) per row in the set, "
           "factor 1.0: us per call, median [p10 .. p90] over %d alternated replays of %d calls" % (VOCAB, VOCAB // 100, reps, launches))
@@ -188,9 +259,9 @@ def penalty_leg(dev, reps, launches, parent_so):
 
             def fused(a=a, head=head):
                 for _ in range(launches):
-                    assert libs["this"].zl_sample_advance_ex(*head(), p(one), p(zero), p(a["seen"]), i64(words), stream()) == 0
+                    assert libs["this"].zl_sample_advance_ex(*head(), _opts(rep_penalty=one, presence=zero, seen=a["seen"], seen_ld=words),
+                                                             stream()) == 0
             for which, l in libs.items():
-                l.zl_sample_advance.argtypes = libs["this"].zl_sample_advance.argtypes
                 graphs[(rows, name, which + ": sample_advance")] = _graph(lambda l=l, plain=plain: plain(l))
                 graphs[(rows, name, which + ": repetition_penalty + sample_advance")] = _graph(lambda l=l, two=two: two(l))
             graphs[(rows, name, "this: sample_advance_ex")] = _graph(fused)
@@ -203,12 +274,8 @@ def penalty_leg(dev, reps, launches, parent_so):
 
 
 def opts_leg(dev, reps, launches, parent_so, with_bias, with_top, rows_list=(1, 8)):
-    from zhilight_amd._lib import lib
-    libs = {"this": lib()}
-    if parent_so:
-        libs["parent"] = C.CDLL(parent_so)
-    p = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)           # noqa: E731
-    i64 = C.c_int64
+    libs, parent_ex = _libs(parent_so)
+    p, i64 = _p, C.c_int64
     words = ops.seen_words(VOCAB)
     print("# the launch alone with a logit bias / top-N, warm rows of %d fp16 logits (normal, sigma 2); the penalty set holds %d ids per row "
           "(factor 1.0), the biases are 0.0: us per call, median [p10 .. p90] over %d alternated replays of %d calls"
@@ -238,14 +305,17 @@ def opts_leg(dev, reps, launches, parent_so, with_bias, with_top, rows_list=(1, 
             head = lambda a=a: (p(logits), C.c_int(2), i64(rows), i64(VOCAB), i64(VOCAB), p(a["T"]), p(a["k"]), p(a["p"]), p(a["seeds"]),   # noqa: E731
                                 p(a["draws"]), p(None), p(tok), p(None), p(None), p(None), p(None), p(a["lp"]), p(None))
             stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)                                                             # noqa: E731
-            pen = lambda a=a: (p(one), p(zero), p(a["seen"]), i64(words))                                                                    # noqa: E731
-            nopen = lambda: (p(None), p(None), p(None), i64(0))                                                                              # noqa: E731
+            pen = lambda a=a: dict(rep_penalty=one, presence=zero, seen=a["seen"], seen_ld=words)                                            # noqa: E731
 
-            def nine(cnt, n):
-                b = bias.get(cnt)
-                t_ = top.get(n)
-                return ((p(b[0]), p(b[1]), p(b[2]), i64(cnt), p(b[3]), i64(words)) if b else (p(None), p(None), p(None), i64(0), p(None), i64(0))) + \
-                       ((C.c_int(n), p(t_[0]), p(t_[1])) if t_ else (C.c_int(0), p(None), p(None)))
+            def fields(seen, cnt, n):
+                """the struct's fields: the penalty group (seen), a bias of cnt entries per row (0: none), top-N n (0: off)"""
+                f = pen() if seen else {}
+                if cnt:
+                    b = bias[cnt]
+                    f.update(bias_ids=b[0], bias_vals=b[1], bias_cnt=b[2], bias_ld=cnt, bias_bits=b[3], bias_bits_ld=words)
+                if n:
+                    f.update(top_n=n, top_ids=top[n][0], top_logprobs=top[n][1])
+                return f
 
             def cell(fn):
                 def run():
@@ -261,22 +331,21 @@ def opts_leg(dev, reps, launches, parent_so, with_bias, with_top, rows_list=(1, 
             def penalise(l):
                 assert l.zl_repetition_penalty(p(one), p(zero), p(ids), p(bid), p(logits), i64(ids.numel()), i64(VOCAB), C.c_int(2), stream()) == 0
             this = libs["this"]
+            opts = lambda l, seen, cnt, n, head=head, fields=fields: l.zl_sample_advance_ex(*head(), _opts(**fields(seen, cnt, n)), stream())   # noqa: E731
             for which, l in libs.items():                                                # the off path, both libraries
-                l.zl_sample_advance.argtypes = this.zl_sample_advance.argtypes
-                l.zl_sample_advance_ex.argtypes = this.zl_sample_advance_ex.argtypes
                 graphs[(rows, name, which + ": sample_advance")] = cell(lambda l=l, head=head: l.zl_sample_advance(*head(), stream()))
-                graphs[(rows, name, which + ": sample_advance_ex (seen)")] = cell(lambda l=l, head=head, pen=pen: l.zl_sample_advance_ex(*head(), *pen(), stream()))
-            opts = lambda pn, cnt, n, head=head: this.zl_sample_advance_opts(*head(), *pn(), *nine(cnt, n), stream())                        # noqa: E731
+                if l is this or parent_ex:
+                    graphs[(rows, name, which + ": sample_advance_ex (seen)")] = cell(lambda l=l, opts=opts: opts(l, True, 0, 0))
             if with_bias:
                 for cnt in (1, 300):
-                    graphs[(rows, name, "opts: bias %d" % cnt)] = cell(lambda cnt=cnt, opts=opts: opts(nopen, cnt, 0))
+                    graphs[(rows, name, "opts: bias %d" % cnt)] = cell(lambda cnt=cnt, opts=opts: opts(this, False, cnt, 0))
                     graphs[(rows, name, "host: scatter_logits %d + sample_advance" % cnt)] = cell(
                         lambda cnt=cnt, head=head: (scatter(this, cnt), this.zl_sample_advance(*head(), stream())))
             if with_top:
                 for n in (5, 20):
-                    graphs[(rows, name, "opts: top-N %d" % n)] = cell(lambda n=n, opts=opts: opts(nopen, 0, n))
+                    graphs[(rows, name, "opts: top-N %d" % n)] = cell(lambda n=n, opts=opts: opts(this, False, 0, n))
             if with_bias and with_top:
-                graphs[(rows, name, "opts: seen + bias 300 + top-N 5")] = cell(lambda opts=opts, pen=pen: opts(pen, 300, 5))
+                graphs[(rows, name, "opts: seen + bias 300 + top-N 5")] = cell(lambda opts=opts: opts(this, True, 300, 5))
                 graphs[(rows, name, "host: repetition_penalty + scatter_logits 300 + sample_advance")] = cell(
                     lambda head=head: (penalise(this), scatter(this, 300), this.zl_sample_advance(*head(), stream())))
             keep.append(a)
@@ -386,12 +455,8 @@ def _bench_automaton(n, dev):
 
 
 def grammar_leg(dev, reps, launches, parent_so):
-    from zhilight_amd._lib import lib
-    libs = {"this": lib()}
-    if parent_so:
-        libs["parent"] = C.CDLL(parent_so)
-    p = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)           # noqa: E731
-    i64 = C.c_int64
+    libs, parent_ex = _libs(parent_so)
+    p, i64 = _p, C.c_int64
     words = ops.seen_words(VOCAB)
     fsm = _bench_automaton(VOCAB, dev)
     print("# the token automaton: warm rows of %d fp16 logits (normal, sigma 2), T 0.8, top-k 40, top-p 0.95; a state allows every other class, "
@@ -413,9 +478,7 @@ def grammar_leg(dev, reps, launches, parent_so):
         head = lambda a=a, logits=logits, tok=tok, rows=rows: (p(logits), C.c_int(2), i64(rows), i64(VOCAB), i64(VOCAB), p(a["T"]), p(a["k"]),   # noqa: E731
                                                                 p(a["p"]), p(a["seeds"]), p(a["draws"]), p(None), p(tok), p(None), p(None), p(None),
                                                                 p(None), p(a["lp"]), p(None))
-        pen = lambda a=a, one=one, zero=zero: (p(one), p(zero), p(a["seen"]), i64(words))                                                        # noqa: E731
-        nopen = (p(None), p(None), p(None), i64(0))
-        nine = (p(None), p(None), p(None), i64(0), p(None), i64(0), C.c_int(0), p(None), p(None))
+        pen = lambda a=a, one=one, zero=zero: dict(rep_penalty=one, presence=zero, seen=a["seen"], seen_ld=words)                                # noqa: E731
 
         def cell(fn):
             def run():
@@ -424,21 +487,19 @@ def grammar_leg(dev, reps, launches, parent_so):
             return _graph(run)
         this = libs["this"]
         for which, l in libs.items():                                        # (a) the off path, both libraries
-            for name in ("zl_sample_advance", "zl_sample_advance_ex", "zl_sample_advance_opts"):
-                getattr(l, name).argtypes = getattr(this, name).argtypes
             graphs[(rows, which + ": sample_advance")] = cell(lambda l=l, head=head: l.zl_sample_advance(*head(), stream()))
-            graphs[(rows, which + ": sample_advance_ex (seen)")] = cell(lambda l=l, head=head, pen=pen: l.zl_sample_advance_ex(*head(), *pen(), stream()))
-            graphs[(rows, which + ": sample_advance_opts (seen, all nine off)")] = cell(
-                lambda l=l, head=head, pen=pen: l.zl_sample_advance_opts(*head(), *pen(), *nine, stream()))
+            if l is this or parent_ex:
+                graphs[(rows, which + ": sample_advance_ex (seen)")] = cell(lambda l=l, head=head, pen=pen: l.zl_sample_advance_ex(*head(), _opts(**pen()),
+                                                                                                                             stream()))
         st = torch.zeros(rows, dtype=torch.int32, device=dev)                # (b) masked: the rows start in state 0 and move between the two
-        tables = lambda st=st: (p(fsm[0]), i64(fsm[0].shape[1]), p(fsm[1]), p(fsm[2]), p(fsm[3]), p(fsm[4]), i64(fsm[0].shape[0]),            # noqa: E731
-                                i64(fsm[3].numel()), p(st))
-        graphs[(rows, "fsm: masked")] = cell(lambda head=head, tables=tables: this.zl_sample_advance_fsm(*head(), *nopen, *nine, *tables(), stream()))
-        graphs[(rows, "fsm: masked + seen")] = cell(lambda head=head, pen=pen, tables=tables: this.zl_sample_advance_fsm(*head(), *pen(), *nine, *tables(),
-                                                                                                                        stream()))
+        tables = lambda st=st: dict(fsm_mask=fsm[0], fsm_mask_ld=fsm[0].shape[1], fsm_default=fsm[1], fsm_exc_off=fsm[2], fsm_exc_tok=fsm[3],    # noqa: E731
+                                    fsm_exc_next=fsm[4], fsm_states=fsm[0].shape[0], fsm_exceptions=fsm[3].numel(), fsm_state=st)
+        graphs[(rows, "fsm: masked")] = cell(lambda head=head, tables=tables: this.zl_sample_advance_ex(*head(), _opts(**tables()), stream()))
+        graphs[(rows, "fsm: masked + seen")] = cell(lambda head=head, pen=pen, tables=tables: this.zl_sample_advance_ex(*head(), _opts(**pen(), **tables()),
+                                                                                                                       stream()))
         free = torch.full((rows,), -1, dtype=torch.int32, device=dev)
         graphs[(rows, "fsm: tables, every row unconstrained")] = cell(
-            lambda head=head, tables=tables, free=free: this.zl_sample_advance_fsm(*head(), *nopen, *nine, *tables(free), stream()))
+            lambda head=head, tables=tables, free=free: this.zl_sample_advance_ex(*head(), _opts(**tables(free)), stream()))
         keep.append((logits, ids, tok, one, zero, a, st, free))
     t = _alternate(graphs, reps)
     print("# rows | %-50s | us per call" % "call")
@@ -446,7 +507,7 @@ def grammar_leg(dev, reps, launches, parent_so):
         print("  %4d | %-50s | %7.2f [%7.2f .. %7.2f]" % ((rows, which) + _stats(ms, launches)), flush=True)
     # the speculative call: the chain's worst case, every draft allowed and an exception of its state
     chain = fsm
-    print("# zl_spec_sample_accept(_fsm), B = 1, both launches: every draft hits a 5000-entry exception list (the states alternate); us per call")
+    print("# zl_spec_sample_accept(_ex with the automaton), B = 1, both launches: every draft hits a 5000-entry exception list (the states alternate); us per call")
     graphs, keep = {}, []
     for K in (4, 31):
         len_q = K + 1
@@ -574,7 +635,7 @@ def main():
             opts_step_leg(dev, a.reps)
         return
     if not a.step_only:
-        launch_leg(dev, a.reps, a.launches)
+        launch_leg(dev, a.reps, a.launches, a.parent_so)
     if not a.launch_only:
         step_leg(dev, a.reps)
 

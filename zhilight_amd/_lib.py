@@ -23,7 +23,7 @@ SYMBOLS = [
     "zl_moe_fill_m_indices",
     "zl_embedding_rope",
     "zl_fp8_per_token_cast", "zl_fp8_block_dequant", "zl_fp8_block_gemm_group", "zl_fp8_block_packed_bytes", "zl_fp8_block_pack", "zl_fp8_block_gemm_group_packed", "zl_moe_top_k_softmax", "zl_moe_group_topk",
-    "zl_cast", "zl_copy_2d", "zl_index_select", "zl_argmax_advance", "zl_arange_i32", "zl_divide_i32", "zl_scatter_update_dim0", "zl_sort_pairs_i32", "zl_log_softmax_bias", "zl_softmax_rows", "zl_topk_rows", "zl_gather_logits", "zl_scatter_logits", "zl_repetition_penalty", "zl_spec_accept", "zl_lookup_draft", "zl_stop_advance", "zl_slots_admit", "zl_sample_advance", "zl_spec_sample_accept", "zl_sample_advance_ex", "zl_spec_sample_accept_ex", "zl_seen_mark", "zl_sample_advance_opts", "zl_spec_sample_accept_opts", "zl_sample_advance_fsm", "zl_spec_sample_accept_fsm", "zl_slots_admit_fsm", "zl_reduce_abs_max", "zl_binary_op", "zl_scale", "zl_act_inplace",
+    "zl_cast", "zl_copy_2d", "zl_index_select", "zl_argmax_advance", "zl_arange_i32", "zl_divide_i32", "zl_scatter_update_dim0", "zl_sort_pairs_i32", "zl_log_softmax_bias", "zl_softmax_rows", "zl_topk_rows", "zl_gather_logits", "zl_scatter_logits", "zl_repetition_penalty", "zl_spec_accept", "zl_lookup_draft", "zl_stop_advance", "zl_slots_admit", "zl_sample_advance", "zl_spec_sample_accept", "zl_sample_advance_ex", "zl_spec_sample_accept_ex", "zl_seen_mark", "zl_slots_admit_fsm", "zl_reduce_abs_max", "zl_binary_op", "zl_scale", "zl_act_inplace",
     "zl_count_nonfinite", "zl_perm_narrow_u16", "zl_perm_reverse_u16", "zl_permute_input_u16", "zl_gptq_permute_rows",
     "zl_version", "zl_status_string", "zl_device_cu_count",
     "zl_gptq_shuffle", "zl_gptq_increase_zero", "zl_gptq_q4_to_q8", "zl_transpose_2d", "zl_gptq_reconstruct",
@@ -65,6 +65,15 @@ class W4Opts(C.Structure):
         "phase_rounds", "phase_ksplit", "phase_ksplit_min_m", "phase_min_m", "phase_max_m", "phase_small_off",
         "tiled_min_m", "tiled_bm", "tiled_splitk", "mfma_ks", "mfma_rounds", "small_algo", "tiled_wide",
         "slab", "slab_min_m", "slab_nw", "slab_gpw", "slab_r", "defer_norm")] + [("row_ss", C.c_void_p), ("row_ss_out", C.c_void_p)]
+
+
+class SampleOpts(C.Structure):
+    """zl_sample_opts_t: the options of zl_sample_advance_ex / zl_spec_sample_accept_ex, every field 8 bytes wide; all zero = no option"""
+    _fields_ = [(n, C.c_int64 if n in ("seen_ld", "bias_ld", "bias_bits_ld", "top_n", "fsm_mask_ld", "fsm_states", "fsm_exceptions")
+                 else C.c_void_p) for n in (
+        "rep_penalty", "presence", "seen", "seen_ld", "bias_ids", "bias_vals", "bias_cnt", "bias_ld", "bias_bits", "bias_bits_ld",
+        "top_n", "top_ids", "top_logprobs", "fsm_mask", "fsm_mask_ld", "fsm_default", "fsm_exc_off", "fsm_exc_tok", "fsm_exc_next",
+        "fsm_states", "fsm_exceptions", "fsm_state", "fsm_row_states")]
 
 
 class W4Layout(C.Structure):
@@ -109,21 +118,11 @@ def lib():
         l.zl_spec_sample_accept.restype = C.c_int
         l.zl_spec_sample_accept.argtypes = [C.c_void_p, C.c_int] + [C.c_int64] * 4 + [C.c_void_p] * 17
         l.zl_sample_advance_ex.restype = C.c_int
-        l.zl_sample_advance_ex.argtypes = [C.c_void_p, C.c_int] + [C.c_int64] * 3 + [C.c_void_p] * 16 + [C.c_int64, C.c_void_p]
+        # opts: C.byref(SampleOpts) or None.  Declared as a plain pointer, like every other struct argument here: a typed
+        # POINTER(SampleOpts) would refuse the class of a reloaded module (tests/test_abi.py reloads this one)
+        l.zl_sample_advance_ex.argtypes = l.zl_sample_advance.argtypes[:-1] + [C.c_void_p, C.c_void_p]
         l.zl_spec_sample_accept_ex.restype = C.c_int
-        l.zl_spec_sample_accept_ex.argtypes = [C.c_void_p, C.c_int] + [C.c_int64] * 4 + [C.c_void_p] * 19 + [C.c_int64, C.c_void_p]
-        opts = [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]      # the nine arguments of the _opts calls
-        l.zl_sample_advance_opts.restype = C.c_int
-        l.zl_sample_advance_opts.argtypes = [C.c_void_p, C.c_int] + [C.c_int64] * 3 + [C.c_void_p] * 16 + [C.c_int64] + opts + [C.c_void_p]
-        l.zl_spec_sample_accept_opts.restype = C.c_int
-        l.zl_spec_sample_accept_opts.argtypes = [C.c_void_p, C.c_int] + [C.c_int64] * 4 + [C.c_void_p] * 19 + [C.c_int64] + opts + [C.c_void_p]
-        fsm = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] * 2 + [C.c_void_p]      # the tables, S, E and fsm_state of the _fsm calls
-        l.zl_sample_advance_fsm.restype = C.c_int
-        l.zl_sample_advance_fsm.argtypes = ([C.c_void_p, C.c_int] + [C.c_int64] * 3 + [C.c_void_p] * 16 + [C.c_int64] + opts + fsm
-                                            + [C.c_void_p])
-        l.zl_spec_sample_accept_fsm.restype = C.c_int
-        l.zl_spec_sample_accept_fsm.argtypes = ([C.c_void_p, C.c_int] + [C.c_int64] * 4 + [C.c_void_p] * 19 + [C.c_int64] + opts + fsm
-                                                + [C.c_void_p] * 2)
+        l.zl_spec_sample_accept_ex.argtypes = l.zl_spec_sample_accept.argtypes[:-1] + [C.c_void_p, C.c_void_p]
         l.zl_stop_advance.restype = C.c_int
         l.zl_stop_advance.argtypes = ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_int64] * 2
                                       + [C.c_void_p] * 9)

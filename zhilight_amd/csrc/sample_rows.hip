@@ -1036,222 +1036,122 @@ __global__ void k_seen_mark(uint32_t* __restrict__ seen, int64_t seen_ld, int64_
     if (id >= 0 && id < n) atomicOr(&seen[t * seen_ld + (id >> 5)], 1u << (id & 31));
 }
 
-// the _opts arguments' own refusals (0 = fine), behind the plain calls' checks
-int opts_check(const Opts& o, int64_t n) {
-    const int given = (o.bias_ids != nullptr) + (o.bias_vals != nullptr) + (o.bias_cnt != nullptr) + (o.bias_bits != nullptr);
-    ZL_CHECK_ARG(given == 0 || given == 4, ZL_EINVAL);
-    ZL_CHECK_ARG(o.top_n <= 0 || (o.top_ids && o.top_lp), ZL_EINVAL);
-    ZL_CHECK_ARG(given == 0 || (o.bias_ld >= 1 && o.bias_ld <= 1024 && o.bias_bits_ld >= (n + 31) / 32), ZL_ESHAPE);
-    ZL_CHECK_ARG(o.top_n >= 0 && o.top_n <= kMaxTop, ZL_ESHAPE);
-    return 0;
-}
+constexpr zl_sample_opts_t kNoOpts{};                                   // opts == NULL
 
-// the _fsm arguments' own refusals (0 = fine); E arrives as the caller's int64
-int fsm_check(const Fsm& fa, int64_t S, int64_t E, int64_t n, bool spec) {
-    const int given = (fa.mask != nullptr) + (fa.dflt != nullptr) + (fa.exc_off != nullptr) + (fa.exc_tok != nullptr) + (fa.exc_next != nullptr) +
-                      (fa.state != nullptr);
-    ZL_CHECK_ARG(given == 0 || given == 6, ZL_EINVAL);
-    if (given == 0) return 0;
-    ZL_CHECK_ARG(!spec || fa.row_states, ZL_EINVAL);
-    ZL_CHECK_ARG(S >= 1 && S < ((int64_t)1 << 31) && E >= 0 && E < ((int64_t)1 << 31) && fa.mask_ld >= (n + 31) / 32, ZL_ESHAPE);
-    return 0;
-}
-
-// the two launchers.  MODE: 2 where a bias or top-N is asked for, else 1 <=> seen != NULL, else 0 -- so the plain and _ex entry
-// points, and an _opts call with its nine arguments NULL / 0, launch the instantiations they always have
-int sample_advance_launch(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
-                          const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
-                          int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
-                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const Opts& o, Fsm fa, int64_t S,
-                          int64_t E, zl_stream_t s) {
-    ZL_CHECK_ARG(logits && temperature && top_k && top_p, ZL_EINVAL);
+// every refusal the two operations share (0 = fine), in the order of their codes: the pointers (own_ptrs: the operation's own),
+// the shape (own_shape: the operation's own), the dtype, then the bias / top-N group's checks and the automaton's
+int sample_check(const void* logits, int type, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k, const float* top_p,
+                 const int64_t* seeds, const int64_t* draws, const float* u_in, bool own_ptrs, bool own_shape, const zl_sample_opts_t& so,
+                 bool spec) {
+    ZL_CHECK_ARG(logits && temperature && top_k && top_p && own_ptrs, ZL_EINVAL);
     ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
-    ZL_CHECK_ARG(tokens || next_tokens, ZL_EINVAL);
-    ZL_CHECK_ARG(!seen || (rep_penalty && presence), ZL_EINVAL);
-    ZL_CHECK_ARG(rows >= 1 && n >= 1 && ld >= n && n < ((int64_t)1 << 31) && rows < ((int64_t)1 << 31), ZL_ESHAPE);
-    ZL_CHECK_ARG(!seen || seen_ld >= (n + 31) / 32, ZL_ESHAPE);
+    ZL_CHECK_ARG(!so.seen || (so.rep_penalty && so.presence), ZL_EINVAL);
+    ZL_CHECK_ARG(own_shape && n >= 1 && ld >= n && n < ((int64_t)1 << 31), ZL_ESHAPE);
+    ZL_CHECK_ARG(!so.seen || so.seen_ld >= (n + 31) / 32, ZL_ESHAPE);
     ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
-    if (const int e = opts_check(o, n)) return e;
-    if (const int e = fsm_check(fa, S, E, n, false)) return e;
-    fa.S = (int)S, fa.E = (int)E;
-    const dim3 g((unsigned)rows), b(kThreads);
-    hipStream_t hs = (hipStream_t)s;
-    const int mode = fa.mask ? 3 : (o.bias_ids || o.top_n > 0) ? 2 : (seen ? 1 : 0);
-#define ZL_ARGS                                                                                                                              \
-    (const uint16_t*)logits, ld, (int)n, 1, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens, next_tokens, \
-        logprobs, u_out, rep_penalty, presence, seen, seen_ld, (const int32_t*)nullptr
-#define ZL_SAMPLE(BF, PEN) hipLaunchKernelGGL((k_sample_advance<BF, false, PEN>), g, b, 0, hs, ZL_ARGS)
-#define ZL_SAMPLE_OPTS(BF) hipLaunchKernelGGL((k_sample_advance_opts<BF, false>), g, b, 0, hs, ZL_ARGS, o)
-#define ZL_SAMPLE_FSM(BF) hipLaunchKernelGGL((k_sample_advance_fsm<BF, false>), g, b, 0, hs, ZL_ARGS, o, fa)
-    if (type == ZL_T_F16) {
-        if (mode == 3) ZL_SAMPLE_FSM(false);
-        else if (mode == 2) ZL_SAMPLE_OPTS(false);
-        else if (mode == 1) ZL_SAMPLE(false, true);
-        else ZL_SAMPLE(false, false);
-    } else {
-        if (mode == 3) ZL_SAMPLE_FSM(true);
-        else if (mode == 2) ZL_SAMPLE_OPTS(true);
-        else if (mode == 1) ZL_SAMPLE(true, true);
-        else ZL_SAMPLE(true, false);
-    }
-#undef ZL_SAMPLE
-#undef ZL_SAMPLE_OPTS
-#undef ZL_SAMPLE_FSM
-#undef ZL_ARGS
-    return zl_launch_status();
-}
-
-int spec_sample_accept_launch(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
-                              const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
-                              const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
-                              int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
-                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const Opts& o, Fsm fa,
-                              int64_t S, int64_t E, zl_stream_t s) {
-    ZL_CHECK_ARG(logits && temperature && top_k && top_p && drafts && accepted && out_tokens, ZL_EINVAL);
-    ZL_CHECK_ARG((seeds && draws) || u_in, ZL_EINVAL);
-    ZL_CHECK_ARG(out_logprobs || !logprobs, ZL_EINVAL);                 // the task's log-probability is read from its rows'
-    ZL_CHECK_ARG(!seen || (rep_penalty && presence), ZL_EINVAL);
-    ZL_CHECK_ARG(b >= 1 && len_q >= 2 && len_q <= kMaxDrafts + 1 && n >= 1 && ld >= n && n < ((int64_t)1 << 31) && b < ((int64_t)1 << 31) &&
-                     b * len_q < ((int64_t)1 << 31),
+    const int bias = (so.bias_ids != nullptr) + (so.bias_vals != nullptr) + (so.bias_cnt != nullptr) + (so.bias_bits != nullptr);
+    ZL_CHECK_ARG(bias == 0 || bias == 4, ZL_EINVAL);
+    ZL_CHECK_ARG(so.top_n <= 0 || (so.top_ids && so.top_logprobs), ZL_EINVAL);
+    ZL_CHECK_ARG(bias == 0 || (so.bias_ld >= 1 && so.bias_ld <= 1024 && so.bias_bits_ld >= (n + 31) / 32), ZL_ESHAPE);
+    ZL_CHECK_ARG(so.top_n >= 0 && so.top_n <= kMaxTop, ZL_ESHAPE);
+    const int fsm = (so.fsm_mask != nullptr) + (so.fsm_default != nullptr) + (so.fsm_exc_off != nullptr) + (so.fsm_exc_tok != nullptr) +
+                    (so.fsm_exc_next != nullptr) + (so.fsm_state != nullptr);
+    ZL_CHECK_ARG(fsm == 0 || fsm == 6, ZL_EINVAL);
+    if (fsm == 0) return 0;
+    ZL_CHECK_ARG(!spec || so.fsm_row_states, ZL_EINVAL);
+    ZL_CHECK_ARG(so.fsm_states >= 1 && so.fsm_states < ((int64_t)1 << 31) && so.fsm_exceptions >= 0 && so.fsm_exceptions < ((int64_t)1 << 31) &&
+                     so.fsm_mask_ld >= (n + 31) / 32,
                  ZL_ESHAPE);
-    ZL_CHECK_ARG(!seen || seen_ld >= (n + 31) / 32, ZL_ESHAPE);
-    ZL_CHECK_ARG(type == ZL_T_F16 || type == ZL_T_BF16, ZL_EDTYPE);
-    if (const int e = opts_check(o, n)) return e;
-    if (const int e = fsm_check(fa, S, E, n, true)) return e;
-    fa.S = (int)S, fa.E = (int)E;
-    // the picks: one 1024-thread workgroup per logit row, zl_sample_advance's kernel under the task's parameters, into out_tokens
-    const dim3 g((unsigned)(b * len_q)), blk(kThreads);
-    hipStream_t hs = (hipStream_t)s;
-    const int mode = fa.mask ? 3 : (o.bias_ids || o.top_n > 0) ? 2 : (seen ? 1 : 0);
-#define ZL_ARGS                                                                                                                          \
-    (const uint16_t*)logits, ld, (int)n, (int)len_q, temperature, top_k, top_p, seeds, draws, u_in, out_tokens, nullptr, nullptr, nullptr, nullptr, \
-        out_logprobs, u_out, rep_penalty, presence, seen, seen_ld, drafts
-#define ZL_SAMPLE(BF, PEN) hipLaunchKernelGGL((k_sample_advance<BF, true, PEN>), g, blk, 0, hs, ZL_ARGS)
-#define ZL_SAMPLE_OPTS(BF) hipLaunchKernelGGL((k_sample_advance_opts<BF, true>), g, blk, 0, hs, ZL_ARGS, o)
-#define ZL_SAMPLE_FSM(BF) hipLaunchKernelGGL((k_sample_advance_fsm<BF, true>), g, blk, 0, hs, ZL_ARGS, o, fa)
-    if (type == ZL_T_F16) {
-        if (mode == 3) ZL_SAMPLE_FSM(false);
-        else if (mode == 2) ZL_SAMPLE_OPTS(false);
-        else if (mode == 1) ZL_SAMPLE(false, true);
-        else ZL_SAMPLE(false, false);
-    } else {
-        if (mode == 3) ZL_SAMPLE_FSM(true);
-        else if (mode == 2) ZL_SAMPLE_OPTS(true);
-        else if (mode == 1) ZL_SAMPLE(true, true);
-        else ZL_SAMPLE(true, false);
-    }
-#undef ZL_SAMPLE
-#undef ZL_SAMPLE_OPTS
-#undef ZL_SAMPLE_FSM
-#undef ZL_ARGS
-    const int e = zl_launch_status();
-    if (e) return e;
-#define ZL_ACCEPT(TOP, FSM, grid, tn, ti, tl)                                                                                                  \
-    hipLaunchKernelGGL((k_spec_sample_accept<TOP, FSM>), grid, dim3(64), 0, hs, drafts, out_tokens, out_logprobs, accepted, tokens, positions,   \
-                       placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q, seen, seen_ld, tn, ti, tl, fa.state,        \
-                       (const int32_t*)fa.row_states)
-    const dim3 per_task((unsigned)b), per_lane((unsigned)((b + 63) / 64));
-    if (o.top_n > 0) {
-        if (mode == 3) ZL_ACCEPT(true, true, per_task, o.top_n, o.top_ids, o.top_lp);
-        else ZL_ACCEPT(true, false, per_task, o.top_n, o.top_ids, o.top_lp);
-    } else {
-        if (mode == 3) ZL_ACCEPT(false, true, per_lane, 0, (int32_t*)nullptr, (float*)nullptr);
-        else ZL_ACCEPT(false, false, per_lane, 0, (int32_t*)nullptr, (float*)nullptr);
-    }
-#undef ZL_ACCEPT
-    return zl_launch_status();
+    return 0;
+}
+
+// the one selection and launch of k_sample_advance*, one 1024-thread workgroup per logit row; a... = the 22 arguments every
+// instantiation takes.  MODE: 3 with an automaton, else 2 where a bias or top-N is asked for, else 1 <=> seen != NULL, else 0 -- so
+// a call without options launches the instantiation it always has, and a bias without seen stays MODE 2
+template <bool BF, bool SPEC, class... A>
+void launch_rows_as(const zl_sample_opts_t& so, unsigned grid, hipStream_t hs, A... a) {
+    const Opts o{so.bias_ids, so.bias_vals, so.bias_cnt, so.bias_ld, so.bias_bits, so.bias_bits_ld, (int)so.top_n, so.top_ids, so.top_logprobs};
+    const Fsm fa{so.fsm_mask,     so.fsm_mask_ld,     so.fsm_default,         so.fsm_exc_off, so.fsm_exc_tok,
+                 so.fsm_exc_next, (int)so.fsm_states, (int)so.fsm_exceptions, so.fsm_state,   SPEC ? so.fsm_row_states : nullptr};
+    const dim3 g(grid), b(kThreads);
+    if (so.fsm_mask) hipLaunchKernelGGL((k_sample_advance_fsm<BF, SPEC>), g, b, 0, hs, a..., o, fa);
+    else if (so.bias_ids || so.top_n > 0) hipLaunchKernelGGL((k_sample_advance_opts<BF, SPEC>), g, b, 0, hs, a..., o);
+    else if (so.seen) hipLaunchKernelGGL((k_sample_advance<BF, SPEC, true>), g, b, 0, hs, a...);
+    else hipLaunchKernelGGL((k_sample_advance<BF, SPEC, false>), g, b, 0, hs, a...);
+}
+
+template <bool SPEC, class... A>
+void launch_rows(int type, const zl_sample_opts_t& so, unsigned grid, hipStream_t hs, A... a) {
+    if (type == ZL_T_F16) launch_rows_as<false, SPEC>(so, grid, hs, a...);
+    else launch_rows_as<true, SPEC>(so, grid, hs, a...);
 }
 
 }  // namespace
 
 extern "C" {
 
-int zl_sample_advance(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
-                      const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
-                      int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out, zl_stream_t s) {
-    return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
-                                 next_tokens, logprobs, u_out, nullptr, nullptr, nullptr, 0, Opts{}, Fsm{}, 0, 0, s);
-}
-
 int zl_sample_advance_ex(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
                          const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
                          int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
-                         const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
-    return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
-                                 next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld, Opts{}, Fsm{}, 0, 0, s);
+                         const zl_sample_opts_t* opts, zl_stream_t s) {
+    const zl_sample_opts_t& so = opts ? *opts : kNoOpts;
+    if (const int e = sample_check(logits, type, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens || next_tokens,
+                                   rows >= 1 && rows < ((int64_t)1 << 31), so, false))
+        return e;
+    launch_rows<false>(type, so, (unsigned)rows, (hipStream_t)s, (const uint16_t*)logits, ld, (int)n, 1, temperature, top_k, top_p, seeds, draws,
+                       u_in, tokens, positions, placement, valid_lens, next_tokens, logprobs, u_out, so.rep_penalty, so.presence, so.seen,
+                       so.seen_ld, (const int32_t*)nullptr);
+    return zl_launch_status();
 }
 
-int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
-                          const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
-                          const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
-                          int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out, zl_stream_t s) {
-    return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
-                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, nullptr, nullptr, nullptr, 0, Opts{}, Fsm{}, 0, 0, s);
+int zl_sample_advance(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
+                      const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
+                      int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out, zl_stream_t s) {
+    return zl_sample_advance_ex(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement,
+                                valid_lens, next_tokens, logprobs, u_out, nullptr, s);
 }
 
 int zl_spec_sample_accept_ex(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
                              const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
                              const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
                              int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
-                             const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, zl_stream_t s) {
-    return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
-                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, rep_penalty, presence, seen,
-                                     seen_ld, Opts{}, Fsm{}, 0, 0, s);
+                             const zl_sample_opts_t* opts, zl_stream_t s) {
+    const zl_sample_opts_t& so = opts ? *opts : kNoOpts;
+    if (const int e = sample_check(logits, type, n, ld, temperature, top_k, top_p, seeds, draws, u_in,
+                                   drafts && accepted && out_tokens && (out_logprobs || !logprobs),   // the task's log-probability is read from its rows'
+                                   b >= 1 && len_q >= 2 && len_q <= kMaxDrafts + 1 && b < ((int64_t)1 << 31) && b * len_q < ((int64_t)1 << 31),
+                                   so, true))
+        return e;
+    // the picks: zl_sample_advance's kernel under the task's parameters, into out_tokens
+    hipStream_t hs = (hipStream_t)s;
+    launch_rows<true>(type, so, (unsigned)(b * len_q), hs, (const uint16_t*)logits, ld, (int)n, (int)len_q, temperature, top_k, top_p, seeds, draws,
+                      u_in, out_tokens, nullptr, nullptr, nullptr, nullptr, out_logprobs, u_out, so.rep_penalty, so.presence, so.seen, so.seen_ld,
+                      drafts);
+    if (const int e = zl_launch_status()) return e;
+#define ZL_ACCEPT(TOP, FSM, grid, tn, ti, tl)                                                                                                  \
+    hipLaunchKernelGGL((k_spec_sample_accept<TOP, FSM>), grid, dim3(64), 0, hs, drafts, out_tokens, out_logprobs, accepted, tokens, positions,   \
+                       placement, valid_lens, logprobs, u_in ? nullptr : draws, (int)b, (int)len_q, so.seen, so.seen_ld, tn, ti, tl,            \
+                       so.fsm_state, (const int32_t*)so.fsm_row_states)
+    const dim3 per_task((unsigned)b), per_lane((unsigned)((b + 63) / 64));
+    if (so.top_n > 0) {
+        if (so.fsm_mask) ZL_ACCEPT(true, true, per_task, (int)so.top_n, so.top_ids, so.top_logprobs);
+        else ZL_ACCEPT(true, false, per_task, (int)so.top_n, so.top_ids, so.top_logprobs);
+    } else {
+        if (so.fsm_mask) ZL_ACCEPT(false, true, per_lane, 0, (int32_t*)nullptr, (float*)nullptr);
+        else ZL_ACCEPT(false, false, per_lane, 0, (int32_t*)nullptr, (float*)nullptr);
+    }
+#undef ZL_ACCEPT
+    return zl_launch_status();
 }
 
-int zl_sample_advance_opts(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
-                           const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
-                           int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
-                           const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
-                           const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits, int64_t bias_bits_ld,
-                           int top_n, int32_t* top_ids, float* top_logprobs, zl_stream_t s) {
-    return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
-                                 next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld,
-                                 Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs}, Fsm{}, 0, 0, s);
+int zl_spec_sample_accept(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
+                          const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
+                          const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
+                          int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out, zl_stream_t s) {
+    return zl_spec_sample_accept_ex(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
+                                    placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, nullptr, s);
 }
 
-int zl_spec_sample_accept_opts(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
-                               const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
-                               const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
-                               int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
-                               const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
-                               const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits,
-                               int64_t bias_bits_ld, int top_n, int32_t* top_ids, float* top_logprobs, zl_stream_t s) {
-    return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
-                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, rep_penalty, presence, seen,
-                                     seen_ld, Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs},
-                                     Fsm{}, 0, 0, s);
-}
-
-int zl_sample_advance_fsm(const void* logits, int type, int64_t rows, int64_t n, int64_t ld, const float* temperature, const int32_t* top_k,
-                          const float* top_p, const int64_t* seeds, int64_t* draws, const float* u_in, int32_t* tokens, int32_t* positions,
-                          int32_t* placement, int32_t* valid_lens, int64_t* next_tokens, float* logprobs, float* u_out,
-                          const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
-                          const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits, int64_t bias_bits_ld,
-                          int top_n, int32_t* top_ids, float* top_logprobs, const uint32_t* fsm_mask, int64_t mask_ld,
-                          const int32_t* fsm_default, const int32_t* fsm_exc_off, const int32_t* fsm_exc_tok, const int32_t* fsm_exc_next,
-                          int64_t S, int64_t E, int32_t* fsm_state, zl_stream_t s) {
-    return sample_advance_launch(logits, type, rows, n, ld, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions, placement, valid_lens,
-                                 next_tokens, logprobs, u_out, rep_penalty, presence, seen, seen_ld,
-                                 Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs},
-                                 Fsm{fsm_mask, mask_ld, fsm_default, fsm_exc_off, fsm_exc_tok, fsm_exc_next, 0, 0, fsm_state, nullptr}, S, E, s);
-}
-
-int zl_spec_sample_accept_fsm(const void* logits, int type, int64_t b, int64_t len_q, int64_t n, int64_t ld, const int32_t* drafts,
-                              const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seeds, int64_t* draws,
-                              const float* u_in, int32_t* tokens, int32_t* positions, int32_t* placement, int32_t* valid_lens,
-                              int32_t* accepted, int32_t* out_tokens, float* out_logprobs, float* logprobs, float* u_out,
-                              const float* rep_penalty, const float* presence, uint32_t* seen, int64_t seen_ld, const int32_t* bias_ids,
-                              const float* bias_vals, const int32_t* bias_cnt, int64_t bias_ld, const uint32_t* bias_bits,
-                              int64_t bias_bits_ld, int top_n, int32_t* top_ids, float* top_logprobs, const uint32_t* fsm_mask,
-                              int64_t mask_ld, const int32_t* fsm_default, const int32_t* fsm_exc_off, const int32_t* fsm_exc_tok,
-                              const int32_t* fsm_exc_next, int64_t S, int64_t E, int32_t* fsm_state, int32_t* row_states, zl_stream_t s) {
-    return spec_sample_accept_launch(logits, type, b, len_q, n, ld, drafts, temperature, top_k, top_p, seeds, draws, u_in, tokens, positions,
-                                     placement, valid_lens, accepted, out_tokens, out_logprobs, logprobs, u_out, rep_penalty, presence, seen,
-                                     seen_ld, Opts{bias_ids, bias_vals, bias_cnt, bias_ld, bias_bits, bias_bits_ld, top_n, top_ids, top_logprobs},
-                                     Fsm{fsm_mask, mask_ld, fsm_default, fsm_exc_off, fsm_exc_tok, fsm_exc_next, 0, 0, fsm_state, row_states}, S, E,
-                                     s);
-}
 
 int zl_seen_mark(uint32_t* seen, int64_t seen_ld, int64_t b, int64_t n, const int32_t* tokens, int64_t n_tok, int64_t tok_ld, zl_stream_t s) {
     ZL_CHECK_ARG(seen && tokens, ZL_EINVAL);

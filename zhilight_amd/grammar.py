@@ -1,4 +1,5 @@
-"""Token automata for constrained output (numpy only): the host half of zl_sample_advance_fsm / zl_spec_sample_accept_fsm.
+"""Token automata for constrained output (numpy only): the host half of zl_sample_opts_t's automaton group
+(zl_sample_advance_ex / zl_spec_sample_accept_ex).
 
 A TokenAutomaton is a DFA over token ids.  pack() turns it into the five device tables of include/zhilight_amd.h -- per state a dense
 allow-bitmap over the vocabulary, a default next state and an ascending exception list in CSR form -- which LLaMA.load_grammar copies

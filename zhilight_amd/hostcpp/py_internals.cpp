@@ -6,8 +6,11 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cstddef>
+
 #include "bm_functions.h"
 #include "nn_amd.h"
+#include "zhilight_amd.h"
 
 namespace py = pybind11;
 using namespace bmengine;
@@ -66,11 +69,38 @@ struct PyCtx {
 const int kBF = (int)DataType::kBFloat16;
 const char* fdt(bool bf16) { return bf16 ? "uint16" : "float16"; }
 
+// the C compiler's view of the option structs that _lib.py mirrors in ctypes: {struct: (sizeof, [(field, offsetof), ...])}, the
+// fields in declaration order
+py::dict struct_layouts() {
+    py::dict out;
+#define ZL_FIELD(T, f) fields.append(py::make_tuple(#f, offsetof(T, f)));
+#define ZL_STRUCT(T, ...)                                  \
+    {                                                      \
+        py::list fields;                                   \
+        __VA_ARGS__                                        \
+        out[#T] = py::make_tuple(sizeof(T), fields);       \
+    }
+#define F(f) ZL_FIELD(zl_sample_opts_t, f)
+    ZL_STRUCT(zl_sample_opts_t, F(rep_penalty) F(presence) F(seen) F(seen_ld) F(bias_ids) F(bias_vals) F(bias_cnt) F(bias_ld) F(bias_bits)
+              F(bias_bits_ld) F(top_n) F(top_ids) F(top_logprobs) F(fsm_mask) F(fsm_mask_ld) F(fsm_default) F(fsm_exc_off) F(fsm_exc_tok)
+              F(fsm_exc_next) F(fsm_states) F(fsm_exceptions) F(fsm_state) F(fsm_row_states))
+#undef F
+#define F(f) ZL_FIELD(zl_w4_opts_t, f)
+    ZL_STRUCT(zl_w4_opts_t, F(scratch) F(scratch_bytes) F(phase_rounds) F(phase_ksplit) F(phase_ksplit_min_m) F(phase_min_m) F(phase_max_m)
+              F(phase_small_off) F(tiled_min_m) F(tiled_bm) F(tiled_splitk) F(mfma_ks) F(mfma_rounds) F(small_algo) F(tiled_wide) F(slab)
+              F(slab_min_m) F(slab_nw) F(slab_gpw) F(slab_r) F(defer_norm) F(row_ss) F(row_ss_out))
+#undef F
+#undef ZL_STRUCT
+#undef ZL_FIELD
+    return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(zl_internals, m) {
     m.doc() = "C++ operator layer of zhilight_amd (bmengine-on-HIP shim + nn:: wrappers) exposed for tests";
     py::register_exception<BMEngineException>(m, "BMEngineException", PyExc_RuntimeError);
+    m.def("struct_layouts", &struct_layouts);
 
     py::class_<PyCtx>(m, "Context")
         .def(py::init<int>(), py::arg("device") = 0)

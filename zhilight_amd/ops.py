@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import W4Layout, W4Opts, ZLError, check, lib
+from ._lib import SampleOpts, W4Layout, W4Opts, ZLError, check, lib
 
 F16, BF16 = 0, 1
 EPI_BIAS, EPI_ADD_C, EPI_RESIDUAL, EPI_SILU_MUL, EPI_SILU_MUL_F32 = 1, 2, 4, 8, 16
@@ -1043,22 +1043,6 @@ def seen_mark(seen, tokens, n):
     return seen
 
 
-def _penalty_args(what, count, n, device, rep_penalty, presence, seen):
-    """The checks of (rep_penalty, presence, seen) of sample_advance / spec_sample_accept; count = the rows / tasks they are per."""
-    if seen is None:
-        if rep_penalty is not None or presence is not None:
-            raise ZLError(f"{what}: rep_penalty / presence act on the classes of seen: give the bitmap")
-        return
-    for t, name in ((rep_penalty, "rep_penalty"), (presence, "presence")):
-        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.numel() == count and t.is_contiguous()):
-            raise ZLError(f"{what}: {name}: contiguous float32 of length {count}, given with seen")
-    if not (torch.is_tensor(seen) and seen.dtype == torch.int32 and seen.dim() == 2 and seen.shape[0] == count and seen.is_contiguous()
-            and seen.shape[1] >= seen_words(n)):
-        raise ZLError(f"{what}: seen: contiguous int32 ({count}, >= ceil(n / 32))")
-    if any(t.device != device for t in (rep_penalty, presence, seen)):
-        raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
-
-
 LOGIT_BIAS_MAX = 1024      # bias entries per task
 TOP_LOGPROBS_MAX = 32      # top-N alternatives per row
 
@@ -1464,9 +1448,81 @@ def slots_admit(blob, tokens, positions, placement, valid_lens, sampler=None, st
     return dev_blob
 
 
-def _opts_args(what, count, top_shape, n, device, bias, top_n, top_ids, top_logprobs):
-    """The checks of (bias, top_n, top_ids, top_logprobs) of sample_advance / spec_sample_accept -> the nine C arguments; count = the
-    rows / tasks the bias is per, top_shape = the leading shape of the top-N outputs."""
+def grammar_tables(packed, device):
+    """grammar.TokenAutomaton.pack()'s five arrays as the `fsm` tuple of sample_advance / spec_sample_accept: int32 tensors on the device
+    (the bitmap's uint32 words viewed as int32, as seen)"""
+    mask, default, exc_off, exc_tok, exc_next = packed
+    return (torch.from_numpy(np.ascontiguousarray(mask).view(np.int32)).to(device), torch.from_numpy(np.ascontiguousarray(default)).to(device),
+            torch.from_numpy(np.ascontiguousarray(exc_off)).to(device), torch.from_numpy(np.ascontiguousarray(exc_tok)).to(device),
+            torch.from_numpy(np.ascontiguousarray(exc_next)).to(device))
+
+
+def _sample_logits(what, rows_text, logits, **first):
+    """The checks of the logits of sample_advance / spec_sample_accept; first = the required tensors the first message names with them."""
+    names = list(first)
+    if not all(torch.is_tensor(t) for t in (logits, *first.values())):
+        raise ZLError(f"{what}: logits, {', '.join(names[:-1])} and {names[-1]} are tensors")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise ZLError(f"{what}: {rows_text} logits with unit column stride")
+    if logits.dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError(f"{what}: fp16 or bf16 logits, not {logits.dtype} (the selection works on the 16-bit pattern)")
+    if logits.shape[1] >= 1 << 31:
+        raise ZLError(f"{what}: a row holds fewer than 2^31 classes")
+
+
+def _sample_tensors(what, logits, one_dim, required, generator, optional):
+    """The checks of the per-row / per-task tensors of sample_advance / spec_sample_accept, each entry (tensor, dtype, elements, name,
+    the message's shape text): the required ones, the generator triple (seeds, draws, u), the optional ones (None = not given), and
+    last that all of them are on the CUDA device of the logits.  one_dim: every tensor is 1-D."""
+    def sized(t, dtype, count, name, text):
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.numel() == count and t.is_contiguous() and (t.dim() == 1 or not one_dim)):
+            raise ZLError(f"{what}: {name}: contiguous {str(dtype).replace('torch.', '')} {text}")
+
+    for entry in required:
+        sized(*entry)
+    seeds, draws, u = generator
+    if u[0] is not None:
+        sized(*u)
+    elif seeds[0] is None or draws[0] is None:
+        raise ZLError(f"{what}: give seeds and draws, or u")
+    if u[0] is None or seeds[0] is not None:
+        sized(*seeds)
+    if u[0] is None or draws[0] is not None:
+        sized(*draws)
+    for entry in optional:
+        if entry[0] is not None:
+            sized(*entry)
+    if not logits.is_cuda or any(e[0] is not None and e[0].device != logits.device for e in (*required, *generator, *optional)):
+        raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
+
+
+def _sample_opts(what, count, top_shape, n, device, rep_penalty, presence, seen, bias, top_n, top_ids, top_logprobs, fsm, fsm_state,
+                 row_states=None):
+    """The checks of the options of sample_advance / spec_sample_accept -> their zl_sample_opts_t (by reference), None when nothing is
+    on.  count = the rows / tasks the options are per, top_shape = the leading shape of the top-N outputs (and of row_states, the
+    speculative call's).
+    The struct holds addresses only: the caller keeps the tensors referenced until the C call has returned (its arguments are)."""
+    o = SampleOpts()
+    if seen is None:
+        if rep_penalty is not None or presence is not None:
+            raise ZLError(f"{what}: rep_penalty / presence act on the classes of seen: give the bitmap")
+    else:
+        for t, name in ((rep_penalty, "rep_penalty"), (presence, "presence")):
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.numel() == count and t.is_contiguous()):
+                raise ZLError(f"{what}: {name}: contiguous float32 of length {count}, given with seen")
+        if not (torch.is_tensor(seen) and seen.dtype == torch.int32 and seen.dim() == 2 and seen.shape[0] == count and seen.is_contiguous()
+                and seen.shape[1] >= seen_words(n)):
+            raise ZLError(f"{what}: seen: contiguous int32 ({count}, >= ceil(n / 32))")
+        if any(t.device != device for t in (rep_penalty, presence, seen)):
+            raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
+        o.rep_penalty, o.presence, o.seen, o.seen_ld = rep_penalty.data_ptr(), presence.data_ptr(), seen.data_ptr(), seen.shape[1]
+    if row_states is not None:
+        if not (torch.is_tensor(row_states) and row_states.dtype == torch.int32 and row_states.numel() == math.prod(top_shape)
+                and row_states.is_contiguous()):
+            raise ZLError(f"{what}: row_states: contiguous int32 (B, K + 1)")
+        if row_states.device != device:
+            raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
+        o.fsm_row_states = row_states.data_ptr()
     if bias is not None:
         if not (isinstance(bias, (tuple, list)) and len(bias) == 4 and all(torch.is_tensor(t) for t in bias)):
             raise ZLError(f"{what}: bias is logit_bias_pack's (ids, vals, cnt, bits)")
@@ -1483,9 +1539,8 @@ def _opts_args(what, count, top_shape, n, device, bias, top_n, top_ids, top_logp
             raise ZLError(f"{what}: bias bits: contiguous int32 ({count}, >= ceil(n / 32))")
         if any(t.device != device for t in bias):
             raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
-        args = [_p(ids), _p(vals), _p(cnt), _i(ids.shape[1]), _p(bits), _i(bits.shape[1])]
-    else:
-        args = [_p(None), _p(None), _p(None), _i(0), _p(None), _i(0)]
+        o.bias_ids, o.bias_vals, o.bias_cnt, o.bias_ld = ids.data_ptr(), vals.data_ptr(), cnt.data_ptr(), ids.shape[1]
+        o.bias_bits, o.bias_bits_ld = bits.data_ptr(), bits.shape[1]
     top_n = int(top_n)
     if not 0 <= top_n <= TOP_LOGPROBS_MAX:
         raise ZLError(f"{what}: top_n in 0 .. {TOP_LOGPROBS_MAX}")
@@ -1494,37 +1549,27 @@ def _opts_args(what, count, top_shape, n, device, bias, top_n, top_ids, top_logp
         for t, dtype, name in ((top_ids, torch.int32, "top_ids"), (top_logprobs, torch.float32, "top_logprobs")):
             if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == device):
                 raise ZLError(f"{what}: {name}: contiguous {str(dtype).replace('torch.', '')} {shape} on the logits' device, given with top_n")
-        return args + [C.c_int(top_n), _p(top_ids), _p(top_logprobs)]
-    return args + [C.c_int(0), _p(None), _p(None)]
-
-
-def grammar_tables(packed, device):
-    """grammar.TokenAutomaton.pack()'s five arrays as the `fsm` tuple of sample_advance / spec_sample_accept: int32 tensors on the device
-    (the bitmap's uint32 words viewed as int32, as seen)"""
-    mask, default, exc_off, exc_tok, exc_next = packed
-    return (torch.from_numpy(np.ascontiguousarray(mask).view(np.int32)).to(device), torch.from_numpy(np.ascontiguousarray(default)).to(device),
-            torch.from_numpy(np.ascontiguousarray(exc_off)).to(device), torch.from_numpy(np.ascontiguousarray(exc_tok)).to(device),
-            torch.from_numpy(np.ascontiguousarray(exc_next)).to(device))
-
-
-def _fsm_args(what, count, n, device, fsm, fsm_state):
-    """The checks of (fsm, fsm_state) of sample_advance / spec_sample_accept -> zl_*_fsm's nine C arguments behind the _opts ones."""
-    if not (isinstance(fsm, (tuple, list)) and len(fsm) == 5 and all(torch.is_tensor(t) and t.dtype == torch.int32 and t.is_contiguous()
-                                                                     for t in fsm)):
-        raise ZLError(f"{what}: fsm is (mask, default, exc_off, exc_tok, exc_next), contiguous int32 tensors (grammar_tables)")
-    mask, default, exc_off, exc_tok, exc_next = fsm
-    if not (mask.dim() == 2 and default.dim() == 1 and exc_off.dim() == 1 and exc_tok.dim() == 1 and exc_next.dim() == 1
-            and mask.shape[0] >= 1 and default.numel() == mask.shape[0] and exc_off.numel() == mask.shape[0] + 1
-            and exc_next.numel() == exc_tok.numel() and mask.shape[1] >= seen_words(n)):
-        raise ZLError(f"{what}: fsm: mask (S, >= ceil(n / 32)), default (S), exc_off (S + 1), exc_tok / exc_next (E)")
-    if not (torch.is_tensor(fsm_state) and fsm_state.dtype == torch.int32 and fsm_state.dim() == 1 and fsm_state.numel() == count
-            and fsm_state.is_contiguous()):
-        raise ZLError(f"{what}: fsm_state: contiguous int32 of length {count}, given with fsm")
-    if any(t.device != device for t in tuple(fsm) + (fsm_state,)):
-        raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
-    empty = exc_tok.numel() == 0                                            # no exception anywhere: the lists are never read
-    return [_p(mask), _i(mask.shape[1]), _p(default), _p(exc_off), _p(exc_off if empty else exc_tok), _p(exc_off if empty else exc_next),
-            _i(mask.shape[0]), _i(exc_tok.numel()), _p(fsm_state)]
+        o.top_n, o.top_ids, o.top_logprobs = top_n, top_ids.data_ptr(), top_logprobs.data_ptr()
+    if fsm is not None:
+        if not (isinstance(fsm, (tuple, list)) and len(fsm) == 5 and all(torch.is_tensor(t) and t.dtype == torch.int32 and t.is_contiguous()
+                                                                         for t in fsm)):
+            raise ZLError(f"{what}: fsm is (mask, default, exc_off, exc_tok, exc_next), contiguous int32 tensors (grammar_tables)")
+        mask, default, exc_off, exc_tok, exc_next = fsm
+        if not (mask.dim() == 2 and default.dim() == 1 and exc_off.dim() == 1 and exc_tok.dim() == 1 and exc_next.dim() == 1
+                and mask.shape[0] >= 1 and default.numel() == mask.shape[0] and exc_off.numel() == mask.shape[0] + 1
+                and exc_next.numel() == exc_tok.numel() and mask.shape[1] >= seen_words(n)):
+            raise ZLError(f"{what}: fsm: mask (S, >= ceil(n / 32)), default (S), exc_off (S + 1), exc_tok / exc_next (E)")
+        if not (torch.is_tensor(fsm_state) and fsm_state.dtype == torch.int32 and fsm_state.dim() == 1 and fsm_state.numel() == count
+                and fsm_state.is_contiguous()):
+            raise ZLError(f"{what}: fsm_state: contiguous int32 of length {count}, given with fsm")
+        if any(t.device != device for t in tuple(fsm) + (fsm_state,)):
+            raise ZLError(f"{what}: CUDA logits, every other tensor on the logits' device")
+        if exc_tok.numel() == 0:                                            # no exception anywhere: the lists are never read
+            exc_tok = exc_next = exc_off
+        o.fsm_mask, o.fsm_mask_ld, o.fsm_default, o.fsm_exc_off = mask.data_ptr(), mask.shape[1], default.data_ptr(), exc_off.data_ptr()
+        o.fsm_exc_tok, o.fsm_exc_next, o.fsm_states, o.fsm_exceptions = exc_tok.data_ptr(), exc_next.data_ptr(), mask.shape[0], fsm[3].numel()
+        o.fsm_state = fsm_state.data_ptr()
+    return C.byref(o) if seen is not None or bias is not None or top_n or fsm is not None else None
 
 
 def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=None, tokens=None, positions=None, placement=None,
@@ -1538,90 +1583,41 @@ def sample_advance(logits, temperature, top_k, top_p, seeds=None, draws=None, u=
     Philox4x32-10 words keyed by seeds[r] (int64) and counted by draws[r] (int64), and draws += 1.  tokens <- pick (int32),
     next_tokens <- pick (int64), positions / placement / valid_lens += 1 (each optional, tokens or next_tokens required); logprobs
     (rows) fp32 <- the pick's tempered log-probability (T <= 0: at T = 1); u_out (rows) fp32 <- the uniforms used.  Returns
-    next_tokens if given, else tokens.
+    next_tokens if given, else tokens.  The options below travel as one zl_sample_opts_t to zl_sample_advance_ex.
     seen (rows, >= ceil(n / 32)) int32, a bitmap of token ids per row (seen_words, seen_mark), with rep_penalty / presence (rows) fp32:
-    zl_sample_advance_ex -- a class whose bit is set is read as repetition_penalty's value of it (presence != 0 ? x - T(presence) :
+    the penalty group -- a class whose bit is set is read as repetition_penalty's value of it (presence != 0 ? x - T(presence) :
     x < 0 ? x * T(factor) : x / T(factor)), the rule above runs on that row, logprobs is the penalised distribution's, the logits in
     memory stay as they are, and the pick's bit is set in seen: the same results as repetition_penalty over the set + this call
     without seen, in the one launch.
-    bias = logit_bias_pack's tuple, per row: zl_sample_advance_opts -- a class of the row's bias set is read as T(f32(y) + f32(T(bias))),
+    bias = logit_bias_pack's tuple, per row: the bias group -- a class of the row's bias set is read as T(f32(y) + f32(T(bias))),
     y = the class after the penalty (scatter_logits(add=True)'s expression; -inf bans the class); the bias enters neither seen nor the
     logits in memory, and needs no seen.  top_n = N in 1 .. 32 with top_ids (rows, N) int32 / top_logprobs (rows, N) fp32: the first
     min(N, n) classes of the row AS THE PICK SAW IT, larger value first, then lower index, with their tempered log-probabilities
     (the pick's entry is bit-equal to logprobs); -1 / NaN behind n and on a row whose largest value is NaN or +-inf.  The same
     results as repetition_penalty + scatter_logits(add=True) + this call without them, in the one launch.
-    fsm = grammar_tables' five tensors with fsm_state (rows) int32: zl_sample_advance_fsm -- a row whose state s lies in [0, S) reads
+    fsm = grammar_tables' five tensors with fsm_state (rows) int32: the automaton group -- a row whose state s lies in [0, S) reads
     every class whose bit is clear in mask[s] as -inf (in front of the penalty and the bias; the logits in memory stay), everything
     above runs on that row, and fsm_state <- delta(s, pick): the exception's target where exc_tok[exc_off[s] : exc_off[s + 1]] holds the
     pick, else default[s].  A state outside [0, S) leaves the row unconstrained and is not changed.  The same results as
     masked_fill(-inf) on a copy + this call without fsm."""
+    what = "sample_advance"
     if (fsm is None) != (fsm_state is None):
-        raise ZLError("sample_advance: fsm and fsm_state are given together")
-    if not all(torch.is_tensor(t) for t in (logits, temperature, top_k, top_p)):
-        raise ZLError("sample_advance: logits, temperature, top_k and top_p are tensors")
-    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
-        raise ZLError("sample_advance: (rows, n) logits with unit column stride")
-    if logits.dtype not in (torch.float16, torch.bfloat16):
-        raise ZLError(f"sample_advance: fp16 or bf16 logits, not {logits.dtype} (the selection works on the 16-bit pattern)")
+        raise ZLError(f"{what}: fsm and fsm_state are given together")
+    _sample_logits(what, "(rows, n)", logits, temperature=temperature, top_k=top_k, top_p=top_p)
     rows, n = logits.shape
-    if n >= 1 << 31:
-        raise ZLError("sample_advance: a row holds fewer than 2^31 classes")
-
-    def per_row(t, dtype, what):
-        if not (torch.is_tensor(t) and t.dtype == dtype and t.dim() == 1 and t.numel() == rows and t.is_contiguous()):
-            raise ZLError(f"sample_advance: {what}: contiguous {str(dtype).replace('torch.', '')} of length rows")
-
-    per_row(temperature, torch.float32, "temperature")
-    per_row(top_k, torch.int32, "top_k")
-    per_row(top_p, torch.float32, "top_p")
-    if u is not None:
-        per_row(u, torch.float32, "u")
-    elif seeds is None or draws is None:
-        raise ZLError("sample_advance: give seeds and draws, or u")
-    if u is None or seeds is not None:
-        per_row(seeds, torch.int64, "seeds")
-    if u is None or draws is not None:
-        per_row(draws, torch.int64, "draws")
     if tokens is None and next_tokens is None:
-        raise ZLError("sample_advance: give tokens or next_tokens")
-    for t, what in ((tokens, "tokens"), (positions, "positions"), (placement, "placement"), (valid_lens, "valid_lens")):
-        if t is not None:
-            per_row(t, torch.int32, what)
-    if next_tokens is not None:
-        per_row(next_tokens, torch.int64, "next_tokens")
-    if logprobs is not None:
-        per_row(logprobs, torch.float32, "logprobs")
-    if u_out is not None:
-        per_row(u_out, torch.float32, "u_out")
-    others = (temperature, top_k, top_p, seeds, draws, u, tokens, positions, placement, valid_lens, next_tokens, logprobs, u_out)
-    if not logits.is_cuda or any(t is not None and t.device != logits.device for t in others):
-        raise ZLError("sample_advance: CUDA logits, every other tensor on the logits' device")
-    _penalty_args("sample_advance", rows, n, logits.device, rep_penalty, presence, seen)
-    code = 2 if logits.dtype == torch.float16 else 6
-    if fsm is not None:
-        opts = _opts_args("sample_advance", rows, (rows,), n, logits.device, bias, top_n, top_ids, top_logprobs)
-        fargs = _fsm_args("sample_advance", rows, n, logits.device, fsm, fsm_state)
-        check(lib().zl_sample_advance_fsm(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k),
-                                          _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement), _p(valid_lens),
-                                          _p(next_tokens), _p(logprobs), _p(u_out), _p(rep_penalty), _p(presence), _p(seen),
-                                          _i(seen.shape[1] if seen is not None else 0), *opts, *fargs, _stream()), "sample_advance")
-        return next_tokens if next_tokens is not None else tokens
-    if bias is not None or top_n != 0:
-        opts = _opts_args("sample_advance", rows, (rows,), n, logits.device, bias, top_n, top_ids, top_logprobs)
-        check(lib().zl_sample_advance_opts(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k),
-                                           _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement), _p(valid_lens),
-                                           _p(next_tokens), _p(logprobs), _p(u_out), _p(rep_penalty), _p(presence), _p(seen),
-                                           _i(seen.shape[1] if seen is not None else 0), *opts, _stream()), "sample_advance")
-        return next_tokens if next_tokens is not None else tokens
-    if seen is not None:
-        check(lib().zl_sample_advance_ex(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k),
-                                         _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement), _p(valid_lens),
-                                         _p(next_tokens), _p(logprobs), _p(u_out), _p(rep_penalty), _p(presence), _p(seen),
-                                         _i(seen.shape[1]), _stream()), "sample_advance")
-        return next_tokens if next_tokens is not None else tokens
-    check(lib().zl_sample_advance(_p(logits), C.c_int(code), _i(rows), _i(n), _i(logits.stride(0)), _p(temperature), _p(top_k), _p(top_p),
-                                  _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement), _p(valid_lens), _p(next_tokens),
-                                  _p(logprobs), _p(u_out), _stream()), "sample_advance")
+        raise ZLError(f"{what}: give tokens or next_tokens")
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    per_row = lambda t, dtype, name: (t, dtype, rows, name, "of length rows")                      # noqa: E731
+    _sample_tensors(what, logits, True, [per_row(temperature, f32, "temperature"), per_row(top_k, i32, "top_k"), per_row(top_p, f32, "top_p")],
+                    [per_row(seeds, i64, "seeds"), per_row(draws, i64, "draws"), per_row(u, f32, "u")],
+                    [per_row(tokens, i32, "tokens"), per_row(positions, i32, "positions"), per_row(placement, i32, "placement"),
+                     per_row(valid_lens, i32, "valid_lens"), per_row(next_tokens, i64, "next_tokens"), per_row(logprobs, f32, "logprobs"),
+                     per_row(u_out, f32, "u_out")])
+    opts = _sample_opts(what, rows, (rows,), n, logits.device, rep_penalty, presence, seen, bias, top_n, top_ids, top_logprobs, fsm, fsm_state)
+    check(lib().zl_sample_advance_ex(_p(logits), C.c_int(2 if logits.dtype == torch.float16 else 6), _i(rows), _i(n), _i(logits.stride(0)),
+                                     _p(temperature), _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions),
+                                     _p(placement), _p(valid_lens), _p(next_tokens), _p(logprobs), _p(u_out), opts, _stream()), what)
     return next_tokens if next_tokens is not None else tokens
 
 
@@ -1640,105 +1636,48 @@ def spec_sample_accept(logits, drafts, temperature, top_k, top_p, seeds=None, dr
     sequence is what sample_advance emits step by step.  out_logprobs <- the picks' tempered log-probabilities, NaN behind the
     bonus token; logprobs (B) <- that of picks[b, accepted] (needs out_logprobs); u_out <- the uniform of every row.  Returns
     (accepted (B) int32, out_tokens (B, len_q) int32); accepted / out_tokens: buffers to write into (a captured call).
-    seen (B, >= ceil(n / 32)) int32 with rep_penalty / presence (B) fp32, per task: zl_spec_sample_accept_ex -- row (b, i) is
+    The options below travel as one zl_sample_opts_t to zl_spec_sample_accept_ex.
+    seen (B, >= ceil(n / 32)) int32 with rep_penalty / presence (B) fp32, per task: the penalty group -- row (b, i) is
     sample_advance(seen=)'s pick under the set seen[b] + the in-range drafts[b, :i] (the row counts only if they were emitted), and
     the bits of the emitted tokens out_tokens[b, :accepted + 1] are set in seen[b]; the rejected drafts' are not.
     bias (logit_bias_pack's tuple, per task) / top_n with top_ids (B, K + 1, N) int32 and top_logprobs (B, K + 1, N) fp32:
-    zl_spec_sample_accept_opts -- every row (b, i) is sample_advance(bias=, top_n=)'s under task b's bias (the drafts in front of a row
+    the bias and top-N groups -- every row (b, i) is sample_advance(bias=, top_n=)'s under task b's bias (the drafts in front of a row
     change its penalty set only), the rows behind the bonus token hold -1 / NaN.
-    fsm (grammar_tables' tensors) with fsm_state (B) int32 and row_states (B, K + 1) int32: zl_spec_sample_accept_fsm -- row (b, i) is
+    fsm (grammar_tables' tensors) with fsm_state (B) int32 and row_states (B, K + 1) int32: the automaton group -- row (b, i) is
     sample_advance(fsm=)'s under the state s_i, s_0 = fsm_state[b], s_{j+1} = delta(s_j, drafts[b, j]); row_states[b, i] <- delta(s_i,
     picks[b, i]) and fsm_state[b] <- row_states[b, accepted[b]]: the state has moved over exactly the emitted tokens."""
+    what = "spec_sample_accept"
     if (fsm is None) != (fsm_state is None) or (fsm is None) != (row_states is None):
-        raise ZLError("spec_sample_accept: fsm, fsm_state and row_states are given together")
-    if not all(torch.is_tensor(t) for t in (logits, drafts, temperature, top_k, top_p)):
-        raise ZLError("spec_sample_accept: logits, drafts, temperature, top_k and top_p are tensors")
-    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
-        raise ZLError("spec_sample_accept: (B * len_q, n) logits with unit column stride")
-    if logits.dtype not in (torch.float16, torch.bfloat16):
-        raise ZLError(f"spec_sample_accept: fp16 or bf16 logits, not {logits.dtype} (the selection works on the 16-bit pattern)")
+        raise ZLError(f"{what}: fsm, fsm_state and row_states are given together")
+    _sample_logits(what, "(B * len_q, n)", logits, drafts=drafts, temperature=temperature, top_k=top_k, top_p=top_p)
     if drafts.dim() != 2 or drafts.shape[1] < 1 or drafts.dtype != torch.int32 or not drafts.is_contiguous():
-        raise ZLError("spec_sample_accept: drafts are (B, K) contiguous int32, K >= 1")
+        raise ZLError(f"{what}: drafts are (B, K) contiguous int32, K >= 1")
     b, len_q, n = drafts.shape[0], drafts.shape[1] + 1, logits.shape[1]
     if len_q > 32:
-        raise ZLError("spec_sample_accept: at most 32 rows per task (K <= 31)")
+        raise ZLError(f"{what}: at most 32 rows per task (K <= 31)")
     if b < 1 or logits.shape[0] != b * len_q:
-        raise ZLError("spec_sample_accept: one logit row per task and draft position: B * (K + 1) rows")
-    if n >= 1 << 31:
-        raise ZLError("spec_sample_accept: a row holds fewer than 2^31 classes")
-
-    def sized(t, dtype, count, what, shape):
-        if not (torch.is_tensor(t) and t.dtype == dtype and t.numel() == count and t.is_contiguous()):
-            raise ZLError(f"spec_sample_accept: {what}: contiguous {str(dtype).replace('torch.', '')} {shape}")
-
-    per_task = lambda t, dtype, what: sized(t, dtype, b, what, "of length B")                       # noqa: E731
-    per_row = lambda t, dtype, what: sized(t, dtype, b * len_q, what, "(B, K + 1)")                  # noqa: E731
-    per_task(temperature, torch.float32, "temperature")
-    per_task(top_k, torch.int32, "top_k")
-    per_task(top_p, torch.float32, "top_p")
-    if u is not None:
-        per_row(u, torch.float32, "u")
-    elif seeds is None or draws is None:
-        raise ZLError("spec_sample_accept: give seeds and draws, or u")
-    if u is None or seeds is not None:
-        per_task(seeds, torch.int64, "seeds")
-    if u is None or draws is not None:
-        per_task(draws, torch.int64, "draws")
-    for t, what in ((tokens, "tokens"), (positions, "positions"), (placement, "placement"), (valid_lens, "valid_lens"), (accepted, "accepted")):
-        if t is not None:
-            per_task(t, torch.int32, what)
-    if logprobs is not None:
-        per_task(logprobs, torch.float32, "logprobs")
-        if out_logprobs is None:
-            raise ZLError("spec_sample_accept: logprobs is read from out_logprobs: give both")
-    if out_tokens is not None:
-        per_row(out_tokens, torch.int32, "out_tokens")
-    if out_logprobs is not None:
-        per_row(out_logprobs, torch.float32, "out_logprobs")
-    if u_out is not None:
-        per_row(u_out, torch.float32, "u_out")
-    others = (drafts, temperature, top_k, top_p, seeds, draws, u, tokens, positions, placement, valid_lens, accepted, out_tokens, out_logprobs,
-              logprobs, u_out)
-    if not logits.is_cuda or any(t is not None and t.device != logits.device for t in others):
-        raise ZLError("spec_sample_accept: CUDA logits, every other tensor on the logits' device")
-    _penalty_args("spec_sample_accept", b, n, logits.device, rep_penalty, presence, seen)
+        raise ZLError(f"{what}: one logit row per task and draft position: B * (K + 1) rows")
+    if logprobs is not None and out_logprobs is None:
+        raise ZLError(f"{what}: logprobs is read from out_logprobs: give both")
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    per_task = lambda t, dtype, name: (t, dtype, b, name, "of length B")                           # noqa: E731
+    per_row = lambda t, dtype, name: (t, dtype, b * len_q, name, "(B, K + 1)")                     # noqa: E731
+    _sample_tensors(what, logits, False, [(drafts, i32, b * (len_q - 1), "drafts", "(B, K)"), per_task(temperature, f32, "temperature"),
+                                          per_task(top_k, i32, "top_k"), per_task(top_p, f32, "top_p")],
+                    [per_task(seeds, i64, "seeds"), per_task(draws, i64, "draws"), per_row(u, f32, "u")],
+                    [per_task(tokens, i32, "tokens"), per_task(positions, i32, "positions"), per_task(placement, i32, "placement"),
+                     per_task(valid_lens, i32, "valid_lens"), per_task(accepted, i32, "accepted"), per_task(logprobs, f32, "logprobs"),
+                     per_row(out_tokens, i32, "out_tokens"), per_row(out_logprobs, f32, "out_logprobs"), per_row(u_out, f32, "u_out")])
+    opts = _sample_opts(what, b, (b, len_q), n, logits.device, rep_penalty, presence, seen, bias, top_n, top_ids, top_logprobs, fsm, fsm_state,
+                        row_states)
     if accepted is None:
         accepted = torch.empty(b, dtype=torch.int32, device=logits.device)
     if out_tokens is None:
         out_tokens = torch.empty((b, len_q), dtype=torch.int32, device=logits.device)
-    code = 2 if logits.dtype == torch.float16 else 6
-    if fsm is not None:
-        per_row(row_states, torch.int32, "row_states")
-        if row_states.device != logits.device:
-            raise ZLError("spec_sample_accept: CUDA logits, every other tensor on the logits' device")
-        opts = _opts_args("spec_sample_accept", b, (b, len_q), n, logits.device, bias, top_n, top_ids, top_logprobs)
-        fargs = _fsm_args("spec_sample_accept", b, n, logits.device, fsm, fsm_state)
-        check(lib().zl_spec_sample_accept_fsm(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts),
-                                              _p(temperature), _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions),
-                                              _p(placement), _p(valid_lens), _p(accepted), _p(out_tokens), _p(out_logprobs), _p(logprobs),
-                                              _p(u_out), _p(rep_penalty), _p(presence), _p(seen),
-                                              _i(seen.shape[1] if seen is not None else 0), *opts, *fargs, _p(row_states), _stream()),
-              "spec_sample_accept")
-        return accepted, out_tokens.view(b, len_q)
-    if bias is not None or top_n != 0:
-        opts = _opts_args("spec_sample_accept", b, (b, len_q), n, logits.device, bias, top_n, top_ids, top_logprobs)
-        check(lib().zl_spec_sample_accept_opts(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts),
-                                               _p(temperature), _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions),
-                                               _p(placement), _p(valid_lens), _p(accepted), _p(out_tokens), _p(out_logprobs), _p(logprobs),
-                                               _p(u_out), _p(rep_penalty), _p(presence), _p(seen),
-                                               _i(seen.shape[1] if seen is not None else 0), *opts, _stream()), "spec_sample_accept")
-        return accepted, out_tokens.view(b, len_q)
-    if seen is not None:
-        check(lib().zl_spec_sample_accept_ex(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts),
-                                             _p(temperature), _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions),
-                                             _p(placement), _p(valid_lens), _p(accepted), _p(out_tokens), _p(out_logprobs), _p(logprobs),
-                                             _p(u_out), _p(rep_penalty), _p(presence), _p(seen), _i(seen.shape[1]), _stream()),
-              "spec_sample_accept")
-        return accepted, out_tokens.view(b, len_q)
-    check(lib().zl_spec_sample_accept(_p(logits), C.c_int(code), _i(b), _i(len_q), _i(n), _i(logits.stride(0)), _p(drafts), _p(temperature),
-                                      _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u), _p(tokens), _p(positions), _p(placement),
-                                      _p(valid_lens), _p(accepted), _p(out_tokens), _p(out_logprobs), _p(logprobs), _p(u_out), _stream()),
-          "spec_sample_accept")
+    check(lib().zl_spec_sample_accept_ex(_p(logits), C.c_int(2 if logits.dtype == torch.float16 else 6), _i(b), _i(len_q), _i(n),
+                                         _i(logits.stride(0)), _p(drafts), _p(temperature), _p(top_k), _p(top_p), _p(seeds), _p(draws), _p(u),
+                                         _p(tokens), _p(positions), _p(placement), _p(valid_lens), _p(accepted), _p(out_tokens),
+                                         _p(out_logprobs), _p(logprobs), _p(u_out), opts, _stream()), what)
     return accepted, out_tokens.view(b, len_q)
 
 
