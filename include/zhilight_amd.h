@@ -558,6 +558,39 @@ int zl_decode_attn_causal(const uint16_t* q, const int32_t* buf_lens, const uint
                           int64_t b, int64_t len_q, int64_t h, int64_t hkv, int64_t d, float scale, int64_t max_len_buf,
                           int bshd, int dtype, zl_stream_t s);
 
+/* Two-segment decode attention: tasks that share a prompt read its K / V rows from ONE buffer instead of a copy each.
+ * The call carries G prefix buffers: prefix_k / prefix_v are device arrays of G pointers, buffer g has prefix_caps[g] rows in the
+ * call's layout (BSHD (cap, Hkv, D), or BHSD (Hkv, cap, D) with its own cap as the head stride), prefix_lens[g] of them valid.
+ * Task b names g = prefix_of[b]; a value outside [0, G) means "none".  With
+ *     P = min(prefix_lens[g], prefix_caps[g], valid_lens[b], buf_lens[b])   (P = 0 for "none", and never below 0)
+ * task b's key j is row j of prefix buffer g for j < P and row j of its OWN buffer for P <= j < min(valid_lens[b], buf_lens[b]):
+ * indices stay absolute, own rows below P and prefix rows from P on are never read.  The output is zl_decode_attn(mask = NULL,
+ * valid_lens)'s formula over those keys (max init -1e20, Z init 1e-20, fp32 softmax and accumulation); a task without a visible
+ * key gets a zero row.  No table value makes a launch read or write outside its operands: bad values are resolved by the clamps
+ * above.  The caller's to keep: prefix_caps[g] <= max_prefix_len, buf_lens[b] <= max_len_buf (keys beyond are not attended to).
+ * q / out (B, 1, H, D) T, fp16 or bf16; D == 128 and H / Hkv <= 16 (ZL_ESHAPE otherwise).
+ * Two launches: partials + merge.  The partial launch holds, in one grid that depends on the scalar arguments only, the own items
+ * (task, kv head, split of [P, valid)) and the shared items (prefix, kv head, split of the prefix, 16-row tile): a shared item's
+ * query rows are the H / Hkv rows of each member of the prefix, the members found on the device from prefix_of, so membership,
+ * prefix_lens and valid_lens may change between replays of one captured graph.  A prefix's rows are streamed once per 16 query rows
+ * instead of once per task.  A task's output bits depend on its own table entries only, not on the other members or its index.
+ * workspace: zl_decode_attn_shared_workspace_bytes(...) bytes.  No allocation, no sync.
+ * _ex: keys per split on either side, multiples of 32 and at least 128 (the workspace is sized for 128), 0 = the launcher's. */
+int64_t zl_decode_attn_shared_workspace_bytes(int64_t b, int64_t g, int64_t h, int64_t hkv, int64_t d, int64_t max_prefix_len,
+                                              int64_t max_len_buf);
+int zl_decode_attn_shared(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs,
+                          const uint16_t* const* v_bufs, const int32_t* valid_lens, const int32_t* prefix_of /* (B) */,
+                          const int32_t* prefix_lens /* (G) */, const int32_t* prefix_caps /* (G) */,
+                          const uint16_t* const* prefix_k /* G pointers */, const uint16_t* const* prefix_v, uint16_t* out,
+                          void* workspace, int64_t b, int64_t g, int64_t h, int64_t hkv, int64_t d, float scale,
+                          int64_t max_prefix_len, int64_t max_len_buf, int bshd, int dtype, zl_stream_t s);
+int zl_decode_attn_shared_ex(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs,
+                             const uint16_t* const* v_bufs, const int32_t* valid_lens, const int32_t* prefix_of,
+                             const int32_t* prefix_lens, const int32_t* prefix_caps, const uint16_t* const* prefix_k,
+                             const uint16_t* const* prefix_v, uint16_t* out, void* workspace, int64_t b, int64_t g, int64_t h,
+                             int64_t hkv, int64_t d, float scale, int64_t max_prefix_len, int64_t max_len_buf, int bshd, int dtype,
+                             int64_t shared_split_len, int64_t own_split_len, zl_stream_t s);
+
 /* Fused decode attention front end (len_q == 1 per task, prefix visibility): rope_qk_cache +
  * copy_to_rag_buffer2 + multi_query_attention_rag_buffer in one pass over the fused qkv rows
  * (B, (H + 2 Hkv) D).  q and the new k are rotated with the cached cos/sin (one rounding to T, as the
@@ -808,6 +841,19 @@ int zl_prefill_attn_varlen_q8(const uint16_t* q, const int32_t* cu_seqlens_q, co
                               const uint16_t* k_new, const uint16_t* v_new, uint16_t* out,
                               const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
                               int64_t d, float scale, int dtype, int groups, zl_stream_t s);
+/* zl_prefill_attn_varlen_q8's two sources with an UNQUANTISED history: a chunk that continues rows held in ANOTHER buffer (a prompt
+ * encoded on top of a shared prefix, zl_decode_attn_shared).  Key / value row j of task i is
+ *   j <  pos0[i]   row j of hist_k[i] / hist_v[i], (hist_lens[i], Hkv, D) T, BSHD
+ *   j >= pos0[i]   row j - pos0[i] of the task's slice of k_new / v_new (total_q, Hkv, D), rows laid out as q's
+ * and everything after that is zl_prefill_attn_varlen, so the output equals that launch on buffers holding both bit for bit.
+ * BSHD only; D = 128; fp16 / bf16.  A task with pos0[i] = 0 may leave its history pointers null; a task whose hist_lens[i] is below
+ * its pos0[i] is dropped (its rows of `out` are not written).  No table value makes the kernel read or write outside the operands.
+ * No allocation, no sync.  Statuses as zl_prefill_attn_varlen_q8. */
+int zl_prefill_attn_varlen_hist(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                                const uint16_t* const* hist_k, const uint16_t* const* hist_v, const int32_t* hist_lens,
+                                const uint16_t* k_new, const uint16_t* v_new, uint16_t* out,
+                                const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
+                                int64_t d, float scale, int dtype, int groups, zl_stream_t s);
 
 
 /* ------------------------------------------------------------------------------------------------

@@ -38,10 +38,11 @@ SYMBOLS = [
     "zl_quant_group_32", "zl_dequant_sum_quant_g32", "zl_dequant_group_32",
     "zl_fp8_calc_scale", "zl_fp8_cvt_half", "zl_fp8_gemm_nt",
     "zl_decode_attn_workspace_bytes", "zl_decode_attn", "zl_decode_attn_ex", "zl_decode_attn_causal", "zl_decode_attn_fused",
+    "zl_decode_attn_shared_workspace_bytes", "zl_decode_attn_shared", "zl_decode_attn_shared_ex",
     "zl_decode_attn_split_len", "zl_decode_attn_splits", "zl_w4a16_gemm_attn_merge",
     "zl_decode_attn_la_split_len", "zl_decode_attn_la_workspace_bytes", "zl_decode_attn_la",
     "zl_quant_calc_scale_zp", "zl_dequant_group", "zl_quant_copy_to_rag_buffer", "zl_rope_quant_scatter_decode", "zl_decode_attn_quant", "zl_decode_attn_quant_ex",
-    "zl_prefill_attn", "zl_prefill_attn_ex", "zl_prefill_attn_varlen", "zl_prefill_attn_varlen_q8",
+    "zl_prefill_attn", "zl_prefill_attn_ex", "zl_prefill_attn_varlen", "zl_prefill_attn_varlen_q8", "zl_prefill_attn_varlen_hist",
     "zl_element_add_scale", "zl_gate_mul", "zl_gate_fuse", "zl_dense_m_bytes", "zl_dense_pack_m", "zl_gemm_nt_packed", "zl_row_ss", "zl_w4a16_emits_row_ss", "zl_w4a16_takes_row_ss", "zl_permute_input", "zl_embedding",
     "zl_w8m_bytes", "zl_w8m_pack", "zl_w8a8_gemm_phase", "zl_w8a8_gemm_phase_ex", "zl_w8a8_qkv_rope_scatter",
     "zl_quant_calc_scale", "zl_rmsnorm_quant", "zl_int8_gemm_nt", "zl_quant_scale_back",
@@ -97,6 +98,7 @@ def lib():
             getattr(l, name)  # AttributeError if the library does not export it
         l.zl_status_string.restype = C.c_char_p
         l.zl_decode_attn_workspace_bytes.restype = C.c_int64
+        l.zl_decode_attn_shared_workspace_bytes.restype = C.c_int64
         l.zl_decode_attn_split_len.restype = C.c_int64
         l.zl_decode_attn_la_split_len.restype = C.c_int64
         l.zl_decode_attn_la_workspace_bytes.restype = C.c_int64

@@ -63,7 +63,26 @@ struct AttnParams {
     // causal ("staircase") form of k_decode_attn_mfma (zl_decode_attn_causal): query row qi of a task sees valid_lens[b] + qi keys;
     // the 16-row tiles of its len_q * n_rep rows are folded into grid.y (blockIdx.y = tile * hkv + kv head)
     int causal = 0;
+    // two-segment form of k_decode_attn_mfma (zl_decode_attn_shared): task b's keys [0, P_b) are rows of prefix buffer prefix_of[b],
+    // its keys [P_b, valid) rows of its own buffer (shared_prefix_rows).  One 1-D grid holds both kinds of workgroups: sh_grid shared
+    // items (prefix, kv head, split of sh_split_len keys, 16-row tile of the members' rows), then b * hkv * own_splits own items
+    // (task, kv head, split of split_len keys counted from P_b).  A (task, head) has max_splits = sh_splits + own_splits record
+    // slots, the shared ones first.
+    const int32_t* prefix_of = nullptr;       // (b)
+    const int32_t* prefix_lens = nullptr;     // (g)
+    const int32_t* prefix_caps = nullptr;     // (g)
+    const uint16_t* const* prefix_k = nullptr;
+    const uint16_t* const* prefix_v = nullptr;
+    int g = 0, sh_split_len = 0, sh_splits = 0, own_splits = 0, sh_tiles = 0, sh_grid = 0;
 };
+
+// P_b of the two-segment form: min(prefix_lens[g], prefix_caps[g], valid_lens[b], buf_lens[b]) for g = prefix_of[b] in [0, G), else 0;
+// never negative, so no table value takes a reader outside a buffer
+__device__ __forceinline__ int shared_prefix_rows(const AttnParams& p, int b) {
+    const int g = p.prefix_of[b];
+    if ((unsigned)g >= (unsigned)p.g) return 0;
+    return max(0, min(min(p.prefix_lens[g], p.prefix_caps[g]), min(p.valid_lens[b], p.buf_lens[b])));
+}
 
 typedef _Float16 hv2 __attribute__((ext_vector_type(2)));
 
@@ -832,6 +851,17 @@ __device__ __forceinline__ void attn_tail_la(const AttnParams& p, float* xw, int
     ZL_APROBE(7);
 }
 
+// 16 words of LDS in the two-segment instantiation of k_decode_attn_mfma only: the other instantiations declare nothing
+template <bool SHARED>
+__device__ __forceinline__ int* shared_row_tasks() {
+    if constexpr (SHARED) {
+        __shared__ int tasks[16];
+        return tasks;
+    } else {
+        return nullptr;
+    }
+}
+
 #ifndef ZL_ATTN8_WAVES_PER_SIMD
 #define ZL_ATTN8_WAVES_PER_SIMD 2      // 8-wave instantiation: 2 = one workgroup per CU (135 VGPRs), 4 = two (128 VGPRs, a few spilled)
 #endif
@@ -854,29 +884,82 @@ __device__ __forceinline__ void attn_tail_la(const AttnParams& p, float* xw, int
 // the prefix form compares t1; a 16-row tile walks the keys its LAST row sees, rows that see none of a split leave (0, -1e20, 0)
 // records the merge never reads (k_decode_attn_combine counts a row's splits from its own limit).  The keys a later row sees and an
 // earlier one does not were written this step, so they are finite and need no V zeroing (the mask form's 0 x NaN problem).
-template <int DT, int NW = 4, bool LA = false, int PF = 1, bool MASKED = false, bool CAUSAL = false>
+// SHARED (one query row per task, zl_decode_attn_shared): the workgroup is an item of AttnParams' 1-D grid.  An own item is the prefix
+// form over the task's own buffer with its first key at P_b.  A shared item walks a split of a PREFIX buffer for a 16-row tile of
+// the rows of the prefix's members (member rank * n_rep + head of the group; the members are the tasks with prefix_of == g in task
+// order, counted here from prefix_of itself) -- K / V rows read once for up to 16 query rows of several tasks.  A row's limit is its
+// task's P_b, a lane-constant register as in the causal form; the MFMA columns, the softmax state and the records are per row, so a
+// row's bits depend neither on the rows it shares a tile with nor on its place in the tile.  The tiles of one (prefix, kv head, split)
+// are 8 workgroup ids apart: they run behind one L2 (workgroups are dealt round-robin over the 8 XCDs), which fetches the split once.
+template <int DT, int NW = 4, bool LA = false, int PF = 1, bool MASKED = false, bool CAUSAL = false, bool SHARED = false>
 __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL_ATTN8_OCC(NW)) void k_decode_attn_mfma(const AttnParams p) {
     // (MASKED: two workgroups per SIMD set -- under the prefix form's 128-register budget the visibility word sent the V set to scratch)
     static_assert(!MASKED || (!LA && PF == 1), "the mask form exists for the two-launch route only");
     static_assert(!CAUSAL || (!LA && PF == 1 && !MASKED && NW == 4), "the causal form exists for the two-launch route only");
+    static_assert(!SHARED || (!LA && PF == 1 && !MASKED && !CAUSAL && NW == 4), "the two-segment form exists for the two-launch route only");
     __shared__ __attribute__((aligned(16))) uint16_t vs[NW][32 * kMVS];     // 9 KB per wave (36 / 72 KB); reused for the wave merge
-    const int b = blockIdx.z, hk = CAUSAL ? (int)(blockIdx.y % (unsigned)p.hkv) : (int)blockIdx.y, split = blockIdx.x;
-    // this workgroup's query rows: [row0, row0 + nrows) of the task's len_q * n_rep (one tile of 16 in the causal form)
-    const int row0 = CAUSAL ? 16 * (int)(blockIdx.y / (unsigned)p.hkv) : 0;
-    const int nrows = CAUSAL ? min(16, p.rows - row0) : p.rows;
-    const int len = p.buf_lens[b];
+    int* const row_task = shared_row_tasks<SHARED>();     // SHARED: the task of each row of a shared item's tile (no LDS otherwise)
+    // SHARED: the item of this workgroup -- sg >= 0: a shared item of prefix sg and row tile s_tile, else an own item of task s_b
+    int sg = -1, s_b = 0, s_hk = 0, s_split = 0, s_tile = 0, s_nrows = 0, s_len = 0, s_elen = 0, s_t0 = 0;
+    if constexpr (SHARED) {
+        const int id = blockIdx.x;
+        if (id < p.sh_grid) {
+            const int slot = id >> 3;
+#ifdef ZL_ATTN_SHARED_SPREAD       // A/B build (profiles/shared_prefix.txt, "shared, spread"): an item's tiles are grid neighbours, one per XCD
+            s_tile = id % p.sh_tiles;
+            const int it = id / p.sh_tiles;
+            (void)slot;
+#else
+            s_tile = slot % p.sh_tiles;
+            const int it = (slot / p.sh_tiles) * 8 + (id & 7);
+#endif
+            if (it >= p.g * p.hkv * p.sh_splits) return;         // the padding that keeps an item's tiles 8 ids apart
+            s_split = it % p.sh_splits;
+            s_hk = (it / p.sh_splits) % p.hkv;
+            sg = it / (p.sh_splits * p.hkv);
+            // the prefix's members, 64 tasks per round trip (a lane looks at one task, the ballot counts them): most shared items of
+            // a launch are empty tiles, so what they cost is this count
+            int members = 0;
+            for (int base = 0; base < p.b; base += 64) {
+                const int i = base + (int)(threadIdx.x & 63);
+                members += __popcll(__ballot(i < p.b && p.prefix_of[i] == sg));
+            }
+            s_nrows = min(16, members * p.n_rep - 16 * s_tile);
+            if (s_nrows <= 0) return;
+            s_len = max(0, p.prefix_caps[sg]);
+            s_elen = min(s_len, p.prefix_lens[sg]);
+            s_t0 = s_split * p.sh_split_len;
+        } else {
+            const int oid = id - p.sh_grid;
+            s_split = oid % p.own_splits;
+            s_hk = (oid / p.own_splits) % p.hkv;
+            s_b = oid / (p.own_splits * p.hkv);
+            s_nrows = p.n_rep;
+            s_len = p.buf_lens[s_b];
+            s_elen = min(s_len, p.valid_lens[s_b]);
+            s_t0 = shared_prefix_rows(p, s_b) + s_split * p.split_len;
+        }
+    }
+    const int b = SHARED ? s_b : (int)blockIdx.z;
+    const int hk = SHARED ? s_hk : CAUSAL ? (int)(blockIdx.y % (unsigned)p.hkv) : (int)blockIdx.y;
+    const int split = SHARED ? s_split : (int)blockIdx.x;
+    // this workgroup's query rows: [row0, row0 + nrows) of the task's len_q * n_rep (one tile of 16 in the causal form; SHARED: of the
+    // prefix's members' rows)
+    const int row0 = SHARED ? 16 * s_tile : CAUSAL ? 16 * (int)(blockIdx.y / (unsigned)p.hkv) : 0;
+    const int nrows = SHARED ? s_nrows : CAUSAL ? min(16, p.rows - row0) : p.rows;
+    const int len = SHARED ? s_len : p.buf_lens[b];
     // CAUSAL: the tile's last row sees the most keys
-    const int vlen_in = MASKED ? 0x7fffffff : CAUSAL ? p.valid_lens[b] + (row0 + nrows - 1) / p.n_rep : p.valid_lens[b];
+    const int vlen_in = SHARED ? s_elen : MASKED ? 0x7fffffff : CAUSAL ? p.valid_lens[b] + (row0 + nrows - 1) / p.n_rep : p.valid_lens[b];
     const int8_t* mrow = nullptr;
     if constexpr (MASKED) {
         size_t mask_off = 0;
         for (int i = 0; i < b; ++i) mask_off += (size_t)p.buf_lens[i];
         mrow = p.mask + mask_off;                        // len_q == 1: one row of len entries per task
     }
-    const uint16_t* kbase = p.k_bufs[b];
-    const uint16_t* vbase = p.v_bufs[b];
+    const uint16_t* kbase = (SHARED && sg >= 0) ? p.prefix_k[sg] : p.k_bufs[b];
+    const uint16_t* vbase = (SHARED && sg >= 0) ? p.prefix_v[sg] : p.v_bufs[b];
     const int elen = min(len, vlen_in);
-    const int t0 = split * p.split_len;
+    const int t0 = SHARED ? s_t0 : split * p.split_len;
     const int nw = LA ? __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6)) : NW;   // LA: 1 / 2 / 4 (8) waves, as launched
     ZL_APROBE_INIT();
     ZL_APROBE(0);
@@ -891,7 +974,7 @@ __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL
         }
         return;
     }
-    const int t1 = min(elen, t0 + p.split_len);
+    const int t1 = min(elen, t0 + ((SHARED && sg >= 0) ? p.sh_split_len : p.split_len));
     const int last_key = t1 - 1;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -945,9 +1028,29 @@ __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL
         uint4 z = make_uint4(0, 0, 0, 0);
         const bool live = r < nrows;
         const int rr = row0 + (live ? r : 0);
-        const int qi = rr / p.n_rep, head = hk * p.n_rep + rr % p.n_rep;
+        int qi = rr / p.n_rep, qb = b;
+        const int head = hk * p.n_rep + rr % p.n_rep;
         if constexpr (CAUSAL) rlim = min(t1, p.valid_lens[b] + qi);
-        const uint16_t* qp = p.q + (((size_t)b * p.len_q + qi) * p.h + head) * kMD + 8 * kq;
+        if constexpr (SHARED) {
+            if (sg >= 0) {                              // the row's task: member number qi of the prefix, in task order
+                int seen = 0;
+                qb = 0;
+                for (int base = 0; base < p.b; base += 64) {
+                    const int i = base + lane;
+                    unsigned long long m = __ballot(i < p.b && p.prefix_of[i] == sg);
+                    const int c = __popcll(m);
+                    if (qi >= seen && qi < seen + c) {
+                        for (int k = seen; k < qi; ++k) m &= m - 1;        // drop the members in front of this row's
+                        qb = base + __ffsll(m) - 1;
+                    }
+                    seen += c;
+                }
+                rlim = min(t1, shared_prefix_rows(p, qb));
+                if (wave == 0 && kq == 0) row_task[r] = qb;
+            }
+            qi = 0;
+        }
+        const uint16_t* qp = p.q + (((size_t)qb * p.len_q + qi) * p.h + head) * kMD + 8 * kq;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             uint4 v = *reinterpret_cast<const uint4*>(qp + 32 * t);
@@ -1000,7 +1103,7 @@ __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int key = cur + 16 * blk + 4 * kq + i;
-                bool vis = key < (CAUSAL ? rlim : t1);
+                bool vis = key < ((CAUSAL || SHARED) ? rlim : t1);
                 if constexpr (MASKED) vis = (vbits >> (16 * blk + 4 * kq + i)) & 1u;      // the ballot already holds key < t1
                 sv[blk][i] = vis ? st[blk][i] * p.scale : -INFINITY;
                 mloc = fmaxf(mloc, sv[blk][i]);
@@ -1118,8 +1221,10 @@ __global__ __launch_bounds__(64 * NW, PF >= 3 ? 1 : (PF == 2 || MASKED) ? 2 : ZL
             a = __builtin_fmaf(src[w * WS + d], f, a);
             lt = __builtin_fmaf(src[w * WS + kMD + 1], f, lt);
         }
-        const int qi = (row0 + i) / p.n_rep, head = hk * p.n_rep + (row0 + i) % p.n_rep;
-        const size_t rec = (((size_t)b * p.len_q + qi) * p.h + head) * p.max_splits + split;
+        const int qi = SHARED ? 0 : (row0 + i) / p.n_rep, head = hk * p.n_rep + (row0 + i) % p.n_rep;
+        // SHARED: a shared item's record goes to the row's task, an own item's behind the task's sh_splits shared slots
+        const int rb = (SHARED && sg >= 0) ? row_task[i] : b, rs = (SHARED && sg < 0) ? p.sh_splits + split : split;
+        const size_t rec = (((size_t)rb * p.len_q + qi) * p.h + head) * p.max_splits + rs;
         if (p.half_partials) {
             uint16_t* hp = reinterpret_cast<uint16_t*>(p.ws);
             // lt >= 1: the split's largest score gives exp(0) -- except, in the mask form, a split without a visible key (lt = 0)
@@ -1441,6 +1546,65 @@ __global__ __launch_bounds__(kMD) void k_decode_attn_combine_h(const AttnParams 
     p.out[(size_t)vh * kMD + d] = __builtin_bit_cast(uint16_t, zl_f32_to_f16(a * zi));
 }
 
+// The merge of the two-segment form (zl_decode_attn_shared): a (task, head)'s ceil(P / sh_split_len) shared records and its
+// ceil((valid - P) / split_len) own ones, counted from the tables as the partial launch clipped them, folded with
+// k_decode_attn_combine's arithmetic.  grid (B * H), block 128.  A task without a visible key has no record and gets a zero row.
+template <int DT>
+__global__ __launch_bounds__(kMD) void k_decode_attn_shared_combine(const AttnParams p) {
+    __shared__ float sm[kMaxSplits], sl[kMaxSplits];
+    const int vh = blockIdx.x, b = vh / p.h, d = threadIdx.x;
+    const int pre = shared_prefix_rows(p, b);
+    const int elen = min(p.buf_lens[b], p.valid_lens[b]);
+    const int ns_sh = min((pre + p.sh_split_len - 1) / p.sh_split_len, p.sh_splits);
+    const int ns_own = elen > pre ? min((elen - pre + p.split_len - 1) / p.split_len, p.own_splits) : 0;
+    const int ns = ns_sh + ns_own;
+    const float* src = p.ws + (size_t)vh * p.max_splits * (kMD + 2);
+    auto slot = [&](int s) { return s < ns_sh ? s : p.sh_splits + (s - ns_sh); };
+    // as in k_decode_attn_combine, the accumulator loads must not queue up behind one another or behind the statistics: up to 16
+    // records are requested at once, before the statistics have come back through LDS; more go four at a time
+    float v[16];
+    if (ns <= 16) {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = src[(size_t)slot(min(u, max(ns - 1, 0))) * (kMD + 2) + d];
+    }
+    for (int s = d; s < ns; s += kMD) {
+        const float* rec = src + (size_t)slot(s) * (kMD + 2);
+        sm[s] = rec[kMD];
+        sl[s] = rec[kMD + 1];
+    }
+    __syncthreads();
+    float mn = -1e20f;
+    for (int s = 0; s < ns; ++s) mn = fmaxf(mn, sm[s]);
+    float a = 0.f, z = 0.f;
+    if (ns <= 16) {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            if (u < ns) {
+                const float f = __expf(sm[u] - mn);
+                a = __builtin_fmaf(v[u], f, a);
+                z = __builtin_fmaf(sl[u], f, z);
+            }
+        }
+    } else {
+        int s = 0;
+        for (; s + 4 <= ns; s += 4) {
+            const float v0 = src[(size_t)slot(s) * (kMD + 2) + d], v1 = src[(size_t)slot(s + 1) * (kMD + 2) + d];
+            const float v2 = src[(size_t)slot(s + 2) * (kMD + 2) + d], v3 = src[(size_t)slot(s + 3) * (kMD + 2) + d];
+            const float f0 = __expf(sm[s] - mn), f1 = __expf(sm[s + 1] - mn), f2 = __expf(sm[s + 2] - mn), f3 = __expf(sm[s + 3] - mn);
+            a = __builtin_fmaf(v0, f0, a); z = __builtin_fmaf(sl[s], f0, z);
+            a = __builtin_fmaf(v1, f1, a); z = __builtin_fmaf(sl[s + 1], f1, z);
+            a = __builtin_fmaf(v2, f2, a); z = __builtin_fmaf(sl[s + 2], f2, z);
+            a = __builtin_fmaf(v3, f3, a); z = __builtin_fmaf(sl[s + 3], f3, z);
+        }
+        for (; s < ns; ++s) {
+            const float f = __expf(sm[s] - mn);
+            a = __builtin_fmaf(src[(size_t)slot(s) * (kMD + 2) + d], f, a);
+            z = __builtin_fmaf(sl[s], f, z);
+        }
+    }
+    p.out[(size_t)vh * kMD + d] = ZT<DT>::from_f32(a / (z + 1e-20f));
+}
+
 // ---- host side: one place for the launch parameters' geometry, one for each launch --------------------------------------------
 // An entry point below checks its arguments, names the AttnParams fields it sets differently from the struct's defaults, takes the
 // geometry from attn_geometry and hands the struct to a launch helper.  A new variant's field is a default in the struct and one
@@ -1648,6 +1812,60 @@ int zl_decode_attn_causal(const uint16_t* q, const int32_t* buf_lens, const uint
     ZL_CHECK_ARG(b <= 65535 && hkv * tiles <= 65535 && b * len_q * h < ((int64_t)1 << 31), ZL_ELIMIT);
     ZL_ATTN_TRY(launch_mfma<4, false, 1, false, true>(p, dtype, (hipStream_t)s));
     return launch_combine<kMD>(p, dtype, (hipStream_t)s);
+}
+
+int64_t zl_decode_attn_shared_workspace_bytes(int64_t b, int64_t g, int64_t h, int64_t hkv, int64_t d, int64_t max_prefix_len,
+                                              int64_t max_len_buf) {
+    if (b <= 0 || g <= 0 || h <= 0 || hkv <= 0 || d <= 0 || max_prefix_len <= 0 || max_len_buf <= 0) return ZL_EINVAL;
+    // record slots of a (task, head) at the smallest split (128 keys) on both sides
+    return b * h * ((max_prefix_len + 127) / 128 + (max_len_buf + 127) / 128) * (d + 2) * 4;
+}
+
+int zl_decode_attn_shared_ex(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs, const uint16_t* const* v_bufs,
+                             const int32_t* valid_lens, const int32_t* prefix_of, const int32_t* prefix_lens, const int32_t* prefix_caps,
+                             const uint16_t* const* prefix_k, const uint16_t* const* prefix_v, uint16_t* out, void* workspace, int64_t b,
+                             int64_t g, int64_t h, int64_t hkv, int64_t d, float scale, int64_t max_prefix_len, int64_t max_len_buf,
+                             int bshd, int dtype, int64_t shared_split_len, int64_t own_split_len, zl_stream_t s) {
+    ZL_ATTN_TRY(attn_check_args(q && buf_lens && k_bufs && v_bufs && valid_lens && prefix_of && prefix_lens && prefix_caps && prefix_k &&
+                                    prefix_v && out && workspace, b, 1, h, hkv, d, max_len_buf));
+    ZL_CHECK_ARG(g > 0 && max_prefix_len > 0, ZL_EINVAL);
+    // 128 keys at least: the workspace is sized for that (zl_decode_attn_shared_workspace_bytes)
+    for (const int64_t sl : {shared_split_len, own_split_len}) ZL_CHECK_ARG(sl == 0 || (sl >= 128 && sl % 32 == 0 && sl <= ((int64_t)1 << 30)), ZL_EINVAL);
+    ZL_CHECK_ARG(d == kMD && h / hkv <= 16, ZL_ESHAPE);
+    ZL_CHECK_ARG(attn_dtype_ok(dtype), ZL_EDTYPE);
+    ZL_CHECK_ARG(b <= 65535 && g <= 65535 && hkv <= 65535 && max_prefix_len < ((int64_t)1 << 30) && max_len_buf < ((int64_t)1 << 30), ZL_ELIMIT);
+    AttnParams p;
+    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.valid_lens = valid_lens;
+    p.prefix_of = prefix_of; p.prefix_lens = prefix_lens; p.prefix_caps = prefix_caps; p.prefix_k = prefix_k; p.prefix_v = prefix_v;
+    p.out = out; p.ws = (float*)workspace; p.scale = scale; p.bshd = bshd; p.passes = 1; p.g = (int)g;
+    ZL_ATTN_TRY(attn_geometry(p, b, 1, h, hkv, max_len_buf, kMaxSplits, (int)own_split_len));
+    p.own_splits = p.max_splits;
+    // 16-row tiles the rows of one prefix's members can fill, and the split that gives the shared items about a chip's worth of workgroups
+    p.sh_tiles = (int)((b * p.n_rep + 15) / 16);
+    p.sh_split_len = shared_split_len ? (int)shared_split_len : attn_split_len(g * p.sh_tiles, hkv, max_prefix_len);
+    p.sh_splits = (int)((max_prefix_len + p.sh_split_len - 1) / p.sh_split_len);
+    p.max_splits = p.sh_splits + p.own_splits;
+    ZL_CHECK_ARG(p.max_splits <= kMaxSplits, ZL_ELIMIT);
+    const int64_t sh_grid = (g * hkv * p.sh_splits + 7) / 8 * 8 * p.sh_tiles, grid = sh_grid + b * hkv * p.own_splits;
+    ZL_CHECK_ARG(grid < ((int64_t)1 << 31) && b * h < ((int64_t)1 << 31), ZL_ELIMIT);
+    p.sh_grid = (int)sh_grid;
+    hipStream_t hs = (hipStream_t)s;
+    return by_dtype(dtype, [&](auto dt) -> int {
+        constexpr int DT = decltype(dt)::value;
+        hipLaunchKernelGGL((k_decode_attn_mfma<DT, 4, false, 1, false, false, true>), dim3((unsigned)grid), dim3(256), 0, hs, p);
+        ZL_ATTN_TRY(zl_launch_status());
+        hipLaunchKernelGGL((k_decode_attn_shared_combine<DT>), dim3((unsigned)(b * h)), dim3(kMD), 0, hs, p);
+        return zl_launch_status();
+    });
+}
+
+int zl_decode_attn_shared(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs, const uint16_t* const* v_bufs,
+                          const int32_t* valid_lens, const int32_t* prefix_of, const int32_t* prefix_lens, const int32_t* prefix_caps,
+                          const uint16_t* const* prefix_k, const uint16_t* const* prefix_v, uint16_t* out, void* workspace, int64_t b,
+                          int64_t g, int64_t h, int64_t hkv, int64_t d, float scale, int64_t max_prefix_len, int64_t max_len_buf,
+                          int bshd, int dtype, zl_stream_t s) {
+    return zl_decode_attn_shared_ex(q, buf_lens, k_bufs, v_bufs, valid_lens, prefix_of, prefix_lens, prefix_caps, prefix_k, prefix_v, out,
+                                    workspace, b, g, h, hkv, d, scale, max_prefix_len, max_len_buf, bshd, dtype, 0, 0, s);
 }
 
 int64_t zl_decode_attn_split_len(int64_t b, int64_t hkv, int64_t max_len_buf) {

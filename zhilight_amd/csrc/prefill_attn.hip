@@ -72,6 +72,11 @@ struct PrefillParams {
     const float* const* v_scales;
     const uint16_t* k_new;          // (total_q, hkv, D), rows as q's
     const uint16_t* v_new;
+    // HIST (varlen only): rows below a task's pos0 come from its UNQUANTISED history buffer (hist_lens[task] rows, BSHD), rows from
+    // pos0 on from k_new / v_new as in the Q8 form
+    const uint16_t* const* hist_k;
+    const uint16_t* const* hist_v;
+    const int32_t* hist_lens;
 };
 
 template <int DT>
@@ -107,8 +112,9 @@ __device__ __forceinline__ uint4 pf_deq8(uint32_t lo, uint32_t hi, float sc) {
 // DT = ZL_F16 / ZL_BF16: probabilities are rounded to T for the P.V product (flash-attention arithmetic)
 constexpr int kGroupLds = (kBK * kKRow + kBK * kVRow) * 2;     // one group's K + V tile: 35 840 bytes (>= its 32.5 KB merge record)
 
-template <int DT, int G, bool Q8 = false>
+template <int DT, int G, bool Q8 = false, bool HIST = false>
 __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const PrefillParams p) {
+    static_assert(!(Q8 && HIST), "one kind of history per launch");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_pf[];
     const int group = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));     // 4 waves each
     uint16_t* ks = reinterpret_cast<uint16_t*>(smem_pf + (size_t)group * kGroupLds);
@@ -135,7 +141,9 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
     const uint8_t* vcod = nullptr;
     const float* ksc = nullptr;
     const float* vsc = nullptr;
-    if (Q8 || p.work) {
+    const uint16_t* hkb = nullptr;                        // HIST: the task's history buffer
+    const uint16_t* hvb = nullptr;
+    if (Q8 || HIST || p.work) {
         // varlen: the caller's table lists the (task, query tile) items longest first, so item order is LPT order across the tasks as
         // it is within one task above.  A wrong table cannot make the workgroup read or write outside the operands: an item outside
         // the tasks or past its task's rows is dropped, the rows are clamped to total_q and the keys to the buffer's length
@@ -154,6 +162,12 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
             kcod = p.k_codes[task]; vcod = p.v_codes[task];
             ksc = p.k_scales[task]; vsc = p.v_scales[task];
             if (pos0 > 0 && (!kcod || !vcod || !ksc || !vsc)) return;    // a task without history may leave them null
+        } else if constexpr (HIST) {
+            kb = p.k_new + (size_t)qa * p.hkv * kD;
+            vb = p.v_new + (size_t)qa * p.hkv * kD;
+            hkb = p.hist_k[task]; hvb = p.hist_v[task];
+            // a task without history may leave them null; a history shorter than pos0 cannot hold the rows below pos0: dropped
+            if (pos0 > 0 && (!hkb || !hvb || p.hist_lens[task] < pos0)) return;
         } else {
             kb = p.k_bufs[task];
             vb = p.v_bufs[task];
@@ -222,9 +236,11 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 4) void k_prefill_attn(const 
             hq = dead_ ? 1 : 3;                                                                            \
             if (dead_) { vr0 = vr1 = vr2 = vr3 = make_uint4(0, 0, 0, 0); }                                 \
         } else {                                                                                           \
-            const size_t ro_ = Q8 ? (size_t)(kc_ - pos0) * kv_stride : (size_t)kc_ * kv_stride;            \
-            const uint16_t* kp_ = kb + kv_off + ro_;                                                       \
-            const uint16_t* vp_ = vb + kv_off + ro_;                                                       \
+            const bool hist_ = HIST && kc_ < pos0;        /* a history row: row kc_ of the task's BSHD history buffer */ \
+            const size_t ro_ = hist_ ? ((size_t)kc_ * p.hkv + hk) * kD                                     \
+                                     : kv_off + ((Q8 || HIST) ? (size_t)(kc_ - pos0) * kv_stride : (size_t)kc_ * kv_stride); \
+            const uint16_t* kp_ = (hist_ ? hkb : kb) + ro_;                                                \
+            const uint16_t* vp_ = (hist_ ? hvb : vb) + ro_;                                                \
             ZL_PF_LOAD1(0, kp_, vp_, dead_) ZL_PF_LOAD1(1, kp_, vp_, dead_) ZL_PF_LOAD1(2, kp_, vp_, dead_) ZL_PF_LOAD1(3, kp_, vp_, dead_) \
             hq = 0;                                                                                        \
         }                                                                                                  \
@@ -430,20 +446,20 @@ extern "C" int zl_prefill_attn(const uint16_t* q, const uint16_t* k_buf, const u
     return zl_prefill_attn_ex(q, k_buf, v_buf, out, s_q, pos0, h, hkv, d, scale, len_buf, bshd, dtype, 0, s);
 }
 
-template <int DT, int G, bool Q8 = false>
+template <int DT, int G, bool Q8 = false, bool HIST = false>
 static int launch_prefill(const PrefillParams& p, dim3 grid, hipStream_t hs) {
     const size_t lds = (size_t)G * kGroupLds + (size_t)4 * G * 16 * sizeof(float);       // tiles + one 64-byte strip per wave
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prefill_attn<DT, G, Q8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prefill_attn<DT, G, Q8, HIST>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return ZL_ELIMIT;
     }
-    hipLaunchKernelGGL((k_prefill_attn<DT, G, Q8>), grid, dim3(256 * G), lds, hs, p);
+    hipLaunchKernelGGL((k_prefill_attn<DT, G, Q8, HIST>), grid, dim3(256 * G), lds, hs, p);
     return zl_launch_status();
 }
 
 // the launch of either form: `groups` wave groups per workgroup (1 / 2 / 4: the key tiles of a query tile are dealt to them
 // round-robin; 0 = the launcher's choice), one workgroup per (work item, head)
-template <bool Q8 = false>
+template <bool Q8 = false, bool HIST = false>
 static int dispatch_prefill(PrefillParams& p, int64_t items, int dtype, int groups, bool plain_map, hipStream_t hs) {
     ZL_CHECK_ARG(items * p.h < ((int64_t)1 << 31), ZL_ELIMIT);
     const dim3 grid((unsigned)(items * p.h));
@@ -455,7 +471,7 @@ static int dispatch_prefill(PrefillParams& p, int64_t items, int dtype, int grou
     const int total = (int)(items * p.h);
     p.pair = (groups == 1 && total % 2 == 0 && total <= 2 * cus) ? 1 : 0;
     if (plain_map) p.pair = 2;
-#define ZL_PF_G(GG) return dtype == ZL_F16 ? launch_prefill<ZL_F16, GG, Q8>(p, grid, hs) : launch_prefill<ZL_BF16, GG, Q8>(p, grid, hs);
+#define ZL_PF_G(GG) return dtype == ZL_F16 ? launch_prefill<ZL_F16, GG, Q8, HIST>(p, grid, hs) : launch_prefill<ZL_BF16, GG, Q8, HIST>(p, grid, hs);
     switch (groups) {
         case 1: ZL_PF_G(1)
         case 2: ZL_PF_G(2)
@@ -526,4 +542,27 @@ extern "C" int zl_prefill_attn_varlen_q8(const uint16_t* q, const int32_t* cu_se
     p.k_codes = k_codes; p.v_codes = v_codes; p.k_scales = k_scales; p.v_scales = v_scales; p.k_new = k_new; p.v_new = v_new;
     p.n_work = (int)n_work; p.b = (int)b; p.total_q = (int)total_q;
     return dispatch_prefill<true>(p, n_work, dtype, groups, false, (hipStream_t)s);
+}
+
+// the varlen launch on an unquantised history: rows below pos0[i] are read from the task's history buffer hist_k[i] / hist_v[i]
+// (hist_lens[i] rows, BSHD), rows from pos0[i] on from k_new / v_new -- zl_prefill_attn_varlen_q8's two sources without the dequant.
+// What is staged is what zl_prefill_attn_varlen stages from a buffer that holds both, so the outputs are equal bit for bit
+extern "C" int zl_prefill_attn_varlen_hist(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                                           const uint16_t* const* hist_k, const uint16_t* const* hist_v, const int32_t* hist_lens,
+                                           const uint16_t* k_new, const uint16_t* v_new, uint16_t* out,
+                                           const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
+                                           int64_t d, float scale, int dtype, int groups, zl_stream_t s) {
+    ZL_CHECK_ARG(q && cu_seqlens_q && pos0 && buf_lens && hist_k && hist_v && hist_lens && k_new && v_new && out && work, ZL_EINVAL);
+    ZL_CHECK_ARG(b > 0 && total_q > 0 && n_work > 0 && h > 0 && hkv > 0, ZL_EINVAL);
+    ZL_CHECK_ARG(d == kD && h % hkv == 0, ZL_ESHAPE);
+    ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
+    ZL_CHECK_ARG(groups == 0 || groups == 1 || groups == 2 || groups == 4, ZL_EINVAL);
+    ZL_CHECK_ARG(h <= 65535 && b < ((int64_t)1 << 30) && total_q < ((int64_t)1 << 31) && n_work < ((int64_t)1 << 31), ZL_ELIMIT);
+    PrefillParams p = {};
+    p.q = q; p.out = out;
+    p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv); p.bshd = 1; p.scale = scale;
+    p.work = work; p.cu_q = cu_seqlens_q; p.pos0s = pos0; p.buf_lens = buf_lens;
+    p.hist_k = hist_k; p.hist_v = hist_v; p.hist_lens = hist_lens; p.k_new = k_new; p.v_new = v_new;
+    p.n_work = (int)n_work; p.b = (int)b; p.total_q = (int)total_q;
+    return dispatch_prefill<false, true>(p, n_work, dtype, groups, false, (hipStream_t)s);
 }

@@ -950,6 +950,29 @@ class DynBatchContext:
     # stood at `at`, so it has room - (at - steps_left) left now; admit / park take the minimum of these when a guarded slot replaces
     # the one that bounded steps_left.  A slot in neither table is bounded by steps_left as it stands
     slot_room: Dict[int, tuple] = field(default_factory=dict)
+    # LLaMA.new_shared_prefixes: prefix buffers that slots read their first keys from instead of holding a copy (SharedPrefixes); a
+    # context that has them decodes through zl_decode_attn_shared
+    shared: Optional["SharedPrefixes"] = None
+
+
+@dataclass
+class SharedPrefixes:
+    """The prefix table of a context (LLaMA.new_shared_prefixes; include/zhilight_amd.h, zl_decode_attn_shared, has the rule): G buffers
+    of `rows` K/V rows for every layer, and per slot the prefix it reads its first keys from.  The host mirrors are what the admission
+    calls check against; nothing but LLaMA.load_prefix / admit / admit_samples / park writes either side."""
+    kv: List[torch.Tensor]      # owners: per prefix (layers, 2, rows, Hkv, D)
+    k_addrs: torch.Tensor       # (layers, G) int64
+    v_addrs: torch.Tensor
+    prefix_of: torch.Tensor     # (B) int32, -1 = none
+    prefix_lens: torch.Tensor   # (G) int32 valid rows
+    prefix_caps: torch.Tensor   # (G) int32, all `rows`
+    rows: int
+    of_host: List[int] = field(default_factory=list)
+    lens_host: List[int] = field(default_factory=list)
+
+    def users(self, g):
+        """the slots that read prefix g"""
+        return [s for s, v in enumerate(self.of_host) if v == g]
 
 
 # LLaMA.verify's result: the (B * len_q, vocab) logits of the step's rows, accepted (B) int32 drafts per task, tokens (B, len_q) int32 =
@@ -1066,15 +1089,17 @@ class _PromptRows:
       k_tab / v_tab / ks_tab / vs_tab, kv, kv_off    its buffers: (layers, n) pointer tables ("cache", "temp", "q8"); the one task's
                                  (layers, 2, rows, Hkv, D) tensor for the one-task launch ("cache", "temp"); "own": the byte offset
                                  of each task's first row in the call's k / v
-      last_rows, tasks_dev, ends_dev    the tail: int64 row of each task's last token, its index, int32 end -- None for one task"""
+      last_rows, tasks_dev, ends_dev    the tail: int64 row of each task's last token, its index, int32 end -- None for one task
+      hist_lens, hist_lens_dev   "hist" (prompts behind a shared prefix, `prefixes` = a prefix index or None per task): the rows each task
+                                 reads from its prefix buffer (= its pos0, 0 for None); k_tab / v_tab point to the prefix buffers"""
     labels_dev = ks_rows = vs_rows = len_bufs_dev = plan = k_tab = v_tab = ks_tab = vs_tab = kv = kv_off = None
-    last_rows = tasks_dev = ends_dev = None
+    last_rows = tasks_dev = ends_dev = hist_lens = hist_lens_dev = None
 
     @classmethod
-    def of(cls, model, ctx, tasks, prompts, pos0s, q8_history=False, labels=None):
-        if len(tasks) == 1:
+    def of(cls, model, ctx, tasks, prompts, pos0s, q8_history=False, labels=None, prefixes=None):
+        if len(tasks) == 1 and prefixes is None:
             return cls.one(model, ctx, tasks[0], prompts[0], pos0s[0], q8_history, labels)
-        return cls.many(model, ctx, tasks, prompts, pos0s, q8_history, labels)
+        return cls.many(model, ctx, tasks, prompts, pos0s, q8_history, labels, prefixes)
 
     @classmethod
     def one(cls, model, ctx, task, prompt, pos0, q8_history=False, labels=None, pos=None):
@@ -1113,7 +1138,7 @@ class _PromptRows:
         return r
 
     @classmethod
-    def many(cls, model, ctx, tasks, prompts, pos0s, q8_history=False, labels=None):
+    def many(cls, model, ctx, tasks, prompts, pos0s, q8_history=False, labels=None, prefixes=None):
         """the pieces of n tasks back to back: the K/V scatter takes one "task" per row, the attention one table entry per task"""
         r, c, dev = cls(), model.cfg, model.device
         n = len(tasks)
@@ -1139,7 +1164,15 @@ class _PromptRows:
         r.k_rows, r.v_rows = ctx.k_addrs.index_select(1, rows_dev), ctx.v_addrs.index_select(1, rows_dev)
         if ctx.kv_quant:
             r.ks_rows, r.vs_rows = ctx.ks_addrs.index_select(1, rows_dev), ctx.vs_addrs.index_select(1, rows_dev)
-        if q8_history:                                    # history from the cache, own rows from the concatenated k / v
+        if prefixes is not None:                          # history from the tasks' prefix buffers, own rows from the concatenated k / v
+            sh, g_n = ctx.shared, ctx.shared.prefix_lens.numel()
+            r.route, r.att_pos0s, r.len_bufs = "hist", pos0s, [ctx.max_len_buf] * n
+            r.hist_lens = [0 if g is None else p0 for g, p0 in zip(prefixes, pos0s)]
+            r.hist_lens_dev = torch.tensor(r.hist_lens, dtype=torch.int32).to(dev)
+            pick = torch.tensor([g_n if g is None else g for g in prefixes], dtype=torch.int64).to(dev)     # column G: a null pointer
+            null = torch.zeros((sh.k_addrs.shape[0], 1), dtype=torch.int64, device=dev)
+            r.k_tab, r.v_tab = (torch.cat([t, null], dim=1).index_select(1, pick) for t in (sh.k_addrs, sh.v_addrs))
+        elif q8_history:                                  # history from the cache, own rows from the concatenated k / v
             r.route, r.att_pos0s, r.len_bufs = "q8", pos0s, [ctx.max_len_buf] * n
             r.k_tab, r.v_tab = ctx.k_addrs.index_select(1, r.tasks_dev), ctx.v_addrs.index_select(1, r.tasks_dev)
             r.ks_tab, r.vs_tab = ctx.ks_addrs.index_select(1, r.tasks_dev), ctx.vs_addrs.index_select(1, r.tasks_dev)
@@ -1167,7 +1200,7 @@ class _DecodeRoute:
     encode's layer body (DESIGN 4 "One route, one layer body" has the condition and the ZL_* switch of every value)."""
     qkv: str                    # "w4" zl_w4a16_qkv_rope_scatter | "w8" layernorm_quant + w8a8_qkv_rope_scatter | "plain" project_qkv + rope / scatter
     norm: Optional[str]         # "w4" only, its RMSNorm: "fused" in registers | "launch" of its own | "row_ss" from statistics the projections hand on
-    attn: str                   # "hook" | "la" | "splits" (records left for attn_out) | "mqa" | "valu_fused" (rope / scatter included) | "quant"
+    attn: str                   # "hook" | "shared" (zl_decode_attn_shared: a context with a prefix table) | "la" | "splits" (records left for attn_out) | "mqa" | "valu_fused" (rope / scatter included) | "quant"
     out: str                    # "merge" w4_attn_out_merge | "merge_gate_up" w4_attn_out_gate_up, "merge" where it declines | "linear" attn_out_add
     skip_attn: bool             # bench.py's legs, resolved against the route: stage 2 is left out ...
     skip_proj: bool             # ... stages 1 and 3 are
@@ -1405,6 +1438,82 @@ class LLaMA:
             valid_lens=torch.full((batch,), start_pos + 1, **i32), k_addrs=k_addrs, v_addrs=v_addrs,
             max_len_buf=len_buf, kv=kv, **quant_kw)
 
+    def new_shared_prefixes(self, ctx: DynBatchContext, count: int, rows: int) -> SharedPrefixes:
+        """Give ctx `count` prefix buffers of `rows` K/V rows (every layer, the context's BSHD layout and element type) and the table
+        that lets a slot say "my first P keys live over there" (SharedPrefixes; zl_decode_attn_shared has the rule).  From here on the
+        context's decode steps run the two-segment attention; a slot whose prefix_of is -1 -- all of them now -- attends over its own
+        buffer as before.  Refused: an INT8 cache, tensor parallelism, a head size other than 128 or more than 16 query heads per kv
+        head, a row-expanded view, a context that has a table already."""
+        c, dev = self.cfg, self.device
+        count, rows = int(count), int(rows)
+        if ctx.kv_quant or self.tp or c.dim_head != 128 or c.num_heads // c.num_kv_heads > 16 or ctx.row_expanded:
+            raise ops.ZLError("new_shared_prefixes: not on an INT8 KV cache, under tensor parallelism, for a row-expanded view, nor for head "
+                              "sizes other than 128 / more than 16 query heads per kv head")
+        if ctx.shared is not None or count < 1 or rows < 1:
+            raise ops.ZLError("new_shared_prefixes: one table per context, of one buffer and one row at least")
+        b = ctx.tokens.numel()
+        kv = [torch.zeros((c.num_layers, 2, rows, c.num_kv_heads, c.dim_head), dtype=c.torch_dtype, device=dev) for _ in range(count)]
+        i32 = dict(dtype=torch.int32, device=dev)
+        ctx.shared = SharedPrefixes(
+            kv=kv, rows=rows,
+            k_addrs=torch.tensor([[t[l, 0].data_ptr() for t in kv] for l in range(c.num_layers)], dtype=torch.int64, device=dev),
+            v_addrs=torch.tensor([[t[l, 1].data_ptr() for t in kv] for l in range(c.num_layers)], dtype=torch.int64, device=dev),
+            prefix_of=torch.full((b,), -1, **i32), prefix_lens=torch.zeros(count, **i32), prefix_caps=torch.full((count,), rows, **i32),
+            of_host=[-1] * b, lens_host=[0] * count)
+        return ctx.shared
+
+    def _load_prefixes(self, what, ctx: DynBatchContext, gs, token_lists):
+        """encode token_lists[j] into prefix buffer gs[j], all in one pass through the existing prompt path: an auxiliary context whose
+        task j's buffer IS prefix gs[j] -> the logits of every list's last row.  Checked before any launch: a table, distinct indices
+        in range that no slot reads, 1 <= tokens <= rows."""
+        sh = ctx.shared
+        if sh is None:
+            raise ops.ZLError(f"{what}: the context has no shared prefixes (LLaMA.new_shared_prefixes)")
+        gs = [int(g) for g in gs]
+        toks = [torch.as_tensor(t).reshape(-1) for t in token_lists]
+        if not gs or len(set(gs)) != len(gs) or any(not 0 <= g < len(sh.kv) for g in gs):
+            raise ops.ZLError(f"{what}: distinct prefix indices below {len(sh.kv)}")
+        for g, t in zip(gs, toks):
+            if not 1 <= t.numel() <= sh.rows:
+                raise ops.ZLError(f"{what}: prefix {g}: {t.numel()} tokens, the buffer holds 1 .. {sh.rows}")
+            if sh.users(g):
+                raise ops.ZLError(f"{what}: prefix {g} is read by slots {sh.users(g)}")
+        n, dev = len(gs), self.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        cols = torch.tensor(gs, dtype=torch.int64, device=dev)
+        aux = DynBatchContext(tokens=torch.zeros(n, **i32), positions=torch.zeros(n, **i32), placement=torch.zeros(n, **i32),
+                              buf_lens=torch.full((n,), sh.rows, **i32), valid_lens=torch.ones(n, **i32),
+                              k_addrs=sh.k_addrs.index_select(1, cols), v_addrs=sh.v_addrs.index_select(1, cols), max_len_buf=sh.rows,
+                              kv=[sh.kv[g] for g in gs])
+        r, hidden = self._prefill_rows(aux, list(range(n)), toks, [0] * n)
+        last = hidden[-1:] if r.last_rows is None else hidden.index_select(0, r.last_rows)
+        logits = self._prompt_logits_and_pick(last, aux.tokens)
+        lens = [int(t.numel()) for t in toks]
+        sh.prefix_lens.index_copy_(0, cols, torch.tensor(lens, dtype=torch.int32).to(dev))
+        for g, s in zip(gs, lens):
+            sh.lens_host[g] = s
+        return logits
+
+    def load_prefix(self, ctx: DynBatchContext, g: int, tokens):
+        """Encode `tokens` into prefix buffer g of the context's table and set its length -> the logits of the last row (1, vocab).
+        Refused while a slot reads the prefix."""
+        return self._load_prefixes("load_prefix", ctx, [g], [tokens])
+
+    def _set_prefix_of(self, ctx: DynBatchContext, slots, values):
+        """prefix_of[slots[j]] = values[j] on the device (in place: a captured step reads the table) and in the host mirror"""
+        sh = ctx.shared
+        both = torch.tensor(list(slots) + list(values), dtype=torch.int64).to(self.device)
+        sh.prefix_of.index_copy_(0, both[:len(slots)], both[len(slots):].to(torch.int32))
+        for s, v in zip(slots, values):
+            sh.of_host[s] = v
+
+    def release_prefix(self, ctx: DynBatchContext, slots):
+        """the slots read no prefix any more (prefix_of = -1): for slots that are about to be admitted anew"""
+        if ctx.shared is not None:
+            stale = [int(s) for s in slots if ctx.shared.of_host[int(s)] != -1]
+            if stale:
+                self._set_prefix_of(ctx, stale, [-1] * len(stale))
+
     def _buffers(self, b):
         if b not in self._bufs:
             c, dev = self.cfg, self.device
@@ -1428,6 +1537,19 @@ class LLaMA:
         if ctx.steps_left <= 0 and not torch.cuda.is_current_stream_capturing():
             raise ops.ZLError("decode step past the end of the KV buffers (placement >= len_buf): grow the buffers first "
                               "(the reference asserts pos_buf < len_buf, ragged_buffer_kernel.cu:194-222)")
+        sh = ctx.shared
+        if sh is not None:
+            # a context with a prefix table: the two-segment attention between the qkv stage and a plain attn_out projection -- no
+            # merging prologue, no in-launch merge (their records know one segment).  Every other context is routed as before
+            if attend_rows is not None:
+                raise ops.ZLError("speculative rows (verify / step_lookup) over shared prefixes are not supported")
+            if gemv_only or skip_gemv:
+                raise ops.ZLError("gemv_only / skip_gemv: not on a context with shared prefixes")
+            key = ("shared_ws", b, len(sh.kv), sh.rows, ctx.max_len_buf)
+            if key not in self._bufs:
+                self._bufs[key] = ops.decode_attn_shared_workspace(b, len(sh.kv), c.num_heads, c.num_kv_heads, c.dim_head, sh.rows,
+                                                                   ctx.max_len_buf, self.device)
+            workspace = self._bufs[key]
         if workspace is None:
             workspace = self._bufs.setdefault(("ws", b, ctx.max_len_buf),
                                               ops.decode_attn_workspace(b, 1, c.num_heads, c.dim_head, ctx.max_len_buf, self.device))
@@ -1445,7 +1567,7 @@ class LLaMA:
             qkv = "w8"
         # a few rows: the split merge of the decode attention rides in the attn_out projection's prologue (one launch less)
         merge_plan = None
-        if qkv == "w4" and not self.tp and attend_rows is None and env("ZL_ATTN_MERGE", "1") != "0" and all(l.attn_out.perm is None for l in self.layers):
+        if qkv == "w4" and not self.tp and attend_rows is None and sh is None and env("ZL_ATTN_MERGE", "1") != "0" and all(l.attn_out.perm is None for l in self.layers):
             merge_plan = ops.attn_merge_plan(b, c.num_heads, c.num_kv_heads, c.dim_head, ctx.max_len_buf, first.attn_out.weight, c.torch_dtype)
         # the split merge INSIDE the attention launch (last-arriving workgroup of a (task, kv head) pair, zl_decode_attn_la) wherever
         # the step would otherwise run the two-launch path (split kernel + merge kernel): same records, same merge arithmetic, one
@@ -1454,7 +1576,7 @@ class LLaMA:
         # ZL_ATTN_LA: auto (default) / 0 off / 1 everywhere; ZL_ATTN_LA_SPLIT = keys per split (multiple of 32, 0 = the two-launch
         # path's), ZL_ATTN_LA_HALF = 1 half-precision split records
         la, la_mode = None, env("ZL_ATTN_LA", _ATTN_LA_DEFAULT)
-        if mfma_attn and not ctx.kv_quant and attend_rows is None and (la_mode == "1" or (la_mode == "auto" and merge_plan is None)):
+        if mfma_attn and not ctx.kv_quant and attend_rows is None and sh is None and (la_mode == "1" or (la_mode == "auto" and merge_plan is None)):
             la_split = int(env("ZL_ATTN_LA_SPLIT", "0") or 0)
             eff = la_split or ops.decode_attn_la_split_len(b, c.num_kv_heads, ctx.max_len_buf)
             if (ctx.max_len_buf + eff - 1) // eff <= 64:
@@ -1472,7 +1594,7 @@ class LLaMA:
         # register-resident norm prologue below.  ZL_ROW_SS=0 off; ZL_ROW_SS_MIN_M: rows it starts at
         # (not with MoE layers: their feed-forward has no w_out to produce the statistics nor a gate|up projection to consume them)
         stats = None
-        if (qkv == "w4" and (la is not None or attend_rows is not None) and not self.tp and not self.moe
+        if (qkv == "w4" and (la is not None or attend_rows is not None or sh is not None) and not self.tp and not self.moe
                 and env("ZL_ROW_SS", "1") != "0" and int(env("ZL_ROW_SS_MIN_M", "8")) <= b <= 32 and c.dim_model % 1024 == 0
                 and all(l.attn_out.perm is None and l.w_out.perm is None and l.w_in_gated.perm is None for l in self.layers)
                 and ops.w4_row_ss_routes(b, [first.attn_out.weight, first.w_out.weight],
@@ -1491,7 +1613,9 @@ class LLaMA:
             raise ops.ZLError("skip_gemv: the fused W4 decode route with the merging attn_out projection only")
         if qkv == "w4":                                   # 9..32 rows without the statistics: a launch of its own, or the deferred norm (ZL_DEFER_NORM)
             norm = "row_ss" if stats is not None else "fused" if b <= max(8, _fused_norm_rows(first.qkv.weight)) else "launch"
-        if ctx.kv_quant or attend_rows is not None:
+        if sh is not None:
+            attn = "shared"
+        elif ctx.kv_quant or attend_rows is not None:
             attn = "quant" if ctx.kv_quant else "hook"
         elif la is not None or merge_plan is not None:
             attn = "la" if la is not None else "splits"
@@ -1570,6 +1694,11 @@ class LLaMA:
         k, v, shape = ctx.k_addrs[li], ctx.v_addrs[li], (bufs["q"].shape[0], 1, c.num_heads, c.dim_head)
         if r.attn == "hook":
             r.hook(li, bufs["q"], bufs["attn"], r.workspace)
+        elif r.attn == "shared":
+            sh = ctx.shared
+            ops.decode_attention_shared(bufs["q"].view(shape), ctx.buf_lens, k, v, ctx.valid_lens, sh.prefix_of, sh.prefix_lens, sh.prefix_caps,
+                                        sh.k_addrs[li], sh.v_addrs[li], r.scale, sh.rows, ctx.max_len_buf, c.num_kv_heads,
+                                        out=bufs["attn"].view(shape), workspace=r.workspace)
         elif r.attn == "la":
             ops.decode_attention_la(bufs["q"].view(shape), ctx.buf_lens, k, v, ctx.valid_lens, r.scale, ctx.max_len_buf, c.num_kv_heads,
                                     r.la[0], out=bufs["attn"].view(shape), split_len=r.la[1], half=r.la[2])
@@ -1717,11 +1846,16 @@ class LLaMA:
             raise ops.ZLError("kv_history='cache' on an INT8 KV cache needs head size 128")
         return bool(ctx.kv_quant and kv_history == "cache")
 
-    def _check_prompt_piece(self, what, ctx: DynBatchContext, task, s, pos0, history_readable):
-        """the checks of one task's piece (s rows at pos0), before any launch: it fits the task's buffers, and a continued piece
-        into an INT8 cache has something to read its history from -- the prompt's temporaries or kv_history="cache"."""
+    def _check_prompt_piece(self, what, ctx: DynBatchContext, task, s, pos0, history_readable, behind_prefix=False):
+        """the checks of one task's piece (s rows at pos0), before any launch: it fits the task's buffers, a continued piece
+        into an INT8 cache has something to read its history from -- the prompt's temporaries or kv_history="cache" --, and a
+        continued piece does not go to a slot that reads a shared prefix (its own buffer holds nothing below the prefix's length;
+        behind_prefix: admit(prefixes=), whose attention reads the prefix buffer)."""
         if s < 1 or pos0 < 0 or pos0 + s + 1 > ctx.max_len_buf:
             raise ops.ZLError(f"{what}: prompt of task {task} ({s} tokens at {pos0}) does not fit the task's KV buffer")
+        if pos0 > 0 and not behind_prefix and ctx.shared is not None and 0 <= task < len(ctx.shared.of_host) and ctx.shared.of_host[task] != -1:
+            raise ops.ZLError(f"{what}: task {task} reads a shared prefix: a continued prompt piece would attend over own rows that were "
+                              "never written (admit(prefixes=) encodes a prompt behind a prefix)")
         if ctx.kv_quant and pos0 != 0 and not history_readable:
             # a later piece without the prompt's temporary unquantised buffers (prefill(chunk=...) keeps them): the reference
             # falls back to de-quantising the cache there ("WARNING: de-quantize prompt kv cache!", attention.cpp:511-516)
@@ -1827,7 +1961,7 @@ class LLaMA:
         tasks, pos0, q8_history = self._check_prompt_batch("prefill_batch", ctx, tasks, prompts, pos0, kv_history)
         return self._prompt_tail(ctx, *self._prefill_rows(ctx, tasks, prompts, pos0, q8_history))
 
-    def _check_prompt_batch(self, what, ctx: DynBatchContext, tasks, prompts, pos0, kv_history):
+    def _check_prompt_batch(self, what, ctx: DynBatchContext, tasks, prompts, pos0, kv_history, behind_prefix=False):
         """the argument checks of prefill_batch / score, before any launch -> (tasks, pos0 as int lists, q8_history)"""
         q8_history = self._check_kv_history(ctx, kv_history)
         tasks = [int(t) for t in tasks]
@@ -1838,7 +1972,7 @@ class LLaMA:
         if len(set(tasks)) != n or any(t < 0 or t >= ctx.tokens.numel() for t in tasks):
             raise ops.ZLError(f"{what}: tasks must be distinct indices of the batch")
         for t, pr, p0 in zip(tasks, prompts, pos0):
-            self._check_prompt_piece(what, ctx, t, int(pr.numel()), p0, q8_history)
+            self._check_prompt_piece(what, ctx, t, int(pr.numel()), p0, q8_history, behind_prefix)
         return tasks, pos0, q8_history
 
     def new_prefix_cache(self, ctx: DynBatchContext, num_blocks, block_size=128, max_prefix=4096):
@@ -1952,7 +2086,7 @@ class LLaMA:
             sums, matches = d[0].float(), d[1] == 0
         return ScoreResult(r.logprob, r.lse, r.greedy, r.greedy_logit, cu, sums, matches, None)
 
-    def _prefill_rows(self, ctx: DynBatchContext, tasks, prompts, pos0s, q8_history=False, labels=None):
+    def _prefill_rows(self, ctx: DynBatchContext, tasks, prompts, pos0s, q8_history=False, labels=None, prefixes=None):
         """The layer loop of prompt encode over the rows of the call's tasks (checked by the callers) -> (_PromptRows, hidden rows
         before the output norm).  Sequence: separate RMSNorm, W4A16 GEMM (M = rows: the M-tiled MFMA kernel, the arithmetic of
         the reference's M > 40 dequant + GEMM branch) -- every linear over the summed rows --, rope_qk_cache, then the K/V scatter
@@ -1961,7 +2095,7 @@ class LLaMA:
         (ops.prefill_attention_varlen_q8), for one task or several; no unquantised copy of earlier rows is used.
         labels (LLaMA.score: one host label per row) are uploaded with the call's tables for _score_rows."""
         c = self.cfg
-        r = _PromptRows.of(self, ctx, tasks, prompts, pos0s, q8_history, labels)
+        r = _PromptRows.of(self, ctx, tasks, prompts, pos0s, q8_history, labels, prefixes)
         total = r.cu[-1]
         hidden = ops.embedding(r.tokens, self.token_embedding, c.scale_emb)
         cos, sin = self._rope_tables(r.pos)
@@ -1985,6 +2119,8 @@ class LLaMA:
           "temp"   the chunked prompt's temporaries, which this piece's rows have just joined (attention.cpp:497-510);
           "q8"     the INT8 cache below pos0, dequantised where the kernel stages it, and k3 / v3 from there on: a quantised buffer
                    and no prompt temporaries (attention.cpp:510-516).
+          "hist"   the task's shared prefix buffer below pos0 and k3 / v3 from there on (admit(prefixes=): the own buffer holds nothing
+                   below pos0).
         Head size 128: the MFMA kernels -- the one-task launch on the task's tensors, or one varlen launch over the tables of
         several tasks; other head sizes: per task the mask form of multi_query_attention_rag_buffer."""
         c = self.cfg
@@ -1999,6 +2135,9 @@ class LLaMA:
             if r.route == "temp":
                 ops.copy_to_rag_buffer2(r.placement, r.len_bufs_dev, k4, v4, r.k_tab[li], r.v_tab[li])
         if d == 128:
+            if r.route == "hist":
+                return ops.prefill_attention_varlen_hist(q3, r.lens, r.att_pos0s, k3, v3, r.k_tab[li], r.v_tab[li], r.hist_lens, r.len_bufs,
+                                                         hkv, scale, plan=r.plan, hist_lens_dev=r.hist_lens_dev)
             if r.route == "q8":
                 return ops.prefill_attention_varlen_q8(q3, r.lens, r.att_pos0s, k3, v3, r.k_tab[li], r.v_tab[li], r.ks_tab[li],
                                                        r.vs_tab[li], r.len_bufs, hkv, scale, plan=r.plan)
@@ -2039,6 +2178,10 @@ class LLaMA:
         for t, end in zip(r.tasks, r.ends):
             ctx.slot_guard.pop(t, None)
             ctx.slot_room[t] = (ctx.max_len_buf - end, ctx.steps_left)
+        if ctx.shared is not None:                        # a task whose own rows start at 0 reads no prefix (a piece behind one: admit(prefixes=))
+            stale = [t for t, end, s in zip(r.tasks, r.ends, r.lens) if end == s and ctx.shared.of_host[t] != -1]
+            if stale:
+                self._set_prefix_of(ctx, stale, [-1] * len(stale))
         return logits
 
     def _prompt_logits_and_pick(self, last_hidden, picks):
@@ -2147,6 +2290,8 @@ class LLaMA:
             raise ops.ZLError("verify: not on the INT8 KV cache")
         if self.tp:
             raise ops.ZLError("verify: not under tensor parallelism")
+        if ctx.shared is not None:
+            raise ops.ZLError("verify: speculative rows over shared prefixes are not supported")
         if c.dim_head != 128:
             raise ops.ZLError("verify: head size 128 only (the matrix-core decode attention)")
         if attn not in ("auto", "causal", "rows"):
@@ -2711,7 +2856,7 @@ class LLaMA:
         ctx.slot_room.update({t: (v, ctx.steps_left) for t, v in left.items()})
 
     def admit(self, ctx: DynBatchContext, slots, prompts, requests, sampler: SamplerState, stop: Optional[StopState] = None,
-              lookup: Optional[LookupState] = None, cache=None, kv_history=None):
+              lookup: Optional[LookupState] = None, cache=None, kv_history=None, prefixes=None):
         """Put new requests into slots of a running batch, in place (the reference's scheduler moving a task into max_batch_active,
         src/generator/batch_generator.cpp, where SearcherImplV1 builds the task's state on the host).  In order: prefill_batch(ctx,
         slots, prompts) -- prefill_cached when a prefix cache is given --; ONE upload and ONE launch (ops.slots_pack / slots_admit)
@@ -2734,9 +2879,22 @@ class LLaMA:
         the grammar too, so the prompt is encoded WITHOUT its last token, which becomes the slot's pending token in the prompt pick's
         place; the first step then draws the first token under sampler and grammar.  Such a slot's prompt counts as len - 1 for the
         length limit and the guard, the returned logits row is that of prompt[:-1], the default history is prompt[:-1] (the pending
-        token enters it through the drafter's append, which makes it the full prompt), and a 1-token prompt is refused."""
+        token enters it through the drafter's append, which makes it the full prompt), and a 1-token prompt is refused.
+        prefixes (a context with shared prefixes, LLaMA.new_shared_prefixes): per slot a loaded prefix index g, or None.  prompts[j] is
+        then the part BEHIND prefix g: its rows sit at positions P + i (P = the prefix's length), go into the slot's own buffer at
+        those rows and attend to the prefix buffer and to themselves (ops.prefill_attention_varlen_hist); the slot's prefix_of
+        becomes g, and the guard and the length limit count P + len.  No K/V row of the prefix is copied.  Not with cache= nor with
+        a drafter.  Every slot this call admits WITHOUT a prefix has its prefix_of reset to -1."""
         b = self._slot_states("admit", ctx, sampler, stop, lookup)
         prompts = list(prompts)
+        offsets = None
+        if prefixes is not None:
+            sh, prefixes = ctx.shared, [None if g is None else int(g) for g in prefixes]
+            if sh is None or cache is not None or lookup is not None or len(prefixes) != len(prompts):
+                raise ops.ZLError("admit: prefixes= needs a context with shared prefixes and one entry per slot; not with cache= nor a drafter")
+            if any(g is not None and (not 0 <= g < len(sh.kv) or sh.lens_host[g] < 1) for g in prefixes):
+                raise ops.ZLError("admit: prefixes= names loaded prefixes of the context (LLaMA.load_prefix)")
+            offsets = [0 if g is None else sh.lens_host[g] for g in prefixes]
         requests = [dict(rq or {}) for rq in requests]
         for j, rq in enumerate(requests if len(requests) == len(prompts) else []):      # a count that is off is refused below
             if rq.get("grammar") is not None:
@@ -2745,13 +2903,18 @@ class LLaMA:
                 if pr.numel() < 2:
                     raise ops.ZLError("admit: a request with a grammar needs a prompt of 2 tokens at least (the last one is re-fed)")
                 prompts[j], rq["grammar"] = pr[:-1], (g, int(pr[-1]))
-        slots, _, _ = self._check_prompt_batch("admit", ctx, slots, prompts, None, kv_history)
+        slots, _, _ = self._check_prompt_batch("admit", ctx, slots, prompts, offsets, kv_history, behind_prefix=offsets is not None)
         if len(requests) != len(slots):
             raise ops.ZLError("admit: one request per slot")
-        entries, guards = self._slot_entries("admit", ctx, slots, prompts, requests, stop, lookup)
+        entries, guards = self._slot_entries("admit", ctx, slots, prompts, requests, stop, lookup, offsets)
         blob, _ = ops.slots_pack(entries, self.cfg.vocab_size, self.slot_widths(sampler, stop, lookup))
         before = ctx.steps_left
-        if cache is None:
+        if offsets is not None:
+            out = self._prompt_tail(ctx, *self._prefill_rows(ctx, slots, prompts, offsets, prefixes=prefixes))
+            named = [(s, g) for s, g in zip(slots, prefixes) if g is not None]
+            if named:
+                self._set_prefix_of(ctx, [s for s, _ in named], [g for _, g in named])
+        elif cache is None:
             out = self.prefill_batch(ctx, slots, prompts, kv_history=kv_history)
         else:
             out = self.prefill_cached(ctx, cache, slots, prompts, kv_history=kv_history)
@@ -2770,14 +2933,14 @@ class LLaMA:
             raise ops.ZLError(f"{what}: grammar names no loaded automaton of this sampler")
         return int(g)
 
-    def _slot_entries(self, what, ctx, slots, prompts, requests, stop, lookup):
-        """the per-slot half of an admission, host only: prompts[j] = the tokens the prompt encode sees for slots[j]; with a stop state
-        the request's length limit is clamped and the slot's guard computed, with a drafter the history defaults to those tokens
-        -> (slots_pack's entries, {slot: guard})"""
+    def _slot_entries(self, what, ctx, slots, prompts, requests, stop, lookup, offsets=None):
+        """the per-slot half of an admission, host only: prompts[j] = the tokens the prompt encode sees for slots[j] (behind offsets[j]
+        rows of a shared prefix, which count for the limit and the guard); with a stop state the request's length limit is clamped and
+        the slot's guard computed, with a drafter the history defaults to those tokens -> (slots_pack's entries, {slot: guard})"""
         k = lookup.k if lookup is not None else 0
         entries, guards = [], {}
-        for s, pr, rq in zip(slots, prompts, requests):
-            n = int(pr.numel())
+        for j, (s, pr, rq) in enumerate(zip(slots, prompts, requests)):
+            n = int(pr.numel()) + (offsets[j] if offsets is not None else 0)
             if stop is not None:
                 raw = rq.get("max_new_tokens", 0)
                 if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or not 0 <= int(raw) < 1 << 31:
@@ -2806,7 +2969,7 @@ class LLaMA:
         return desc
 
     def admit_samples(self, ctx: DynBatchContext, groups, sampler: SamplerState, stop: Optional[StopState] = None,
-                      lookup: Optional[LookupState] = None, cache=None, kv_history=None):
+                      lookup: Optional[LookupState] = None, cache=None, kv_history=None, share=None):
         """Admit several samples of one prompt for ONE prompt encode (the reference's num_results: batch_generator.cpp gives a task's
         first step num_results rows and copies its buffers per result on the host): groups = [(slots, prompt, requests)], slots[0] the
         group's source, requests[j] the request of slots[j] (dicts over ops.SLOT_REQUEST_KEYS, None = the defaults).  In order:
@@ -2822,7 +2985,11 @@ class LLaMA:
         length limit and the guard (every slot of a group gets the guard its source would get), the default history is prompt[:-1],
         a request's grammar handle travels as (start, prompt[-1]), and the result is the prompt encode's: the logits row of
         prompt[:-1] per GROUP (with a cache: (logits, matched)).  Every other slot's rows are untouched and no tensor is reallocated.
-        Refused before any launch, with nothing changed: everything admit refuses, and a slot that occurs twice across the groups."""
+        Refused before any launch, with nothing changed: everything admit refuses, and a slot that occurs twice across the groups.
+        share (a context with shared prefixes): one prefix index per group.  prompt[:-1] is then encoded into THAT prefix buffer
+        instead of a source slot and no K/V row is copied: the group's slots get prefix_of = g, position = placement = P = len - 1,
+        valid length P + 1 and prompt[-1] pending, and read the prefix in place from the first step on.  The buffer must hold P rows
+        and be read by no slot outside the call's own; not with cache= nor a drafter."""
         self._slot_states("admit_samples", ctx, sampler, stop, lookup)
         what = "admit_samples"
         gs = []
@@ -2849,6 +3016,8 @@ class LLaMA:
         entries, guards = self._slot_entries(what, ctx, flat, heads, [rq for _, _, rqs in gs for rq in rqs], stop, lookup)
         blob, _ = ops.slots_pack(entries, self.cfg.vocab_size, self.slot_widths(sampler, stop, lookup))
         b = ctx.tokens.numel()
+        if share is not None:
+            return self._admit_shared_samples(ctx, gs, share, cache, blob, guards, sampler, stop, lookup)
         lens = [ctx.max_len_buf] * b
         desc, _ = ops.kv_fork_check(self.fork_descriptors([(slots, pr) for slots, pr, _ in gs]), lens, b, self.cfg.vocab_size)
         before = ctx.steps_left
@@ -2865,6 +3034,53 @@ class LLaMA:
             for d in slots[1:]:
                 ctx.slot_guard.pop(d, None)
                 ctx.slot_room[d] = ctx.slot_room[slots[0]]
+        if ctx.shared is not None:                                            # a copy reads no prefix (the sources: _prompt_tail)
+            stale = [d for slots, _, _ in gs for d in slots[1:] if ctx.shared.of_host[d] != -1]
+            if stale:
+                self._set_prefix_of(ctx, stale, [-1] * len(stale))
+        self._slots_launch(ctx, blob, sampler, stop, lookup)
+        if guards:
+            ctx.slot_guard.update(guards)
+            self._steps_left_after_admission(ctx, before)
+        return out
+
+    def _admit_shared_samples(self, ctx, gs, share, cache, blob, guards, sampler, stop, lookup):
+        """admit_samples(share=) behind its checks of the groups: the prefixes' own checks, the prompt encode into the prefix buffers,
+        the slots' rows of the context, the admission launch"""
+        what, sh = "admit_samples", ctx.shared
+        try:
+            share = [int(g) for g in share]
+        except (TypeError, ValueError):
+            raise ops.ZLError(f"{what}: share is one prefix index per group") from None
+        if sh is None or cache is not None or lookup is not None or len(share) != len(gs):
+            raise ops.ZLError(f"{what}: share= needs a context with shared prefixes and one prefix per group; not with cache= nor a drafter")
+        mine = {s for slots, _, _ in gs for s in slots}
+        if len(set(share)) != len(share) or any(not 0 <= g < len(sh.kv) for g in share):
+            raise ops.ZLError(f"{what}: share: distinct prefix indices below {len(sh.kv)}")
+        for g, (_, pr, _) in zip(share, gs):
+            if pr.numel() - 1 > sh.rows:
+                raise ops.ZLError(f"{what}: a prompt of {pr.numel()} tokens does not fit a prefix buffer of {sh.rows} rows")
+            if any(s not in mine for s in sh.users(g)):
+                raise ops.ZLError(f"{what}: prefix {g} is read by slots outside this call")
+        before = ctx.steps_left
+        old = [s for s in mine if sh.of_host[s] != -1]
+        if old:                                                               # the call's own slots let go of what they read
+            self._set_prefix_of(ctx, old, [-1] * len(old))
+        out = self._load_prefixes(what, ctx, share, [pr[:-1] for _, pr, _ in gs])
+        slots = [s for ss, _, _ in gs for s in ss]
+        ps = [int(pr.numel()) - 1 for ss, pr, _ in gs for _ in ss]
+        rows = torch.tensor(slots + ps + [p + 1 for p in ps] + [int(pr[-1]) for ss, pr, _ in gs for _ in ss], dtype=torch.int64).to(self.device)
+        n = len(slots)
+        idx, pos, valid, tok = rows[:n], rows[n:2 * n].to(torch.int32), rows[2 * n:3 * n].to(torch.int32), rows[3 * n:].to(torch.int32)
+        ctx.tokens.index_copy_(0, idx, tok)
+        ctx.positions.index_copy_(0, idx, pos)
+        ctx.placement.index_copy_(0, idx, pos)
+        ctx.valid_lens.index_copy_(0, idx, valid)
+        self._set_prefix_of(ctx, slots, [g for g, (ss, _, _) in zip(share, gs) for _ in ss])
+        ctx.steps_left = min(ctx.steps_left, ctx.max_len_buf - max(ps))
+        for s, p in zip(slots, ps):
+            ctx.slot_guard.pop(s, None)
+            ctx.slot_room[s] = (ctx.max_len_buf - p, ctx.steps_left)
         self._slots_launch(ctx, blob, sampler, stop, lookup)
         if guards:
             ctx.slot_guard.update(guards)
@@ -2887,6 +3103,10 @@ class LLaMA:
             raise ops.ZLError("park: only a slot known to be finished is parked (finished = the host copy of stop.finished)")
         blob, _ = ops.slots_pack([(s, None) for s in slots], self.cfg.vocab_size, self.slot_widths(sampler, stop, lookup))
         self._slots_launch(ctx, blob, sampler, stop, lookup, parked_ok=set(slots))
+        if ctx.shared is not None:                            # a parked slot attends over row 0 of its OWN buffer
+            stale = [s for s in slots if ctx.shared.of_host[s] != -1]
+            if stale:
+                self._set_prefix_of(ctx, stale, [-1] * len(stale))
         before = ctx.steps_left
         ctx.slot_guard.update({s: 0 for s in slots})
         self._steps_left_after_admission(ctx, before)

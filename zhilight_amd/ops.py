@@ -2252,6 +2252,67 @@ def decode_attention_causal(batch_q, buf_lens, k_addrs, v_addrs, valid_lens, sca
     return out
 
 
+def decode_attn_shared_workspace_bytes(b, g, h, num_kv_heads, d, max_prefix_len, max_len_buf):
+    """bytes of split records decode_attention_shared needs (zl_decode_attn_shared_workspace_bytes)"""
+    nbytes = int(lib().zl_decode_attn_shared_workspace_bytes(_i(b), _i(g), _i(h), _i(num_kv_heads), _i(d), _i(max_prefix_len), _i(max_len_buf)))
+    if nbytes < 0:
+        check(nbytes, "decode_attn_shared_workspace_bytes")
+    return nbytes
+
+
+def decode_attn_shared_workspace(b, g, h, num_kv_heads, d, max_prefix_len, max_len_buf, device):
+    return torch.empty(decode_attn_shared_workspace_bytes(b, g, h, num_kv_heads, d, max_prefix_len, max_len_buf) // 4, dtype=torch.float32,
+                       device=device)
+
+
+def decode_attention_shared(batch_q, buf_lens, k_addrs, v_addrs, valid_lens, prefix_of, prefix_lens, prefix_caps, prefix_k_addrs,
+                            prefix_v_addrs, scale, max_prefix_len, max_len_buf, num_kv_heads, bshd=True, out=None, workspace=None,
+                            shared_split_len=0, own_split_len=0):
+    """Two-segment decode attention (zl_decode_attn_shared): batch_q (B, 1, H, 128) or (B, H, 128); task b's first
+    P = min(prefix_lens[g], prefix_caps[g], valid_lens[b], buf_lens[b]) keys are rows of prefix buffer g = prefix_of[b] (P = 0 for a g
+    outside [0, G)), its keys [P, valid) rows of its own buffer.  prefix_k_addrs / prefix_v_addrs: pointer tables of the G prefix buffers
+    (make_ptr_table), each prefix_caps[g] rows in the own buffers' layout; prefix_caps[g] <= max_prefix_len is the caller's to keep.
+    workspace: decode_attn_shared_workspace(...).  Split lengths: multiples of 32 from 128 on, 0 = the launcher's.  Returns out, shaped
+    like batch_q."""
+    what = "decode_attention_shared"
+    _chk_cuda(batch_q, buf_lens, k_addrs, v_addrs, valid_lens, prefix_of, prefix_lens, prefix_caps, prefix_k_addrs, prefix_v_addrs, out,
+              workspace)
+    if batch_q.dim() not in (3, 4) or (batch_q.dim() == 4 and batch_q.shape[1] != 1) or not batch_q.is_contiguous():
+        raise ZLError(f"{what}: batch_q is a contiguous (B, 1, H, D) or (B, H, D): one query row per task")
+    b, h, d = batch_q.shape[0], batch_q.shape[-2], batch_q.shape[-1]
+    dt = _dt(batch_q)
+    if batch_q.dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError(f"{what}: fp16 or bf16 queries")
+    if d != 128 or num_kv_heads < 1 or h % num_kv_heads or h // num_kv_heads > 16:
+        raise ZLError(f"{what}: head size 128, H a multiple of the kv heads, at most 16 query heads per kv head")
+    g = int(prefix_lens.numel())
+    if b < 1 or g < 1 or int(max_prefix_len) < 1 or int(max_len_buf) < 1:
+        raise ZLError(f"{what}: at least one task, one prefix buffer and one row on either side")
+    for t, dty, n, name in ((buf_lens, torch.int32, b, "buf_lens"), (valid_lens, torch.int32, b, "valid_lens"),
+                            (prefix_of, torch.int32, b, "prefix_of"), (k_addrs, torch.int64, b, "k_addrs"), (v_addrs, torch.int64, b, "v_addrs"),
+                            (prefix_lens, torch.int32, g, "prefix_lens"), (prefix_caps, torch.int32, g, "prefix_caps"),
+                            (prefix_k_addrs, torch.int64, g, "prefix_k_addrs"), (prefix_v_addrs, torch.int64, g, "prefix_v_addrs")):
+        if t.dtype != dty or t.numel() != n or t.device != batch_q.device or not t.is_contiguous():
+            raise ZLError(f"{what}: {name}: {n} contiguous entries of {dty} on the queries' device")
+    for sl in (shared_split_len, own_split_len):
+        if sl and (sl < 128 or sl % 32):
+            raise ZLError(f"{what}: a split length is a multiple of 32, at least 128 (0: the launcher's)")
+    if out is None:
+        out = torch.empty_like(batch_q)
+    else:
+        _chk_out(out, b, h * d, batch_q.dtype, batch_q.device, what)
+    need = decode_attn_shared_workspace_bytes(b, g, h, num_kv_heads, d, max_prefix_len, max_len_buf)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=batch_q.device)
+    elif workspace.device != batch_q.device or workspace.numel() * workspace.element_size() < need:
+        raise ZLError(f"{what}: workspace too small / wrong device")
+    check(lib().zl_decode_attn_shared_ex(_p(batch_q), _p(buf_lens), _p(k_addrs), _p(v_addrs), _p(valid_lens), _p(prefix_of), _p(prefix_lens),
+                                         _p(prefix_caps), _p(prefix_k_addrs), _p(prefix_v_addrs), _p(out), _p(workspace), _i(b), _i(g), _i(h),
+                                         _i(num_kv_heads), _i(d), _f(scale), _i(max_prefix_len), _i(max_len_buf), C.c_int(int(bshd)),
+                                         C.c_int(dt), _i(shared_split_len), _i(own_split_len), _stream()), "decode_attn_shared")
+    return out
+
+
 def decode_attn_la_split_len(b, num_kv_heads, max_len_buf):
     """keys per split zl_decode_attn_la picks for this batch geometry (a multiple of 32)"""
     return int(lib().zl_decode_attn_la_split_len(_i(b), _i(num_kv_heads), _i(max_len_buf)))
@@ -2679,6 +2740,45 @@ def prefill_attention_varlen_q8(q, lens, pos0, k_new, v_new, k_addrs, v_addrs, k
                                           _p(v_tab), _p(ks_tab), _p(vs_tab), _p(k_new), _p(v_new), _p(out), _p(plan.work),
                                           _i(plan.n_work), _i(plan.b), _i(total_q), _i(h), _i(num_kv_heads), _i(d), _f(scale),
                                           C.c_int(_dt(q)), C.c_int(groups), _stream()), "prefill_attn_varlen_q8")
+    return out
+
+
+def prefill_attention_varlen_hist(q, lens, pos0, k_new, v_new, hist_k_addrs, hist_v_addrs, hist_lens, buf_lens, num_kv_heads, scale,
+                                  out=None, groups=None, plan=None, hist_lens_dev=None):
+    """prefill_attention_varlen for chunks that continue rows held in ANOTHER, unquantised buffer (a prompt encoded on top of a shared
+    prefix): key row j of task i is row j of its history buffer for j < pos0[i] and row j - pos0[i] of its k_new / v_new slice from
+    there on -- bit-identical to prefill_attention_varlen on buffers that hold both.  q (total_q, H, 128), k_new / v_new (total_q, Hkv,
+    128); hist_k_addrs / hist_v_addrs: device int64 tables of the tasks' history buffers ((hist_lens[i], Hkv, 128), BSHD; 0 for a task
+    with pos0 = 0); hist_lens: host ints, pos0[i] <= hist_lens[i] (checked here).  lens / pos0 / buf_lens / plan as for
+    prefill_attention_varlen (buf_lens[i]: the keys a task may see at most, pos0[i] + lens[i] <= buf_lens[i]).  hist_lens_dev: the
+    caller's int32 device copy of hist_lens (several layers share it), made here otherwise."""
+    what = "prefill_attention_varlen_hist"
+    _chk_cuda(q, k_new, v_new, hist_k_addrs, hist_v_addrs)
+    if q.dim() != 3 or k_new.dim() != 3:
+        raise ZLError(f"{what}: q (total_q, H, D), k_new / v_new (total_q, Hkv, D)")
+    total_q, h, d = q.shape
+    if d != 128:
+        raise ZLError(f"{what}: head size {d}: only 128")
+    plan, out, groups = _varlen_args(what, q, lens, pos0, buf_lens, plan, out, groups)
+    if num_kv_heads < 1 or h % num_kv_heads:
+        raise ZLError(f"{what}: H must be a multiple of Hkv")
+    for t in (k_new, v_new):
+        if tuple(t.shape) != (total_q, num_kv_heads, d) or t.dtype != q.dtype or t.device != q.device:
+            raise ZLError(f"{what}: k_new / v_new: (total_q, Hkv, D) rows of q's dtype on q's device")
+    for t in (hist_k_addrs, hist_v_addrs):
+        if t.dtype != torch.int64 or t.numel() != plan.b or t.device != q.device:
+            raise ZLError(f"{what}: one int64 history pointer per task, on q's device")
+    hl = [int(x) for x in hist_lens]
+    if len(hl) != plan.b or any(p0 > n for p0, n in zip(plan.pos0, hl)):
+        raise ZLError(f"{what}: one history length per task, none below the task's pos0")
+    if hist_lens_dev is None:
+        hist_lens_dev = torch.tensor(hl, dtype=torch.int32).to(q.device)
+    elif hist_lens_dev.dtype != torch.int32 or hist_lens_dev.numel() != plan.b or hist_lens_dev.device != q.device:
+        raise ZLError(f"{what}: hist_lens_dev: one int32 per task on q's device")
+    check(lib().zl_prefill_attn_varlen_hist(_p(q), _p(plan.cu_seqlens_q), _p(plan.pos0_dev), _p(plan.buf_lens_dev), _p(hist_k_addrs),
+                                            _p(hist_v_addrs), _p(hist_lens_dev), _p(k_new), _p(v_new), _p(out), _p(plan.work),
+                                            _i(plan.n_work), _i(plan.b), _i(total_q), _i(h), _i(num_kv_heads), _i(d), _f(scale),
+                                            C.c_int(_dt(q)), C.c_int(groups), _stream()), "prefill_attn_varlen_hist")
     return out
 
 
