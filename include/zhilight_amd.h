@@ -889,6 +889,7 @@ int zl_embedding_rope(const int32_t* ids, const uint16_t* weight, uint16_t* out,
  * quant_scale_back, quant_back_act_mul (src/nn/quant/int8/quant_kernel.h:15-128; kernels
  * quant_kernel.cu:15-47, 106-151, 231-246, 589-614) and the cuBLASLt IMMA call of
  * Int8Linear::forward (src/nn/linear/linear.cpp:557-635).  Integer results are bit-exact.
+ * A row of zeros (both quantisers): codes 0, scale 0 (the reference divides by zero).
  * ---------------------------------------------------------------------------------------------- */
 int zl_quant_calc_scale(const uint16_t* x, int8_t* q, float* scale, int64_t m, int64_t k, int dtype,
                         zl_stream_t s);

@@ -994,7 +994,7 @@ void zlo_quant_calc_scale(const uint16_t* x, int8_t* q, float* scale, int64_t m,
             float v = fabsf(T2f(x[r * k + i], dtype));
             amax = v > amax ? v : amax;
         }
-        float bs = 127.f / amax;
+        float bs = amax > 0.f ? 127.f / amax : 0.f; /* a zero row: codes 0, scale 0 (the reference divides by 0) */
         for (int64_t i = 0; i < k; ++i) q[r * k + i] = (int8_t)nearbyintf(T2f(x[r * k + i], dtype) * bs);
         scale[r] = amax / 127.f;
     }
@@ -1026,7 +1026,7 @@ void zlo_rmsnorm_quant(const uint16_t* x, const uint16_t* w, uint16_t* out, int8
         float ss = block_tree_sum(part, threads);
         float rs = 1.0f / sqrtf(ss / (float)dim + eps);
         amax = T2f(f2T(amax, dtype), dtype);
-        float bs = (float)(127.0 / (double)amax);
+        float bs = amax > 0.f ? (float)(127.0 / (double)amax) : 0.f; /* a zero row: codes 0, scale 0 (the reference divides by 0) */
         for (int64_t i = 0; i < dim; ++i) {
             float v = vw[i] / scale;
             out[r * dim + i] = f2T(v * rs, dtype);

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void k_quant_rows(const uint16_t* __restrict__
         for (int i = threadIdx.x; i < k; i += 256) amax = fmaxf(amax, fabsf(ZT<DT>::to_f32(x[off + i])));
     }
     amax = zl_block_max(amax, red);
-    const float bs = 127.f / amax;
+    const float bs = amax > 0.f ? 127.f / amax : 0.f;   // a row of zeros: codes 0, scale 0 (the reference divides by zero)
     if constexpr (VEC) {
         for (int i = threadIdx.x * 8; i < k; i += 256 * 8) {
             const uint4 v = *reinterpret_cast<const uint4*>(x + off + i);   // L1/L2 hit
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void k_rmsnorm_quant(const uint16_t* __restric
     const float rs = zl_rsqrt_rn(ss / (float)dim + eps);
     amax = zl_block_max(amax, red);
     amax = ZT<DT>::to_f32(ZT<DT>::from_f32(amax));             // the reference reduces the max in T
-    const float bs = (float)(127.0 / (double)amax);
+    const float bs = amax > 0.f ? (float)(127.0 / (double)amax) : 0.f;   // a row of zeros: codes 0, scale 0 (the reference divides by zero)
     if constexpr (VEC) {
         for (int i = threadIdx.x * 8; i < dim; i += 256 * 8) {
             uint32_t o16[4] = {0, 0, 0, 0}, o8[2] = {0, 0};
