@@ -329,6 +329,38 @@ int zl_gemm_nt_packed(const uint16_t* x, int64_t ldx, const uint16_t* wp, const 
 int zl_gemm_nt_f32(const uint16_t* x, int64_t ldx, const uint16_t* w /* (N,K) */, float* y, int64_t m, int64_t n, int64_t k, float alpha,
                    int dtype, zl_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------
+ * MXFP4  Weight-only linears on OCP Microscaling FP4 weights (no counterpart in the reference: quant type 11 of this project).
+ * THE FORMAT.  A weight W (N, K), K % 32 == 0, is two byte tensors:
+ *   codes  uint8 (N, K/2)   byte j of row n holds element 2j in bits 0-3 and element 2j + 1 in bits 4-7
+ *   scales uint8 (N, K/32)  E8M0: one power of two per 32 consecutive elements of a row
+ *   value(c) = (-1)^(c >> 3) * {0, 0.5, 1, 1.5, 2, 3, 4, 6}[c & 7]   (E2M1; code 8, "-0", is 0)
+ *   W[n, k]  = value(code[n, k]) * 2^(scales[n, k / 32] - 127)
+ * Scale byte 255 is the format's NaN: loaders refuse a tensor that holds one, the kernels do not define it.
+ * The kernels read this layout as it is (a block is 16 contiguous bytes = one 16-byte load): there is no packed copy, a weight
+ * costs 0.53125 B.  codes must be 16-byte aligned.
+ *
+ * zl_mxfp4_linear: y = T(x . W^T [+ bias]) for T = fp16 / bf16 (dtype), x (M, K) with row stride ldx (% 8 == 0, 16-byte aligned),
+ * y (M, N) -- (M, N / 2) under ZL_EPI_SILU_MUL.  Epilogues: ZL_EPI_BIAS, ZL_EPI_RESIDUAL, ZL_EPI_SILU_MUL with exactly the
+ * arithmetic stated for zl_w4a16_gemm above, "half" read as T; SILU_MUL wants the row-interleaved [gate; up] matrix (row 2j gate,
+ * row 2j + 1 up; a bias is indexed by those stored rows) and excludes RESIDUAL.  residual may alias y.
+ * NUMERICS: no weight is ever rounded.  The unscaled E2M1 values are exact in fp16 and bf16; each 32-element block's products
+ * are exact and summed in fp32, the block's partial sum is scaled by 2^(e - 127) in fp32 (exact) and added to the fp32
+ * accumulator; the only other roundings are the final one to T and the epilogue's stated ones.  This holds for every scale byte
+ * 0..254 in both types -- there is no scale range an fp16 launch has to leave for a slower route.
+ * WHICH KERNEL A SHAPE TAKES (zl_mxfp4_route answers on the host without launching; < 0: the ZL_E* code the launch would return):
+ *   M = 1..4    ZL_MXFP4_GEMV    wave per two weight rows, 16 B of codes per lane and block, fp32 FMAs
+ *   M = 5..32   ZL_MXFP4_STREAM  workgroup per 16 weight rows, K split over its 4 waves, v_mfma_f32_16x16x32 per block: W read once
+ *   M > 32      ZL_MXFP4_TILED   64 x 64 outputs per workgroup, dequantised on the fly (prompt chunks)
+ * zl_mxfp4_dequant: W as (N, K) T, rounded once (exact in bf16; in fp16 for -23 <= e - 127 <= 13) -- tests and debugging.
+ * ---------------------------------------------------------------------------------------------- */
+enum { ZL_MXFP4_GEMV = 1, ZL_MXFP4_STREAM = 2, ZL_MXFP4_TILED = 3 };
+int zl_mxfp4_route(int64_t m, int64_t n, int64_t k);
+int zl_mxfp4_linear(const uint16_t* x, int64_t ldx, const uint8_t* codes, const uint8_t* scales, const uint16_t* bias,
+                    const uint16_t* residual, uint16_t* y, int64_t m, int64_t n, int64_t k, int dtype, int epilogue, zl_stream_t s);
+int zl_mxfp4_dequant(const uint8_t* codes, const uint8_t* scales, uint16_t* out /* (N,K) T */, int64_t n, int64_t k, int dtype,
+                     zl_stream_t s);
+
 /* lm_head + greedy pick without a separate argmax pass over the logits: the GEMV leaves each wavefront's
  * best (rounded logit, row index) in argmax_ws (zl_argmax_workspace_bytes(m, n) bytes); zl_greedy_advance
  * reduces them per activation row (first index on ties, like torch.argmax) and does the between-steps

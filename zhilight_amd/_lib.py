@@ -50,6 +50,7 @@ SYMBOLS = [
     "zl_quant_back_copy_to_buffer",
     "zl_w4a8_weight_to_int8", "zl_quant_scale_back_f32",
     "zl_awq_dequantize", "zl_awq_gemm_workspace_bytes", "zl_awq_gemm",
+    "zl_mxfp4_route", "zl_mxfp4_linear", "zl_mxfp4_dequant",
 ]
 
 

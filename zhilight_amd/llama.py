@@ -112,12 +112,16 @@ class ModelConfig:
                    dtype="bfloat16")
 
 
+MXFP4 = 11      # QuantConfig.quant_type of OCP MXFP4 checkpoints (the reference's QuantType enum ends at 10)
+
+
 @dataclass
 class QuantConfig:
     """model::QuantConfig (src/model/model_config.hpp:132-177); quant_type 5 = GPTQ W4A16 k-major.
     `awq` marks an AWQ checkpoint taken through the reference's AWQ_USE_EXLLAMA route
     (Int4GPTQ with is_awq, src/nn/linear/linear.cpp:694-698, 1139-1143): the tensors are converted to the
-    same k-major operands at load, the kernels are the GPTQ ones."""
+    same k-major operands at load, the kernels are the GPTQ ones.
+    quant_type 11 = MXFP4 (OCP microscaled FP4 weights, group_size 32; outside the reference's enum 0-10): Mxfp4EncoderLayer."""
     quant_type: int = 5
     group_size: int = 128
     sym: bool = False
@@ -129,6 +133,11 @@ class QuantConfig:
         """QuantConfig.adapt_hf_config (zhilight/quant.py:35-88): gptq -> type 5; awq -> type 5 with the AWQ
         load transform (what the reference does under AWQ_USE_EXLLAMA=1, its faster decode route)."""
         method = qc.get("quant_method", "gptq")
+        if method == "mxfp4":
+            # transformers' Mxfp4Config: E2M1 codes + E8M0 scales per 32 elements, nothing else to configure
+            return cls(MXFP4, 32, True, False, False)
+        if method == "quark":
+            return cls._from_quark(qc)
         if method not in ("gptq", "awq"):
             raise ops.ZLError(f"Unsupported quant_method {method}")
         if qc.get("bits", 4) != 4:
@@ -141,6 +150,30 @@ class QuantConfig:
                 raise ops.ZLError("AWQ checkpoints without zero points are not supported")
             return cls(5, qc.get("group_size", 128), False, False, True)
         return cls(5, qc.get("group_size", 128), qc.get("sym", False), act_order, False)
+
+    @classmethod
+    def _from_quark(cls, qc: dict):
+        """AMD Quark exports (quant_method "quark"): accepted only when the global weight spec is MXFP4 -- dtype fp4, per-group
+        along the input axis, group size 32, E8M0 (power-of-two) scales.  Every other Quark scheme is refused by name.  An
+        activation spec (`input_tensors`, e.g. the fp4 activations of a W4A4 export) is IGNORED: the model is executed weight-only,
+        activations stay fp16 / bf16.  Per-layer overrides (`layer_quant_config`, `layer_type_quant_config`) other than empty are
+        refused: one format for every linear."""
+        g = qc.get("global_quant_config") or {}
+        w = g.get("weight")
+        if isinstance(w, (list, tuple)):
+            w = w[0] if len(w) == 1 else None
+        if not isinstance(w, dict):
+            raise ops.ZLError("Unsupported Quark config: no single global weight spec")
+        dtype, scheme = str(w.get("dtype", "")).lower(), str(w.get("qscheme", "")).lower()
+        scale_fmt = str(w.get("scale_format", w.get("scale_type", ""))).lower()
+        what = f"Quark dtype={dtype or '?'} qscheme={scheme or '?'} group_size={w.get('group_size')} scale_format={scale_fmt or '?'}"
+        if dtype not in ("fp4", "mxfp4", "fp4_e2m1") or scheme != "per_group" or w.get("group_size") != 32 or scale_fmt != "e8m0":
+            raise ops.ZLError(f"Unsupported {what}: only fp4 / per_group / group_size 32 / e8m0 (MXFP4) is supported")
+        if w.get("ch_axis", -1) not in (-1, 1):
+            raise ops.ZLError(f"Unsupported {what}: groups must run along the input axis")
+        if qc.get("layer_quant_config") or qc.get("layer_type_quant_config"):
+            raise ops.ZLError("Unsupported Quark config: per-layer overrides")
+        return cls(MXFP4, 32, True, False, False)
 
 
 def hf_name_to_internal(name: str) -> str:
@@ -585,6 +618,127 @@ class Int8EncoderLayer:
                                      "silu", hidden.dtype)
         aq, sa = ops.quant_calc_scale(act)
         ops.quant_back_element_add_scale(self.w_out.gemm(aq), sa, self.w_out.scale, hidden, 1.0, out=hidden)
+
+
+def mxfp4_tensors(sd, prefix):
+    """The ONE place that knows how an MXFP4 linear is spelled in a checkpoint -> (codes (N, K/2) uint8, scales (N, K/32) uint8,
+    bias or None).  Accepted: `<name>.weight` uint8 (N, K/2) + `<name>.weight_scale` uint8 (N, K/32) (the spelling Quark's
+    exporter is documented to write) and `<name>.weight_blocks` (N, K/32, 16) + `<name>.weight_scales` (transformers' mxfp4
+    integration), plus an optional `<name>.bias`.  UNVERIFIED against a real Quark checkpoint: none was available when this was
+    written; a different spelling is a change to this function only."""
+    if prefix + ".weight_blocks" in sd:
+        codes, scales = sd[prefix + ".weight_blocks"], sd.get(prefix + ".weight_scales")
+    else:
+        codes, scales = sd.get(prefix + ".weight"), sd.get(prefix + ".weight_scale")
+    if codes is None or scales is None:
+        raise ops.ZLError(f"{prefix}: MXFP4 tensors not found (.weight + .weight_scale, or .weight_blocks + .weight_scales)")
+    codes, scales = (t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t)) for t in (codes, scales))
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise ops.ZLError(f"{prefix}: MXFP4 codes and scales are uint8 tensors (got {codes.dtype}, {scales.dtype})")
+    if codes.dim() == 3:
+        codes = codes.reshape(codes.shape[0], -1)
+    return codes, scales, sd.get(prefix + ".bias")
+
+
+class Mxfp4Linear:
+    """A linear on MXFP4 weights (quant type 11): y = T(x . W^T + bias), T = fp16 or bf16, no weight ever rounded
+    (ops.mxfp4_linear).  `fuse` concatenates rows like Linear::fuse; row_interleave for the gated pair."""
+
+    def __init__(self, name, dim_in, dim_out):
+        self.name, self.dim_in, self.dim_out = name, dim_in, dim_out
+        self.weight: Optional[ops.Mxfp4Weight] = None
+        self.bias = None
+
+    def load_state_dict(self, sd, prefix, device, dtype):
+        codes, scales, bias = mxfp4_tensors(sd, prefix)
+        if tuple(codes.shape) != (self.dim_out, self.dim_in // 2) or tuple(scales.shape) != (self.dim_out, self.dim_in // 32):
+            raise ops.ZLError(f"{prefix}: codes {tuple(codes.shape)} / scales {tuple(scales.shape)} do not fit a "
+                              f"({self.dim_out}, {self.dim_in}) MXFP4 weight")
+        self.weight = ops.Mxfp4Weight.from_checkpoint(_dev_t(codes, device), _dev_t(scales, device))
+        if bias is not None:
+            self.bias = _dev_t(bias, device).to(dtype).contiguous()
+        return self
+
+    @staticmethod
+    def fuse(name, parts: List["Mxfp4Linear"], row_interleave=False):
+        out = Mxfp4Linear(name, parts[0].dim_in, sum(p.dim_out for p in parts))
+        out.weight = ops.Mxfp4Weight.from_checkpoint(torch.cat([p.weight.codes for p in parts], dim=0),
+                                                     torch.cat([p.weight.scales for p in parts], dim=0), row_interleave)
+        if any(p.bias is not None for p in parts):
+            ref = next(p.bias for p in parts if p.bias is not None)
+            b = torch.cat([p.bias if p.bias is not None else torch.zeros(p.dim_out, dtype=ref.dtype, device=ref.device) for p in parts])
+            if row_interleave:
+                b = b.view(2, -1).t().reshape(-1)
+            out.bias = b.contiguous()
+        return out
+
+    @classmethod
+    def random(cls, name, dim_in, dim_out, device, gen, row_interleave=False):
+        l = cls(name, dim_in, dim_out)
+        l.weight = ops.Mxfp4Weight.random(dim_out, dim_in, device, gen, std=0.25 / math.sqrt(dim_in), row_interleave=row_interleave)
+        return l
+
+    def nbytes(self):
+        return self.weight.nbytes()
+
+    def forward(self, x, out=None, residual=None, epilogue=0):
+        return ops.mxfp4_linear(x, self.weight, bias=self.bias, residual=residual, out=out, epilogue=epilogue)
+
+
+class Mxfp4EncoderLayer:
+    """EncoderLayer over Mxfp4Linear (quant type 11), on the plain route of the decode step and of prompt encode: a stand-alone
+    RMSNorm, q|k|v fused by row concatenation (its bias: Qwen2-style checkpoints), gate|up fused row-interleaved under the
+    silu*mul epilogue, attn_out and w_out under the residual epilogue -- 4 GEMM launches + 2 norms per layer."""
+
+    def __init__(self, cfg: ModelConfig, quant: QuantConfig, idx: int):
+        if not cfg.activate_fn.startswith("silu"):
+            raise ops.ZLError("MXFP4 layers: silu feed-forward only")
+        self.cfg, self.quant, self.idx = cfg, quant, idx
+        self.unfused = None
+
+    def load_state_dict(self, sd, prefix, device):
+        c, dt = self.cfg, self.cfg.torch_dtype
+        hd, kvd = c.num_heads * c.dim_head, c.num_kv_heads * c.dim_head
+        self.ln_attn = _dev_t(sd[prefix + ".ln_attn.weight"], device).to(dt)
+        self.ln_ff = _dev_t(sd[prefix + ".ln_ff.weight"], device).to(dt)
+        lin = lambda sub, din, dout: Mxfp4Linear(prefix + "." + sub, din, dout).load_state_dict(sd, prefix + "." + sub, device, dt)  # noqa: E731
+        self.qkv = Mxfp4Linear.fuse(prefix + ".attn.project_qkv",
+                                    [lin("attn.project_q", c.dim_model, hd), lin("attn.project_k", c.dim_model, kvd),
+                                     lin("attn.project_v", c.dim_model, kvd)])
+        self.attn_out = lin("attn.attn_out", hd, c.dim_model)
+        self.w_in_gated = Mxfp4Linear.fuse(prefix + ".ff.w_in_gated", [lin("ff.w_in", c.dim_model, c.dim_ff),
+                                                                      lin("ff.w_gated", c.dim_model, c.dim_ff)], row_interleave=True)
+        self.w_out = lin("ff.w_out", c.dim_ff, c.dim_model)
+
+    def init_random(self, device, gen):
+        """weights quantised (ops.mxfp4_quantize) from N(0, 1 / sqrt(K)) / 4"""
+        c, dt = self.cfg, self.cfg.torch_dtype
+        hd, kvd = c.num_heads * c.dim_head, c.num_kv_heads * c.dim_head
+        self.ln_attn = (1.0 + 0.05 * torch.randn(c.dim_model, device=device, generator=gen)).to(dt)
+        self.ln_ff = (1.0 + 0.05 * torch.randn(c.dim_model, device=device, generator=gen)).to(dt)
+        self.qkv = Mxfp4Linear.random("qkv", c.dim_model, hd + 2 * kvd, device, gen)
+        self.attn_out = Mxfp4Linear.random("attn_out", hd, c.dim_model, device, gen)
+        self.w_in_gated = Mxfp4Linear.random("w_in_gated", c.dim_model, 2 * c.dim_ff, device, gen, row_interleave=True)
+        self.w_out = Mxfp4Linear.random("w_out", c.dim_ff, c.dim_model, device, gen)
+
+    def linears(self):
+        return [self.qkv, self.attn_out, self.w_in_gated, self.w_out]
+
+    def weight_bytes(self):
+        return sum(l.nbytes() for l in self.linears())
+
+    def project_qkv(self, hidden, eps, out=None):
+        return self.qkv.forward(ops.rmsnorm(hidden, self.ln_attn, eps), out=out)
+
+    def attn_out_add(self, attn, hidden):
+        self.attn_out.forward(attn, residual=hidden, out=hidden)
+
+    def ff_add(self, hidden, eps, act_buf=None):
+        rows = hidden.shape[0]
+        if act_buf is not None and act_buf.shape[0] != rows:
+            act_buf = None
+        act = self.w_in_gated.forward(ops.rmsnorm(hidden, self.ln_ff, eps), out=act_buf, epilogue=ops.EPI_SILU_MUL)
+        self.w_out.forward(act, residual=hidden, out=hidden)
 
 
 # decode attention with the split merge inside its launch (zl_decode_attn_la): default of the ZL_ATTN_LA switch
@@ -1221,14 +1375,21 @@ class LLaMA:
         only; heads, kv heads, dim_ff and the vocabulary must divide by the TP degree."""
         if cfg.scale_depth > 0 and quant.quant_type != 0:
             raise ops.ZLError("scale_depth (MiniCPM residual scaling) is only wired into the unquantised layer stack")
-        if quant.quant_type != 0 and cfg.torch_dtype != torch.float16:
+        if quant.quant_type not in (0, MXFP4) and cfg.torch_dtype != torch.float16:
             raise ops.ZLError("the W4A16 / int8 routes are fp16 (q_gemm_k_major.cu:989 asserts half)")
         self.cfg, self.quant, self.device = cfg, quant, torch.device(device)
-        # QuantType (zhilight/quant.py:8-19): 0 NoQuant, 2 AutoInt8, 5 GPTQ (AWQ-as-exllama rides on 5)
-        layer_cls = {0: DenseEncoderLayer, 2: Int8EncoderLayer}.get(quant.quant_type, EncoderLayer)
+        # QuantType (zhilight/quant.py:8-19): 0 NoQuant, 2 AutoInt8, 5 GPTQ (AWQ-as-exllama rides on 5); 11 MXFP4 is this project's
+        layer_cls = {0: DenseEncoderLayer, 2: Int8EncoderLayer, MXFP4: Mxfp4EncoderLayer}.get(quant.quant_type, EncoderLayer)
         self.tp = tp if tp is not None and tp.size > 1 else None
         self.full_cfg = cfg
         self.moe = any(cfg.is_moe_layer(i) for i in range(cfg.num_layers))
+        if quant.quant_type == MXFP4:
+            if quant.group_size != 32:
+                raise ops.ZLError("MXFP4: the block size is 32")
+            if self.tp:
+                raise ops.ZLError("MXFP4 models: tensor parallelism is not supported")
+            if self.moe:
+                raise ops.ZLError("MXFP4 models: MoE layers are not supported")
         if self.moe:
             # MoE models: the W4 route without tensor / expert parallelism (MoEEncoderLayer refuses the rest); the dense layers a
             # model lists in mlp_only_layers stay EncoderLayer

@@ -3403,3 +3403,136 @@ def mha_fwd_kvcache_mla(q, kcache, head_size_v, seqlens_k, block_table, softmax_
                                          _i(head_size_v), _i(cd - head_size_v), _i(page), _i(mb), _f(softmax_scale), C.c_int(_dt(q)), _stream()),
           "mha_fwd_kvcache_mla")
     return out, lse
+
+
+# --------------------------------------------------------------------------------------------------
+# MXFP4: OCP microscaled FP4 weights (include/zhilight_amd.h "MXFP4"; csrc/mxfp4.hip).  Quant type 11 of this project.
+# --------------------------------------------------------------------------------------------------
+MXFP4_GEMV, MXFP4_STREAM, MXFP4_TILED = 1, 2, 3
+MXFP4_BLOCK = 32
+_E2M1_MIDS = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)       # between codes i and i + 1 of {0, .5, 1, 1.5, 2, 3, 4, 6}
+
+
+def mxfp4_quantize(w):
+    """A float (N, K) tensor (K % 32 == 0, any device) -> (codes uint8 (N, K/2), scales uint8 (N, K/32)) under the OCP MX rule:
+    a block's exponent is floor(log2(amax)) - 2 (E2M1's largest exponent), an all-zero block gets scale byte 0; elements are
+    rounded to the nearest E2M1 value, ties to the even code, and saturate at +-6.  Plain torch, float64: a tool for tests,
+    init_random and the benchmarks, not a hot path."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK != 0:
+        raise ZLError("mxfp4_quantize: (N, K) with K % 32 == 0")
+    n, k = w.shape
+    blocks = w.detach().to(torch.float64).reshape(n, k // MXFP4_BLOCK, MXFP4_BLOCK)
+    if not bool(torch.isfinite(blocks).all()):
+        raise ZLError("mxfp4_quantize: non-finite weights")
+    amax = blocks.abs().amax(dim=2)
+    _, ex = torch.frexp(amax)                               # amax = m * 2^ex, m in [0.5, 1): floor(log2(amax)) = ex - 1
+    byte = torch.where(amax > 0, (ex.to(torch.int64) - 3 + 127).clamp(0, 254), torch.zeros_like(ex, dtype=torch.int64))
+    a = torch.ldexp(blocks.abs(), (127 - byte).unsqueeze(2).to(torch.int32))
+    code = torch.zeros_like(a, dtype=torch.int64)
+    for i, mid in enumerate(_E2M1_MIDS):                    # a tie goes to the even one of codes i, i + 1
+        code += (a >= mid) if i % 2 else (a > mid)
+    code = torch.where((blocks < 0) & (code > 0), code + 8, code).reshape(n, k).to(torch.uint8)
+    return (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous(), byte.to(torch.uint8).contiguous()
+
+
+class Mxfp4Weight:
+    """An MXFP4 matrix on the device as the kernels read it -- the checkpoint's own layout: codes uint8 (N, K/2), scales uint8
+    (N, K/32); 0.53125 B per weight, no packed copy.  row_interleave stores source row (i % 2) * (N / 2) + i / 2 at row i, so
+    that a vertically concatenated [gate; up] matrix becomes (gate_j, up_j) row pairs for the silu*mul epilogue."""
+
+    def __init__(self, codes, scales, row_interleave=False):
+        self.codes, self.scales, self.row_interleave = codes, scales, bool(row_interleave)
+        self.n, self.k = codes.shape[0], codes.shape[1] * 2
+
+    @classmethod
+    def from_checkpoint(cls, codes, scales, row_interleave=False):
+        """codes (N, K/2) or (N, K/32, 16) uint8, scales (N, K/32) uint8, CUDA tensors.  Refuses a scale byte 255 (the format's NaN)
+        with one host-side check."""
+        if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or not (codes.is_cuda and scales.is_cuda):
+            raise ZLError("Mxfp4Weight: codes and scales are uint8 CUDA tensors")
+        if codes.dim() == 3:
+            codes = codes.reshape(codes.shape[0], -1)
+        if (codes.dim() != 2 or scales.dim() != 2 or codes.shape[1] % 16 != 0 or scales.shape[0] != codes.shape[0]
+                or scales.shape[1] * 16 != codes.shape[1]):
+            raise ZLError(f"Mxfp4Weight: codes {tuple(codes.shape)} / scales {tuple(scales.shape)} are not (N, K/2) / (N, K/32)")
+        if bool((scales == 255).any()):
+            raise ZLError("Mxfp4Weight: scale byte 255 (the E8M0 NaN) in the checkpoint")
+        if row_interleave:
+            n = codes.shape[0]
+            if n % 2:
+                raise ZLError("Mxfp4Weight: row_interleave needs an even row count")
+            idx = torch.arange(n, device=codes.device).view(2, n // 2).t().reshape(-1)
+            codes, scales = codes[idx], scales[idx]
+        return cls(codes.contiguous(), scales.contiguous(), row_interleave)
+
+    @classmethod
+    def random(cls, n, k, device, gen=None, std=0.05, row_interleave=False):
+        codes, scales = mxfp4_quantize(torch.randn(n, k, device=device, generator=gen) * std)
+        return cls.from_checkpoint(codes, scales, row_interleave)
+
+    def nbytes(self):
+        return self.codes.numel() + self.scales.numel()
+
+    def dequantize(self, dtype=torch.float16):
+        return mxfp4_dequantize(self.codes, self.scales, dtype)
+
+
+def mxfp4_route(m, n, k):
+    """which kernel mxfp4_linear launches for (m, n, k): MXFP4_GEMV (1..4 rows), MXFP4_STREAM (5..32), MXFP4_TILED (more)"""
+    r = int(lib().zl_mxfp4_route(_i(m), _i(n), _i(k)))
+    if r < 0:
+        check(r, "mxfp4_route")
+    return r
+
+
+def mxfp4_dequantize(codes, scales, dtype=torch.float16, out=None):
+    """W (N, K) in fp16 / bf16, rounded once (exact in bf16, in fp16 for 2^-23 .. 2^13 scales): tests and debugging"""
+    _chk_cuda(codes, scales)
+    n, k = codes.shape[0], codes.shape[1] * 2
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or tuple(scales.shape) != (n, k // 32) or k % 32:
+        raise ZLError("mxfp4_dequantize: codes uint8 (N, K/2), scales uint8 (N, K/32)")
+    if out is None:
+        out = torch.empty((n, k), dtype=dtype, device=codes.device)
+    else:
+        _chk_out(out, n, k, dtype, codes.device, "mxfp4_dequantize")
+    check(lib().zl_mxfp4_dequant(_p(codes), _p(scales), _p(out), _i(n), _i(k), C.c_int(_dt(out)), _stream()), "mxfp4_dequantize")
+    return out
+
+
+def mxfp4_linear(x, w: Mxfp4Weight, bias=None, residual=None, out=None, epilogue=0):
+    """y = T(x . W^T [+ bias]) on an Mxfp4Weight, T = x.dtype (fp16 / bf16), fp32 accumulation, no rounding of a weight.
+    bias adds EPI_BIAS, residual EPI_RESIDUAL (y = T(residual + T(acc + bias)); out may alias it); EPI_SILU_MUL on a
+    row-interleaved [gate; up] weight writes N / 2 columns.  x: (.., K) with unit element stride; a 2-D x may have a row
+    stride > K (% 8 == 0)."""
+    _chk_cuda(bias, residual)
+    if not x.is_cuda or x.stride(-1) != 1:
+        raise ZLError("mxfp4_linear: x must be a CUDA tensor with contiguous rows")
+    x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])
+    m, k = x2.shape
+    if k != w.k:
+        raise ZLError("size K mismatch")
+    if m > 1 and x2.stride(0) < k:
+        raise ZLError("mxfp4_linear: overlapping rows")
+    silu = epilogue & EPI_SILU_MUL
+    if silu and not w.row_interleave:
+        raise ZLError("mxfp4_linear: EPI_SILU_MUL needs a row-interleaved [gate; up] weight")
+    n_out = w.n // 2 if silu else w.n
+    for t, what in ((bias, "bias"), (residual, "residual")):
+        if t is not None and (t.dtype != x.dtype or t.device != x.device):
+            raise ZLError(f"mxfp4_linear: {what} dtype / device")
+    if bias is not None:
+        if bias.numel() != w.n:
+            raise ZLError("mxfp4_linear: bias size")
+        epilogue |= EPI_BIAS
+    if residual is not None:
+        if residual.numel() != m * n_out:
+            raise ZLError("mxfp4_linear: residual size")
+        epilogue |= EPI_RESIDUAL
+    if out is None:
+        out = torch.empty((m, n_out), dtype=x.dtype, device=x.device)
+    else:
+        _chk_out(out, m, n_out, x.dtype, x.device, "mxfp4_linear")
+    ldx = x2.stride(0) if m > 1 else k
+    check(lib().zl_mxfp4_linear(_p(x2), _i(ldx), _p(w.codes), _p(w.scales), _p(bias), _p(residual), _p(out), _i(m), _i(w.n), _i(k),
+                                C.c_int(_dt(x)), C.c_int(epilogue), _stream()), "mxfp4_linear")
+    return out
