@@ -360,6 +360,27 @@ int zl_mxfp4_linear(const uint16_t* x, int64_t ldx, const uint8_t* codes, const 
                     const uint16_t* residual, uint16_t* y, int64_t m, int64_t n, int64_t k, int dtype, int epilogue, zl_stream_t s);
 int zl_mxfp4_dequant(const uint8_t* codes, const uint8_t* scales, uint16_t* out /* (N,K) T */, int64_t n, int64_t k, int dtype,
                      zl_stream_t s);
+/* MXFP8 ACTIVATIONS (opt-in prompt route, csrc/mxfp4_a8.hip): the activations are rounded to OCP MXFP8 and the product runs on
+ * v_mfma_scale_f32_16x16x128_f8f6f4, which decodes E4M3 x E2M1 and applies both E8M0 block scales itself.
+ * zl_mxfp8_quantize: x (M, K) T with row stride ldx (% 8 == 0, 16-byte aligned), K % 32 == 0 -> xq uint8 (M, K), E4M3 "fn" codes (no
+ *   infinity, largest value 448, subnormals down to 2^-9), and xs uint8 (M, K/32), E8M0.  Per block of 32 elements (OCP MX v1.0, the
+ *   conventions of the weight format): byte = clamp(floor(log2(amax)) - 8 + 127, 0, 254), an all-zero block gets byte 0;
+ *   xq = x / 2^(byte - 127), exact in fp32, rounded ONCE to the nearest E4M3 value, ties to the even code, saturating at +-448 (an
+ *   element above 448 2^(byte - 127), e.g. 500 under amax 511, becomes 448).  x is finite: a NaN or an infinity is not defined.
+ * zl_mxfp4_a8_linear: y[m, n] = T( sum_b 2^(xs[m, b] + scales[n, b] - 254) * sum_{i < 32} E4M3(xq[m, 32 b + i]) * E2M1(code[n, 32 b + i])
+ *   [+ bias] ), y (M, N) -- (M, N / 2) under ZL_EPI_SILU_MUL -- with the epilogues of zl_mxfp4_linear and their arithmetic.  xq (M, K)
+ *   and xs (M, K/32) contiguous, codes / scales the checkpoint's tensors as above (no packed copy); K % 32 == 0 (a K that is no
+ *   multiple of 128 is padded with zero codes in registers), any M >= 1, xq and codes 16-byte aligned, xs and scales 4-byte aligned
+ *   when K % 128 == 0.  Meant for more than 32 rows: fewer rows are bandwidth-bound and belong to zl_mxfp4_linear.
+ *   NUMERICS: the operands are never rounded again -- every product E4M3 x E2M1 is exact (at most 6 significant bits) -- and the
+ *   sum is accumulated in fp32 INSIDE the instruction: the order of its 128-term sum and its internal rounding are not documented
+ *   (tests hold it to 2 K roundings of the absolute sum).  One workgroup owns an output over all of K: no atomics, the same bits on
+ *   every run.  DEFINED when every xs[m, b] + scales[n, b] - 254 lies in fp32's normal exponent range (-126 .. 127); scale byte
+ *   255 is excluded at load as above. */
+int zl_mxfp8_quantize(const uint16_t* x, int64_t ldx, uint8_t* xq /* (M,K) */, uint8_t* xs /* (M,K/32) */, int64_t m, int64_t k, int dtype,
+                      zl_stream_t s);
+int zl_mxfp4_a8_linear(const uint8_t* xq, const uint8_t* xs, const uint8_t* codes, const uint8_t* scales, const uint16_t* bias,
+                       const uint16_t* residual, uint16_t* y, int64_t m, int64_t n, int64_t k, int dtype, int epilogue, zl_stream_t s);
 
 /* lm_head + greedy pick without a separate argmax pass over the logits: the GEMV leaves each wavefront's
  * best (rounded logit, row index) in argmax_ws (zl_argmax_workspace_bytes(m, n) bytes); zl_greedy_advance

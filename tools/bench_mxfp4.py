@@ -1,6 +1,7 @@
 """MXFP4 linears and the MXFP4 decode step on the Llama-3-8B geometry (DESIGN 4 "MXFP4 weights", profiles/mxfp4.txt).
 
     python tools/bench_mxfp4.py [--iters 100] [--no-linears] [--no-steps] [--layers 32]
+    python tools/bench_mxfp4.py --act mxfp8 [--iters 100] [--layers 32]      (DESIGN 4 "MXFP8 activations", profiles/mxfp4_a8.txt)
 
 Method: hipEvent pairs around every iteration after 10 warm-ups, >= 100 iterations; the linears rotate through >= 4
 weight buffers totalling more than 256 MB, so every read of a weight comes from HBM -- an iteration is one hipGraph replay of one
@@ -10,6 +11,11 @@ launch per buffer, reported per launch (eager launches measure the host: ~14 us 
   steps     the whole decode step (hipGraph replay of step_greedy) at batch 1 / 8 / 32, sequence 1024, in tokens/s, for quant type 11
             (MXFP4), type 0 (fp16), type 5 (GPTQ) on its default route and type 5 on the plain route (ZL_FUSE_QKV_ROPE=0): the
             like-for-like comparison, MXFP4 having no fused qkv + rotary launch
+  --act mxfp8  the prompt route with MXFP8 activations against the weight-only tiled route, in the same run, alternating the two:
+            the four projections at M = 128, 512, 2048 -- the weight-only launch, the quantiser, the A8 GEMM and quantiser + GEMM as one
+            replay, "speedup" = weight-only / (quantiser + GEMM) -- and the time to the first token of a 1024-token prompt (LLaMA.prefill,
+            eager launches between two events: both ways pay the same launches but for the quantisers) on ONE model whose linears are
+            switched between the routes, so both ways read the same weights
 One JSON line per measurement on stdout."""
 import argparse
 import json
@@ -85,6 +91,63 @@ def bench_linears(dev, iters):
         torch.cuda.empty_cache()
 
 
+def bench_act(dev, iters, layers, rows=(128, 512, 2048), prompt_len=1024):
+    gen = torch.Generator(device=dev).manual_seed(1)
+    us = lambda q: [round(t * 1e6, 2) for t in q]  # noqa: E731
+    for name, n, k, epi in LINEARS:
+        nbuf = max(4, int(256e6 // (n * k * 0.53125)) + 2)
+        ws = [random_weight(n, k, dev, gen, bool(epi & ops.EPI_SILU_MUL)) for _ in range(nbuf)]
+        for dtype in (torch.float16, torch.bfloat16):
+            for m in rows:
+                x = torch.randn(m, k, device=dev, generator=gen).to(dtype)
+                out = torch.zeros(m, n // 2 if epi & ops.EPI_SILU_MUL else n, dtype=dtype, device=dev)
+                kw = dict(residual=out if epi & ops.EPI_RESIDUAL else None, out=out, epilogue=epi & ops.EPI_SILU_MUL)
+                q = ops.mxfp8_quantize(x)
+                legs = {"weight_only": lambda w: ops.mxfp4_linear(x, w, **kw), "quantise": lambda w: ops.mxfp8_quantize(x, out=q),
+                        "a8_gemm": lambda w: ops.mxfp4_a8_linear(q[0], q[1], w, dtype, **kw),
+                        "a8": lambda w: ops.mxfp4_a8_linear(*ops.mxfp8_quantize(x, out=q), w, dtype, **kw)}
+                graphs = {}
+                for leg, run in legs.items():
+                    run(ws[0])
+                    torch.cuda.synchronize()
+                    graphs[leg] = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graphs[leg]):
+                        for w in ws:
+                            run(w)
+                times = {leg: [] for leg in legs}
+                for _ in range(4):                                 # alternate the legs: four rounds of iters / 4 replays each
+                    for leg, g in graphs.items():
+                        times[leg] += timed(lambda i: g.replay(), max(1, iters // 4), warmup=3)
+                res = {leg: [t / nbuf for t in quantiles(ts)] for leg, ts in times.items()}
+                del graphs
+                w16, a8 = res["weight_only"], res["a8"]
+                print(json.dumps({"what": "act_linear", "name": name, "n": n, "k": k, "m": m, "dtype": str(dtype).split(".")[1], "buffers": nbuf,
+                                  **{leg + "_us_p50_p10_p90": us(r) for leg, r in res.items()},
+                                  "speedup_p50": round(w16[0] / a8[0], 3), "speedup_p10_p90": [round(w16[1] / a8[2], 3), round(w16[2] / a8[1], 3)],
+                                  "a8_tflops": round(2.0 * m * n * k / a8[0] * 1e-12, 1)}), flush=True)
+        del ws
+        torch.cuda.empty_cache()
+    cfg = ModelConfig.llama3_8b()
+    cfg.num_layers = layers
+    model = LLaMA(cfg, QuantConfig(11, 32), dev).init_random(seed=1234)
+    prompt = torch.randint(0, cfg.vocab_size, (prompt_len,), device=dev, dtype=torch.int32, generator=gen)
+    ctx = model.new_context(1, prompt_len + 64, 0)
+
+    def prefill(act):
+        for layer in model.layers:
+            for lin in layer.linears():
+                lin.act_quant = act
+        ctx.positions.zero_(), ctx.placement.zero_(), ctx.valid_lens.zero_()
+        model.prefill(ctx, 0, prompt)
+    times = {"": [], "mxfp8": []}
+    for _ in range(4):
+        for act in times:
+            times[act] += timed(lambda i: prefill(act), max(1, iters // 10), warmup=1)
+    w16, a8 = quantiles(times[""]), quantiles(times["mxfp8"])
+    print(json.dumps({"what": "ttft", "layers": layers, "prompt": prompt_len, "weight_only_ms_p50_p10_p90": [round(t * 1e3, 3) for t in w16],
+                      "a8_ms_p50_p10_p90": [round(t * 1e3, 3) for t in a8], "speedup_p50": round(w16[0] / a8[0], 3)}), flush=True)
+
+
 def bench_steps(dev, iters, layers, seq=1024):
     cfg = ModelConfig.llama3_8b()
     cfg.num_layers = layers
@@ -125,8 +188,11 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--no-linears", action="store_true")
     ap.add_argument("--no-steps", action="store_true")
+    ap.add_argument("--act", choices=("", "mxfp8"), default="", help="mxfp8: the A/B of the MXFP8-activation prompt route, nothing else")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.act:
+        return bench_act(dev, args.iters, args.layers)
     if not args.no_linears:
         bench_linears(dev, args.iters)
     if not args.no_steps:

@@ -19,25 +19,13 @@
 //                              the lane groups turns into MFMA B fragments; 16 / 32 activation rows as A fragments
 //   > 32 rows   k_mxfp4_tiled  64 x 64 outputs per workgroup (a wave: 64 rows x 16 columns), no K split; weights re-read per
 //                              64-row slice of x (prompt chunks)
-#include "zl_common.h"
-#include "zl_w4m_epilogue.h"
+#include "zl_mxfp4.h"
 
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef __bf16 b8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-struct Mx4Params {
-    const uint16_t* x;
-    int64_t ldx;
-    const uint8_t* codes;
-    const uint8_t* scales;
-    const uint16_t* bias;
-    const uint16_t* residual;
-    uint16_t* y;
-    int m, n, k, nb, epi;       // nb = k / 32
-};
 
 // 2^(e - 127) as fp32; byte 0 is 2^-127, an fp32 subnormal
 __device__ __forceinline__ float mx_scale_f32(uint32_t e) { return __builtin_bit_cast(float, e ? e << 23 : 0x00400000u); }
@@ -86,27 +74,6 @@ template <int DT>
 __device__ __forceinline__ float mx_x_hi(uint32_t pair) {
     if constexpr (DT == ZL_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(pair >> 16));
     else return __builtin_bit_cast(float, pair & 0xffff0000u);
-}
-
-// ---- the epilogues of zl_w4a16 (include/zhilight_amd.h) for either T.  v: the fp32 sum of output (m, n)
-template <int DT>
-__device__ __forceinline__ void mx_store_plain(const Mx4Params& p, int m, int n, float v) {
-    if ((p.epi & ZL_EPI_BIAS) && p.bias) v += ZT<DT>::to_f32(p.bias[n]);
-    uint16_t o = ZT<DT>::from_f32(v);
-    const size_t at = (size_t)m * p.n + n;
-    if (p.epi & ZL_EPI_RESIDUAL) o = ZT<DT>::from_f32(ZT<DT>::to_f32(p.residual[at]) + ZT<DT>::to_f32(o));
-    p.y[at] = o;
-}
-// g, u: the sums of rows 2 j (gate) and 2 j + 1 (up) of the row-interleaved matrix; writes column j of n / 2
-template <int DT>
-__device__ __forceinline__ void mx_store_gated(const Mx4Params& p, int m, int j, float g, float u) {
-    if ((p.epi & ZL_EPI_BIAS) && p.bias) {
-        g += ZT<DT>::to_f32(p.bias[2 * j]);
-        u += ZT<DT>::to_f32(p.bias[2 * j + 1]);
-    }
-    g = ZT<DT>::to_f32(ZT<DT>::from_f32(g));
-    u = ZT<DT>::to_f32(ZT<DT>::from_f32(u));
-    p.y[(size_t)m * (p.n / 2) + j] = ZT<DT>::from_f32(silu_f32(g) * u);
 }
 
 // ---- 1..4 rows ------------------------------------------------------------------------------------------------------------
@@ -267,21 +234,6 @@ __device__ __forceinline__ void mx_run(const Mx4Params& p, const uint32_t* __res
                 }
             }
             load(u, quad + (u + PF) * step);
-        }
-    }
-}
-
-// the outputs of one 16 x 16 tile: rows m0 + 4 kq + i, column n.  Gated: columns pair up across lanes n, n ^ 1 (n even = gate)
-template <int DT>
-__device__ __forceinline__ void mx_store_tile(const Mx4Params& p, int m0, int n, int kq, const f4& v) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = m0 + 4 * kq + i;
-        if (p.epi & ZL_EPI_SILU_MUL) {
-            const float other = __shfl_xor(v[i], 1, 64);
-            if (!(n & 1) && n + 1 < p.n && row < p.m) mx_store_gated<DT>(p, row, n >> 1, v[i], other);
-        } else if (n < p.n && row < p.m) {
-            mx_store_plain<DT>(p, row, n, v[i]);
         }
     }
 }

@@ -121,12 +121,16 @@ class QuantConfig:
     `awq` marks an AWQ checkpoint taken through the reference's AWQ_USE_EXLLAMA route
     (Int4GPTQ with is_awq, src/nn/linear/linear.cpp:694-698, 1139-1143): the tensors are converted to the
     same k-major operands at load, the kernels are the GPTQ ones.
-    quant_type 11 = MXFP4 (OCP microscaled FP4 weights, group_size 32; outside the reference's enum 0-10): Mxfp4EncoderLayer."""
+    quant_type 11 = MXFP4 (OCP microscaled FP4 weights, group_size 32; outside the reference's enum 0-10): Mxfp4EncoderLayer.
+    `act_quant` (type 11 only; set by the caller, never by from_hf): "" = weight-only, activations stay fp16 / bf16; "mxfp8" = linears
+    over more than MXFP4_A8_ABOVE_ROWS rows quantise their input to OCP MXFP8 and run on the scaled MFMA (ops.mxfp4_a8_linear) --
+    prompt encode gets faster and its activations carry an E4M3 rounding; decode steps are untouched."""
     quant_type: int = 5
     group_size: int = 128
     sym: bool = False
     act_order: bool = False
     awq: bool = False
+    act_quant: str = ""
 
     @classmethod
     def from_hf(cls, qc: dict):
@@ -640,14 +644,21 @@ def mxfp4_tensors(sd, prefix):
     return codes, scales, sd.get(prefix + ".bias")
 
 
+# QuantConfig.act_quant == "mxfp8": a linear over MORE rows than this quantises its input and runs ops.mxfp4_a8_linear; up to this
+# many rows (decode steps: bandwidth-bound) it stays on the weight-only kernels, bit for bit.  ops.mxfp4_route's last boundary.
+MXFP4_A8_ABOVE_ROWS = 32
+
+
 class Mxfp4Linear:
     """A linear on MXFP4 weights (quant type 11): y = T(x . W^T + bias), T = fp16 or bf16, no weight ever rounded
-    (ops.mxfp4_linear).  `fuse` concatenates rows like Linear::fuse; row_interleave for the gated pair."""
+    (ops.mxfp4_linear).  `fuse` concatenates rows like Linear::fuse; row_interleave for the gated pair.  act_quant (set by the
+    layer from QuantConfig.act_quant): "mxfp8" sends more than MXFP4_A8_ABOVE_ROWS rows through mxfp8_quantize + mxfp4_a8_linear."""
 
     def __init__(self, name, dim_in, dim_out):
         self.name, self.dim_in, self.dim_out = name, dim_in, dim_out
         self.weight: Optional[ops.Mxfp4Weight] = None
         self.bias = None
+        self.act_quant = ""
 
     def load_state_dict(self, sd, prefix, device, dtype):
         codes, scales, bias = mxfp4_tensors(sd, prefix)
@@ -682,6 +693,9 @@ class Mxfp4Linear:
         return self.weight.nbytes()
 
     def forward(self, x, out=None, residual=None, epilogue=0):
+        if self.act_quant == "mxfp8" and x.numel() // x.shape[-1] > MXFP4_A8_ABOVE_ROWS:
+            xq, xs = ops.mxfp8_quantize(x)
+            return ops.mxfp4_a8_linear(xq, xs, self.weight, x.dtype, bias=self.bias, residual=residual, out=out, epilogue=epilogue)
         return ops.mxfp4_linear(x, self.weight, bias=self.bias, residual=residual, out=out, epilogue=epilogue)
 
 
@@ -709,6 +723,11 @@ class Mxfp4EncoderLayer:
         self.w_in_gated = Mxfp4Linear.fuse(prefix + ".ff.w_in_gated", [lin("ff.w_in", c.dim_model, c.dim_ff),
                                                                       lin("ff.w_gated", c.dim_model, c.dim_ff)], row_interleave=True)
         self.w_out = lin("ff.w_out", c.dim_ff, c.dim_model)
+        self._set_act_quant()
+
+    def _set_act_quant(self):
+        for l in self.linears():
+            l.act_quant = self.quant.act_quant
 
     def init_random(self, device, gen):
         """weights quantised (ops.mxfp4_quantize) from N(0, 1 / sqrt(K)) / 4"""
@@ -720,6 +739,7 @@ class Mxfp4EncoderLayer:
         self.attn_out = Mxfp4Linear.random("attn_out", hd, c.dim_model, device, gen)
         self.w_in_gated = Mxfp4Linear.random("w_in_gated", c.dim_model, 2 * c.dim_ff, device, gen, row_interleave=True)
         self.w_out = Mxfp4Linear.random("w_out", c.dim_ff, c.dim_model, device, gen)
+        self._set_act_quant()
 
     def linears(self):
         return [self.qkv, self.attn_out, self.w_in_gated, self.w_out]
@@ -1373,6 +1393,10 @@ class LLaMA:
     def __init__(self, cfg: ModelConfig, quant: QuantConfig, device="cuda:0", tp=None):
         """tp: parallel.TPGroup (rank, size, process group) for tensor parallelism over the GPUs of a node -- W4 route
         only; heads, kv heads, dim_ff and the vocabulary must divide by the TP degree."""
+        if quant.act_quant not in ("", "mxfp8"):
+            raise ops.ZLError(f"Unsupported act_quant {quant.act_quant!r}: '' (weight-only) or 'mxfp8'")
+        if quant.act_quant and quant.quant_type != MXFP4:
+            raise ops.ZLError("act_quant='mxfp8' is the prompt route of MXFP4 models (quant type 11) only")
         if cfg.scale_depth > 0 and quant.quant_type != 0:
             raise ops.ZLError("scale_depth (MiniCPM residual scaling) is only wired into the unquantised layer stack")
         if quant.quant_type not in (0, MXFP4) and cfg.torch_dtype != torch.float16:

@@ -3536,3 +3536,62 @@ def mxfp4_linear(x, w: Mxfp4Weight, bias=None, residual=None, out=None, epilogue
     check(lib().zl_mxfp4_linear(_p(x2), _i(ldx), _p(w.codes), _p(w.scales), _p(bias), _p(residual), _p(out), _i(m), _i(w.n), _i(k),
                                 C.c_int(_dt(x)), C.c_int(epilogue), _stream()), "mxfp4_linear")
     return out
+
+
+def mxfp8_quantize(x, out=None):
+    """fp16 / bf16 activations (.., K), K % 32 == 0 -> (codes uint8 (M, K) E4M3, scales uint8 (M, K/32) E8M0) under the OCP MX
+    rule stated at zl_mxfp8_quantize (block exponent floor(log2(amax)) - 8, nearest E4M3 value, ties to even, saturating at 448): the
+    activation operand of mxfp4_a8_linear.  A 2-D x may have a row stride > K (% 8 == 0); out = (codes, scales) to reuse buffers."""
+    if not x.is_cuda or x.stride(-1) != 1 or x.dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError("mxfp8_quantize: x must be an fp16 / bf16 CUDA tensor with contiguous rows")
+    x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])
+    m, k = x2.shape
+    if k % MXFP4_BLOCK or m < 1:
+        raise ZLError("mxfp8_quantize: (M, K) with K % 32 == 0")
+    if m > 1 and x2.stride(0) < k:
+        raise ZLError("mxfp8_quantize: overlapping rows")
+    if out is None:
+        out = (torch.empty((m, k), dtype=torch.uint8, device=x.device), torch.empty((m, k // MXFP4_BLOCK), dtype=torch.uint8, device=x.device))
+    else:
+        _chk_out(out[0], m, k, torch.uint8, x.device, "mxfp8_quantize")
+        _chk_out(out[1], m, k // MXFP4_BLOCK, torch.uint8, x.device, "mxfp8_quantize")
+    check(lib().zl_mxfp8_quantize(_p(x2), _i(x2.stride(0) if m > 1 else k), _p(out[0]), _p(out[1]), _i(m), _i(k), C.c_int(_dt(x)), _stream()),
+          "mxfp8_quantize")
+    return out
+
+
+def mxfp4_a8_linear(xq, xs, w: Mxfp4Weight, dtype, bias=None, residual=None, out=None, epilogue=0):
+    """y = T(xq . W^T [+ bias]) for MXFP8 activations (mxfp8_quantize's codes (M, K) and scales (M, K/32)) on an Mxfp4Weight, T = dtype
+    (fp16 / bf16), on the scaled MFMA (zl_mxfp4_a8_linear has the numerics); bias, residual, out and epilogue as in mxfp4_linear."""
+    _chk_cuda(xq, xs, bias, residual)
+    if xq.dtype != torch.uint8 or xs.dtype != torch.uint8 or xq.dim() != 2 or not (xq.is_contiguous() and xs.is_contiguous()):
+        raise ZLError("mxfp4_a8_linear: xq (M, K) and xs (M, K/32) are contiguous uint8 tensors")
+    m, k = xq.shape
+    if k != w.k:
+        raise ZLError("size K mismatch")
+    if k % MXFP4_BLOCK or tuple(xs.shape) != (m, k // MXFP4_BLOCK):
+        raise ZLError(f"mxfp4_a8_linear: xs {tuple(xs.shape)} is not (M, K/32) = ({m}, {k // MXFP4_BLOCK})")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError("mxfp4_a8_linear: dtype is torch.float16 or torch.bfloat16")
+    silu = epilogue & EPI_SILU_MUL
+    if silu and not w.row_interleave:
+        raise ZLError("mxfp4_a8_linear: EPI_SILU_MUL needs a row-interleaved [gate; up] weight")
+    n_out = w.n // 2 if silu else w.n
+    for t, what in ((bias, "bias"), (residual, "residual")):
+        if t is not None and (t.dtype != dtype or t.device != xq.device):
+            raise ZLError(f"mxfp4_a8_linear: {what} dtype / device")
+    if bias is not None:
+        if bias.numel() != w.n:
+            raise ZLError("mxfp4_a8_linear: bias size")
+        epilogue |= EPI_BIAS
+    if residual is not None:
+        if residual.numel() != m * n_out:
+            raise ZLError("mxfp4_a8_linear: residual size")
+        epilogue |= EPI_RESIDUAL
+    if out is None:
+        out = torch.empty((m, n_out), dtype=dtype, device=xq.device)
+    else:
+        _chk_out(out, m, n_out, dtype, xq.device, "mxfp4_a8_linear")
+    check(lib().zl_mxfp4_a8_linear(_p(xq), _p(xs), _p(w.codes), _p(w.scales), _p(bias), _p(residual), _p(out), _i(m), _i(w.n), _i(k),
+                                   C.c_int(_dt(out)), C.c_int(epilogue), _stream()), "mxfp4_a8_linear")
+    return out
