@@ -381,6 +381,41 @@ int zl_mxfp8_quantize(const uint16_t* x, int64_t ldx, uint8_t* xq /* (M,K) */, u
                       zl_stream_t s);
 int zl_mxfp4_a8_linear(const uint8_t* xq, const uint8_t* xs, const uint8_t* codes, const uint8_t* scales, const uint16_t* bias,
                        const uint16_t* residual, uint16_t* y, int64_t m, int64_t n, int64_t k, int dtype, int epilogue, zl_stream_t s);
+/* EXPERT STACKS (csrc/mxfp4_moe.hip): the routed feed-forward of MXFP4 mixture-of-experts models, T = fp16 / bf16 (dtype).
+ * THE OPERAND is the checkpoint's tensors, stacked: codes uint8 (E, N, K/2), scales uint8 (E, N, K/32) in the format above, expert e
+ *   at codes + e * expert_stride_codes / scales + e * expert_stride_scales BYTES (strides >= one expert's tensor, the code stride
+ *   % 16 == 0).  No packed copy: 0.53125 B per weight.  K % 32 == 0 is the only shape rule; x (x_rows, K) with row stride ldx (% 8 == 0),
+ *   x and codes 16-byte aligned.  ZL_EPI_SILU_MUL wants every expert's matrix row-interleaved (row 2j gate, row 2j + 1 up).
+ * zl_mxfp4_moe_grouped: ONE launch for every expert, with the rows, clamping and limits of zl_w4a16_gemm_grouped: the `pairs` sorted
+ *   positions are grouped by expert, expert e owning the run of expert_loads[e] positions after those of experts 0..e-1 (device,
+ *   num_experts int32); positions past the last run are not computed.  Position j reads x row index[j] / in_div (in_div = 0: row j),
+ *   clamped to [0, x_rows), and writes y row j (out_scatter = 0) or index[j] (out_scatter = 1); y rows outside [0, y_rows) are not
+ *   written.  y (y_rows, N) -- (y_rows, N / 2) under ZL_EPI_SILU_MUL; epilogue 0 or ZL_EPI_SILU_MUL (experts have no bias).  No host
+ *   synchronisation: the grid is sized from zl_moe_grouped_tiles(pairs, num_experts, zl_mxfp4_moe_bm(pairs, num_experts)) and every
+ *   workgroup derives its (expert, tile) from expert_loads on the device.
+ *   ROUTES (zl_mxfp4_moe_bm: the rows of a tile, from the average rows per active expert):
+ *     16 / 32  workgroup = 16 weight rows of the expert x BM sorted rows, K split over its 4 waves by quads of four blocks, folded
+ *              through LDS: an expert's weights are read once per BM of its rows (decode batches)
+ *     64       workgroup = 64 sorted rows x 64 weight rows, a wave 16 weight rows over all of K (prompts)
+ *   The gathered rows are read from x in place: an MFMA A fragment is one lane's 16-byte load through its own row pointer.
+ * zl_mxfp4_moe_pairs: the small-M form, no sort and no table -- pair j (< pairs <= 65535) multiplies x row j / in_div (in_div = 0: row
+ *   j) with expert expert_ids[j]'s matrix (an id outside the stack: row j is not written) and writes y row j (y: pairs rows).  A wave
+ *   owns two weight rows, lane l walks blocks l, l + 64, ... (the ZL_MXFP4_GEMV walk).
+ * NUMERICS: those of zl_mxfp4_linear, by the same device code -- no weight is rounded, exact products, each block's fp32 partial sum
+ *   scaled by 2^(e - 127) into the fp32 accumulator, one rounding to T; ZL_EPI_SILU_MUL: gate and up rounded to T, then T(silu(g) u).
+ *   One workgroup owns an output over all of K: no atomics, the same bits on every run.  In the grouped form a row's bits depend on
+ *   its own activation row and expert alone -- not on the rows that share its tile, its place in the tile, or the tile shape (all
+ *   three routes sum K in one order) -- so a request keeps its bits however a batch is put together.  The pairs form sums in another
+ *   order (an FMA chain per lane against MFMA partial sums): the two forms are NOT bit-equal to each other, unlike
+ *   zl_w4a16_gemm_grouped / _pairs; both keep the error bound of the MXFP4 linears. */
+int zl_mxfp4_moe_bm(int64_t pairs, int64_t num_experts);
+int zl_mxfp4_moe_grouped(const uint16_t* x, int64_t ldx, int64_t x_rows, const uint8_t* codes, const uint8_t* scales, int64_t num_experts,
+                         int64_t expert_stride_codes, int64_t expert_stride_scales, const int32_t* expert_loads, const int32_t* index,
+                         int64_t pairs, int in_div, int out_scatter, uint16_t* y, int64_t y_rows, int64_t n, int64_t k, int dtype,
+                         int epilogue, zl_stream_t s);
+int zl_mxfp4_moe_pairs(const uint16_t* x, int64_t ldx, int64_t x_rows, const uint8_t* codes, const uint8_t* scales, int64_t num_experts,
+                       int64_t expert_stride_codes, int64_t expert_stride_scales, const int32_t* expert_ids, int64_t pairs, int in_div,
+                       uint16_t* y, int64_t n, int64_t k, int dtype, int epilogue, zl_stream_t s);
 
 /* lm_head + greedy pick without a separate argmax pass over the logits: the GEMV leaves each wavefront's
  * best (rounded logit, row index) in argmax_ws (zl_argmax_workspace_bytes(m, n) bytes); zl_greedy_advance

@@ -2,6 +2,7 @@
 
     python tools/bench_mxfp4.py [--iters 100] [--no-linears] [--no-steps] [--layers 32]
     python tools/bench_mxfp4.py --act mxfp8 [--iters 100] [--layers 32]      (DESIGN 4 "MXFP8 activations", profiles/mxfp4_a8.txt)
+    python tools/bench_mxfp4.py --moe [--iters 100]                          (DESIGN 4 "MXFP4 experts", profiles/mxfp4_moe.txt)
 
 Method: hipEvent pairs around every iteration after 10 warm-ups, >= 100 iterations; the linears rotate through >= 4
 weight buffers totalling more than 256 MB, so every read of a weight comes from HBM -- an iteration is one hipGraph replay of one
@@ -16,6 +17,14 @@ launch per buffer, reported per launch (eager launches measure the host: ~14 us 
             replay, "speedup" = weight-only / (quantiser + GEMM) -- and the time to the first token of a 1024-token prompt (LLaMA.prefill,
             eager launches between two events: both ways pay the same launches but for the quantisers) on ONE model whose linears are
             switched between the routes, so both ways read the same weights
+  --moe     the routed feed-forward on MXFP4 expert stacks (DESIGN 4 "MXFP4 experts", profiles/mxfp4_moe.txt) at the Qwen3-30B-A3B
+            geometry (128 experts, top-k 8, dim_model 2048, moe_intermediate_size 768) at 1, 4, 8, 32, 512 rows.  An iteration is one
+            hipGraph replay of Mxfp4MoEEncoderLayer.moe (router, top-k, [sort,] gate|up, down, combine) on each of 16 layers (5 GB of
+            experts: the few experts a small batch touches do not stay in the caches), per layer, with the pairs form (up to 32 rows)
+            and the grouped form forced in turn -- their crossover is the layer's m_thres.  Against, in the same run: "loop", what the
+            code before these kernels could do with the same weights -- ops.mxfp4_linear per active expert over gathered rows, which
+            needs the loads on the host, so it is timed eagerly between two events, and so is layer.moe next to it ("eager") -- and
+            "gptq", MoEEncoderLayer.moe (GPTQ W4A16 experts, grouped route) at the same geometry, as replays.
 One JSON line per measurement on stdout."""
 import argparse
 import json
@@ -27,7 +36,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from zhilight_amd import ops  # noqa: E402
-from zhilight_amd.llama import LLaMA, ModelConfig, QuantConfig  # noqa: E402
+from zhilight_amd.llama import LLaMA, ModelConfig, MoEEncoderLayer, Mxfp4MoEEncoderLayer, QuantConfig  # noqa: E402
 
 HBM = 8.0e12
 LINEARS = (("qkv", 6144, 4096, 0), ("attn_out", 4096, 4096, ops.EPI_RESIDUAL), ("gate_up", 28672, 4096, ops.EPI_SILU_MUL),
@@ -148,6 +157,83 @@ def bench_act(dev, iters, layers, rows=(128, 512, 2048), prompt_len=1024):
                       "a8_ms_p50_p10_p90": [round(t * 1e3, 3) for t in a8], "speedup_p50": round(w16[0] / a8[0], 3)}), flush=True)
 
 
+def moe_loop(layer, xn):
+    """the routed feed-forward without the expert-grouped kernels: one mxfp4_linear pair per active expert over its gathered rows"""
+    c = layer.cfg
+    k = c.moe_top_k
+    weights, ids = ops.moe_top_k_softmax(ops.gemm_nt_f32(xn, layer.router), k, norm_topk_prob=c.norm_topk_prob)
+    flat = ids.reshape(-1).long()
+    order = torch.argsort(flat, stable=True)
+    counts = torch.bincount(flat, minlength=c.moe_num_experts).tolist()           # the host has to know the loads
+    down = torch.empty((flat.numel(), c.dim_model), dtype=xn.dtype, device=xn.device)
+    pos = 0
+    for e, cnt in enumerate(counts):
+        if cnt:
+            sel = order[pos:pos + cnt]
+            act = ops.mxfp4_linear(xn[sel // k], ops.Mxfp4Weight(layer.w_up.codes[e], layer.w_up.scales[e], True), epilogue=ops.EPI_SILU_MUL)
+            down[sel] = ops.mxfp4_linear(act, ops.Mxfp4Weight(layer.w_down.codes[e], layer.w_down.scales[e]))
+            pos += cnt
+    return ops.moe_sum_experts(down, ops.arange_i32(flat.numel(), xn.device), weights)
+
+
+def bench_moe(dev, iters, nbuf=16, rows=ROWS):
+    gen = torch.Generator(device=dev).manual_seed(1)
+    geo = dict(num_layers=1, dim_model=2048, num_heads=32, dim_head=128, num_kv_heads=4, dim_ff=768, model_type="qwen3_moe", qk_norm="head",
+               moe_num_experts=128, moe_top_k=8, moe_intermediate_size=768, norm_topk_prob=True)
+    e, d, ff = 128, 2048, 768
+    u8 = lambda lo, hi, *shape: torch.randint(lo, hi, shape, dtype=torch.uint8, device=dev, generator=gen)  # noqa: E731
+    router = lambda dt: (torch.randn(e, d, device=dev, generator=gen) / d ** 0.5).to(dt)  # noqa: E731
+
+    def mx_layer(dt):
+        layer = Mxfp4MoEEncoderLayer(ModelConfig(dtype=dt, **geo), QuantConfig(11, 32), 0)
+        layer.router = router(layer.cfg.torch_dtype)
+        layer.w_up = ops.Mxfp4MoEWeight(u8(0, 256, e, 2 * ff, d // 2), u8(120, 123, e, 2 * ff, d // 32), True)
+        layer.w_down = ops.Mxfp4MoEWeight(u8(0, 256, e, d, ff // 2), u8(120, 123, e, d, ff // 32))
+        return layer
+
+    def gptq_layer():
+        layer = MoEEncoderLayer(ModelConfig(**geo), QuantConfig(5, 128), 0)
+        layer.router = router(torch.float16)
+        km = lambda n, k: ([torch.randint(-2 ** 31, 2 ** 31 - 1, (n, k // 8), dtype=torch.int32, device=dev, generator=gen) for _ in range(e)],  # noqa: E731
+                           [u8(1, 16, n, k // 128) for _ in range(e)],
+                           [(torch.rand(n, k // 128, device=dev, generator=gen) * 0.01 + 1e-3).half() for _ in range(e)])
+        layer.w_up = ops.W4MMoEWeight.from_k_major(*km(2 * ff, d), 128, row_interleave=True)
+        layer.w_down = ops.W4MMoEWeight.from_k_major(*km(d, ff), 128)
+        return layer
+
+    def replay_us(layers, x):
+        for layer in layers[:2]:
+            layer.moe(x)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for layer in layers:
+                layer.moe(x)
+        return [round(t / len(layers) * 1e6, 2) for t in quantiles(timed(lambda i: graph.replay(), iters))]
+    for dt in ("half", "bfloat16"):
+        layers = [mx_layer(dt) for _ in range(nbuf)]
+        for m in rows:
+            x = torch.randn(m, d, device=dev, generator=gen).to(layers[0].cfg.torch_dtype)
+            rec = {"what": "moe", "dtype": dt, "rows": m, "pairs": m * 8, "bm": ops.mxfp4_moe_bm(m * 8, e), "buffers": nbuf}
+            for form, thres in (("pairs", 1 << 30), ("grouped", 0)):
+                if form == "grouped" or m <= 32:
+                    for layer in layers:
+                        layer.m_thres = thres
+                    rec[form + "_us_p50_p10_p90"] = replay_us(layers, x)
+            if dt == "half":
+                eager = lambda fn: [round(t * 1e6, 1) for t in quantiles(timed(lambda i: fn(layers[i % nbuf], x), iters))]  # noqa: E731
+                rec["grouped_eager_us_p50_p10_p90"] = eager(lambda layer, x: layer.moe(x))
+                rec["loop_eager_us_p50_p10_p90"] = eager(moe_loop)
+            print(json.dumps(rec), flush=True)
+        del layers
+        torch.cuda.empty_cache()
+    layers = [gptq_layer() for _ in range(nbuf)]
+    for m in rows:
+        x = torch.randn(m, d, device=dev, generator=gen).half()
+        print(json.dumps({"what": "moe_gptq", "rows": m, "route": "pairs" if m <= layers[0].m_thres else "grouped", "buffers": nbuf,
+                          "us_p50_p10_p90": replay_us(layers, x)}), flush=True)
+
+
 def bench_steps(dev, iters, layers, seq=1024):
     cfg = ModelConfig.llama3_8b()
     cfg.num_layers = layers
@@ -189,8 +275,11 @@ def main():
     ap.add_argument("--no-linears", action="store_true")
     ap.add_argument("--no-steps", action="store_true")
     ap.add_argument("--act", choices=("", "mxfp8"), default="", help="mxfp8: the A/B of the MXFP8-activation prompt route, nothing else")
+    ap.add_argument("--moe", action="store_true", help="the routed feed-forward on MXFP4 expert stacks, nothing else")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.moe:
+        return bench_moe(dev, args.iters)
     if args.act:
         return bench_act(dev, args.iters, args.layers)
     if not args.no_linears:

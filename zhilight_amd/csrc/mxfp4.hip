@@ -23,58 +23,7 @@
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-// 2^(e - 127) as fp32; byte 0 is 2^-127, an fp32 subnormal
-__device__ __forceinline__ float mx_scale_f32(uint32_t e) { return __builtin_bit_cast(float, e ? e << 23 : 0x00400000u); }
-
-// ---- E2M1 -> T, eight codes of one dword (element 2j in bits 0-3 of byte j, 2j + 1 in bits 4-7) to four packed pairs in
-// element order.  |code| indexes an 8-entry byte table through v_perm_b32; the sign bit is moved on top of it.
-// fp16: the high byte of the value is the whole value (0x00 0x38 0x3C 0x3E 0x40 0x42 0x44 0x46 = 0 .5 1 1.5 2 3 4 6)
-__device__ __forceinline__ void mx_decode8_f16(uint32_t q, uint32_t out[4]) {
-    const uint32_t lo = q & 0x07070707u, hi = (q >> 4) & 0x07070707u;
-    const uint32_t bl = __builtin_amdgcn_perm(0x46444240u, 0x3E3C3800u, lo) | ((q << 4) & 0x80808080u);   // elements 0 2 4 6
-    const uint32_t bh = __builtin_amdgcn_perm(0x46444240u, 0x3E3C3800u, hi) | (q & 0x80808080u);          // elements 1 3 5 7
-    out[0] = __builtin_amdgcn_perm(bh, bl, 0x040C000Cu);
-    out[1] = __builtin_amdgcn_perm(bh, bl, 0x050C010Cu);
-    out[2] = __builtin_amdgcn_perm(bh, bl, 0x060C020Cu);
-    out[3] = __builtin_amdgcn_perm(bh, bl, 0x070C030Cu);
-}
-// bf16: two bytes per value (0 3F00 3F80 3FC0 4000 4040 4080 40C0)
-__device__ __forceinline__ void mx_decode8_bf16(uint32_t q, uint32_t out[4]) {
-    const uint32_t lo = q & 0x07070707u, hi = (q >> 4) & 0x07070707u;
-    const uint32_t hl = __builtin_amdgcn_perm(0x40404040u, 0x3F3F3F00u, lo) | ((q << 4) & 0x80808080u);
-    const uint32_t hh = __builtin_amdgcn_perm(0x40404040u, 0x3F3F3F00u, hi) | (q & 0x80808080u);
-    const uint32_t ll = __builtin_amdgcn_perm(0xC0804000u, 0xC0800000u, lo);
-    const uint32_t lh = __builtin_amdgcn_perm(0xC0804000u, 0xC0800000u, hi);
-    const uint32_t e02 = __builtin_amdgcn_perm(hl, ll, 0x05010400u), e46 = __builtin_amdgcn_perm(hl, ll, 0x07030602u);   // (e0, e2), (e4, e6)
-    const uint32_t e13 = __builtin_amdgcn_perm(hh, lh, 0x05010400u), e57 = __builtin_amdgcn_perm(hh, lh, 0x07030602u);   // (e1, e3), (e5, e7)
-    out[0] = __builtin_amdgcn_perm(e13, e02, 0x05040100u);
-    out[1] = __builtin_amdgcn_perm(e13, e02, 0x07060302u);
-    out[2] = __builtin_amdgcn_perm(e57, e46, 0x05040100u);
-    out[3] = __builtin_amdgcn_perm(e57, e46, 0x07060302u);
-}
-
-template <int DT>
-__device__ __forceinline__ f4 mx_mfma(uint4 a, uint4 b, f4 c) {
-    if constexpr (DT == ZL_F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
-}
-
-template <int DT>
-__device__ __forceinline__ float mx_x_lo(uint32_t pair) {
-    if constexpr (DT == ZL_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(pair & 0xffffu));
-    else return __builtin_bit_cast(float, pair << 16);
-}
-template <int DT>
-__device__ __forceinline__ float mx_x_hi(uint32_t pair) {
-    if constexpr (DT == ZL_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(pair >> 16));
-    else return __builtin_bit_cast(float, pair & 0xffff0000u);
-}
+typedef mx_f4 f4;
 
 // ---- 1..4 rows ------------------------------------------------------------------------------------------------------------
 constexpr int kGW = 4;          // waves per workgroup; a wave owns weight rows 2 w, 2 w + 1
@@ -95,58 +44,7 @@ __global__ __launch_bounds__(kGW * 64) void k_mxfp4_gemv(const Mx4Params p) {
     float acc[2][MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[0][m] = acc[1][m] = 0.f;
-
-    // the weights of the lane's next block are asked for before this one is consumed
-    uint4 q0n = make_uint4(0, 0, 0, 0), q1n = q0n;
-    uint32_t e0n = 0, e1n = 0;
-    if (lane < p.nb) {
-        q0n = zl_load_nt(c0 + lane); q1n = zl_load_nt(c1 + lane);
-        e0n = s0[lane]; e1n = s1[lane];
-    }
-#pragma unroll 1
-    for (int b = lane; b < p.nb; b += 64) {
-        const uint4 q0 = q0n, q1 = q1n;
-        const float f0 = mx_scale_f32(e0n), f1 = mx_scale_f32(e1n);
-        if (b + 64 < p.nb) {
-            q0n = zl_load_nt(c0 + b + 64); q1n = zl_load_nt(c1 + b + 64);
-            e0n = s0[b + 64]; e1n = s1[b + 64];
-        }
-        uint4 xv[MT][4];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const uint4* xp = reinterpret_cast<const uint4*>(p.x + (size_t)m * p.ldx + (size_t)b * 32);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) xv[m][t] = xp[t];
-        }
-        float part[2][MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) part[0][m] = part[1][m] = 0.f;
-        const uint32_t qq[2][4] = {{q0.x, q0.y, q0.z, q0.w}, {q1.x, q1.y, q1.z, q1.w}};
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                uint32_t w[4];
-                mx_decode8_f16(qq[r][t], w);
-#pragma unroll
-                for (int m = 0; m < MT; ++m) {
-                    const uint32_t xs[4] = {xv[m][t].x, xv[m][t].y, xv[m][t].z, xv[m][t].w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float wl = (float)__builtin_bit_cast(_Float16, (uint16_t)(w[i] & 0xffffu));
-                        const float wh = (float)__builtin_bit_cast(_Float16, (uint16_t)(w[i] >> 16));
-                        part[r][m] = __builtin_fmaf(wl, mx_x_lo<DT>(xs[i]), part[r][m]);
-                        part[r][m] = __builtin_fmaf(wh, mx_x_hi<DT>(xs[i]), part[r][m]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            acc[0][m] = __builtin_fmaf(part[0][m], f0, acc[0][m]);
-            acc[1][m] = __builtin_fmaf(part[1][m], f1, acc[1][m]);
-        }
-    }
+    mx_gemv_run<DT, MT>(p.nb, c0, c1, s0, s1, p.x, p.ldx, lane, acc);
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
         acc[0][m] = zl_wave_sum(acc[0][m]);
@@ -156,88 +54,17 @@ __global__ __launch_bounds__(kGW * 64) void k_mxfp4_gemv(const Mx4Params p) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             if (p.epi & ZL_EPI_SILU_MUL) {
-                mx_store_gated<DT>(p, m, n0 / 2, acc[0][m], acc[1][m]);       // n is even: the wave holds the pair
+                mx_store_gated<DT>(p, m, p.n / 2, n0 / 2, acc[0][m], acc[1][m]);       // n is even: the wave holds the pair
             } else {
-                mx_store_plain<DT>(p, m, n0, acc[0][m]);
-                if (two) mx_store_plain<DT>(p, m, n1, acc[1][m]);
+                mx_store_plain<DT>(p, m, p.n, n0, acc[0][m]);
+                if (two) mx_store_plain<DT>(p, m, p.n, n1, acc[1][m]);
             }
         }
     }
 }
 
 // ---- the matrix-core kernels ----------------------------------------------------------------------------------------------
-// One 32-element block of 16 weight rows against MT x 16 activation rows: lane (nrow = lane % 16, kq = lane / 16) needs codes
-// 8 kq .. 8 kq + 7 of row n (one dword) as its B fragment and x[row nrow of the tile][the same k] (16 B) as its A fragment; the
-// product lands as D[row 4 kq + i][column nrow], i.e. one weight row and therefore one scale per lane.
-// mx_run walks QUADS of four consecutive blocks, q0, q0 + step, ...: lane (nrow, kq) loads the whole block 4 quad + kq of its row
-// (16 B: a wave instruction covers 64 contiguous bytes of each of 16 rows), and a 4 x 4 transposition between the four 16-lane
-// groups -- v_permlane32_swap on registers (0, 2), (1, 3), then v_permlane16_swap on (0, 1), (2, 3) -- leaves in register b the
-// lane's dword of block 4 quad + b: its B fragment.  The operands of the next PF quads are in flight (a ring of PF register slots,
-// static indices); blocks past the last one hold zeros, which add an exact 0.
-__device__ __forceinline__ void mx_transpose4(uint32_t (&r)[4]) {
-    auto s02 = __builtin_amdgcn_permlane32_swap(r[0], r[2], false, false);
-    auto s13 = __builtin_amdgcn_permlane32_swap(r[1], r[3], false, false);
-    auto t01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
-    auto t23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
-    r[0] = t01[0]; r[1] = t01[1]; r[2] = t23[0]; r[3] = t23[1];
-}
-
-template <int DT, int MT, int PF>
-__device__ __forceinline__ void mx_run(const Mx4Params& p, const uint32_t* __restrict__ crow, const uint8_t* __restrict__ srow, int q0, int step,
-                                       const uint16_t* (&xrow)[MT], bool (&live)[MT], int kq, f4 (&acc)[MT]) {
-    const int nq = (p.nb + 3) >> 2;
-    uint4 q[PF];
-    uint32_t e[PF][4];
-    uint4 a[PF][4][MT];
-    auto load = [&](int slot, int quad) {
-        q[slot] = make_uint4(0, 0, 0, 0);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            e[slot][g] = 0;
-#pragma unroll
-            for (int t = 0; t < MT; ++t) a[slot][g][t] = make_uint4(0, 0, 0, 0);
-        }
-        if (quad < nq) {
-            if (4 * quad + kq < p.nb) q[slot] = zl_load_nt(reinterpret_cast<const uint4*>(crow) + 4 * quad + kq);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int b = 4 * quad + g;
-                if (b < p.nb) {
-                    e[slot][g] = srow[b];
-#pragma unroll
-                    for (int t = 0; t < MT; ++t)
-                        if (live[t]) a[slot][g][t] = *reinterpret_cast<const uint4*>(xrow[t] + (size_t)b * 32 + kq * 8);
-                }
-            }
-        }
-    };
-#pragma unroll
-    for (int u = 0; u < PF; ++u) load(u, q0 + u * step);
-#pragma unroll 1
-    for (int quad = q0; quad < nq; quad += PF * step) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            uint32_t frag[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-            mx_transpose4(frag);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float f = mx_scale_f32(e[u][g]);
-                uint32_t w[4];
-                if constexpr (DT == ZL_F16) mx_decode8_f16(frag[g], w);
-                else mx_decode8_bf16(frag[g], w);
-                const uint4 bf = make_uint4(w[0], w[1], w[2], w[3]);
-#pragma unroll
-                for (int t = 0; t < MT; ++t) {
-                    const f4 part = mx_mfma<DT>(a[u][g][t], bf, (f4){0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[t][i] = __builtin_fmaf(part[i], f, acc[t][i]);
-                }
-            }
-            load(u, quad + (u + PF) * step);
-        }
-    }
-}
-
+// (zl_mxfp4.h: mx_run has the fragment maps, the quad walk and the operand ring)
 template <int DT, int MT>
 __global__ __launch_bounds__(256) void k_mxfp4_stream(const Mx4Params p) {
     __shared__ float red[3][MT * 4][64];

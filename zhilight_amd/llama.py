@@ -124,7 +124,8 @@ class QuantConfig:
     quant_type 11 = MXFP4 (OCP microscaled FP4 weights, group_size 32; outside the reference's enum 0-10): Mxfp4EncoderLayer.
     `act_quant` (type 11 only; set by the caller, never by from_hf): "" = weight-only, activations stay fp16 / bf16; "mxfp8" = linears
     over more than MXFP4_A8_ABOVE_ROWS rows quantise their input to OCP MXFP8 and run on the scaled MFMA (ops.mxfp4_a8_linear) --
-    prompt encode gets faster and its activations carry an E4M3 rounding; decode steps are untouched."""
+    prompt encode gets faster and its activations carry an E4M3 rounding; decode steps are untouched.  In an MoE model
+    (Mxfp4MoEEncoderLayer) the q|k|v and attn_out linears follow act_quant; the EXPERTS stay weight-only at every row count."""
     quant_type: int = 5
     group_size: int = 128
     sym: bool = False
@@ -710,7 +711,8 @@ class Mxfp4EncoderLayer:
         self.cfg, self.quant, self.idx = cfg, quant, idx
         self.unfused = None
 
-    def load_state_dict(self, sd, prefix, device):
+    def load_state_dict(self, sd, prefix, device, ff=True):
+        """ff=False: the attention half and both norms only (Mxfp4MoEEncoderLayer loads its own feed-forward)"""
         c, dt = self.cfg, self.cfg.torch_dtype
         hd, kvd = c.num_heads * c.dim_head, c.num_kv_heads * c.dim_head
         self.ln_attn = _dev_t(sd[prefix + ".ln_attn.weight"], device).to(dt)
@@ -720,16 +722,17 @@ class Mxfp4EncoderLayer:
                                     [lin("attn.project_q", c.dim_model, hd), lin("attn.project_k", c.dim_model, kvd),
                                      lin("attn.project_v", c.dim_model, kvd)])
         self.attn_out = lin("attn.attn_out", hd, c.dim_model)
-        self.w_in_gated = Mxfp4Linear.fuse(prefix + ".ff.w_in_gated", [lin("ff.w_in", c.dim_model, c.dim_ff),
-                                                                      lin("ff.w_gated", c.dim_model, c.dim_ff)], row_interleave=True)
-        self.w_out = lin("ff.w_out", c.dim_ff, c.dim_model)
+        if ff:
+            self.w_in_gated = Mxfp4Linear.fuse(prefix + ".ff.w_in_gated", [lin("ff.w_in", c.dim_model, c.dim_ff),
+                                                                          lin("ff.w_gated", c.dim_model, c.dim_ff)], row_interleave=True)
+            self.w_out = lin("ff.w_out", c.dim_ff, c.dim_model)
         self._set_act_quant()
 
     def _set_act_quant(self):
         for l in self.linears():
             l.act_quant = self.quant.act_quant
 
-    def init_random(self, device, gen):
+    def init_random(self, device, gen, ff=True):
         """weights quantised (ops.mxfp4_quantize) from N(0, 1 / sqrt(K)) / 4"""
         c, dt = self.cfg, self.cfg.torch_dtype
         hd, kvd = c.num_heads * c.dim_head, c.num_kv_heads * c.dim_head
@@ -737,8 +740,9 @@ class Mxfp4EncoderLayer:
         self.ln_ff = (1.0 + 0.05 * torch.randn(c.dim_model, device=device, generator=gen)).to(dt)
         self.qkv = Mxfp4Linear.random("qkv", c.dim_model, hd + 2 * kvd, device, gen)
         self.attn_out = Mxfp4Linear.random("attn_out", hd, c.dim_model, device, gen)
-        self.w_in_gated = Mxfp4Linear.random("w_in_gated", c.dim_model, 2 * c.dim_ff, device, gen, row_interleave=True)
-        self.w_out = Mxfp4Linear.random("w_out", c.dim_ff, c.dim_model, device, gen)
+        if ff:
+            self.w_in_gated = Mxfp4Linear.random("w_in_gated", c.dim_model, 2 * c.dim_ff, device, gen, row_interleave=True)
+            self.w_out = Mxfp4Linear.random("w_out", c.dim_ff, c.dim_model, device, gen)
         self._set_act_quant()
 
     def linears(self):
@@ -759,6 +763,105 @@ class Mxfp4EncoderLayer:
             act_buf = None
         act = self.w_in_gated.forward(ops.rmsnorm(hidden, self.ln_ff, eps), out=act_buf, epilogue=ops.EPI_SILU_MUL)
         self.w_out.forward(act, residual=hidden, out=hidden)
+
+
+# rows up to which Mxfp4MoEEncoderLayer takes the pairs form: the measured crossover (tools/bench_mxfp4.py --moe, profiles/mxfp4_moe.txt:
+# the pairs form 1.4 - 1.7 x faster up to 8 rows, level in fp16 and behind in bf16 at 32; DESIGN 4, "MXFP4 experts")
+_MXFP4_MOE_M_THRES_DEFAULT = "8"
+
+
+class Mxfp4MoEEncoderLayer(Mxfp4EncoderLayer):
+    """Mxfp4EncoderLayer with a routed mixture-of-experts feed-forward on MXFP4 expert stacks (Qwen3-MoE; quant type 11): the
+    attention half and both norms are Mxfp4EncoderLayer's, ln_ff + router + experts replace w_in_gated / w_out.  The router is
+    Qwen3-MoE's (fp32 logits, softmax, top-k, renormalised with norm_topk_prob); the experts are two stacks of checkpoint tensors
+    (ops.Mxfp4MoEWeight: gate|up row-interleaved per expert, down) and run in ONE launch per projection whatever the number of
+    active experts.  Weight-only at every row count: QuantConfig.act_quant reaches q|k|v and attn_out, not the experts.  Not with
+    tensor or expert parallelism or shared experts (ZLError)."""
+
+    def __init__(self, cfg: ModelConfig, quant: QuantConfig, idx: int):
+        if cfg.model_type != "qwen3_moe":
+            # the routing rule and the plain swiglu below are Qwen3-MoE's (gpt-oss, say, needs sinks, a clamped swiglu, expert biases)
+            raise ops.ZLError(f"MXFP4 models: MoE layers of model_type 'qwen3_moe' only (got {cfg.model_type!r})")
+        if os.environ.get("MOE_EXP_PARALLEL", "0") not in ("", "0"):
+            raise ops.ZLError("MXFP4 models: MoE layers: expert parallelism is not supported")
+        if cfg.dim_model % 32 or cfg.moe_intermediate_size % 32:
+            raise ops.ZLError("MXFP4 models: MoE layers: dim_model and moe_intermediate_size are multiples of 32")
+        if not (0 < cfg.moe_top_k <= min(32, cfg.moe_num_experts)):
+            raise ops.ZLError("MXFP4 models: MoE layers: 1 <= num_experts_per_tok <= min(32, num_experts)")
+        super().__init__(cfg, quant, idx)
+        # rows up to this take the pairs form (MXFP4_MOE_M_THRES, read at load)
+        self.m_thres = int(os.environ.get("MXFP4_MOE_M_THRES", _MXFP4_MOE_M_THRES_DEFAULT) or 0)
+        self.router = self.w_up = self.w_down = None
+        self.last_route = None
+
+    def load_state_dict(self, sd, prefix, device):
+        c = self.cfg
+        if any(k.startswith(prefix + ".ff.shared_expert") for k in sd):
+            raise ops.ZLError(f"{prefix}: shared experts are not supported")
+        super().load_state_dict(sd, prefix, device, ff=False)      # ln_attn, ln_ff, fused q|k|v, attn_out
+        router = sd[prefix + ".ff.router.weight"]
+        if tuple(router.shape) != (c.moe_num_experts, c.dim_model):
+            raise ops.ZLError(f"{prefix}: router weight shape {tuple(router.shape)} != {(c.moe_num_experts, c.dim_model)}")
+        self.router = _dev_t(router, device).to(c.torch_dtype).contiguous()
+        ff = c.moe_intermediate_size
+
+        def expert(name, n, k):                                     # either spelling -> (codes (n, k / 2), scales (n, k / 32)) on the device
+            codes, scales, bias = mxfp4_tensors(sd, name)
+            if bias is not None:
+                raise ops.ZLError(f"{name}: expert biases are not supported")
+            if tuple(codes.shape) != (n, k // 2) or tuple(scales.shape) != (n, k // 32):
+                raise ops.ZLError(f"{name}: codes {tuple(codes.shape)} / scales {tuple(scales.shape)} do not fit a ({n}, {k}) MXFP4 weight")
+            return _dev_t(codes, device), _dev_t(scales, device)
+        up, down = ([], []), ([], [])
+        for e in range(c.moe_num_experts):
+            g, u = (expert(f"{prefix}.ff.experts.{e}.{nm}", ff, c.dim_model) for nm in ("w_in", "w_gated"))
+            d = expert(f"{prefix}.ff.experts.{e}.w_out", c.dim_model, ff)
+            for j in range(2):
+                up[j].append(torch.cat([g[j], u[j]]))
+                down[j].append(d[j])
+        self.w_up = ops.Mxfp4MoEWeight.from_checkpoint(*up, row_interleave=True)
+        self.w_down = ops.Mxfp4MoEWeight.from_checkpoint(*down)
+
+    def init_random(self, device, gen):
+        """the attention half as Mxfp4EncoderLayer's; expert weights quantised from N(0, 1 / sqrt(K)) / 4, router rows
+        N(0, 1) / sqrt(dim_model): logits O(1), so the top-k picks spread over the experts"""
+        c = self.cfg
+        super().init_random(device, gen, ff=False)
+        e, ff = c.moe_num_experts, c.moe_intermediate_size
+        self.router = (torch.randn(e, c.dim_model, device=device, generator=gen) / math.sqrt(c.dim_model)).to(c.torch_dtype)
+        self.w_up = ops.Mxfp4MoEWeight.random(e, 2 * ff, c.dim_model, device, gen, std=0.25 / math.sqrt(c.dim_model), row_interleave=True)
+        self.w_down = ops.Mxfp4MoEWeight.random(e, c.dim_model, ff, device, gen, std=0.25 / math.sqrt(ff))
+
+    def linears(self):
+        return [self.qkv, self.attn_out]
+
+    def weight_bytes(self):
+        return sum(l.nbytes() for l in self.linears()) + self.w_up.nbytes() + self.w_down.nbytes() + self.router.numel() * 2
+
+    def moe(self, xn):
+        """the routed feed-forward of normalised rows xn (T, dim_model) -> (T, dim_model), both of the model's dtype"""
+        c = self.cfg
+        t, e, k = xn.shape[0], c.moe_num_experts, c.moe_top_k
+        logits = ops.gemm_nt_f32(xn, self.router)
+        loads = torch.zeros(e + 1, dtype=torch.int32, device=xn.device)       # tokens per expert | per worker (one)
+        weights, ids = ops.moe_top_k_softmax(logits, k, norm_topk_prob=c.norm_topk_prob, worker_load=loads[e:], expert_load=loads[:e])
+        self.last_route = (ids, weights)                                        # (tests: the routing the step took)
+        p = t * k
+        pair = ops.arange_i32(p, xn.device)
+        if t <= self.m_thres:
+            # a few rows: one GEMV per (token, slot) pair straight from the routing ids, pair order throughout
+            act = ops.mxfp4_moe_pairs(xn, self.w_up, ids, in_div=k, epilogue=ops.EPI_SILU_MUL)
+            return ops.moe_sum_experts(ops.mxfp4_moe_pairs(act, self.w_down, ids), pair, weights)
+        # the pairs sorted by expert on the device (stable), gate|up over the tokens gathered in place, down scattered back to pair
+        # order, then the weighted combine: every output row sums its k slots in order
+        _, order = ops.sort_pairs_i32(ids.reshape(-1), pair, max_key=e)
+        act = ops.mxfp4_moe_grouped(xn, self.w_up, loads[:e], order, p, in_div=k, epilogue=ops.EPI_SILU_MUL)
+        down = ops.mxfp4_moe_grouped(act, self.w_down, loads[:e], order, p, out_scatter=True)
+        return ops.moe_sum_experts(down, pair, weights)
+
+    def ff_add(self, hidden, eps, act_buf=None):
+        """hidden += moe(ln_ff(hidden)) in place (the residual add in T arithmetic)"""
+        ops.element_add_scale(hidden, self.moe(ops.rmsnorm(hidden, self.ln_ff, eps)), 1.0, True, out=hidden)
 
 
 # decode attention with the split merge inside its launch (zl_decode_attn_la): default of the ZL_ATTN_LA switch
@@ -1412,9 +1515,10 @@ class LLaMA:
                 raise ops.ZLError("MXFP4: the block size is 32")
             if self.tp:
                 raise ops.ZLError("MXFP4 models: tensor parallelism is not supported")
-            if self.moe:
-                raise ops.ZLError("MXFP4 models: MoE layers are not supported")
-        if self.moe:
+            # MoE layers (Qwen3-MoE only; Mxfp4MoEEncoderLayer refuses the rest) next to the dense ones of mlp_only_layers
+            self.layers = [Mxfp4MoEEncoderLayer(cfg, quant, i) if cfg.is_moe_layer(i) else Mxfp4EncoderLayer(cfg, quant, i)
+                           for i in range(cfg.num_layers)]
+        elif self.moe:
             # MoE models: the W4 route without tensor / expert parallelism (MoEEncoderLayer refuses the rest); the dense layers a
             # model lists in mlp_only_layers stay EncoderLayer
             if self.tp:

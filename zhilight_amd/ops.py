@@ -3595,3 +3595,121 @@ def mxfp4_a8_linear(xq, xs, w: Mxfp4Weight, dtype, bias=None, residual=None, out
     check(lib().zl_mxfp4_a8_linear(_p(xq), _p(xs), _p(w.codes), _p(w.scales), _p(bias), _p(residual), _p(out), _i(m), _i(w.n), _i(k),
                                    C.c_int(_dt(out)), C.c_int(epilogue), _stream()), "mxfp4_a8_linear")
     return out
+
+
+# ---- MXFP4 expert stacks (include/zhilight_amd.h "MXFP4", EXPERT STACKS; csrc/mxfp4_moe.hip) -------------------------------------
+class Mxfp4MoEWeight:
+    """The experts of one MoE projection as MXFP4 checkpoint tensors, stacked: codes uint8 (E, N, K/2), scales uint8 (E, N, K/32) --
+    what zl_mxfp4_moe_grouped / _pairs read, 0.53125 B per weight, no packed copy.  row_interleave is applied per expert as in
+    Mxfp4Weight: every expert's [gate; up] matrix becomes (gate_j, up_j) row pairs for the silu*mul epilogue."""
+
+    def __init__(self, codes, scales, row_interleave=False):
+        self.codes, self.scales, self.row_interleave = codes, scales, bool(row_interleave)
+        self.experts, self.n, self.k = codes.shape[0], codes.shape[1], codes.shape[2] * 2
+        self.stride_bytes = (codes.stride(0), scales.stride(0))
+
+    @classmethod
+    def from_checkpoint(cls, codes, scales, row_interleave=False):
+        """codes / scales: lists with one (N, K/2) or (N, K/32, 16) / (N, K/32) uint8 CUDA tensor per expert, or the stacked
+        (E, N, K/2) or (E, N, K/32, 16) / (E, N, K/32) tensors.  Refuses a scale byte 255 (the format's NaN) with one host-side check."""
+        if isinstance(codes, (list, tuple)):
+            if not codes or len(codes) != len(scales) or any(c.shape != codes[0].shape for c in codes) or any(s.shape != scales[0].shape for s in scales):
+                raise ZLError("Mxfp4MoEWeight: one codes and one scales tensor per expert, every expert of the same shape")
+            codes, scales = torch.stack(list(codes)), torch.stack(list(scales))
+        if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or not (codes.is_cuda and scales.is_cuda):
+            raise ZLError("Mxfp4MoEWeight: codes and scales are uint8 CUDA tensors")
+        if codes.dim() == 4:
+            codes = codes.reshape(codes.shape[0], codes.shape[1], -1)
+        if (codes.dim() != 3 or scales.dim() != 3 or codes.shape[2] % 16 != 0 or scales.shape[:2] != codes.shape[:2]
+                or scales.shape[2] * 16 != codes.shape[2]):
+            raise ZLError(f"Mxfp4MoEWeight: codes {tuple(codes.shape)} / scales {tuple(scales.shape)} are not (E, N, K/2) / (E, N, K/32)")
+        if bool((scales == 255).any()):
+            raise ZLError("Mxfp4MoEWeight: scale byte 255 (the E8M0 NaN) in the checkpoint")
+        if row_interleave:
+            n = codes.shape[1]
+            if n % 2:
+                raise ZLError("Mxfp4MoEWeight: row_interleave needs an even row count")
+            idx = torch.arange(n, device=codes.device).view(2, n // 2).t().reshape(-1)
+            codes, scales = codes[:, idx], scales[:, idx]
+        return cls(codes.contiguous(), scales.contiguous(), row_interleave)
+
+    @classmethod
+    def random(cls, experts, n, k, device, gen=None, std=0.05, row_interleave=False):
+        codes, scales = mxfp4_quantize(torch.randn(experts * n, k, device=device, generator=gen) * std)
+        return cls.from_checkpoint(codes.view(experts, n, k // 2), scales.view(experts, n, k // MXFP4_BLOCK), row_interleave)
+
+    def nbytes(self):
+        return self.codes.numel() + self.scales.numel()
+
+    def dequantize(self, e, dtype=torch.float16):
+        """expert e's matrix (N, K) as stored (row-interleaved if the stack is)"""
+        return mxfp4_dequantize(self.codes[e], self.scales[e], dtype)
+
+
+def mxfp4_moe_bm(pairs, num_experts):
+    """rows per tile of a zl_mxfp4_moe_grouped launch over `pairs` sorted rows: 16, 32 (K split over the workgroup's waves) or 64"""
+    return int(lib().zl_mxfp4_moe_bm(_i(pairs), _i(num_experts)))
+
+
+def _mxfp4_moe_args(what, x, w, epilogue):
+    if not x.is_cuda or x.dtype not in (torch.float16, torch.bfloat16) or x.dim() != 2:
+        raise ZLError(f"{what}: (rows, K) fp16 / bf16 CUDA activations")
+    if x.shape[1] != w.k or x.stride(1) != 1:
+        raise ZLError(f"{what}: size K mismatch")
+    if x.shape[0] > 1 and x.stride(0) < w.k:
+        raise ZLError(f"{what}: overlapping rows")
+    if epilogue not in (0, EPI_SILU_MUL) or (epilogue and not w.row_interleave):
+        raise ZLError(f"{what}: epilogue 0, or the silu*mul of a row-interleaved gate|up stack")
+    return w.n // 2 if epilogue else w.n
+
+
+def mxfp4_moe_grouped(x, w: Mxfp4MoEWeight, expert_loads, index, pairs, in_div=0, out_scatter=False, out=None, out_rows=None,
+                      epilogue=0):
+    """zl_mxfp4_moe_grouped: every expert's MXFP4 matrix times its sorted rows in one launch, T = x.dtype.  Sorted position j (< pairs)
+    reads x row index[j] // in_div (in_div = 0: row j) and writes out row j (out_scatter: row index[j]); expert e owns the
+    expert_loads[e] positions after those of experts < e.  out: (out_rows or pairs, n) -- n / 2 columns with EPI_SILU_MUL.  A row's bits
+    do not depend on the rows it shares a launch with."""
+    n_out = _mxfp4_moe_args("mxfp4_moe_grouped", x, w, epilogue)
+    _chk_cuda(expert_loads, index)
+    if expert_loads.dtype != torch.int32 or expert_loads.numel() != w.experts:
+        raise ZLError("mxfp4_moe_grouped: expert_loads is one int32 per expert of the stack")
+    if index is not None and (index.dtype != torch.int32 or index.numel() < pairs):
+        raise ZLError("mxfp4_moe_grouped: index holds pairs int32")
+    if index is None and (in_div or out_scatter):
+        raise ZLError("mxfp4_moe_grouped: gathering or scattering rows needs the index")
+    rows = out_rows if out_rows is not None else pairs
+    if out is None:
+        out = torch.empty((rows, n_out), dtype=x.dtype, device=x.device)
+    else:
+        _chk_out(out, rows, n_out, x.dtype, x.device, "mxfp4_moe_grouped")
+    if pairs == 0:
+        return out
+    sc, ss = w.stride_bytes
+    check(lib().zl_mxfp4_moe_grouped(_p(x), _i(x.stride(0)), _i(x.shape[0]), _p(w.codes), _p(w.scales), _i(w.experts), _i(sc), _i(ss),
+                                     _p(expert_loads), _p(index), _i(pairs), C.c_int(int(in_div)), C.c_int(int(bool(out_scatter))),
+                                     _p(out), _i(rows), _i(w.n), _i(w.k), C.c_int(_dt(x)), C.c_int(epilogue), _stream()),
+          "mxfp4_moe_grouped")
+    return out
+
+
+def mxfp4_moe_pairs(x, w: Mxfp4MoEWeight, expert_ids, in_div=0, out=None, epilogue=0):
+    """zl_mxfp4_moe_pairs, the small-M form of mxfp4_moe_grouped: pair j of expert_ids (any shape, flattened) multiplies x row
+    j // in_div (in_div = 0: row j) with its expert's matrix -> out row j.  Inside the grouped form's error bound, not its bits."""
+    n_out = _mxfp4_moe_args("mxfp4_moe_pairs", x, w, epilogue)
+    _chk_cuda(expert_ids)
+    if expert_ids.dtype != torch.int32:
+        raise ZLError("mxfp4_moe_pairs: int32 expert ids")
+    p = expert_ids.numel()
+    if p > 65535:
+        raise ZLError("mxfp4_moe_pairs: at most 65535 pairs")
+    if out is None:
+        out = torch.empty((p, n_out), dtype=x.dtype, device=x.device)
+    else:
+        _chk_out(out, p, n_out, x.dtype, x.device, "mxfp4_moe_pairs")
+    if p == 0:
+        return out
+    sc, ss = w.stride_bytes
+    check(lib().zl_mxfp4_moe_pairs(_p(x), _i(x.stride(0)), _i(x.shape[0]), _p(w.codes), _p(w.scales), _i(w.experts), _i(sc), _i(ss),
+                                   _p(expert_ids), _i(p), C.c_int(int(in_div)), _p(out), _i(w.n), _i(w.k), C.c_int(_dt(x)),
+                                   C.c_int(epilogue), _stream()), "mxfp4_moe_pairs")
+    return out
