@@ -3,6 +3,7 @@
     python tools/bench_mxfp4.py [--iters 100] [--no-linears] [--no-steps] [--layers 32]
     python tools/bench_mxfp4.py --act mxfp8 [--iters 100] [--layers 32]      (DESIGN 4 "MXFP8 activations", profiles/mxfp4_a8.txt)
     python tools/bench_mxfp4.py --moe [--iters 100]                          (DESIGN 4 "MXFP4 experts", profiles/mxfp4_moe.txt)
+    python tools/bench_mxfp4.py --moe --act mxfp8 [--iters 100]              (DESIGN 4 "MXFP8 activations for the experts", profiles/mxfp4_moe_a8.txt)
 
 Method: hipEvent pairs around every iteration after 10 warm-ups, >= 100 iterations; the linears rotate through >= 4
 weight buffers totalling more than 256 MB, so every read of a weight comes from HBM -- an iteration is one hipGraph replay of one
@@ -25,6 +26,10 @@ launch per buffer, reported per launch (eager launches measure the host: ~14 us 
             code before these kernels could do with the same weights -- ops.mxfp4_linear per active expert over gathered rows, which
             needs the loads on the host, so it is timed eagerly between two events, and so is layer.moe next to it ("eager") -- and
             "gptq", MoEEncoderLayer.moe (GPTQ W4A16 experts, grouped route) at the same geometry, as replays.
+  --moe --act mxfp8  the same layers and replays at 64, 128, 512, 2048 rows with the grouped form forced: the weight-only experts
+            (ops.mxfp4_moe_grouped) against the MXFP8 route (two ops.mxfp8_quantize + two ops.mxfp4_moe_a8_grouped), alternating in one
+            process on the same weights in four rounds; "ratio" = weight-only / MXFP8 over the replays paired in order; "quantise" = a
+            replay of the route's two quantiser launches alone and their share of the MXFP8 route's median.
 One JSON line per measurement on stdout."""
 import argparse
 import json
@@ -234,6 +239,56 @@ def bench_moe(dev, iters, nbuf=16, rows=ROWS):
                           "us_p50_p10_p90": replay_us(layers, x)}), flush=True)
 
 
+def bench_moe_act(dev, iters, nbuf=16, rows=(64, 128, 512, 2048)):
+    gen = torch.Generator(device=dev).manual_seed(1)
+    e, d, ff, k = 128, 2048, 768, 8
+    geo = dict(num_layers=1, dim_model=d, num_heads=32, dim_head=128, num_kv_heads=4, dim_ff=ff, model_type="qwen3_moe", qk_norm="head",
+               moe_num_experts=e, moe_top_k=k, moe_intermediate_size=ff, norm_topk_prob=True)
+    u8 = lambda lo, hi, *shape: torch.randint(lo, hi, shape, dtype=torch.uint8, device=dev, generator=gen)  # noqa: E731
+    us = lambda ts, n: [round(t / n * 1e6, 2) for t in quantiles(ts)]  # noqa: E731
+    for dt in ("half", "bfloat16"):
+        layers = []
+        for _ in range(nbuf):
+            layer = Mxfp4MoEEncoderLayer(ModelConfig(dtype=dt, **geo), QuantConfig(11, 32, act_quant="mxfp8"), 0)
+            layer.m_thres = 0                                      # the grouped form at every row count
+            layer.router = (torch.randn(e, d, device=dev, generator=gen) / d ** 0.5).to(layer.cfg.torch_dtype)
+            layer.w_up = ops.Mxfp4MoEWeight(u8(0, 256, e, 2 * ff, d // 2), u8(120, 123, e, 2 * ff, d // 32), True)
+            layer.w_down = ops.Mxfp4MoEWeight(u8(0, 256, e, d, ff // 2), u8(120, 123, e, d, ff // 32))
+            layers.append(layer)
+        for m in rows:
+            x = torch.randn(m, d, device=dev, generator=gen).to(layers[0].cfg.torch_dtype)
+            act = torch.randn(m * k, ff, device=dev, generator=gen).to(x.dtype)
+
+            def quantise(layer):
+                ops.mxfp8_quantize(x)
+                ops.mxfp8_quantize(act)
+            legs = {"weight_only": (1 << 30, lambda layer: layer.moe(x)), "a8": (32, lambda layer: layer.moe(x)), "quantise": (32, quantise)}
+            graphs = {}
+            for leg, (above, run) in legs.items():
+                for layer in layers:
+                    layer.a8_above_rows = above
+                run(layers[0])
+                torch.cuda.synchronize()
+                graphs[leg] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[leg]):
+                    for layer in layers:
+                        run(layer)
+            times = {leg: [] for leg in legs}
+            for _ in range(4):                                     # alternate the legs: four rounds of iters / 4 replays each
+                for leg, g in graphs.items():
+                    times[leg] += timed(lambda i: g.replay(), max(1, iters // 4), warmup=3)
+            del graphs
+            ratio = quantiles([a / b for a, b in zip(times["weight_only"], times["a8"])])
+            w16, a8, qt = (us(times[leg], nbuf) for leg in ("weight_only", "a8", "quantise"))
+            print(json.dumps({"what": "moe_act", "dtype": dt, "rows": m, "pairs": m * k, "bm_weight_only": ops.mxfp4_moe_bm(m * k, e),
+                              "bm_a8": ops.mxfp4_moe_a8_bm(m * k, e), "buffers": nbuf, "weight_only_us_p50_p10_p90": w16,
+                              "a8_us_p50_p10_p90": a8, "ratio_p50_p10_p90": [round(r, 3) for r in ratio],
+                              "a8_p90_below_weight_only_p10": a8[2] < w16[1], "quantise_us_p50_p10_p90": qt,
+                              "quantise_share": round(qt[0] / a8[0], 3)}), flush=True)
+        del layers
+        torch.cuda.empty_cache()
+
+
 def bench_steps(dev, iters, layers, seq=1024):
     cfg = ModelConfig.llama3_8b()
     cfg.num_layers = layers
@@ -279,7 +334,7 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.moe:
-        return bench_moe(dev, args.iters)
+        return bench_moe_act(dev, args.iters) if args.act else bench_moe(dev, args.iters)
     if args.act:
         return bench_act(dev, args.iters, args.layers)
     if not args.no_linears:

@@ -106,16 +106,6 @@ struct Mx4A8Params : Mx4Params {
 constexpr int kA8T = 4;         // 16 x 16 tiles per wave along M and along N
 constexpr int kA8Rows = 16 * kA8T, kA8Cols = 4 * 16 * kA8T;      // workgroup tile 64 x 256
 
-// the four scale bytes of blocks b0 .. b0 + 3 of a row (b0 % 4 == 0); blocks past nb read as 127 (their codes are zeros)
-__device__ __forceinline__ uint32_t mx_scale4(const uint8_t* srow, int b0, int nb, bool dwords) {
-    if (dwords) return b0 < nb ? *reinterpret_cast<const uint32_t*>(srow + b0) : 0x7f7f7f7fu;
-    uint32_t v = 0x7f7f7f7fu;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (b0 + j < nb) v = (v & ~(0xffu << (8 * j))) | ((uint32_t)srow[b0 + j] << (8 * j));
-    return v;
-}
-
 struct Mx4A8Frag {
     i8v a[kA8T];
     uint4 b[kA8T];

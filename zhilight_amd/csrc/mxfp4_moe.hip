@@ -38,58 +38,6 @@ namespace {
 
 typedef mx_f4 f4;
 
-struct Mx4MoeParams : Mx4Params {       // x, ldx, y, n, k, nb, epi; codes / scales: expert 0's; bias = residual = nullptr; m unused
-    int x_rows, y_rows;
-    int64_t stride_codes, stride_scales;  // bytes between experts
-    int experts;
-    const int32_t* loads;                 // grouped: (experts) rows per expert
-    const int32_t* index;                 // grouped: (pairs) sorted position -> pair id
-    const int32_t* ids;                   // pairs: (pairs) expert of each pair
-    int pairs, in_div, out_scatter;
-};
-
-// ---- grouped: which expert / tile slot blockIdx.y is (every wave scans the same loads: uniform over the workgroup, no barrier) -----
-struct Mx4MoeTile { int expert, pos0, nvalid; };     // expert < 0: an idle slot of the bound
-
-template <int BM>
-__device__ __forceinline__ Mx4MoeTile mx_moe_tile(const Mx4MoeParams& p, int slot, int lane) {
-    int f_e = -1, f_t = 0, f_off = 0, f_len = 0;
-    int tile_base = 0, row_base = 0;
-    for (int c = 0; c < p.experts; c += 64) {
-        const int e = c + lane;
-        int l = e < p.experts ? p.loads[e] : 0;
-        l = l < 0 ? 0 : (l > p.pairs ? p.pairs : l);
-        const int t = (l + BM - 1) / BM;
-        int ti = t, li = l;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int a = __shfl_up(ti, d, 64), b = __shfl_up(li, d, 64);
-            if (lane >= d) { ti += a; li += b; }
-        }
-        const int t_ex = tile_base + ti - t, l_ex = row_base + li - l;
-        const unsigned long long hit = __ballot(slot >= t_ex && slot < t_ex + t);
-        if (hit) {
-            const int src = __builtin_ctzll(hit);
-            f_e = __shfl(e, src, 64);
-            f_t = slot - __shfl(t_ex, src, 64);
-            f_off = __shfl(l_ex, src, 64);
-            f_len = __shfl(l, src, 64);
-            break;
-        }
-        tile_base += __shfl(ti, 63, 64);
-        row_base += __shfl(li, 63, 64);
-        if (row_base >= p.pairs) break;          // the runs past here start beyond the last pair
-    }
-    Mx4MoeTile r;
-    r.expert = __builtin_amdgcn_readfirstlane(f_e);
-    r.pos0 = __builtin_amdgcn_readfirstlane(f_off + f_t * BM);
-    int nv = __builtin_amdgcn_readfirstlane(f_len - f_t * BM);
-    nv = nv > BM ? BM : nv;
-    r.nvalid = nv > p.pairs - r.pos0 ? p.pairs - r.pos0 : nv;
-    if (r.nvalid <= 0) r.expert = -1;
-    return r;
-}
-
 // the tile's rows: lane (nrow, kq)'s A-fragment pointers (tile row 16 t + nrow) and, in lane l, the output row of tile row l (< 0: none)
 template <int MT>
 __device__ __forceinline__ int mx_moe_rows(const Mx4MoeParams& p, const Mx4MoeTile& w, int lane, const uint16_t* (&xrow)[MT], bool (&live)[MT]) {

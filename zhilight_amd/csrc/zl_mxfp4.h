@@ -1,7 +1,8 @@
 // zl_mxfp4.h -- what the MXFP4 kernels share (mxfp4.hip: fp16 / bf16 activations; mxfp4_a8.hip: MXFP8 activations; mxfp4_moe.hip:
-// expert stacks): the launch parameters, the epilogues of zl_w4a16 (include/zhilight_amd.h) for either T, and the device code of
-// the weight-only kernels -- the E2M1 decode, the 32-wide MFMA step, the per-lane GEMV walk (mx_gemv_run) and the quad walk of the
-// matrix-core kernels (mx_run).  One copy: a kernel that calls them has the numerics stated in mxfp4.hip.
+// expert stacks; mxfp4_moe_a8.hip: expert stacks on MXFP8 activations): the launch parameters, the work table of the grouped forms,
+// the epilogues of zl_w4a16 (include/zhilight_amd.h) for either T, and the device code of the weight-only kernels -- the E2M1
+// decode, the 32-wide MFMA step, the per-lane GEMV walk (mx_gemv_run) and the quad walk of the matrix-core kernels (mx_run).  One
+// copy: a kernel that calls them has the numerics stated in mxfp4.hip.
 #pragma once
 #include "zl_common.h"
 #include "zl_w4m_epilogue.h"
@@ -255,4 +256,68 @@ __device__ __forceinline__ void mx_run(const Mx4Params& p, const uint32_t* __res
             load(u, quad + (c + PF) * step);
         }
     }
+}
+
+// ---- what the MXFP8-activation kernels share (mxfp4_a8.hip, mxfp4_moe_a8.hip) --------------------------------------------------
+// the four scale bytes of blocks b0 .. b0 + 3 of a row (b0 % 4 == 0); blocks past nb read as 127 (their codes are zeros)
+__device__ __forceinline__ uint32_t mx_scale4(const uint8_t* srow, int b0, int nb, bool dwords) {
+    if (dwords) return b0 < nb ? *reinterpret_cast<const uint32_t*>(srow + b0) : 0x7f7f7f7fu;
+    uint32_t v = 0x7f7f7f7fu;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (b0 + j < nb) v = (v & ~(0xffu << (8 * j))) | ((uint32_t)srow[b0 + j] << (8 * j));
+    return v;
+}
+
+// ---- what the expert-stack kernels share (mxfp4_moe.hip, mxfp4_moe_a8.hip) ------------------------------------------------------
+struct Mx4MoeParams : Mx4Params {       // x, ldx, y, n, k, nb, epi; codes / scales: expert 0's; bias = residual = nullptr; m unused
+    int x_rows, y_rows;
+    int64_t stride_codes, stride_scales;  // bytes between experts
+    int experts;
+    const int32_t* loads;                 // grouped: (experts) rows per expert
+    const int32_t* index;                 // grouped: (pairs) sorted position -> pair id
+    const int32_t* ids;                   // pairs: (pairs) expert of each pair
+    int pairs, in_div, out_scatter;
+};
+
+// ---- grouped: which expert / tile slot blockIdx.y is (every wave scans the same loads: uniform over the workgroup, no barrier) -----
+struct Mx4MoeTile { int expert, pos0, nvalid; };     // expert < 0: an idle slot of the bound
+
+template <int BM>
+__device__ __forceinline__ Mx4MoeTile mx_moe_tile(const Mx4MoeParams& p, int slot, int lane) {
+    int f_e = -1, f_t = 0, f_off = 0, f_len = 0;
+    int tile_base = 0, row_base = 0;
+    for (int c = 0; c < p.experts; c += 64) {
+        const int e = c + lane;
+        int l = e < p.experts ? p.loads[e] : 0;
+        l = l < 0 ? 0 : (l > p.pairs ? p.pairs : l);
+        const int t = (l + BM - 1) / BM;
+        int ti = t, li = l;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int a = __shfl_up(ti, d, 64), b = __shfl_up(li, d, 64);
+            if (lane >= d) { ti += a; li += b; }
+        }
+        const int t_ex = tile_base + ti - t, l_ex = row_base + li - l;
+        const unsigned long long hit = __ballot(slot >= t_ex && slot < t_ex + t);
+        if (hit) {
+            const int src = __builtin_ctzll(hit);
+            f_e = __shfl(e, src, 64);
+            f_t = slot - __shfl(t_ex, src, 64);
+            f_off = __shfl(l_ex, src, 64);
+            f_len = __shfl(l, src, 64);
+            break;
+        }
+        tile_base += __shfl(ti, 63, 64);
+        row_base += __shfl(li, 63, 64);
+        if (row_base >= p.pairs) break;          // the runs past here start beyond the last pair
+    }
+    Mx4MoeTile r;
+    r.expert = __builtin_amdgcn_readfirstlane(f_e);
+    r.pos0 = __builtin_amdgcn_readfirstlane(f_off + f_t * BM);
+    int nv = __builtin_amdgcn_readfirstlane(f_len - f_t * BM);
+    nv = nv > BM ? BM : nv;
+    r.nvalid = nv > p.pairs - r.pos0 ? p.pairs - r.pos0 : nv;
+    if (r.nvalid <= 0) r.expert = -1;
+    return r;
 }

@@ -125,7 +125,8 @@ class QuantConfig:
     `act_quant` (type 11 only; set by the caller, never by from_hf): "" = weight-only, activations stay fp16 / bf16; "mxfp8" = linears
     over more than MXFP4_A8_ABOVE_ROWS rows quantise their input to OCP MXFP8 and run on the scaled MFMA (ops.mxfp4_a8_linear) --
     prompt encode gets faster and its activations carry an E4M3 rounding; decode steps are untouched.  In an MoE model
-    (Mxfp4MoEEncoderLayer) the q|k|v and attn_out linears follow act_quant; the EXPERTS stay weight-only at every row count."""
+    (Mxfp4MoEEncoderLayer) the q|k|v and attn_out linears follow act_quant, and so do the EXPERTS in chunks of more than
+    MXFP4_MOE_A8_ABOVE_ROWS token rows (ops.mxfp4_moe_a8_grouped); at or below it they stay weight-only."""
     quant_type: int = 5
     group_size: int = 128
     sym: bool = False
@@ -648,6 +649,12 @@ def mxfp4_tensors(sd, prefix):
 # QuantConfig.act_quant == "mxfp8": a linear over MORE rows than this quantises its input and runs ops.mxfp4_a8_linear; up to this
 # many rows (decode steps: bandwidth-bound) it stays on the weight-only kernels, bit for bit.  ops.mxfp4_route's last boundary.
 MXFP4_A8_ABOVE_ROWS = 32
+# ... and the experts of Mxfp4MoEEncoderLayer: a chunk of MORE token rows than this quantises its rows and runs ops.mxfp4_moe_a8_grouped.
+# Never below MXFP4_A8_ABOVE_ROWS (decode and speculative steps stay weight-only).  Measured (tools/bench_mxfp4.py --moe --act mxfp8,
+# profiles/mxfp4_moe_a8.txt; DESIGN 4, "MXFP8 activations for the experts"): 64 rows is the smallest measured row count, and from it on
+# the MXFP8 route's p90 is below the weight-only route's p10 (1.9 x at 64 and 128 rows, 3.0 x at 512, 2.5 x at 2048) -- so the route
+# starts AT 64 rows; 33 .. 63 rows were not measured and stay weight-only.
+MXFP4_MOE_A8_ABOVE_ROWS = 63
 
 
 class Mxfp4Linear:
@@ -775,8 +782,10 @@ class Mxfp4MoEEncoderLayer(Mxfp4EncoderLayer):
     attention half and both norms are Mxfp4EncoderLayer's, ln_ff + router + experts replace w_in_gated / w_out.  The router is
     Qwen3-MoE's (fp32 logits, softmax, top-k, renormalised with norm_topk_prob); the experts are two stacks of checkpoint tensors
     (ops.Mxfp4MoEWeight: gate|up row-interleaved per expert, down) and run in ONE launch per projection whatever the number of
-    active experts.  Weight-only at every row count: QuantConfig.act_quant reaches q|k|v and attn_out, not the experts.  Not with
-    tensor or expert parallelism or shared experts (ZLError)."""
+    active experts.  QuantConfig.act_quant == "mxfp8" reaches q|k|v and attn_out and, in chunks of more than a8_above_rows (=
+    MXFP4_MOE_A8_ABOVE_ROWS) token rows, the experts: the rows are quantised to MXFP8 once per projection and both grouped launches run
+    on the scaled MFMA (ops.mxfp4_moe_a8_grouped); shorter chunks and decode steps stay weight-only, bit for bit.  Not with tensor or
+    expert parallelism or shared experts (ZLError)."""
 
     def __init__(self, cfg: ModelConfig, quant: QuantConfig, idx: int):
         if cfg.model_type != "qwen3_moe":
@@ -791,6 +800,8 @@ class Mxfp4MoEEncoderLayer(Mxfp4EncoderLayer):
         super().__init__(cfg, quant, idx)
         # rows up to this take the pairs form (MXFP4_MOE_M_THRES, read at load)
         self.m_thres = int(os.environ.get("MXFP4_MOE_M_THRES", _MXFP4_MOE_M_THRES_DEFAULT) or 0)
+        # act_quant == "mxfp8": chunks of more token rows than this take the MXFP8 route of the experts
+        self.a8_above_rows = max(MXFP4_MOE_A8_ABOVE_ROWS, MXFP4_A8_ABOVE_ROWS)
         self.router = self.w_up = self.w_down = None
         self.last_route = None
 
@@ -855,6 +866,13 @@ class Mxfp4MoEEncoderLayer(Mxfp4EncoderLayer):
         # the pairs sorted by expert on the device (stable), gate|up over the tokens gathered in place, down scattered back to pair
         # order, then the weighted combine: every output row sums its k slots in order
         _, order = ops.sort_pairs_i32(ids.reshape(-1), pair, max_key=e)
+        if self.quant.act_quant == "mxfp8" and t > self.a8_above_rows:
+            # the T token rows quantised once (the kernel gathers them: no row is quantised twice), then the activations
+            xq, xs = ops.mxfp8_quantize(xn)
+            act = ops.mxfp4_moe_a8_grouped(xq, xs, self.w_up, xn.dtype, loads[:e], order, p, in_div=k, epilogue=ops.EPI_SILU_MUL)
+            aq, as_ = ops.mxfp8_quantize(act)
+            down = ops.mxfp4_moe_a8_grouped(aq, as_, self.w_down, xn.dtype, loads[:e], order, p, out_scatter=True)
+            return ops.moe_sum_experts(down, pair, weights)
         act = ops.mxfp4_moe_grouped(xn, self.w_up, loads[:e], order, p, in_div=k, epilogue=ops.EPI_SILU_MUL)
         down = ops.mxfp4_moe_grouped(act, self.w_down, loads[:e], order, p, out_scatter=True)
         return ops.moe_sum_experts(down, pair, weights)
