@@ -381,6 +381,26 @@ int zl_mxfp8_quantize(const uint16_t* x, int64_t ldx, uint8_t* xq /* (M,K) */, u
                       zl_stream_t s);
 int zl_mxfp4_a8_linear(const uint8_t* xq, const uint8_t* xs, const uint8_t* codes, const uint8_t* scales, const uint16_t* bias,
                        const uint16_t* residual, uint16_t* y, int64_t m, int64_t n, int64_t k, int dtype, int epilogue, zl_stream_t s);
+/* MXFP4 ACTIVATIONS (opt-in prompt route, W4A4, csrc/mxfp4_a4.hip): the activations are rounded to OCP MXFP4 -- the weights' own
+ * format -- and the product runs on the FP4 x FP4 form of v_mfma_scale_f32_16x16x128_f8f6f4.
+ * zl_mxfp4_act_quantize: x (M, K) T with row stride ldx (% 8 == 0, 16-byte aligned), K % 32 == 0 -> xq uint8 (M, K/2) and xs uint8
+ *   (M, K/32) in THE FORMAT above: element 2j in bits 0-3 of byte j, element 2j + 1 in bits 4-7, E8M0 scale bytes; xq 16-byte aligned.
+ *   Per block of 32 elements (OCP MX v1.0): byte = clamp(floor(log2(amax)) - 2 + 127, 0, 254), an all-zero block gets byte 0;
+ *   x / 2^(byte - 127) is exact in fp32 and rounded ONCE to the nearest E2M1 value, ties to the even code, saturating at +-6 (an
+ *   element in (6, 8) 2^(byte - 127), e.g. 7.5 under amax 7.75, becomes 6).  A negative element that rounds to zero gets code 8,
+ *   which decodes to 0.  Integer arithmetic, no hardware converter.  x is finite: a NaN or an infinity is not defined.
+ * zl_mxfp4_a4_linear: y[m, n] = T( sum_b 2^(xs[m, b] + scales[n, b] - 254) * sum_{i < 32} E2M1(xq[m, 32 b + i]) * E2M1(code[n, 32 b + i])
+ *   [+ bias] ), y (M, N) -- (M, N / 2) under ZL_EPI_SILU_MUL -- with the epilogues of zl_mxfp4_linear and their arithmetic.  xq (M, K/2)
+ *   and xs (M, K/32) contiguous; every other argument, limit and alignment rule as for zl_mxfp4_a8_linear (K % 32 == 0, a K that is no
+ *   multiple of 128 is padded with zero codes in registers; xs and scales 4-byte aligned when K % 128 == 0).  Meant for more than 32 rows.
+ *   NUMERICS: every product E2M1 x E2M1 is exact (at most 4 significant bits), the sum is accumulated in fp32 INSIDE the instruction
+ *   (tests hold it to 2 K roundings of the absolute sum).  One workgroup owns an output over all of K: no atomics, the same bits on
+ *   every run, and a row's bits do not depend on M.  DEFINED when every xs[m, b] + scales[n, b] - 254 lies in fp32's normal exponent
+ *   range (-126 .. 127); scale byte 255 is excluded at load as above. */
+int zl_mxfp4_act_quantize(const uint16_t* x, int64_t ldx, uint8_t* xq /* (M,K/2) */, uint8_t* xs /* (M,K/32) */, int64_t m, int64_t k,
+                          int dtype, zl_stream_t s);
+int zl_mxfp4_a4_linear(const uint8_t* xq, const uint8_t* xs, const uint8_t* codes, const uint8_t* scales, const uint16_t* bias,
+                       const uint16_t* residual, uint16_t* y, int64_t m, int64_t n, int64_t k, int dtype, int epilogue, zl_stream_t s);
 /* EXPERT STACKS (csrc/mxfp4_moe.hip): the routed feed-forward of MXFP4 mixture-of-experts models, T = fp16 / bf16 (dtype).
  * THE OPERAND is the checkpoint's tensors, stacked: codes uint8 (E, N, K/2), scales uint8 (E, N, K/32) in the format above, expert e
  *   at codes + e * expert_stride_codes / scales + e * expert_stride_scales BYTES (strides >= one expert's tensor, the code stride

@@ -2,6 +2,7 @@
 
     python tools/bench_mxfp4.py [--iters 100] [--no-linears] [--no-steps] [--layers 32]
     python tools/bench_mxfp4.py --act mxfp8 [--iters 100] [--layers 32]      (DESIGN 4 "MXFP8 activations", profiles/mxfp4_a8.txt)
+    python tools/bench_mxfp4.py --act mxfp4 [--iters 100] [--layers 32]      (DESIGN 4 "MXFP4 activations", profiles/mxfp4_a4.txt)
     python tools/bench_mxfp4.py --moe [--iters 100]                          (DESIGN 4 "MXFP4 experts", profiles/mxfp4_moe.txt)
     python tools/bench_mxfp4.py --moe --act mxfp8 [--iters 100]              (DESIGN 4 "MXFP8 activations for the experts", profiles/mxfp4_moe_a8.txt)
 
@@ -18,6 +19,10 @@ launch per buffer, reported per launch (eager launches measure the host: ~14 us 
             replay, "speedup" = weight-only / (quantiser + GEMM) -- and the time to the first token of a 1024-token prompt (LLaMA.prefill,
             eager launches between two events: both ways pay the same launches but for the quantisers) on ONE model whose linears are
             switched between the routes, so both ways read the same weights
+  --act mxfp4  the same run with a third route, W4A4: weight-only tiled, MXFP8 (quantiser + GEMM) and MXFP4 (ops.mxfp4_act_quantize +
+            ops.mxfp4_a4_linear) alternate on the same weights; "a4_speedup" = weight-only / (quantiser + GEMM), "a4_over_a8" = MXFP8
+            route / MXFP4 route, "a4_p90_below_weight_only_p10" is the condition on the route's threshold; the time to the first token
+            for the three routes
   --moe     the routed feed-forward on MXFP4 expert stacks (DESIGN 4 "MXFP4 experts", profiles/mxfp4_moe.txt) at the Qwen3-30B-A3B
             geometry (128 experts, top-k 8, dim_model 2048, moe_intermediate_size 768) at 1, 4, 8, 32, 512 rows.  An iteration is one
             hipGraph replay of Mxfp4MoEEncoderLayer.moe (router, top-k, [sort,] gate|up, down, combine) on each of 16 layers (5 GB of
@@ -105,7 +110,7 @@ def bench_linears(dev, iters):
         torch.cuda.empty_cache()
 
 
-def bench_act(dev, iters, layers, rows=(128, 512, 2048), prompt_len=1024):
+def bench_act(dev, iters, layers, rows=(128, 512, 2048), prompt_len=1024, a4=False):
     gen = torch.Generator(device=dev).manual_seed(1)
     us = lambda q: [round(t * 1e6, 2) for t in q]  # noqa: E731
     for name, n, k, epi in LINEARS:
@@ -120,6 +125,11 @@ def bench_act(dev, iters, layers, rows=(128, 512, 2048), prompt_len=1024):
                 legs = {"weight_only": lambda w: ops.mxfp4_linear(x, w, **kw), "quantise": lambda w: ops.mxfp8_quantize(x, out=q),
                         "a8_gemm": lambda w: ops.mxfp4_a8_linear(q[0], q[1], w, dtype, **kw),
                         "a8": lambda w: ops.mxfp4_a8_linear(*ops.mxfp8_quantize(x, out=q), w, dtype, **kw)}
+                if a4:
+                    q4 = ops.mxfp4_act_quantize(x)
+                    legs.update({"a4_quantise": lambda w: ops.mxfp4_act_quantize(x, out=q4),
+                                 "a4_gemm": lambda w: ops.mxfp4_a4_linear(q4[0], q4[1], w, dtype, **kw),
+                                 "a4": lambda w: ops.mxfp4_a4_linear(*ops.mxfp4_act_quantize(x, out=q4), w, dtype, **kw)})
                 graphs = {}
                 for leg, run in legs.items():
                     run(ws[0])
@@ -135,10 +145,15 @@ def bench_act(dev, iters, layers, rows=(128, 512, 2048), prompt_len=1024):
                 res = {leg: [t / nbuf for t in quantiles(ts)] for leg, ts in times.items()}
                 del graphs
                 w16, a8 = res["weight_only"], res["a8"]
-                print(json.dumps({"what": "act_linear", "name": name, "n": n, "k": k, "m": m, "dtype": str(dtype).split(".")[1], "buffers": nbuf,
-                                  **{leg + "_us_p50_p10_p90": us(r) for leg, r in res.items()},
-                                  "speedup_p50": round(w16[0] / a8[0], 3), "speedup_p10_p90": [round(w16[1] / a8[2], 3), round(w16[2] / a8[1], 3)],
-                                  "a8_tflops": round(2.0 * m * n * k / a8[0] * 1e-12, 1)}), flush=True)
+                rec = {"what": "act_linear", "name": name, "n": n, "k": k, "m": m, "dtype": str(dtype).split(".")[1], "buffers": nbuf,
+                       **{leg + "_us_p50_p10_p90": us(r) for leg, r in res.items()},
+                       "speedup_p50": round(w16[0] / a8[0], 3), "speedup_p10_p90": [round(w16[1] / a8[2], 3), round(w16[2] / a8[1], 3)],
+                       "a8_tflops": round(2.0 * m * n * k / a8[0] * 1e-12, 1)}
+                if a4:
+                    r4 = res["a4"]
+                    rec.update({"a4_speedup_p50": round(w16[0] / r4[0], 3), "a4_over_a8_p50": round(a8[0] / r4[0], 3),
+                                "a4_p90_below_weight_only_p10": r4[2] < w16[1], "a4_gemm_tflops": round(2.0 * m * n * k / res["a4_gemm"][0] * 1e-12, 1)})
+                print(json.dumps(rec), flush=True)
         del ws
         torch.cuda.empty_cache()
     cfg = ModelConfig.llama3_8b()
@@ -153,13 +168,17 @@ def bench_act(dev, iters, layers, rows=(128, 512, 2048), prompt_len=1024):
                 lin.act_quant = act
         ctx.positions.zero_(), ctx.placement.zero_(), ctx.valid_lens.zero_()
         model.prefill(ctx, 0, prompt)
-    times = {"": [], "mxfp8": []}
+    times = {"": [], "mxfp8": [], **({"mxfp4": []} if a4 else {})}
     for _ in range(4):
         for act in times:
             times[act] += timed(lambda i: prefill(act), max(1, iters // 10), warmup=1)
     w16, a8 = quantiles(times[""]), quantiles(times["mxfp8"])
-    print(json.dumps({"what": "ttft", "layers": layers, "prompt": prompt_len, "weight_only_ms_p50_p10_p90": [round(t * 1e3, 3) for t in w16],
-                      "a8_ms_p50_p10_p90": [round(t * 1e3, 3) for t in a8], "speedup_p50": round(w16[0] / a8[0], 3)}), flush=True)
+    rec = {"what": "ttft", "layers": layers, "prompt": prompt_len, "weight_only_ms_p50_p10_p90": [round(t * 1e3, 3) for t in w16],
+           "a8_ms_p50_p10_p90": [round(t * 1e3, 3) for t in a8], "speedup_p50": round(w16[0] / a8[0], 3)}
+    if a4:
+        r4 = quantiles(times["mxfp4"])
+        rec.update({"a4_ms_p50_p10_p90": [round(t * 1e3, 3) for t in r4], "a4_speedup_p50": round(w16[0] / r4[0], 3)})
+    print(json.dumps(rec), flush=True)
 
 
 def moe_loop(layer, xn):
@@ -329,14 +348,17 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--no-linears", action="store_true")
     ap.add_argument("--no-steps", action="store_true")
-    ap.add_argument("--act", choices=("", "mxfp8"), default="", help="mxfp8: the A/B of the MXFP8-activation prompt route, nothing else")
+    ap.add_argument("--act", choices=("", "mxfp8", "mxfp4"), default="",
+                    help="mxfp8: the A/B of the MXFP8-activation prompt route, nothing else; mxfp4: the same with the W4A4 route as a third leg")
     ap.add_argument("--moe", action="store_true", help="the routed feed-forward on MXFP4 expert stacks, nothing else")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.moe:
+        if args.act == "mxfp4":
+            ap.error("--moe --act mxfp4: the experts have no MXFP4-activation route")
         return bench_moe_act(dev, args.iters) if args.act else bench_moe(dev, args.iters)
     if args.act:
-        return bench_act(dev, args.iters, args.layers)
+        return bench_act(dev, args.iters, args.layers, a4=args.act == "mxfp4")
     if not args.no_linears:
         bench_linears(dev, args.iters)
     if not args.no_steps:

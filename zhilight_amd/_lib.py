@@ -51,6 +51,7 @@ SYMBOLS = [
     "zl_w4a8_weight_to_int8", "zl_quant_scale_back_f32",
     "zl_awq_dequantize", "zl_awq_gemm_workspace_bytes", "zl_awq_gemm",
     "zl_mxfp4_route", "zl_mxfp4_linear", "zl_mxfp4_dequant", "zl_mxfp8_quantize", "zl_mxfp4_a8_linear",
+    "zl_mxfp4_act_quantize", "zl_mxfp4_a4_linear",
     "zl_mxfp4_moe_bm", "zl_mxfp4_moe_grouped", "zl_mxfp4_moe_pairs", "zl_mxfp4_moe_a8_bm", "zl_mxfp4_moe_a8_grouped",
 ]
 

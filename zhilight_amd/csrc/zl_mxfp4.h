@@ -1,5 +1,5 @@
-// zl_mxfp4.h -- what the MXFP4 kernels share (mxfp4.hip: fp16 / bf16 activations; mxfp4_a8.hip: MXFP8 activations; mxfp4_moe.hip:
-// expert stacks; mxfp4_moe_a8.hip: expert stacks on MXFP8 activations): the launch parameters, the work table of the grouped forms,
+// zl_mxfp4.h -- what the MXFP4 kernels share (mxfp4.hip: fp16 / bf16 activations; mxfp4_a8.hip: MXFP8 activations; mxfp4_a4.hip:
+// MXFP4 activations; mxfp4_moe.hip: expert stacks; mxfp4_moe_a8.hip: expert stacks on MXFP8 activations): the launch parameters, the work table of the grouped forms,
 // the epilogues of zl_w4a16 (include/zhilight_amd.h) for either T, and the device code of the weight-only kernels -- the E2M1
 // decode, the 32-wide MFMA step, the per-lane GEMV walk (mx_gemv_run) and the quad walk of the matrix-core kernels (mx_run).  One
 // copy: a kernel that calls them has the numerics stated in mxfp4.hip.
@@ -258,7 +258,7 @@ __device__ __forceinline__ void mx_run(const Mx4Params& p, const uint32_t* __res
     }
 }
 
-// ---- what the MXFP8-activation kernels share (mxfp4_a8.hip, mxfp4_moe_a8.hip) --------------------------------------------------
+// ---- what the scaled-MFMA kernels share (mxfp4_a8.hip, mxfp4_a4.hip, mxfp4_moe_a8.hip) --------------------------------------------------
 // the four scale bytes of blocks b0 .. b0 + 3 of a row (b0 % 4 == 0); blocks past nb read as 127 (their codes are zeros)
 __device__ __forceinline__ uint32_t mx_scale4(const uint8_t* srow, int b0, int nb, bool dwords) {
     if (dwords) return b0 < nb ? *reinterpret_cast<const uint32_t*>(srow + b0) : 0x7f7f7f7fu;

@@ -126,7 +126,9 @@ class QuantConfig:
     over more than MXFP4_A8_ABOVE_ROWS rows quantise their input to OCP MXFP8 and run on the scaled MFMA (ops.mxfp4_a8_linear) --
     prompt encode gets faster and its activations carry an E4M3 rounding; decode steps are untouched.  In an MoE model
     (Mxfp4MoEEncoderLayer) the q|k|v and attn_out linears follow act_quant, and so do the EXPERTS in chunks of more than
-    MXFP4_MOE_A8_ABOVE_ROWS token rows (ops.mxfp4_moe_a8_grouped); at or below it they stay weight-only."""
+    MXFP4_MOE_A8_ABOVE_ROWS token rows (ops.mxfp4_moe_a8_grouped); at or below it they stay weight-only.  "mxfp4" = W4A4, what Quark's
+    MXFP4 exports are calibrated for: linears over more than MXFP4_A4_ABOVE_ROWS rows quantise their input to OCP MXFP4 and run on
+    the FP4 x FP4 scaled MFMA (ops.mxfp4_a4_linear); the experts of an MoE model stay weight-only under it."""
     quant_type: int = 5
     group_size: int = 128
     sym: bool = False
@@ -649,6 +651,10 @@ def mxfp4_tensors(sd, prefix):
 # QuantConfig.act_quant == "mxfp8": a linear over MORE rows than this quantises its input and runs ops.mxfp4_a8_linear; up to this
 # many rows (decode steps: bandwidth-bound) it stays on the weight-only kernels, bit for bit.  ops.mxfp4_route's last boundary.
 MXFP4_A8_ABOVE_ROWS = 32
+# QuantConfig.act_quant == "mxfp4": the same boundary for ops.mxfp4_act_quantize + ops.mxfp4_a4_linear.  Never below
+# MXFP4_A8_ABOVE_ROWS; the route may not start at a row count where it is slower than the weight-only route (tools/bench_mxfp4.py
+# --act mxfp4, profiles/mxfp4_a4.txt; DESIGN 4, "MXFP4 activations").
+MXFP4_A4_ABOVE_ROWS = 32
 # ... and the experts of Mxfp4MoEEncoderLayer: a chunk of MORE token rows than this quantises its rows and runs ops.mxfp4_moe_a8_grouped.
 # Never below MXFP4_A8_ABOVE_ROWS (decode and speculative steps stay weight-only).  Measured (tools/bench_mxfp4.py --moe --act mxfp8,
 # profiles/mxfp4_moe_a8.txt; DESIGN 4, "MXFP8 activations for the experts"): 64 rows is the smallest measured row count, and from it on
@@ -660,7 +666,8 @@ MXFP4_MOE_A8_ABOVE_ROWS = 63
 class Mxfp4Linear:
     """A linear on MXFP4 weights (quant type 11): y = T(x . W^T + bias), T = fp16 or bf16, no weight ever rounded
     (ops.mxfp4_linear).  `fuse` concatenates rows like Linear::fuse; row_interleave for the gated pair.  act_quant (set by the
-    layer from QuantConfig.act_quant): "mxfp8" sends more than MXFP4_A8_ABOVE_ROWS rows through mxfp8_quantize + mxfp4_a8_linear."""
+    layer from QuantConfig.act_quant): "mxfp8" sends more than MXFP4_A8_ABOVE_ROWS rows through mxfp8_quantize + mxfp4_a8_linear,
+    "mxfp4" more than MXFP4_A4_ABOVE_ROWS rows through mxfp4_act_quantize + mxfp4_a4_linear."""
 
     def __init__(self, name, dim_in, dim_out):
         self.name, self.dim_in, self.dim_out = name, dim_in, dim_out
@@ -701,9 +708,13 @@ class Mxfp4Linear:
         return self.weight.nbytes()
 
     def forward(self, x, out=None, residual=None, epilogue=0):
-        if self.act_quant == "mxfp8" and x.numel() // x.shape[-1] > MXFP4_A8_ABOVE_ROWS:
+        rows = x.numel() // x.shape[-1]
+        if self.act_quant == "mxfp8" and rows > MXFP4_A8_ABOVE_ROWS:
             xq, xs = ops.mxfp8_quantize(x)
             return ops.mxfp4_a8_linear(xq, xs, self.weight, x.dtype, bias=self.bias, residual=residual, out=out, epilogue=epilogue)
+        if self.act_quant == "mxfp4" and rows > MXFP4_A4_ABOVE_ROWS:
+            xq, xs = ops.mxfp4_act_quantize(x)
+            return ops.mxfp4_a4_linear(xq, xs, self.weight, x.dtype, bias=self.bias, residual=residual, out=out, epilogue=epilogue)
         return ops.mxfp4_linear(x, self.weight, bias=self.bias, residual=residual, out=out, epilogue=epilogue)
 
 
@@ -784,8 +795,9 @@ class Mxfp4MoEEncoderLayer(Mxfp4EncoderLayer):
     (ops.Mxfp4MoEWeight: gate|up row-interleaved per expert, down) and run in ONE launch per projection whatever the number of
     active experts.  QuantConfig.act_quant == "mxfp8" reaches q|k|v and attn_out and, in chunks of more than a8_above_rows (=
     MXFP4_MOE_A8_ABOVE_ROWS) token rows, the experts: the rows are quantised to MXFP8 once per projection and both grouped launches run
-    on the scaled MFMA (ops.mxfp4_moe_a8_grouped); shorter chunks and decode steps stay weight-only, bit for bit.  Not with tensor or
-    expert parallelism or shared experts (ZLError)."""
+    on the scaled MFMA (ops.mxfp4_moe_a8_grouped); shorter chunks and decode steps stay weight-only, bit for bit.  Under act_quant ==
+    "mxfp4" q|k|v and attn_out take the W4A4 route and the EXPERTS STAY WEIGHT-ONLY: there is no expert-grouped A4 launch yet.  Not
+    with tensor or expert parallelism or shared experts (ZLError)."""
 
     def __init__(self, cfg: ModelConfig, quant: QuantConfig, idx: int):
         if cfg.model_type != "qwen3_moe":
@@ -1514,10 +1526,10 @@ class LLaMA:
     def __init__(self, cfg: ModelConfig, quant: QuantConfig, device="cuda:0", tp=None):
         """tp: parallel.TPGroup (rank, size, process group) for tensor parallelism over the GPUs of a node -- W4 route
         only; heads, kv heads, dim_ff and the vocabulary must divide by the TP degree."""
-        if quant.act_quant not in ("", "mxfp8"):
-            raise ops.ZLError(f"Unsupported act_quant {quant.act_quant!r}: '' (weight-only) or 'mxfp8'")
+        if quant.act_quant not in ("", "mxfp8", "mxfp4"):
+            raise ops.ZLError(f"Unsupported act_quant {quant.act_quant!r}: '' (weight-only), 'mxfp8' or 'mxfp4'")
         if quant.act_quant and quant.quant_type != MXFP4:
-            raise ops.ZLError("act_quant='mxfp8' is the prompt route of MXFP4 models (quant type 11) only")
+            raise ops.ZLError(f"act_quant={quant.act_quant!r} is a prompt route of MXFP4 models (quant type 11) only")
         if cfg.scale_depth > 0 and quant.quant_type != 0:
             raise ops.ZLError("scale_depth (MiniCPM residual scaling) is only wired into the unquantised layer stack")
         if quant.quant_type not in (0, MXFP4) and cfg.torch_dtype != torch.float16:

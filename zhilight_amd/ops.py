@@ -3597,6 +3597,67 @@ def mxfp4_a8_linear(xq, xs, w: Mxfp4Weight, dtype, bias=None, residual=None, out
     return out
 
 
+def mxfp4_act_quantize(x, out=None):
+    """fp16 / bf16 activations (.., K), K % 32 == 0 -> (codes uint8 (M, K/2) E2M1, scales uint8 (M, K/32) E8M0) in the weights' byte
+    format under the OCP MX rule stated at zl_mxfp4_act_quantize (block exponent floor(log2(amax)) - 2, nearest E2M1 value, ties to
+    the even code, saturating at 6): the activation operand of mxfp4_a4_linear.  A 2-D x may have a row stride > K (% 8 == 0);
+    out = (codes, scales) to reuse buffers."""
+    if not x.is_cuda or x.stride(-1) != 1 or x.dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError("mxfp4_act_quantize: x must be an fp16 / bf16 CUDA tensor with contiguous rows")
+    x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])
+    m, k = x2.shape
+    if k % MXFP4_BLOCK or m < 1:
+        raise ZLError("mxfp4_act_quantize: (M, K) with K % 32 == 0")
+    if m > 1 and x2.stride(0) < k:
+        raise ZLError("mxfp4_act_quantize: overlapping rows")
+    if out is None:
+        out = (torch.empty((m, k // 2), dtype=torch.uint8, device=x.device), torch.empty((m, k // MXFP4_BLOCK), dtype=torch.uint8, device=x.device))
+    else:
+        _chk_out(out[0], m, k // 2, torch.uint8, x.device, "mxfp4_act_quantize")
+        _chk_out(out[1], m, k // MXFP4_BLOCK, torch.uint8, x.device, "mxfp4_act_quantize")
+    check(lib().zl_mxfp4_act_quantize(_p(x2), _i(x2.stride(0) if m > 1 else k), _p(out[0]), _p(out[1]), _i(m), _i(k), C.c_int(_dt(x)), _stream()),
+          "mxfp4_act_quantize")
+    return out
+
+
+def mxfp4_a4_linear(xq, xs, w: Mxfp4Weight, dtype, bias=None, residual=None, out=None, epilogue=0):
+    """y = T(xq . W^T [+ bias]) for MXFP4 activations (mxfp4_act_quantize's codes (M, K/2) and scales (M, K/32)) on an Mxfp4Weight,
+    T = dtype (fp16 / bf16), on the FP4 x FP4 scaled MFMA (zl_mxfp4_a4_linear has the numerics); bias, residual, out and epilogue as
+    in mxfp4_linear."""
+    _chk_cuda(xq, xs, bias, residual)
+    if xq.dtype != torch.uint8 or xs.dtype != torch.uint8 or xq.dim() != 2 or not (xq.is_contiguous() and xs.is_contiguous()):
+        raise ZLError("mxfp4_a4_linear: xq (M, K/2) and xs (M, K/32) are contiguous uint8 tensors")
+    m, k = xq.shape[0], xq.shape[1] * 2
+    if k != w.k:
+        raise ZLError("size K mismatch")
+    if k % MXFP4_BLOCK or tuple(xs.shape) != (m, k // MXFP4_BLOCK):
+        raise ZLError(f"mxfp4_a4_linear: xs {tuple(xs.shape)} is not (M, K/32) = ({m}, {k // MXFP4_BLOCK})")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError("mxfp4_a4_linear: dtype is torch.float16 or torch.bfloat16")
+    silu = epilogue & EPI_SILU_MUL
+    if silu and not w.row_interleave:
+        raise ZLError("mxfp4_a4_linear: EPI_SILU_MUL needs a row-interleaved [gate; up] weight")
+    n_out = w.n // 2 if silu else w.n
+    for t, what in ((bias, "bias"), (residual, "residual")):
+        if t is not None and (t.dtype != dtype or t.device != xq.device):
+            raise ZLError(f"mxfp4_a4_linear: {what} dtype / device")
+    if bias is not None:
+        if bias.numel() != w.n:
+            raise ZLError("mxfp4_a4_linear: bias size")
+        epilogue |= EPI_BIAS
+    if residual is not None:
+        if residual.numel() != m * n_out:
+            raise ZLError("mxfp4_a4_linear: residual size")
+        epilogue |= EPI_RESIDUAL
+    if out is None:
+        out = torch.empty((m, n_out), dtype=dtype, device=xq.device)
+    else:
+        _chk_out(out, m, n_out, dtype, xq.device, "mxfp4_a4_linear")
+    check(lib().zl_mxfp4_a4_linear(_p(xq), _p(xs), _p(w.codes), _p(w.scales), _p(bias), _p(residual), _p(out), _i(m), _i(w.n), _i(k),
+                                   C.c_int(_dt(out)), C.c_int(epilogue), _stream()), "mxfp4_a4_linear")
+    return out
+
+
 # ---- MXFP4 expert stacks (include/zhilight_amd.h "MXFP4", EXPERT STACKS; csrc/mxfp4_moe.hip) -------------------------------------
 class Mxfp4MoEWeight:
     """The experts of one MoE projection as MXFP4 checkpoint tensors, stacked: codes uint8 (E, N, K/2), scales uint8 (E, N, K/32) --
