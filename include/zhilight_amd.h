@@ -460,6 +460,33 @@ int zl_mxfp4_moe_a8_grouped(const uint8_t* xq, const uint8_t* xs, int64_t x_rows
                             int64_t num_experts, int64_t expert_stride_codes, int64_t expert_stride_scales,
                             const int32_t* expert_loads, const int32_t* index, int64_t pairs, int in_div, int out_scatter, uint16_t* y,
                             int64_t y_rows, int64_t n, int64_t k, int dtype, int epilogue, zl_stream_t s);
+/* EXPERT STACKS ON MXFP4 ACTIVATIONS (opt-in prompt route, W4A4, csrc/mxfp4_moe_a4.hip): zl_mxfp4_moe_grouped with the activations of
+ * zl_mxfp4_a4_linear -- every active expert's MXFP4 matrix times its routed MXFP4 rows in ONE launch on the FP4 x FP4 form of the
+ * scaled MFMA.
+ * LAYOUT: xq uint8 (x_rows, K/2) E2M1 codes and xs uint8 (x_rows, K/32) E8M0 bytes, contiguous, as zl_mxfp4_act_quantize writes them
+ *   (the weights' own format); codes / scales the expert stack above with its byte strides; K % 32 == 0 is the only shape rule (a K
+ *   that is no multiple of 128 is padded with zero codes under scale byte 127); xq and codes 16-byte aligned, and when K/32 % 4 == 0
+ *   the scale rows are read as dwords: xs and scales 4-byte aligned, expert_stride_scales % 4 == 0.  Rows, clamping, epilogues (0 or
+ *   ZL_EPI_SILU_MUL), y, the limits and the error codes are those of zl_mxfp4_moe_a8_grouped: position j reads row index[j] / in_div
+ *   (in_div = 0: row j) of xq and xs, clamped to [0, x_rows), and writes y row j or, under out_scatter, index[j]; rows outside
+ *   [0, y_rows) and positions past the last run are not written.  No host synchronisation: the grid is sized from
+ *   zl_moe_grouped_tiles(pairs, num_experts, zl_mxfp4_moe_a4_bm(pairs, num_experts)).
+ * ROUTES (zl_mxfp4_moe_a4_bm: the rows BM of a tile, 16 / 32 / 64 from the average rows per active expert): one kernel at three
+ *   heights -- a workgroup is one (expert, tile of BM sorted rows) x 256 weight rows, four waves of BM x 64 outputs; the weights go
+ *   from global memory into the MFMA operand registers (a ring of four steps), the tile's gathered activation rows are staged
+ *   through LDS in MFMA fragment order once per workgroup (double-buffered per 512 elements of K).  Every height runs two workgroups
+ *   per CU.  Meant for chunks of more than 32 token rows.
+ * NUMERICS: those of zl_mxfp4_a4_linear -- the operands are never rounded again, every product E2M1 x E2M1 is exact and the sum is
+ *   accumulated in fp32 inside the instruction, then one rounding to T and the epilogue's arithmetic.  Row j is BIT-EQUAL to
+ *   zl_mxfp4_a4_linear on the same xq / xs row and the same expert's matrix: a row's bits do not depend on its tile, its place in the
+ *   tile, BM or the rows that share its launch.  No K split, no atomics: the same bits on every run.  DEFINED when every
+ *   xs + scales - 254 lies in -126 .. 127, as there. */
+int zl_mxfp4_moe_a4_bm(int64_t pairs, int64_t num_experts);
+int zl_mxfp4_moe_a4_grouped(const uint8_t* xq /* (x_rows, K/2) */, const uint8_t* xs /* (x_rows, K/32) */, int64_t x_rows,
+                            const uint8_t* codes, const uint8_t* scales, int64_t num_experts,
+                            int64_t expert_stride_codes, int64_t expert_stride_scales,
+                            const int32_t* expert_loads, const int32_t* index, int64_t pairs, int in_div, int out_scatter,
+                            uint16_t* y, int64_t y_rows, int64_t n, int64_t k, int dtype, int epilogue, zl_stream_t s);
 
 /* lm_head + greedy pick without a separate argmax pass over the logits: the GEMV leaves each wavefront's
  * best (rounded logit, row index) in argmax_ws (zl_argmax_workspace_bytes(m, n) bytes); zl_greedy_advance

@@ -5,6 +5,7 @@
     python tools/bench_mxfp4.py --act mxfp4 [--iters 100] [--layers 32]      (DESIGN 4 "MXFP4 activations", profiles/mxfp4_a4.txt)
     python tools/bench_mxfp4.py --moe [--iters 100]                          (DESIGN 4 "MXFP4 experts", profiles/mxfp4_moe.txt)
     python tools/bench_mxfp4.py --moe --act mxfp8 [--iters 100]              (DESIGN 4 "MXFP8 activations for the experts", profiles/mxfp4_moe_a8.txt)
+    python tools/bench_mxfp4.py --moe --act mxfp4 [--iters 100]              (DESIGN 4 "MXFP4 activations for the experts", profiles/mxfp4_moe_a4.txt)
 
 Method: hipEvent pairs around every iteration after 10 warm-ups, >= 100 iterations; the linears rotate through >= 4
 weight buffers totalling more than 256 MB, so every read of a weight comes from HBM -- an iteration is one hipGraph replay of one
@@ -35,6 +36,9 @@ launch per buffer, reported per launch (eager launches measure the host: ~14 us 
             (ops.mxfp4_moe_grouped) against the MXFP8 route (two ops.mxfp8_quantize + two ops.mxfp4_moe_a8_grouped), alternating in one
             process on the same weights in four rounds; "ratio" = weight-only / MXFP8 over the replays paired in order; "quantise" = a
             replay of the route's two quantiser launches alone and their share of the MXFP8 route's median.
+  --moe --act mxfp4  the same run with a third route, W4A4 (two ops.mxfp4_act_quantize + two ops.mxfp4_moe_a4_grouped): the three routes
+            alternate on the same weights; "a4_ratio" = weight-only / MXFP4 and "a8_over_a4" = MXFP8 / MXFP4 over the replays paired in
+            order, "a4_p90_below_weight_only_p10" is the condition on MXFP4_MOE_A4_ABOVE_ROWS, "a4_quantise" the two MXFP4 quantisers.
 One JSON line per measurement on stdout."""
 import argparse
 import json
@@ -258,7 +262,7 @@ def bench_moe(dev, iters, nbuf=16, rows=ROWS):
                           "us_p50_p10_p90": replay_us(layers, x)}), flush=True)
 
 
-def bench_moe_act(dev, iters, nbuf=16, rows=(64, 128, 512, 2048)):
+def bench_moe_act(dev, iters, nbuf=16, rows=(64, 128, 512, 2048), a4=False):
     gen = torch.Generator(device=dev).manual_seed(1)
     e, d, ff, k = 128, 2048, 768, 8
     geo = dict(num_layers=1, dim_model=d, num_heads=32, dim_head=128, num_kv_heads=4, dim_ff=ff, model_type="qwen3_moe", qk_norm="head",
@@ -268,7 +272,7 @@ def bench_moe_act(dev, iters, nbuf=16, rows=(64, 128, 512, 2048)):
     for dt in ("half", "bfloat16"):
         layers = []
         for _ in range(nbuf):
-            layer = Mxfp4MoEEncoderLayer(ModelConfig(dtype=dt, **geo), QuantConfig(11, 32, act_quant="mxfp8"), 0)
+            layer = Mxfp4MoEEncoderLayer(ModelConfig(dtype=dt, **geo), QuantConfig(11, 32), 0)
             layer.m_thres = 0                                      # the grouped form at every row count
             layer.router = (torch.randn(e, d, device=dev, generator=gen) / d ** 0.5).to(layer.cfg.torch_dtype)
             layer.w_up = ops.Mxfp4MoEWeight(u8(0, 256, e, 2 * ff, d // 2), u8(120, 123, e, 2 * ff, d // 32), True)
@@ -281,11 +285,18 @@ def bench_moe_act(dev, iters, nbuf=16, rows=(64, 128, 512, 2048)):
             def quantise(layer):
                 ops.mxfp8_quantize(x)
                 ops.mxfp8_quantize(act)
-            legs = {"weight_only": (1 << 30, lambda layer: layer.moe(x)), "a8": (32, lambda layer: layer.moe(x)), "quantise": (32, quantise)}
+
+            def quantise4(layer):
+                ops.mxfp4_act_quantize(x)
+                ops.mxfp4_act_quantize(act)
+            moe = lambda layer: layer.moe(x)  # noqa: E731
+            legs = {"weight_only": ("", moe), "a8": ("mxfp8", moe), "quantise": ("", quantise)}
+            if a4:
+                legs.update({"a4": ("mxfp4", moe), "a4_quantise": ("", quantise4)})
             graphs = {}
-            for leg, (above, run) in legs.items():
-                for layer in layers:
-                    layer.a8_above_rows = above
+            for leg, (act_quant, run) in legs.items():
+                for layer in layers:                               # the route of the leg, above 32 rows
+                    layer.quant, layer.a8_above_rows, layer.a4_above_rows = QuantConfig(11, 32, act_quant=act_quant), 32, 32
                 run(layers[0])
                 torch.cuda.synchronize()
                 graphs[leg] = torch.cuda.CUDAGraph()
@@ -299,11 +310,18 @@ def bench_moe_act(dev, iters, nbuf=16, rows=(64, 128, 512, 2048)):
             del graphs
             ratio = quantiles([a / b for a, b in zip(times["weight_only"], times["a8"])])
             w16, a8, qt = (us(times[leg], nbuf) for leg in ("weight_only", "a8", "quantise"))
-            print(json.dumps({"what": "moe_act", "dtype": dt, "rows": m, "pairs": m * k, "bm_weight_only": ops.mxfp4_moe_bm(m * k, e),
-                              "bm_a8": ops.mxfp4_moe_a8_bm(m * k, e), "buffers": nbuf, "weight_only_us_p50_p10_p90": w16,
-                              "a8_us_p50_p10_p90": a8, "ratio_p50_p10_p90": [round(r, 3) for r in ratio],
-                              "a8_p90_below_weight_only_p10": a8[2] < w16[1], "quantise_us_p50_p10_p90": qt,
-                              "quantise_share": round(qt[0] / a8[0], 3)}), flush=True)
+            rec = {"what": "moe_act", "dtype": dt, "rows": m, "pairs": m * k, "bm_weight_only": ops.mxfp4_moe_bm(m * k, e),
+                   "bm_a8": ops.mxfp4_moe_a8_bm(m * k, e), "buffers": nbuf, "weight_only_us_p50_p10_p90": w16,
+                   "a8_us_p50_p10_p90": a8, "ratio_p50_p10_p90": [round(r, 3) for r in ratio],
+                   "a8_p90_below_weight_only_p10": a8[2] < w16[1], "quantise_us_p50_p10_p90": qt,
+                   "quantise_share": round(qt[0] / a8[0], 3)}
+            if a4:
+                r4, q4 = us(times["a4"], nbuf), us(times["a4_quantise"], nbuf)
+                paired = lambda num: [round(r, 3) for r in quantiles([a / b for a, b in zip(times[num], times["a4"])])]  # noqa: E731
+                rec.update({"bm_a4": ops.mxfp4_moe_a4_bm(m * k, e), "a4_us_p50_p10_p90": r4, "a4_ratio_p50_p10_p90": paired("weight_only"),
+                            "a8_over_a4_p50_p10_p90": paired("a8"), "a4_p90_below_weight_only_p10": r4[2] < w16[1],
+                            "a4_quantise_us_p50_p10_p90": q4, "a4_quantise_share": round(q4[0] / r4[0], 3)})
+            print(json.dumps(rec), flush=True)
         del layers
         torch.cuda.empty_cache()
 
@@ -354,9 +372,7 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.moe:
-        if args.act == "mxfp4":
-            ap.error("--moe --act mxfp4: the experts have no MXFP4-activation route")
-        return bench_moe_act(dev, args.iters) if args.act else bench_moe(dev, args.iters)
+        return bench_moe_act(dev, args.iters, a4=args.act == "mxfp4") if args.act else bench_moe(dev, args.iters)
     if args.act:
         return bench_act(dev, args.iters, args.layers, a4=args.act == "mxfp4")
     if not args.no_linears:

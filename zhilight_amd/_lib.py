@@ -53,6 +53,7 @@ SYMBOLS = [
     "zl_mxfp4_route", "zl_mxfp4_linear", "zl_mxfp4_dequant", "zl_mxfp8_quantize", "zl_mxfp4_a8_linear",
     "zl_mxfp4_act_quantize", "zl_mxfp4_a4_linear",
     "zl_mxfp4_moe_bm", "zl_mxfp4_moe_grouped", "zl_mxfp4_moe_pairs", "zl_mxfp4_moe_a8_bm", "zl_mxfp4_moe_a8_grouped",
+    "zl_mxfp4_moe_a4_bm", "zl_mxfp4_moe_a4_grouped",
 ]
 
 

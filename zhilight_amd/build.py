@@ -18,11 +18,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # per-source extras.  w4_slab.hip: its item loops (up to 4 groups x 8 tiles, the next group's normalisation in slices between the
 # items) must unroll completely -- ring slots, accumulators and wait counts are static only then -- and the NORM instantiations
 # exceed the unroller's default budget for `#pragma unroll` (16 K): the ring went to scratch behind dynamic indices
-# mxfp4_a8.hip, mxfp4_a4.hip, mxfp4_moe.hip, mxfp4_moe_a8.hip: scalar fp32 arithmetic only -- the quantiser's element loop, the accumulator updates of
-# the quad walk and the epilogues (mxfp4_moe_a8.hip promises mxfp4_a8.hip's bits) are not to be vectorised into v_pk_*_f32
+# mxfp4_a8.hip, mxfp4_a4.hip, mxfp4_moe.hip, mxfp4_moe_a8.hip, mxfp4_moe_a4.hip: scalar fp32 arithmetic only -- the quantiser's element loop, the
+# accumulator updates of the quad walk and the epilogues (mxfp4_moe_a8.hip promises mxfp4_a8.hip's bits, mxfp4_moe_a4.hip mxfp4_a4.hip's) are
+# not to be vectorised into v_pk_*_f32
 _SCALAR_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"w4_slab.hip": ["-mllvm", "-pragma-unroll-threshold=200000"],
-               "mxfp4_a8.hip": _SCALAR_F32, "mxfp4_a4.hip": _SCALAR_F32, "mxfp4_moe.hip": _SCALAR_F32, "mxfp4_moe_a8.hip": _SCALAR_F32}
+               "mxfp4_a8.hip": _SCALAR_F32, "mxfp4_a4.hip": _SCALAR_F32, "mxfp4_moe.hip": _SCALAR_F32, "mxfp4_moe_a8.hip": _SCALAR_F32,
+               "mxfp4_moe_a4.hip": _SCALAR_F32}
 
 
 # ZL_BUILD_EXPERIMENTAL=1: also build what was measured and left off the product path: the loader /

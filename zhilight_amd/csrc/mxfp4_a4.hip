@@ -34,19 +34,16 @@
 // two A register buffers: whole contiguous KBs either way, no bank conflicts.  The scale dwords of tile w go the same way.  Two LDS
 // buffers (2 x 17 KB), ONE barrier per super-step: buffer (S + 1) & 1 is written after the multiplies of S and was last read in
 // S - 1, before the barrier that ended it.
-// WHAT THE COMPILER NEEDED (each found in the assembly, see the comments at the code): every global load is unconditional -- a block
+// WHAT THE COMPILER NEEDED (each found in the assembly, see the comments at the code, zl_mxfp4_a4.h): every global load is unconditional -- a block
 // past K / 32 selects the ADDRESS of a zero block (scale byte 127), so it reads exact zeros -- because a load under a branch turns
 // the following waits into vmcnt(0); an empty asm statement after each row tile's MFMAs pins the source order, or all 64 MFMAs of a
 // super-step sink below its loads and the kernel spills; K / 32 % 4 is a template argument.
 // Rows / columns past M / N are clamped for the loads and not stored; a wave whose 64 columns lie past N multiplies nothing but
 // stays for the staging and the barriers.
-#include <type_traits>
-
-#include "zl_mxfp4.h"
+#include "zl_mxfp4_a4.h"
 
 namespace {
 
-typedef int i8v __attribute__((ext_vector_type(8)));
 typedef mx_f4 f4;
 
 // ---- quantiser ---------------------------------------------------------------------------------------------------------------
@@ -115,52 +112,8 @@ struct Mx4A4Params : Mx4Params {
     int mtiles;                 // ceil(m / 64)
 };
 
-constexpr int kA4T = 4;         // 16 x 16 tiles per wave along M and along N
+constexpr int kA4T = kA4TN;     // 16 x 16 tiles per wave along M and along N (the step, the zero block and the guarded loads: zl_mxfp4_a4.h)
 constexpr int kA4Rows = 16 * kA4T, kA4Cols = 4 * 16 * kA4T;      // workgroup tile 64 x 256
-
-__device__ __forceinline__ i8v mx_a4_operand(const uint4& q) { return (i8v){(int)q.x, (int)q.y, (int)q.z, (int)q.w, 0, 0, 0, 0}; }
-
-// MFMA step J of a super-step: the 16 tiles of the wave on block 16 S + 4 g + J, scale byte J of the super-step's dwords.  After a
-// row tile's four MFMAs `next(tm)` asks LDS for that row tile's piece of the FOLLOWING step (into the other A buffer): it is used a
-// whole step later.
-template <int J, class Next>
-__device__ __forceinline__ void mx_a4_step(const uint4 (&a)[kA4T], const uint4 (&b)[kA4T], const uint32_t (&sa)[kA4T],
-                                           const uint32_t (&sb)[kA4T], f4 (&acc)[kA4T][kA4T], Next next) {
-#pragma unroll
-    for (int tm = 0; tm < kA4T; ++tm) {
-#pragma unroll
-        for (int tn = 0; tn < kA4T; ++tn)
-            acc[tm][tn] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(mx_a4_operand(a[tm]), mx_a4_operand(b[tn]), acc[tm][tn], 4, 4, J,
-                                                                           (int)sa[tm], J, (int)sb[tn]);
-        // an empty statement that pins the source order of loads and MFMAs: left alone, instruction selection sinks all 64 MFMAs of a
-        // super-step below its loads -- four steps of A and B live at once, past 256 VGPRs into scratch -- and no load may cross it,
-        // so the prefetch distances below are the ones that run
-        asm volatile("" : "+v"(acc[tm][0]), "+v"(acc[tm][1]), "+v"(acc[tm][2]), "+v"(acc[tm][3]) : : "memory");
-        next(tm);
-    }
-}
-
-// What a block past the last one reads as: zero codes under scale byte 127.  Never written, and NOT const: a constant would be
-// folded into the kernel and the selected load below would turn back into a load under a branch.
-__device__ uint4 kA4ZeroCodes = {0u, 0u, 0u, 0u};
-__device__ uint32_t kA4UnitScales = 0x7f7f7f7fu;
-
-// The 16 bytes of block blk of a row of codes; GUARD: a block past the last one reads the zero block instead.  The ADDRESS is
-// selected and the load is unconditional: after a load under a branch the compiler's wait counts can no longer tell how many
-// younger loads are in flight and every wait becomes vmcnt(0) -- a step would wait for the operands it has just asked for.
-template <bool GUARD>
-__device__ __forceinline__ uint4 mx_a4_block(const uint8_t* row, int blk, int nb) {
-    const uint4* at = reinterpret_cast<const uint4*>(row + (size_t)blk * 16);
-    if (GUARD) at = blk < nb ? at : &kA4ZeroCodes;
-    return *at;
-}
-// mx_scale4 with the dword form's load unconditional for the same reason.  DW (K / 32 % 4 == 0, every model shape) is a template
-// argument: the byte-by-byte form loads under branches, and a kernel that merely CONTAINS it loses its wait counts
-template <bool DW>
-__device__ __forceinline__ uint32_t mx_a4_scale4(const uint8_t* srow, int b0, int nb) {
-    if (!DW) return mx_scale4(srow, b0, nb, false);
-    return *(b0 < nb ? reinterpret_cast<const uint32_t*>(srow + b0) : &kA4UnitScales);
-}
 
 template <int DT, bool DW>
 __global__ __launch_bounds__(256, 2) void k_mxfp4_a4(const Mx4A4Params p) {

@@ -258,7 +258,7 @@ __device__ __forceinline__ void mx_run(const Mx4Params& p, const uint32_t* __res
     }
 }
 
-// ---- what the scaled-MFMA kernels share (mxfp4_a8.hip, mxfp4_a4.hip, mxfp4_moe_a8.hip) --------------------------------------------------
+// ---- what the scaled-MFMA kernels share (mxfp4_a8.hip, mxfp4_a4.hip, mxfp4_moe_a8.hip, mxfp4_moe_a4.hip; FP4 x FP4 alone: zl_mxfp4_a4.h) ----
 // the four scale bytes of blocks b0 .. b0 + 3 of a row (b0 % 4 == 0); blocks past nb read as 127 (their codes are zeros)
 __device__ __forceinline__ uint32_t mx_scale4(const uint8_t* srow, int b0, int nb, bool dwords) {
     if (dwords) return b0 < nb ? *reinterpret_cast<const uint32_t*>(srow + b0) : 0x7f7f7f7fu;
@@ -269,7 +269,7 @@ __device__ __forceinline__ uint32_t mx_scale4(const uint8_t* srow, int b0, int n
     return v;
 }
 
-// ---- what the expert-stack kernels share (mxfp4_moe.hip, mxfp4_moe_a8.hip) ------------------------------------------------------
+// ---- what the expert-stack kernels share (mxfp4_moe.hip, mxfp4_moe_a8.hip, mxfp4_moe_a4.hip) ----------------------------------------
 struct Mx4MoeParams : Mx4Params {       // x, ldx, y, n, k, nb, epi; codes / scales: expert 0's; bias = residual = nullptr; m unused
     int x_rows, y_rows;
     int64_t stride_codes, stride_scales;  // bytes between experts

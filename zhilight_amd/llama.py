@@ -128,7 +128,8 @@ class QuantConfig:
     (Mxfp4MoEEncoderLayer) the q|k|v and attn_out linears follow act_quant, and so do the EXPERTS in chunks of more than
     MXFP4_MOE_A8_ABOVE_ROWS token rows (ops.mxfp4_moe_a8_grouped); at or below it they stay weight-only.  "mxfp4" = W4A4, what Quark's
     MXFP4 exports are calibrated for: linears over more than MXFP4_A4_ABOVE_ROWS rows quantise their input to OCP MXFP4 and run on
-    the FP4 x FP4 scaled MFMA (ops.mxfp4_a4_linear); the experts of an MoE model stay weight-only under it."""
+    the FP4 x FP4 scaled MFMA (ops.mxfp4_a4_linear); the experts of an MoE model follow in chunks of more than MXFP4_MOE_A4_ABOVE_ROWS
+    token rows (ops.mxfp4_moe_a4_grouped) and stay weight-only at or below it."""
     quant_type: int = 5
     group_size: int = 128
     sym: bool = False
@@ -661,6 +662,13 @@ MXFP4_A4_ABOVE_ROWS = 32
 # the MXFP8 route's p90 is below the weight-only route's p10 (1.9 x at 64 and 128 rows, 3.0 x at 512, 2.5 x at 2048) -- so the route
 # starts AT 64 rows; 33 .. 63 rows were not measured and stay weight-only.
 MXFP4_MOE_A8_ABOVE_ROWS = 63
+# ... and the same boundary under act_quant == "mxfp4": a chunk of MORE token rows than this runs ops.mxfp4_act_quantize +
+# ops.mxfp4_moe_a4_grouped.  Never below MXFP4_A4_ABOVE_ROWS.  The rule: the route starts at the smallest measured row count (64, 128,
+# 512, 2048: tools/bench_mxfp4.py --moe --act mxfp4, profiles/mxfp4_moe_a4.txt; DESIGN 4, "MXFP4 activations for the experts") at
+# which its p90 is below the weight-only route's p10; unmeasured row counts stay weight-only.  Measured: that holds from 64 rows on
+# (1.87 x at 64 and 128 rows, 3.1 x at 512, 3.3 x at 2048 in fp16) -- so the route starts AT 64 rows.  Against the MXFP8 route it is
+# level up to 512 rows (0.97 - 1.05 x) and 1.3 x ahead at 2048.
+MXFP4_MOE_A4_ABOVE_ROWS = 63
 
 
 class Mxfp4Linear:
@@ -796,8 +804,10 @@ class Mxfp4MoEEncoderLayer(Mxfp4EncoderLayer):
     active experts.  QuantConfig.act_quant == "mxfp8" reaches q|k|v and attn_out and, in chunks of more than a8_above_rows (=
     MXFP4_MOE_A8_ABOVE_ROWS) token rows, the experts: the rows are quantised to MXFP8 once per projection and both grouped launches run
     on the scaled MFMA (ops.mxfp4_moe_a8_grouped); shorter chunks and decode steps stay weight-only, bit for bit.  Under act_quant ==
-    "mxfp4" q|k|v and attn_out take the W4A4 route and the EXPERTS STAY WEIGHT-ONLY: there is no expert-grouped A4 launch yet.  Not
-    with tensor or expert parallelism or shared experts (ZLError)."""
+    "mxfp4" q|k|v and attn_out take the W4A4 route and so do the experts in chunks of more than a4_above_rows (=
+    MXFP4_MOE_A4_ABOVE_ROWS) token rows: ops.mxfp4_act_quantize once per projection and both grouped launches on the FP4 x FP4 scaled
+    MFMA (ops.mxfp4_moe_a4_grouped); shorter chunks and decode steps stay weight-only, bit for bit.  Not with tensor or expert
+    parallelism or shared experts (ZLError)."""
 
     def __init__(self, cfg: ModelConfig, quant: QuantConfig, idx: int):
         if cfg.model_type != "qwen3_moe":
@@ -814,6 +824,8 @@ class Mxfp4MoEEncoderLayer(Mxfp4EncoderLayer):
         self.m_thres = int(os.environ.get("MXFP4_MOE_M_THRES", _MXFP4_MOE_M_THRES_DEFAULT) or 0)
         # act_quant == "mxfp8": chunks of more token rows than this take the MXFP8 route of the experts
         self.a8_above_rows = max(MXFP4_MOE_A8_ABOVE_ROWS, MXFP4_A8_ABOVE_ROWS)
+        # act_quant == "mxfp4": ... the W4A4 route of the experts
+        self.a4_above_rows = max(MXFP4_MOE_A4_ABOVE_ROWS, MXFP4_A4_ABOVE_ROWS)
         self.router = self.w_up = self.w_down = None
         self.last_route = None
 
@@ -884,6 +896,13 @@ class Mxfp4MoEEncoderLayer(Mxfp4EncoderLayer):
             act = ops.mxfp4_moe_a8_grouped(xq, xs, self.w_up, xn.dtype, loads[:e], order, p, in_div=k, epilogue=ops.EPI_SILU_MUL)
             aq, as_ = ops.mxfp8_quantize(act)
             down = ops.mxfp4_moe_a8_grouped(aq, as_, self.w_down, xn.dtype, loads[:e], order, p, out_scatter=True)
+            return ops.moe_sum_experts(down, pair, weights)
+        if self.quant.act_quant == "mxfp4" and t > self.a4_above_rows:
+            # the same steps on MXFP4 activations: W4A4
+            xq, xs = ops.mxfp4_act_quantize(xn)
+            act = ops.mxfp4_moe_a4_grouped(xq, xs, self.w_up, xn.dtype, loads[:e], order, p, in_div=k, epilogue=ops.EPI_SILU_MUL)
+            aq, as_ = ops.mxfp4_act_quantize(act)
+            down = ops.mxfp4_moe_a4_grouped(aq, as_, self.w_down, xn.dtype, loads[:e], order, p, out_scatter=True)
             return ops.moe_sum_experts(down, pair, weights)
         act = ops.mxfp4_moe_grouped(xn, self.w_up, loads[:e], order, p, in_div=k, epilogue=ops.EPI_SILU_MUL)
         down = ops.mxfp4_moe_grouped(act, self.w_down, loads[:e], order, p, out_scatter=True)

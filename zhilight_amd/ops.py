@@ -3819,3 +3819,48 @@ def mxfp4_moe_a8_grouped(xq, xs, w: Mxfp4MoEWeight, dtype, expert_loads, index, 
                                         _p(out), _i(rows), _i(w.n), _i(w.k), C.c_int(_dt(out)), C.c_int(epilogue), _stream()),
           "mxfp4_moe_a8_grouped")
     return out
+
+
+# ---- MXFP4 expert stacks on MXFP4 activations, W4A4 (include/zhilight_amd.h "MXFP4", EXPERT STACKS ON MXFP4 ACTIVATIONS; csrc/mxfp4_moe_a4.hip)
+def mxfp4_moe_a4_bm(pairs, num_experts):
+    """rows per tile of a zl_mxfp4_moe_a4_grouped launch over `pairs` sorted rows: 16, 32 or 64 (one kernel at three heights)"""
+    return int(lib().zl_mxfp4_moe_a4_bm(_i(pairs), _i(num_experts)))
+
+
+def mxfp4_moe_a4_grouped(xq, xs, w: Mxfp4MoEWeight, dtype, expert_loads, index, pairs, in_div=0, out_scatter=False, out=None,
+                         out_rows=None, epilogue=0):
+    """zl_mxfp4_moe_a4_grouped: mxfp4_moe_grouped on MXFP4 activations (mxfp4_act_quantize's codes xq (rows, K/2) and scales xs
+    (rows, K/32)), on the FP4 x FP4 scaled MFMA, T = dtype (fp16 / bf16).  Positions, index, in_div, out_scatter, out and epilogue as
+    in mxfp4_moe_grouped.  Row j has the bits of mxfp4_a4_linear on the same xq / xs row and the same expert's matrix."""
+    _chk_cuda(xq, xs, expert_loads, index)
+    if xq.dtype != torch.uint8 or xs.dtype != torch.uint8 or xq.dim() != 2 or not (xq.is_contiguous() and xs.is_contiguous()):
+        raise ZLError("mxfp4_moe_a4_grouped: xq (rows, K/2) and xs (rows, K/32) are contiguous uint8 tensors")
+    m, k = xq.shape[0], 2 * xq.shape[1]
+    if k != w.k:
+        raise ZLError("mxfp4_moe_a4_grouped: size K mismatch")
+    if m < 1 or k % MXFP4_BLOCK or tuple(xs.shape) != (m, k // MXFP4_BLOCK):
+        raise ZLError(f"mxfp4_moe_a4_grouped: xs {tuple(xs.shape)} is not (rows, K/32) = ({m}, {k // MXFP4_BLOCK})")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ZLError("mxfp4_moe_a4_grouped: dtype is torch.float16 or torch.bfloat16")
+    if epilogue not in (0, EPI_SILU_MUL) or (epilogue and not w.row_interleave):
+        raise ZLError("mxfp4_moe_a4_grouped: epilogue 0, or the silu*mul of a row-interleaved gate|up stack")
+    n_out = w.n // 2 if epilogue else w.n
+    if expert_loads.dtype != torch.int32 or expert_loads.numel() != w.experts:
+        raise ZLError("mxfp4_moe_a4_grouped: expert_loads is one int32 per expert of the stack")
+    if index is not None and (index.dtype != torch.int32 or index.numel() < pairs):
+        raise ZLError("mxfp4_moe_a4_grouped: index holds pairs int32")
+    if index is None and (in_div or out_scatter):
+        raise ZLError("mxfp4_moe_a4_grouped: gathering or scattering rows needs the index")
+    rows = out_rows if out_rows is not None else pairs
+    if out is None:
+        out = torch.empty((rows, n_out), dtype=dtype, device=xq.device)
+    else:
+        _chk_out(out, rows, n_out, dtype, xq.device, "mxfp4_moe_a4_grouped")
+    if pairs == 0:
+        return out
+    sc, ss = w.stride_bytes
+    check(lib().zl_mxfp4_moe_a4_grouped(_p(xq), _p(xs), _i(m), _p(w.codes), _p(w.scales), _i(w.experts), _i(sc), _i(ss),
+                                        _p(expert_loads), _p(index), _i(pairs), C.c_int(int(in_div)), C.c_int(int(bool(out_scatter))),
+                                        _p(out), _i(rows), _i(w.n), _i(w.k), C.c_int(_dt(out)), C.c_int(epilogue), _stream()),
+          "mxfp4_moe_a4_grouped")
+    return out
