@@ -1013,6 +1013,25 @@ int zl_prefill_attn_varlen_hist(const uint16_t* q, const int32_t* cu_seqlens_q, 
                                 const uint16_t* k_new, const uint16_t* v_new, uint16_t* out,
                                 const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
                                 int64_t d, float scale, int dtype, int groups, zl_stream_t s);
+/* Head size 64: zl_prefill_attn and zl_prefill_attn_varlen with D = 64, a kernel of its own (prefill_attn_d64.hip: 128-key tiles,
+ * no wave groups -- there is no `groups` and no `d` argument; the D = 128 entry points keep answering ZL_ESHAPE for d != 128).
+ *   q / out       (s_q, H, 64), varlen (total_q, H, 64) with task i's rows cu_seqlens_q[i] .. cu_seqlens_q[i + 1] - 1; fp16 or bf16
+ *   k / v         per task BSHD (len_buf, Hkv, 64) or BHSD (Hkv, len_buf, 64), already holding the chunk's own rows at pos0 ..
+ *   work          the table of zl_prefill_attn_varlen: (task, 64-row query tile) pairs, longest first
+ * The arithmetic is zl_prefill_attn's: out[q, h, :] = softmax_{j <= pos0 + q}(scale * q.K_j) . V, softmax in fp32 with the running
+ * maximum starting at -1e20, probabilities rounded to T into the P.V product, fp32 accumulation, one rounding to T; kv head =
+ * head / (H / Hkv).  A row's bits depend on its query row and the keys it sees only -- not on len_buf beyond them, on the other
+ * tasks of the launch or on which of the two entry points ran it -- and rows behind a task's last visible key are never read (they
+ * may hold NaN).  A wrong table never makes the kernel read or write outside the operands (items outside the tasks or past a task's
+ * rows are dropped, rows are clamped to total_q, keys to buf_lens[i]).  No allocation, no sync.  ZL_EINVAL: null operand, a count
+ * <= 0; ZL_ESHAPE: h % hkv, pos0 + s_q > len_buf; ZL_EDTYPE: not fp16 / bf16; ZL_ELIMIT: grid overflow.  There is no INT8-history
+ * and no shared-prefix form at D = 64. */
+int zl_prefill_attn_d64(const uint16_t* q, const uint16_t* k_buf, const uint16_t* v_buf, uint16_t* out, int64_t s_q,
+                        int64_t pos0, int64_t h, int64_t hkv, float scale, int64_t len_buf, int bshd, int dtype, zl_stream_t s);
+int zl_prefill_attn_d64_varlen(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                               const uint16_t* const* k_bufs, const uint16_t* const* v_bufs, uint16_t* out,
+                               const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
+                               float scale, int bshd, int dtype, zl_stream_t s);
 
 
 /* ------------------------------------------------------------------------------------------------

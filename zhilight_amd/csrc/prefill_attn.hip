@@ -486,7 +486,7 @@ extern "C" int zl_prefill_attn_ex(const uint16_t* q, const uint16_t* k_buf, cons
                                   int dtype, int groups, zl_stream_t s) {
     ZL_CHECK_ARG(q && k_buf && v_buf && out && s_q > 0 && pos0 >= 0 && h > 0 && hkv > 0 && len_buf > 0, ZL_EINVAL);
     ZL_CHECK_ARG(h % hkv == 0 && pos0 + s_q <= len_buf, ZL_ESHAPE);
-    ZL_CHECK_ARG(d == kD, ZL_ESHAPE);          // other head sizes: the mask form of zl_decode_attn
+    ZL_CHECK_ARG(d == kD, ZL_ESHAPE);          // head size 64: zl_prefill_attn_d64 (prefill_attn_d64.hip); others: the mask form of zl_decode_attn
     ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
     ZL_CHECK_ARG(h <= 65535, ZL_ELIMIT);
     const bool plain_map = groups == -1;               // A/B switch: one group, work items in plain dispatch order (the round-4 launch)

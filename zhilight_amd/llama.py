@@ -1411,7 +1411,8 @@ class _PromptRows:
                                  len_q = 1; (layers, scatter tasks) pointer tables, ks_rows / vs_rows None on an fp16 cache
       route, att_pos0s, len_bufs, len_bufs_dev, plan    what the attention reads (LLaMA._prompt_scatter_attend lists the routes): per
                                  task the first key row's position and the buffer rows (host; device for the mask form), and the
-                                 varlen plan (head size 128: several tasks, or the "q8" route)
+                                 varlen plan (kernel route: several tasks, or the "q8" route)
+      kernel                     LLaMA._prompt_attn_kernel() when the rows were built: the MFMA prompt kernels, not the mask form
       k_tab / v_tab / ks_tab / vs_tab, kv, kv_off    its buffers: (layers, n) pointer tables ("cache", "temp", "q8"); the one task's
                                  (layers, 2, rows, Hkv, D) tensor for the one-task launch ("cache", "temp"); "own": the byte offset
                                  of each task's first row in the call's k / v
@@ -1432,6 +1433,7 @@ class _PromptRows:
         """one task's piece at pos0; pos: its positions where the caller holds them already (a part of a dual-stream piece).  The
         labels are the one upload of this form"""
         r, c, dev = cls(), model.cfg, model.device
+        r.kernel = model._prompt_attn_kernel()
         s = int(prompt.numel())
         r.tasks, r.lens, r.cu, r.ends = [task], [s], [0, s], [pos0 + s]
         r.tokens = prompt.to(device=dev, dtype=torch.int32).contiguous()
@@ -1455,7 +1457,7 @@ class _PromptRows:
             r.k_tab, r.v_tab = tab[:, 0:1], tab[:, 1:2]
         elif ctx.kv_quant:
             r.route, r.att_pos0s, r.len_bufs = "own", [0], [s]
-            if c.dim_head != 128:                         # the mask form's tables; the one-task launch takes k3 / v3 themselves
+            if not r.kernel:                              # the mask form's tables; the one-task launch takes k3 / v3 themselves
                 r.len_bufs_dev = torch.tensor(r.len_bufs, dtype=torch.int32, device=dev)
                 r.kv_off = torch.zeros(1, dtype=torch.int64, device=dev)
         else:
@@ -1467,6 +1469,7 @@ class _PromptRows:
     def many(cls, model, ctx, tasks, prompts, pos0s, q8_history=False, labels=None, prefixes=None):
         """the pieces of n tasks back to back: the K/V scatter takes one "task" per row, the attention one table entry per task"""
         r, c, dev = cls(), model.cfg, model.device
+        r.kernel = model._prompt_attn_kernel()
         n = len(tasks)
         lens = [int(pr.numel()) for pr in prompts]
         total = sum(lens)
@@ -1509,7 +1512,7 @@ class _PromptRows:
             r.route, r.att_pos0s, r.len_bufs = "cache", pos0s, [ctx.max_len_buf] * n
             r.k_tab, r.v_tab = ctx.k_addrs.index_select(1, r.tasks_dev), ctx.v_addrs.index_select(1, r.tasks_dev)
             r.len_bufs_dev = ctx.buf_lens.index_select(0, r.tasks_dev)
-        if c.dim_head == 128:
+        if r.kernel:
             r.plan = ops.prefill_varlen_plan(lens, r.att_pos0s, r.len_bufs, dev)
         return r
 
@@ -2133,8 +2136,14 @@ class LLaMA:
             return ops.rope_cos_sin_yarn(pos, c.dim_head, c.rope_theta, rs["factor"], low, high, msc)
         raise ops.ZLError(f"rope_scaling type {kind!r} is not supported (supported: llama3, dynamic, yarn)")
 
+    def _prompt_attn_kernel(self):
+        """whether prompt attention runs on the MFMA prompt kernels: head size 128 always, head size 64 unless ZL_PREFILL_D64=0 (read
+        at call time, like ZL_ATTN_MFMA: the mask form, for A/B runs)"""
+        d = self.cfg.dim_head
+        return d == 128 or (d == 64 and os.environ.get("ZL_PREFILL_D64", "1") != "0")
+
     def _prefill_mask(self, s, len_buf, pos0=0):
-        """causal mask + workspace for head sizes the MFMA prefill kernel does not cover"""
+        """causal mask + workspace of the mask form (head sizes the MFMA prompt kernels do not cover; ZL_PREFILL_D64=0)"""
         key = ("prefill", s, len_buf, pos0)
         if key not in self._bufs:
             c, dev = self.cfg, self.device
@@ -2459,8 +2468,9 @@ class LLaMA:
                    and no prompt temporaries (attention.cpp:510-516).
           "hist"   the task's shared prefix buffer below pos0 and k3 / v3 from there on (admit(prefixes=): the own buffer holds nothing
                    below pos0).
-        Head size 128: the MFMA kernels -- the one-task launch on the task's tensors, or one varlen launch over the tables of
-        several tasks; other head sizes: per task the mask form of multi_query_attention_rag_buffer."""
+        Head sizes 128 and 64 (r.kernel): the MFMA kernels -- the one-task launch on the task's tensors, or one varlen launch over
+        the tables of several tasks ("q8" / "hist": head size 128 only, refused before this); other head sizes, and head size 64
+        under ZL_PREFILL_D64=0: per task the mask form of multi_query_attention_rag_buffer."""
         c = self.cfg
         h, hkv, d = c.num_heads, c.num_kv_heads, c.dim_head
         scale = 1.0 / math.sqrt(d)
@@ -2472,7 +2482,7 @@ class LLaMA:
                                          len_q=r.len_q)
             if r.route == "temp":
                 ops.copy_to_rag_buffer2(r.placement, r.len_bufs_dev, k4, v4, r.k_tab[li], r.v_tab[li])
-        if d == 128:
+        if r.kernel:
             if r.route == "hist":
                 return ops.prefill_attention_varlen_hist(q3, r.lens, r.att_pos0s, k3, v3, r.k_tab[li], r.v_tab[li], r.hist_lens, r.len_bufs,
                                                          hkv, scale, plan=r.plan, hist_lens_dev=r.hist_lens_dev)

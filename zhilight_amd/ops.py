@@ -2585,7 +2585,8 @@ def multi_query_attention_rag_buffer_quant(batch_q, buf_lens, key_buf_addrs, val
 def prefill_attention(q, k_buf, v_buf, pos0, num_kv_heads, scale, bshd=True, out=None, groups=None):
     """Causal attention of one task's prompt chunk (attn_encode_group -> flash attention in the reference,
     src/nn/attention/attention.cpp:442-622).  q (s_q, H, D); k_buf / v_buf the task's buffers (len_buf, Hkv, D)
-    [bshd] or (Hkv, len_buf, D), already holding the chunk's rows at pos0 .. pos0 + s_q - 1."""
+    [bshd] or (Hkv, len_buf, D), already holding the chunk's rows at pos0 .. pos0 + s_q - 1.  D = 128 (zl_prefill_attn_ex) or
+    64 (zl_prefill_attn_d64: a kernel without wave groups, `groups` None / 0 / 1 only)."""
     _chk_cuda(q, k_buf, v_buf)
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise ZLError("prefill_attention: fp16 / bf16 only")
@@ -2593,10 +2594,23 @@ def prefill_attention(q, k_buf, v_buf, pos0, num_kv_heads, scale, bshd=True, out
     len_buf = k_buf.shape[0] if bshd else k_buf.shape[1]
     if out is None:
         out = torch.empty_like(q)
+    if d == 64:
+        _no_groups_d64("prefill_attention", groups)
+        check(lib().zl_prefill_attn_d64(_p(q), _p(k_buf), _p(v_buf), _p(out), _i(s_q), _i(pos0), _i(h), _i(num_kv_heads), _f(scale),
+                                        _i(len_buf), C.c_int(int(bshd)), C.c_int(_dt(q)), _stream()), "prefill_attn_d64")
+        return out
+    if d != 128:
+        raise ZLError(f"prefill_attention: head size {d}: the prompt-attention kernels cover 64 and 128")
     groups = int(os.environ.get("ZL_PREFILL_GROUPS", "0") or 0) if groups is None else groups     # 0: the launcher's choice
     check(lib().zl_prefill_attn_ex(_p(q), _p(k_buf), _p(v_buf), _p(out), _i(s_q), _i(pos0), _i(h), _i(num_kv_heads), _i(d),
                                    _f(scale), _i(len_buf), C.c_int(int(bshd)), C.c_int(_dt(q)), C.c_int(groups), _stream()), "prefill_attn")
     return out
+
+
+def _no_groups_d64(what, groups):
+    """the head-size-64 kernel has no wave groups: only the launcher's choice (None / 0) or one group can be asked for"""
+    if groups not in (None, 0, 1):
+        raise ZLError(f"{what}: groups={groups} at head size 64: that kernel has no wave groups (None, 0 or 1)")
 
 
 def prefill_work_items(lens, pos0):
@@ -2674,13 +2688,24 @@ def prefill_attention_varlen(q, lens, pos0, k_addrs, v_addrs, buf_lens, num_kv_h
     src/nn/attention/attention.cpp:442-562, as one varlen call).  q (total_q, H, D): task i's rows back to back, lens[i] of them, at
     positions pos0[i] ..; k_addrs / v_addrs device int64 tables of the tasks' K/V buffers (buf_lens[i] rows each, BSHD or BHSD),
     which already hold the chunks' own rows.  lens / pos0 / buf_lens are host ints (checked here); `plan` (prefill_varlen_plan of
-    the same lists) spares the upload when several layers share it.  Per task bit-identical to prefill_attention(.., groups)."""
+    the same lists) spares the upload when several layers share it.  Per task bit-identical to prefill_attention(.., groups).
+    D = 128 or 64 (zl_prefill_attn_d64_varlen; `groups` as for prefill_attention)."""
     _chk_cuda(q, k_addrs, v_addrs)
-    plan, out, groups = _varlen_args("prefill_attention_varlen", q, lens, pos0, buf_lens, plan, out, groups)
     total_q, h, d = q.shape
+    if d not in (64, 128):
+        raise ZLError(f"prefill_attention_varlen: head size {d}: the prompt-attention kernels cover 64 and 128")
+    if d == 64:
+        _no_groups_d64("prefill_attention_varlen", groups)
+    plan, out, groups = _varlen_args("prefill_attention_varlen", q, lens, pos0, buf_lens, plan, out, groups)
     for t in (k_addrs, v_addrs):
         if t.dtype != torch.int64 or t.numel() != plan.b:
             raise ZLError("prefill_attention_varlen: one int64 K / V pointer per task")
+    if d == 64:
+        check(lib().zl_prefill_attn_d64_varlen(_p(q), _p(plan.cu_seqlens_q), _p(plan.pos0_dev), _p(plan.buf_lens_dev), _p(k_addrs),
+                                               _p(v_addrs), _p(out), _p(plan.work), _i(plan.n_work), _i(plan.b), _i(total_q), _i(h),
+                                               _i(num_kv_heads), _f(scale), C.c_int(int(bshd)), C.c_int(_dt(q)), _stream()),
+              "prefill_attn_d64_varlen")
+        return out
     check(lib().zl_prefill_attn_varlen(_p(q), _p(plan.cu_seqlens_q), _p(plan.pos0_dev), _p(plan.buf_lens_dev), _p(k_addrs),
                                        _p(v_addrs), _p(out), _p(plan.work), _i(plan.n_work), _i(plan.b), _i(total_q), _i(h),
                                        _i(num_kv_heads), _i(d), _f(scale), C.c_int(int(bshd)), C.c_int(_dt(q)), C.c_int(groups),
