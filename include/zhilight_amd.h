@@ -695,12 +695,22 @@ int zl_decode_attn(const uint16_t* q, const int32_t* buf_lens, const uint16_t* c
                    const uint16_t* const* v_bufs, const int8_t* mask, const int32_t* valid_lens,
                    uint16_t* out, void* workspace, int64_t b, int64_t len_q, int64_t h, int64_t hkv,
                    int64_t d, float scale, int64_t max_len_buf, int bshd, int dtype, zl_stream_t s);
-/* algo: 0 = the launcher's choice (matrix-core kernel where it applies), 1 = the VALU split-KV kernel (the one masks,
- * D != 128 and more than 16 query rows per kv head always take) */
+/* algo: 0 = the launcher's choice (a matrix-core kernel where zl_decode_attn_kernel says so), 1 = the VALU split-KV kernel (the
+ * one that head sizes other than 64 and 128, more than 16 query rows per kv head, masks at D = 64 and masks with len_q > 1 or
+ * with valid_lens at D = 128 always take).
+ * D = 64, no mask, 2 <= len_q * H / Hkv <= 16 (one row per kv head measured faster on the VALU kernel and stays there):
+ * k_decode_attn_d64 (decode_attn_d64.hip) -- S^T = K . Q^T on v_mfma_f32_16x16x32 with K fragments straight from global memory,
+ * 64-key chunks per wave, probabilities rounded to T into P.V, the VALU route's grid, split length, fp32 split records and merge
+ * (zl_decode_attn_workspace_bytes is unchanged).  Keys at or behind min(buf_lens, valid_lens) are never loaded, a task without a
+ * visible key gets a zero row, a row's bits do not depend on the other rows of its kv head. */
 int zl_decode_attn_ex(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs,
                       const uint16_t* const* v_bufs, const int8_t* mask, const int32_t* valid_lens,
                       uint16_t* out, void* workspace, int64_t b, int64_t len_q, int64_t h, int64_t hkv,
                       int64_t d, float scale, int64_t max_len_buf, int bshd, int dtype, int algo, zl_stream_t s);
+/* The kernel zl_decode_attn_ex takes for a shape, by the launcher's own rule (host only, no device call): 1 = a matrix-core kernel
+ * (k_decode_attn_mfma at D = 128, k_decode_attn_d64 at D = 64), 0 = the VALU split-KV kernel.  masked: 0 = valid_lens alone,
+ * 1 = an int8 mask alone, 2 = a mask together with valid_lens.  Shapes the launcher refuses give 0. */
+int zl_decode_attn_kernel(int64_t len_q, int64_t h, int64_t hkv, int64_t d, int masked, int algo);
 
 /* Causal ("staircase") decode attention: the len_q rows of task b are the last token and len_q - 1 draft tokens of a speculative
  * step, row qi sees the keys j < min(buf_lens[b], valid_lens[b] + qi) -- what zl_decode_attn computes with the int8 mask
@@ -754,7 +764,12 @@ int zl_decode_attn_shared_ex(const uint16_t* q, const int32_t* buf_lens, const u
  * copy_to_rag_buffer2 + multi_query_attention_rag_buffer in one pass over the fused qkv rows
  * (B, (H + 2 Hkv) D).  q and the new k are rotated with the cached cos/sin (one rounding to T, as the
  * unfused kernels do), the new k/v row is stored at placement[b] by the workgroup whose KV split owns
- * that slot and consumed from registers, so results equal the three-kernel sequence. */
+ * that slot and consumed from registers, so results equal the three-kernel sequence.
+ * D = 64 and 2 <= H / Hkv <= 16 (zl_decode_attn_kernel's rule): the fused form of k_decode_attn_d64
+ * (decode_attn_d64.hip) -- q and the new k rotate in the MFMA fragment registers, the stored row is
+ * injected into the fragment of the lane that would have loaded it, and the output is
+ * zl_rope_scatter_decode + zl_decode_attn_ex(algo = 0)'s bit for bit.  Every other shape: the VALU
+ * split-KV kernel. */
 int zl_decode_attn_fused(const float* cosv, const float* sinv, const uint16_t* qkv, const int32_t* placement,
                          const int32_t* buf_lens, const int32_t* valid_lens, uint16_t* const* k_bufs,
                          uint16_t* const* v_bufs, uint16_t* out, void* workspace, int64_t b, int64_t h,

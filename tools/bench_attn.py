@@ -14,8 +14,89 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zhilight_amd import ops  # noqa: E402
 
 
+def head64(a):
+    """--d 64: the attention launch pair at head size 64, the matrix-core kernel (algo 0) against the VALU kernel (algo 1) and
+    zl_decode_attn_fused against rope_scatter_decode + algo 1.  One process, one hipGraph of `layers` launches per route, the
+    routes' replays alternated, HIP events around every replay: median [p10, p90] us per launch (pair)."""
+    dev, d = torch.device("cuda:0"), 64
+    dt = torch.bfloat16 if a.bf16 else torch.float16
+    i32 = dict(dtype=torch.int32, device=dev)
+    print(f"# head size 64, {'bf16' if a.bf16 else 'fp16'}, {'BHSD' if a.bhsd else 'BSHD'}, {a.layers} launches per replay, {a.iters} samples per route")
+    print("# H Hkv keys batch | algo0 (matrix cores) | algo1 (VALU) | fused | rope_scatter + algo1 | max |algo0 - algo1|, max |fused - unfused| of the outputs"
+          "      us per launch pair: median [p10, p90]")
+    for h, hkv in [tuple(int(v) for v in s.split(",")) for s in a.shapes.split(";")]:
+        for seq in [int(v) for v in a.seqs.split(",")]:
+            for batch in [int(v) for v in a.batches.split(",")]:
+                len_buf = (seq + 64 + 63) // 64 * 64
+                shape = (a.layers, 2, hkv, len_buf, d) if a.bhsd else (a.layers, 2, len_buf, hkv, d)
+                kv = [torch.randn(shape, dtype=dt, device=dev) for _ in range(batch)]
+                k_addrs = torch.tensor([[t[l, 0].data_ptr() for t in kv] for l in range(a.layers)], dtype=torch.int64, device=dev)
+                v_addrs = torch.tensor([[t[l, 1].data_ptr() for t in kv] for l in range(a.layers)], dtype=torch.int64, device=dev)
+                pos, buf_lens, valid = torch.full((batch,), seq, **i32), torch.full((batch,), len_buf, **i32), torch.full((batch,), seq + 1, **i32)
+                cos, sin = ops.rope_cos_sin(pos, d, 1e4, True, None)
+                qkv = torch.randn(batch, (h + 2 * hkv) * d, dtype=dt, device=dev)
+                q, out = torch.empty(batch, h * d, dtype=dt, device=dev), torch.empty(batch, h * d, dtype=dt, device=dev)
+                ws = ops.decode_attn_workspace(batch, 1, h, d, len_buf, dev)
+
+                def attn(l):
+                    ops.multi_query_attention_rag_buffer(q.view(batch, 1, h, d), buf_lens, k_addrs[l], v_addrs[l], None, 1.0 / math.sqrt(d),
+                                                         len_buf, hkv, valid_lens=valid, bshd=not a.bhsd, out=out.view(batch, 1, h, d), workspace=ws)
+
+                def scatter(l):
+                    ops.rope_scatter_decode(cos, sin, qkv, pos, buf_lens, k_addrs[l], v_addrs[l], h, hkv, d, bshd=not a.bhsd, q_out=q)
+
+                def fused(l):
+                    ops.decode_attention_fused(cos, sin, qkv, pos, buf_lens, valid, k_addrs[l], v_addrs[l], h, hkv, d, 1.0 / math.sqrt(d),
+                                               len_buf, bshd=not a.bhsd, out=out, workspace=ws)
+
+                scatter(0)
+                routes = (("0", (attn,)), ("1", (attn,)), ("0", (fused,)), ("1", (scatter, attn)))
+                graphs, outs, caller_algo = [], [], os.environ.get("ZL_ATTN_MFMA")
+                for algo, steps in routes:                     # the wrappers read ZL_ATTN_MFMA per call: the graph keeps the kernel
+                    os.environ["ZL_ATTN_MFMA"] = "1" if algo == "0" else "0"
+                    def run():
+                        for l in range(a.layers):
+                            for f in steps:
+                                f(l)
+                    run()                                      # once eagerly (code objects), then into the graph
+                    torch.cuda.synchronize()
+                    outs.append(out.float().clone())           # the last buffer set's rows, compared across the routes below
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        run()
+                    graphs.append(g)
+                if caller_algo is None:                        # the caller's setting again
+                    os.environ.pop("ZL_ATTN_MFMA")
+                else:
+                    os.environ["ZL_ATTN_MFMA"] = caller_algo
+                for g in graphs:
+                    g.replay()
+                torch.cuda.synchronize()
+                samples = [[] for _ in graphs]
+                for _ in range(a.iters):
+                    for g, s in zip(graphs, samples):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        g.replay()
+                        e1.record()
+                        e1.synchronize()
+                        s.append(e0.elapsed_time(e1) * 1e3 / a.layers)
+                cells = []
+                for s in samples:
+                    s.sort()
+                    cells.append(f"{s[len(s) // 2]:7.2f} [{s[len(s) // 10]:7.2f}, {s[len(s) * 9 // 10]:7.2f}]")
+                diff = f"{(outs[0] - outs[1]).abs().max().item():.2e} {(outs[2] - outs[3]).abs().max().item():.2e}"
+                print(f"{h:3d} {hkv:3d} {seq:5d} {batch:3d} | " + " | ".join(cells) + " | " + diff, flush=True)
+                del kv, graphs
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--d", type=int, default=128, choices=(64, 128), help="64: the head-size-64 leg (head64), algo 0 against algo 1 in one process")
+    ap.add_argument("--shapes", default="36,36;32,8;14,2;64,8", help="--d 64: H,Hkv pairs")
+    ap.add_argument("--seqs", default="1024,4096", help="--d 64: visible keys")
+    ap.add_argument("--batches", default="1,8,32", help="--d 64")
+    ap.add_argument("--bf16", action="store_true", help="--d 64: bf16 instead of fp16")
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--seq", type=int, default=1024)
     ap.add_argument("--layers", type=int, default=32)
@@ -25,6 +106,8 @@ def main():
     ap.add_argument("--unfused", action="store_true", help="rope+scatter launch, then zl_decode_attn (the matrix-core kernel when it applies)")
     ap.add_argument("--q8", action="store_true", help="INT8 KV cache: rope+quantise+scatter launch, then attention over codes")
     a = ap.parse_args()
+    if a.d == 64:
+        return head64(a)
     dev = torch.device("cuda:0")
     h, hkv, d = 32, 8, 128
     len_buf = (a.seq + 64 + 63) // 64 * 64

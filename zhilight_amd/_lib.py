@@ -37,7 +37,7 @@ SYMBOLS = [
     "zl_copy_to_rag_buffer2", "zl_copy_to_rag_buffer_bytes", "zl_kv_blocks_copy", "zl_kv_blocks_copy_ex", "zl_kv_fork", "zl_kv_fork_ex", "zl_rope_scatter_decode", "zl_w4a16_qkv_rope_scatter", "zl_w4a16_qkv_rope_scatter_ex", "zl_decode_attn_splits_h", "zl_decode_attn_splits_h_mask", "zl_decode_attn_combine_h", "zl_w4a16_gemm_attn_merge_h", "zl_w4a16_gemm_attn_merge_h_ex",
     "zl_quant_group_32", "zl_dequant_sum_quant_g32", "zl_dequant_group_32",
     "zl_fp8_calc_scale", "zl_fp8_cvt_half", "zl_fp8_gemm_nt",
-    "zl_decode_attn_workspace_bytes", "zl_decode_attn", "zl_decode_attn_ex", "zl_decode_attn_causal", "zl_decode_attn_fused",
+    "zl_decode_attn_workspace_bytes", "zl_decode_attn", "zl_decode_attn_ex", "zl_decode_attn_kernel", "zl_decode_attn_causal", "zl_decode_attn_fused",
     "zl_decode_attn_shared_workspace_bytes", "zl_decode_attn_shared", "zl_decode_attn_shared_ex",
     "zl_decode_attn_split_len", "zl_decode_attn_splits", "zl_w4a16_gemm_attn_merge",
     "zl_decode_attn_la_split_len", "zl_decode_attn_la_workspace_bytes", "zl_decode_attn_la",

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "zl_common.h"
+#include "decode_attn_d64.h"
 
 namespace {
 
@@ -1740,6 +1741,18 @@ int launch_valu_q8(const AttnParams& p, int64_t d, int dtype, hipStream_t st) {
     });
 }
 
+// head size 64 on the matrix cores (decode_attn_d64.hip): the partial launch over p's geometry, then the fp32 merge of the VALU route
+int launch_d64(const AttnParams& p, int dtype, hipStream_t st) {
+    DecodeD64Params g;
+    g.q = p.q; g.buf_lens = p.buf_lens; g.valid_lens = p.valid_lens; g.k_bufs = p.k_bufs; g.v_bufs = p.v_bufs; g.ws = p.ws;
+    g.b = p.b; g.len_q = p.len_q; g.h = p.h; g.hkv = p.hkv; g.n_rep = p.n_rep; g.rows = p.rows; g.split_len = p.split_len;
+    g.max_splits = p.max_splits; g.bshd = p.bshd; g.scale = p.scale;
+    g.qkv = p.qkv; g.cosv = p.cosv; g.sinv = p.sinv; g.placement = p.placement; g.k_bufs_w = p.k_bufs_w; g.v_bufs_w = p.v_bufs_w;
+    g.neox = p.neox;
+    ZL_ATTN_TRY(zl_decode_attn_d64_launch(g, dtype, st));
+    return launch_combine<64>(p, dtype, st);
+}
+
 // zl_decode_attn_splits / _splits_h / _splits_h_mask: one query row per task on the matrix-core kernel, records only, no merge
 int attn_splits(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs, const uint16_t* const* v_bufs,
                 const int8_t* mask, const int32_t* valid_lens, void* workspace, int64_t b, int64_t h, int64_t hkv, int64_t d,
@@ -1765,6 +1778,14 @@ int64_t zl_decode_attn_workspace_bytes(int64_t b, int64_t len_q, int64_t h, int6
     return b * len_q * h * splits * (d + 2) * 4;
 }
 
+int zl_decode_attn_kernel(int64_t len_q, int64_t h, int64_t hkv, int64_t d, int masked, int algo) {
+    if (len_q <= 0 || h <= 0 || hkv <= 0 || h % hkv != 0 || algo == 1 || len_q * (h / hkv) > 16) return 0;
+    if (d == kMD) return masked == 0 || (masked == 1 && len_q == 1);     // the mask form: one query row per task, no valid_lens
+    // decode_attn_d64.hip: prefix visibility only, and two query rows per kv head at least -- with one (MHA at len_q == 1) 15 of the
+    // 16 MFMA rows idle and the VALU kernel measured ahead (profiles/decode_attn_d64.txt: 9.6 against 10.0 us at batch 1)
+    return d == 64 && masked == 0 && len_q * (h / hkv) >= 2;
+}
+
 int zl_decode_attn(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs,
                    const uint16_t* const* v_bufs, const int8_t* mask, const int32_t* valid_lens, uint16_t* out,
                    void* workspace, int64_t b, int64_t len_q, int64_t h, int64_t hkv, int64_t d, float scale,
@@ -1788,8 +1809,9 @@ int zl_decode_attn_ex(const uint16_t* q, const int32_t* buf_lens, const uint16_t
     hipStream_t hs = (hipStream_t)s;
     // decode fast path on the matrix cores: all query rows of a kv head in one 16-row MFMA block
     // with the reference's visibility mask instead of prefix lengths: the same kernel's mask form, for one query row per task
-    if (algo != 1 && (!mask || (len_q == 1 && !valid_lens)) && d == kMD && p.rows <= 16) {
+    if (zl_decode_attn_kernel(len_q, h, hkv, d, mask ? (valid_lens ? 2 : 1) : 0, algo)) {
         p.passes = 1;
+        if (d == 64) return launch_d64(p, dtype, hs);
         ZL_ATTN_TRY(mask ? launch_mfma<4, false, 1, true>(p, dtype, hs) : launch_mfma<>(p, dtype, hs));
         return launch_combine<kMD>(p, dtype, hs);
     }
@@ -1985,6 +2007,10 @@ int zl_decode_attn_fused(const float* cosv, const float* sinv, const uint16_t* q
     p.qkv = qkv; p.cosv = cosv; p.sinv = sinv; p.placement = placement; p.k_bufs_w = k_bufs; p.v_bufs_w = v_bufs; p.neox = neox;
     ZL_ATTN_TRY(attn_geometry(p, b, 1, h, hkv, max_len_buf));
     ZL_ATTN_TRY(attn_set_passes(p, valu_rt(p.rows)));
+    if (d == 64 && zl_decode_attn_kernel(1, h, hkv, d, 0, 0)) {       // head size 64: the fused form of the matrix-core kernel
+        p.passes = 1;
+        return launch_d64(p, dtype, (hipStream_t)s);
+    }
     return launch_valu<true>(p, d, dtype, (hipStream_t)s);
 }
 

@@ -1530,6 +1530,9 @@ class _DecodeRoute:
     qkv: str                    # "w4" zl_w4a16_qkv_rope_scatter | "w8" layernorm_quant + w8a8_qkv_rope_scatter | "plain" project_qkv + rope / scatter
     norm: Optional[str]         # "w4" only, its RMSNorm: "fused" in registers | "launch" of its own | "row_ss" from statistics the projections hand on
     attn: str                   # "hook" | "shared" (zl_decode_attn_shared: a context with a prefix table) | "la" | "splits" (records left for attn_out) | "mqa" | "valu_fused" (rope / scatter included) | "quant"
+    # ("valu_fused" names the launch, zl_decode_attn_fused, not its kernel: at head size 64 with 2 .. 16 query heads per kv head that
+    # launch runs the matrix-core kernel of decode_attn_d64.hip, and the name is historical; with one head per kv head -- MiniCPM-2B --
+    # and at every other head size it is the VALU kernel)
     out: str                    # "merge" w4_attn_out_merge | "merge_gate_up" w4_attn_out_gate_up, "merge" where it declines | "linear" attn_out_add
     skip_attn: bool             # bench.py's legs, resolved against the route: stage 2 is left out ...
     skip_proj: bool             # ... stages 1 and 3 are

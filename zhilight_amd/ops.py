@@ -2180,6 +2180,15 @@ def w4_qkv_rope_scatter(x, w, cos, sin, placement, buf_lens, k_addrs, v_addrs, n
     return q_out
 
 
+def decode_attn_kernel(len_q, h, num_kv_heads, d, masked=False, valid_lens=False, algo=None):
+    """The kernel multi_query_attention_rag_buffer takes for a shape (zl_decode_attn_kernel, host only): 1 = a matrix-core kernel
+    (D = 128, and D = 64 without a mask), 0 = the VALU split-KV kernel.  masked / valid_lens: whether the call carries a mask /
+    valid lengths (no mask means valid lengths); algo None: the one the wrappers pass (ZL_ATTN_MFMA)."""
+    m = (2 if valid_lens else 1) if masked else 0
+    return int(lib().zl_decode_attn_kernel(_i(len_q), _i(h), _i(num_kv_heads), _i(d), C.c_int(m),
+                                           C.c_int(_attn_algo() if algo is None else int(algo))))
+
+
 def decode_attn_workspace(b, len_q, h, d, max_len_buf, device):
     nbytes = lib().zl_decode_attn_workspace_bytes(_i(b), _i(len_q), _i(h), _i(d), _i(max_len_buf))
     if nbytes < 0:
