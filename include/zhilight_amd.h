@@ -712,6 +712,31 @@ int zl_decode_attn_ex(const uint16_t* q, const int32_t* buf_lens, const uint16_t
  * 1 = an int8 mask alone, 2 = a mask together with valid_lens.  Shapes the launcher refuses give 0. */
 int zl_decode_attn_kernel(int64_t len_q, int64_t h, int64_t hkv, int64_t d, int masked, int algo);
 
+/* Sliding-window decode attention with attention sinks at head size 64 (gpt-oss's attention; decode_attn_d64.hip).  The reference
+ * has no counterpart: its decode attention sees the whole prefix and has no sink.  zl_decode_attn_ex(mask = NULL, d = 64) with two
+ * additions that can be used separately or together.  With elen = min(buf_lens[b], valid_lens[b]) and lo = max(0, elen - window)
+ * (window == 0: no window, lo = 0) every query row of task b sees the keys lo <= j < elen -- HF's `sliding_window`: the newest key
+ * counts among the `window` -- and with sinks (H) fp32 != NULL, one logit per query head in score units (not multiplied by scale),
+ *   m = max(max_j s_j, sinks[h]),  out[b,q,h,:] = sum_j p_j V_j / (sum_j p_j + exp(sinks[h] - m) + 1e-20),  p_j = rn_T(exp(s_j - m)):
+ * the sink adds to the normaliser only, it has no value row and is not rounded to T.  Everything else is k_decode_attn_d64's: fp32
+ * scores, running maximum from -1e20, fp32 accumulation, one rounding to T, GQA head mapping, BSHD / BHSD buffers, fp16 / bf16, a
+ * zero row for a task without a visible key.  1 <= len_q * H / Hkv <= 16 rows per kv head, all on the matrix-core kernel; all rows
+ * of a task see the same key range.
+ * NEVER READ: keys outside [lo, elen) -- in front of the window as well as behind it; they may hold NaN.
+ * LAUNCHES: the splits are counted from lo: grid (ceil(min(window, max_len_buf) / split), Hkv, B) with split =
+ * zl_decode_attn_split_len(b, hkv, min(window, max_len_buf)) -- scalar arguments only (the launch can be captured), and no larger
+ * for a longer buffer.  A window of one split (gpt-oss: 128) is ONE launch: the workgroup takes the sink and stores `out` itself.
+ * Longer windows write fp32 split records and run the merge, which takes the sink.  window == 0 or >= max_len_buf: the grid, records
+ * and merge of zl_decode_attn_ex's D = 64 kernel (sinks == NULL too: its bits).  workspace: zl_decode_attn_workspace_bytes(b, len_q,
+ * h, 64, max_len_buf).  No allocation, no sync.  A caller's decode step is zl_rope_scatter_decode followed by this call; there is
+ * no fused form, no INT8-cache, shared-prefix or causal (speculative) form and no D = 128 form.
+ * ZL_EINVAL: a null operand (sinks may be null), a count <= 0, window < 0; ZL_ESHAPE: h % hkv, more than 16 rows per kv head;
+ * ZL_EDTYPE: not fp16 / bf16; ZL_ELIMIT: b or hkv > 65535, max_len_buf >= 2^31, more splits than the merge holds. */
+int zl_decode_attn_window(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs,
+                          const uint16_t* const* v_bufs, const int32_t* valid_lens, uint16_t* out, void* workspace,
+                          int64_t b, int64_t len_q, int64_t h, int64_t hkv, float scale, int64_t max_len_buf, int bshd, int dtype,
+                          int64_t window, const float* sinks /* (H) or NULL */, zl_stream_t s);
+
 /* Causal ("staircase") decode attention: the len_q rows of task b are the last token and len_q - 1 draft tokens of a speculative
  * step, row qi sees the keys j < min(buf_lens[b], valid_lens[b] + qi) -- what zl_decode_attn computes with the int8 mask
  * mask[b][qi, j] = j < valid_lens[b] + qi, on the matrix-core kernel and with ONE pass over the task's K / V for all of its rows
@@ -1047,6 +1072,25 @@ int zl_prefill_attn_d64_varlen(const uint16_t* q, const int32_t* cu_seqlens_q, c
                                const uint16_t* const* k_bufs, const uint16_t* const* v_bufs, uint16_t* out,
                                const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
                                float scale, int bshd, int dtype, zl_stream_t s);
+/* Sliding-window prompt attention with attention sinks at head size 64 (prefill_attn_d64.hip, a second instantiation of the kernel
+ * above; the plain entry points keep their kernel and bits).  The reference has no counterpart.  The row at position t = pos0 + r
+ * sees the keys max(0, t - window + 1) <= j <= t (window == 0: no window) -- what a zl_decode_attn_window step with valid_lens =
+ * t + 1 sees -- and with sinks (H) fp32 != NULL, m = max(max_j s_j, sinks[h]) and
+ *   out[r, h, :] = sum_j p_j V_j / (sum_j p_j + exp(sinks[h] - m) + 1e-20),  p_j = rn_T(exp(s_j - m)),
+ * the sink in score units (not multiplied by scale), in the normaliser only.  Everything else, the operands and the work table are
+ * zl_prefill_attn_d64's / _varlen's; the varlen launch equals the one-task launch per task bit for bit, and window >= pos0 + s_q
+ * with sinks == NULL gives the plain entry points' bits.
+ * NEVER READ: keys in front of the first key of a workgroup's (64-row tile's) first row's window, or behind its last row's position.
+ * A workgroup walks the 128-key tiles from that first key on, about window / 128 + 1 of them however long the prefix; 32-key
+ * groups outside a wave's rows' windows are skipped.  No allocation, no sync.  Statuses as the plain entry points, and ZL_EINVAL
+ * for window < 0. */
+int zl_prefill_attn_d64_window(const uint16_t* q, const uint16_t* k_buf, const uint16_t* v_buf, uint16_t* out, int64_t s_q,
+                               int64_t pos0, int64_t h, int64_t hkv, float scale, int64_t len_buf, int bshd, int dtype,
+                               int64_t window, const float* sinks /* (H) or NULL */, zl_stream_t s);
+int zl_prefill_attn_d64_varlen_window(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                                      const uint16_t* const* k_bufs, const uint16_t* const* v_bufs, uint16_t* out,
+                                      const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
+                                      float scale, int bshd, int dtype, int64_t window, const float* sinks, zl_stream_t s);
 
 
 /* ------------------------------------------------------------------------------------------------

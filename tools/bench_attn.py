@@ -90,8 +90,91 @@ def head64(a):
                 del kv, graphs
 
 
+def _alternate(fns, iters, reps):
+    """fns: callables that enqueue `reps` launches (graph replays, or eager loops); replays alternated, HIP events around each:
+    per route the median [p10, p90] us per launch"""
+    for f in fns:
+        f()
+    torch.cuda.synchronize()
+    samples = [[] for _ in fns]
+    for _ in range(iters):
+        for f, s in zip(fns, samples):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            s.append(e0.elapsed_time(e1) * 1e3 / reps)
+    cells = []
+    for s in samples:
+        s.sort()
+        cells.append(f"{s[len(s) // 2]:8.2f} [{s[len(s) // 10]:8.2f}, {s[len(s) * 9 // 10]:8.2f}]")
+    return cells
+
+
+def window64(a):
+    """--d 64 --window N [--sinks]: the sliding-window kernels.  Decode: zl_decode_attn_window over `seq` valid keys against the
+    only way the plain call bounds its work -- zl_decode_attn_ex with valid_lens = N on the same buffers, which computes something
+    else (the FIRST N keys) and is a cost reference only -- and against the plain call over all `seq` keys; one hipGraph of `layers`
+    launches over distinct buffers per route.  Prompt (--prompt-rows R): zl_prefill_attn_d64_window against zl_prefill_attn_d64 on the
+    same R rows, eager launches.  Median [p10, p90] us per launch (pair)."""
+    dev, d = torch.device("cuda:0"), 64
+    dt = torch.bfloat16 if a.bf16 else torch.float16
+    i32 = dict(dtype=torch.int32, device=dev)
+    scale = 1.0 / math.sqrt(d)
+    print(f"# head size 64, window {a.window}, sinks {a.sinks}, {'bf16' if a.bf16 else 'fp16'}, {'BHSD' if a.bhsd else 'BSHD'}, "
+          f"{a.layers} launches per replay, {a.iters} samples per route")
+    print("# decode: H Hkv keys batch | window | plain, valid_lens = window (cost reference) | plain, all keys      us per launch (pair): median [p10, p90]")
+    for h, hkv in [tuple(int(v) for v in s.split(",")) for s in a.shapes.split(";")]:
+        sinks = torch.randn(h, dtype=torch.float32, device=dev) if a.sinks else None
+        for seq in [int(v) for v in a.seqs.split(",")]:
+            for batch in [int(v) for v in a.batches.split(",")]:
+                len_buf = (seq + 64 + 63) // 64 * 64
+                shape = (a.layers, 2, hkv, len_buf, d) if a.bhsd else (a.layers, 2, len_buf, hkv, d)
+                kv = [torch.randn(shape, dtype=dt, device=dev) for _ in range(batch)]
+                k_addrs = torch.tensor([[t[l, 0].data_ptr() for t in kv] for l in range(a.layers)], dtype=torch.int64, device=dev)
+                v_addrs = torch.tensor([[t[l, 1].data_ptr() for t in kv] for l in range(a.layers)], dtype=torch.int64, device=dev)
+                buf_lens, valid, first = torch.full((batch,), len_buf, **i32), torch.full((batch,), seq, **i32), torch.full((batch,), a.window, **i32)
+                q, out = torch.randn(batch, 1, h, d, dtype=dt, device=dev), torch.empty(batch, 1, h, d, dtype=dt, device=dev)
+                ws = ops.decode_attn_workspace(batch, 1, h, d, len_buf, dev)
+                graphs = []
+                for kw in (dict(valid_lens=valid, window=a.window, sinks=sinks), dict(valid_lens=first), dict(valid_lens=valid)):
+                    def run():
+                        for l in range(a.layers):
+                            ops.multi_query_attention_rag_buffer(q, buf_lens, k_addrs[l], v_addrs[l], None, scale, len_buf, hkv,
+                                                                 bshd=not a.bhsd, out=out, workspace=ws, **kw)
+                    run()
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        run()
+                    graphs.append(g)
+                cells = _alternate([g.replay for g in graphs], a.iters, a.layers)
+                print(f"{h:3d} {hkv:3d} {seq:5d} {batch:3d} | " + " | ".join(cells), flush=True)
+                del kv, graphs
+    if a.prompt_rows:
+        print("# prompt: H Hkv rows | window | plain      us per launch: median [p10, p90]")
+        for h, hkv in [tuple(int(v) for v in s.split(",")) for s in a.shapes.split(";")]:
+            sinks = torch.randn(h, dtype=torch.float32, device=dev) if a.sinks else None
+            for rows in [int(v) for v in a.prompt_rows.split(",")]:
+                q = torch.randn(rows, h, d, dtype=dt, device=dev)
+                k, v = (torch.randn((hkv, rows, d) if a.bhsd else (rows, hkv, d), dtype=dt, device=dev) for _ in range(2))
+                out = torch.empty_like(q)
+                reps = 4
+                def win():
+                    for _ in range(reps):
+                        ops.prefill_attention(q, k, v, 0, hkv, scale, not a.bhsd, out=out, window=a.window, sinks=sinks)
+                def plain():
+                    for _ in range(reps):
+                        ops.prefill_attention(q, k, v, 0, hkv, scale, not a.bhsd, out=out)
+                print(f"{h:3d} {hkv:3d} {rows:5d} | " + " | ".join(_alternate([win, plain], a.iters, reps)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--window", type=int, default=0, help="--d 64: the sliding-window leg (window64) with this window")
+    ap.add_argument("--sinks", action="store_true", help="--d 64 --window N: with attention sinks")
+    ap.add_argument("--prompt-rows", default="", help="--d 64 --window N: also time windowed prompt attention over these row counts")
     ap.add_argument("--d", type=int, default=128, choices=(64, 128), help="64: the head-size-64 leg (head64), algo 0 against algo 1 in one process")
     ap.add_argument("--shapes", default="36,36;32,8;14,2;64,8", help="--d 64: H,Hkv pairs")
     ap.add_argument("--seqs", default="1024,4096", help="--d 64: visible keys")
@@ -107,7 +190,7 @@ def main():
     ap.add_argument("--q8", action="store_true", help="INT8 KV cache: rope+quantise+scatter launch, then attention over codes")
     a = ap.parse_args()
     if a.d == 64:
-        return head64(a)
+        return window64(a) if a.window or a.sinks else head64(a)
     dev = torch.device("cuda:0")
     h, hkv, d = 32, 8, 128
     len_buf = (a.seq + 64 + 63) // 64 * 64

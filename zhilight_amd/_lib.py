@@ -44,6 +44,7 @@ SYMBOLS = [
     "zl_quant_calc_scale_zp", "zl_dequant_group", "zl_quant_copy_to_rag_buffer", "zl_rope_quant_scatter_decode", "zl_decode_attn_quant", "zl_decode_attn_quant_ex",
     "zl_prefill_attn", "zl_prefill_attn_ex", "zl_prefill_attn_varlen", "zl_prefill_attn_varlen_q8", "zl_prefill_attn_varlen_hist",
     "zl_prefill_attn_d64", "zl_prefill_attn_d64_varlen",
+    "zl_decode_attn_window", "zl_prefill_attn_d64_window", "zl_prefill_attn_d64_varlen_window",
     "zl_element_add_scale", "zl_gate_mul", "zl_gate_fuse", "zl_dense_m_bytes", "zl_dense_pack_m", "zl_gemm_nt_packed", "zl_row_ss", "zl_w4a16_emits_row_ss", "zl_w4a16_takes_row_ss", "zl_permute_input", "zl_embedding",
     "zl_w8m_bytes", "zl_w8m_pack", "zl_w8a8_gemm_phase", "zl_w8a8_gemm_phase_ex", "zl_w8a8_qkv_rope_scatter",
     "zl_quant_calc_scale", "zl_rmsnorm_quant", "zl_int8_gemm_nt", "zl_quant_scale_back",

@@ -75,6 +75,10 @@ struct AttnParams {
     const uint16_t* const* prefix_k = nullptr;
     const uint16_t* const* prefix_v = nullptr;
     int g = 0, sh_split_len = 0, sh_splits = 0, own_splits = 0, sh_tiles = 0, sh_grid = 0;
+    // window / sink form at head size 64 (zl_decode_attn_window; k_decode_attn_combine<DT, 64, true>): window > 0 -> the records
+    // are those of the splits counted from max(0, elen - window); sinks (h) fp32 or null -> one logit per head in the normaliser
+    int window = 0;
+    const float* sinks = nullptr;
 };
 
 // P_b of the two-segment form: min(prefix_lens[g], prefix_caps[g], valid_lens[b], buf_lens[b]) for g = prefix_of[b] in [0, G), else 0;
@@ -1457,7 +1461,9 @@ __global__ __launch_bounds__(256, 3) void k_decode_attn_mfma_q8(const AttnParams
 
 // grid (B*len_q*H), block D.  Split statistics go through LDS once; the per-d accumulation then issues
 // independent loads back to back (the first version walked the splits with dependent loads: 6 us).
-template <int DT, int D>
+// WS (window / sinks): the splits are counted over the window's keys, and the head's sink logit s_h joins the maximum and adds
+// exp(s_h - max) to the normaliser.  WS = false is the kernel every other route launches, untouched.
+template <int DT, int D, bool WS = false>
 __global__ void k_decode_attn_combine(const AttnParams p) {
     constexpr int kMaxS = 512;
     __shared__ float sf[kMaxS];
@@ -1467,7 +1473,12 @@ __global__ void k_decode_attn_combine(const AttnParams p) {
     const int len = p.buf_lens[b];
     // causal form: row qi's splits end at its own limit valid + qi (the splits beyond hold no record of it, or an empty one)
     const int vlen_in = p.valid_lens ? p.valid_lens[b] + (p.causal ? (vh / p.h) % p.len_q : 0) : 0x7fffffff;
-    const int elen = p.mask ? len : min(len, vlen_in);
+    int elen = p.mask ? len : min(len, vlen_in);
+    float sink = -INFINITY;
+    if constexpr (WS) {
+        if (p.window > 0) elen = max(0, min(elen, p.window));      // elen - lo
+        if (p.sinks) sink = p.sinks[vh % p.h];
+    }
     const int ns = min((elen + p.split_len - 1) / p.split_len, kMaxS);
     const int d = threadIdx.x;
     const float* src = p.ws + (size_t)vh * p.max_splits * (D + 2);
@@ -1484,6 +1495,7 @@ __global__ void k_decode_attn_combine(const AttnParams p) {
         __syncthreads();
         float mn = -1e20f;
         for (int s = 0; s < ns; ++s) mn = fmaxf(mn, sf[s]);
+        if constexpr (WS) mn = fmaxf(mn, sink);
         float a = 0.f, z = 0.f;
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
@@ -1493,6 +1505,7 @@ __global__ void k_decode_attn_combine(const AttnParams p) {
                 z = __builtin_fmaf(sf[64 + u], f, z);
             }
         }
+        if constexpr (WS) z += __expf(sink - mn);
         p.out[(size_t)vh * D + d] = ZT<DT>::from_f32(a / (z + 1e-20f));
         return;
     }
@@ -1502,14 +1515,16 @@ __global__ void k_decode_attn_combine(const AttnParams p) {
         sf[s] = ms;
         mloc = fmaxf(mloc, ms);
     }
-    const float mn = zl_block_max(mloc, red);
+    float mn = zl_block_max(mloc, red);
+    if constexpr (WS) mn = fmaxf(mn, sink);
     float zloc = 0.f;
     for (int s = d; s < ns; s += D) {
         const float f = __expf(sf[s] - mn);
         sf[s] = f;
         zloc = __builtin_fmaf(src[(size_t)s * (D + 2) + D + 1], f, zloc);
     }
-    const float z = zl_block_sum(zloc, red);  // also orders the sf[] writes before the reads below
+    float z = zl_block_sum(zloc, red);  // also orders the sf[] writes before the reads below
+    if constexpr (WS) z += __expf(sink - mn);
     float a = 0.f;
     int s = 0;
     for (; s + 4 <= ns; s += 4) {
@@ -1671,10 +1686,10 @@ int launch_mfma(const AttnParams& p, int dtype, hipStream_t st, int waves = NW) 
 }
 
 // the merge of fp32 split records as a launch of its own
-template <int D>
+template <int D, bool WS = false>
 int launch_combine(const AttnParams& p, int dtype, hipStream_t st) {
     return by_dtype(dtype, [&](auto dt) {
-        hipLaunchKernelGGL((k_decode_attn_combine<decltype(dt)::value, D>), dim3((unsigned)((int64_t)p.b * p.len_q * p.h)), dim3(D), 0, st, p);
+        hipLaunchKernelGGL((k_decode_attn_combine<decltype(dt)::value, D, WS>), dim3((unsigned)((int64_t)p.b * p.len_q * p.h)), dim3(D), 0, st, p);
         return zl_launch_status();
     });
 }
@@ -1749,8 +1764,10 @@ int launch_d64(const AttnParams& p, int dtype, hipStream_t st) {
     g.max_splits = p.max_splits; g.bshd = p.bshd; g.scale = p.scale;
     g.qkv = p.qkv; g.cosv = p.cosv; g.sinv = p.sinv; g.placement = p.placement; g.k_bufs_w = p.k_bufs_w; g.v_bufs_w = p.v_bufs_w;
     g.neox = p.neox;
+    g.window = p.window; g.sinks = p.sinks; g.out = p.out;
     ZL_ATTN_TRY(zl_decode_attn_d64_launch(g, dtype, st));
-    return launch_combine<64>(p, dtype, st);
+    if (p.window > 0 && p.max_splits == 1) return ZL_OK;          // the one-workgroup window wrote `out` itself
+    return p.window > 0 || p.sinks ? launch_combine<64, true>(p, dtype, st) : launch_combine<64>(p, dtype, st);
 }
 
 // zl_decode_attn_splits / _splits_h / _splits_h_mask: one query row per task on the matrix-core kernel, records only, no merge
@@ -1816,6 +1833,24 @@ int zl_decode_attn_ex(const uint16_t* q, const int32_t* buf_lens, const uint16_t
         return launch_combine<kMD>(p, dtype, hs);
     }
     return launch_valu<false>(p, d, dtype, hs);
+}
+
+int zl_decode_attn_window(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs, const uint16_t* const* v_bufs,
+                          const int32_t* valid_lens, uint16_t* out, void* workspace, int64_t b, int64_t len_q, int64_t h, int64_t hkv,
+                          float scale, int64_t max_len_buf, int bshd, int dtype, int64_t window, const float* sinks, zl_stream_t s) {
+    ZL_ATTN_TRY(attn_check_args(q && buf_lens && k_bufs && v_bufs && valid_lens && out && workspace && window >= 0, b, len_q, h, hkv,
+                                64, max_len_buf));
+    ZL_CHECK_ARG(len_q * (h / hkv) <= 16, ZL_ESHAPE);
+    ZL_CHECK_ARG(attn_dtype_ok(dtype), ZL_EDTYPE);
+    ZL_CHECK_ARG(b <= 65535 && hkv <= 65535 && max_len_buf < ((int64_t)1 << 31), ZL_ELIMIT);
+    AttnParams p;
+    p.q = q; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs; p.valid_lens = valid_lens;
+    p.out = out; p.ws = (float*)workspace; p.scale = scale; p.bshd = bshd; p.passes = 1; p.sinks = sinks;
+    // a window that no buffer exceeds hides nothing (lo = 0 for every task): the plain grid, whose records are the same
+    p.window = window < max_len_buf ? (int)window : 0;
+    // the window's splits, not the buffer's: min(window, max_len_buf) keys from each task's own first visible key
+    ZL_ATTN_TRY(attn_geometry(p, b, len_q, h, hkv, p.window ? p.window : max_len_buf));
+    return launch_d64(p, dtype, (hipStream_t)s);
 }
 
 int zl_decode_attn_causal(const uint16_t* q, const int32_t* buf_lens, const uint16_t* const* k_bufs, const uint16_t* const* v_bufs,

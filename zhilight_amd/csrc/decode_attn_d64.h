@@ -22,7 +22,14 @@ struct DecodeD64Params {
     uint16_t* const* k_bufs_w = nullptr;      // writable views of k_bufs / v_bufs
     uint16_t* const* v_bufs_w = nullptr;
     int neox = 1;
+    // window form (window > 0; plain form only, zl_decode_attn_window): the rows of task b see the keys [max(0, elen - window), elen),
+    // elen = min(buf_lens[b], valid_lens[b]); split s starts s * split_len keys behind the window's first key and max_splits counts
+    // the window's splits.  max_splits == 1: the workgroup writes `out` (T, (b, len_q, h, 64)) itself, with sinks (h) fp32 or null
+    int window = 0;
+    const float* sinks = nullptr;
+    uint16_t* out = nullptr;
 };
 
-// the partial launch alone: grid (max_splits, hkv, b), 256 threads; the caller follows it with the merge
+// the partial launch alone: grid (max_splits, hkv, b), 256 threads; the caller follows it with the merge -- except in the window form
+// with max_splits == 1, which leaves the finished rows in `out`
 int zl_decode_attn_d64_launch(const DecodeD64Params& p, int dtype, hipStream_t st);

@@ -1,5 +1,5 @@
 // decode_attn_d64.hip -- prefix-visibility decode attention for head size 64 on the matrix cores (k_decode_attn_d64; reached through
-// zl_decode_attn_ex and zl_decode_attn_fused, attention.hip).
+// zl_decode_attn_ex, zl_decode_attn_fused and, with a sliding window and sinks, zl_decode_attn_window, attention.hip).
 //
 // The arithmetic is zl_decode_attn's: out[b,q,h,:] = softmax_{j < min(buf_lens[b], valid_lens[b])}(scale * q.K_j) . V, scores in fp32, the
 // running maximum starting at -1e20, probabilities rounded to T for the P.V product (the normaliser sums what the product uses), fp32
@@ -43,6 +43,21 @@
 // clamped reads may race its own store: they are the ones zeroed).  A task without a visible key leaves no record and the merge
 // writes a zero row.  MFMA columns, softmax state and records are per query row: a row's bits do not depend on the other rows of its
 // tile.  Table values only clip: valid_lens <= 0 ends the workgroup, placement outside [0, len) stores nothing.
+//
+// Window / sink variant (WIN != 0, zl_decode_attn_window; plain form only).  With elen = min(buf_lens, valid_lens) a task's rows see
+// the keys lo <= j < elen, lo = max(0, elen - window), and an optional per-head sink logit joins the normaliser (no value row):
+//   work split   RELATIVE to lo: workgroup (s, kv head, task) walks [lo + s * split_len, min(elen, lo + (s + 1) * split_len)), so the
+//                grid is ceil(min(window, max_len_buf) / split_len) splits whatever the buffer's length -- scalar arguments only, the
+//                launch can be captured.  A chunk starts at any key (a row is 128 bytes, every piece stays 16-byte aligned); the loads
+//                start at lo, clamp at the split's last visible key as above, and nothing in front of lo is ever addressed.
+//   WIN == 2     the window fits ONE split (gpt-oss: 128 keys): after the four-wave merge the workgroup takes the sink into the
+//                normaliser, divides, rounds to T and stores the `out` rows itself -- no records, no merge launch.  A task without a
+//                visible key gets its zero rows here.  Without a sink the bits are those of the record + merge pair (one split's
+//                factor is exp(0) = 1).
+//   WIN == 1     longer windows: the fp32 record goes to relative split index s; k_decode_attn_combine counts its splits from
+//                elen - lo and takes the sink.
+// Sinks without a window run the plain form (WIN == 0) and meet the sink in the merge.  Not covered: the fused form, the INT8
+// cache, the shared-prefix and causal launches, D = 128.
 #include "decode_attn_d64.h"
 
 namespace {
@@ -118,8 +133,9 @@ __device__ __forceinline__ void dd64_rope(uint4 (&x)[2], const float (&c)[2][8],
 
 // (FUSE: three workgroups per CU instead of the four that LDS allows -- the new row's 12 registers and the injection took the loop
 // past the plain form's 128-register budget and into scratch; its first V loads go out behind the rotation for the same reason)
-template <int DT, bool FUSE>
+template <int DT, bool FUSE, int WIN = 0>
 __global__ __launch_bounds__(64 * kWaves, FUSE ? 3 : 4) void k_decode_attn_d64(const DecodeD64Params p) {
+    static_assert(!(FUSE && WIN), "the window form has no fused front end");
     __shared__ __attribute__((aligned(16))) uint16_t vs[kWaves][kChunk * kVRow];     // 10 KB per wave; reused for the wave merge
 
     const int b = blockIdx.z, hk = blockIdx.y, split = blockIdx.x;
@@ -130,10 +146,19 @@ __global__ __launch_bounds__(64 * kWaves, FUSE ? 3 : 4) void k_decode_attn_d64(c
     const uint16_t* vbase = p.v_bufs[b];
     const int place = FUSE ? p.placement[b] : -1;
     const int elen = min(len, vlen);
-    const int t0 = split * p.split_len;
+    // WIN: the split counts from the window's first key
+    const int t0 = (WIN && elen > p.window ? elen - p.window : 0) + split * p.split_len;
     // FUSE: the workgroup whose split covers the new token's slot stores it even when nothing of the split is visible
     const bool owns_new = FUSE && place >= t0 && place < t0 + p.split_len && place < len;
-    if (len <= 0 || (t0 >= elen && !owns_new)) return;
+    if (len <= 0 || (t0 >= elen && !owns_new)) {
+        if constexpr (WIN == 2) {                         // no merge launch behind this one: the task's zero rows (workgroup-uniform)
+            for (int idx = threadIdx.x; idx < p.rows * kD; idx += 64 * kWaves) {
+                const int i = idx / kD, head = hk * p.n_rep + i % p.n_rep;
+                p.out[(((size_t)b * p.len_q + i / p.n_rep) * p.h + head) * kD + idx % kD] = 0;
+            }
+        }
+        return;
+    }
     const int t1 = min(elen, t0 + p.split_len);
     const int last_key = t1 > 0 ? t1 - 1 : 0;             // 0 <= last_key < len
 
@@ -322,6 +347,14 @@ __global__ __launch_bounds__(64 * kWaves, FUSE ? 3 : 4) void k_decode_attn_d64(c
             lt = __builtin_fmaf(src[w * WS + kD + 1], f, lt);
         }
         const int qi = i / p.n_rep, head = hk * p.n_rep + i % p.n_rep;
+        if constexpr (WIN == 2) {
+            // the only split: m = max(max_j s_j, sink), out = sum p V / (sum p + exp(sink - m) + 1e-20); no sink: f = 1, the pair's bits
+            const float sink = p.sinks ? p.sinks[head] : -INFINITY;
+            const float m2 = fmaxf(mn, sink);
+            const float f = __expf(mn - m2);
+            p.out[(((size_t)b * p.len_q + qi) * p.h + head) * kD + d] = ZT<DT>::from_f32(a * f / (lt * f + __expf(sink - m2) + 1e-20f));
+            continue;
+        }
         float* dst = p.ws + ((((size_t)b * p.len_q + qi) * p.h + head) * p.max_splits + split) * (kD + 2);
         dst[d] = a;
         if (d == 0) {
@@ -335,7 +368,16 @@ __global__ __launch_bounds__(64 * kWaves, FUSE ? 3 : 4) void k_decode_attn_d64(c
 
 int zl_decode_attn_d64_launch(const DecodeD64Params& p, int dtype, hipStream_t st) {
     const dim3 grid((unsigned)p.max_splits, (unsigned)p.hkv, (unsigned)p.b), block(64 * kWaves);
-    if (p.qkv) {
+    if (p.window > 0) {                                   // max_splits counts the window's splits; one split: the direct form
+        if (p.qkv) return ZL_EINVAL;
+        if (p.max_splits == 1) {
+            if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_d64<ZL_F16, false, 2>), grid, block, 0, st, p);
+            else hipLaunchKernelGGL((k_decode_attn_d64<ZL_BF16, false, 2>), grid, block, 0, st, p);
+        } else {
+            if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_d64<ZL_F16, false, 1>), grid, block, 0, st, p);
+            else hipLaunchKernelGGL((k_decode_attn_d64<ZL_BF16, false, 1>), grid, block, 0, st, p);
+        }
+    } else if (p.qkv) {
         if (dtype == ZL_F16) hipLaunchKernelGGL((k_decode_attn_d64<ZL_F16, true>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((k_decode_attn_d64<ZL_BF16, true>), grid, block, 0, st, p);
     } else {

@@ -26,6 +26,21 @@
 // A row's bits depend on its own query row and on the keys it sees only: tiles are cut at absolute key positions, the skipped groups
 // and the tiles a row sees nothing of add exact zeros, and keys behind a workgroup's last visible key are never loaded (their slots
 // hold a clamped K row and a zero V row), so neither len_buf nor the other tasks of a launch nor the entry point reach the result.
+//
+// Window / sink variant (WIN, zl_prefill_attn_d64_window / _varlen_window): the row at position t sees the keys
+// max(0, t - window + 1) <= j <= t, and an optional per-head sink logit joins the normaliser (no value row).
+//   tiles        the walk starts at the 128-key tile of the workgroup's first row's first key, k_lo = max(0, pos0 + q0 - window + 1),
+//                and so do the staged loads: a workgroup touches at most window + 63 keys (+ the tile's rounding) however long the
+//                prefix.  Slots of the first tile in front of k_lo are addressed at k_lo (a clamped K row, a zero V row), the mirror
+//                image of the slots behind the last visible key: nothing outside a workgroup's rows' windows is loaded.
+//   skip         a 32-key group wholly in front of the window of the wave's FIRST row is skipped, wave-uniformly, as a group
+//                beyond the wave's last row is.  The lower-bound select runs only in tiles that reach in front of the window of the
+//                wave's LAST row, as `diag` does for the upper edge.  A row whose window has not begun keeps the maximum -1e20, its
+//                probabilities are exp2(-inf) = 0 exactly.
+//   sink         once, in the normalise step: m = max(m_run, sink * log2 e), the factor exp2(m_run - m) on l and -- folded into the
+//                reciprocal that goes through the strip -- on O, and exp2(sink * log2 e - m) added to l.
+//   work map     the same tables and orders are accepted.  With a window every item walks about (window + 64) / 128 + 1 tiles, so
+//                longest-first and the paired map neither help nor hurt: any order balances.
 #include <stdlib.h>
 #include "zl_common.h"
 
@@ -54,6 +69,9 @@ struct Prefill64Params {
     const uint16_t* const* k_bufs;
     const uint16_t* const* v_bufs;
     int n_work, b, total_q;
+    // WIN: keys per row (0 < window <= 2^30; "no window" is 2^30) and the (h) fp32 sink logits or null
+    int window;
+    const float* sinks;
 };
 
 template <int DT>
@@ -74,7 +92,7 @@ __device__ __forceinline__ uint16_t pf64_round(float x) {      // a probability 
     }
 }
 
-template <int DT>
+template <int DT, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void k_prefill_attn_d64(const Prefill64Params p) {
     __shared__ __attribute__((aligned(16))) uint16_t ks[kBK * kKRow];
     __shared__ __attribute__((aligned(16))) uint16_t vt[kBK * kVRow];
@@ -139,6 +157,13 @@ __global__ __launch_bounds__(256, 2) void k_prefill_attn_d64(const Prefill64Para
     const int last_q = min(q0 + kBQ, s_q) - 1;
     const int n_keys = min(pos0 + last_q + 1, len_buf);   // keys any row of this workgroup may see, never past the buffer
     const int n_tiles = (n_keys + kBK - 1) / kBK;
+    // WIN: the workgroup's first visible key (addresses stay inside [k_lo, n_keys)), its tile, and the first keys of the windows of
+    // the wave's first and last row
+    const int k_lo = WIN ? min(max(pos0 + q0 - p.window + 1, 0), n_keys - 1) : 0;
+    const int tile0 = WIN ? max(pos0 + q0 - p.window + 1, 0) / kBK : 0;
+    const int wave_lo = WIN ? max(pos0 + q0 + wave * 16 - p.window + 1, 0) : 0;
+    const int wave_lo_last = WIN ? max(wave_last - p.window + 1, 0) : 0;
+    const int qlo = WIN ? qpos - p.window + 1 : 0;         // keys qlo .. qpos are visible to this lane's query
 
     // staging: thread -> 16-byte piece spc of the rows srow + 32 c.  Named registers: arrays filled from two places end up on the stack
     uint4 kr0, kr1, kr2, kr3, vr0, vr1, vr2, vr3;
@@ -146,23 +171,24 @@ __global__ __launch_bounds__(256, 2) void k_prefill_attn_d64(const Prefill64Para
 #define ZL_P64_LOAD1(c_, key0_)                                                                            \
     {                                                                                                      \
         const int kg_ = (key0_) + srow + 32 * c_;                                                          \
-        const size_t ro_ = kv_off + (size_t)(kg_ < n_keys ? kg_ : n_keys - 1) * kv_stride + spc;           \
+        const int kc_ = WIN && kg_ < k_lo ? k_lo : (kg_ < n_keys ? kg_ : n_keys - 1);                      \
+        const size_t ro_ = kv_off + (size_t)kc_ * kv_stride + spc;                                         \
         kr##c_ = *reinterpret_cast<const uint4*>(kb + ro_);                                                \
         vr##c_ = *reinterpret_cast<const uint4*>(vb + ro_);                                                \
-        if (kg_ >= n_keys) vr##c_ = make_uint4(0, 0, 0, 0);   /* finite: its probability is exactly 0 */   \
+        if (kg_ != kc_) vr##c_ = make_uint4(0, 0, 0, 0);      /* finite: its probability is exactly 0 */   \
     }
 #define ZL_P64_LOAD(tile_) ZL_P64_LOAD1(0, (tile_) * kBK) ZL_P64_LOAD1(1, (tile_) * kBK) ZL_P64_LOAD1(2, (tile_) * kBK) ZL_P64_LOAD1(3, (tile_) * kBK)
 #define ZL_P64_ST(c_)                                                                                      \
     *reinterpret_cast<uint4*>(&ks[(srow + 32 * c_) * kKRow + spc]) = kr##c_;                               \
     *reinterpret_cast<uint4*>(&vt[(srow + 32 * c_) * kVRow + spc]) = vr##c_;
-    ZL_P64_LOAD(0)
+    ZL_P64_LOAD(tile0)
 
     const float sl2 = p.scale * 1.44269504088896340736f;  // scores live in the log2 domain: v_exp_f32 is exp2
     typedef short s4 __attribute__((ext_vector_type(4)));
     typedef short s8 __attribute__((ext_vector_type(8)));
     const uint16_t* vtr = vt + (4 * kq + (nq >> 2)) * kVRow + 4 * (nq & 3);
 
-    for (int tile = 0; tile < n_tiles; ++tile) {
+    for (int tile = tile0; tile < n_tiles; ++tile) {
         const int key0 = tile * kBK;
         __syncthreads();                                  // the previous tile is consumed
         ZL_P64_ST(0) ZL_P64_ST(1) ZL_P64_ST(2) ZL_P64_ST(3)
@@ -172,11 +198,13 @@ __global__ __launch_bounds__(256, 2) void k_prefill_attn_d64(const Prefill64Para
         // ---- S^T = K . Q^T per 32-key group j (two 16-key blocks x two d steps); lane: query nq, keys key0 + 16 kb + 4 kq + i.
         //      A group beyond the wave's last row is skipped; the causal select runs only where the tile reaches the wave's diagonal
         const bool diag = key0 + kBK - 1 > pos0 + q0 + wave * 16;
+        const bool edge = WIN && key0 < wave_lo_last;     // some key of the tile lies in front of some row's window
         f4 st[8];
         float mloc = -INFINITY;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (key0 + 32 * j > wave_last) continue;      // wave-uniform
+            if (WIN && key0 + 32 * j + 31 < wave_lo) continue;
 #pragma unroll
             for (int kb2 = 2 * j; kb2 < 2 * j + 2; ++kb2) {
                 const uint16_t* kp = &ks[(kb2 * 16 + nq) * kKRow + 8 * kq];
@@ -186,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void k_prefill_attn_d64(const Prefill64Para
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int key = key0 + kb2 * 16 + 4 * kq + i;
-                    const float sv = (!diag || key <= qpos) ? acc[i] * sl2 : -INFINITY;
+                    const float sv = ((!diag || key <= qpos) && (!edge || key >= qlo)) ? acc[i] * sl2 : -INFINITY;
                     acc[i] = sv;
                     mloc = fmaxf(mloc, sv);
                 }
@@ -215,6 +243,7 @@ __global__ __launch_bounds__(256, 2) void k_prefill_attn_d64(const Prefill64Para
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (key0 + 32 * j > wave_last) continue;
+            if (WIN && key0 + 32 * j + 31 < wave_lo) continue;
             uint32_t w[4];
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
@@ -244,7 +273,16 @@ __global__ __launch_bounds__(256, 2) void k_prefill_attn_d64(const Prefill64Para
     // ---- normalise: l of query nq = the sum over its 4 lanes; 1 / l reaches the C layout through the strip
     l_run += __shfl_xor(l_run, 16, 64);
     l_run += __shfl_xor(l_run, 32, 64);
-    if (kq == 0) strip[wave][nq] = 1.0f / (l_run + 1e-20f);
+    float inv_l = 1.0f / (l_run + 1e-20f);
+    if constexpr (WIN) {
+        if (p.sinks) {
+            const float sk = p.sinks[head] * 1.44269504088896340736f;
+            const float m2 = fmaxf(m_run, sk);
+            const float f = __builtin_amdgcn_exp2f(m_run - m2);
+            inv_l = f / (l_run * f + __builtin_amdgcn_exp2f(sk - m2) + 1e-20f);
+        }
+    }
+    if (kq == 0) strip[wave][nq] = inv_l;
     __builtin_amdgcn_s_waitcnt(0xc07f);
     const f4 inv = *reinterpret_cast<const f4*>(&strip[wave][4 * kq]);
 #pragma unroll
@@ -265,17 +303,31 @@ int launch_prefill_d64(Prefill64Params& p, int64_t items, int dtype, hipStream_t
     int cus = zl_device_cu_count();
     if (cus <= 0) cus = 256;
     p.pair = (total % 2 == 0 && total <= 2 * cus) ? 1 : 0;
-    if (dtype == ZL_F16) hipLaunchKernelGGL(k_prefill_attn_d64<ZL_F16>, dim3((unsigned)total), dim3(256), 0, hs, p);
-    else hipLaunchKernelGGL(k_prefill_attn_d64<ZL_BF16>, dim3((unsigned)total), dim3(256), 0, hs, p);
+    if (p.window > 0) {
+        if (dtype == ZL_F16) hipLaunchKernelGGL((k_prefill_attn_d64<ZL_F16, true>), dim3((unsigned)total), dim3(256), 0, hs, p);
+        else hipLaunchKernelGGL((k_prefill_attn_d64<ZL_BF16, true>), dim3((unsigned)total), dim3(256), 0, hs, p);
+    } else {
+        if (dtype == ZL_F16) hipLaunchKernelGGL(k_prefill_attn_d64<ZL_F16>, dim3((unsigned)total), dim3(256), 0, hs, p);
+        else hipLaunchKernelGGL(k_prefill_attn_d64<ZL_BF16>, dim3((unsigned)total), dim3(256), 0, hs, p);
+    }
     return zl_launch_status();
+}
+
+// the window entry points' two arguments (window >= 0 checked) -> the kernel's: every row sees at most 2^30 keys
+void set_window(Prefill64Params& p, int64_t window, const float* sinks) {
+    constexpr int64_t kNone = (int64_t)1 << 30;
+    p.window = (int)(window == 0 || window > kNone ? kNone : window);
+    p.sinks = sinks;
 }
 
 }  // namespace
 
-extern "C" int zl_prefill_attn_d64(const uint16_t* q, const uint16_t* k_buf, const uint16_t* v_buf, uint16_t* out, int64_t s_q,
-                                   int64_t pos0, int64_t h, int64_t hkv, float scale, int64_t len_buf, int bshd, int dtype,
-                                   zl_stream_t s) {
+// the one-task launch; win: the WIN instantiation with `window` (>= 0, 0 = none) and `sinks` (or null)
+static int prefill_d64(const uint16_t* q, const uint16_t* k_buf, const uint16_t* v_buf, uint16_t* out, int64_t s_q, int64_t pos0,
+                       int64_t h, int64_t hkv, float scale, int64_t len_buf, int bshd, int dtype, bool win, int64_t window,
+                       const float* sinks, zl_stream_t s) {
     ZL_CHECK_ARG(q && k_buf && v_buf && out && s_q > 0 && pos0 >= 0 && h > 0 && hkv > 0 && len_buf > 0, ZL_EINVAL);
+    ZL_CHECK_ARG(!win || window >= 0, ZL_EINVAL);
     ZL_CHECK_ARG(h % hkv == 0 && pos0 + s_q <= len_buf, ZL_ESHAPE);
     ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
     ZL_CHECK_ARG(h <= 65535 && len_buf < ((int64_t)1 << 31), ZL_ELIMIT);
@@ -284,15 +336,16 @@ extern "C" int zl_prefill_attn_d64(const uint16_t* q, const uint16_t* k_buf, con
     p.s_q = (int)s_q; p.pos0 = (int)pos0; p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv);
     p.len_buf = (int)len_buf; p.bshd = bshd; p.scale = scale;
     p.nx = (int)((s_q + kBQ - 1) / kBQ);
+    if (win) set_window(p, window, sinks);
     return launch_prefill_d64(p, p.nx, dtype, (hipStream_t)s);
 }
 
-extern "C" int zl_prefill_attn_d64_varlen(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
-                                          const uint16_t* const* k_bufs, const uint16_t* const* v_bufs, uint16_t* out,
-                                          const int32_t* work, int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv,
-                                          float scale, int bshd, int dtype, zl_stream_t s) {
+static int prefill_d64_varlen(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                              const uint16_t* const* k_bufs, const uint16_t* const* v_bufs, uint16_t* out, const int32_t* work,
+                              int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv, float scale, int bshd, int dtype,
+                              bool win, int64_t window, const float* sinks, zl_stream_t s) {
     ZL_CHECK_ARG(q && cu_seqlens_q && pos0 && buf_lens && k_bufs && v_bufs && out && work, ZL_EINVAL);
-    ZL_CHECK_ARG(b > 0 && total_q > 0 && n_work > 0 && h > 0 && hkv > 0, ZL_EINVAL);
+    ZL_CHECK_ARG(b > 0 && total_q > 0 && n_work > 0 && h > 0 && hkv > 0 && (!win || window >= 0), ZL_EINVAL);
     ZL_CHECK_ARG(h % hkv == 0, ZL_ESHAPE);
     ZL_CHECK_ARG(dtype == ZL_F16 || dtype == ZL_BF16, ZL_EDTYPE);
     ZL_CHECK_ARG(h <= 65535 && b < ((int64_t)1 << 30) && total_q < ((int64_t)1 << 31) && n_work < ((int64_t)1 << 31), ZL_ELIMIT);
@@ -301,5 +354,37 @@ extern "C" int zl_prefill_attn_d64_varlen(const uint16_t* q, const int32_t* cu_s
     p.h = (int)h; p.hkv = (int)hkv; p.n_rep = (int)(h / hkv); p.bshd = bshd; p.scale = scale;
     p.work = work; p.cu_q = cu_seqlens_q; p.pos0s = pos0; p.buf_lens = buf_lens; p.k_bufs = k_bufs; p.v_bufs = v_bufs;
     p.n_work = (int)n_work; p.b = (int)b; p.total_q = (int)total_q;
+    if (win) set_window(p, window, sinks);
     return launch_prefill_d64(p, n_work, dtype, (hipStream_t)s);
 }
+
+extern "C" {
+
+int zl_prefill_attn_d64(const uint16_t* q, const uint16_t* k_buf, const uint16_t* v_buf, uint16_t* out, int64_t s_q, int64_t pos0,
+                        int64_t h, int64_t hkv, float scale, int64_t len_buf, int bshd, int dtype, zl_stream_t s) {
+    return prefill_d64(q, k_buf, v_buf, out, s_q, pos0, h, hkv, scale, len_buf, bshd, dtype, false, 0, nullptr, s);
+}
+
+int zl_prefill_attn_d64_window(const uint16_t* q, const uint16_t* k_buf, const uint16_t* v_buf, uint16_t* out, int64_t s_q, int64_t pos0,
+                               int64_t h, int64_t hkv, float scale, int64_t len_buf, int bshd, int dtype, int64_t window,
+                               const float* sinks, zl_stream_t s) {
+    return prefill_d64(q, k_buf, v_buf, out, s_q, pos0, h, hkv, scale, len_buf, bshd, dtype, true, window, sinks, s);
+}
+
+int zl_prefill_attn_d64_varlen(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                               const uint16_t* const* k_bufs, const uint16_t* const* v_bufs, uint16_t* out, const int32_t* work,
+                               int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv, float scale, int bshd, int dtype,
+                               zl_stream_t s) {
+    return prefill_d64_varlen(q, cu_seqlens_q, pos0, buf_lens, k_bufs, v_bufs, out, work, n_work, b, total_q, h, hkv, scale, bshd,
+                              dtype, false, 0, nullptr, s);
+}
+
+int zl_prefill_attn_d64_varlen_window(const uint16_t* q, const int32_t* cu_seqlens_q, const int32_t* pos0, const int32_t* buf_lens,
+                                      const uint16_t* const* k_bufs, const uint16_t* const* v_bufs, uint16_t* out, const int32_t* work,
+                                      int64_t n_work, int64_t b, int64_t total_q, int64_t h, int64_t hkv, float scale, int bshd,
+                                      int dtype, int64_t window, const float* sinks, zl_stream_t s) {
+    return prefill_d64_varlen(q, cu_seqlens_q, pos0, buf_lens, k_bufs, v_bufs, out, work, n_work, b, total_q, h, hkv, scale, bshd,
+                              dtype, true, window, sinks, s);
+}
+
+}  // extern "C"

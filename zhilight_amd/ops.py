@@ -2196,16 +2196,43 @@ def decode_attn_workspace(b, len_q, h, d, max_len_buf, device):
     return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
 
 
+def _window_args(what, d, h, device, window, sinks, mask=None, groups=None):
+    """the checks of the window / sink forms (zl_decode_attn_window, zl_prefill_attn_d64[_varlen]_window), in `what`'s name: head
+    size 64, no mask, no wave groups, window >= 0, sinks None or an fp32 (H) tensor on `device`"""
+    if d != 64:
+        raise ZLError(f"{what}: window / sinks at head size {d}: the sliding-window kernels cover head size 64")
+    if mask is not None:
+        raise ZLError(f"{what}: window / sinks with a mask: the sliding-window kernels take valid lengths only")
+    if groups not in (None, 0, 1):
+        raise ZLError(f"{what}: window / sinks with groups={groups}: the head-size-64 kernel has no wave groups")
+    if int(window) < 0:
+        raise ZLError(f"{what}: window {window} < 0")
+    if sinks is not None and not (torch.is_tensor(sinks) and sinks.dtype == torch.float32 and tuple(sinks.shape) == (h,)
+                                  and sinks.device == device and sinks.is_contiguous()):
+        raise ZLError(f"{what}: sinks: a contiguous fp32 tensor of shape ({h},) on q's device")
+
+
 def multi_query_attention_rag_buffer(batch_q, buf_lens, key_buf_addrs, val_buf_addrs, mask, scale, max_len_buf,
-                                     num_kv_heads, valid_lens=None, bshd=True, out=None, workspace=None):
+                                     num_kv_heads, valid_lens=None, bshd=True, out=None, workspace=None, window=0, sinks=None):
     """nn::multi_query_attention_rag_buffer / attention_qkv_rag_buffer
-    (src/nn/attention/attention_kernel.cu:1252-1457, 1150-1213).  batch_q (B, len_q, H, D)."""
-    _chk_cuda(batch_q, buf_lens, key_buf_addrs, val_buf_addrs, mask, valid_lens)
+    (src/nn/attention/attention_kernel.cu:1252-1457, 1150-1213).  batch_q (B, len_q, H, D).
+    window > 0 / sinks (H) fp32 (no reference counterpart; D = 64, valid_lens, no mask): zl_decode_attn_window -- a task's rows see
+    its last `window` visible keys, and sinks[h] joins head h's softmax normaliser."""
     b, len_q, h, d = batch_q.shape
+    windowed = window != 0 or sinks is not None
+    if windowed:
+        _window_args("multi_query_attention_rag_buffer", d, h, batch_q.device, window, sinks, mask)
+    _chk_cuda(batch_q, buf_lens, key_buf_addrs, val_buf_addrs, mask, valid_lens)
     if out is None:
         out = torch.empty_like(batch_q)
     if workspace is None:
         workspace = decode_attn_workspace(b, len_q, h, d, max_len_buf, batch_q.device)
+    if windowed:
+        check(lib().zl_decode_attn_window(_p(batch_q), _p(buf_lens), _p(key_buf_addrs), _p(val_buf_addrs), _p(valid_lens), _p(out),
+                                          _p(workspace), _i(b), _i(len_q), _i(h), _i(num_kv_heads), _f(scale), _i(max_len_buf),
+                                          C.c_int(int(bshd)), C.c_int(_dt(batch_q)), _i(window), _p(sinks), _stream()),
+              "decode_attn_window")
+        return out
     check(lib().zl_decode_attn_ex(_p(batch_q), _p(buf_lens), _p(key_buf_addrs), _p(val_buf_addrs), _p(mask),
                                _p(valid_lens), _p(out), _p(workspace), _i(b), _i(len_q), _i(h), _i(num_kv_heads),
                                _i(d), _f(scale), _i(max_len_buf), C.c_int(int(bshd)), C.c_int(_dt(batch_q)),
@@ -2591,18 +2618,28 @@ def multi_query_attention_rag_buffer_quant(batch_q, buf_lens, key_buf_addrs, val
     return out
 
 
-def prefill_attention(q, k_buf, v_buf, pos0, num_kv_heads, scale, bshd=True, out=None, groups=None):
+def prefill_attention(q, k_buf, v_buf, pos0, num_kv_heads, scale, bshd=True, out=None, groups=None, window=0, sinks=None):
     """Causal attention of one task's prompt chunk (attn_encode_group -> flash attention in the reference,
     src/nn/attention/attention.cpp:442-622).  q (s_q, H, D); k_buf / v_buf the task's buffers (len_buf, Hkv, D)
     [bshd] or (Hkv, len_buf, D), already holding the chunk's rows at pos0 .. pos0 + s_q - 1.  D = 128 (zl_prefill_attn_ex) or
-    64 (zl_prefill_attn_d64: a kernel without wave groups, `groups` None / 0 / 1 only)."""
+    64 (zl_prefill_attn_d64: a kernel without wave groups, `groups` None / 0 / 1 only).
+    window > 0 / sinks (H) fp32 (D = 64; zl_prefill_attn_d64_window): the row at position t sees the keys t - window + 1 .. t, and
+    sinks[h] joins head h's softmax normaliser."""
+    s_q, h, d = q.shape
+    windowed = window != 0 or sinks is not None
+    if windowed:
+        _window_args("prefill_attention", d, h, q.device, window, sinks, groups=groups)
     _chk_cuda(q, k_buf, v_buf)
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise ZLError("prefill_attention: fp16 / bf16 only")
-    s_q, h, d = q.shape
     len_buf = k_buf.shape[0] if bshd else k_buf.shape[1]
     if out is None:
         out = torch.empty_like(q)
+    if windowed:
+        check(lib().zl_prefill_attn_d64_window(_p(q), _p(k_buf), _p(v_buf), _p(out), _i(s_q), _i(pos0), _i(h), _i(num_kv_heads),
+                                               _f(scale), _i(len_buf), C.c_int(int(bshd)), C.c_int(_dt(q)), _i(window), _p(sinks),
+                                               _stream()), "prefill_attn_d64_window")
+        return out
     if d == 64:
         _no_groups_d64("prefill_attention", groups)
         check(lib().zl_prefill_attn_d64(_p(q), _p(k_buf), _p(v_buf), _p(out), _i(s_q), _i(pos0), _i(h), _i(num_kv_heads), _f(scale),
@@ -2692,15 +2729,19 @@ def _varlen_args(what, q, lens, pos0, buf_lens, plan, out, groups):
 
 
 def prefill_attention_varlen(q, lens, pos0, k_addrs, v_addrs, buf_lens, num_kv_heads, scale, bshd=True, out=None, groups=None,
-                             plan=None):
+                             plan=None, window=0, sinks=None):
     """Causal attention of B tasks' prompt chunks in one launch (attn_encode_group's per-task flash-attention loop,
     src/nn/attention/attention.cpp:442-562, as one varlen call).  q (total_q, H, D): task i's rows back to back, lens[i] of them, at
     positions pos0[i] ..; k_addrs / v_addrs device int64 tables of the tasks' K/V buffers (buf_lens[i] rows each, BSHD or BHSD),
     which already hold the chunks' own rows.  lens / pos0 / buf_lens are host ints (checked here); `plan` (prefill_varlen_plan of
     the same lists) spares the upload when several layers share it.  Per task bit-identical to prefill_attention(.., groups).
-    D = 128 or 64 (zl_prefill_attn_d64_varlen; `groups` as for prefill_attention)."""
-    _chk_cuda(q, k_addrs, v_addrs)
+    D = 128 or 64 (zl_prefill_attn_d64_varlen; `groups` as for prefill_attention).  window / sinks as for prefill_attention
+    (zl_prefill_attn_d64_varlen_window)."""
     total_q, h, d = q.shape
+    windowed = window != 0 or sinks is not None
+    if windowed:
+        _window_args("prefill_attention_varlen", d, h, q.device, window, sinks, groups=groups)
+    _chk_cuda(q, k_addrs, v_addrs)
     if d not in (64, 128):
         raise ZLError(f"prefill_attention_varlen: head size {d}: the prompt-attention kernels cover 64 and 128")
     if d == 64:
@@ -2709,6 +2750,13 @@ def prefill_attention_varlen(q, lens, pos0, k_addrs, v_addrs, buf_lens, num_kv_h
     for t in (k_addrs, v_addrs):
         if t.dtype != torch.int64 or t.numel() != plan.b:
             raise ZLError("prefill_attention_varlen: one int64 K / V pointer per task")
+    if windowed:
+        check(lib().zl_prefill_attn_d64_varlen_window(_p(q), _p(plan.cu_seqlens_q), _p(plan.pos0_dev), _p(plan.buf_lens_dev),
+                                                      _p(k_addrs), _p(v_addrs), _p(out), _p(plan.work), _i(plan.n_work), _i(plan.b),
+                                                      _i(total_q), _i(h), _i(num_kv_heads), _f(scale), C.c_int(int(bshd)),
+                                                      C.c_int(_dt(q)), _i(window), _p(sinks), _stream()),
+              "prefill_attn_d64_varlen_window")
+        return out
     if d == 64:
         check(lib().zl_prefill_attn_d64_varlen(_p(q), _p(plan.cu_seqlens_q), _p(plan.pos0_dev), _p(plan.buf_lens_dev), _p(k_addrs),
                                                _p(v_addrs), _p(out), _p(plan.work), _i(plan.n_work), _i(plan.b), _i(total_q), _i(h),
